@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X-native dycore.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs if --dump-outputs is given and prints the result line:
+metric, value, unit, higher_is_better, dtype, ms_per_step and the run's config.  Everything else below (live counters, roofline,
+calibration, per-kernel times, power, micro section, multi-GPU diagnostics, cpu_baseline) runs only with --full; the --no-* options
+switch parts of it off.
+--dump-outputs DIR: right after the timed region, the fields the timed path leaves in the coupler (density_dry, uvel, vvel, wvel, temp
+          and the tracers) as DIR/<name>.npy, float64: the same fixed, seeded sample of 2^19 cells per field (all cells of a smaller
+          block; with N > 1, 2^19 / N cells of every rank's block, rank after rank), 4 MiB per field.
 
 metric  : cell-updates/s (whole job) of Dynamics_Euler_Stratified_WenoFV::time_step on the supercell grid.
           One cell-update = one (k,j,i,iens) cell advanced through one dycore sub-cycle (3 SSPRK stages, all
@@ -60,6 +68,10 @@ def parse():
     ap.add_argument("--ny", type=int, default=400, help="local block, y")
     ap.add_argument("--nz", type=int, default=100)
     ap.add_argument("--nens", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: live counters, roofline, calibration, per-kernel "
+                    "times, power, the micro section, multi-GPU diagnostics and the CPU baseline (the --no-* options switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the fields of the last timed step as DIR/<name>.npy "
+                    "(a fixed, seeded sample of 2^19 cells per field, float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--full-loop", action="store_true", help="time the whole supercell_example step (dycore, Kessler, sponge, nudger) "
                     "instead of the dycore alone (SURVEY 8(d): report both); not the headline metric")
@@ -90,6 +102,8 @@ def parse():
                     help="wall-clock limit of a run: a rank that has not finished by then prints where it is and exits non-zero "
                          "(a first contact between GPUs over RCCL must fail fast, not hang the caller's lease)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
     if a.workload == "config3":
         a.full_loop = True
     if a.workload == "config4":
@@ -637,6 +651,33 @@ def micro_section(torch, modules, coupler, dycore, micro, dt, a):
     return res
 
 
+DUMP_CELLS = 1 << 19                                             # cells sampled per field (all ranks together)
+DUMP_SEED = 20241016
+
+
+def dump_outputs(torch, dist, coupler, world, rank, out_dir):
+    """--dump-outputs: the fields the timed path leaves in the coupler, sampled at the same flat cell indices of every field (drawn
+    from a fixed seed, so the sample depends only on the block's shape and the number of ranks), gathered to rank 0, one float64
+    .npy per field.  Called by every rank (a collective with N > 1)."""
+    import numpy as np
+    dm = coupler.get_data_manager_readonly()
+    names = ["density_dry", "uvel", "vvel", "wvel", "temp"] + list(coupler.get_tracer_names())
+    numel = dm.get(names[0], True).numel()
+    n = min(numel, max(1, DUMP_CELLS // world))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(numel, size=n, replace=False)) if n < numel else np.arange(numel)
+    idx = torch.from_numpy(idx).to(dm.get(names[0], True).device)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+    for name in names:
+        s = dm.get(name, True).reshape(-1).index_select(0, idx).to(torch.float64).contiguous()
+        if world > 1:
+            parts = [torch.empty_like(s) for _ in range(world)]
+            dist.all_gather(parts, s)
+            s = torch.cat(parts)
+        if rank == 0:
+            np.save(os.path.join(out_dir, name + ".npy"), s.cpu().numpy())
+
+
 def spawn_ranks(a):
     """`python bench.py --gpus N` without a launcher (WORLD_SIZE unset): start the N ranks ourselves, one per GPU, as a
     `torch.distributed.run` CHILD process -- this parent never touches the GPU (no HIP call before or after; counting devices
@@ -719,7 +760,7 @@ def main():
     # live counters first: fresh child processes under rocprofv3 --pmc, BEFORE this process imports torch or touches the GPU.  (They carry
     # their own time limits and are ended as a process group; the run's watchdog is armed behind them, with the whole budget.)
     live_pmc, live_pmc_why = None, "not attempted"
-    if a.gpus == 1 and "WORLD_SIZE" not in os.environ and not a.no_pmc and not a.strict and not a.full_loop and a.workload in ("config2", "config4"):
+    if a.full and a.gpus == 1 and "WORLD_SIZE" not in os.environ and not a.no_pmc and not a.strict and not a.full_loop and a.workload in ("config2", "config4"):
         progress("rocprofv3 --pmc child processes (live counters of this run's kernels) ...")
         live_pmc, live_pmc_why = pmc_children(a)
         progress("live counters: %s" % ("ok" if live_pmc else live_pmc_why))
@@ -807,41 +848,46 @@ def main():
         step()
     sync()
     progress("warm-up done")
-    power = PowerSampler(local_rank).start()
+    power = PowerSampler(local_rank).start() if a.full else None
     dycore.profile(3)                                            # ONE hipEvent pair per time_step on the handle's stream (pairs around every stage and the dominant kernel cost 1.5 % of the step: tools/event_overhead.py)
     t0 = time.perf_counter()
     for _ in range(a.steps):
         step()
     sync()
     el = time.perf_counter() - t0
-    power_timed = power.stop()
+    power_timed = power.stop() if power is not None else None
     progress("timed region done")
+    if a.dump_outputs:                                           # (before anything below steps the model again)
+        dump_outputs(torch, dist, coupler, world, rank, a.dump_outputs)
+        progress("outputs written to %s" % a.dump_outputs)
     sched = dycore.schedule()                                    # what the timed time_steps ran (mw_dycore_schedule), not re-derived here
     KNAMES = ["xz_state", "tracer_patch", "tracer_update_unfused", "halo", "convert", "y_state", "y_tracers", "tracers_fused"]
     prof_step = dycore.profile_get(9)                            # every time_step, first launch to the join: live, over the timed region
     prof_stage = (prof_step[0], 3 * prof_step[1])                # = its three RK stages (the bench's dt is one sub-cycle)
-    # Outside the timed region: every kernel class bracketed by events (their markers cost ~2 % of the step), same schedule
-    dycore.profile(1)
-    for _ in range(3):
-        step()
-    prof = {n: dycore.profile_get(i) for i, n in enumerate(KNAMES)}
-    prof_waits = (dycore.profile_get(10), dycore.profile_get(11))  # pipelined schedule of a decomposed block: the compute stream's waits for the state / tracer strips
-    prof_dom = prof["xz_state"]                                  # the dominant kernel on its own: live, the three steps behind the timed region
     dycore.profile(0)
-    # Outside the timed region: the same kernels with the two pipelines serialised, so that each kernel's duration is
-    # exclusive.  (With N > 1 -- or option overlap = 1 -- the state and tracer pipelines of the timed region run on two streams and
-    # share the chip; on one rank the default schedule is one stream and the two sets of numbers agree.)
-    prof_excl = None
-    if not a.strict:
-        dycore.set_option("overlap", 0)                          # (a handle option: nothing in this process reads the environment per launch)
-        dycore.time_step(coupler, dt)
-        torch.cuda.synchronize()
+    prof = prof_waits = prof_dom = prof_excl = None
+    if a.full:
+        # Outside the timed region: every kernel class bracketed by events (their markers cost ~2 % of the step), same schedule
         dycore.profile(1)
         for _ in range(3):
-            dycore.time_step(coupler, dt)
-        prof_excl = {n: dycore.profile_get(i) for i, n in enumerate(KNAMES)}
+            step()
+        prof = {n: dycore.profile_get(i) for i, n in enumerate(KNAMES)}
+        prof_waits = (dycore.profile_get(10), dycore.profile_get(11))  # pipelined schedule of a decomposed block: the compute stream's waits for the state / tracer strips
+        prof_dom = prof["xz_state"]                              # the dominant kernel on its own: live, the three steps behind the timed region
         dycore.profile(0)
-        dycore.set_option("overlap", -1)
+        # Outside the timed region: the same kernels with the two pipelines serialised, so that each kernel's duration is
+        # exclusive.  (With N > 1 -- or option overlap = 1 -- the state and tracer pipelines of the timed region run on two streams and
+        # share the chip; on one rank the default schedule is one stream and the two sets of numbers agree.)
+        if not a.strict:
+            dycore.set_option("overlap", 0)                      # (a handle option: nothing in this process reads the environment per launch)
+            dycore.time_step(coupler, dt)
+            torch.cuda.synchronize()
+            dycore.profile(1)
+            for _ in range(3):
+                dycore.time_step(coupler, dt)
+            prof_excl = {n: dycore.profile_get(i) for i, n in enumerate(KNAMES)}
+            dycore.profile(0)
+            dycore.set_option("overlap", -1)
     el_local = el
     if world > 1:
         t = torch.tensor([el], dtype=torch.float64, device=device)
@@ -879,7 +925,7 @@ def main():
     # own time per step, what the exchange costs on the critical path (the compute stream's waits for the strips, per RK stage), and the
     # SAME block as a one-rank periodic domain timed on the same GPUs right behind the run -- efficiency computed inside the run
     multi = None
-    if "WORLD_SIZE" in os.environ:
+    if a.full and "WORLD_SIZE" in os.environ:
         progress("multi-GPU diagnostics (per-rank times, strip waits, the one-rank block) ...")
         mine = {"rank": rank, "device": torch.cuda.get_device_name(local_rank), "ms_per_step": el_local / a.steps * 1e3,
                 "wait_state_strips_ms_per_stage": (prof_waits[0][0] / prof_waits[0][1]) if prof_waits[0][1] else 0.0,
@@ -930,91 +976,6 @@ def main():
         value = total_updates / el
         ms_per_step = el / a.steps * 1e3
         per_gpu = value / world
-        # ---- the flux stencil of one RK stage = 32 V B per cell, against everything that stage launches
-        stage_ms_live = (prof_stage[0] / prof_stage[1]) if (prof_stage[1] and not two_streams and not a.strict) else None
-        stage_ms = stage_ms_live if stage_ms_live else ms_per_step / 3.0
-        stage_bytes = 32.0 * V * ncells_local
-        achieved = stage_bytes / (stage_ms * 1e-3) / 1e9
-        # ---- the dominant kernel on its own
-        flux_ms, flux_n = prof_dom
-        avg_flux_s = flux_ms / 1e3 / max(1, flux_n)
-        # k_xz_state per cell and launch: read 5 (state) + 5 (y tendencies) [+ 5 q^n in stages 2,3], write 5 + 2 doubles + 2 bytes
-        dom_bytes = ((10 + 15 + 15) / 3.0 + 7) * 8.0 * ncells_local + 2.0 * ncells_local
-        if a.strict:                                             # general path: k_flux reads V, writes 3V doubles per cell
-            dom_bytes = 32.0 * V * ncells_local
-        dom_achieved = dom_bytes / avg_flux_s / 1e9 if flux_n else None
-        # ---- counters from the committed rocprofv3 summary: only while the kernel sources are the profiled ones
-        traffic, dom_traffic, valu_busy, valu_instr, prov, valu_side, derived = None, None, None, None, None, None, None
-        pmc = os.path.join(ROOT, "profiles", "latest_summary.json")
-        if (live_pmc is not None or os.path.exists(pmc)) and not a.strict:
-            try:
-                now = kernel_source_hash()
-                if live_pmc is not None:                       # counted on THIS box by this run's own child processes
-                    pj = live_pmc
-                    prov = {"file": None, "source": "live: rocprofv3 --pmc child processes of this bench run (%.0f s)" % pj["seconds"], "tag": "live",
-                            "profiled_sources_sha16": now, "current_sources_sha16": now, "valid": int(pj["cells_per_launch"]) == ncells_local}
-                else:
-                    pj = json.load(open(pmc))
-                    prov = {"file": "profiles/latest_summary.json", "source": "replayed from the committed summary (live counters: %s)" % live_pmc_why,
-                            "tag": pj.get("tag"), "profiled_sources_sha16": pj.get("kernel_sources_sha16"),
-                            "current_sources_sha16": now, "valid": bool(pj.get("kernel_sources_sha16") == now and
-                                                                        int(pj.get("cells_per_launch", 0)) == ncells_local)}
-                    if a.ord != 5:
-                        prov["valid"] = False                  # the committed counters are the WENO-5 kernels'
-                if prov["valid"]:
-                    K = pj["kernels"]
-                    ks = [v for k, v in K.items() if k.startswith("k_xz_state")]
-                    dom_traffic = sum(k["hbm_read_bytes"] + k["hbm_write_bytes"] for k in ks) / len(ks)
-                    valu_busy = sum(k["valu_busy_frac"] for k in ks) / len(ks)
-                    valu_instr = sum(k["valu_instr_per_cell"] for k in ks) / len(ks)
-                    stage_k = [v for k, v in K.items() if k.startswith(("k_xz_state", "k_y_all", "k_y_state", "k_y_tracers", "k_tracers_fused", "k_tracer_patch"))]
-                    nstages = sum(k["calls"] for k in ks)      # one k_xz_state launch per RK stage
-                    traffic = sum((k["hbm_read_bytes"] + k["hbm_write_bytes"]) * k["calls"] for k in stage_k if "hbm_read_bytes" in k) / nstages
-                    # per-kernel counted bandwidth of the profiled run (bytes / that run's average duration) and VALU-busy range
-                    big = [k for k in stage_k if "hbm_read_bytes" in k and k.get("avg_us", 0) > 50]
-                    kbw = [(k["hbm_read_bytes"] + k["hbm_write_bytes"]) / (k["avg_us"] * 1e-6) / 1e12 for k in big]
-                    kvb = [k["valu_busy_frac"] for k in big if "valu_busy_frac" in k]
-                    derived = {"kernel_TBps_min": min(kbw), "kernel_TBps_max": max(kbw), "valu_busy_min": min(kvb), "valu_busy_max": max(kvb),
-                               "traffic_over_algorithmic": traffic / (32.0 * V * ncells_local)}
-                    # fp64-VALU side of the roofline (the binding one): counted VALU instructions of one cell-update against the
-                    # chip's issue rate (1024 SIMDs, one wave64 instruction per 4 cycles, 2.4 GHz peak engine clock)
-                    instr_cu = sum(k["valu_instr_per_cell"] * k["calls"] for k in stage_k if "valu_instr_per_cell" in k) / nstages * 3.0
-                    valu_side = {"instr_per_cell_update": instr_cu, "achieved_wave_instr_per_s": per_gpu * instr_cu / 64.0,
-                                 "peak_wave_instr_per_s": 1024 * 2.4e9 / 4.0, "frac": per_gpu * instr_cu / 64.0 / (1024 * 2.4e9 / 4.0),
-                                 "source": "SQ_INSTS_VALU of %s x live cell-updates/s" % (prov["file"] or "this run's rocprofv3 --pmc children")}
-            except Exception:
-                traffic = dom_traffic = valu_side = derived = None
-        # ---- measured ceilings (mw_calib_*): the fp64 issue rate this chip sustains, the stage's bare arithmetic, the streaming copy rate
-        cal, floors, bound = None, None, "hbm"
-        if world == 1 and not a.no_calib and not a.strict:
-            try:
-                cal = calibration(torch, device, ncells_local)
-                peak_meas = max(c["wave_instr_per_s"] for c in cal["fma64"])
-                fl_s, fl_r = cal["stage_arith"]["smooth"]["ms_per_stage_of_requested_cells"], cal["stage_arith"]["rough"]["ms_per_stage_of_requested_cells"]
-                fl_c = cal["stage_arith"]["cloud_free"]["ms_per_stage_of_requested_cells"]
-                hbm_floor = (traffic / (cal["stream_copy_TBps"] * 1e12) * 1e3) if traffic else None
-                alg_floor = stage_bytes / (cal["stream_copy_TBps"] * 1e12) * 1e3
-                top = max(fl_s, hbm_floor or 0.0)
-                floors = {"arith_floor_ms_per_stage": fl_s, "arith_floor_ms_per_stage_rough_data": fl_r,
-                          "arith_floor_ms_per_stage_cloud_free_data": fl_c, "stage_over_arith_floor_cloud_free": stage_ms / fl_c,
-                          "hbm_floor_ms_per_stage_counted_traffic": hbm_floor, "hbm_floor_ms_per_stage_algorithmic_bytes": alg_floor,
-                          "stream_copy_TBps": cal["stream_copy_TBps"], "stage_ms": stage_ms, "stage_over_arith_floor": stage_ms / fl_s,
-                          "stage_over_max_floor": stage_ms / top,
-                          "frac_ceiling_if_arith_bound": stage_bytes / (fl_s * 1e-3) / 8.0e12,
-                          "what": "arith floor = mw_calib_stage_arith: 24 WENO-5 + 3 Riemann solves + passive fluxes per cell on registers, no HBM "
-                                  "traffic, k_xz_state's workgroup shape; hbm floor = bytes / the measured streaming copy rate"}
-                if valu_side:
-                    valu_side["peak_measured"] = peak_meas
-                    valu_side["frac_of_measured"] = valu_side["achieved_wave_instr_per_s"] / peak_meas
-                    valu_side["clock_GHz_under_fma_load"] = [c["clock_GHz_in_kernel"] for c in cal["fma64"]]
-                # what the numbers say: the stage cannot beat its bare arithmetic, which alone caps the algorithmic HBM fraction
-                cap = floors["frac_ceiling_if_arith_bound"]
-                bound = ("fp64-valu + hbm co-limited: the stage's bare arithmetic alone takes %.2f ms (%.2f ms on this cloud-free state, where the zero "
-                         "short-cut leaves 18 of 24 reconstructions; frac <= %.2f / %.2f at any schedule), its counted traffic at streaming speed %s; "
-                         "0.60 of 8 TB/s is out of reach in fp64 with the reference's limiter"
-                         % (fl_s, fl_c, cap, stage_bytes / (fl_c * 1e-3) / 8.0e12, ("%.2f ms" % hbm_floor) if hbm_floor else "n/a"))
-            except Exception as e:                               # calibration is evidence, not the measurement
-                cal = {"error": "%s: %s" % (type(e).__name__, e)}
         what = "complete supercell_example loop: WENO-FV dycore + Kessler + sponge_layer + ColumnNudger" if a.full_loop else "WENO-FV dycore only"
         if a.workload == "config3":
             what = "complete supercell_kessler_surrogate loop: WENO-FV dycore + ponni MLP inference (MFMA) beside Kessler + sponge_layer + ColumnNudger"
@@ -1041,49 +1002,137 @@ def main():
                        "hbm_frac_cell_update": value * 64 * V / 8.0e12 / world,
                        # through the Coupler boundary, which is what is timed: + 32 V for D1 and D13, + 24 with immersed boundaries
                        "alg_bytes_per_cell_update_boundary": 96 * V + (24 if city is not None else 0),
-                       "hbm_frac_cell_update_boundary": value * (96 * V + (24 if city is not None else 0)) / 8.0e12 / world},
-            # bound: the resource that binds the stage: its COUNTED HBM traffic -- 2.1 x the algorithmic bytes: y tendencies,
-            # face mass fluxes, tracer y fluxes written by one launch and read by the next -- moving at 4.6-5.6 TB/s, with the fp64
-            # instruction stream at 0.80-0.87 VALU busy right under it (the WENO-3 build, half the arithmetic, takes 93 % of the time).
-            # achieved / peak / frac are SURVEY.md 8(d)'s algorithmic figure (32 V B per cell against 8 TB/s: what the north star's 60 %
-            # target is quoted in); traffic / traffic_frac the counted bytes; roofline.fp64_valu the instruction side.
-            "roofline": {"bound": bound,
-                         "floors": floors,
-                         "binding_resource": ("HBM traffic of the stage's three launches (counted bytes: roofline.traffic = %.2f x algorithmic; "
-                                              "%.2f-%.2f TB/s per kernel in the profiled run, a streaming copy reaches 5.0-5.5 on this part) with "
-                                              "fp64 VALU issue co-limiting at %.2f-%.2f busy; numbers from roofline.pmc_provenance.file"
-                                              % (derived["traffic_over_algorithmic"], derived["kernel_TBps_min"], derived["kernel_TBps_max"],
-                                                 derived["valu_busy_min"], derived["valu_busy_max"])) if derived else
-                                             "HBM traffic of the stage's launches with fp64 VALU issue co-limiting (DESIGN.md 0b / 0c); no counter "
-                                             "summary matches the current kernel sources, so no figures are quoted here",
-                         "binding_resource_derived": derived,
-                         "kernel": "one RK stage = k_y_all (y faces of all variables) + k_xz_state + k_tracers_fused + k_tracer_patch "
-                                   "(SURVEY.md 8(d) flux stencil, 32 V B per cell)" if not a.strict else "one RK stage (general path)",
-                         "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0, "traffic": traffic,
-                         "traffic_frac": (traffic / (stage_ms * 1e-3) / 8.0e12) if traffic else None,
-                         "alg_bytes_per_launch": stage_bytes, "avg_launch_ms": stage_ms,
-                         "avg_launch_ms_source": "hipEvents around every time_step on the handle's stream over the timed region, / 3 RK stages (a pair per stage costs 1.5 % of what it times)" if stage_ms_live
-                                                 else "ms_per_step / 3 (two-stream schedule: a stage's launches overlap the next stage's)",
-                         "launches": prof_stage[1] if stage_ms_live else 3 * a.steps,
-                         "pmc_provenance": prov,
-                         "dominant_kernel": {"kernel": "k_flux" if a.strict else "k_xz_state", "achieved": dom_achieved,
-                                             "frac": (dom_achieved / 8000.0) if dom_achieved else None, "traffic": dom_traffic,
-                                             "avg_launch_ms": avg_flux_s * 1e3, "launches": flux_n, "alg_bytes_per_launch": dom_bytes,
-                                             "avg_launch_ms_source": "hipEvents around every launch on its stream, the three steps behind the timed region",
-                                             "avg_launch_ms_exclusive": (prof_excl["xz_state"][0] / max(1, prof_excl["xz_state"][1])) if prof_excl else None,
-                                             "valu_busy_frac": valu_busy, "valu_instr_per_cell": valu_instr},
-                         "fp64_valu": valu_side,
-                         "calibration": cal,
-                         "pipeline": {"alg_bytes_per_cell_update": 64 * V, "achieved": per_gpu * 64 * V / 1e9, "frac": per_gpu * 64 * V / 8.0e12}},
-            "multi_gpu": multi,
-            "power": {"timed_region": power_timed, "what": "package power (hwmon power1_*) and shader clock (freq1_input) of this rank's card, sampled every 10 ms: "
-                      "timed_region = the K timed steps (short: the package-power reading is still ramping up from idle there); simulation_loop = 2 s windows of the whole loop "
-                      "of the micro section, early (cloud-free) against late (storm, mature) -- the steady figures; board limit 1400 W"},
-            "kernel_ms_per_step": {k: v[0] / 3.0 for k, v in prof.items()},
-            "kernel_ms_per_step_exclusive": ({k: v[0] / 3.0 for k, v in prof_excl.items()} if prof_excl else None),
+                       "hbm_frac_cell_update_boundary": value * (96 * V + (24 if city is not None else 0)) / 8.0e12 / world}
         }
+        if a.full:
+            # ---- the flux stencil of one RK stage = 32 V B per cell, against everything that stage launches
+            stage_ms_live = (prof_stage[0] / prof_stage[1]) if (prof_stage[1] and not two_streams and not a.strict) else None
+            stage_ms = stage_ms_live if stage_ms_live else ms_per_step / 3.0
+            stage_bytes = 32.0 * V * ncells_local
+            achieved = stage_bytes / (stage_ms * 1e-3) / 1e9
+            # ---- the dominant kernel on its own
+            flux_ms, flux_n = prof_dom
+            avg_flux_s = flux_ms / 1e3 / max(1, flux_n)
+            # k_xz_state per cell and launch: read 5 (state) + 5 (y tendencies) [+ 5 q^n in stages 2,3], write 5 + 2 doubles + 2 bytes
+            dom_bytes = ((10 + 15 + 15) / 3.0 + 7) * 8.0 * ncells_local + 2.0 * ncells_local
+            if a.strict:                                             # general path: k_flux reads V, writes 3V doubles per cell
+                dom_bytes = 32.0 * V * ncells_local
+            dom_achieved = dom_bytes / avg_flux_s / 1e9 if flux_n else None
+            # ---- counters from the committed rocprofv3 summary: only while the kernel sources are the profiled ones
+            traffic, dom_traffic, valu_busy, valu_instr, prov, valu_side, derived = None, None, None, None, None, None, None
+            pmc = os.path.join(ROOT, "profiles", "latest_summary.json")
+            if (live_pmc is not None or os.path.exists(pmc)) and not a.strict:
+                try:
+                    now = kernel_source_hash()
+                    if live_pmc is not None:                       # counted live by this run's own child processes
+                        pj = live_pmc
+                        prov = {"file": None, "source": "live: rocprofv3 --pmc child processes of this bench run (%.0f s)" % pj["seconds"], "tag": "live",
+                                "profiled_sources_sha16": now, "current_sources_sha16": now, "valid": int(pj["cells_per_launch"]) == ncells_local}
+                    else:
+                        pj = json.load(open(pmc))
+                        prov = {"file": "profiles/latest_summary.json", "source": "replayed from the committed summary (live counters: %s)" % live_pmc_why,
+                                "tag": pj.get("tag"), "profiled_sources_sha16": pj.get("kernel_sources_sha16"),
+                                "current_sources_sha16": now, "valid": bool(pj.get("kernel_sources_sha16") == now and
+                                                                            int(pj.get("cells_per_launch", 0)) == ncells_local)}
+                        if a.ord != 5:
+                            prov["valid"] = False                  # the committed counters are the WENO-5 kernels'
+                    if prov["valid"]:
+                        K = pj["kernels"]
+                        ks = [v for k, v in K.items() if k.startswith("k_xz_state")]
+                        dom_traffic = sum(k["hbm_read_bytes"] + k["hbm_write_bytes"] for k in ks) / len(ks)
+                        valu_busy = sum(k["valu_busy_frac"] for k in ks) / len(ks)
+                        valu_instr = sum(k["valu_instr_per_cell"] for k in ks) / len(ks)
+                        stage_k = [v for k, v in K.items() if k.startswith(("k_xz_state", "k_y_all", "k_y_state", "k_y_tracers", "k_tracers_fused", "k_tracer_patch"))]
+                        nstages = sum(k["calls"] for k in ks)      # one k_xz_state launch per RK stage
+                        traffic = sum((k["hbm_read_bytes"] + k["hbm_write_bytes"]) * k["calls"] for k in stage_k if "hbm_read_bytes" in k) / nstages
+                        # per-kernel counted bandwidth of the profiled run (bytes / that run's average duration) and VALU-busy range
+                        big = [k for k in stage_k if "hbm_read_bytes" in k and k.get("avg_us", 0) > 50]
+                        kbw = [(k["hbm_read_bytes"] + k["hbm_write_bytes"]) / (k["avg_us"] * 1e-6) / 1e12 for k in big]
+                        kvb = [k["valu_busy_frac"] for k in big if "valu_busy_frac" in k]
+                        derived = {"kernel_TBps_min": min(kbw), "kernel_TBps_max": max(kbw), "valu_busy_min": min(kvb), "valu_busy_max": max(kvb),
+                                   "traffic_over_algorithmic": traffic / (32.0 * V * ncells_local)}
+                        # fp64-VALU side of the roofline (the binding one): counted VALU instructions of one cell-update against the
+                        # chip's issue rate (1024 SIMDs, one wave64 instruction per 4 cycles, 2.4 GHz peak engine clock)
+                        instr_cu = sum(k["valu_instr_per_cell"] * k["calls"] for k in stage_k if "valu_instr_per_cell" in k) / nstages * 3.0
+                        valu_side = {"instr_per_cell_update": instr_cu, "achieved_wave_instr_per_s": per_gpu * instr_cu / 64.0,
+                                     "peak_wave_instr_per_s": 1024 * 2.4e9 / 4.0, "frac": per_gpu * instr_cu / 64.0 / (1024 * 2.4e9 / 4.0),
+                                     "source": "SQ_INSTS_VALU of %s x live cell-updates/s" % (prov["file"] or "this run's rocprofv3 --pmc children")}
+                except Exception:
+                    traffic = dom_traffic = valu_side = derived = None
+            # ---- measured ceilings (mw_calib_*): the fp64 issue rate this chip sustains, the stage's bare arithmetic, the streaming copy rate
+            cal, floors, bound = None, None, "hbm"
+            if world == 1 and not a.no_calib and not a.strict:
+                try:
+                    cal = calibration(torch, device, ncells_local)
+                    peak_meas = max(c["wave_instr_per_s"] for c in cal["fma64"])
+                    fl_s, fl_r = cal["stage_arith"]["smooth"]["ms_per_stage_of_requested_cells"], cal["stage_arith"]["rough"]["ms_per_stage_of_requested_cells"]
+                    fl_c = cal["stage_arith"]["cloud_free"]["ms_per_stage_of_requested_cells"]
+                    hbm_floor = (traffic / (cal["stream_copy_TBps"] * 1e12) * 1e3) if traffic else None
+                    alg_floor = stage_bytes / (cal["stream_copy_TBps"] * 1e12) * 1e3
+                    top = max(fl_s, hbm_floor or 0.0)
+                    floors = {"arith_floor_ms_per_stage": fl_s, "arith_floor_ms_per_stage_rough_data": fl_r,
+                              "arith_floor_ms_per_stage_cloud_free_data": fl_c, "stage_over_arith_floor_cloud_free": stage_ms / fl_c,
+                              "hbm_floor_ms_per_stage_counted_traffic": hbm_floor, "hbm_floor_ms_per_stage_algorithmic_bytes": alg_floor,
+                              "stream_copy_TBps": cal["stream_copy_TBps"], "stage_ms": stage_ms, "stage_over_arith_floor": stage_ms / fl_s,
+                              "stage_over_max_floor": stage_ms / top,
+                              "frac_ceiling_if_arith_bound": stage_bytes / (fl_s * 1e-3) / 8.0e12,
+                              "what": "arith floor = mw_calib_stage_arith: 24 WENO-5 + 3 Riemann solves + passive fluxes per cell on registers, no HBM "
+                                      "traffic, k_xz_state's workgroup shape; hbm floor = bytes / the measured streaming copy rate"}
+                    if valu_side:
+                        valu_side["peak_measured"] = peak_meas
+                        valu_side["frac_of_measured"] = valu_side["achieved_wave_instr_per_s"] / peak_meas
+                        valu_side["clock_GHz_under_fma_load"] = [c["clock_GHz_in_kernel"] for c in cal["fma64"]]
+                    # what the numbers say: the stage cannot beat its bare arithmetic, which alone caps the algorithmic HBM fraction
+                    cap = floors["frac_ceiling_if_arith_bound"]
+                    bound = ("fp64-valu + hbm co-limited: the stage's bare arithmetic alone takes %.2f ms (%.2f ms on this cloud-free state, where the zero "
+                             "short-cut leaves 18 of 24 reconstructions; frac <= %.2f / %.2f at any schedule), its counted traffic at streaming speed %s; "
+                             "0.60 of 8 TB/s is out of reach in fp64 with the reference's limiter"
+                             % (fl_s, fl_c, cap, stage_bytes / (fl_c * 1e-3) / 8.0e12, ("%.2f ms" % hbm_floor) if hbm_floor else "n/a"))
+                except Exception as e:                               # calibration is evidence, not the measurement
+                    cal = {"error": "%s: %s" % (type(e).__name__, e)}
+            out.update({
+                # bound: the resource that binds the stage: its COUNTED HBM traffic -- 2.1 x the algorithmic bytes: y tendencies,
+                # face mass fluxes, tracer y fluxes written by one launch and read by the next -- moving at 4.6-5.6 TB/s, with the fp64
+                # instruction stream at 0.80-0.87 VALU busy right under it (the WENO-3 build, half the arithmetic, takes 93 % of the time).
+                # achieved / peak / frac are SURVEY.md 8(d)'s algorithmic figure (32 V B per cell against 8 TB/s: what the north star's 60 %
+                # target is quoted in); traffic / traffic_frac the counted bytes; roofline.fp64_valu the instruction side.
+                "roofline": {"bound": bound,
+                             "floors": floors,
+                             "binding_resource": ("HBM traffic of the stage's three launches (counted bytes: roofline.traffic = %.2f x algorithmic; "
+                                                  "%.2f-%.2f TB/s per kernel in the profiled run, a streaming copy reaches 5.0-5.5 on this part) with "
+                                                  "fp64 VALU issue co-limiting at %.2f-%.2f busy; numbers from roofline.pmc_provenance.file"
+                                                  % (derived["traffic_over_algorithmic"], derived["kernel_TBps_min"], derived["kernel_TBps_max"],
+                                                     derived["valu_busy_min"], derived["valu_busy_max"])) if derived else
+                                                 "HBM traffic of the stage's launches with fp64 VALU issue co-limiting (DESIGN.md 0b / 0c); no counter "
+                                                 "summary matches the current kernel sources, so no figures are quoted here",
+                             "binding_resource_derived": derived,
+                             "kernel": "one RK stage = k_y_all (y faces of all variables) + k_xz_state + k_tracers_fused + k_tracer_patch "
+                                       "(SURVEY.md 8(d) flux stencil, 32 V B per cell)" if not a.strict else "one RK stage (general path)",
+                             "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0, "traffic": traffic,
+                             "traffic_frac": (traffic / (stage_ms * 1e-3) / 8.0e12) if traffic else None,
+                             "alg_bytes_per_launch": stage_bytes, "avg_launch_ms": stage_ms,
+                             "avg_launch_ms_source": "hipEvents around every time_step on the handle's stream over the timed region, / 3 RK stages (a pair per stage costs 1.5 % of what it times)" if stage_ms_live
+                                                     else "ms_per_step / 3 (two-stream schedule: a stage's launches overlap the next stage's)",
+                             "launches": prof_stage[1] if stage_ms_live else 3 * a.steps,
+                             "pmc_provenance": prov,
+                             "dominant_kernel": {"kernel": "k_flux" if a.strict else "k_xz_state", "achieved": dom_achieved,
+                                                 "frac": (dom_achieved / 8000.0) if dom_achieved else None, "traffic": dom_traffic,
+                                                 "avg_launch_ms": avg_flux_s * 1e3, "launches": flux_n, "alg_bytes_per_launch": dom_bytes,
+                                                 "avg_launch_ms_source": "hipEvents around every launch on its stream, the three steps behind the timed region",
+                                                 "avg_launch_ms_exclusive": (prof_excl["xz_state"][0] / max(1, prof_excl["xz_state"][1])) if prof_excl else None,
+                                                 "valu_busy_frac": valu_busy, "valu_instr_per_cell": valu_instr},
+                             "fp64_valu": valu_side,
+                             "calibration": cal,
+                             "pipeline": {"alg_bytes_per_cell_update": 64 * V, "achieved": per_gpu * 64 * V / 1e9, "frac": per_gpu * 64 * V / 8.0e12}},
+                "multi_gpu": multi,
+                "power": {"timed_region": power_timed, "what": "package power (hwmon power1_*) and shader clock (freq1_input) of this rank's card, sampled every 10 ms: "
+                          "timed_region = the K timed steps (short: the package-power reading is still ramping up from idle there); simulation_loop = 2 s windows of the whole loop "
+                          "of the micro section, early (cloud-free) against late (storm, mature) -- the steady figures; board limit 1400 W"},
+                "kernel_ms_per_step": {k: v[0] / 3.0 for k, v in prof.items()},
+                "kernel_ms_per_step_exclusive": ({k: v[0] / 3.0 for k, v in prof_excl.items()} if prof_excl else None),
+            })
         pending[0] = out
-        if world == 1 and not a.no_micro and not a.strict and city is None:
+        if a.full and world == 1 and not a.no_micro and not a.strict and city is None:
             progress("micro section (Kessler, MLP, developed state, the whole simulation loop) ...")
             out.update(micro_section(torch, modules, coupler, dycore, micro, dt, a))
             out["config"]["value_simulation_loop"] = out.get("value_simulation_loop")
@@ -1121,7 +1170,7 @@ def main():
                         "(storm.isolated_after / mature.isolated_after = rounds 4-6's figure, back-to-back dycore steps behind the loop: a state the simulation never visits); "
                         "developed = a seeded stress state with cloud / rain rims everywhere"}
             out["roofline"]["state"] = "cloud_free (headline; see frac_by_state for the storm / developed / mature states)"
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             progress("cpu baseline ...")
             out["cpu_baseline"] = cpu_baseline(a.cpu_sample)
         pending[0] = None

@@ -54,7 +54,7 @@ def test_bench_config4_block_under_the_torchrun_launcher():
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "config4", "--steps", "2", "--warmup", "1",
-           "--no-micro", "--no-cpu-baseline"]
+           "--full", "--no-micro", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -84,7 +84,7 @@ def test_bench_micro_section_on_a_small_block():
     roofline, the RCCL self-loop blocks."""
     import json
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--nx", "96", "--ny", "96", "--nz", "40", "--steps", "3", "--warmup", "1", "--storm-steps", "160",
-           "--mature-steps", "330", "--sustained-steps", "40", "--no-pmc", "--no-calib", "--no-cpu-baseline"]
+           "--mature-steps", "330", "--sustained-steps", "40", "--full", "--no-pmc", "--no-calib", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -102,3 +102,36 @@ def test_bench_micro_section_on_a_small_block():
         assert f[k]["frac"] > 0 and f[k]["ms_per_step"] > 0, k
     assert d["simulation_loop"]["steps"] == 157 and d["simulation_loop"]["to_mature"]["steps"] == 327
     assert d["value_simulation_loop"] > 0 and d["value_developed"] > 0 and d["kessler"] and d["mlp"]
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run (no --full) on a small block: one JSON line with the headline keys and none of the --full sections; --steps is the
+    number of timed steps; --dump-outputs writes the last timed step's fields as float64 .npy files, bit-identical between two runs."""
+    import json
+    import numpy as np
+    dumps = []
+    for rep in range(2):
+        d_out = tmp_path / ("out%d" % rep)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--nx", "64", "--ny", "48", "--nz", "32", "--steps", "4", "--warmup", "1",
+               "--dump-outputs", str(d_out)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "cell-updates/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert abs(d["value"] - 64 * 48 * 32 / (d["ms_per_step"] * 1e-3)) <= 1e-9 * d["value"]
+        for k in ("roofline", "power", "kernel_ms_per_step", "multi_gpu", "cpu_baseline", "kessler", "storm"):
+            assert k not in d, k
+        names = sorted(f.name for f in d_out.iterdir())
+        assert names == sorted(n + ".npy" for n in ("density_dry", "uvel", "vvel", "wvel", "temp", "water_vapor", "cloud_liquid", "precip_liquid"))
+        arrs = {n: np.load(str(d_out / n)) for n in names}
+        for n, a in arrs.items():
+            assert a.dtype == np.float64 and a.shape == (64 * 48 * 32,) and np.all(np.isfinite(a)), n
+        assert arrs["density_dry.npy"].min() > 0 and np.abs(arrs["uvel.npy"]).max() > 0
+        dumps.append(arrs)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
