@@ -372,6 +372,13 @@ int  mw_nc_inq_dimlen(mw_nc_t nc, const char *name, long long *len);            
 int  mw_nc_put_vara_double(mw_nc_t nc, int varid, const long long *start, const long long *count, const double *host_data);
 int  mw_nc_put_vara(mw_nc_t nc, int varid, const long long *start, const long long *count, const void *host_data);   /* variable's own type */
 int  mw_nc_set_numrecs(mw_nc_t nc, long long numrecs);
+/* Reads back (HOST, the variable's own type, C order): records [rec_start, rec_start + rec_count) of a record variable in full, record axis
+ * first, or the whole of a fixed-size variable (rec_start 0, rec_count ignored) -- the reads of the training notebooks' input step
+ * (kessler_netcdf_to_numpy.ipynb: nc.variables['inputs'][:], ['outputs'][:], ['time_step_size']) for the files DataGenerator writes. */
+/* nc.inq_var: nc_type (4 int, 5 float, 6 double), rank, extents (up to 8; the record dimension's extent is the number of records) and
+ * whether the variable's first dimension is the record dimension. */
+int  mw_nc_inq_var(mw_nc_t nc, int varid, int *nc_type, int *ndims, long long *shape8, int *is_record);
+int  mw_nc_get_var(mw_nc_t nc, int varid, long long rec_start, long long rec_count, void *host_data);
 int  mw_nc_close(mw_nc_t nc);
 /* The body of Dynamics_Euler_Stratified_WenoFV::output's variable loop, :2176-2185 (and Time_Averager::finalize's,
  * time_averager.h:131-136): ensemble member 0 of the DEVICE field (nz,ny,nx,nens) -> host -> this rank's hyperslab
@@ -410,6 +417,39 @@ int  mw_micro_sample_mask(const mw_grid_t *g, const double *const *in4, const do
                           double thr_active, double thr_inactive, unsigned char *mask, void *stream);
 int  mw_micro_gather_samples(const mw_grid_t *g, const double *rho_d, const double *const *in4, const double *const *out4,
                              const long long *cells, long long n, float *inputs, float *outputs, void *stream);
+
+/* ---- surrogate training (experiments/supercell_kessler_surrogate/jupyter_notebooks) --------------------------------------- */
+/* The notebooks' fit of the single-cell model, natively (csrc/mw_train.hip).  Sets are feature-major fp32 DEVICE
+ * arrays, x (5, n) and y (4, n), batch fastest -- mw_ponni_forward's layout.  Parameters: (models, 104) fp32 DEVICE, per model W1 (5,10),
+ * b1 (10), W2 (10,4), b2 (4) in Keras order (the order of miniweatherml_amd/data/kessler_surrogate_weights.txt); moments the same shape.
+ * Permutations: a 4-round Feistel network on the smallest square power-of-two domain >= n, cycle-walked into [0, n), round keys from
+ * splitmix64 -- the exact definition is the Python restatement miniweatherml_amd/surrogate_train.py (feistel_permutation). */
+#define MW_SURROGATE_MAX_BATCH 8192
+#define MW_SURROGATE_MAX_MODELS 256
+/* kessler_netcdf_to_numpy.ipynb (np.random.shuffle of the samples) + kessler_singlecell_train_example.ipynb (min-max scaling, test_split,
+ * then Keras' validation_split tail): sample p of the permutation of seed (tag 2^64 - 1) goes to position p of [train | val | test], scaled
+ * as (float)(((double)v - min) / (max - min)) -- the strict inference's expression.  raw_in (n, 5), raw_out (n, 4): DEVICE fp32 (slot 0
+ * of DataGenerator's inputs); scl_in (5, 2), scl_out (4, 2): HOST [min, max] rows; n_train + n_val + n_test = n. */
+int  mw_surrogate_prepare(long long n, const float *raw_in, const float *raw_out, const double *scl_in, const double *scl_out,
+                          unsigned long long seed, long long n_train, long long n_val, float *train_x, float *train_y, float *val_x,
+                          float *val_y, float *test_x, float *test_y, void *stream);
+/* One epoch of model.fit(epochs, batch_size, shuffle=True) with Nadam (kessler_singlecell_train_example.ipynb, the compile / fit cells) for
+ * `models` models in ONE launch, one workgroup per model: model m visits the training set in the order of the permutation of (seed + m,
+ * epoch) in batches of `batch` (the last one partial), and takes one Nadam step per batch.  table: HOST-computed per-step scalars of this
+ * epoch's steps, 3 fp32 each (lr (1 - mu_t) / (1 - prod mu), lr mu_t+1 / (1 - prod mu * mu_t+1), 1 - beta2^t), ceil(n / batch) rows,
+ * DEVICE.  stats (models, 2) fp64 DEVICE: sum over the epoch's samples of sum_outputs (y - t)^2 and of sum_outputs |y - t|, each sample with
+ * the weights of its batch (Keras' running `loss` and `mean_absolute_error` = these / (4 n)). */
+int  mw_surrogate_train_epoch(int models, const float *x, const float *y, long long n, int batch, int epoch, unsigned long long seed,
+                              float *params, float *m1, float *m2, const float *table, float beta1, float beta2, float eps, double *stats,
+                              void *stream);
+/* Test aid: loss (1 fp32) and gradient (104 fp32, the parameters' order) of the mean squared error of ONE batch of `batch` samples x (5,
+ * batch), y (4, batch), at params (104); all DEVICE.  The trainer's own batch routine, in a one-workgroup launch. */
+int  mw_surrogate_batch_grad(const float *params, const float *x, const float *y, int batch, float *grad, float *loss, void *stream);
+/* Error sums of `nsets` predictions pred (nsets, 4, n) against y (4, n), all DEVICE fp32 -- model.evaluate / the notebook's test metrics
+ * cell.  out (nsets, 24) fp64 DEVICE: per output v at [6 v ...]: sum (y - p)^2, sum |y - p|, sum (y - p), sum |y|, max |y - p|, max |y|.
+ * Fixed reduction order (run-to-run identical).  workspace: DEVICE, mw_surrogate_errors_workspace_bytes(nsets). */
+long long mw_surrogate_errors_workspace_bytes(int nsets);
+int  mw_surrogate_errors(long long n, int nsets, const float *pred, const float *y, void *workspace, double *out, void *stream);
 
 /* ---- DataManager validators ---------------------------------------------------------------------------- */
 /* core::DataManager::validate / validate_nan / validate_inf / validate_pos (model/core/DataManager.h:385-483) -- the reference's only

@@ -120,6 +120,8 @@ SYMBOLS = {
     "mw_nc_inq_dimlen": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_longlong)]),
     "mw_nc_put_vara_double": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_void_p]),
     "mw_nc_set_numrecs": (C.c_int, [C.c_void_p, C.c_longlong]),
+    "mw_nc_inq_var": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "mw_nc_get_var": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p]),
     "mw_nc_close": (C.c_int, [C.c_void_p]),
     "mw_output_put_field": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.POINTER(Grid), C.c_void_p, C.c_void_p]),
     "mw_horizontal_sponge_column": (C.c_int, [C.POINTER(Grid), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
@@ -134,6 +136,13 @@ SYMBOLS = {
     "mw_micro_gather_samples": (C.c_int, [C.POINTER(Grid), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_longlong,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "mw_ponni_forward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mw_surrogate_prepare": (C.c_int, [C.c_longlong, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_ulonglong,
+                                       C.c_longlong, C.c_longlong] + [C.c_void_p] * 6 + [C.c_void_p]),
+    "mw_surrogate_train_epoch": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_ulonglong] + [C.c_void_p] * 4 +
+                                 [C.c_float] * 3 + [C.c_void_p, C.c_void_p]),
+    "mw_surrogate_batch_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mw_surrogate_errors_workspace_bytes": (C.c_longlong, [C.c_int]),
+    "mw_surrogate_errors": (C.c_int, [C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mw_validate_f64": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]),
     "mw_validate_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]),
     "mw_mlp_forward": (C.c_int, [C.c_longlong] + [C.c_void_p] * 5 + [C.POINTER(C.c_float)] * 4 +

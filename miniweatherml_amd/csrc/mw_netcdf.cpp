@@ -26,6 +26,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
+#include <algorithm>
 
 using mw::set_error;
 
@@ -300,6 +301,57 @@ int mw_nc_put_vara(mw_nc_t nc, int varid, const long long *start, const long lon
 int mw_nc_put_vara_double(mw_nc_t nc, int varid, const long long *start, const long long *count, const double *data) {
   if (nc && varid >= 0 && varid < (int)nc->vars.size() && nc->vars[varid].type != 6) MW_FAIL("nc_put_vara_double: not a double variable");
   return mw_nc_put_vara(nc, varid, start, count, data);
+}
+
+// Type, rank, extents of a variable (the record dimension's extent: the current number of records) and whether it is a record variable.
+int mw_nc_inq_var(mw_nc_t nc, int varid, int *nc_type, int *ndims, long long *shape8, int *is_record) {
+  if (!nc || !nc_type || !ndims || !shape8 || !is_record) MW_FAIL("nc_inq_var: null argument");
+  if (varid < 0 || varid >= (int)nc->vars.size()) MW_FAIL("nc_inq_var: bad variable id");
+  const Var &v = nc->vars[varid];
+  if (v.dims.size() > 8) MW_FAIL("nc_inq_var: more than 8 dimensions");
+  *nc_type = v.type; *ndims = (int)v.dims.size(); *is_record = v.rec ? 1 : 0;
+  for (size_t i = 0; i < v.dims.size(); i++) {
+    shape8[i] = nc->dims[v.dims[i]].len;
+    if (v.rec && i == 0 && mw_nc_inq_dimlen(nc, nc->dims[v.dims[0]].name.c_str(), &shape8[0])) return 1;
+  }
+  return 0;
+}
+
+// Reads records [rec_start, rec_start + rec_count) of a record variable -- every record's whole slab, C order, record axis first --
+// or, for a fixed-size variable, the whole variable (rec_start 0, rec_count ignored), into HOST memory of the variable's own type.
+// The records of one variable are vsize bytes each, recsize apart: they are read in blocks of whole records and byte-swapped here.
+int mw_nc_get_var(mw_nc_t nc, int varid, long long rec_start, long long rec_count, void *data) {
+  if (!nc || !data) MW_FAIL("nc_get_var: null argument");
+  if (nc->defining) MW_FAIL("nc_get_var: still in define mode");
+  if (varid < 0 || varid >= (int)nc->vars.size()) MW_FAIL("nc_get_var: bad variable id");
+  const Var &v = nc->vars[varid];
+  const int es = v.esize();
+  long long slab = 1;                                                // elements per record (record variable) or in total (fixed)
+  for (size_t i = v.rec ? 1 : 0; i < v.dims.size(); i++) slab *= nc->dims[v.dims[i]].len;
+  auto swap_out = [&](const unsigned char *src, unsigned char *dst, long long n) {
+    if (es == 8) for (long long r = 0; r < n; r++) { uint64_t u; memcpy(&u, src + r * 8, 8); u = be64(u); memcpy(dst + r * 8, &u, 8); }
+    else         for (long long r = 0; r < n; r++) { uint32_t u; memcpy(&u, src + r * 4, 4); u = be32(u); memcpy(dst + r * 4, &u, 4); }
+  };
+  unsigned char *dst = (unsigned char *)data;
+  if (!v.rec) {
+    std::vector<unsigned char> b((size_t)(slab * es));
+    if (slab && pread_all(nc->fd, b.data(), b.size(), v.begin)) MW_FAIL("nc_get_var: read failed");
+    swap_out(b.data(), dst, slab);
+    return 0;
+  }
+  long long nrec = 0;
+  if (mw_nc_inq_dimlen(nc, nc->dims[v.dims[0]].name.c_str(), &nrec)) return 1;
+  if (rec_start < 0 || rec_count < 0 || rec_start + rec_count > nrec) MW_FAIL("nc_get_var: records out of range");
+  const long long per = std::max<long long>(1, (64ll << 20) / std::max<long long>(1, nc->recsize));   // records per 64 MB block
+  std::vector<unsigned char> b;
+  for (long long r0 = rec_start; r0 < rec_start + rec_count; r0 += per) {
+    const long long nr = std::min(per, rec_start + rec_count - r0);
+    const long long bytes = (nr - 1) * nc->recsize + slab * es;    // from this block's first slab to the end of its last
+    b.resize((size_t)bytes);
+    if (pread_all(nc->fd, b.data(), (size_t)bytes, v.begin + r0 * nc->recsize)) MW_FAIL("nc_get_var: read failed (file shorter than its records)");
+    for (long long r = 0; r < nr; r++) { swap_out(b.data() + r * nc->recsize, dst, slab); dst += slab * es; }
+  }
+  return 0;
 }
 
 // Sets the record count in the header (the creating / main rank calls this after a record has been written).

@@ -642,6 +642,23 @@ class _NcFile:
     def set_numrecs(self, n):
         check(capi.lib().mw_nc_set_numrecs(self.h, int(n)))
 
+    def get(self, name, rec_start=0, rec_count=None):
+        """Reads a variable back as a numpy array of its own type: a record variable's records [rec_start, rec_start + rec_count) (default:
+        all) in full, record axis first, or the whole of a fixed-size variable (a scalar comes back with shape ())."""
+        L = capi.lib()
+        vid = self.varid(name)
+        ty, nd, rec, shape = C.c_int(0), C.c_int(0), C.c_int(0), (C.c_longlong * 8)()
+        check(L.mw_nc_inq_var(self.h, vid, C.byref(ty), C.byref(nd), shape, C.byref(rec)))
+        dims = [int(shape[i]) for i in range(nd.value)]
+        if rec.value:
+            rec_count = dims[0] - int(rec_start) if rec_count is None else int(rec_count)
+            dims[0] = rec_count
+        out = np.empty(dims, dtype={4: np.int32, 5: np.float32, 6: np.float64}[ty.value])
+        if out.size:
+            check(L.mw_nc_get_var(self.h, vid, int(rec_start) if rec.value else 0, rec_count if rec.value else 0,
+                                  out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def close(self):
         if self.h and self.h.value:
             h, self.h = self.h, C.c_void_p(None)

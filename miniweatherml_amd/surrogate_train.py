@@ -1,0 +1,443 @@
+"""Native training of the Kessler surrogate (5 -> 10 -> 4, LeakyReLU(0.1)) from DataGenerator's sample files: the step of the reference's
+surrogate workflow between generate_micro_data and inference_ponni, which the reference does in Keras
+(experiments/supercell_kessler_surrogate/jupyter_notebooks/kessler_netcdf_to_numpy.ipynb, kessler_singlecell_train_example.ipynb).
+
+    train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, ...) -> dict
+    python -m miniweatherml_amd.surrogate_train FILE... --out DIR [--epochs N] [--models K] [--seed S] ...
+
+The fit is the notebooks' recorded one, restated with integer-defined random choices (Keras' random streams cannot be reproduced):
+pre-shuffle, per-variable min-max scaling over all samples, test split = the tail, validation split = the tail of the rest (Keras'
+validation_split), per-epoch shuffle of the training set, Dense kernels uniform in [-0.05, 0.05), biases 0, loss mse, Nadam (TF 2.x Keras).
+The hot path is csrc/mw_train.hip (one workgroup per model, the batches loop in the kernel); the validation and test predictions are
+mw_ponni_forward's MFMA forward.  This file holds the host side: reading and checking the data, the permutations' definition (restated
+here so that tests can replay the batch order), the Nadam scalars, the reports and the output files.  DESIGN.md section 13.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+MAX_BATCH = 8192                     # MW_SURROGATE_MAX_BATCH (include/mw_cdna4.h)
+MAX_MODELS = 256                     # MW_SURROGATE_MAX_MODELS
+IN_NAMES = ("temperature", "dry air density", "water vapor density", "cloud liquid density", "precipitation density")
+OUT_NAMES = ("temperature", "water vapor density", "cloud liquid density", "precipitation density")
+NADAM = dict(beta1=0.9, beta2=0.999, eps=1e-7, schedule_decay=0.004)    # tf.keras.optimizers.Nadam defaults
+M64 = (1 << 64) - 1
+TAG_PRESHUFFLE, TAG_WEIGHTS = M64, M64 - 1                               # stream tags; epoch e shuffles with tag e
+
+
+class SurrogateTrainError(ValueError):
+    pass
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# integer-defined random choices (the device side is csrc/mw_train.hip: make_feistel / feistel_index)
+def splitmix64(z):
+    z = (int(z) + 0x9E3779B97F4A7C15) & M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+    return z ^ (z >> 31)
+
+
+def _mix32(x):
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7FEB352D)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846CA68B)
+    return x ^ (x >> np.uint32(16))
+
+
+def feistel_keys(a, tag, n):
+    """Round keys and half width of the permutation of [0, n) for the stream (a, tag): base = sm64(sm64(a) ^ tag), key r = the high
+    word of sm64(base + r), r = 0..3; h = the smallest h >= 1 with 4^h >= n."""
+    base = splitmix64(splitmix64(int(a) & M64) ^ (int(tag) & M64))
+    keys = [splitmix64((base + r) & M64) >> 32 for r in range(4)]
+    h = 1
+    while h < 32 and (1 << (2 * h)) < n:
+        h += 1
+    return keys, h
+
+
+def feistel_permutation(n, a, tag):
+    """perm[p] = the sample at position p: four Feistel rounds (L, R) <- (R, L ^ (mix32(R ^ key_r) & mask)) on x = (L << h) | R, applied
+    again while the value is >= n (cycle-walking: a bijection of [0, n))."""
+    keys, h = feistel_keys(a, tag, n)
+    mask = np.uint32((1 << h) - 1)
+
+    def rounds(x):
+        L = (x >> np.uint64(h)).astype(np.uint32)
+        R = (x & np.uint64(mask)).astype(np.uint32)
+        for k in keys:
+            L, R = R, L ^ (_mix32(R ^ np.uint32(k)) & mask)
+        return (L.astype(np.uint64) << np.uint64(h)) | R.astype(np.uint64)
+
+    out = rounds(np.arange(n, dtype=np.uint64))
+    bad = np.flatnonzero(out >= np.uint64(n))
+    while bad.size:
+        out[bad] = rounds(out[bad])
+        bad = bad[out[bad] >= np.uint64(n)]
+    return out.astype(np.int64)
+
+
+def preshuffle_permutation(n, seed):
+    """kessler_netcdf_to_numpy.ipynb's shuffle of all samples: depends on the (split) seed alone."""
+    return feistel_permutation(n, seed, TAG_PRESHUFFLE)
+
+
+def epoch_permutation(n_train, seed, model, epoch):
+    """The order in which model `model` visits the training set in epoch `epoch` (0-based): Keras' shuffle=True."""
+    return feistel_permutation(n_train, (int(seed) + int(model)) & M64, int(epoch))
+
+
+def initial_weights(seed, models):
+    """(models, 104) fp32: Dense kernels RandomUniform(-0.05, 0.05) -- u = (sm64(sm64(sm64(seed + m) ^ tag) + p) >> 40) / 2^24 for
+    parameter index p, w = fp32(0.1 u - 0.05) -- and zero biases (Keras' defaults)."""
+    w = np.zeros((models, 104), dtype=np.float32)
+    for m in range(models):
+        base = splitmix64(splitmix64((int(seed) + m) & M64) ^ TAG_WEIGHTS)
+        for p in list(range(0, 50)) + list(range(60, 100)):
+            u = (splitmix64((base + p) & M64) >> 40) * (1.0 / 16777216.0)
+            w[m, p] = np.float32(0.1 * u - 0.05)
+    return w
+
+
+def split_sizes(n, test_split=0.2, validation_split=0.2):
+    """The notebook's int() arithmetic: n_fit = int((1 - test_split) n) samples are fitted, of which Keras keeps
+    int(n_fit (1 - validation_split)) for training and validates on the rest.  Returns (n_train, n_val, n_test)."""
+    n_fit = int((1.0 - test_split) * n)
+    n_train = int(n_fit * (1.0 - validation_split))
+    return n_train, n_fit - n_train, n - n_fit
+
+
+def nadam_table(steps, learning_rate=1e-3, beta1=0.9, beta2=0.999, schedule_decay=0.004, first_step=0, dtype=np.float32):
+    """Per-step scalars of Nadam (TF 2.x Keras) for steps first_step .. first_step + steps - 1, in fp64 then fp32: with t = step + 1,
+    mu_t = beta1 (1 - 0.5 * 0.96^(decay t)), m_sched = prod mu_1..t;  [lr (1 - mu_t) / (1 - m_sched),  lr mu_t+1 / (1 - m_sched mu_t+1),
+    1 - beta2^t].  The trainer takes them in fp32 (dtype)."""
+    t_all = np.arange(1, first_step + steps + 1, dtype=np.float64)
+    mu = beta1 * (1.0 - 0.5 * 0.96 ** (schedule_decay * t_all))
+    mu_next = beta1 * (1.0 - 0.5 * 0.96 ** (schedule_decay * (t_all + 1.0)))
+    sched = np.cumprod(mu)
+    sl = slice(first_step, first_step + steps)
+    tab = np.stack([learning_rate * (1.0 - mu[sl]) / (1.0 - sched[sl]),
+                    learning_rate * mu_next[sl] / (1.0 - sched[sl] * mu_next[sl]),
+                    1.0 - beta2 ** t_all[sl]], axis=1)
+    return np.ascontiguousarray(tab, dtype=dtype)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# data and arguments (host checks: they run before anything reaches the device)
+def read_samples(sample_files):
+    """Concatenates the files DataGenerator writes (CDF-5: inputs (nsamples, 5, 2), outputs (nsamples, 4) fp32) in the order given, through
+    modules._NcFile.  Returns inputs (n, 5) = slot 0 of the stencil (the single-cell model), outputs (n, 4), and the grid metadata."""
+    from .modules import _NcFile
+    if isinstance(sample_files, (str, os.PathLike)):
+        sample_files = [sample_files]
+    if not sample_files:
+        raise SurrogateTrainError("no sample files given")
+    ins, outs, meta = [], [], None
+    for path in sample_files:
+        nc = _NcFile(os.fspath(path), False)
+        try:
+            i3, o2 = nc.get("inputs"), nc.get("outputs")
+            m = {k: float(nc.get(k)) for k in ("time_step_size", "dx", "dy", "dz")}
+        finally:
+            nc.close()
+        if i3.ndim != 3 or i3.shape[1:] != (5, 2) or o2.ndim != 2 or o2.shape[1] != 4 or o2.shape[0] != i3.shape[0]:
+            raise SurrogateTrainError("%s: expected inputs (nsamples, 5, 2) and outputs (nsamples, 4)" % path)
+        if meta is None:
+            meta = m
+        elif m["time_step_size"] != meta["time_step_size"]:
+            raise SurrogateTrainError("%s: time_step_size %r differs from %r of %s; the Kessler outputs depend on dt, so files of "
+                                      "different time steps cannot be trained together" % (path, m["time_step_size"],
+                                                                                          meta["time_step_size"], sample_files[0]))
+        ins.append(np.ascontiguousarray(i3[:, :, 0]))
+        outs.append(o2)
+    inputs, outputs = np.concatenate(ins).astype(np.float32), np.concatenate(outs).astype(np.float32)
+    meta["files"] = [os.fspath(p) for p in sample_files]
+    return inputs, outputs, meta
+
+
+def data_scaling(inputs, outputs):
+    """Refuses unusable data and returns the min-max tables scl_in (5, 2), scl_out (4, 2) (fp64 arrays holding the fp32 extremes)."""
+    if inputs.shape[0] == 0:
+        raise SurrogateTrainError("the sample files hold zero samples")
+    for arr, what in ((inputs, "inputs"), (outputs, "outputs")):
+        bad = ~np.isfinite(arr)
+        if bad.any():
+            raise SurrogateTrainError("%d non-finite values in the %s (first at sample %d)" % (int(bad.sum()), what, int(np.argwhere(bad)[0][0])))
+    tabs = []
+    for arr, names, what in ((inputs, IN_NAMES, "input"), (outputs, OUT_NAMES, "output")):
+        lo, hi = arr.min(axis=0), arr.max(axis=0)
+        for v in range(arr.shape[1]):
+            if not hi[v] > lo[v]:
+                raise SurrogateTrainError("%s variable %d (%s) is constant (min = max = %r): its scaling (x - min) / (max - min) would "
+                                          "divide by zero" % (what, v, names[v], float(lo[v])))
+        tabs.append(np.ascontiguousarray(np.stack([lo, hi], axis=1).astype(np.float64)))
+    return tabs[0], tabs[1]
+
+
+def check_arguments(n, epochs, batch_size, test_split, validation_split, models):
+    if not (isinstance(batch_size, (int, np.integer)) and 1 <= batch_size <= MAX_BATCH):
+        raise SurrogateTrainError("batch_size must be an integer in [1, %d], got %r" % (MAX_BATCH, batch_size))
+    if not (isinstance(epochs, (int, np.integer)) and epochs >= 1):
+        raise SurrogateTrainError("epochs must be an integer >= 1, got %r" % (epochs,))
+    for name, v in (("test_split", test_split), ("validation_split", validation_split)):
+        if not (0.0 < float(v) < 1.0):
+            raise SurrogateTrainError("%s must be in (0, 1), got %r" % (name, v))
+    if not (isinstance(models, (int, np.integer)) and 1 <= models <= MAX_MODELS):
+        raise SurrogateTrainError("models must be an integer in [1, %d], got %r" % (MAX_MODELS, models))
+    n_train, n_val, n_test = split_sizes(n, test_split, validation_split)
+    for name, k in (("training", n_train), ("validation", n_val), ("test", n_test)):
+        if k < 1:
+            raise SurrogateTrainError("the %s set would be empty (%d samples, test_split %r, validation_split %r)" % (name, n, test_split,
+                                                                                                                  validation_split))
+    return n_train, n_val, n_test
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# output files
+def _fmt(v):
+    return repr(float(v))                # shortest text that reads back to the same double (= the fp32 value)
+
+
+def write_outputs(out_dir, weights, scl_in, scl_out, history):
+    """weights.txt (104 values, the layout of data/kessler_surrogate_weights.txt), input_scaling.txt / output_scaling.txt (`min max` rows)
+    and history.json; returns the three paths inference_ponni takes (keras_weights_txt, nn_input_scaling, nn_output_scaling)."""
+    os.makedirs(out_dir, exist_ok=True)
+    w = np.asarray(weights, dtype=np.float32).ravel()
+    paths = [os.path.join(out_dir, f) for f in ("weights.txt", "input_scaling.txt", "output_scaling.txt")]
+    with open(paths[0], "w") as f:
+        for title, a, b in (("dense_6 kernel (5,10) row-major", 0, 50), ("dense_6 bias (10)", 50, 60), ("dense_7 kernel (10,4) row-major", 60, 100),
+                            ("dense_7 bias (4)", 100, 104)):
+            f.write("# %s\n" % title)
+            f.writelines(_fmt(x) + "\n" for x in w[a:b])
+    for path, tab in ((paths[1], scl_in), (paths[2], scl_out)):
+        with open(path, "w") as f:
+            f.writelines("%s %s\n" % (_fmt(lo), _fmt(hi)) for lo, hi in np.asarray(tab))
+    with open(os.path.join(out_dir, "history.json"), "w") as f:
+        json.dump(history, f, indent=1)
+    return paths
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the device side
+_LAYERS = ((0, 5, 10, 0.0, 0), (1, 10, 10, 0.0, 50), (2, 10, 10, 0.1, 0), (0, 10, 4, 0.0, 60), (1, 4, 4, 0.0, 100))
+
+
+class Trainer:
+    """The device state of one training run: the three scaled sets, K models' parameters and moments, the Nadam table.  epoch() is one
+    training launch plus the validation pass, with one host synchronisation (the copy of the weights and sums)."""
+
+    def __init__(self, raw_in, raw_out, scl_in, scl_out, n_split, seed=0, split_seed=None, models=1, batch_size=1024, epochs=10,
+                 learning_rate=1e-3):
+        import torch
+        from . import capi
+        self.torch, self.L = torch, capi.lib()
+        self.device = raw_in.device
+        self.n_train, self.n_val, self.n_test = n_split
+        self.K, self.B, self.seed = int(models), int(batch_size), int(seed)
+        self.split_seed = self.seed if split_seed is None else int(split_seed)
+        self.steps = (self.n_train + self.B - 1) // self.B
+        dev, f32 = self.device, torch.float32
+        self.sets = {k: (torch.empty((5, n), dtype=f32, device=dev), torch.empty((4, n), dtype=f32, device=dev))
+                     for k, n in (("train", self.n_train), ("val", self.n_val), ("test", self.n_test))}
+        dp = C.POINTER(C.c_double)
+        self.scl_in, self.scl_out = np.ascontiguousarray(scl_in, np.float64), np.ascontiguousarray(scl_out, np.float64)
+        (tx, ty), (vx, vy), (sx, sy) = self.sets["train"], self.sets["val"], self.sets["test"]
+        with torch.cuda.device(dev):
+            capi.check(self.L.mw_surrogate_prepare(raw_in.shape[0], self._p(raw_in), self._p(raw_out), self.scl_in.ctypes.data_as(dp),
+                                                   self.scl_out.ctypes.data_as(dp), self.split_seed & M64, self.n_train, self.n_val,
+                                                   *[self._p(t) for t in (tx, ty, vx, vy, sx, sy)], self._stream()))
+        # ONE device buffer for what the host reads each epoch: parameters (K, 104) fp32 | training sums (K, 2) fp64 | validation sums (K, 24)
+        self.buf = torch.zeros(self.K * (104 * 4 + 2 * 8 + 24 * 8), dtype=torch.uint8, device=dev)
+        self.params = self.buf[:self.K * 416].view(f32).view(self.K, 104)
+        self.tstats = self.buf[self.K * 416:self.K * 432].view(torch.float64).view(self.K, 2)
+        self.vstats = self.buf[self.K * 432:].view(torch.float64).view(self.K, 24)
+        self.params.copy_(torch.from_numpy(initial_weights(self.seed, self.K)))
+        self.m1 = torch.zeros((self.K, 104), dtype=f32, device=dev)
+        self.m2 = torch.zeros((self.K, 104), dtype=f32, device=dev)
+        self.lr = float(learning_rate)
+        self.table = torch.from_numpy(nadam_table(self.steps * int(epochs), self.lr, NADAM["beta1"], NADAM["beta2"],
+                                                  NADAM["schedule_decay"])).to(dev)
+        # validation predictions: groups of models whose (4, n_val) outputs fit in 1 GiB
+        self.group = max(1, min(self.K, (1 << 30) // (16 * self.n_val)))
+        self.pred = torch.empty(self.group * 4 * max(self.n_val, self.n_test), dtype=f32, device=dev)
+        self.ws = torch.empty(int(self.L.mw_surrogate_errors_workspace_bytes(self.group)), dtype=torch.uint8, device=dev)
+        self.test_out = torch.empty(24, dtype=torch.float64, device=dev)
+        self.epoch_no = 0
+
+    def _p(self, t):
+        return C.c_void_p(t.data_ptr())
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _predict(self, w104, x, out):
+        from .modules import _PonniLayer
+        from .capi import check
+        lay = (_PonniLayer * 5)(*[_PonniLayer(*r) for r in _LAYERS])
+        w = np.ascontiguousarray(w104, dtype=np.float32)
+        check(self.L.mw_ponni_forward(C.cast(lay, C.c_void_p), 5, w.ctypes.data_as(C.POINTER(C.c_float)), 104, x.shape[1], self._p(x),
+                                      self._p(out), self._stream()))
+
+    def _errors(self, n, nsets, pred, y, out_ptr):
+        from .capi import check
+        check(self.L.mw_surrogate_errors(n, nsets, self._p(pred), self._p(y), self._p(self.ws), out_ptr, self._stream()))
+
+    def validate(self, weights):
+        """Launches the validation pass of every model (weights: HOST (K, 104)); its sums land in vstats (read at the next copy)."""
+        vx, vy = self.sets["val"]
+        from .capi import check
+        with self.torch.cuda.device(self.device):
+            check(self.L.mw_mlp_set_strict(0))
+            for g0 in range(0, self.K, self.group):
+                ng = min(self.group, self.K - g0)
+                pred = self.pred[:ng * 4 * self.n_val].view(ng, 4, self.n_val)
+                for j in range(ng):
+                    self._predict(weights[g0 + j], vx, pred[j])
+                self._errors(self.n_val, ng, pred, vy, C.c_void_p(self.vstats.data_ptr() + g0 * 24 * 8))
+
+    def epoch(self):
+        """One training launch, ONE host synchronisation (a single copy of weights and sums), the validation launches.  Returns the host
+        copy: weights (K, 104), this epoch's training sums (K, 2) and the PREVIOUS epoch's validation sums (K, 24)."""
+        from .capi import check
+        tx, ty = self.sets["train"]
+        with self.torch.cuda.device(self.device):
+            check(self.L.mw_surrogate_train_epoch(self.K, self._p(tx), self._p(ty), self.n_train, self.B, self.epoch_no, self.seed & M64,
+                                                  self._p(self.params), self._p(self.m1), self._p(self.m2),
+                                                  C.c_void_p(self.table.data_ptr() + self.epoch_no * self.steps * 12), NADAM["beta1"],
+                                                  NADAM["beta2"], NADAM["eps"], self._p(self.tstats), self._stream()))
+        host = self._host()
+        self.validate(host[0])
+        self.epoch_no += 1
+        return host
+
+    def _host(self):
+        b = self.buf.cpu().numpy()
+        K = self.K
+        return (b[:K * 416].view(np.float32).reshape(K, 104).copy(), b[K * 416:K * 432].view(np.float64).reshape(K, 2).copy(),
+                b[K * 432:].view(np.float64).reshape(K, 24).copy())
+
+    def finish(self):
+        """The last epoch's validation sums (one more copy)."""
+        return self._host()
+
+    def test_errors(self, w104):
+        sx, sy = self.sets["test"]
+        pred = self.pred[:4 * self.n_test].view(4, self.n_test)
+        with self.torch.cuda.device(self.device):
+            self._predict(w104, sx, pred)
+            self._errors(self.n_test, 1, pred, sy, self._p(self.test_out))
+        return self.test_out.cpu().numpy().reshape(4, 6)
+
+
+def _metrics(s):
+    """The notebook's test cell from the error sums of one set (4 outputs x [sum d^2, sum |d|, sum d, sum |o|, max |d|, max |o|])."""
+    s = np.asarray(s, dtype=np.float64).reshape(4, 6)
+    return {"max_relative_error": (s[:, 4] / s[:, 5]).tolist(), "mean_relative_error": (s[:, 1] / s[:, 3]).tolist(),
+            "mean_relative_bias": (s[:, 2] / s[:, 3]).tolist()}
+
+
+def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test_split=0.2, validation_split=0.2, learning_rate=1e-3,
+                    seed=0, models=1, device="cuda:0", split_seed=None, verbose=False):
+    """Trains `models` surrogates (seeds seed .. seed + models - 1; the pre-shuffle / split uses split_seed, default seed) on the samples of
+    `sample_files` and returns a dict: per-model `history` (Keras' loss, mean_absolute_error, val_loss, val_mean_absolute_error per
+    epoch), `weights` (models, 104) fp32, `best_model` (lowest final val_loss, ties to the lowest index), `test_metrics` of the best model
+    (the notebook's three, scaled space, per output), the scaling tables, the data's time_step_size / dx / dy / dz and the seeds.
+    out_dir: also writes the best model's weights.txt, input_scaling.txt, output_scaling.txt and history.json there."""
+    inputs, outputs, meta = read_samples(sample_files)
+    scl_in, scl_out = data_scaling(inputs, outputs)
+    n = inputs.shape[0]
+    n_split = check_arguments(n, epochs, batch_size, test_split, validation_split, models)
+    import torch
+    dev = torch.device(device)
+    raw_in = torch.from_numpy(inputs).to(dev)
+    raw_out = torch.from_numpy(outputs).to(dev)
+    tr = Trainer(raw_in, raw_out, scl_in, scl_out, n_split, seed, split_seed, models, batch_size, epochs, learning_rate)
+    del raw_in, raw_out
+    K, (n_train, n_val, n_test) = int(models), n_split
+    hist = [{"loss": [], "mean_absolute_error": [], "val_loss": [], "val_mean_absolute_error": []} for _ in range(K)]
+    secs = []
+
+    def add_val(vs):
+        for m in range(K):
+            s = vs[m].reshape(4, 6)
+            hist[m]["val_loss"].append(float(s[:, 0].sum() / (4 * n_val)))
+            hist[m]["val_mean_absolute_error"].append(float(s[:, 1].sum() / (4 * n_val)))
+
+    def report(e):
+        if not verbose:
+            return
+        print("Epoch %d/%d" % (e + 1, epochs))
+        for m in range(K):
+            h = hist[m]
+            print("%s%d/%d - %.3fs - loss: %.4e - mean_absolute_error: %.4e - val_loss: %.4e - val_mean_absolute_error: %.4e"
+                  % ("model %d: " % m if K > 1 else "", tr.steps, tr.steps, secs[e], h["loss"][e], h["mean_absolute_error"][e],
+                     h["val_loss"][e], h["val_mean_absolute_error"][e]), flush=True)
+
+    t0 = time.perf_counter()
+    for e in range(int(epochs)):
+        w, ts, vs = tr.epoch()
+        secs.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        for m in range(K):
+            hist[m]["loss"].append(float(ts[m, 0] / (4 * n_train)))
+            hist[m]["mean_absolute_error"].append(float(ts[m, 1] / (4 * n_train)))
+        if e > 0:
+            add_val(vs)
+            report(e - 1)
+    w, _, vs = tr.finish()
+    add_val(vs)
+    report(int(epochs) - 1)
+    final = np.array([h["val_loss"][-1] for h in hist])
+    best = int(np.argmin(final))                                        # first minimum: ties go to the lowest index
+    tst = tr.test_errors(w[best])
+    metrics = _metrics(tst)
+    metrics["test_loss"] = float(tst[:, 0].sum() / (4 * n_test))
+    seeds = [int(seed) + m for m in range(K)]
+    result = {"history": hist, "weights": w, "best_model": best, "test_metrics": metrics, "input_scaling": scl_in, "output_scaling": scl_out,
+              "seeds": seeds, "split_seed": tr.split_seed, "n_train": n_train, "n_val": n_val, "n_test": n_test, "epoch_seconds": secs,
+              "batch_size": int(batch_size), "epochs": int(epochs), "learning_rate": float(learning_rate)}
+    result.update({k: meta[k] for k in ("time_step_size", "dx", "dy", "dz", "files")})
+    if verbose:
+        print("Max relative errors:  ", metrics["max_relative_error"])
+        print("Mean relative errors: ", metrics["mean_relative_error"])
+        print("Mean relative bias:   ", metrics["mean_relative_bias"], flush=True)
+    if out_dir is not None:
+        js = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in result.items() if k != "weights"}
+        js["best_weights"] = w[best].astype(np.float64).tolist()
+        result["files_written"] = write_outputs(out_dir, w[best], scl_in, scl_out, js)
+    return result
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m miniweatherml_amd.surrogate_train",
+                                 description="Train the Kessler surrogate (5 -> 10 -> 4) on DataGenerator sample files, on the GPU.")
+    ap.add_argument("files", nargs="+", help="sample files written by generate_micro_data (concatenated in this order)")
+    ap.add_argument("--out", required=True, help="directory for weights.txt, input_scaling.txt, output_scaling.txt, history.json")
+    ap.add_argument("--epochs", type=int, default=10)
+    ap.add_argument("--batch-size", type=int, default=1024)
+    ap.add_argument("--test-split", type=float, default=0.2)
+    ap.add_argument("--validation-split", type=float, default=0.2)
+    ap.add_argument("--learning-rate", type=float, default=1e-3)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--split-seed", type=int, default=None, help="seed of the pre-shuffle (default: --seed)")
+    ap.add_argument("--models", type=int, default=1, help="train seeds seed .. seed+K-1 at once and keep the best (lowest val_loss)")
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    try:
+        r = train_surrogate(a.files, a.out, a.epochs, a.batch_size, a.test_split, a.validation_split, a.learning_rate, a.seed, a.models,
+                            a.device, a.split_seed, verbose=True)
+    except SurrogateTrainError as e:
+        print("ERROR: %s" % e, file=sys.stderr)
+        return 2
+    print("best model %d (seed %d); wrote %s" % (r["best_model"], r["seeds"][r["best_model"]], ", ".join(r["files_written"])))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
