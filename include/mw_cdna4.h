@@ -341,11 +341,27 @@ int  mw_mlp_forward(long long ncells, const double *temp, const double *rho_d, c
  * microphysics_kessler_ponni.h:103-110); 0 (default): the MFMA kernels (the same products summed in the matrix cores' order). */
 int  mw_mlp_set_strict(int strict);
 
+/* The STENCIL model 9 -> 10 -> 4 on the coupler's fields: the network the sample files are written for.  Features 0..4 are the cell's
+ * (temp, rho_d, rho_v, rho_c, rho_r); features 5..8 are (temp, rho_v, rho_c, rho_r) of level min(nz - 1, k + 1) of the same column and
+ * ensemble member -- DataGenerator::generate_samples_stencil's inputs(:, 0:5, 0) and inputs(:, 0:4, 1),
+ * experiments/supercell_kessler_surrogate/custom_modules/generate_micro_surrogate_data.h:139-156; the layers, the scaling and the
+ * un-scaling + clip are mw_mlp_forward's (microphysics_kessler_ponni.h:103-110, :182-186, :198-201).  Fields: DEVICE fp64, level-major
+ * (cell (k, col) at k * ncol + col, ncol = ny * nx * nens).  W1 (9,10), b1 (10), W2 (10,4), b2 (4): HOST fp32, Keras layout; scl_in
+ * (9,2), scl_out (4,2): HOST fp64 [min,max] rows.  The four outputs must not overlap any input (level k + 1 is an input of level k):
+ * overlap is an error.  Honours mw_mlp_set_strict: 0 = MFMA tiles, a wave sweeps 16 columns top-down and carries the level above in
+ * registers, every input read once plus one level per z chunk; 1 = thread per cell, index order, no contraction. */
+int  mw_mlp_stencil_forward(int nz, long long ncol, const double *temp, const double *rho_d, const double *rho_v, const double *rho_c,
+                            const double *rho_r, const float *W1, const float *b1, const float *W2, const float *b2,
+                            const double *scl_in, const double *scl_out, double *temp_out, double *rho_v_out, double *rho_c_out,
+                            double *rho_r_out, void *stream);
+/* The number of levels of one z chunk that mw_mlp_stencil_forward's MFMA kernel uses for (nz, ncol) (nz: a single chunk). */
+int  mw_mlp_stencil_chunk(int nz, long long ncol);
+
 /* ponni's own surface: ponni::Inference<...>::forward_batch_parallel(float2d in(num_in, batch)) -> float2d
  * (num_out, batch), experiments/supercell_kessler_surrogate/custom_modules/microphysics_kessler_ponni.h:40-45,103-110,189, for a stack
  * of ponni::Matvec<float> (kind 0: weights (n_in, n_out) in Keras order, y = x W), ponni::Bias<float> (kind 1) and ponni::Relu<float>(n,
  * negative_slope) (kind 2) layers.  layers / params: HOST memory (params = all weights back to back, `offset` in floats); in / out:
- * DEVICE fp32, batch fastest.  The surrogate's stack (5 -> 10 -> 4) runs on the MFMA tiles, any other stack of up to 10 layers, widths
+ * DEVICE fp32, batch fastest.  The surrogate's stacks (5 -> 10 -> 4 and 9 -> 10 -> 4) run on the MFMA tiles, any other stack of up to 10 layers, widths
  * <= 32 and 960 parameters on a thread-per-element kernel; a size mismatch between consecutive layers is an error (Inference::validate). */
 typedef struct { int kind, n_in, n_out; float negative_slope; int offset; } mw_ponni_layer_t;
 int  mw_ponni_forward(const mw_ponni_layer_t *layers, int nlayers, const float *params, int nparams, long long batch,
@@ -448,6 +464,16 @@ int  mw_surrogate_batch_grad(const float *params, const float *x, const float *y
 /* Error sums of `nsets` predictions pred (nsets, 4, n) against y (4, n), all DEVICE fp32 -- model.evaluate / the notebook's test metrics
  * cell.  out (nsets, 24) fp64 DEVICE: per output v at [6 v ...]: sum (y - p)^2, sum |y - p|, sum (y - p), sum |y|, max |y - p|, max |y|.
  * Fixed reduction order (run-to-run identical).  workspace: DEVICE, mw_surrogate_errors_workspace_bytes(nsets). */
+/* The same three for n_in = 5 (the functions above) or n_in = 9, the stencil model: raw_in (n, 9) in the feature order of
+ * mw_mlp_stencil_forward, x (9, n), scl_in (9, 2), parameters and gradient (144): W1 (9,10), b1 (10), W2 (10,4), b2 (4). */
+int  mw_surrogate_prepare_v2(int n_in, long long n, const float *raw_in, const float *raw_out, const double *scl_in, const double *scl_out,
+                             unsigned long long seed, long long n_train, long long n_val, float *train_x, float *train_y, float *val_x,
+                             float *val_y, float *test_x, float *test_y, void *stream);
+int  mw_surrogate_train_epoch_v2(int n_in, int models, const float *x, const float *y, long long n, int batch, int epoch,
+                                 unsigned long long seed, float *params, float *m1, float *m2, const float *table, float beta1, float beta2,
+                                 float eps, double *stats, void *stream);
+int  mw_surrogate_batch_grad_v2(int n_in, const float *params, const float *x, const float *y, int batch, float *grad, float *loss,
+                                void *stream);
 long long mw_surrogate_errors_workspace_bytes(int nsets);
 int  mw_surrogate_errors(long long n, int nsets, const float *pred, const float *y, void *workspace, double *out, void *stream);
 

@@ -141,10 +141,18 @@ SYMBOLS = {
     "mw_surrogate_train_epoch": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_ulonglong] + [C.c_void_p] * 4 +
                                  [C.c_float] * 3 + [C.c_void_p, C.c_void_p]),
     "mw_surrogate_batch_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mw_surrogate_prepare_v2": (C.c_int, [C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_ulonglong,
+                                          C.c_longlong, C.c_longlong] + [C.c_void_p] * 6 + [C.c_void_p]),
+    "mw_surrogate_train_epoch_v2": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_ulonglong] +
+                                    [C.c_void_p] * 4 + [C.c_float] * 3 + [C.c_void_p, C.c_void_p]),
+    "mw_surrogate_batch_grad_v2": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mw_surrogate_errors_workspace_bytes": (C.c_longlong, [C.c_int]),
     "mw_surrogate_errors": (C.c_int, [C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mw_validate_f64": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]),
     "mw_validate_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]),
+    "mw_mlp_stencil_forward": (C.c_int, [C.c_int, C.c_longlong] + [C.c_void_p] * 5 + [C.POINTER(C.c_float)] * 4 +
+                               [C.POINTER(C.c_double)] * 2 + [C.c_void_p] * 4 + [C.c_void_p]),
+    "mw_mlp_stencil_chunk": (C.c_int, [C.c_int, C.c_longlong]),
     "mw_mlp_forward": (C.c_int, [C.c_longlong] + [C.c_void_p] * 5 + [C.POINTER(C.c_float)] * 4 +
                        [C.POINTER(C.c_double)] * 2 + [C.c_void_p] * 4 + [C.c_void_p]),
 }

@@ -26,7 +26,7 @@ namespace mw {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct MlpP {
-  float a1[2][64];      // layer-1 A operand per MFMA m, per lane
+  float a1[3][64];      // layer-1 A operand per MFMA m, per lane (m = 2: only the 9-input stack's feature 8)
   float c1[4][4];       // layer-1 C init (bias) [g][reg]
   float a2[3][64];      // layer-2 A operand per MFMA j, per lane
   float c2[4];          // layer-2 C init for reg 0 of group g (bias of output g)
@@ -146,35 +146,38 @@ __global__ __launch_bounds__(256) void k_mlp_x2(MlpP P, long long ncells, const 
 // ponni::Inference::forward_batch_parallel for the surrogate's stack on fp32 arrays in ponni's own layout -- in (5, batch), out (4, batch),
 // batch fastest (microphysics_kessler_ponni.h:176-189: ponni_in(feature, iglob)) -- with the same MFMA tiles as k_mlp: lane group g
 // reads feature g's row (64 contiguous bytes per group and tile), output n leaves from group n.  The activation slope is an argument
-// (ponni::Relu<float>(n, negative_slope), :105).
-template <int TILES>
+// (ponni::Relu<float>(n, negative_slope), :105).  NM1 = 3: the 9 -> 10 -> 4 stack of the stencil model, K = 9 padded to 12 (group 0 also
+// reads feature 8; one more layer-1 MFMA, everything else the same).
+template <int TILES, int NM1>
 __global__ __launch_bounds__(256) void k_mlp_f32(MlpP P, float slope, long long batch, const float *__restrict__ in, float *__restrict__ out) {
 #pragma clang fp contract(off)
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4, cidx = lane & 15;
   const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
   const long long nwaves = ((long long)gridDim.x * 256) >> 6;
-  const float *in_g = in + (long long)g * batch, *in_4 = in + 4 * batch;
+  const float *in_g = in + (long long)g * batch, *in_4 = in + (NM1 == 3 ? 4 + g : 4) * batch, *in_8 = in + 8 * batch;
   float *out_g = out + (long long)g * batch;
-  const float a10 = P.a1[0][lane], a11 = P.a1[1][lane];
+  const float a10 = P.a1[0][lane], a11 = P.a1[1][lane], a12 = P.a1[2][lane];
   const float a20 = P.a2[0][lane], a21 = P.a2[1][lane], a22 = P.a2[2][lane];
   const f32x4 c1 = {P.c1[g][0], P.c1[g][1], P.c1[g][2], P.c1[g][3]};
   const f32x4 c2 = {P.c2[g], 0.f, 0.f, 0.f};
   const long long ntiles = (batch + 15) / 16;
   for (long long t0 = wave * TILES; t0 < ntiles; t0 += nwaves * TILES) {
-    float x0[TILES], x4[TILES];
+    float x0[TILES], x4[TILES], x8[TILES];
 #pragma unroll
     for (int u = 0; u < TILES; u++) {
       const long long cell = (t0 + u) * 16 + cidx;
       const bool ok = cell < batch;
       x0[u] = ok ? in_g[cell] : 0.f;
-      x4[u] = (ok && g == 0) ? in_4[cell] : 0.f;
+      x4[u] = (ok && (NM1 == 3 || g == 0)) ? in_4[cell] : 0.f;
+      if (NM1 == 3) x8[u] = (ok && g == 0) ? in_8[cell] : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < TILES; u++) {
       const long long cell = (t0 + u) * 16 + cidx;
       f32x4 d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a10, x0[u], c1, 0, 0, 0);
       d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a11, x4[u], d1, 0, 0, 0);
+      if (NM1 == 3) d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a12, x8[u], d1, 0, 0, 0);
       const float h0 = d1[0] > 0.f ? d1[0] : slope * d1[0], h1 = d1[1] > 0.f ? d1[1] : slope * d1[1], h2 = d1[2] > 0.f ? d1[2] : slope * d1[2];
       f32x4 d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a20, h0, c2, 0, 0, 0);
       d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a21, h1, d2, 0, 0, 0);
@@ -250,14 +253,14 @@ __global__ __launch_bounds__(256) void k_mlp_strict(MlpRef P, long long n, const
   rho_r_out[c] = fmax(0.0, y[3] * P.out_rng[3] + P.out_min[3]);
 }
 // The MFMA operand images of the 5 -> 10 -> 4 stack (see the header of this file): A operands per lane, C initialisers = the biases.
-static void build_operand_images(MlpP &P, const float *W1, const float *b1, const float *W2, const float *b2) {
+static void build_operand_images(MlpP &P, const float *W1, const float *b1, const float *W2, const float *b2, int n_in = 5) {
   memset(&P, 0, sizeof(P));
   auto rho = [](int u) { return (u / 3) * 4 + (u % 3); };      // hidden unit u -> D1 row with row % 4 < 3
   for (int lane = 0; lane < 64; lane++) {
     int o = lane & 15, g = lane >> 4;
     int u = -1;
     for (int uu = 0; uu < 10; uu++) if (rho(uu) == o) u = uu;
-    for (int m = 0; m < 2; m++) { int in = 4 * m + g; P.a1[m][lane] = (u >= 0 && in < 5) ? W1[in * 10 + u] : 0.f; }
+    for (int m = 0; m < 3; m++) { int in = 4 * m + g; P.a1[m][lane] = (u >= 0 && in < n_in) ? W1[in * 10 + u] : 0.f; }
     int n = (o % 4 == 0) ? o / 4 : -1;                          // output n lives at row 4n
     for (int j = 0; j < 3; j++) {
       int row = 4 * g + j, uk = -1;                             // k-slot g of MFMA j is hidden row 4g + j
@@ -328,7 +331,7 @@ extern "C" int mw_mlp_forward(long long ncells, const double *temp, const double
 // ponni::Inference<...>::forward_batch_parallel (microphysics_kessler_ponni.h:189) for a stack of ponni layers on fp32 device arrays in
 // ponni's layout: in (n_in of the first layer, batch), out (n_out of the last, batch), batch fastest.  layers / params: HOST memory
 // (params = the layers' weights back to back: a Matvec's (n_in, n_out) kernel in Keras order, a Bias's vector; offsets in floats).
-// The surrogate's stack Matvec(5,10), Bias(10), Relu(10), Matvec(10,4), Bias(4) runs on the MFMA tiles; any other stack that fits
+// The surrogate's stacks Matvec(5 or 9,10), Bias(10), Relu(10), Matvec(10,4), Bias(4) run on the MFMA tiles; any other stack that fits
 // the limits (MW_PONNI_MAX_*), and every stack under mw_mlp_set_strict(1), on the thread-per-element kernel (index order, no contraction).
 extern "C" int mw_ponni_forward(const mw_ponni_layer_t *layers, int nlayers, const float *params, int nparams, long long batch,
                                 const float *in, float *out, void *stream) {
@@ -350,15 +353,17 @@ extern "C" int mw_ponni_forward(const mw_ponni_layer_t *layers, int nlayers, con
     width = L.n_out;
   }
   hipStream_t st = (hipStream_t)stream;
-  const bool surrogate = nlayers == 5 && layers[0].kind == 0 && layers[0].n_in == 5 && layers[0].n_out == 10 && layers[1].kind == 1 &&
+  const int n_in = layers[0].n_in;
+  const bool surrogate = nlayers == 5 && layers[0].kind == 0 && (n_in == 5 || n_in == 9) && layers[0].n_out == 10 && layers[1].kind == 1 &&
                          layers[2].kind == 2 && layers[3].kind == 0 && layers[3].n_out == 4 && layers[4].kind == 1;
   if (surrogate && !g_mlp_strict) {
     MlpP P;
-    build_operand_images(P, params + layers[0].offset, params + layers[1].offset, params + layers[3].offset, params + layers[4].offset);
+    build_operand_images(P, params + layers[0].offset, params + layers[1].offset, params + layers[3].offset, params + layers[4].offset, n_in);
     constexpr int TILES = 4;
     long long blocks = (((batch + 15) / 16 + TILES - 1) / TILES + 3) / 4;
     blocks = std::max<long long>(1, std::min<long long>(blocks, 256 * 16));
-    hipLaunchKernelGGL(k_mlp_f32<TILES>, dim3((unsigned)blocks), dim3(256), 0, st, P, layers[2].negative_slope, batch, in, out);
+    if (n_in == 5) hipLaunchKernelGGL((k_mlp_f32<TILES, 2>), dim3((unsigned)blocks), dim3(256), 0, st, P, layers[2].negative_slope, batch, in, out);
+    else           hipLaunchKernelGGL((k_mlp_f32<TILES, 3>), dim3((unsigned)blocks), dim3(256), 0, st, P, layers[2].negative_slope, batch, in, out);
     MW_LAUNCH_CHECK();
     return 0;
   }
@@ -368,6 +373,202 @@ extern "C" int mw_ponni_forward(const mw_ponni_layer_t *layers, int nlayers, con
   for (int l = 0; l < nlayers; l++) { S.kind[l] = layers[l].kind; S.n_in[l] = layers[l].n_in; S.n_out[l] = layers[l].n_out; S.off[l] = layers[l].offset; S.slope[l] = layers[l].negative_slope; }
   memcpy(S.params, params, sizeof(float) * (size_t)nparams);
   hipLaunchKernelGGL(k_ponni_generic, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, S, batch, in, out);
+  MW_LAUNCH_CHECK();
+  return 0;
+}
+
+// =====================================================================================================
+// The STENCIL model 9 -> 10 -> 4 on the coupler's fields (level-major: cell (k, col) at k * ncol + col).  Features 0..4 are the cell's
+// (temp, rho_d, rho_v, rho_c, rho_r), features 5..8 are (temp, rho_v, rho_c, rho_r) of level min(nz - 1, k + 1) of the same column:
+// DataGenerator::generate_samples_stencil's inputs(:, :, 0) and inputs(0..3, 1) (generate_micro_surrogate_data.h:139-156).
+//
+// k_mlp_stencil: k_mlp's tiles with layer 1 as K = 9 padded to 12 (three MFMAs), one wave per (16-column tile, z chunk), the levels swept
+// TOP-DOWN so that the level-above operand is what the previous iteration loaded -- every input is read once (plus one level per chunk):
+//   MFMA 0, k-slot g : feature g of level k (group g loads field g, as in k_mlp)
+//   MFMA 1, k-slot g : the SAME lane's value of level k + 1, scaled as feature 5 / - / 6 / 7 (group 1 holds rho_d, which has no
+//                      level-above feature: its A operand is zero) -- carried in a register, no lane movement
+//   MFMA 2           : rho_r of levels k and k + 1.  Group (k & 1) loads rho_r of level k, so group 0 always holds the last even level
+//                      and group 1 the last odd one; the A operand (W1 rows 4 and 8) swaps its two groups with the parity of k.
+// Layer 2, un-scaling and clip are k_mlp's.  The outputs must not alias the inputs (level k + 1 is an input of level k, and a chunk's
+// first level-above is computed by another wave).
+// =====================================================================================================
+namespace mw {
+
+struct StencilP {
+  float a1[4][64];      // layer-1 A operands: [0] cell features 0..3, [1] level-above features by group, [2] / [3] rho_r rows for even / odd k
+  float c1[4][4];
+  float a2[3][64];
+  float c2[4];
+  double in_min[9], in_rng[9];
+  double out_min[4], out_rng[4];
+};
+
+template <int U>
+__global__ __launch_bounds__(256) void k_mlp_stencil(StencilP P, int nz, long long ncol, int zc, int nchunks,
+                                                     const double *__restrict__ temp, const double *__restrict__ rho_d,
+                                                     const double *__restrict__ rho_v, const double *__restrict__ rho_c,
+                                                     const double *__restrict__ rho_r, double *__restrict__ o_temp,
+                                                     double *__restrict__ o_rv, double *__restrict__ o_rc, double *__restrict__ o_rr) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const int g = lane >> 4, cidx = lane & 15;
+  const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
+  const long long ntiles = (ncol + 15) / 16;
+  if (wave >= ntiles * nchunks) return;                                   // (wave-uniform)
+  const int chunk = (int)(wave % nchunks);
+  const long long col = (wave / nchunks) * 16 + cidx;
+  const bool ok = col < ncol;
+  const int k_lo = chunk * zc, k_hi = min(nz, k_lo + zc) - 1, k_top = min(nz - 1, k_hi + 1);
+  const double *in_g = (g == 0) ? temp : (g == 1) ? rho_d : (g == 2) ? rho_v : rho_c;
+  double *out_g = (g == 0) ? o_temp : (g == 1) ? o_rv : (g == 2) ? o_rc : o_rr;
+  const int fa = (g == 0) ? 5 : (g == 2) ? 6 : (g == 3) ? 7 : 1;          // the feature this lane's field is one level down (group 1: none)
+  const double imin = P.in_min[g], irng = 1.0 / P.in_rng[g], amin = P.in_min[fa], arng = 1.0 / P.in_rng[fa];
+  const double rmin = P.in_min[4], rrng = 1.0 / P.in_rng[4], ramin = P.in_min[8], rarng = 1.0 / P.in_rng[8];
+  const double omin = P.out_min[g], orng = P.out_rng[g];
+  const float a10 = P.a1[0][lane], a11 = P.a1[1][lane], a12e = P.a1[2][lane], a12o = P.a1[3][lane];
+  const float a20 = P.a2[0][lane], a21 = P.a2[1][lane], a22 = P.a2[2][lane];
+  const f32x4 c1 = {P.c1[g][0], P.c1[g][1], P.c1[g][2], P.c1[g][3]};
+  const f32x4 c2 = {P.c2[g], 0.f, 0.f, 0.f};
+  // the level above the chunk's top (the top level itself at the model top): the one level a chunk reads twice
+  float above = 0.f, rr_s = 0.f;          // rr_s: this group's latest rho_r, scaled as feature 4 when it is level k and as feature 8 when k + 1
+  double rr_raw = rmin;
+  if (ok) {
+    above = (float)((in_g[(long long)k_top * ncol + col] - amin) * arng);
+    if (g == ((k_hi & 1) ^ 1)) rr_raw = rho_r[(long long)k_top * ncol + col];
+  }
+  for (int k0 = k_hi; k0 >= k_lo; k0 -= U) {
+    double xin[U], xrr[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int k = k0 - u;
+      const bool lv = ok && k >= k_lo;
+      xin[u] = lv ? in_g[(long long)k * ncol + col] : imin;
+      xrr[u] = (lv && g == (k & 1)) ? rho_r[(long long)k * ncol + col] : rmin;
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int k = k0 - u;
+      if (k >= k_lo) {                                                    // (wave-uniform)
+        const bool mine = g == (k & 1);                                   // this group holds rho_r of level k, the other one of level k + 1
+        if (mine) rr_raw = xrr[u];
+        const float b0 = (float)((xin[u] - imin) * irng);                 // fp64 math, stored as float (microphysics_kessler_ponni.h:182-186)
+        const float b2 = (g < 2) ? (mine ? (float)((rr_raw - rmin) * rrng) : (float)((rr_raw - ramin) * rarng)) : 0.f;
+        f32x4 d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a10, b0, c1, 0, 0, 0);
+        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a11, above, d1, 0, 0, 0);
+        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32((k & 1) ? a12o : a12e, b2, d1, 0, 0, 0);
+        above = (float)((xin[u] - amin) * arng);                          // level k is level k - 1's level above
+        const float h0 = leaky(d1[0]), h1 = leaky(d1[1]), h2 = leaky(d1[2]);
+        f32x4 d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a20, h0, c2, 0, 0, 0);
+        d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a21, h1, d2, 0, 0, 0);
+        d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a22, h2, d2, 0, 0, 0);
+        double y = (double)d2[0] * orng + omin;                           // :198-201
+        if (g != 0) y = fmax(0.0, y);
+        if (ok) out_g[(long long)k * ncol + col] = y;
+      }
+    }
+  }
+}
+
+// STRICT form: thread = cell, index order, no contraction, the quotient form of the scaling -- k_mlp_strict with nine features.
+struct StencilRef { float W1[90], b1[10], W2[40], b2[4]; double in_min[9], in_rng[9], out_min[4], out_rng[4]; };
+__global__ __launch_bounds__(256) void k_mlp_stencil_strict(StencilRef P, int nz, long long ncol, const double *__restrict__ temp,
+                                                            const double *__restrict__ rho_d, const double *__restrict__ rho_v,
+                                                            const double *__restrict__ rho_c, const double *__restrict__ rho_r,
+                                                            double *__restrict__ temp_out, double *__restrict__ rho_v_out,
+                                                            double *__restrict__ rho_c_out, double *__restrict__ rho_r_out) {
+#pragma clang fp contract(off)
+  const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (c >= (long long)nz * ncol) return;
+  const long long k = c / ncol;
+  const long long ca = (k + 1 < nz) ? c + ncol : c;                       // level min(nz - 1, k + 1), same column
+  const double in[9] = {temp[c], rho_d[c], rho_v[c], rho_c[c], rho_r[c], temp[ca], rho_v[ca], rho_c[ca], rho_r[ca]};
+  float x[9], h[10], y[4];
+#pragma unroll
+  for (int i = 0; i < 9; i++) x[i] = (float)((in[i] - P.in_min[i]) / P.in_rng[i]);
+#pragma unroll
+  for (int o = 0; o < 10; o++) {
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < 9; i++) acc += x[i] * P.W1[i * 10 + o];
+    acc = acc + P.b1[o];
+    h[o] = acc > 0.f ? acc : 0.1f * acc;
+  }
+#pragma unroll
+  for (int o = 0; o < 4; o++) {
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < 10; i++) acc += h[i] * P.W2[i * 4 + o];
+    y[o] = acc + P.b2[o];
+  }
+  temp_out[c]  =           y[0] * P.out_rng[0] + P.out_min[0];
+  rho_v_out[c] = fmax(0.0, y[1] * P.out_rng[1] + P.out_min[1]);
+  rho_c_out[c] = fmax(0.0, y[2] * P.out_rng[2] + P.out_min[2]);
+  rho_r_out[c] = fmax(0.0, y[3] * P.out_rng[3] + P.out_min[3]);
+}
+
+} // namespace mw
+
+// z chunks of the production kernel: a wave owns (16 columns, zc levels).  One chunk per column unless the tiles alone leave the chip
+// short of waves; then as many chunks as bring ntiles * nchunks to STENCIL_WAVES, but never shorter than STENCIL_MIN_ZC levels (a chunk
+// re-reads one level of four fields: 4 / (9 zc) of its input).
+static constexpr long long STENCIL_WAVES = 256 * 4 * 8 * 2;      // 256 CUs x 4 SIMDs x 8 wave slots, twice over
+static constexpr int STENCIL_MIN_ZC = 8;
+extern "C" int mw_mlp_stencil_chunk(int nz, long long ncol) {
+  if (nz < 1 || ncol < 1) return 0;
+  const long long ntiles = (ncol + 15) / 16;
+  long long want = (STENCIL_WAVES + ntiles - 1) / ntiles;
+  want = std::max<long long>(1, std::min<long long>(want, (nz + STENCIL_MIN_ZC - 1) / STENCIL_MIN_ZC));
+  return (int)((nz + want - 1) / want);
+}
+
+extern "C" int mw_mlp_stencil_forward(int nz, long long ncol, const double *temp, const double *rho_d, const double *rho_v,
+                                      const double *rho_c, const double *rho_r, const float *W1, const float *b1, const float *W2,
+                                      const float *b2, const double *scl_in, const double *scl_out, double *temp_out, double *rho_v_out,
+                                      double *rho_c_out, double *rho_r_out, void *stream) {
+  if (nz < 1 || ncol < 1) MW_FAIL("mlp_stencil: nz and ncol must be >= 1");
+  if (!temp || !rho_d || !rho_v || !rho_c || !rho_r || !W1 || !b1 || !W2 || !b2 || !scl_in || !scl_out || !temp_out ||
+      !rho_v_out || !rho_c_out || !rho_r_out) MW_FAIL("mlp_stencil: null pointer");
+  const long long ncells = (long long)nz * ncol;
+  for (const double *o : {temp_out, rho_v_out, rho_c_out, rho_r_out})
+    for (const double *i : {temp, rho_d, rho_v, rho_c, rho_r})
+      if (o < i + ncells && i < o + ncells) MW_FAIL("mlp_stencil: the outputs must not overlap the inputs (level k + 1 is an input of level k)");
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  if (g_mlp_strict) {
+    StencilRef R;
+    memcpy(R.W1, W1, sizeof(R.W1)); memcpy(R.b1, b1, sizeof(R.b1)); memcpy(R.W2, W2, sizeof(R.W2)); memcpy(R.b2, b2, sizeof(R.b2));
+    for (int i = 0; i < 9; i++) { R.in_min[i] = scl_in[i * 2 + 0]; R.in_rng[i] = scl_in[i * 2 + 1] - scl_in[i * 2 + 0]; }
+    for (int i = 0; i < 4; i++) { R.out_min[i] = scl_out[i * 2 + 0]; R.out_rng[i] = scl_out[i * 2 + 1] - scl_out[i * 2 + 0]; }
+    hipLaunchKernelGGL(k_mlp_stencil_strict, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, R, nz, ncol, temp, rho_d,
+                       rho_v, rho_c, rho_r, temp_out, rho_v_out, rho_c_out, rho_r_out);
+    MW_LAUNCH_CHECK();
+    return 0;
+  }
+  StencilP P;
+  {
+    MlpP Q;                                                     // layer 2 and the biases: the single-cell images (W1 rows are placed below)
+    build_operand_images(Q, W1, b1, W2, b2, 0);
+    memset(&P, 0, sizeof(P));
+    memcpy(P.c1, Q.c1, sizeof(P.c1)); memcpy(P.a2, Q.a2, sizeof(P.a2)); memcpy(P.c2, Q.c2, sizeof(P.c2));
+    auto rho = [](int u) { return (u / 3) * 4 + (u % 3); };    // hidden unit u -> D1 row (build_operand_images)
+    const int above_of_group[4] = {5, -1, 6, 7};
+    for (int lane = 0; lane < 64; lane++) {
+      const int o = lane & 15, g = lane >> 4;
+      int u = -1;
+      for (int uu = 0; uu < 10; uu++) if (rho(uu) == o) u = uu;
+      if (u < 0) continue;
+      P.a1[0][lane] = W1[g * 10 + u];
+      P.a1[1][lane] = above_of_group[g] >= 0 ? W1[above_of_group[g] * 10 + u] : 0.f;
+      P.a1[2][lane] = g == 0 ? W1[4 * 10 + u] : g == 1 ? W1[8 * 10 + u] : 0.f;      // even k: group 0 holds level k, group 1 level k + 1
+      P.a1[3][lane] = g == 0 ? W1[8 * 10 + u] : g == 1 ? W1[4 * 10 + u] : 0.f;      // odd k: the other way round
+    }
+  }
+  for (int i = 0; i < 9; i++) { P.in_min[i] = scl_in[i * 2 + 0]; P.in_rng[i] = scl_in[i * 2 + 1] - scl_in[i * 2 + 0]; }
+  for (int i = 0; i < 4; i++) { P.out_min[i] = scl_out[i * 2 + 0]; P.out_rng[i] = scl_out[i * 2 + 1] - scl_out[i * 2 + 0]; }
+  const int zc = mw_mlp_stencil_chunk(nz, ncol), nchunks = (nz + zc - 1) / zc;
+  const long long waves = ((ncol + 15) / 16) * nchunks, blocks = (waves + 3) / 4;
+  if (blocks > 0x7fffffffll) MW_FAIL("mlp_stencil: grid too large");
+  hipLaunchKernelGGL(k_mlp_stencil<4>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, nz, ncol, zc, nchunks, temp, rho_d, rho_v,
+                     rho_c, rho_r, temp_out, rho_v_out, rho_c_out, rho_r_out);
   MW_LAUNCH_CHECK();
   return 0;
 }

@@ -15,6 +15,14 @@
 // LDS; tile entry e (= register e >> 6 of lane e & 63) belongs to thread e, which keeps that parameter and its two Nadam moments in
 // registers for the whole epoch and writes the updated weight back to LDS.  The reduction order is fixed: bit-identical run to run, and
 // a model's result does not depend on the other workgroups.
+//
+// The STENCIL model (9 -> 10 -> 4, NIN = 9): A = [x(9), 1, h(10)] is 20 rows, so the wave accumulates TWO 16x16 tiles over the same D:
+//   P = [x0..x8, 1]^T D : dW1 = rows 0-8 x cols 0-9, db1 = row 9 x cols 0-9, db2 = row 9 x cols 10-13, the two sums = row 9 x cols 14 / 15
+//   Q = [h0..h8, 0, h9]^T D : dW2 = rows 0-8 and 10 x cols 10-13 (h9 sits in row 10 so that no Q entry shares a thread with a live P entry)
+// 32 MFMAs per 64-sample chunk, 146 live entries, still one per thread: thread e owns entry e of P if that is live, else entry e of Q.
+// (A 32x32x2 tile would hold all 20 rows at once, but 16 accumulator registers per lane with 1024 entries over 256 threads breaks "entry
+// e belongs to thread e", and its 32 columns would be half empty; two 16x16 tiles cost 4 more accumulator registers and 8 KiB less LDS.)
+// The single-cell instantiation (NIN = 5) is the code above, unchanged in every operation.
 // =====================================================================================================
 #include "../../include/mw_cdna4.h"
 #include "mw_common.h"
@@ -65,31 +73,38 @@ __device__ __forceinline__ long long feistel_index(const Feistel &F, long long p
 }
 
 // ---- the batch routine (shared by the trainer and the test aid) ----
-constexpr int TPB = 256, NPAR = 104;
+constexpr int TPB = 256;
+template <int NIN> constexpr int npar() { return NIN * 10 + 10 + 40 + 4; }      // 104 | 144
 struct SetRef { const float *x, *y; long long n; };
 struct Identity { __device__ long long operator()(long long p) const { return p; } };
 struct Shuffled { Feistel F; __device__ long long operator()(long long p) const { return feistel_index(F, p); } };
-struct Sample { float v[9]; };                                          // x0..x4, t0..t3
+template <int NIN> struct Sample { float v[NIN + 4]; };                    // x0..x(NIN-1), t0..t3
 
-struct Smem {
-  float W[NPAR];                                                        // the current parameters
+template <int NIN> struct Smem;
+template <> struct Smem<5> {
+  float W[104];                                                         // the current parameters
   float A[TPB][16], D[TPB][16];                                         // one chunk's rows, wave w owns rows 64 w .. 64 w + 63
   float G[4][TPB];                                                      // the waves' gradient tiles
 };
+template <> struct Smem<9> {
+  float W[144];
+  float A[TPB][12], H[TPB][12], D[TPB][16];                             // A = [x0..x8, 1, 0, 0], H = [h0..h8, 0, h9, 0]
+  float G[4][2][TPB];                                                   // the waves' tiles P and Q
+};
 
 // sample at batch position c + threadIdx.x (zero beyond the batch)
-template <class Pos>
-__device__ __forceinline__ void fetch(const SetRef &S, const Pos &pos, long long first, int B, int c, Sample &s) {
+template <int NIN, class Pos>
+__device__ __forceinline__ void fetch(const SetRef &S, const Pos &pos, long long first, int B, int c, Sample<NIN> &s) {
   const int i = c + (int)threadIdx.x;
   const bool ok = i < B;
   const long long idx = ok ? pos(first + i) : 0;
 #pragma unroll
-  for (int f = 0; f < 5; f++) s.v[f] = ok ? S.x[f * S.n + idx] : 0.f;
+  for (int f = 0; f < NIN; f++) s.v[f] = ok ? S.x[f * S.n + idx] : 0.f;
 #pragma unroll
-  for (int o = 0; o < 4; o++) s.v[5 + o] = ok ? S.y[o * S.n + idx] : 0.f;
+  for (int o = 0; o < 4; o++) s.v[NIN + o] = ok ? S.y[o * S.n + idx] : 0.f;
 }
 
-__device__ __forceinline__ void sample_rows(const float *W, const Sample &s, bool ok, float *a, float *d) {
+__device__ __forceinline__ void sample_rows(const float *W, const Sample<5> &s, bool ok, float *a, float *d) {
   const float *W1 = W, *b1 = W + 50, *W2 = W + 60, *b2 = W + 100;
   float pre[10], h[10], r[4];
 #pragma unroll
@@ -129,6 +144,54 @@ __device__ __forceinline__ void sample_rows(const float *W, const Sample &s, boo
   for (int q = 0; q < 4; q++) { ((f32x4 *)a)[q] = A[q]; ((f32x4 *)d)[q] = D[q]; }
 }
 
+// the stencil model's rows: a = [x0..x8, 1, 0, 0], hrow = [h0..h8, 0, h9, 0] (12 floats each), d as above
+__device__ __forceinline__ void sample_rows(const float *W, const Sample<9> &s, bool ok, float *a, float *hrow, float *d) {
+  const float *W1 = W, *b1 = W + 90, *W2 = W + 100, *b2 = W + 140;
+  float pre[10], h[10], r[4];
+#pragma unroll
+  for (int u = 0; u < 10; u++) {
+    float acc = b1[u];
+#pragma unroll
+    for (int i = 0; i < 9; i++) acc = fmaf(s.v[i], W1[i * 10 + u], acc);
+    pre[u] = acc;
+    h[u] = acc > 0.f ? acc : 0.1f * acc;
+  }
+  float sq = 0.f, ab = 0.f;
+#pragma unroll
+  for (int n = 0; n < 4; n++) {
+    float acc = b2[n];
+#pragma unroll
+    for (int u = 0; u < 10; u++) acc = fmaf(h[u], W2[u * 4 + n], acc);
+    r[n] = acc - s.v[9 + n];
+    sq = fmaf(r[n], r[n], sq);
+    ab += fabsf(r[n]);
+  }
+  f32x4 A[3], H[3], D[4];
+#pragma unroll
+  for (int i = 0; i < 12; i++) {
+    const float av = i < 9 ? s.v[i] : i == 9 ? 1.f : 0.f;
+    const float hv = i < 9 ? h[i] : i == 10 ? h[9] : 0.f;
+    A[i >> 2][i & 3] = ok ? av : 0.f;
+    H[i >> 2][i & 3] = ok ? hv : 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < 16; i++) {
+    float dv;
+    if (i < 10) {
+      float acc = 0.f;
+#pragma unroll
+      for (int n = 0; n < 4; n++) acc = fmaf(W2[i * 4 + n], r[n], acc);
+      dv = pre[i] > 0.f ? acc : 0.1f * acc;
+    } else if (i < 14) dv = r[i - 10];
+    else dv = (i == 14) ? sq : ab;
+    D[i >> 2][i & 3] = ok ? dv : 0.f;
+  }
+#pragma unroll
+  for (int q = 0; q < 3; q++) { ((f32x4 *)a)[q] = A[q]; ((f32x4 *)hrow)[q] = H[q]; }
+#pragma unroll
+  for (int q = 0; q < 4; q++) ((f32x4 *)d)[q] = D[q];
+}
+
 // LDS rows written by other lanes of the SAME wave become visible (no workgroup barrier needed: a wave reads only its own slice)
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -140,11 +203,11 @@ __device__ __forceinline__ void wave_sync() {
 // thread's sample of the batch's first chunk; on exit the sample of the NEXT batch's first chunk (next_B > 0), fetched while this batch's
 // last chunk computes.  Ends with the tile in sm.G (read after a workgroup barrier); the caller barriers before the next call.
 template <class Pos>
-__device__ float batch_tile(Smem &sm, const SetRef &S, const Pos &pos, long long first, int B, long long next_first, int next_B, Sample &pf) {
+__device__ float batch_tile(Smem<5> &sm, const SetRef &S, const Pos &pos, long long first, int B, long long next_first, int next_B, Sample<5> &pf) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int c0 = 0; c0 < B; c0 += TPB) {
-    const Sample cur = pf;
+    const Sample<5> cur = pf;
     if (c0 + TPB < B) fetch(S, pos, first, B, c0 + TPB, pf);
     else if (next_B > 0) fetch(S, pos, next_first, next_B, 0, pf);
     sample_rows(sm.W, cur, c0 + tid < B, sm.A[tid], sm.D[tid]);
@@ -161,6 +224,34 @@ __device__ float batch_tile(Smem &sm, const SetRef &S, const Pos &pos, long long
   return ((sm.G[0][tid] + sm.G[1][tid]) + sm.G[2][tid]) + sm.G[3][tid];
 }
 
+// The stencil model's: the tiles P and Q (see the header), the thread's own entry taken from the tile `which` (0 = P, 1 = Q).
+template <class Pos>
+__device__ float batch_tile(Smem<9> &sm, const SetRef &S, const Pos &pos, long long first, int B, long long next_first, int next_B, Sample<9> &pf,
+                            int which) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
+  f32x4 accP = {0.f, 0.f, 0.f, 0.f}, accQ = {0.f, 0.f, 0.f, 0.f};
+  for (int c0 = 0; c0 < B; c0 += TPB) {
+    const Sample<9> cur = pf;
+    if (c0 + TPB < B) fetch(S, pos, first, B, c0 + TPB, pf);
+    else if (next_B > 0) fetch(S, pos, next_first, next_B, 0, pf);
+    sample_rows(sm.W, cur, c0 + tid < B, sm.A[tid], sm.H[tid], sm.D[tid]);
+    wave_sync();
+    const float *Aw = sm.A[wave * 64], *Hw = sm.H[wave * 64], *Dw = sm.D[wave * 64];
+    const int ca = c < 12 ? c : 11;                                     // columns 12..15 of A and H do not exist: zero rows of the tiles
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const float dv = Dw[(4 * j + g) * 16 + c], av = Aw[(4 * j + g) * 12 + ca], hv = Hw[(4 * j + g) * 12 + ca];
+      accP = __builtin_amdgcn_mfma_f32_16x16x4f32(c < 12 ? av : 0.f, dv, accP, 0, 0, 0);
+      accQ = __builtin_amdgcn_mfma_f32_16x16x4f32(c < 12 ? hv : 0.f, dv, accQ, 0, 0, 0);
+    }
+    wave_sync();
+  }
+#pragma unroll
+  for (int r = 0; r < 4; r++) { sm.G[wave][0][r * 64 + lane] = accP[r]; sm.G[wave][1][r * 64 + lane] = accQ[r]; }
+  __syncthreads();
+  return ((sm.G[0][which][tid] + sm.G[1][which][tid]) + sm.G[2][which][tid]) + sm.G[3][which][tid];
+}
+
 // tile entry e (register e >> 6, lane e & 63: row 4 (lane >> 4) + reg, column lane & 15) -> parameter index, or -1 / -2 (sum r^2) / -3 (sum |r|)
 __device__ __forceinline__ int param_of_entry(int e) {
   const int lane = e & 63, row = 4 * (lane >> 4) + (e >> 6), col = lane & 15;
@@ -172,16 +263,32 @@ __device__ __forceinline__ int param_of_entry(int e) {
   return -1;
 }
 
+// the stencil model's: sets `which` (the tile the entry is read from)
+__device__ __forceinline__ int param_of_entry9(int e, int &which) {
+  const int lane = e & 63, row = 4 * (lane >> 4) + (e >> 6), col = lane & 15;
+  which = 0;
+  if (row < 9 && col < 10) return row * 10 + col;                       // P: W1 (9,10)
+  if (row == 9 && col < 10) return 90 + col;                            // P: b1
+  if (row == 9 && col < 14) return 140 + col - 10;                      // P: b2
+  if (row == 9) return col == 14 ? -2 : -3;
+  which = 1;
+  if (col >= 10 && col < 14 && (row < 9 || row == 10)) return 100 + (row < 9 ? row : 9) * 4 + col - 10;   // Q: W2 (10,4), h9 in row 10
+  return -1;
+}
+
 struct TrainArgs {
   SetRef S; int B; int epoch; uint64_t seed;
   float *params, *m1, *m2; const float *table; double *stats;
   float beta1, beta2, eps;
 };
 
+template <int NIN>
 __global__ __launch_bounds__(TPB) void k_surrogate_train(TrainArgs a) {
-  __shared__ Smem sm;
+  constexpr int NPAR = npar<NIN>();
+  __shared__ Smem<NIN> sm;
   const int tid = threadIdx.x, model = blockIdx.x;
-  const int p = param_of_entry(tid);
+  int which = 0;
+  const int p = NIN == 5 ? param_of_entry(tid) : param_of_entry9(tid, which);
   float w = 0.f, m = 0.f, v = 0.f;
   if (p >= 0) {
     w = a.params[model * NPAR + p]; m = a.m1[model * NPAR + p]; v = a.m2[model * NPAR + p];
@@ -189,7 +296,7 @@ __global__ __launch_bounds__(TPB) void k_surrogate_train(TrainArgs a) {
   }
   const Shuffled pos{make_feistel(a.seed + (uint64_t)model, (uint64_t)a.epoch, a.S.n)};
   const long long n = a.S.n, steps = (n + a.B - 1) / a.B;
-  Sample pf;
+  Sample<NIN> pf;
   fetch(a.S, pos, 0, (int)std::min<long long>(a.B, n), 0, pf);
   double sq = 0.0, ab = 0.0;
   __syncthreads();
@@ -198,7 +305,9 @@ __global__ __launch_bounds__(TPB) void k_surrogate_train(TrainArgs a) {
     const int B = (int)std::min<long long>(a.B, n - first);
     const long long nf = first + B;
     const int nB = (int)std::min<long long>(a.B, n - nf);
-    const float gsum = batch_tile(sm, a.S, pos, first, B, nf, nB > 0 ? nB : 0, pf);
+    float gsum;
+    if constexpr (NIN == 5) gsum = batch_tile(sm, a.S, pos, first, B, nf, nB > 0 ? nB : 0, pf);
+    else gsum = batch_tile(sm, a.S, pos, first, B, nf, nB > 0 ? nB : 0, pf, which);
     if (p >= 0) {                                                       // Nadam (TF 2.x Keras), scalars from the host table
       const float cg = a.table[3 * s], cm = a.table[3 * s + 1], bc2 = a.table[3 * s + 2];
       const float gr = gsum * (0.5f / (float)B);                        // d mean((y - t)^2) = 2 r / (4 B)
@@ -215,15 +324,19 @@ __global__ __launch_bounds__(TPB) void k_surrogate_train(TrainArgs a) {
   else if (p == -3) a.stats[2 * model + 1] = ab;
 }
 
+template <int NIN>
 __global__ __launch_bounds__(TPB) void k_surrogate_grad(const float *__restrict__ params, SetRef S, int B, float *__restrict__ grad,
                                                         float *__restrict__ loss) {
-  __shared__ Smem sm;
-  const int tid = threadIdx.x, p = param_of_entry(tid);
+  __shared__ Smem<NIN> sm;
+  int which = 0;
+  const int tid = threadIdx.x, p = NIN == 5 ? param_of_entry(tid) : param_of_entry9(tid, which);
   if (p >= 0) sm.W[p] = params[p];
-  Sample pf;
+  Sample<NIN> pf;
   fetch(S, Identity(), 0, B, 0, pf);
   __syncthreads();
-  const float gsum = batch_tile(sm, S, Identity(), 0, B, 0, 0, pf);
+  float gsum;
+  if constexpr (NIN == 5) gsum = batch_tile(sm, S, Identity(), 0, B, 0, 0, pf);
+  else gsum = batch_tile(sm, S, Identity(), 0, B, 0, 0, pf, which);
   if (p >= 0) grad[p] = gsum * (0.5f / (float)B);
   else if (p == -2) loss[0] = gsum / (4.f * (float)B);
 }
@@ -231,9 +344,10 @@ __global__ __launch_bounds__(TPB) void k_surrogate_grad(const float *__restrict_
 // ---- data preparation: pre-shuffle, split, scaling, feature-major sets ----
 struct PrepArgs {
   long long n, n_train, n_val; Feistel F; const float *raw_in, *raw_out;
-  double in_min[5], in_rng[5], out_min[4], out_rng[4];
+  double in_min[9], in_rng[9], out_min[4], out_rng[4];
   float *x[3], *y[3];
 };
+template <int NIN>
 __global__ __launch_bounds__(TPB) void k_surrogate_prepare(PrepArgs a) {
   const long long stride = (long long)gridDim.x * TPB;
   for (long long p = (long long)blockIdx.x * TPB + threadIdx.x; p < a.n; p += stride) {
@@ -242,7 +356,7 @@ __global__ __launch_bounds__(TPB) void k_surrogate_prepare(PrepArgs a) {
     const long long q = set == 0 ? p : set == 1 ? p - a.n_train : p - a.n_train - a.n_val;
     const long long len = set == 0 ? a.n_train : set == 1 ? a.n_val : a.n - a.n_train - a.n_val;
 #pragma unroll
-    for (int f = 0; f < 5; f++) a.x[set][f * len + q] = (float)(((double)a.raw_in[src * 5 + f] - a.in_min[f]) / a.in_rng[f]);
+    for (int f = 0; f < NIN; f++) a.x[set][f * len + q] = (float)(((double)a.raw_in[src * NIN + f] - a.in_min[f]) / a.in_rng[f]);
 #pragma unroll
     for (int o = 0; o < 4; o++) a.y[set][o * len + q] = (float)(((double)a.raw_out[src * 4 + o] - a.out_min[o]) / a.out_rng[o]);
   }
@@ -293,31 +407,46 @@ using namespace mw;
 
 extern "C" {
 
-int mw_surrogate_prepare(long long n, const float *raw_in, const float *raw_out, const double *scl_in, const double *scl_out,
-                         unsigned long long seed, long long n_train, long long n_val, float *train_x, float *train_y, float *val_x,
-                         float *val_y, float *test_x, float *test_y, void *stream) {
+static int check_n_in(int n_in, const char *who) {
+  if (n_in != 5 && n_in != 9) MW_FAIL(std::string(who) + ": n_in must be 5 (single cell) or 9 (stencil), got " + std::to_string(n_in));
+  return 0;
+}
+
+int mw_surrogate_prepare_v2(int n_in, long long n, const float *raw_in, const float *raw_out, const double *scl_in, const double *scl_out,
+                            unsigned long long seed, long long n_train, long long n_val, float *train_x, float *train_y, float *val_x,
+                            float *val_y, float *test_x, float *test_y, void *stream) {
+  if (check_n_in(n_in, "surrogate_prepare")) return 1;
   if (!raw_in || !raw_out || !scl_in || !scl_out || !train_x || !train_y || !val_x || !val_y || !test_x || !test_y)
     MW_FAIL("surrogate_prepare: null argument");
   if (n < 3 || n_train < 1 || n_val < 1 || n - n_train - n_val < 1) MW_FAIL("surrogate_prepare: every set needs at least one sample");
   PrepArgs a;
   memset(&a, 0, sizeof(a));
-  for (int f = 0; f < 5; f++) { a.in_min[f] = scl_in[2 * f]; a.in_rng[f] = scl_in[2 * f + 1] - scl_in[2 * f]; }
+  for (int f = 0; f < n_in; f++) { a.in_min[f] = scl_in[2 * f]; a.in_rng[f] = scl_in[2 * f + 1] - scl_in[2 * f]; }
   for (int o = 0; o < 4; o++) { a.out_min[o] = scl_out[2 * o]; a.out_rng[o] = scl_out[2 * o + 1] - scl_out[2 * o]; }
-  for (int f = 0; f < 5; f++) if (!(a.in_rng[f] > 0)) MW_FAIL("surrogate_prepare: input " + std::to_string(f) + " has max <= min");
+  for (int f = 0; f < n_in; f++) if (!(a.in_rng[f] > 0)) MW_FAIL("surrogate_prepare: input " + std::to_string(f) + " has max <= min");
   for (int o = 0; o < 4; o++) if (!(a.out_rng[o] > 0)) MW_FAIL("surrogate_prepare: output " + std::to_string(o) + " has max <= min");
   if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
   a.n = n; a.n_train = n_train; a.n_val = n_val; a.F = make_feistel(seed, TAG_PRESHUFFLE, n);
   a.raw_in = raw_in; a.raw_out = raw_out;
   a.x[0] = train_x; a.y[0] = train_y; a.x[1] = val_x; a.y[1] = val_y; a.x[2] = test_x; a.y[2] = test_y;
   const long long blocks = std::max(1ll, std::min((n + TPB - 1) / TPB, 256ll * 16));
-  hipLaunchKernelGGL(k_surrogate_prepare, dim3((unsigned)blocks), dim3(TPB), 0, (hipStream_t)stream, a);
+  if (n_in == 5) hipLaunchKernelGGL(k_surrogate_prepare<5>, dim3((unsigned)blocks), dim3(TPB), 0, (hipStream_t)stream, a);
+  else           hipLaunchKernelGGL(k_surrogate_prepare<9>, dim3((unsigned)blocks), dim3(TPB), 0, (hipStream_t)stream, a);
   MW_LAUNCH_CHECK();
   return 0;
 }
 
-int mw_surrogate_train_epoch(int models, const float *x, const float *y, long long n, int batch, int epoch, unsigned long long seed,
-                             float *params, float *m1, float *m2, const float *table, float beta1, float beta2, float eps, double *stats,
-                             void *stream) {
+int mw_surrogate_prepare(long long n, const float *raw_in, const float *raw_out, const double *scl_in, const double *scl_out,
+                         unsigned long long seed, long long n_train, long long n_val, float *train_x, float *train_y, float *val_x,
+                         float *val_y, float *test_x, float *test_y, void *stream) {
+  return mw_surrogate_prepare_v2(5, n, raw_in, raw_out, scl_in, scl_out, seed, n_train, n_val, train_x, train_y, val_x, val_y, test_x, test_y,
+                                 stream);
+}
+
+int mw_surrogate_train_epoch_v2(int n_in, int models, const float *x, const float *y, long long n, int batch, int epoch,
+                                unsigned long long seed, float *params, float *m1, float *m2, const float *table, float beta1, float beta2,
+                                float eps, double *stats, void *stream) {
+  if (check_n_in(n_in, "surrogate_train_epoch")) return 1;
   if (!x || !y || !params || !m1 || !m2 || !table || !stats) MW_FAIL("surrogate_train_epoch: null argument");
   if (models < 1 || models > MW_SURROGATE_MAX_MODELS) MW_FAIL("surrogate_train_epoch: models must be in [1, " + std::to_string(MW_SURROGATE_MAX_MODELS) + "]");
   if (batch < 1 || batch > MW_SURROGATE_MAX_BATCH) MW_FAIL("surrogate_train_epoch: batch must be in [1, " + std::to_string(MW_SURROGATE_MAX_BATCH) + "]");
@@ -327,18 +456,32 @@ int mw_surrogate_train_epoch(int models, const float *x, const float *y, long lo
   a.S = SetRef{x, y, n}; a.B = batch; a.epoch = epoch; a.seed = seed;
   a.params = params; a.m1 = m1; a.m2 = m2; a.table = table; a.stats = stats;
   a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-  hipLaunchKernelGGL(k_surrogate_train, dim3((unsigned)models), dim3(TPB), 0, (hipStream_t)stream, a);
+  if (n_in == 5) hipLaunchKernelGGL(k_surrogate_train<5>, dim3((unsigned)models), dim3(TPB), 0, (hipStream_t)stream, a);
+  else           hipLaunchKernelGGL(k_surrogate_train<9>, dim3((unsigned)models), dim3(TPB), 0, (hipStream_t)stream, a);
+  MW_LAUNCH_CHECK();
+  return 0;
+}
+
+int mw_surrogate_train_epoch(int models, const float *x, const float *y, long long n, int batch, int epoch, unsigned long long seed,
+                             float *params, float *m1, float *m2, const float *table, float beta1, float beta2, float eps, double *stats,
+                             void *stream) {
+  return mw_surrogate_train_epoch_v2(5, models, x, y, n, batch, epoch, seed, params, m1, m2, table, beta1, beta2, eps, stats, stream);
+}
+
+int mw_surrogate_batch_grad_v2(int n_in, const float *params, const float *x, const float *y, int batch, float *grad, float *loss,
+                               void *stream) {
+  if (check_n_in(n_in, "surrogate_batch_grad")) return 1;
+  if (!params || !x || !y || !grad || !loss) MW_FAIL("surrogate_batch_grad: null argument");
+  if (batch < 1 || batch > MW_SURROGATE_MAX_BATCH) MW_FAIL("surrogate_batch_grad: batch must be in [1, " + std::to_string(MW_SURROGATE_MAX_BATCH) + "]");
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  if (n_in == 5) hipLaunchKernelGGL(k_surrogate_grad<5>, dim3(1), dim3(TPB), 0, (hipStream_t)stream, params, SetRef{x, y, (long long)batch}, batch, grad, loss);
+  else           hipLaunchKernelGGL(k_surrogate_grad<9>, dim3(1), dim3(TPB), 0, (hipStream_t)stream, params, SetRef{x, y, (long long)batch}, batch, grad, loss);
   MW_LAUNCH_CHECK();
   return 0;
 }
 
 int mw_surrogate_batch_grad(const float *params, const float *x, const float *y, int batch, float *grad, float *loss, void *stream) {
-  if (!params || !x || !y || !grad || !loss) MW_FAIL("surrogate_batch_grad: null argument");
-  if (batch < 1 || batch > MW_SURROGATE_MAX_BATCH) MW_FAIL("surrogate_batch_grad: batch must be in [1, " + std::to_string(MW_SURROGATE_MAX_BATCH) + "]");
-  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
-  hipLaunchKernelGGL(k_surrogate_grad, dim3(1), dim3(TPB), 0, (hipStream_t)stream, params, SetRef{x, y, (long long)batch}, batch, grad, loss);
-  MW_LAUNCH_CHECK();
-  return 0;
+  return mw_surrogate_batch_grad_v2(5, params, x, y, batch, grad, loss, stream);
 }
 
 long long mw_surrogate_errors_workspace_bytes(int nsets) { return nsets < 1 ? 0 : (long long)nsets * ERR_BLOCKS * NSTAT * (long long)sizeof(double); }

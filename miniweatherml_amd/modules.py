@@ -331,7 +331,9 @@ def load_h5_weights(fname, group, dataset):
 def load_surrogate_weights(weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None):
     """The Keras weights + min/max scaling tables (microphysics_kessler_ponni.h:97-135).  weights_h5: the reference's
     `keras_weights_h5` file, read like ponni::load_h5_weights does (:103-107); weights_txt: a text export of the 104 values
-    (tools/export_mlp_weights.sh).  Default: the reference's shipped weight file (miniweatherml_amd/data/)."""
+    (tools/export_mlp_weights.sh).  Default: the reference's shipped weight file (miniweatherml_amd/data/).
+    The model is inferred from the text files: 5 scaling rows + 104 weights = the single-cell model (W1 (5,10)), 9 rows + 144 weights = the
+    two-cell stencil model (W1 (9,10); surrogate_train --stencil).  Any other pairing is refused; so is an .h5 file of a stencil model."""
     if weights_txt is None and weights_h5 is None:
         weights_h5 = os.path.join(_DATA, "supercell_kessler_singlecell_model_weights.h5")
     if weights_h5 is not None:
@@ -340,14 +342,20 @@ def load_surrogate_weights(weights_txt=None, in_scaling_txt=None, out_scaling_tx
         W2 = load_h5_weights(weights_h5, "/dense_7/dense_7", "kernel:0")       # Matvec 2   (10, 4)
         b2 = load_h5_weights(weights_h5, "/dense_7/dense_7", "bias:0")
         if W1.shape != (5, 10) or b1.shape != (10,) or W2.shape != (10, 4) or b2.shape != (4,):
-            endrun("surrogate weight file: expected Dense(5->10) and Dense(10->4)")
-        w = None
+            endrun("surrogate weight file: expected Dense(5->10) and Dense(10->4) (an .h5 file of the stencil model is not supported: "
+                   "use the text files surrogate_train writes)")
+        nw = 104
     else:
-        w = np.loadtxt(weights_txt, dtype=np.float64, comments="#").astype(np.float32)
-        if w.size != 104:
-            endrun("surrogate weight file must hold 104 values")
-        W1, b1, W2, b2 = w[:50].reshape(5, 10).copy(), w[50:60].copy(), w[60:100].reshape(10, 4).copy(), w[100:104].copy()
-    scl_in = np.loadtxt(in_scaling_txt or os.path.join(_DATA, "kessler_surrogate_input_scaling.txt")).reshape(5, 2)
+        w = np.loadtxt(weights_txt, dtype=np.float64, comments="#").astype(np.float32).ravel()
+        nw = w.size
+    scl_in = np.atleast_2d(np.loadtxt(in_scaling_txt or os.path.join(_DATA, "kessler_surrogate_input_scaling.txt")))
+    rows = scl_in.shape[0] if scl_in.shape[1:] == (2,) else -1
+    if (rows, nw) not in ((5, 104), (9, 144)):
+        endrun("surrogate files: %d input scaling rows with %d weights; expected 5 rows + 104 weights (single-cell model) or 9 rows + 144 "
+               "weights (stencil model)" % (rows if rows >= 0 else scl_in.size // 2, nw))
+    if weights_h5 is None:
+        a = 10 * rows
+        W1, b1, W2, b2 = w[:a].reshape(rows, 10).copy(), w[a:a + 10].copy(), w[a + 10:a + 50].reshape(10, 4).copy(), w[a + 50:a + 54].copy()
     scl_out = np.loadtxt(out_scaling_txt or os.path.join(_DATA, "kessler_surrogate_output_scaling.txt")).reshape(4, 2)
     return W1, b1, W2, b2, np.ascontiguousarray(scl_in), np.ascontiguousarray(scl_out)
 
@@ -365,6 +373,38 @@ def mlp_forward(temp, rho_d, rho_v, rho_c, rho_r, W1, b1, W2, b2, scl_in, scl_ou
                                         scl_in.ctypes.data_as(dp), scl_out.ctypes.data_as(dp), *[_ptr(o) for o in outs],
                                         _stream_ptr(temp.device)))
     return outs
+
+
+def mlp_stencil_forward(nz, temp, rho_d, rho_v, rho_c, rho_r, W1, b1, W2, b2, scl_in, scl_out, outs=None, strict=0):
+    """mlp_forward for the two-cell stencil model (W1 (9,10), scl_in (9,2)): the fields are whole coupler arrays (nz, ...) and features
+    5..8 come from level min(nz - 1, k + 1) of the same column (stencil_features states the order).  The outputs never alias the inputs."""
+    fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+    if W1.shape != (9, 10) or scl_in.shape != (9, 2):
+        endrun("mlp_stencil_forward: W1 must be (9, 10) and scl_in (9, 2), got %r and %r" % (W1.shape, scl_in.shape))
+    if temp.numel() % int(nz) != 0:
+        endrun("mlp_stencil_forward: %d cells are not a whole number of columns of nz = %d" % (temp.numel(), nz))
+    if outs is None:
+        outs = [torch.empty_like(temp) for _ in range(4)]
+    check(capi.lib().mw_mlp_set_strict(int(bool(strict))))
+    with torch.cuda.device(temp.device):
+        check(capi.lib().mw_mlp_stencil_forward(int(nz), temp.numel() // int(nz), _ptr(temp), _ptr(rho_d), _ptr(rho_v), _ptr(rho_c), _ptr(rho_r),
+                                                W1.ctypes.data_as(fp), b1.ctypes.data_as(fp), W2.ctypes.data_as(fp), b2.ctypes.data_as(fp),
+                                                scl_in.ctypes.data_as(dp), scl_out.ctypes.data_as(dp), *[_ptr(o) for o in outs],
+                                                _stream_ptr(temp.device)))
+    return outs
+
+
+def stencil_features(fields, nz):
+    """The nine inputs of the stencil model on the host (pure numpy): fields = (temp, density_dry, water_vapor, cloud_liquid, precip_liquid),
+    arrays whose first axis is the nz levels (any trailing shape: (ny, nx, nens) or flat columns).  Returns (9, ncells) in C order of the
+    fields: rows 0..4 the cell's five, rows 5..8 temp, water_vapor, cloud_liquid, precip_liquid of level min(nz - 1, k + 1) of the same
+    column and ensemble member (DataGenerator's inputs(:, :, 0) and inputs(:, 0:4, 1))."""
+    f = [np.asarray(a).reshape(int(nz), -1) for a in fields]
+    if len(f) != 5 or any(a.shape != f[0].shape for a in f):
+        endrun("stencil_features: five fields of one shape (nz, ...) expected")
+    up = np.minimum(np.arange(int(nz)) + 1, int(nz) - 1)
+    rows = f + [f[i][up] for i in (0, 2, 3, 4)]
+    return np.stack([r.reshape(-1) for r in rows])
 
 
 class _PonniLayer(C.Structure):
@@ -419,8 +459,12 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
         dm = coupler.get_data_manager_readwrite()
         temp, rho_d = dm.get("temp"), dm.get("density_dry", readonly=True)
         rho_v, rho_c, rho_r = dm.get("water_vapor"), dm.get("cloud_liquid"), dm.get("precip_liquid")
-        self._nn_out = mlp_forward(temp, rho_d, rho_v, rho_c, rho_r, self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out,
-                                   self._nn_out, strict=self.mlp_strict)
+        if self.W1.shape[0] == 9:                                              # the stencil model: what load_surrogate_weights found
+            self._nn_out = mlp_stencil_forward(coupler.get_nz(), temp, rho_d, rho_v, rho_c, rho_r, self.W1, self.b1, self.W2, self.b2,
+                                               self.scl_in, self.scl_out, self._nn_out, strict=self.mlp_strict)
+        else:
+            self._nn_out = mlp_forward(temp, rho_d, rho_v, rho_c, rho_r, self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out,
+                                       self._nn_out, strict=self.mlp_strict)
         super().time_step(coupler, dt)
         if self.online:                                                        # :273-276
             self._diffs = self.mean_diffs(coupler)                             # (the prints of :266-269 come first)

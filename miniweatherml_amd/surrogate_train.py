@@ -9,7 +9,9 @@ The fit is the notebooks' recorded one, restated with integer-defined random cho
 pre-shuffle, per-variable min-max scaling over all samples, test split = the tail, validation split = the tail of the rest (Keras'
 validation_split), per-epoch shuffle of the training set, Dense kernels uniform in [-0.05, 0.05), biases 0, loss mse, Nadam (TF 2.x Keras).
 The hot path is csrc/mw_train.hip (one workgroup per model, the batches loop in the kernel); the validation and test predictions are
-mw_ponni_forward's MFMA forward.  This file holds the host side: reading and checking the data, the permutations' definition (restated
+mw_ponni_forward's MFMA forward.  stencil=True (CLI --stencil) trains the two-cell stencil model 9 -> 10 -> 4 instead: the cell's five
+inputs plus temperature, vapor, cloud and precipitation of the level above (STENCIL_IN_NAMES; slot 1 of the sample files), 144 parameters,
+the same fit.  This file holds the host side: reading and checking the data, the permutations' definition (restated
 here so that tests can replay the batch order), the Nadam scalars, the reports and the output files.  DESIGN.md section 13.
 """
 import argparse
@@ -24,6 +26,8 @@ import numpy as np
 MAX_BATCH = 8192                     # MW_SURROGATE_MAX_BATCH (include/mw_cdna4.h)
 MAX_MODELS = 256                     # MW_SURROGATE_MAX_MODELS
 IN_NAMES = ("temperature", "dry air density", "water vapor density", "cloud liquid density", "precipitation density")
+ABOVE_ROWS = (0, 1, 2, 3)            # rows of slot 1 that DataGenerator assigns (generate_micro_surrogate_data.h:139-142): row 4 never is
+STENCIL_IN_NAMES = IN_NAMES + tuple(IN_NAMES[v] + " (level above)" for v in (0, 2, 3, 4))       # slot 1 has no dry density
 OUT_NAMES = ("temperature", "water vapor density", "cloud liquid density", "precipitation density")
 NADAM = dict(beta1=0.9, beta2=0.999, eps=1e-7, schedule_decay=0.004)    # tf.keras.optimizers.Nadam defaults
 M64 = (1 << 64) - 1
@@ -93,13 +97,28 @@ def epoch_permutation(n_train, seed, model, epoch):
     return feistel_permutation(n_train, (int(seed) + int(model)) & M64, int(epoch))
 
 
-def initial_weights(seed, models):
-    """(models, 104) fp32: Dense kernels RandomUniform(-0.05, 0.05) -- u = (sm64(sm64(sm64(seed + m) ^ tag) + p) >> 40) / 2^24 for
+def n_params(stencil=False):
+    """104 (single cell: W1 (5,10), b1 (10), W2 (10,4), b2 (4)) or 144 (stencil: W1 (9,10), ...)."""
+    return 144 if stencil else 104
+
+
+def split_weights(w):
+    """W1, b1, W2, b2 of a flat parameter vector of either model (Keras order)."""
+    w = np.asarray(w)
+    n_in = {104: 5, 144: 9}[w.size]
+    a = 10 * n_in
+    return w[:a].reshape(n_in, 10), w[a:a + 10], w[a + 10:a + 50].reshape(10, 4), w[a + 50:a + 54]
+
+
+def initial_weights(seed, models, stencil=False):
+    """(models, 104 | 144) fp32: Dense kernels RandomUniform(-0.05, 0.05) -- u = (sm64(sm64(sm64(seed + m) ^ tag) + p) >> 40) / 2^24 for
     parameter index p, w = fp32(0.1 u - 0.05) -- and zero biases (Keras' defaults)."""
-    w = np.zeros((models, 104), dtype=np.float32)
+    npar = n_params(stencil)
+    nw1 = npar - 54
+    w = np.zeros((models, npar), dtype=np.float32)
     for m in range(models):
         base = splitmix64(splitmix64((int(seed) + m) & M64) ^ TAG_WEIGHTS)
-        for p in list(range(0, 50)) + list(range(60, 100)):
+        for p in list(range(0, nw1)) + list(range(nw1 + 10, nw1 + 50)):
             u = (splitmix64((base + p) & M64) >> 40) * (1.0 / 16777216.0)
             w[m, p] = np.float32(0.1 * u - 0.05)
     return w
@@ -130,9 +149,11 @@ def nadam_table(steps, learning_rate=1e-3, beta1=0.9, beta2=0.999, schedule_deca
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # data and arguments (host checks: they run before anything reaches the device)
-def read_samples(sample_files):
+def read_samples(sample_files, stencil=False):
     """Concatenates the files DataGenerator writes (CDF-5: inputs (nsamples, 5, 2), outputs (nsamples, 4) fp32) in the order given, through
-    modules._NcFile.  Returns inputs (n, 5) = slot 0 of the stencil (the single-cell model), outputs (n, 4), and the grid metadata."""
+    modules._NcFile.  Returns inputs (n, 5) = slot 0 of the stencil (the single-cell model), outputs (n, 4), and the grid metadata.
+    stencil=True: inputs (n, 9) = slot 0, then rows 0..3 of slot 1 (temperature, vapor, cloud and precipitation of the level above; its
+    row 4 is never assigned and is not read)."""
     from .modules import _NcFile
     if isinstance(sample_files, (str, os.PathLike)):
         sample_files = [sample_files]
@@ -154,7 +175,7 @@ def read_samples(sample_files):
             raise SurrogateTrainError("%s: time_step_size %r differs from %r of %s; the Kessler outputs depend on dt, so files of "
                                       "different time steps cannot be trained together" % (path, m["time_step_size"],
                                                                                           meta["time_step_size"], sample_files[0]))
-        ins.append(np.ascontiguousarray(i3[:, :, 0]))
+        ins.append(np.concatenate([i3[:, :, 0], i3[:, ABOVE_ROWS, 1]], axis=1) if stencil else np.ascontiguousarray(i3[:, :, 0]))
         outs.append(o2)
     inputs, outputs = np.concatenate(ins).astype(np.float32), np.concatenate(outs).astype(np.float32)
     meta["files"] = [os.fspath(p) for p in sample_files]
@@ -162,7 +183,7 @@ def read_samples(sample_files):
 
 
 def data_scaling(inputs, outputs):
-    """Refuses unusable data and returns the min-max tables scl_in (5, 2), scl_out (4, 2) (fp64 arrays holding the fp32 extremes)."""
+    """Refuses unusable data and returns the min-max tables scl_in (5 | 9, 2), scl_out (4, 2) (fp64 arrays holding the fp32 extremes)."""
     if inputs.shape[0] == 0:
         raise SurrogateTrainError("the sample files hold zero samples")
     for arr, what in ((inputs, "inputs"), (outputs, "outputs")):
@@ -170,7 +191,7 @@ def data_scaling(inputs, outputs):
         if bad.any():
             raise SurrogateTrainError("%d non-finite values in the %s (first at sample %d)" % (int(bad.sum()), what, int(np.argwhere(bad)[0][0])))
     tabs = []
-    for arr, names, what in ((inputs, IN_NAMES, "input"), (outputs, OUT_NAMES, "output")):
+    for arr, names, what in ((inputs, STENCIL_IN_NAMES if inputs.shape[1] == 9 else IN_NAMES, "input"), (outputs, OUT_NAMES, "output")):
         lo, hi = arr.min(axis=0), arr.max(axis=0)
         for v in range(arr.shape[1]):
             if not hi[v] > lo[v]:
@@ -205,16 +226,22 @@ def _fmt(v):
 
 
 def write_outputs(out_dir, weights, scl_in, scl_out, history):
-    """weights.txt (104 values, the layout of data/kessler_surrogate_weights.txt), input_scaling.txt / output_scaling.txt (`min max` rows)
-    and history.json; returns the three paths inference_ponni takes (keras_weights_txt, nn_input_scaling, nn_output_scaling)."""
+    """weights.txt (104 values, the layout of data/kessler_surrogate_weights.txt; 144 for the stencil model), input_scaling.txt /
+    output_scaling.txt (`min max` rows, 5 | 9 and 4) and history.json; returns the three paths inference_ponni takes (keras_weights_txt,
+    nn_input_scaling, nn_output_scaling)."""
     os.makedirs(out_dir, exist_ok=True)
     w = np.asarray(weights, dtype=np.float32).ravel()
+    n_in = np.asarray(scl_in).shape[0]
+    if (n_in, w.size) not in ((5, 104), (9, 144)):
+        raise SurrogateTrainError("write_outputs: %d input scaling rows with %d weights is neither the single-cell model (5, 104) nor the "
+                                  "stencil model (9, 144)" % (n_in, w.size))
+    a = 10 * n_in
     paths = [os.path.join(out_dir, f) for f in ("weights.txt", "input_scaling.txt", "output_scaling.txt")]
     with open(paths[0], "w") as f:
-        for title, a, b in (("dense_6 kernel (5,10) row-major", 0, 50), ("dense_6 bias (10)", 50, 60), ("dense_7 kernel (10,4) row-major", 60, 100),
-                            ("dense_7 bias (4)", 100, 104)):
+        for title, lo, hi in (("dense_6 kernel (%d,10) row-major" % n_in, 0, a), ("dense_6 bias (10)", a, a + 10),
+                              ("dense_7 kernel (10,4) row-major", a + 10, a + 50), ("dense_7 bias (4)", a + 50, a + 54)):
             f.write("# %s\n" % title)
-            f.writelines(_fmt(x) + "\n" for x in w[a:b])
+            f.writelines(_fmt(x) + "\n" for x in w[lo:hi])
     for path, tab in ((paths[1], scl_in), (paths[2], scl_out)):
         with open(path, "w") as f:
             f.writelines("%s %s\n" % (_fmt(lo), _fmt(hi)) for lo, hi in np.asarray(tab))
@@ -225,12 +252,18 @@ def write_outputs(out_dir, weights, scl_in, scl_out, history):
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the device side
-_LAYERS = ((0, 5, 10, 0.0, 0), (1, 10, 10, 0.0, 50), (2, 10, 10, 0.1, 0), (0, 10, 4, 0.0, 60), (1, 4, 4, 0.0, 100))
+def _layers(n_in):
+    a = 10 * n_in
+    return ((0, n_in, 10, 0.0, 0), (1, 10, 10, 0.0, a), (2, 10, 10, 0.1, 0), (0, 10, 4, 0.0, a + 10), (1, 4, 4, 0.0, a + 50))
+
+
+_LAYERS = _layers(5)
 
 
 class Trainer:
     """The device state of one training run: the three scaled sets, K models' parameters and moments, the Nadam table.  epoch() is one
-    training launch plus the validation pass, with one host synchronisation (the copy of the weights and sums)."""
+    training launch plus the validation pass, with one host synchronisation (the copy of the weights and sums).  The model follows the
+    data: raw_in (n, 5) trains the single-cell model (104 parameters), raw_in (n, 9) the stencil model (144)."""
 
     def __init__(self, raw_in, raw_out, scl_in, scl_out, n_split, seed=0, split_seed=None, models=1, batch_size=1024, epochs=10,
                  learning_rate=1e-3):
@@ -238,28 +271,33 @@ class Trainer:
         from . import capi
         self.torch, self.L = torch, capi.lib()
         self.device = raw_in.device
+        self.n_in = int(raw_in.shape[1])
+        if self.n_in not in (5, 9) or np.asarray(scl_in).shape != (self.n_in, 2):
+            raise SurrogateTrainError("Trainer: inputs (n, %d) with a scaling table %r; expected (n, 5) or (n, 9) and as many scaling rows"
+                                      % (self.n_in, np.asarray(scl_in).shape))
+        self.npar = NP = 54 + 10 * self.n_in
         self.n_train, self.n_val, self.n_test = n_split
         self.K, self.B, self.seed = int(models), int(batch_size), int(seed)
         self.split_seed = self.seed if split_seed is None else int(split_seed)
         self.steps = (self.n_train + self.B - 1) // self.B
         dev, f32 = self.device, torch.float32
-        self.sets = {k: (torch.empty((5, n), dtype=f32, device=dev), torch.empty((4, n), dtype=f32, device=dev))
+        self.sets = {k: (torch.empty((self.n_in, n), dtype=f32, device=dev), torch.empty((4, n), dtype=f32, device=dev))
                      for k, n in (("train", self.n_train), ("val", self.n_val), ("test", self.n_test))}
         dp = C.POINTER(C.c_double)
         self.scl_in, self.scl_out = np.ascontiguousarray(scl_in, np.float64), np.ascontiguousarray(scl_out, np.float64)
         (tx, ty), (vx, vy), (sx, sy) = self.sets["train"], self.sets["val"], self.sets["test"]
         with torch.cuda.device(dev):
-            capi.check(self.L.mw_surrogate_prepare(raw_in.shape[0], self._p(raw_in), self._p(raw_out), self.scl_in.ctypes.data_as(dp),
-                                                   self.scl_out.ctypes.data_as(dp), self.split_seed & M64, self.n_train, self.n_val,
-                                                   *[self._p(t) for t in (tx, ty, vx, vy, sx, sy)], self._stream()))
+            capi.check(self.L.mw_surrogate_prepare_v2(self.n_in, raw_in.shape[0], self._p(raw_in), self._p(raw_out), self.scl_in.ctypes.data_as(dp),
+                                                      self.scl_out.ctypes.data_as(dp), self.split_seed & M64, self.n_train, self.n_val,
+                                                      *[self._p(t) for t in (tx, ty, vx, vy, sx, sy)], self._stream()))
         # ONE device buffer for what the host reads each epoch: parameters (K, 104) fp32 | training sums (K, 2) fp64 | validation sums (K, 24)
-        self.buf = torch.zeros(self.K * (104 * 4 + 2 * 8 + 24 * 8), dtype=torch.uint8, device=dev)
-        self.params = self.buf[:self.K * 416].view(f32).view(self.K, 104)
-        self.tstats = self.buf[self.K * 416:self.K * 432].view(torch.float64).view(self.K, 2)
-        self.vstats = self.buf[self.K * 432:].view(torch.float64).view(self.K, 24)
-        self.params.copy_(torch.from_numpy(initial_weights(self.seed, self.K)))
-        self.m1 = torch.zeros((self.K, 104), dtype=f32, device=dev)
-        self.m2 = torch.zeros((self.K, 104), dtype=f32, device=dev)
+        self.buf = torch.zeros(self.K * (NP * 4 + 2 * 8 + 24 * 8), dtype=torch.uint8, device=dev)
+        self.params = self.buf[:self.K * NP * 4].view(f32).view(self.K, NP)
+        self.tstats = self.buf[self.K * NP * 4:self.K * (NP * 4 + 16)].view(torch.float64).view(self.K, 2)
+        self.vstats = self.buf[self.K * (NP * 4 + 16):].view(torch.float64).view(self.K, 24)
+        self.params.copy_(torch.from_numpy(initial_weights(self.seed, self.K, stencil=self.n_in == 9)))
+        self.m1 = torch.zeros((self.K, NP), dtype=f32, device=dev)
+        self.m2 = torch.zeros((self.K, NP), dtype=f32, device=dev)
         self.lr = float(learning_rate)
         self.table = torch.from_numpy(nadam_table(self.steps * int(epochs), self.lr, NADAM["beta1"], NADAM["beta2"],
                                                   NADAM["schedule_decay"])).to(dev)
@@ -279,9 +317,9 @@ class Trainer:
     def _predict(self, w104, x, out):
         from .modules import _PonniLayer
         from .capi import check
-        lay = (_PonniLayer * 5)(*[_PonniLayer(*r) for r in _LAYERS])
+        lay = (_PonniLayer * 5)(*[_PonniLayer(*r) for r in _layers(self.n_in)])
         w = np.ascontiguousarray(w104, dtype=np.float32)
-        check(self.L.mw_ponni_forward(C.cast(lay, C.c_void_p), 5, w.ctypes.data_as(C.POINTER(C.c_float)), 104, x.shape[1], self._p(x),
+        check(self.L.mw_ponni_forward(C.cast(lay, C.c_void_p), 5, w.ctypes.data_as(C.POINTER(C.c_float)), self.npar, x.shape[1], self._p(x),
                                       self._p(out), self._stream()))
 
     def _errors(self, n, nsets, pred, y, out_ptr):
@@ -307,7 +345,7 @@ class Trainer:
         from .capi import check
         tx, ty = self.sets["train"]
         with self.torch.cuda.device(self.device):
-            check(self.L.mw_surrogate_train_epoch(self.K, self._p(tx), self._p(ty), self.n_train, self.B, self.epoch_no, self.seed & M64,
+            check(self.L.mw_surrogate_train_epoch_v2(self.n_in, self.K, self._p(tx), self._p(ty), self.n_train, self.B, self.epoch_no, self.seed & M64,
                                                   self._p(self.params), self._p(self.m1), self._p(self.m2),
                                                   C.c_void_p(self.table.data_ptr() + self.epoch_no * self.steps * 12), NADAM["beta1"],
                                                   NADAM["beta2"], NADAM["eps"], self._p(self.tstats), self._stream()))
@@ -318,9 +356,9 @@ class Trainer:
 
     def _host(self):
         b = self.buf.cpu().numpy()
-        K = self.K
-        return (b[:K * 416].view(np.float32).reshape(K, 104).copy(), b[K * 416:K * 432].view(np.float64).reshape(K, 2).copy(),
-                b[K * 432:].view(np.float64).reshape(K, 24).copy())
+        K, nb = self.K, self.npar * 4
+        return (b[:K * nb].view(np.float32).reshape(K, self.npar).copy(), b[K * nb:K * (nb + 16)].view(np.float64).reshape(K, 2).copy(),
+                b[K * (nb + 16):].view(np.float64).reshape(K, 24).copy())
 
     def finish(self):
         """The last epoch's validation sums (one more copy)."""
@@ -343,13 +381,14 @@ def _metrics(s):
 
 
 def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test_split=0.2, validation_split=0.2, learning_rate=1e-3,
-                    seed=0, models=1, device="cuda:0", split_seed=None, verbose=False):
+                    seed=0, models=1, device="cuda:0", split_seed=None, verbose=False, stencil=False):
     """Trains `models` surrogates (seeds seed .. seed + models - 1; the pre-shuffle / split uses split_seed, default seed) on the samples of
     `sample_files` and returns a dict: per-model `history` (Keras' loss, mean_absolute_error, val_loss, val_mean_absolute_error per
     epoch), `weights` (models, 104) fp32, `best_model` (lowest final val_loss, ties to the lowest index), `test_metrics` of the best model
     (the notebook's three, scaled space, per output), the scaling tables, the data's time_step_size / dx / dy / dz and the seeds.
-    out_dir: also writes the best model's weights.txt, input_scaling.txt, output_scaling.txt and history.json there."""
-    inputs, outputs, meta = read_samples(sample_files)
+    out_dir: also writes the best model's weights.txt, input_scaling.txt, output_scaling.txt and history.json there.
+    stencil=True: the two-cell stencil model (9 inputs, `weights` (models, 144), `"inputs": "stencil"` in the result and history.json)."""
+    inputs, outputs, meta = read_samples(sample_files, stencil=stencil)
     scl_in, scl_out = data_scaling(inputs, outputs)
     n = inputs.shape[0]
     n_split = check_arguments(n, epochs, batch_size, test_split, validation_split, models)
@@ -401,7 +440,8 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     seeds = [int(seed) + m for m in range(K)]
     result = {"history": hist, "weights": w, "best_model": best, "test_metrics": metrics, "input_scaling": scl_in, "output_scaling": scl_out,
               "seeds": seeds, "split_seed": tr.split_seed, "n_train": n_train, "n_val": n_val, "n_test": n_test, "epoch_seconds": secs,
-              "batch_size": int(batch_size), "epochs": int(epochs), "learning_rate": float(learning_rate)}
+              "batch_size": int(batch_size), "epochs": int(epochs), "learning_rate": float(learning_rate),
+              "inputs": "stencil" if stencil else "single_cell"}
     result.update({k: meta[k] for k in ("time_step_size", "dx", "dy", "dz", "files")})
     if verbose:
         print("Max relative errors:  ", metrics["max_relative_error"])
@@ -416,7 +456,7 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m miniweatherml_amd.surrogate_train",
-                                 description="Train the Kessler surrogate (5 -> 10 -> 4) on DataGenerator sample files, on the GPU.")
+                                 description="Train the Kessler surrogate (5 -> 10 -> 4, or 9 -> 10 -> 4 with --stencil) on DataGenerator sample files, on the GPU.")
     ap.add_argument("files", nargs="+", help="sample files written by generate_micro_data (concatenated in this order)")
     ap.add_argument("--out", required=True, help="directory for weights.txt, input_scaling.txt, output_scaling.txt, history.json")
     ap.add_argument("--epochs", type=int, default=10)
@@ -428,10 +468,11 @@ def main(argv=None):
     ap.add_argument("--split-seed", type=int, default=None, help="seed of the pre-shuffle (default: --seed)")
     ap.add_argument("--models", type=int, default=1, help="train seeds seed .. seed+K-1 at once and keep the best (lowest val_loss)")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--stencil", action="store_true", help="train the two-cell stencil model (the cell and the level above: 9 inputs, 144 weights)")
     a = ap.parse_args(argv)
     try:
         r = train_surrogate(a.files, a.out, a.epochs, a.batch_size, a.test_split, a.validation_split, a.learning_rate, a.seed, a.models,
-                            a.device, a.split_seed, verbose=True)
+                            a.device, a.split_seed, verbose=True, stencil=a.stencil)
     except SurrogateTrainError as e:
         print("ERROR: %s" % e, file=sys.stderr)
         return 2
