@@ -1,6 +1,6 @@
 // =====================================================================================================
 // mw_calib.h -- calibration kernels (no reference counterpart; SURVEY.md 8(d): "fp64 vector 78.6 TFLOP/s ... absent from the
-// local guide -- calibrate with an FMA microbenchmark").  Included by mw_dycore.hip behind mw_march.h.
+// local guide -- calibrate with an FMA microbenchmark").  Included by mw_dycore_aids.hip behind mw_march.h.
 //
 //   k_calib_fma64       independent v_fma_f64 chains, W wavefronts per SIMD: the SUSTAINED fp64 issue rate of this part under its own
 //                       power management (wave-instructions per second) and the shader clock it ran at (cycle counter / real-time
@@ -9,6 +9,7 @@
 //                       passive fluxes, on register windows fed from a table that stays in L2 (no HBM traffic, one store per thread
 //                       at the end), with the register budget and occupancy of k_xz_state (256 threads, 2 workgroups per CU).
 //                       Its time for N cells is the floor of a stage of N cells for ANY schedule of this arithmetic on this chip.
+//   k_calib_copy        the known-byte streaming copy that calibrates the profiler's FETCH_SIZE / WRITE_SIZE.
 //   k_spin / k_scale    test aids: a kernel that occupies a stream for a given time (delay fuzz of the exchange tests) and
 //                       buf *= f (the self-loop transport's sum over identical blocks).
 // =====================================================================================================
@@ -143,6 +144,13 @@ __global__ void k_spin(long long ticks) {                        // wall_clock64
 __global__ __launch_bounds__(256) void k_scale(double *__restrict__ buf, long long n, double f) {
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   if (t < n) buf[t] *= f;
+}
+
+// Streaming copy with this library's access shape (8 bytes per lane, consecutive lanes consecutive doubles): the known-byte
+// workload used to calibrate rocprofv3's FETCH_SIZE / WRITE_SIZE on gfx950 (MI355X_MICROARCH.md, HBM section).
+__global__ __launch_bounds__(256) void k_calib_copy(const double *__restrict__ in, double *__restrict__ out, long long n) {
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = in[i];
 }
 
 int launch_spin(long long usec, hipStream_t st) {

@@ -1,5 +1,5 @@
 // =====================================================================================================
-// mw_march.h -- the production RK-stage kernels ("shared reconstruction, marching").   Included by mw_dycore.hip.
+// mw_march.h -- the production RK-stage kernels ("shared reconstruction, marching").   Included by the mw_march_*.hip units (and mw_dycore_aids.hip).
 //
 // Each cell is reconstructed ONCE per direction and variable (24 WENO calls per cell and stage for V = 8, like the
 // reference's D6 kernel) and its two edge values are handed to the two adjacent faces without touching memory:
@@ -270,37 +270,6 @@ __device__ __forceinline__ void convert_cell_tracers(const DyP &p, const Coupler
 #pragma unroll
   for (int tr = 0; tr < 4; tr++) if (tr < Cf<K>::ntr(p)) s[(long long)(5 + tr) * sV] = r.tr[tr] * inv_den;
 }
-// stand-alone form (2-D runs, walls / open boundaries or a neighbour exchange in y, two-stream schedule)
-// (ylo, yhi: only the cells with j < ylo, j >= yhi or within HX cells of the block's west / east edge -- the strips that the pipelined
-//  multi-rank schedule packs and the rows its edge-strip y launch reads; the rest is converted inside k_y_all<true>.  ylo >= ny: all.)
-// (strips != 0: the launch covers the strip cells only -- whole rows j < ylo and j >= yhi first, then the 2 HX west / east columns of the rows
-//  between -- instead of all cells with most threads leaving at once: 50 -> a few us on the compute stream of a 400 x 400 x 100 block)
-__global__ __launch_bounds__(256) void k_coupler_to_state_fast(DyP p, CouplerPtrs c, double *__restrict__ S, int ylo, int yhi, int strips) {
-  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int k = blockIdx.y;
-  const int NXI = p.nx * p.nens;
-  int j, ie;
-  if (strips) {
-    const int hxn = p.HX * p.nens;
-    const long long nA = (long long)(ylo + p.ny - yhi) * NXI, nB = (long long)(yhi - ylo) * 2 * hxn;
-    if (t >= nA + nB) return;
-    if (t < nA) { const int jj = (int)(t / NXI); ie = (int)(t - (long long)jj * NXI); j = jj < ylo ? jj : yhi + (jj - ylo); }
-    else { const long long u = t - nA; const int r = (int)(u % (2 * hxn)); j = ylo + (int)(u / (2 * hxn)); ie = r < hxn ? r : NXI - 2 * hxn + r; }
-  } else {
-    if (t >= (long long)p.ny * NXI) return;
-    j = (int)(t / NXI); ie = (int)(t - (long long)j * NXI);
-  }
-  if (j >= ylo && j < yhi && ie >= p.HX * p.nens && ie < NXI - p.HX * p.nens) return;
-  const long long ci = ((long long)k * p.ny + j) * NXI + ie;
-  const CouplerCell r = load_coupler_cell(p, c, cpl(p, ci));
-  double s5[5], inv_den;
-  convert_cell_fast(p, r, k * p.nens + ie % p.nens, s5, inv_den);
-  double *s = S + (long long)(k + p.HZ) * p.sK + (long long)(j + p.HY) * p.sJ + (long long)p.HX * p.nens + ie;
-#pragma unroll
-  for (int v = 0; v < 5; v++) s[(long long)v * p.sV] = s5[v];
-  convert_cell_tracers(p, r, inv_den, s, p.sV);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // Zero-row maps (round 5).  Cloud water and rain are exactly zero over most of a supercell domain (all of it at the start), and after
 // the zero short-cut (MW_ZERO_SKIP) the fused tracer kernel is bound by the HBM traffic of values that are all zero.  The maps let it
@@ -318,7 +287,7 @@ __global__ __launch_bounds__(256) void k_coupler_to_state_fast(DyP p, CouplerPtr
 // exactly zero, and so is the tracer's new value.  The maps are a SUPERSET of the non-zero rows -- a set bit costs the loads, nothing
 // else -- and results equal the run without them (tests/: bitwise up to the sign of a zero; a skipped value enters as +0.0).
 // Handles: x and y periodic, the fused tracer stage; nens == 1 on one rank or as the blocks of a decomposed domain on the pipelined schedule,
-// member-major handles (nens > 1) on one rank with one map set per member (host side: zero_rows_ok / zero_rows_build in mw_dycore.hip).
+// member-major handles (nens > 1) on one rank with one map set per member (host side: zero_rows_ok / zero_rows_build in mw_march_sched.hip).
 // ---------------------------------------------------------------------------------------------------------------
 #define MW_ZR_REACH 3
 #define MW_ZR_HALO (3 * MW_ZR_REACH)                              // rows a tracer can travel in one sub-cycle = halo rows of the maps
@@ -416,6 +385,42 @@ __global__ __launch_bounds__(256) void k_zero_rows(DyP p, CouplerPtrs c, const d
     if (out2) out2[(long long)k * p.ny + j] = word;
   }
 }
+// ---------------------------------------------------------------------------------------------------------------
+// The NON-TEMPLATE kernels of this header.  A kernel is emitted into the code object of every unit that sees its definition (`inline` does
+// not apply to kernels), so exactly one unit may: mw_march_sched.hip defines MW_MARCH_SCHED_KERNELS and launches all of them.
+// ---------------------------------------------------------------------------------------------------------------
+#ifdef MW_MARCH_SCHED_KERNELS
+// stand-alone form (2-D runs, walls / open boundaries or a neighbour exchange in y, two-stream schedule)
+// (ylo, yhi: only the cells with j < ylo, j >= yhi or within HX cells of the block's west / east edge -- the strips that the pipelined
+//  multi-rank schedule packs and the rows its edge-strip y launch reads; the rest is converted inside k_y_all<true>.  ylo >= ny: all.)
+// (strips != 0: the launch covers the strip cells only -- whole rows j < ylo and j >= yhi first, then the 2 HX west / east columns of the rows
+//  between -- instead of all cells with most threads leaving at once: 50 -> a few us on the compute stream of a 400 x 400 x 100 block)
+__global__ __launch_bounds__(256) void k_coupler_to_state_fast(DyP p, CouplerPtrs c, double *__restrict__ S, int ylo, int yhi, int strips) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int k = blockIdx.y;
+  const int NXI = p.nx * p.nens;
+  int j, ie;
+  if (strips) {
+    const int hxn = p.HX * p.nens;
+    const long long nA = (long long)(ylo + p.ny - yhi) * NXI, nB = (long long)(yhi - ylo) * 2 * hxn;
+    if (t >= nA + nB) return;
+    if (t < nA) { const int jj = (int)(t / NXI); ie = (int)(t - (long long)jj * NXI); j = jj < ylo ? jj : yhi + (jj - ylo); }
+    else { const long long u = t - nA; const int r = (int)(u % (2 * hxn)); j = ylo + (int)(u / (2 * hxn)); ie = r < hxn ? r : NXI - 2 * hxn + r; }
+  } else {
+    if (t >= (long long)p.ny * NXI) return;
+    j = (int)(t / NXI); ie = (int)(t - (long long)j * NXI);
+  }
+  if (j >= ylo && j < yhi && ie >= p.HX * p.nens && ie < NXI - p.HX * p.nens) return;
+  const long long ci = ((long long)k * p.ny + j) * NXI + ie;
+  const CouplerCell r = load_coupler_cell(p, c, cpl(p, ci));
+  double s5[5], inv_den;
+  convert_cell_fast(p, r, k * p.nens + ie % p.nens, s5, inv_den);
+  double *s = S + (long long)(k + p.HZ) * p.sK + (long long)(j + p.HY) * p.sJ + (long long)p.HX * p.nens + ie;
+#pragma unroll
+  for (int v = 0; v < 5; v++) s[(long long)v * p.sV] = s5[v];
+  convert_cell_tracers(p, r, inv_den, s, p.sV);
+}
+
 // Decomposed block: M = own rows (compact) OR the west / east neighbours' (rW / rE, nullptr: x is not decomposed); the merged rows next
 // to the south / north edge are packed for those neighbours (sS / sN, nullptr: y is not decomposed -- the halo rows are then the block's
 // own periodic images).
@@ -467,7 +472,7 @@ __global__ __launch_bounds__(256) void k_zero_halo(DyP p, unsigned *__restrict__
 //   iteration k+2, in the lean form (zeros) exactly when Qs[k+2][j] was clear -- for every x tile of the row alike, the form follows from the
 //   row's word alone -- so where the previous Qs is clear the slab row holds zeros already and a lean iteration leaves it alone.  The host
 //   hands the previous maps over only when the previous sub-cycle ran with maps and nothing else has written the slabs since.
-#define MW_ZR_MAPS 10
+// (MW_ZR_MAPS, the number of maps per set: mw_common.h)
 // (fn_ones: FNs = "store" everywhere -- the local maps of a decomposed block cannot know what the neighbours make the tracer kernel read)
 __global__ __launch_bounds__(256) void k_zero_dilate(DyP p, unsigned *__restrict__ M, long long msz, int fn_ones) {
   constexpr int TK = 16, TJ = 64, R = MW_ZR_HALO, LO = R + MW_ZR_BEFORE + 1, HI = R + MW_ZR_AFTER + 1, EK = TK + LO + HI, EJ = TJ + 2 * R;
@@ -581,7 +586,7 @@ __global__ __launch_bounds__(256) void k_zero_verify(DyP p, CouplerPtrs c, const
   }
 }
 
-// Member-major handles (nens > 1, see View in mw_dycore.hip): the two conversions between the coupler's member-fastest arrays and
+// Member-major handles (nens > 1, see View in mw_dycore_int.h): the two conversions between the coupler's member-fastest arrays and
 // the member-after-member slabs, as coalesced passes.  thread = one cell in the COUPLER's order (fused x, member fastest): the
 // coupler side is a unit-stride stream, the slab side 16-lane segments of nens different members.  (Done from inside the
 // per-member marching kernels -- as on the nens = 1 path -- every launch would touch 1/nens of every cache line of the coupler's
@@ -639,6 +644,7 @@ __global__ __launch_bounds__(256) void k_member_to_coupler(DyP p, const double *
   c.u[ci] = s[(long long)idU * m.sV]; c.v[ci] = s[(long long)idV * m.sV]; c.w[ci] = s[(long long)idW * m.sV];
   c.temp[ci] = press / (rho_dry * p.R_d + rho_v * p.R_v);
 }
+#endif // MW_MARCH_SCHED_KERNELS
 
 // ---------------------------------------------------------------------------------------------------------------
 // Y pass, state variables.  thread = (k, interior fused-x lane), marches j over [ja-1, jb] for the chunk [ja, jb).
@@ -656,11 +662,7 @@ __global__ __launch_bounds__(256) void k_member_to_coupler(DyP p, const double *
 // MM = 2 (2 or 4 members): the per-member form of the launch -- wave = one member's 64 x cells, coalesced stores into that member's
 // arrays -- with the nens members of the same cells in ONE workgroup: their 8-byte reads of the coupler's member-fastest arrays, nens
 // doubles apart, then meet in the CU's L1 / the XCD's L2 (the same idea as MemberOff below for the way out).
-struct MemberOff {
-  long long slab, tend, mx, my, mz, fx, fy, fz, cells, per;    // doubles (selectors / flags: bytes) from member e to member e + 1
-  long long zq;                                                // ... and words, for the members' zero-row maps
-  int n, sh;                                                   // members per workgroup (2 or 4) and log2 of it
-};
+// (MemberOff: mw_common.h)
 struct YMember { long long sJ, sK, sV, slab, fyJ, fyK, mfy, nC, tend; int nx; long long per; int n, sh; };
 template <bool CONV, int K, int ORD, int MM = 0>
 __global__ __launch_bounds__(256, 2) void k_y_state(DyP p, const double *__restrict__ S, double *__restrict__ MY,

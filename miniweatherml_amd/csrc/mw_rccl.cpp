@@ -85,7 +85,7 @@ RcclApi &rccl_api() {
   RcclApi &R = rccl_api();                                                                              \
   if (!R.ok) MW_FAIL("RCCL is not available: no librccl.so is mapped in this process and none could be loaded")
 
-// Two LANES: the dycore's state and tracer pipelines (rk_stage_march in mw_dycore.hip) exchange their strips from two different
+// Two LANES: the dycore's state and tracer pipelines (rk_stage_march in mw_march_sched.hip) exchange their strips from two different
 // streams, each hiding the other's transfer.  Each lane has its own side stream and event pair, so that an exchange only waits for
 // the pack kernels of ITS pipeline and only its pipeline's unpack kernels wait for it.  A lane belongs to the first caller stream
 // that uses it; a third stream shares lane 0.

@@ -270,7 +270,7 @@ def test_unsupported_options_fail_loudly(mw):
 
 
 def test_a_block_whose_strides_leave_32_bits_is_refused(mw):
-    """The kernels' row / level / variable strides are 32-bit values (Stride32, csrc/mw_dycore.hip): a block with a variable of 2^31 or more
+    """The kernels' row / level / variable strides are 32-bit values (Stride32, csrc/mw_common.h): a block with a variable of 2^31 or more
     elements (16 GB; four slabs of six of them would not fit the GPU) must be refused at create -- before any large allocation -- not
     wrapped around.  The order change that widens the halo is held to the same rule."""
     import ctypes as C

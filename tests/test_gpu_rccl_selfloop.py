@@ -1,7 +1,7 @@
 """The asynchronous halo exchange inside RESULT-CHECKED time steps on one GPU (round 5).
 
 1. The real RCCL transport (mw_rccl.cpp: pack kernels -> ev_ready -> ncclGroup of sends and receives on the side stream -> ev_done ->
-   unpack kernels; the pipelined and the two-stream schedules of mw_dycore.hip around it).  A periodic domain tiled 2 x 2 or 4 x 2
+   unpack kernels; the pipelined and the two-stream schedules of mw_march_sched.hip around it).  A periodic domain tiled 2 x 2 or 4 x 2
    from copies of ONE block has neighbours whose strips are bit-identical to the block's own, so rank 0 of that decomposition with every
    peer mapped to itself on a 1-rank communicator (mw_dycore_use_rccl_self) exchanges exactly the messages the real job would -- and
    must equal the one-rank run of the block BITWISE.  (halo_exchange, dynamics_euler_stratified_wenofv.h:641-723; neighbour matrix

@@ -10,7 +10,8 @@ C=${MW_SRC_DIR:-$R/miniweatherml_amd/csrc}     # MW_SRC_DIR: another checkout's 
 mkdir -p $R/miniweatherml_amd/ab /tmp/mwvar_$name
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-gpu-rdc -Wno-unused-function -Wno-unused-variable -ffp-contract=on -I/opt/rocm/include"
 objs=""
-for s in mw_host.cpp mw_dycore.hip mw_kessler.hip mw_mlp.hip mw_column.hip mw_output.hip mw_netcdf.cpp mw_rccl.cpp mw_h5.cpp; do
+for f in $C/*.hip $C/*.cpp; do                 # every unit of THAT csrc directory: an older checkout has another list than this one
+  s=$(basename $f)
   o=/tmp/mwvar_$name/${s%.*}.o
   x=""; case $s in *.hip) x="-x hip";; esac
   extra=""; case $s in *.hip) extra="$*";; esac      # (the extra flags reach every HIP source: -DMW_KES_SWEEP=1, -DMW_ZERO_SKIP=0, ...)

@@ -2,6 +2,7 @@
 
     python tools/isa_histogram.py [--src mw_dycore.hip] [--csrc DIR] [--md] <kernel-substring> [...]     (-- extra hipcc flags)
 
+Without --src: the unit that launches the first filtered kernel (unit_of), mw_dycore.hip when none does.
 Compiles the source to device assembly (hipcc -S --offload-device-only) and, per kernel whose demangled name contains one of the
 substrings, counts instructions by class -- for the whole kernel and for its largest loop (the marching loop: the basic blocks
 between the back-edge target with the most instructions and its s_cbranch).  Classes:
@@ -38,7 +39,7 @@ def classify(op, rest):
         if re.match(r"v_(add|sub|subrev|mul|mad|lshl|lshr|ashr|and|or|xor|bfe|bfi|min|max|not|mbcnt|add3|lshl_add|lshl_or|and_or|or3|addc|subb|perm|alignbit|cvt)", op):
             return "int/address VALU"
         return "other VALU"
-    if op.startswith("s_load") or op.startswith("s_buffer_load") or op.startswith("s_store"):
+    if op.startswith(("s_load", "s_buffer_load")):                # (scalar memory is read-only in this project)
         return "SMEM"
     if op.startswith(("global_load", "flat_load", "buffer_load", "scratch_load")):
         return "VMEM load"
@@ -115,12 +116,29 @@ def detail_fp(items):
     return c
 
 
+def unit_of(csrc, filt):
+    """The *.hip of `csrc` that launches (or, for a kernel nobody launches through a macro, defines) a kernel whose name holds one of the
+    substrings `filt`: a kernel lives in the code object of the unit that instantiates it, wherever its text is."""
+    units = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    text = {u: open(os.path.join(csrc, u)).read() for u in units}
+    for pat in (r"(?:MW_KLAUNCH|hipLaunchKernelGGL)\(\(?\s*(?:mw::)?(\w+)", r"__global__[^;{]*?\bvoid\s+(\w+)\s*\("):
+        for u in units:
+            if any(f in k for k in re.findall(pat, text[u]) for f in filt):
+                return u
+        for h in sorted(f for f in os.listdir(csrc) if f.endswith(".h")):         # launched from a header: the unit that includes it
+            if any(f in k for k in re.findall(pat, open(os.path.join(csrc, h)).read()) for f in filt):
+                for u in units:
+                    if '#include "%s"' % h in text[u]:
+                        return u
+    return "mw_dycore.hip"
+
+
 def main():
     args = sys.argv[1:]
     extra = []
     if "--" in args:
         i = args.index("--"); extra = args[i + 1:]; args = args[:i]
-    src = "mw_dycore.hip"
+    src = None
     csrc = os.path.join(ROOT, "miniweatherml_amd", "csrc")
     md = False
     filt = []
@@ -134,6 +152,8 @@ def main():
             md = True
         else:
             filt.append(a)
+    if src is None:
+        src = unit_of(csrc, filt) if filt else "mw_dycore.hip"
     os.makedirs("/tmp/rr", exist_ok=True)
     out = "/tmp/rr/isa_%s.s" % os.path.splitext(src)[0]
     cmd = ["/opt/rocm/bin/hipcc"] + FLAGS + ["-x", "hip", "--offload-device-only", "-S", os.path.join(csrc, src), "-o", out] + extra

@@ -1,6 +1,7 @@
 """Compact per-kernel register / LDS / occupancy table of one HIP source (hipcc -Rpass-analysis=kernel-resource-usage), no GPU needed.
     python tools/kernel_resources.py [mw_dycore.hip] [filter-substring ...] [-- extra hipcc flags]
-Without a source: the one whose text holds the filter (mw_dycore.hip if it does, or if none does)."""
+Without a source: the unit that launches the filtered kernel (a kernel whose text is in a header is compiled by the unit that
+instantiates it: isa_histogram.unit_of); mw_dycore.hip when no unit names the filter."""
 import os
 import re
 import subprocess
@@ -14,13 +15,12 @@ if "--" in args:
 filt = [a for a in args if not a.endswith((".hip", ".cpp"))]
 src = args[0] if args and args[0].endswith((".hip", ".cpp")) else "mw_dycore.hip"
 if not (args and args[0].endswith((".hip", ".cpp"))) and filt:
-    # no source named: the HIP source that defines the filtered kernels (e.g. `k_surrogate` -> mw_train.hip), else the dycore's
-    csrc = os.path.join(root, "miniweatherml_amd", "csrc")
-    hits = sorted(f for f in os.listdir(csrc) if f.endswith(".hip") and any(x in open(os.path.join(csrc, f)).read() for x in filt))
-    src = "mw_dycore.hip" if not hits or "mw_dycore.hip" in hits else hits[0]
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from isa_histogram import unit_of
+    src = unit_of(os.path.join(root, "miniweatherml_amd", "csrc"), filt)
 path = os.path.join(root, "miniweatherml_amd", "csrc", src)
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-ffp-contract=on", "-I/opt/rocm/include",
-       "-x", "hip", "-c", path, "-o", "/tmp/rr/kr.o", "-Rpass-analysis=kernel-resource-usage"] + extra
+       "-x", "hip", "-c", path, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"] + extra
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for ln in out.splitlines():
