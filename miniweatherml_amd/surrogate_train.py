@@ -147,6 +147,15 @@ def nadam_table(steps, learning_rate=1e-3, beta1=0.9, beta2=0.999, schedule_deca
     return np.ascontiguousarray(tab, dtype=dtype)
 
 
+def kernel_nadam_table(steps, learning_rate=1e-3, first_step=0):
+    """The table the trainer's kernel takes.  The kernel receives beta2 as fp32 and runs v <- b v + (1 - b) g^2 with b = fp32(0.999) =
+    0.999000013: 1 - b is exact in fp32 and 1.3e-5 (relative) below 1e-3.  The bias correction 1 - beta2^t must be the one of THAT
+    recursion; built from 0.999 it leaves every sqrt(v_hat) 6.4e-6 too small, every step as much too long -- a one-sided error 50 times
+    fp32's rounding, which adds up along the trajectory ("Gradient and trajectory accuracy").  beta1 needs no such
+    care: Keras' Nadam corrects m with the momentum schedule, not with 1 - beta1^t."""
+    return nadam_table(steps, learning_rate, NADAM["beta1"], float(np.float32(NADAM["beta2"])), NADAM["schedule_decay"], first_step)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # data and arguments (host checks: they run before anything reaches the device)
 def read_samples(sample_files, stencil=False):
@@ -299,8 +308,7 @@ class Trainer:
         self.m1 = torch.zeros((self.K, NP), dtype=f32, device=dev)
         self.m2 = torch.zeros((self.K, NP), dtype=f32, device=dev)
         self.lr = float(learning_rate)
-        self.table = torch.from_numpy(nadam_table(self.steps * int(epochs), self.lr, NADAM["beta1"], NADAM["beta2"],
-                                                  NADAM["schedule_decay"])).to(dev)
+        self.table = torch.from_numpy(kernel_nadam_table(self.steps * int(epochs), self.lr)).to(dev)
         # validation predictions: groups of models whose (4, n_val) outputs fit in 1 GiB
         self.group = max(1, min(self.K, (1 << 30) // (16 * self.n_val)))
         self.pred = torch.empty(self.group * 4 * max(self.n_val, self.n_test), dtype=f32, device=dev)

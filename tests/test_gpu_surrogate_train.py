@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+from surrogate_ref import (GRAD_BATCHES, check_rho, check_test_metrics, deviations, device_batch_grad, gradient_case, host_sets, replay,
+                           signs_ok, torch_forward, torch_model)
 from test_surrogate_train_cpu import write_sample_file
 from util import push_fields
 
@@ -25,60 +27,23 @@ def kessler_like(n, seed):
     return ins.astype(np.float32), y.astype(np.float32)
 
 
-def host_sets(inputs, outputs, split_seed, test_split=0.2, validation_split=0.2):
-    """The device's prepare step restated: pre-shuffle, min-max scaling in fp64 rounded to fp32, [train | val | test]."""
-    from miniweatherml_amd import surrogate_train as st
-    n = inputs.shape[0]
-    perm = st.preshuffle_permutation(n, split_seed)
-    lo_i, hi_i, lo_o, hi_o = inputs.min(0), inputs.max(0), outputs.min(0), outputs.max(0)
-    xs = ((inputs[perm].astype(np.float64) - lo_i) / (hi_i.astype(np.float64) - lo_i)).astype(np.float32)
-    ys = ((outputs[perm].astype(np.float64) - lo_o) / (hi_o.astype(np.float64) - lo_o)).astype(np.float32)
-    n_train, n_val, _ = st.split_sizes(n, test_split, validation_split)
-    cut = [0, n_train, n_train + n_val, n]
-    return [(xs[cut[k]:cut[k + 1]], ys[cut[k]:cut[k + 1]]) for k in range(3)]
-
-
-def torch_model(w104):
-    import torch
-    w = torch.tensor(np.asarray(w104, dtype=np.float64))
-    return [w[:50].reshape(5, 10).clone().requires_grad_(), w[50:60].clone().requires_grad_(), w[60:100].reshape(10, 4).clone().requires_grad_(),
-            w[100:].clone().requires_grad_()]
-
-
-def torch_forward(P, x):
-    import torch
-    return torch.nn.functional.leaky_relu(x @ P[0] + P[1], 0.1) @ P[2] + P[3]
-
-
-@pytest.mark.parametrize("batch", [1024, 300])
+@pytest.mark.parametrize("batch", GRAD_BATCHES)
 def test_batch_gradient_matches_torch_autograd(mw, batch):
+    """Batch sizes where the masking, the wave split and the chunk loop change shape: one sample, below one wave, around 64 and 256, and
+    MW_SURROGATE_MAX_BATCH.  fp32 summation in the worst order stays at or below 2.4e-6 of max|g| for every one of them (CPU), torch
+    fp32's loss at or below 2.3e-7: the two bounds hold for any order.  rho is the per-entry statement (tests/surrogate_ref.py)."""
     import torch
-    from miniweatherml_amd import capi
-    rng = np.random.default_rng(batch)
-    w = (rng.standard_normal(104) * 0.6).astype(np.float32)
-    w[50:60] -= 0.5                                                   # hidden pre-activations of both signs
-    x = rng.random((5, batch), dtype=np.float32)
-    y = rng.random((4, batch), dtype=np.float32)
-    dev = [torch.from_numpy(a).cuda() for a in (w, x, y)]
-    grad = torch.empty(104, dtype=torch.float32, device="cuda")
-    loss = torch.empty(1, dtype=torch.float32, device="cuda")
-    capi.check(capi.lib().mw_surrogate_batch_grad(*[C_ptr(t) for t in dev], batch, C_ptr(grad), C_ptr(loss), None))
-    torch.cuda.synchronize()
+    w, x, y = gradient_case(5, batch)
+    g, loss = device_batch_grad(5, w, x, y, v2=False)
     P = torch_model(w)
     xt = torch.tensor(x.T.astype(np.float64))
-    pre = xt @ P[0] + P[1]
-    assert (pre > 0).double().mean() > 0.1 and (pre < 0).double().mean() > 0.1
+    assert signs_ok(5, w, x)
     ref = torch.nn.functional.mse_loss(torch_forward(P, xt), torch.tensor(y.T.astype(np.float64)))
     ref.backward()
     g_ref = np.concatenate([p.grad.numpy().ravel() for p in P])
-    g = grad.cpu().numpy().astype(np.float64)
+    check_rho(5, w, x, y, g, "single cell, batch %d" % batch)
     assert np.max(np.abs(g - g_ref)) <= 1e-5 * np.max(np.abs(g_ref)), np.max(np.abs(g - g_ref)) / np.max(np.abs(g_ref))
-    assert abs(float(loss.cpu()[0]) - float(ref.detach())) <= 1e-6 * float(ref.detach())
-
-
-def C_ptr(t):
-    import ctypes
-    return ctypes.c_void_p(t.data_ptr())
+    assert abs(loss - float(ref.detach())) <= 1e-6 * float(ref.detach())
 
 
 @pytest.fixture(scope="module")
@@ -87,11 +52,20 @@ def file20k(tmp_path_factory):
     return write_sample_file(tmp_path_factory.mktemp("s20k") / "s.nc", [(ins[:7000], outs[:7000]), (ins[7000:], outs[7000:])]), ins, outs
 
 
+# max|dw| / max|w|, then loss, val_loss, mean_absolute_error, val_mean_absolute_error (largest relative deviation over the epochs).
+# Measured on the MI355X: 2.99e-7, 3.49e-8, 8.51e-9, 2.78e-8, 5.15e-9; bounds = 3 x measured, rounded up to one digit.  torch's fp32
+# replay on the CPU deviates from the fp64 one by 2.5e-7, 8.1e-9, 1.0e-7, 7.2e-9, 2.7e-8 (tests/surrogate_ref.py: replay).
+TRAJECTORY_BOUNDS = (9e-7, 2e-7, 3e-8)
+MAE_BOUNDS = (9e-8, 2e-8)
+
+
 def test_two_epoch_trajectory_matches_torch_nadam(mw, file20k):
     """2 epochs on 20,000 samples at batch 1024 (12,800 training samples: 13 steps per epoch, the last one partial) from the product's
     seeded initial weights in the product's batch order, against torch fp64 (Linear -> leaky_relu(0.1) -> Linear, mse_loss, NAdam(eps=1e-7,
-    momentum_decay=4e-3)).  Measured on the MI355X (first run): max|dw| = 5.9e-6 of max|w|; per-epoch loss 5.9e-7 and val_loss 9.3e-7
-    relative.  Bounds with >= 3x margin: 2e-5, 2e-6, 3e-6."""
+    momentum_decay=4e-3)).  First bounds (>= 3x the first run: max|dw| = 5.9e-6 of max|w|, loss 5.9e-7, val_loss 9.3e-7 relative): 2e-5,
+    2e-6, 3e-6.  Those figures were 23 times torch fp32's own deviation: the bias correction was built from beta2 = 0.999 while the kernel
+    runs fp32(0.999) (surrogate_train.kernel_nadam_table).  With that mended the run stays at fp32's level; both sets of bounds are
+    asserted, TRAJECTORY_BOUNDS being the tighter."""
     import torch
     from miniweatherml_amd import surrogate_train as st
     path, ins, outs = file20k
@@ -99,31 +73,13 @@ def test_two_epoch_trajectory_matches_torch_nadam(mw, file20k):
     r = st.train_surrogate([path], epochs=2, batch_size=1024, seed=seed)
     (tx, ty), (vx, vy), _ = host_sets(ins[:, :, 0], outs, seed)
     assert (r["n_train"], r["n_val"], r["n_test"]) == (12800, 3200, 4000) and len(tx) == 12800
-    P = torch_model(st.initial_weights(seed, 1)[0])
-    opt = torch.optim.NAdam(P, lr=1e-3, betas=(0.9, 0.999), eps=1e-7, momentum_decay=4e-3)
-    X, Y, VX, VY = [torch.tensor(a.astype(np.float64)) for a in (tx, ty, vx, vy)]
-    losses, vlosses = [], []
-    for e in range(2):
-        order = torch.from_numpy(st.epoch_permutation(len(tx), seed, 0, e))
-        tot = 0.0
-        for s in range(0, len(tx), 1024):
-            idx = order[s:s + 1024]
-            opt.zero_grad()
-            loss = torch.nn.functional.mse_loss(torch_forward(P, X[idx]), Y[idx])
-            loss.backward()
-            opt.step()
-            tot += float(loss.detach()) * len(idx)
-        losses.append(tot / len(tx))
-        with torch.no_grad():
-            vlosses.append(float(torch.nn.functional.mse_loss(torch_forward(P, VX), VY)))
-    w_ref = np.concatenate([p.detach().numpy().ravel() for p in P])
+    w_ref, h_ref = replay(torch.float64, [(tx, ty), (vx, vy)], seed, 1024, 2, 1e-3, stencil=False)
     w = r["weights"][0].astype(np.float64)
-    dw = np.max(np.abs(w - w_ref)) / np.max(np.abs(w_ref))
-    h = r["history"][0]
-    dl = max(abs(a - b) / b for a, b in zip(h["loss"], losses))
-    dv = max(abs(a - b) / b for a, b in zip(h["val_loss"], vlosses))
-    print("trajectory: max|dw|/max|w| %.2e, loss %.2e, val_loss %.2e" % (dw, dl, dv))
+    dw, dl, dm, dv, dvm = deviations(w, r["history"][0], w_ref, h_ref)
+    print("trajectory: max|dw|/max|w| %.2e, loss %.2e, val_loss %.2e, mean_absolute_error %.2e, val_mean_absolute_error %.2e" % (dw, dl, dv, dm, dvm))
     assert dw <= 2e-5 and dl <= 2e-6 and dv <= 3e-6
+    assert dw <= TRAJECTORY_BOUNDS[0] and dl <= TRAJECTORY_BOUNDS[1] and dv <= TRAJECTORY_BOUNDS[2]
+    assert dm <= MAE_BOUNDS[0] and dvm <= MAE_BOUNDS[1]
     assert np.max(np.abs(w - st.initial_weights(seed, 1)[0])) > 5e-3           # it moved
 
 
@@ -201,7 +157,8 @@ def test_generate_train_infer_end_to_end(mw, oracle, tmp_path):
         assert np.max(np.abs(o.cpu().numpy() - rr)) <= 1e-5 * (so[k, 1] - so[k, 0]), k
     golden = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "surrogate_notebook_metrics.json")))
     tm = r["test_metrics"]
+    ref = check_test_metrics(r, host_sets(*st.read_samples([gen.fname])[:2], 0)[2], "end to end")
     for key in ("max_relative_error", "mean_relative_error"):
         print("%-20s here %s | notebook %s" % (key, np.array2string(np.array(tm[key]), precision=5), golden[key.replace("error", "test_errors")]))
-    print("%-20s here %s" % ("mean_relative_bias", np.array2string(np.array(tm["mean_relative_bias"]), precision=5)))
+    assert np.all(ref["max_relative_error"] > 0) and np.all(ref["mean_relative_error"] > 0)
     assert json.load(open(os.path.join(out_dir, "history.json")))["best_model"] == 0
