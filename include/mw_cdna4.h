@@ -477,6 +477,32 @@ int  mw_surrogate_batch_grad_v2(int n_in, const float *params, const float *x, c
 long long mw_surrogate_errors_workspace_bytes(int nsets);
 int  mw_surrogate_errors(long long n, int nsets, const float *pred, const float *y, void *workspace, double *out, void *stream);
 
+/* ---- surrogate evaluation in the model loop ------------------------------------------------------------- */
+/* A bank of `models` candidate networks of ONE width, scored against what the microphysics really did to a state: the four `Relative diff`
+ * prints of microphysics_kessler_ponni.h:266-269 for many models at once, split by output field and by the active / inactive classes of
+ * StatisticsGatherer::is_active (gather_micro_statistics.h:61-74), in one pass over the state per group of models and without writing
+ * a prediction to memory.  The handle uploads the models' MFMA operand images and scaling tables once.
+ * n_in 5 (single cell) or 9 (stencil); params HOST (models, 104 | 144) fp32 in the weights.txt order (W1, b1, W2, b2); scl_in HOST
+ * (models, n_in, 2), scl_out HOST (models, 4, 2) fp64 [min,max] rows -- PER MODEL, so that models of different training runs can sit in
+ * one bank.  1 <= models <= MW_SURROGATE_MAX_MODELS.  A scaling row with max == min is an error. */
+typedef struct mw_surrogate_bank_s *mw_surrogate_bank_t;
+int  mw_surrogate_bank_create(mw_surrogate_bank_t *b, int n_in, int models, const float *params, const double *scl_in,
+                              const double *scl_out);
+void mw_surrogate_bank_destroy(mw_surrogate_bank_t b);
+/* G: the number of models the MFMA kernels evaluate per pass over the state (more models: ceil(models / G) passes in one launch). */
+int  mw_surrogate_eval_group(mw_surrogate_bank_t b);
+/* in5: HOST array of 5 DEVICE fp64 fields before the microphysics call (temp, density_dry, water_vapor, cloud_liquid, precip_liquid),
+ * level-major (nz, ncol); truth4: the 4 fields after it (temp, water_vapor, cloud_liquid, precip_liquid).
+ * out: DEVICE fp64 (models + 1, 2, 4, 4) = [model][class][field][statistic]: class 0 = inactive, 1 = active (any of the four
+ * |after - before| > 1e-10); statistics sum d, sum |d|, sum d^2, max |d| of d = prediction - truth over the cells of the class.  Row
+ * `models` is the persistence baseline (prediction = the input field).  counts: DEVICE int64 [2], the cells per class.
+ * Model m's prediction is bit for bit what mw_mlp_forward / mw_mlp_stencil_forward write for its weights and scaling (mw_mlp_set_strict is
+ * honoured); the reduction order is fixed and independent of the number of models and of a model's position in the bank.  Nothing is
+ * written to in5 / truth4.  Asynchronous on `stream`; one call at a time per bank (the handle owns the partial sums' workspace, which
+ * grows -- synchronising -- when a call needs more). */
+int  mw_surrogate_eval(mw_surrogate_bank_t b, int nz, long long ncol, const double *const *in5, const double *const *truth4,
+                       double *out, long long *counts, void *stream);
+
 /* ---- DataManager validators ---------------------------------------------------------------------------- */
 /* core::DataManager::validate / validate_nan / validate_inf / validate_pos (model/core/DataManager.h:385-483) -- the reference's only
  * built-in health check: it copies an entry to the host and loops over it.  Here ONE device pass over the entry's `n` elements

@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MW_LIB_PATH") or os.path.join(_HERE, "libmw_cdna4.so")      # (MW_LIB_PATH: compiler-flag experiments)
 
 MW_MAX_TRACERS = 16
+MW_SURROGATE_MAX_MODELS = 256
 DATA_THERMAL, DATA_SUPERCELL, DATA_CITY, DATA_BUILDING = 0, 1, 2, 3
 BC_PERIODIC, BC_OPEN, BC_WALL = 0, 1, 2
 INIT_IDS = {"thermal": DATA_THERMAL, "supercell": DATA_SUPERCELL, "city": DATA_CITY, "building": DATA_BUILDING}
@@ -148,6 +149,10 @@ SYMBOLS = {
     "mw_surrogate_batch_grad_v2": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mw_surrogate_errors_workspace_bytes": (C.c_longlong, [C.c_int]),
     "mw_surrogate_errors": (C.c_int, [C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mw_surrogate_bank_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "mw_surrogate_bank_destroy": (None, [C.c_void_p]),
+    "mw_surrogate_eval_group": (C.c_int, [C.c_void_p]),
+    "mw_surrogate_eval": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mw_validate_f64": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]),
     "mw_validate_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]),
     "mw_mlp_stencil_forward": (C.c_int, [C.c_int, C.c_longlong] + [C.c_void_p] * 5 + [C.POINTER(C.c_float)] * 4 +

@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 #include <algorithm>
 
 namespace mw {
@@ -521,6 +522,26 @@ extern "C" int mw_mlp_stencil_chunk(int nz, long long ncol) {
   return (int)((nz + want - 1) / want);
 }
 
+// The operand images of the 9 -> 10 -> 4 stencil stack (k_mlp_stencil's header): layer 2 and the biases are the single-cell images.
+static void build_stencil_images(StencilP &P, const float *W1, const float *b1, const float *W2, const float *b2) {
+  MlpP Q;                                                       // layer 2 and the biases: the single-cell images (W1 rows are placed below)
+  build_operand_images(Q, W1, b1, W2, b2, 0);
+  memset(&P, 0, sizeof(P));
+  memcpy(P.c1, Q.c1, sizeof(P.c1)); memcpy(P.a2, Q.a2, sizeof(P.a2)); memcpy(P.c2, Q.c2, sizeof(P.c2));
+  auto rho = [](int u) { return (u / 3) * 4 + (u % 3); };      // hidden unit u -> D1 row (build_operand_images)
+  const int above_of_group[4] = {5, -1, 6, 7};
+  for (int lane = 0; lane < 64; lane++) {
+    const int o = lane & 15, g = lane >> 4;
+    int u = -1;
+    for (int uu = 0; uu < 10; uu++) if (rho(uu) == o) u = uu;
+    if (u < 0) continue;
+    P.a1[0][lane] = W1[g * 10 + u];
+    P.a1[1][lane] = above_of_group[g] >= 0 ? W1[above_of_group[g] * 10 + u] : 0.f;
+    P.a1[2][lane] = g == 0 ? W1[4 * 10 + u] : g == 1 ? W1[8 * 10 + u] : 0.f;      // even k: group 0 holds level k, group 1 level k + 1
+    P.a1[3][lane] = g == 0 ? W1[8 * 10 + u] : g == 1 ? W1[4 * 10 + u] : 0.f;      // odd k: the other way round
+  }
+}
+
 extern "C" int mw_mlp_stencil_forward(int nz, long long ncol, const double *temp, const double *rho_d, const double *rho_v,
                                       const double *rho_c, const double *rho_r, const float *W1, const float *b1, const float *W2,
                                       const float *b2, const double *scl_in, const double *scl_out, double *temp_out, double *rho_v_out,
@@ -544,24 +565,7 @@ extern "C" int mw_mlp_stencil_forward(int nz, long long ncol, const double *temp
     return 0;
   }
   StencilP P;
-  {
-    MlpP Q;                                                     // layer 2 and the biases: the single-cell images (W1 rows are placed below)
-    build_operand_images(Q, W1, b1, W2, b2, 0);
-    memset(&P, 0, sizeof(P));
-    memcpy(P.c1, Q.c1, sizeof(P.c1)); memcpy(P.a2, Q.a2, sizeof(P.a2)); memcpy(P.c2, Q.c2, sizeof(P.c2));
-    auto rho = [](int u) { return (u / 3) * 4 + (u % 3); };    // hidden unit u -> D1 row (build_operand_images)
-    const int above_of_group[4] = {5, -1, 6, 7};
-    for (int lane = 0; lane < 64; lane++) {
-      const int o = lane & 15, g = lane >> 4;
-      int u = -1;
-      for (int uu = 0; uu < 10; uu++) if (rho(uu) == o) u = uu;
-      if (u < 0) continue;
-      P.a1[0][lane] = W1[g * 10 + u];
-      P.a1[1][lane] = above_of_group[g] >= 0 ? W1[above_of_group[g] * 10 + u] : 0.f;
-      P.a1[2][lane] = g == 0 ? W1[4 * 10 + u] : g == 1 ? W1[8 * 10 + u] : 0.f;      // even k: group 0 holds level k, group 1 level k + 1
-      P.a1[3][lane] = g == 0 ? W1[8 * 10 + u] : g == 1 ? W1[4 * 10 + u] : 0.f;      // odd k: the other way round
-    }
-  }
+  build_stencil_images(P, W1, b1, W2, b2);
   for (int i = 0; i < 9; i++) { P.in_min[i] = scl_in[i * 2 + 0]; P.in_rng[i] = scl_in[i * 2 + 1] - scl_in[i * 2 + 0]; }
   for (int i = 0; i < 4; i++) { P.out_min[i] = scl_out[i * 2 + 0]; P.out_rng[i] = scl_out[i * 2 + 1] - scl_out[i * 2 + 0]; }
   const int zc = mw_mlp_stencil_chunk(nz, ncol), nchunks = (nz + zc - 1) / zc;
@@ -569,6 +573,489 @@ extern "C" int mw_mlp_stencil_forward(int nz, long long ncol, const double *temp
   if (blocks > 0x7fffffffll) MW_FAIL("mlp_stencil: grid too large");
   hipLaunchKernelGGL(k_mlp_stencil<4>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, nz, ncol, zc, nchunks, temp, rho_d, rho_v,
                      rho_c, rho_r, temp_out, rho_v_out, rho_c_out, rho_r_out);
+  MW_LAUNCH_CHECK();
+  return 0;
+}
+
+// =====================================================================================================
+// IN-LOOP EVALUATION of a bank of models (mw_surrogate_eval): while Kessler runs the simulation, every candidate network is scored
+// against what Kessler did to the state -- sum d, sum |d|, sum d^2, max |d| of d = prediction - truth per output field, separately for
+// the inactive / active cells of StatisticsGatherer::is_active (gather_micro_statistics.h:61-74), plus the persistence baseline
+// (prediction = input).  No prediction reaches memory.
+//
+// k_surrogate_eval / k_surrogate_eval_stencil are k_mlp's / k_mlp_stencil's tiles with a loop over a group of G models inside: a wave
+// loads its inputs once, takes each model's A operands, biases and scaling constants from LDS and keeps 8 fp64 sums per model in
+// registers (lane group g ends up holding output g, so a lane needs field g of the truth and the input field that output g replaces:
+// the latter is one more load for groups 1..3, of a line another group of the same wave fetches anyway).  The class flag of a cell is
+// the OR over its four lane groups: one ballot, folded by two shifts.  Per cell the arithmetic is the forward kernels' own, expression
+// for expression (the reciprocal ranges come from the same device division), so a prediction has the bits those kernels store.
+// Reduction: per lane in loop order, an xor tree over the 16 lanes of a group, the block's four waves in order, then
+// k_surrogate_eval_final over the blocks in order -- no floating-point atomics.  grid.x depends on the shape alone and grid.y carries the
+// groups of models, so a model's row does not depend on the size of the bank or on its place in it.
+// =====================================================================================================
+namespace mw {
+
+constexpr int EVAL_G5 = 6, EVAL_G9 = 4;    // models per pass, single-cell / stencil: 16 accumulator registers per model + the persistence row's 16,
+                                           // the largest groups that leave two waves per SIMD
+constexpr int EVAL_MAX_BLOCKS = 1024;      // grid.x: grid-stride beyond 4 blocks per CU
+constexpr int EVAL_ROW = 32;               // doubles per model: [class 2][field 4][statistic 4]
+
+struct EvalModel {                         // one model as the MFMA kernels read it from LDS
+  float a1[4][64];                         // n_in 5: MlpP::a1[0..1]; n_in 9: StencilP::a1[0..3]
+  float a2[3][64];
+  float c1[4][4];
+  float c2[4];
+  double in_min[9], in_irng[9];            // in_irng: uploaded as the range, inverted on the device by k_surrogate_bank_recip
+  double out_min[4], out_rng[4];
+};
+struct EvalFields { const double *in[5], *truth[4]; };
+struct EvalAcc { double s[2][4]; };        // [class][sum d, sum |d|, sum d^2, max |d|]
+
+// the larger of two |d|, NaN if either is: a diverged model must not show a finite maximum (fmax would drop the NaN)
+__device__ __forceinline__ double eval_max(double a, double b) { return (b > a || b != b) ? b : a; }
+// one cell of one field: d joins the sums of the cell's class (adding +0.0 elsewhere leaves a sum's bits alone)
+__device__ __forceinline__ void eval_add(EvalAcc &a, double pred, double truth, bool inactive, bool active) {
+#pragma clang fp contract(off)
+  const double d = pred - truth;
+  const double d0 = inactive ? d : 0.0, d1 = active ? d : 0.0;
+  a.s[0][0] += d0; a.s[0][1] += fabs(d0); a.s[0][2] += d0 * d0; a.s[0][3] = eval_max(a.s[0][3], fabs(d0));
+  a.s[1][0] += d1; a.s[1][1] += fabs(d1); a.s[1][2] += d1 * d1; a.s[1][3] = eval_max(a.s[1][3], fabs(d1));
+}
+__device__ __forceinline__ void eval_zero(EvalAcc &a) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) a.s[i >> 2][i & 3] = 0.0;
+}
+// fixed xor tree over LANES neighbouring lanes; every lane ends with the result
+template <int LANES> __device__ __forceinline__ double eval_lane_tree(double v, bool is_max) {
+#pragma unroll
+  for (int off = LANES / 2; off > 0; off >>= 1) { const double o = __shfl_xor(v, off, 64); v = is_max ? eval_max(v, o) : v + o; }
+  return v;
+}
+// the class of the wave's 16 cells from the four lane groups' flags: bit c of the result = some group of cell c raised its flag
+__device__ __forceinline__ bool eval_cell_active(bool flag, int cidx) {
+  unsigned long long b = __ballot(flag);
+  b |= b >> 32; b |= b >> 16;
+  return (b >> cidx) & 1ull;
+}
+
+__global__ __launch_bounds__(64) void k_surrogate_bank_recip(EvalModel *bank, int n_in) {
+  if ((int)threadIdx.x < n_in) bank[blockIdx.x].in_irng[threadIdx.x] = 1.0 / bank[blockIdx.x].in_irng[threadIdx.x];   // k_mlp's `1.0 / P.in_rng[g]`
+}
+
+// the tail of both MFMA kernels: lanes -> groups of 16 -> the block's waves -> this block's row of partial sums
+template <int G>
+__device__ __forceinline__ void eval_block_store(EvalAcc (&acc)[G], EvalAcc &accp, long long nact, int cnt, int m0, int models,
+                                                 double *__restrict__ partial, long long *__restrict__ cpartial) {
+  __shared__ double red[4][4][(G + 1) * 8];
+  __shared__ long long wcount[4];
+  const int lane = threadIdx.x & 63, g = lane >> 4, cidx = lane & 15, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j <= G; j++) {
+    EvalAcc &a = j < G ? acc[j < G ? j : 0] : accp;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const double v = eval_lane_tree<16>(a.s[i >> 2][i & 3], (i & 3) == 3);
+      if (cidx == 0) red[wv][g][j * 8 + i] = v;
+    }
+  }
+  if (lane == 0) wcount[wv] = nact;
+  __syncthreads();
+  for (int e = threadIdx.x; e < (G + 1) * EVAL_ROW; e += 256) {
+    const int j = e >> 5, r = e & 31, c = r >> 4, v = (r >> 2) & 3, s = r & 3;
+    if (j < G ? j >= cnt : blockIdx.y != 0) continue;              // the persistence row leaves from the first group's blocks
+    double q = red[0][v][j * 8 + c * 4 + s];
+#pragma unroll
+    for (int w = 1; w < 4; w++) { const double o = red[w][v][j * 8 + c * 4 + s]; q = s == 3 ? eval_max(q, o) : q + o; }
+    const int row = j < G ? m0 + j : models;
+    partial[((long long)blockIdx.x * (models + 1) + row) * EVAL_ROW + r] = q;
+  }
+  if (threadIdx.x == 0 && blockIdx.y == 0) cpartial[blockIdx.x] = wcount[0] + wcount[1] + wcount[2] + wcount[3];
+}
+
+template <int G>
+__device__ __forceinline__ void eval_load_models(EvalModel (&sm)[G], const EvalModel *__restrict__ bank, int m0, int cnt) {
+  const unsigned *src = (const unsigned *)(bank + m0);
+  unsigned *dst = (unsigned *)sm;
+  for (int i = threadIdx.x; i < cnt * (int)(sizeof(EvalModel) / 4); i += 256) dst[i] = src[i];
+  __syncthreads();
+}
+
+template <int G, int TILES>
+__global__ __launch_bounds__(256) void k_surrogate_eval(const EvalModel *__restrict__ bank, int models, long long ncells, EvalFields F,
+                                                        double *__restrict__ partial, long long *__restrict__ cpartial) {
+#pragma clang fp contract(off)
+  __shared__ EvalModel sm[G];
+  const int m0 = blockIdx.y * G, cnt = min(G, models - m0);
+  eval_load_models<G>(sm, bank, m0, cnt);
+  const int lane = threadIdx.x & 63;
+  const int g = lane >> 4, cidx = lane & 15;
+  const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
+  const long long nwaves = ((long long)gridDim.x * 256) >> 6;
+  const double *in_g = F.in[g], *in_s = F.in[g == 0 ? 4 : g + 1], *tr_g = F.truth[g];     // in_s: rho_r for the network (group 0), else the field output g replaces
+  EvalAcc acc[G], accp;
+#pragma unroll
+  for (int j = 0; j < G; j++) eval_zero(acc[j]);
+  eval_zero(accp);
+  long long nact = 0;
+  const long long ntiles = (ncells + 15) / 16;
+  for (long long t0 = wave * TILES; t0 < ntiles; t0 += nwaves * TILES) {
+    double xin[TILES], xs[TILES], xt[TILES];
+    bool ina[TILES], inn[TILES];
+#pragma unroll
+    for (int u = 0; u < TILES; u++) {
+      const long long cell = (t0 + u) * 16 + cidx;
+      const bool ok = cell < ncells;
+      xin[u] = ok ? in_g[cell] : 0.0;
+      xs[u]  = ok ? in_s[cell] : 0.0;
+      xt[u]  = ok ? tr_g[cell] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < TILES; u++) {
+      const bool ok = (t0 + u) * 16 + cidx < ncells;
+      const double before = g == 0 ? xin[u] : xs[u];
+      const bool act = eval_cell_active(ok && fabs(xt[u] - before) > 1.e-10, cidx);          // gather_micro_statistics.h:61-74
+      ina[u] = ok && act; inn[u] = ok && !act;
+      nact += __popcll(__ballot(ina[u] && g == 0));
+      eval_add(accp, before, xt[u], inn[u], ina[u]);
+    }
+#pragma unroll
+    for (int j = 0; j < G; j++) {
+      if (j < cnt) {                                                                          // (block-uniform)
+        const EvalModel &M = sm[j];
+        const double imin = M.in_min[g], irng = M.in_irng[g], imin4 = M.in_min[4], irng4 = M.in_irng[4];
+        const double omin = M.out_min[g], orng = M.out_rng[g];
+        const float a10 = M.a1[0][lane], a11 = M.a1[1][lane];
+        const float a20 = M.a2[0][lane], a21 = M.a2[1][lane], a22 = M.a2[2][lane];
+        const f32x4 c1 = {M.c1[g][0], M.c1[g][1], M.c1[g][2], M.c1[g][3]};
+        const f32x4 c2 = {M.c2[g], 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < TILES; u++) {                                                     // k_mlp's cell, expression for expression
+          float b0 = (float)((xin[u] - imin) * irng);
+          float b1 = (g == 0) ? (float)((xs[u] - imin4) * irng4) : 0.f;
+          f32x4 d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a10, b0, c1, 0, 0, 0);
+          d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a11, b1, d1, 0, 0, 0);
+          float h0 = leaky(d1[0]), h1 = leaky(d1[1]), h2 = leaky(d1[2]);
+          f32x4 d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a20, h0, c2, 0, 0, 0);
+          d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a21, h1, d2, 0, 0, 0);
+          d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a22, h2, d2, 0, 0, 0);
+          double y = (double)d2[0] * orng + omin;
+          if (g != 0) y = fmax(0.0, y);
+          eval_add(acc[j], y, xt[u], inn[u], ina[u]);
+        }
+      }
+    }
+  }
+  eval_block_store<G>(acc, accp, nact, cnt, m0, models, partial, cpartial);
+}
+
+// k_mlp_stencil's sweep (a wave owns 16 columns x one z chunk at a time, top-down) with the models inside.  What that kernel carries from
+// level to level as scaled floats -- the level above, the two groups' rho_r -- is carried RAW here and scaled per model with the same
+// expressions: the scaling tables are the models' own.
+template <int G, int U>
+__global__ __launch_bounds__(256) void k_surrogate_eval_stencil(const EvalModel *__restrict__ bank, int models, int nz, long long ncol, int zc,
+                                                                int nchunks, EvalFields F, double *__restrict__ partial,
+                                                                long long *__restrict__ cpartial) {
+#pragma clang fp contract(off)
+  __shared__ EvalModel sm[G];
+  const int m0 = blockIdx.y * G, cnt = min(G, models - m0);
+  eval_load_models<G>(sm, bank, m0, cnt);
+  const int lane = threadIdx.x & 63;
+  const int g = lane >> 4, cidx = lane & 15;
+  const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
+  const long long nwaves = ((long long)gridDim.x * 256) >> 6;
+  const double *in_g = F.in[g], *in_s = F.in[g == 0 ? 0 : g + 1], *rho_r = F.in[4], *tr_g = F.truth[g];
+  const int fa = (g == 0) ? 5 : (g == 2) ? 6 : (g == 3) ? 7 : 1;          // k_mlp_stencil: the feature this lane's field is one level down
+  EvalAcc acc[G], accp;
+#pragma unroll
+  for (int j = 0; j < G; j++) eval_zero(acc[j]);
+  eval_zero(accp);
+  long long nact = 0;
+  const long long items = ((ncol + 15) / 16) * nchunks;                   // (16-column tile, z chunk): k_mlp_stencil's wave index
+  for (long long item = wave; item < items; item += nwaves) {
+    const int chunk = (int)(item % nchunks);
+    const long long col = (item / nchunks) * 16 + cidx;
+    const bool ok = col < ncol;
+    const int k_lo = chunk * zc, k_hi = min(nz, k_lo + zc) - 1, k_top = min(nz - 1, k_hi + 1);
+    double above = 0.0, rr = 0.0;                                         // raw: the level above of this lane's field, this group's latest rho_r
+    if (ok) {
+      above = in_g[(long long)k_top * ncol + col];
+      if (g == ((k_hi & 1) ^ 1)) rr = rho_r[(long long)k_top * ncol + col];
+    }
+    for (int k0 = k_hi; k0 >= k_lo; k0 -= U) {
+      double xin[U], xab[U], xrr[U], xs[U], xt[U];
+      bool ina[U], inn[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int k = k0 - u;
+        const bool lv = ok && k >= k_lo;
+        const long long idx = (long long)k * ncol + col;
+        xin[u] = lv ? in_g[idx] : 0.0;
+        xrr[u] = (lv && g == (k & 1)) ? rho_r[idx] : 0.0;
+        xs[u]  = (lv && g != 0) ? in_s[idx] : xin[u];                     // the field output g replaces (group 0: temp, which it holds)
+        xt[u]  = lv ? tr_g[idx] : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int k = k0 - u;
+        const bool lv = ok && k >= k_lo;
+        if (k >= k_lo) {                                                  // (wave-uniform)
+          if (g == (k & 1)) rr = xrr[u];
+          xrr[u] = rr; xab[u] = above; above = xin[u];                    // level k is level k - 1's level above
+        }
+        const bool act = eval_cell_active(lv && fabs(xt[u] - xs[u]) > 1.e-10, cidx);
+        ina[u] = lv && act; inn[u] = lv && !act;
+        nact += __popcll(__ballot(ina[u] && g == 0));
+        eval_add(accp, xs[u], xt[u], inn[u], ina[u]);
+      }
+#pragma unroll
+      for (int j = 0; j < G; j++) {
+        if (j < cnt) {                                                    // (block-uniform)
+          const EvalModel &M = sm[j];
+          const double imin = M.in_min[g], irng = M.in_irng[g], amin = M.in_min[fa], arng = M.in_irng[fa];
+          const double rmin = M.in_min[4], rrng = M.in_irng[4], ramin = M.in_min[8], rarng = M.in_irng[8];
+          const double omin = M.out_min[g], orng = M.out_rng[g];
+          const float a10 = M.a1[0][lane], a11 = M.a1[1][lane], a12e = M.a1[2][lane], a12o = M.a1[3][lane];
+          const float a20 = M.a2[0][lane], a21 = M.a2[1][lane], a22 = M.a2[2][lane];
+          const f32x4 c1 = {M.c1[g][0], M.c1[g][1], M.c1[g][2], M.c1[g][3]};
+          const f32x4 c2 = {M.c2[g], 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int u = 0; u < U; u++) {
+            const int k = k0 - u;
+            if (k >= k_lo) {                                              // (wave-uniform)
+              const bool mine = g == (k & 1);
+              const float b0 = (float)((xin[u] - imin) * irng);
+              const float ab = (float)((xab[u] - amin) * arng);
+              const float b2 = (g < 2) ? (mine ? (float)((xrr[u] - rmin) * rrng) : (float)((xrr[u] - ramin) * rarng)) : 0.f;
+              f32x4 d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a10, b0, c1, 0, 0, 0);
+              d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a11, ab, d1, 0, 0, 0);
+              d1 = __builtin_amdgcn_mfma_f32_16x16x4f32((k & 1) ? a12o : a12e, b2, d1, 0, 0, 0);
+              const float h0 = leaky(d1[0]), h1 = leaky(d1[1]), h2 = leaky(d1[2]);
+              f32x4 d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a20, h0, c2, 0, 0, 0);
+              d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a21, h1, d2, 0, 0, 0);
+              d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a22, h2, d2, 0, 0, 0);
+              double y = (double)d2[0] * orng + omin;
+              if (g != 0) y = fmax(0.0, y);
+              eval_add(acc[j], y, xt[u], inn[u], ina[u]);
+            }
+          }
+        }
+      }
+    }
+  }
+  eval_block_store<G>(acc, accp, nact, cnt, m0, models, partial, cpartial);
+}
+
+// STRICT form: thread = cell with k_mlp_strict's / k_mlp_stencil_strict's expressions (index order, no contraction, the quotient form of the
+// scaling), grid row y = one model (row `models`: persistence); the reduction scheme is the MFMA kernels'.
+template <int NIN>
+__global__ __launch_bounds__(256) void k_surrogate_eval_strict(const StencilRef *__restrict__ bank, int models, int nz, long long ncol, EvalFields F,
+                                                               double *__restrict__ partial, long long *__restrict__ cpartial) {
+#pragma clang fp contract(off)
+  __shared__ double red[4][EVAL_ROW];
+  __shared__ long long wcount[4];
+  __shared__ StencilRef P;                                                // (from LDS: as scalar operands the 144 weights do not fit the SGPRs)
+  const int m = blockIdx.y;
+  for (int i = threadIdx.x; i < (int)(sizeof(StencilRef) / 4); i += 256) ((unsigned *)&P)[i] = ((const unsigned *)(bank + min(m, models - 1)))[i];
+  __syncthreads();
+  const long long n = (long long)nz * ncol;
+  EvalAcc acc[4];
+#pragma unroll
+  for (int v = 0; v < 4; v++) eval_zero(acc[v]);
+  long long nact = 0;
+  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < n; c += (long long)gridDim.x * 256) {
+    const long long k = c / ncol;
+    const long long ca = (k + 1 < nz) ? c + ncol : c;                     // level min(nz - 1, k + 1), same column
+    double in[9] = {F.in[0][c], F.in[1][c], F.in[2][c], F.in[3][c], F.in[4][c], 0.0, 0.0, 0.0, 0.0};
+    if (NIN == 9) { in[5] = F.in[0][ca]; in[6] = F.in[2][ca]; in[7] = F.in[3][ca]; in[8] = F.in[4][ca]; }
+    const double before[4] = {in[0], in[2], in[3], in[4]};
+    const double tr[4] = {F.truth[0][c], F.truth[1][c], F.truth[2][c], F.truth[3][c]};
+    bool act = false;
+#pragma unroll
+    for (int v = 0; v < 4; v++) act = act || fabs(tr[v] - before[v]) > 1.e-10;
+    double pred[4] = {before[0], before[1], before[2], before[3]};
+    if (m < models) {                                                     // (block-uniform)
+      float x[NIN], h[10], y[4];
+#pragma unroll
+      for (int i = 0; i < NIN; i++) x[i] = (float)((in[i] - P.in_min[i]) / P.in_rng[i]);
+#pragma unroll
+      for (int o = 0; o < 10; o++) {
+        float a = 0.f;
+#pragma unroll
+        for (int i = 0; i < NIN; i++) a += x[i] * P.W1[i * 10 + o];
+        a = a + P.b1[o];
+        h[o] = a > 0.f ? a : 0.1f * a;
+      }
+#pragma unroll
+      for (int o = 0; o < 4; o++) {
+        float a = 0.f;
+#pragma unroll
+        for (int i = 0; i < 10; i++) a += h[i] * P.W2[i * 4 + o];
+        y[o] = a + P.b2[o];
+      }
+      pred[0] =           y[0] * P.out_rng[0] + P.out_min[0];
+      pred[1] = fmax(0.0, y[1] * P.out_rng[1] + P.out_min[1]);
+      pred[2] = fmax(0.0, y[2] * P.out_rng[2] + P.out_min[2]);
+      pred[3] = fmax(0.0, y[3] * P.out_rng[3] + P.out_min[3]);
+    }
+#pragma unroll
+    for (int v = 0; v < 4; v++) eval_add(acc[v], pred[v], tr[v], !act, act);
+    nact += act ? 1 : 0;
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int r = 0; r < EVAL_ROW; r++) {
+    const double q = eval_lane_tree<64>(acc[(r >> 2) & 3].s[r >> 4][r & 3], (r & 3) == 3);
+    if (lane == 0) red[wv][r] = q;
+  }
+  for (int off = 32; off > 0; off >>= 1) nact += __shfl_xor(nact, off, 64);
+  if (lane == 0) wcount[wv] = nact;
+  __syncthreads();
+  if (threadIdx.x < EVAL_ROW) {
+    const int r = threadIdx.x;
+    double q = red[0][r];
+#pragma unroll
+    for (int w = 1; w < 4; w++) q = (r & 3) == 3 ? eval_max(q, red[w][r]) : q + red[w][r];
+    partial[((long long)blockIdx.x * (models + 1) + m) * EVAL_ROW + r] = q;
+  }
+  if (threadIdx.x == 0 && m == models) cpartial[blockIdx.x] = wcount[0] + wcount[1] + wcount[2] + wcount[3];
+}
+
+// the blocks' partial rows in block order (k_surrogate_sums_final's scheme): one thread per number of `out`
+__global__ __launch_bounds__(256) void k_surrogate_eval_final(int nblocks, int rows, long long ncells, const double *__restrict__ partial,
+                                                              const long long *__restrict__ cpartial, double *__restrict__ out,
+                                                              long long *__restrict__ counts) {
+  const int e = blockIdx.x * 256 + threadIdx.x, len = rows * EVAL_ROW;
+  if (e < len) {
+    double q = 0.0;
+    for (int b = 0; b < nblocks; b++) {
+      const double o = partial[(long long)b * len + e];
+      q = (e & 3) == 3 ? eval_max(q, o) : q + o;
+    }
+    out[e] = q;
+  }
+  if (e == 0) {
+    long long a = 0;
+    for (int b = 0; b < nblocks; b++) a += cpartial[b];
+    counts[0] = ncells - a; counts[1] = a;
+  }
+}
+
+} // namespace mw
+
+struct mw_surrogate_bank_s {
+  int n_in, models;
+  EvalModel *images;          // DEVICE (models): the MFMA kernels' form
+  StencilRef *refs;           // DEVICE (models): the strict kernel's form (n_in 5: the first 50 of W1, 5 of the scaling rows)
+  double *partial;            // DEVICE (blocks, models + 1, 32), grown on demand
+  long long partial_blocks;
+  long long *cpartial;        // DEVICE (EVAL_MAX_BLOCKS)
+};
+
+extern "C" void mw_surrogate_bank_destroy(mw_surrogate_bank_t b) {
+  if (!b) return;
+  (void)hipFree(b->images); (void)hipFree(b->refs); (void)hipFree(b->partial); (void)hipFree(b->cpartial);
+  delete b;
+}
+
+extern "C" int mw_surrogate_bank_create(mw_surrogate_bank_t *out, int n_in, int models, const float *params, const double *scl_in,
+                                        const double *scl_out) {
+  if (!out) MW_FAIL("surrogate_bank_create: null pointer");
+  *out = nullptr;
+  if (n_in != 5 && n_in != 9) MW_FAIL("surrogate_bank_create: n_in must be 5 (single cell) or 9 (stencil), got " + std::to_string(n_in));
+  if (models < 1 || models > MW_SURROGATE_MAX_MODELS) MW_FAIL("surrogate_bank_create: models must be in [1, " + std::to_string(MW_SURROGATE_MAX_MODELS) + "], got " + std::to_string(models));
+  if (!params || !scl_in || !scl_out) MW_FAIL("surrogate_bank_create: null pointer");
+  for (int m = 0; m < models; m++) {
+    for (int i = 0; i < n_in; i++) if (scl_in[(m * n_in + i) * 2 + 1] == scl_in[(m * n_in + i) * 2])
+      MW_FAIL("surrogate_bank_create: model " + std::to_string(m) + ", input scaling row " + std::to_string(i) + " has max == min");
+    for (int i = 0; i < 4; i++) if (scl_out[(m * 4 + i) * 2 + 1] == scl_out[(m * 4 + i) * 2])
+      MW_FAIL("surrogate_bank_create: model " + std::to_string(m) + ", output scaling row " + std::to_string(i) + " has max == min");
+  }
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  const int npar = 10 * n_in + 54;
+  std::vector<EvalModel> img((size_t)models);
+  std::vector<StencilRef> ref((size_t)models);
+  for (int m = 0; m < models; m++) {
+    const float *W1 = params + (size_t)m * npar, *b1 = W1 + 10 * n_in, *W2 = b1 + 10, *b2 = W2 + 40;
+    EvalModel &E = img[m];
+    StencilRef &R = ref[m];
+    memset(&E, 0, sizeof(E)); memset(&R, 0, sizeof(R));
+    if (n_in == 5) {
+      MlpP Q;
+      build_operand_images(Q, W1, b1, W2, b2);
+      memcpy(E.a1, Q.a1, 2 * sizeof(Q.a1[0])); memcpy(E.a2, Q.a2, sizeof(E.a2)); memcpy(E.c1, Q.c1, sizeof(E.c1)); memcpy(E.c2, Q.c2, sizeof(E.c2));
+    } else {
+      StencilP Q;
+      build_stencil_images(Q, W1, b1, W2, b2);
+      memcpy(E.a1, Q.a1, sizeof(E.a1)); memcpy(E.a2, Q.a2, sizeof(E.a2)); memcpy(E.c1, Q.c1, sizeof(E.c1)); memcpy(E.c2, Q.c2, sizeof(E.c2));
+    }
+    memcpy(R.W1, W1, sizeof(float) * 10 * n_in); memcpy(R.b1, b1, sizeof(R.b1)); memcpy(R.W2, W2, sizeof(R.W2)); memcpy(R.b2, b2, sizeof(R.b2));
+    for (int i = 0; i < 9; i++) { R.in_rng[i] = 1.0; E.in_irng[i] = 1.0; }
+    for (int i = 0; i < n_in; i++) {
+      const double lo = scl_in[(m * n_in + i) * 2], hi = scl_in[(m * n_in + i) * 2 + 1];
+      E.in_min[i] = R.in_min[i] = lo; E.in_irng[i] = R.in_rng[i] = hi - lo;
+    }
+    for (int i = 0; i < 4; i++) {
+      const double lo = scl_out[(m * 4 + i) * 2], hi = scl_out[(m * 4 + i) * 2 + 1];
+      E.out_min[i] = R.out_min[i] = lo; E.out_rng[i] = R.out_rng[i] = hi - lo;
+    }
+  }
+  mw_surrogate_bank_t b = new mw_surrogate_bank_s();
+  b->n_in = n_in; b->models = models; b->images = nullptr; b->refs = nullptr; b->partial = nullptr; b->partial_blocks = 0; b->cpartial = nullptr;
+  hipError_t e = hipMalloc(&b->images, sizeof(EvalModel) * (size_t)models);
+  if (e == hipSuccess) e = hipMalloc(&b->refs, sizeof(StencilRef) * (size_t)models);
+  if (e == hipSuccess) e = hipMalloc(&b->cpartial, sizeof(long long) * EVAL_MAX_BLOCKS);
+  if (e == hipSuccess) e = hipMemcpy(b->images, img.data(), sizeof(EvalModel) * (size_t)models, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(b->refs, ref.data(), sizeof(StencilRef) * (size_t)models, hipMemcpyHostToDevice);
+  if (e == hipSuccess) { hipLaunchKernelGGL(k_surrogate_bank_recip, dim3((unsigned)models), dim3(64), 0, 0, b->images, n_in); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) { mw_surrogate_bank_destroy(b); MW_FAIL(std::string("surrogate_bank_create: ") + hipGetErrorString(e)); }
+  *out = b;
+  return 0;
+}
+
+extern "C" int mw_surrogate_eval_group(mw_surrogate_bank_t b) {
+  if (!b) { mw::set_error("surrogate_eval_group: null handle"); return 0; }
+  return b->n_in == 5 ? EVAL_G5 : EVAL_G9;
+}
+
+extern "C" int mw_surrogate_eval(mw_surrogate_bank_t b, int nz, long long ncol, const double *const *in5, const double *const *truth4,
+                                 double *out, long long *counts, void *stream) {
+  if (!b || !in5 || !truth4 || !out || !counts) MW_FAIL("surrogate_eval: null pointer");
+  if (nz < 1 || ncol < 1) MW_FAIL("surrogate_eval: nz and ncol must be >= 1");
+  EvalFields F;
+  for (int i = 0; i < 5; i++) { if (!in5[i]) MW_FAIL("surrogate_eval: null field"); F.in[i] = in5[i]; }
+  for (int i = 0; i < 4; i++) { if (!truth4[i]) MW_FAIL("surrogate_eval: null field"); F.truth[i] = truth4[i]; }
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  hipStream_t st = (hipStream_t)stream;
+  const long long ncells = (long long)nz * ncol;
+  const int models = b->models, rows = models + 1;
+  // grid.x from the shape alone: a model's partial sums do not depend on how many models share the call
+  constexpr int TILES = 4, U = 4;
+  const int zc = mw_mlp_stencil_chunk(nz, ncol), nchunks = (nz + zc - 1) / zc;
+  long long blocks;
+  if (g_mlp_strict) blocks = (ncells + 255) / 256;
+  else if (b->n_in == 5) blocks = (((ncells + 15) / 16 + TILES - 1) / TILES + 3) / 4;
+  else blocks = (((ncol + 15) / 16) * nchunks + 3) / 4;
+  blocks = std::max<long long>(1, std::min<long long>(blocks, EVAL_MAX_BLOCKS));
+  if (blocks > b->partial_blocks) {
+    (void)hipFree(b->partial); b->partial = nullptr; b->partial_blocks = 0;
+    MW_HIP(hipMalloc(&b->partial, sizeof(double) * (size_t)blocks * rows * EVAL_ROW));
+    b->partial_blocks = blocks;
+  }
+  if (g_mlp_strict) {
+    const dim3 grid((unsigned)blocks, (unsigned)rows);
+    if (b->n_in == 5) hipLaunchKernelGGL(k_surrogate_eval_strict<5>, grid, dim3(256), 0, st, b->refs, models, nz, ncol, F, b->partial, b->cpartial);
+    else              hipLaunchKernelGGL(k_surrogate_eval_strict<9>, grid, dim3(256), 0, st, b->refs, models, nz, ncol, F, b->partial, b->cpartial);
+  } else {
+    const int G = b->n_in == 5 ? EVAL_G5 : EVAL_G9;
+    const dim3 grid((unsigned)blocks, (unsigned)((models + G - 1) / G));
+    if (b->n_in == 5) hipLaunchKernelGGL((k_surrogate_eval<EVAL_G5, TILES>), grid, dim3(256), 0, st, b->images, models, ncells, F, b->partial, b->cpartial);
+    else              hipLaunchKernelGGL((k_surrogate_eval_stencil<EVAL_G9, U>), grid, dim3(256), 0, st, b->images, models, nz, ncol, zc, nchunks, F,
+                                         b->partial, b->cpartial);
+  }
+  MW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_surrogate_eval_final, dim3((unsigned)((rows * EVAL_ROW + 255) / 256)), dim3(256), 0, st, (int)blocks, rows, ncells,
+                     (const double *)b->partial, (const long long *)b->cpartial, out, counts);
   MW_LAUNCH_CHECK();
   return 0;
 }

@@ -10,12 +10,20 @@ simple_city           experiments/simple_city/driver.cpp:9-88                   
 inference_ponni       experiments/supercell_kessler_surrogate/inference_ponni.cpp        dycore, NN + Kessler, sponge, nudger
 gather_statistics     experiments/supercell_kessler_surrogate/gather_statistics.cpp      dycore, Kessler (+ active-cell ratio), sponge, nudger
 generate_micro_data   experiments/supercell_kessler_surrogate/generate_micro_data.cpp    dycore, Kessler (+ training samples), sponge, nudger
+evaluate_surrogates   (none: gather_statistics' loop)                                    dycore, Kessler (+ scores of candidate networks), sponge, nudger
 
 The YAML keys are the reference's (sim_time, nens, nx_glob, ny_glob, nz, xlen, ylen, zlen, dt_phys, out_prefix, init_data,
 out_freq, enable_gravity, file_per_process; keras_weights_h5 / nn_input_scaling / nn_output_scaling for the surrogate).  The
 Keras HDF5 file named by `keras_weights_h5` is read by the library's own reader (mw_h5.cpp = ponni::load_h5_weights); a text export
 (`keras_weights_txt`, tools/export_mlp_weights.sh) is accepted too; without either, the reference's shipped weight file
 (miniweatherml_amd/data/) is used.
+
+evaluate_surrogates scores the networks of a YAML list against the Kessler scheme that runs the simulation (modules.SurrogateEvaluator):
+    surrogate_models:
+      - {name: seed0, keras_weights_txt: out/weights_0.txt, nn_input_scaling: out/input_scaling.txt, nn_output_scaling: out/output_scaling.txt}
+      - ...                                   # (keras_weights_h5 instead of keras_weights_txt for a Keras file; both widths may be mixed)
+    eval_interval: 1                          # evaluate every n-th step (default 1)
+and writes surrogate_evaluation.json (the report and the per-call history) into the working directory.  One rank only.
 """
 import argparse
 import os
@@ -24,7 +32,8 @@ import time
 
 import yaml
 
-EXPERIMENTS = ("supercell_example", "community_benchmark", "simple_city", "inference_ponni", "gather_statistics", "generate_micro_data")
+EXPERIMENTS = ("supercell_example", "community_benchmark", "simple_city", "inference_ponni", "gather_statistics", "generate_micro_data",
+               "evaluate_surrogates")
 
 
 def load_config(path):
@@ -46,7 +55,63 @@ def load_config(path):
         if key in cfg:
             out[key] = str(cfg[key])
     out["_dir"] = os.path.dirname(os.path.abspath(path))
+    for key in ("surrogate_models", "eval_interval"):                          # read by evaluate_surrogates alone (surrogate_config)
+        if key in cfg:
+            out[key] = cfg[key]
     return out
+
+
+def surrogate_config(cfg):
+    """(models, eval_interval) of a loaded configuration for evaluate_surrogates: the checked `surrogate_models` list with its files
+    resolved.  Only that experiment calls it: a list left in the YAML of another experiment is not looked at."""
+    if "surrogate_models" not in cfg:
+        raise KeyError("ERROR: missing key 'surrogate_models' in the YAML input file")
+    interval = int(cfg.get("eval_interval", 1))
+    if interval < 1:
+        raise ValueError("ERROR: eval_interval must be >= 1")
+    return _surrogate_models(cfg["surrogate_models"], cfg["_dir"]), interval
+
+
+def _surrogate_models(entries, yaml_dir):
+    """The `surrogate_models:` list: every entry names a model and its three files (relative paths: from the working directory, as the
+    other file keys, else from the YAML file's directory)."""
+    if not isinstance(entries, list) or not entries:
+        raise ValueError("ERROR: surrogate_models must be a non-empty list")
+    out = []
+    for e in entries:
+        if not isinstance(e, dict) or "name" not in e:
+            raise KeyError("ERROR: every entry of surrogate_models needs a 'name'")
+        if ("keras_weights_txt" in e) == ("keras_weights_h5" in e):
+            raise KeyError("ERROR: surrogate model %r needs exactly one of keras_weights_txt and keras_weights_h5" % e["name"])
+        m = {"name": str(e["name"])}
+        for key in ("keras_weights_txt", "keras_weights_h5", "nn_input_scaling", "nn_output_scaling"):
+            if key in e:
+                p = str(e[key])
+                if not os.path.isabs(p):
+                    here = os.path.normpath(os.path.join(os.getcwd(), p))
+                    p = here if os.path.exists(here) else os.path.normpath(os.path.join(yaml_dir, p))
+                if not os.path.exists(p):
+                    raise FileNotFoundError("ERROR: surrogate model %r: no file %s" % (e["name"], p))
+                m[key] = p
+            elif key.startswith("nn_"):
+                raise KeyError("ERROR: surrogate model %r needs '%s'" % (e["name"], key))
+        out.append(m)
+    if len({m["name"] for m in out}) != len(out):
+        raise ValueError("ERROR: the names of surrogate_models must be unique")
+    return out
+
+
+def _surrogate_evaluator(entries, device):
+    """One bank per width, in the order the widths first appear; the models' names bank after bank."""
+    from . import modules
+    weights = modules.load_surrogate_bank(entries)
+    widths = []
+    for w in weights:
+        if w[0].shape[0] not in widths:
+            widths.append(w[0].shape[0])
+    order = [i for n_in in widths for i, w in enumerate(weights) if w[0].shape[0] == n_in]
+    banks = [modules.SurrogateBank([w for w in weights if w[0].shape[0] == n_in], device) for n_in in widths]
+    return modules.SurrogateEvaluator(banks, [entries[i]["name"] for i in order]), [entries[i] for i in order]
 
 
 def _distributed(device):
@@ -110,6 +175,11 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
         raise ValueError("unknown experiment %r (one of %s)" % (experiment, ", ".join(EXPERIMENTS)))
     cfg = load_config(yaml_path)
     nranks, myrank, device = _distributed(device)
+    if experiment == "evaluate_surrogates":
+        if nranks > 1:
+            raise ValueError("evaluate_surrogates runs on one rank (%d given): SurrogateEvaluator.combine is exact, but the reduction over "
+                             "ranks is not built yet" % nranks)
+        cfg["surrogate_models"], cfg["eval_interval"] = surrogate_config(cfg)
     coupler = _coupler(cfg, device, nranks, myrank, yaml_path)
     dycore = modules.Dynamics_Euler_Stratified_WenoFV()
     info = {"experiment": experiment, "nranks": nranks}
@@ -160,10 +230,23 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
             datagen = modules.DataGenerator()
             datagen.init(coupler, os.getcwd())                                 # generate_micro_data.cpp:66
             info["samples"] = 0
+        evaluator, eval_calls, eval_step = None, [], [0]
+        if experiment == "evaluate_surrogates":
+            evaluator, eval_models = _surrogate_evaluator(cfg["surrogate_models"], device)
 
         def body(dt, etime):                                                   # :73-76
             dycore.time_step(coupler, dt)
-            if stats is not None or datagen is not None:
+            if evaluator is not None:
+                if eval_step[0] % cfg["eval_interval"] == 0:
+                    inp = Coupler(device)
+                    coupler.clone_into(inp)
+                    micro.time_step(coupler, dt)
+                    evaluator.accumulate(inp, coupler)
+                    eval_calls.append({"step": eval_step[0], "etime": etime})
+                else:
+                    micro.time_step(coupler, dt)
+                eval_step[0] += 1
+            elif stats is not None or datagen is not None:
                 inp = Coupler(device)
                 coupler.clone_into(inp)                                        # gather_statistics.cpp:79-80
                 micro.time_step(coupler, dt)
@@ -189,6 +272,21 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
         if stats is not None:
             stats.finalize(coupler)
             info["ratio_active"] = stats.ratio(coupler)
+        if evaluator is not None:
+            import json
+            rep = evaluator.report() if eval_calls else {}
+            doc = {"experiment": experiment, "yaml": os.path.abspath(yaml_path), "eval_interval": cfg["eval_interval"], "steps": steps,
+                   "models": [dict(m, bank=ib, n_in=b.n_in) for ib, b in enumerate(evaluator.banks)
+                              for m in eval_models[sum(x.models for x in evaluator.banks[:ib]):][:b.models]],
+                   "statistics": ["sum_d", "sum_abs_d", "sum_d2", "max_abs_d"], "fields": list(modules.EVAL_FIELDS),
+                   "classes": list(modules.EVAL_CLASSES), "report": rep,
+                   "history": [dict(c, banks=h) for c, h in zip(eval_calls, evaluator.history)]}
+            info["surrogate_evaluation"] = os.path.join(os.getcwd(), "surrogate_evaluation.json")
+            with open(info["surrogate_evaluation"], "w") as f:
+                json.dump(doc, f, indent=1)
+            info["surrogate_report"] = rep
+            if not quiet and rep:
+                print(evaluator.table(rep), flush=True)
     torch.cuda.synchronize(device)
     info.update(etime=etime, steps=steps, main_s=time.perf_counter() - t_main, dycore_etime=dycore.etime, num_out=dycore.num_out)
     if not quiet and coupler.is_mainproc():

@@ -488,6 +488,218 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
         return out
 
 
+# ---- in-loop evaluation of candidate surrogates (mw_surrogate_eval) ---------------------------------------------------------------
+EVAL_FIELDS = ("temp", "water_vapor", "cloud_liquid", "precip_liquid")
+EVAL_CLASSES = ("inactive", "active")
+_EXACT_ONE = 1 << 1074            # sums are kept as integers in units of 2^-1074, the spacing of the smallest doubles: exact addition
+
+
+def load_surrogate_bank(entries):
+    """The models of a `surrogate_models:` list (dicts with keras_weights_txt | keras_weights_h5, nn_input_scaling, nn_output_scaling; `name`
+    and other keys are ignored) as the list of load_surrogate_weights tuples that SurrogateBank takes."""
+    return [load_surrogate_weights(weights_txt=e.get("keras_weights_txt"), in_scaling_txt=e.get("nn_input_scaling"),
+                                   out_scaling_txt=e.get("nn_output_scaling"), weights_h5=e.get("keras_weights_h5")) for e in entries]
+
+
+class SurrogateBank:
+    """mw_surrogate_bank_t: K candidate networks of one width (all single-cell or all stencil), each with its own scaling tables, uploaded
+    once to `device`; evaluate() refuses fields of another device.  models: a list of (W1, b1, W2, b2, scl_in, scl_out) as
+    load_surrogate_weights returns them."""
+
+    def __init__(self, models, device="cuda:0"):
+        self._h = None
+        self.device = torch.device(device)
+        models = list(models)
+        if len(models) < 1:
+            endrun("SurrogateBank: no models")
+        if len(models) > capi.MW_SURROGATE_MAX_MODELS:
+            endrun("SurrogateBank: %d models, at most %d fit one bank" % (len(models), capi.MW_SURROGATE_MAX_MODELS))
+        widths = sorted({int(np.asarray(m[0]).shape[0]) for m in models})
+        if len(widths) != 1:
+            endrun("SurrogateBank: models of different widths (%s inputs) cannot share a bank: one bank per width" % ", ".join(map(str, widths)))
+        self.n_in, self.models = widths[0], len(models)
+        a = 10 * self.n_in
+        for W1, b1, W2, b2, si, so in models:
+            if np.shape(W1) != (self.n_in, 10) or np.shape(b1) != (10,) or np.shape(W2) != (10, 4) or np.shape(b2) != (4,) or \
+                    np.shape(si) != (self.n_in, 2) or np.shape(so) != (4, 2):
+                endrun("SurrogateBank: a model is not Dense(%d->10), Dense(10->4) with (%d, 2) and (4, 2) scaling tables" % (self.n_in, self.n_in))
+        params = np.ascontiguousarray([np.concatenate([np.ravel(m[0]), np.ravel(m[1]), np.ravel(m[2]), np.ravel(m[3])]) for m in models], dtype=np.float32)
+        scl_in = np.ascontiguousarray([m[4] for m in models], dtype=np.float64)
+        scl_out = np.ascontiguousarray([m[5] for m in models], dtype=np.float64)
+        h = C.c_void_p()
+        if capi.lib().mw_device_count() < 1:
+            endrun("SurrogateBank: no HIP device available: libmw_cdna4 has no CPU fallback")
+        with torch.cuda.device(self.device):                              # the handle's allocations live on the current device
+            check(capi.lib().mw_surrogate_bank_create(C.byref(h), self.n_in, self.models, params.ctypes.data_as(C.POINTER(C.c_float)),
+                                                      scl_in.ctypes.data_as(C.POINTER(C.c_double)), scl_out.ctypes.data_as(C.POINTER(C.c_double))))
+        self._h = h
+        self.group = int(capi.lib().mw_surrogate_eval_group(h))           # models per pass over the state
+        self.strict = 0                                                   # 1: the thread-per-cell kernels (mw_mlp_set_strict)
+        self._buf = None
+
+    def __del__(self):
+        try:                                                              # (at interpreter exit the module's globals may be gone)
+            if getattr(self, "_h", None):
+                with torch.cuda.device(self.device):
+                    capi.lib().mw_surrogate_bank_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def evaluate(self, nz, in5, truth4):
+        """in5: the five fields before the microphysics call (temp, density_dry, water_vapor, cloud_liquid, precip_liquid), truth4: the four
+        after it (EVAL_FIELDS); fp64 CUDA tensors of nz levels.  Returns (stats, counts): the raw (K + 1, 2, 4, 4) fp64 array
+        [model | persistence][inactive, active][field][sum d, sum |d|, sum d^2, max |d|], d = prediction - truth, and the int64 cells per
+        class -- one device-to-host copy for both."""
+        if len(in5) != 5 or len(truth4) != 4:
+            endrun("SurrogateBank.evaluate: five input fields and four truth fields expected")
+        n = in5[0].numel()
+        if int(nz) < 1 or n % int(nz) != 0 or any(t.numel() != n for t in list(in5) + list(truth4)):
+            endrun("SurrogateBank.evaluate: the nine fields must have one size, a whole number of columns of nz = %d levels" % nz)
+        dev = self.device
+        if any(t.device != dev for t in list(in5) + list(truth4)):
+            endrun("SurrogateBank.evaluate: the bank lives on %s, the fields on %s" % (dev, sorted({str(t.device) for t in list(in5) + list(truth4)})))
+        nout = (self.models + 1) * 32
+        if self._buf is None:
+            self._buf = torch.empty(nout + 2, dtype=torch.int64, device=dev)                  # the statistics' bytes, then the two counts
+        check(capi.lib().mw_mlp_set_strict(int(bool(self.strict))))
+        with torch.cuda.device(dev):
+            rc = capi.lib().mw_surrogate_eval(self._h, int(nz), n // int(nz), _field_ptr_array(in5), _field_ptr_array(truth4),
+                                              C.c_void_p(self._buf.data_ptr()), C.c_void_p(self._buf.data_ptr() + 8 * nout), _stream_ptr(dev))
+        check(capi.lib().mw_mlp_set_strict(0))
+        check(rc)
+        host = self._buf.cpu().numpy()
+        return host[:nout].view(np.float64).reshape(self.models + 1, 2, 4, 4).copy(), host[nout:].copy()
+
+
+def json_safe(x):
+    """Nested lists of floats with inf / NaN as the strings "inf", "-inf", "nan" (bare tokens are no JSON); finite numbers unchanged."""
+    if isinstance(x, list):
+        return [json_safe(v) for v in x]
+    return x if np.isfinite(x) else str(float(x))
+
+
+def _exact_sum_units(x):
+    n, d = float(x).as_integer_ratio()
+    return n * (_EXACT_ONE // d)
+
+
+def surrogate_scores(stats, counts):
+    """One raw result of SurrogateBank.evaluate as the accumulating form SurrogateEvaluator.combine adds: `sums` (K + 1, 2, 4, 3) exact
+    integers in units of 2^-1074, `nonfinite` the same shape in fp64 (a sum that is inf or NaN -- a diverged model -- lives here and its
+    integer is 0), `max` (K + 1, 2, 4), `counts` (2,) and the number of calls."""
+    stats = np.asarray(stats, dtype=np.float64)
+    s = stats[..., :3]
+    fin = np.isfinite(s)
+    sums = np.zeros(s.shape, dtype=object)
+    flat, ff, src = sums.reshape(-1), fin.reshape(-1), s.reshape(-1)
+    for i in range(flat.size):
+        flat[i] = _exact_sum_units(src[i]) if ff[i] else 0
+    return {"sums": sums, "nonfinite": np.where(fin, 0.0, s), "max": stats[..., 3].copy(), "counts": np.asarray(counts, dtype=np.int64).copy(), "calls": 1}
+
+
+def _sums_to_float(sums, nonfinite):
+    out = np.array([v / _EXACT_ONE for v in sums.reshape(-1)], dtype=np.float64).reshape(sums.shape)      # int / int: correctly rounded
+    return np.where(nonfinite != 0.0, nonfinite, out)
+
+
+class SurrogateEvaluator:
+    """Scores every model of several banks (one per width) against the microphysics in charge, call after call: accumulate(inp, out) with
+    the coupler cloned before micro.time_step and the stepped one (the pair gather_micro_statistics takes), report() at the end.
+    names: the models' names, bank after bank."""
+
+    def __init__(self, banks, names):
+        self.banks = list(banks)
+        self.names = [str(n) for n in names]
+        if len(self.names) != sum(b.models for b in self.banks):
+            endrun("SurrogateEvaluator: %d names for %d models" % (len(self.names), sum(b.models for b in self.banks)))
+        if len(set(self.names)) != len(self.names):
+            endrun("SurrogateEvaluator: model names must be unique")
+        self.total = None
+        self.history = []               # per call: the raw statistics and counts of every bank
+
+    @staticmethod
+    def combine(a, b):
+        """Two results (lists with one surrogate_scores dict per bank) as one: sums add, maxima take the larger, counts and calls add.  The
+        sums are exact integers, so the order of combination cannot matter: (a + b) + c == a + (b + c), also across ranks; by convention
+        `a` is the earlier result."""
+        if len(a) != len(b):
+            endrun("SurrogateEvaluator.combine: results of different evaluators")
+        out = []
+        for x, y in zip(a, b):
+            if x["sums"].shape != y["sums"].shape:
+                endrun("SurrogateEvaluator.combine: results of different banks")
+            out.append({"sums": x["sums"] + y["sums"], "nonfinite": x["nonfinite"] + y["nonfinite"], "max": np.maximum(x["max"], y["max"]),
+                        "counts": x["counts"] + y["counts"], "calls": x["calls"] + y["calls"]})
+        return out
+
+    def accumulate(self, inp, out):
+        """Runs every bank on (inp, out) and adds the call to the running total; returns the call's own result."""
+        names5 = ("temp", "density_dry", "water_vapor", "cloud_liquid", "precip_liquid")
+        in5 = [inp.get_data_manager_readonly().get(n, True) for n in names5]
+        truth4 = [out.get_data_manager_readonly().get(n, True) for n in EVAL_FIELDS]
+        raw = [bank.evaluate(inp.get_nz(), in5, truth4) for bank in self.banks]
+        self.history.append([{"stats": json_safe(s.tolist()), "counts": c.tolist()} for s, c in raw])
+        one = [surrogate_scores(s, c) for s, c in raw]
+        self.total = one if self.total is None else self.combine(self.total, one)
+        return one
+
+    def report(self, result=None):
+        """Per model (and `persistence:<bank>`), per class (inactive, active, all) and field: n, bias = sum d / n, mae, rmse, max_abs and
+        rmse_over_persistence (the skill's denominator: the same class and field of the bank's persistence row).  An empty class has n = 0
+        and None for every statistic; so has a ratio whose persistence rmse is 0.  A statistic that is inf or NaN (a diverged model: NaN reaches
+        the sums AND max_abs) is None too, and its field carries "finite": False."""
+        result = self.total if result is None else result
+        if result is None:
+            endrun("SurrogateEvaluator.report: nothing accumulated")
+        rep, first = {}, 0
+        for ib, (bank, r) in enumerate(zip(self.banks, result)):
+            sums, nonf = r["sums"], r["nonfinite"]
+            # class axis -> (inactive, active, all)
+            s3 = _sums_to_float(np.concatenate([sums, sums.sum(axis=1, keepdims=True)], axis=1),
+                                np.concatenate([nonf, nonf.sum(axis=1, keepdims=True)], axis=1))
+            mx = np.concatenate([r["max"], r["max"].max(axis=1, keepdims=True)], axis=1)
+            n = np.concatenate([r["counts"], [r["counts"].sum()]]).astype(np.float64)
+            some = n > 0
+            with np.errstate(divide="ignore", invalid="ignore"):
+                per = s3 / np.where(some, n, 1.0)[None, :, None, None]
+                rmse = np.sqrt(per[..., 2])
+                skill = rmse / rmse[-1:]
+            ok_skill = some[None, :, None] & (rmse[-1:] > 0)
+            for m in range(bank.models + 1):
+                name = self.names[first + m] if m < bank.models else "persistence:%d" % ib
+                rep[name] = {}
+                for c, cname in enumerate(EVAL_CLASSES + ("all",)):
+                    row = {"n": int(n[c])}
+                    for v, fname in enumerate(EVAL_FIELDS):
+                        if some[c]:
+                            row[fname] = {"bias": float(per[m, c, v, 0]), "mae": float(per[m, c, v, 1]), "rmse": float(rmse[m, c, v]),
+                                          "max_abs": float(mx[m, c, v]),
+                                          "rmse_over_persistence": float(skill[m, c, v]) if ok_skill[0, c, v] else None}
+                            if not all(x is None or np.isfinite(x) for x in row[fname].values()):
+                                row[fname] = {k: (x if x is not None and np.isfinite(x) else None) for k, x in row[fname].items()}
+                                row[fname]["finite"] = False
+                        else:
+                            row[fname] = {"bias": None, "mae": None, "rmse": None, "max_abs": None, "rmse_over_persistence": None}
+                    rep[name][cname] = row
+            first += bank.models
+        return rep
+
+    def table(self, rep=None):
+        """report() as text: one line per model and class, rmse / persistence rmse per field (the skill: < 1 beats doing nothing)."""
+        rep = self.report() if rep is None else rep
+        w = max(len(k) for k in rep)
+        lines = ["%-*s %-8s %12s " % (w, "model", "class", "n") + " ".join("%26s" % ("%s rmse (/pers.)" % f) for f in EVAL_FIELDS)]
+        for name, classes in rep.items():
+            for cname, row in classes.items():
+                cells = []
+                for f in EVAL_FIELDS:
+                    r, q = row[f]["rmse"], row[f]["rmse_over_persistence"]
+                    cells.append("%26s" % ("-" if r is None else "%.6e (%s)" % (r, "-" if q is None else "%.4g" % q)))
+                lines.append("%-*s %-8s %12d " % (w, name, cname, row["n"]) + " ".join(cells))
+        return "\n".join(lines)
+
+
 def perturb_temperature(coupler, thermal=True, random=False):                   # perturb_temperature.h:8-67
     temp = coupler.get_data_manager_readwrite().get("temp")
     with torch.cuda.device(coupler.device):

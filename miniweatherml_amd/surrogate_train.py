@@ -234,29 +234,47 @@ def _fmt(v):
     return repr(float(v))                # shortest text that reads back to the same double (= the fp32 value)
 
 
-def write_outputs(out_dir, weights, scl_in, scl_out, history):
+def _write_weights(path, w, n_in):
+    a = 10 * n_in
+    with open(path, "w") as f:
+        for title, lo, hi in (("dense_6 kernel (%d,10) row-major" % n_in, 0, a), ("dense_6 bias (10)", a, a + 10),
+                              ("dense_7 kernel (10,4) row-major", a + 10, a + 50), ("dense_7 bias (4)", a + 50, a + 54)):
+            f.write("# %s\n" % title)
+            f.writelines(_fmt(x) + "\n" for x in w[lo:hi])
+
+
+def write_outputs(out_dir, weights, scl_in, scl_out, history, all_weights=None, names=None):
     """weights.txt (104 values, the layout of data/kessler_surrogate_weights.txt; 144 for the stencil model), input_scaling.txt /
     output_scaling.txt (`min max` rows, 5 | 9 and 4) and history.json; returns the three paths inference_ponni takes (keras_weights_txt,
-    nn_input_scaling, nn_output_scaling)."""
+    nn_input_scaling, nn_output_scaling).
+    all_weights (models, 104 | 144): also weights_<k>.txt for every model k, in the same layout and beside the same two scaling files; the
+    return value is then (paths, surrogate_models) with the `surrogate_models:` list of the evaluate_surrogates driver (names: the
+    models' names, default model_<k>)."""
     os.makedirs(out_dir, exist_ok=True)
     w = np.asarray(weights, dtype=np.float32).ravel()
     n_in = np.asarray(scl_in).shape[0]
     if (n_in, w.size) not in ((5, 104), (9, 144)):
         raise SurrogateTrainError("write_outputs: %d input scaling rows with %d weights is neither the single-cell model (5, 104) nor the "
                                   "stencil model (9, 144)" % (n_in, w.size))
-    a = 10 * n_in
     paths = [os.path.join(out_dir, f) for f in ("weights.txt", "input_scaling.txt", "output_scaling.txt")]
-    with open(paths[0], "w") as f:
-        for title, lo, hi in (("dense_6 kernel (%d,10) row-major" % n_in, 0, a), ("dense_6 bias (10)", a, a + 10),
-                              ("dense_7 kernel (10,4) row-major", a + 10, a + 50), ("dense_7 bias (4)", a + 50, a + 54)):
-            f.write("# %s\n" % title)
-            f.writelines(_fmt(x) + "\n" for x in w[lo:hi])
+    _write_weights(paths[0], w, n_in)
     for path, tab in ((paths[1], scl_in), (paths[2], scl_out)):
         with open(path, "w") as f:
             f.writelines("%s %s\n" % (_fmt(lo), _fmt(hi)) for lo, hi in np.asarray(tab))
     with open(os.path.join(out_dir, "history.json"), "w") as f:
         json.dump(history, f, indent=1)
-    return paths
+    if all_weights is None:
+        return paths
+    allw = np.asarray(all_weights, dtype=np.float32)
+    if allw.ndim != 2 or allw.shape[1] != w.size:
+        raise SurrogateTrainError("write_outputs: all_weights must be (models, %d), got %r" % (w.size, allw.shape))
+    models = []
+    for k in range(allw.shape[0]):
+        path = os.path.join(out_dir, "weights_%d.txt" % k)
+        _write_weights(path, allw[k], n_in)
+        models.append({"name": str(names[k]) if names is not None else "model_%d" % k, "keras_weights_txt": path,
+                       "nn_input_scaling": paths[1], "nn_output_scaling": paths[2]})
+    return paths, models
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -389,13 +407,15 @@ def _metrics(s):
 
 
 def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test_split=0.2, validation_split=0.2, learning_rate=1e-3,
-                    seed=0, models=1, device="cuda:0", split_seed=None, verbose=False, stencil=False):
+                    seed=0, models=1, device="cuda:0", split_seed=None, verbose=False, stencil=False, keep_all=False):
     """Trains `models` surrogates (seeds seed .. seed + models - 1; the pre-shuffle / split uses split_seed, default seed) on the samples of
     `sample_files` and returns a dict: per-model `history` (Keras' loss, mean_absolute_error, val_loss, val_mean_absolute_error per
     epoch), `weights` (models, 104) fp32, `best_model` (lowest final val_loss, ties to the lowest index), `test_metrics` of the best model
     (the notebook's three, scaled space, per output), the scaling tables, the data's time_step_size / dx / dy / dz and the seeds.
     out_dir: also writes the best model's weights.txt, input_scaling.txt, output_scaling.txt and history.json there.
-    stencil=True: the two-cell stencil model (9 inputs, `weights` (models, 144), `"inputs": "stencil"` in the result and history.json)."""
+    stencil=True: the two-cell stencil model (9 inputs, `weights` (models, 144), `"inputs": "stencil"` in the result and history.json).
+    keep_all=True (with out_dir): also weights_<k>.txt for every trained model, and `surrogate_models` in the result: the list the
+    evaluate_surrogates driver takes (names seed<seed>; the scaling files are the shared ones)."""
     inputs, outputs, meta = read_samples(sample_files, stencil=stencil)
     scl_in, scl_out = data_scaling(inputs, outputs)
     n = inputs.shape[0]
@@ -458,7 +478,11 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     if out_dir is not None:
         js = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in result.items() if k != "weights"}
         js["best_weights"] = w[best].astype(np.float64).tolist()
-        result["files_written"] = write_outputs(out_dir, w[best], scl_in, scl_out, js)
+        if keep_all:
+            result["files_written"], result["surrogate_models"] = write_outputs(out_dir, w[best], scl_in, scl_out, js, all_weights=w,
+                                                                                    names=["seed%d" % sd for sd in seeds])
+        else:
+            result["files_written"] = write_outputs(out_dir, w[best], scl_in, scl_out, js)
     return result
 
 
@@ -475,16 +499,22 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--split-seed", type=int, default=None, help="seed of the pre-shuffle (default: --seed)")
     ap.add_argument("--models", type=int, default=1, help="train seeds seed .. seed+K-1 at once and keep the best (lowest val_loss)")
+    ap.add_argument("--keep-all", action="store_true", help="also write weights_<k>.txt for every trained model and print the surrogate_models list "
+                    "for the evaluate_surrogates driver")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--stencil", action="store_true", help="train the two-cell stencil model (the cell and the level above: 9 inputs, 144 weights)")
     a = ap.parse_args(argv)
     try:
         r = train_surrogate(a.files, a.out, a.epochs, a.batch_size, a.test_split, a.validation_split, a.learning_rate, a.seed, a.models,
-                            a.device, a.split_seed, verbose=True, stencil=a.stencil)
+                            a.device, a.split_seed, verbose=True, stencil=a.stencil, keep_all=a.keep_all)
     except SurrogateTrainError as e:
         print("ERROR: %s" % e, file=sys.stderr)
         return 2
     print("best model %d (seed %d); wrote %s" % (r["best_model"], r["seeds"][r["best_model"]], ", ".join(r["files_written"])))
+    if a.keep_all:
+        print("surrogate_models:")
+        for m in r["surrogate_models"]:
+            print("  - {%s}" % ", ".join("%s: %s" % kv for kv in m.items()))
     return 0
 
 
