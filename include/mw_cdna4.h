@@ -503,6 +503,37 @@ int  mw_surrogate_eval_group(mw_surrogate_bank_t b);
 int  mw_surrogate_eval(mw_surrogate_bank_t b, int nz, long long ncol, const double *const *in5, const double *const *truth4,
                        double *out, long long *counts, void *stream);
 
+/* ---- surrogate rollout: candidate models as ensemble members beside Kessler ------------------------------ */
+/* No reference counterpart (the reference runs one network per simulation, microphysics_kessler_ponni.h:273-276 un-commented).  The
+ * coupler's arrays are member-fastest: cell c (level-major, c = k * ncol + col with ncol = ny * nx columns PER MEMBER), member e at
+ * c * nens + e.  MW_ROLLOUT_MAX_MEMBERS: the most members the dycore steps in one call (its 64-lane x tiling). */
+#define MW_ROLLOUT_MAX_MEMBERS 30
+/* Member `member` of nf (<= MW_MAX_TRACERS) member-fastest DEVICE fp64 fields of n cells x nens members to / from contiguous arrays of n
+ * doubles.  fields / out / in: HOST arrays of nf DEVICE pointers.  The rollout steps Kessler on member 0 ALONE with this pair:
+ * mw_kessler_time_step takes its rain sub-cycle count from the minimum over all the columns it is given, so a candidate member with absurd
+ * rain would change how the truth member is integrated. */
+int  mw_member_extract(long long n, int nens, int member, int nf, const double *const *fields, double *const *out, void *stream);
+int  mw_member_insert(long long n, int nens, int member, int nf, const double *const *in, double *const *fields, void *stream);
+/* Model j of the bank replaces temp, water_vapor, cloud_liquid and precip_liquid of member members[j] IN PLACE with what mw_mlp_forward
+ * (n_in 5) / mw_mlp_stencil_forward (n_in 9) would write for its weights from that member's own five fields before the call: the same
+ * bits, mw_mlp_set_strict honoured.  fields5: HOST array of 5 DEVICE pointers (temp, density_dry, water_vapor, cloud_liquid,
+ * precip_liquid), each (nz, ncol, nens); members: HOST array of the bank's `models` distinct member indices in [0, nens).  density_dry
+ * and every member not listed are not written.  One launch for all models of the bank (at most 32): a 16-cell MFMA tile holds cells of
+ * one member, the waves of a workgroup take consecutive models of the same cells.  The stencil model reads level k + 1 for level k: a
+ * wave (strict: a thread) sweeps its columns top-down in one chunk and carries the level above in registers, so the result is the
+ * out-of-place one and no workspace is needed.  Asynchronous on `stream`. */
+int  mw_surrogate_members_apply(mw_surrogate_bank_t b, const int *members, int nz, long long ncol, int nens, double *const *fields5,
+                                void *stream);
+/* How far every member has moved from member 0, and the member's own totals, for nf (<= MW_MAX_TRACERS) member-fastest DEVICE fp64 fields
+ * of n cells x nens (<= 256) members.  fields: HOST array of nf DEVICE pointers.  out: DEVICE fp64 (nens, nf, 7) = sum d, sum |d|,
+ * sum d^2, max |d| of d = member - member 0 over the cells, then sum x, min x, max x of the member itself; nonfinite: DEVICE int64
+ * (nens, nf), the member's NaN or inf elements.  NaN reaches the sums AND the extrema.  Every element is loaded once; no floating-point
+ * atomics, one fixed reduction order (run-to-run identical).  workspace: DEVICE, mw_member_divergence_workspace_bytes(n, nens, nf) bytes
+ * (0: arguments out of range).  Asynchronous on `stream`. */
+long long mw_member_divergence_workspace_bytes(long long n, int nens, int nf);
+int  mw_member_divergence(long long n, int nens, int nf, const double *const *fields, void *workspace, double *out, long long *nonfinite,
+                          void *stream);
+
 /* ---- DataManager validators ---------------------------------------------------------------------------- */
 /* core::DataManager::validate / validate_nan / validate_inf / validate_pos (model/core/DataManager.h:385-483) -- the reference's only
  * built-in health check: it copies an entry to the host and loops over it.  Here ONE device pass over the entry's `n` elements

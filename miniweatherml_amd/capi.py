@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("MW_LIB_PATH") or os.path.join(_HERE, "libmw_cdna4.so"
 
 MW_MAX_TRACERS = 16
 MW_SURROGATE_MAX_MODELS = 256
+MW_ROLLOUT_MAX_MEMBERS = 30
 DATA_THERMAL, DATA_SUPERCELL, DATA_CITY, DATA_BUILDING = 0, 1, 2, 3
 BC_PERIODIC, BC_OPEN, BC_WALL = 0, 1, 2
 INIT_IDS = {"thermal": DATA_THERMAL, "supercell": DATA_SUPERCELL, "city": DATA_CITY, "building": DATA_BUILDING}
@@ -153,6 +154,11 @@ SYMBOLS = {
     "mw_surrogate_bank_destroy": (None, [C.c_void_p]),
     "mw_surrogate_eval_group": (C.c_int, [C.c_void_p]),
     "mw_surrogate_eval": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mw_member_extract": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
+    "mw_member_insert": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
+    "mw_surrogate_members_apply": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
+    "mw_member_divergence_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
+    "mw_member_divergence": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mw_validate_f64": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]),
     "mw_validate_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]),
     "mw_mlp_stencil_forward": (C.c_int, [C.c_int, C.c_longlong] + [C.c_void_p] * 5 + [C.POINTER(C.c_float)] * 4 +

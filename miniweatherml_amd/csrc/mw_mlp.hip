@@ -1059,3 +1059,246 @@ extern "C" int mw_surrogate_eval(mw_surrogate_bank_t b, int nz, long long ncol, 
   MW_LAUNCH_CHECK();
   return 0;
 }
+
+// =====================================================================================================
+// ROLLOUT of a bank's models as ensemble members (mw_surrogate_members_apply): model j replaces temp and the three water fields of member
+// members[j] of the coupler's member-fastest arrays (cell c, member e at c * nens + e) IN PLACE, from that member's own values.
+//
+// k_members_apply / k_members_apply_stencil are k_mlp's / k_mlp_stencil's tiles on that layout: the 16 cells of a tile belong to ONE
+// member (the A operands are one model's), a wave owns (a group of tiles, one model), and the waves of a workgroup take consecutive models
+// of the SAME cells -- their strided accesses touch the same lines, which so come from HBM once and from L1 / L2 afterwards (the idea of
+// the dycore's members-in-one-workgroup launches).  A model's operands, biases and scaling are read from the bank's image in LDS, as in
+// k_surrogate_eval, and a cell's arithmetic is the forward kernels', expression for expression: the same bits.
+// In place: a single-cell tile is loaded whole before its MFMAs, which join all its lanes, so no store precedes a load of its cells.  The
+// stencil wave sweeps its columns top-down in ONE chunk and carries the level above in registers (k_mlp_stencil's own scheme): level k is
+// loaded before level k is stored, and nobody else reads it -- the result is the out-of-place one without a copy of any level.
+// =====================================================================================================
+namespace mw {
+
+constexpr int APPLY_MAX_MEMBERS = 32;      // members a call can address (the dycore steps at most MW_ROLLOUT_MAX_MEMBERS = 30)
+constexpr int APPLY_MAX_BLOCKS = 256 * 16; // grid.x: grid-stride beyond 16 blocks per CU
+struct ApplyMap { int member[APPLY_MAX_MEMBERS]; };
+struct ApplyFields { double *f[5]; };      // temp, density_dry, water_vapor, cloud_liquid, precip_liquid (density_dry is only read)
+
+// wave -> (model, tile slot) of a workgroup: mpb models per workgroup (1, 2 or 4), 4 / mpb tile slots
+__device__ __forceinline__ void apply_slot(int models, int &j, int &slot, int &slots) {
+  const int mpb = models >= 3 ? 4 : models, wv = threadIdx.x >> 6;
+  slots = 4 / mpb;
+  j = blockIdx.y * mpb + (wv % mpb);
+  slot = wv / mpb;
+}
+static int apply_mpb(int models) { return models >= 3 ? 4 : models; }
+
+template <int TILES>
+__global__ __launch_bounds__(256) void k_members_apply(const EvalModel *__restrict__ bank, int models, ApplyMap map, long long ncells, int nens,
+                                                       ApplyFields F) {
+#pragma clang fp contract(off)
+  __shared__ EvalModel sm[4];
+  const int mpb = models >= 3 ? 4 : models, m0 = blockIdx.y * mpb, cnt = min(mpb, models - m0);
+  eval_load_models<4>(sm, bank, m0, cnt);
+  int j, slot, slots;
+  apply_slot(models, j, slot, slots);
+  if (j >= models) return;                                                // (wave-uniform, after the barrier)
+  const EvalModel &M = sm[j - m0];
+  const int lane = threadIdx.x & 63;
+  const int g = lane >> 4, cidx = lane & 15;
+  const int e = map.member[j];
+  const double *in_g = F.f[g], *rho_r = F.f[4];
+  double *out_g = F.f[g == 0 ? 0 : g + 1];
+  const double imin = M.in_min[g], irng = M.in_irng[g], imin4 = M.in_min[4], irng4 = M.in_irng[4];
+  const double omin = M.out_min[g], orng = M.out_rng[g];
+  const float a10 = M.a1[0][lane], a11 = M.a1[1][lane];
+  const float a20 = M.a2[0][lane], a21 = M.a2[1][lane], a22 = M.a2[2][lane];
+  const f32x4 c1 = {M.c1[g][0], M.c1[g][1], M.c1[g][2], M.c1[g][3]};
+  const f32x4 c2 = {M.c2[g], 0.f, 0.f, 0.f};
+  const long long ntiles = (ncells + 15) / 16;
+  for (long long t0 = ((long long)blockIdx.x * slots + slot) * TILES; t0 < ntiles; t0 += (long long)gridDim.x * slots * TILES) {
+    double xin[TILES], xin4[TILES];
+#pragma unroll
+    for (int u = 0; u < TILES; u++) {
+      const long long cell = (t0 + u) * 16 + cidx;
+      const bool ok = cell < ncells;
+      xin[u]  = ok ? in_g[cell * nens + e] : imin;
+      xin4[u] = (ok && g == 0) ? rho_r[cell * nens + e] : imin4;
+    }
+#pragma unroll
+    for (int u = 0; u < TILES; u++) {                                     // k_mlp's cell, expression for expression
+      const long long cell = (t0 + u) * 16 + cidx;
+      float b0 = (float)((xin[u] - imin) * irng);
+      float b1 = (g == 0) ? (float)((xin4[u] - imin4) * irng4) : 0.f;
+      f32x4 d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a10, b0, c1, 0, 0, 0);
+      d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a11, b1, d1, 0, 0, 0);
+      float h0 = leaky(d1[0]), h1 = leaky(d1[1]), h2 = leaky(d1[2]);
+      f32x4 d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a20, h0, c2, 0, 0, 0);
+      d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a21, h1, d2, 0, 0, 0);
+      d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a22, h2, d2, 0, 0, 0);
+      double y = (double)d2[0] * orng + omin;
+      if (g != 0) y = fmax(0.0, y);
+      if (cell < ncells) out_g[cell * nens + e] = y;
+    }
+  }
+}
+
+// k_mlp_stencil's sweep with one chunk per column: a wave owns 16 columns of one member, all nz levels
+template <int U>
+__global__ __launch_bounds__(256) void k_members_apply_stencil(const EvalModel *__restrict__ bank, int models, ApplyMap map, int nz, long long ncol,
+                                                               int nens, ApplyFields F) {
+#pragma clang fp contract(off)
+  __shared__ EvalModel sm[4];
+  const int mpb = models >= 3 ? 4 : models, m0 = blockIdx.y * mpb, cnt = min(mpb, models - m0);
+  eval_load_models<4>(sm, bank, m0, cnt);
+  int j, slot, slots;
+  apply_slot(models, j, slot, slots);
+  if (j >= models) return;                                                // (wave-uniform, after the barrier)
+  const EvalModel &M = sm[j - m0];
+  const int lane = threadIdx.x & 63;
+  const int g = lane >> 4, cidx = lane & 15;
+  const int e = map.member[j];
+  const double *in_g = F.f[g], *rho_r = F.f[4];
+  double *out_g = F.f[g == 0 ? 0 : g + 1];
+  const int fa = (g == 0) ? 5 : (g == 2) ? 6 : (g == 3) ? 7 : 1;          // k_mlp_stencil: the feature this lane's field is one level down
+  const double imin = M.in_min[g], irng = M.in_irng[g], amin = M.in_min[fa], arng = M.in_irng[fa];
+  const double rmin = M.in_min[4], rrng = M.in_irng[4], ramin = M.in_min[8], rarng = M.in_irng[8];
+  const double omin = M.out_min[g], orng = M.out_rng[g];
+  const float a10 = M.a1[0][lane], a11 = M.a1[1][lane], a12e = M.a1[2][lane], a12o = M.a1[3][lane];
+  const float a20 = M.a2[0][lane], a21 = M.a2[1][lane], a22 = M.a2[2][lane];
+  const f32x4 c1 = {M.c1[g][0], M.c1[g][1], M.c1[g][2], M.c1[g][3]};
+  const f32x4 c2 = {M.c2[g], 0.f, 0.f, 0.f};
+  const long long ntiles = (ncol + 15) / 16, lev = ncol * nens;           // lev: doubles from level k to level k + 1
+  for (long long t = (long long)blockIdx.x * slots + slot; t < ntiles; t += (long long)gridDim.x * slots) {
+    const long long col = t * 16 + cidx;
+    const bool ok = col < ncol;
+    const long long base = col * nens + e;
+    const int k_hi = nz - 1;
+    float above = 0.f;                    // the model top is its own level above
+    double rr_raw = rmin;
+    if (ok) {
+      above = (float)((in_g[(long long)k_hi * lev + base] - amin) * arng);
+      if (g == ((k_hi & 1) ^ 1)) rr_raw = rho_r[(long long)k_hi * lev + base];
+    }
+    for (int k0 = k_hi; k0 >= 0; k0 -= U) {
+      double xin[U], xrr[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int k = k0 - u;
+        const bool lv = ok && k >= 0;
+        xin[u] = lv ? in_g[(long long)k * lev + base] : imin;
+        xrr[u] = (lv && g == (k & 1)) ? rho_r[(long long)k * lev + base] : rmin;
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int k = k0 - u;
+        if (k >= 0) {                                                     // (wave-uniform)
+          const bool mine = g == (k & 1);
+          if (mine) rr_raw = xrr[u];
+          const float b0 = (float)((xin[u] - imin) * irng);
+          const float b2 = (g < 2) ? (mine ? (float)((rr_raw - rmin) * rrng) : (float)((rr_raw - ramin) * rarng)) : 0.f;
+          f32x4 d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a10, b0, c1, 0, 0, 0);
+          d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a11, above, d1, 0, 0, 0);
+          d1 = __builtin_amdgcn_mfma_f32_16x16x4f32((k & 1) ? a12o : a12e, b2, d1, 0, 0, 0);
+          above = (float)((xin[u] - amin) * arng);                        // level k is level k - 1's level above
+          const float h0 = leaky(d1[0]), h1 = leaky(d1[1]), h2 = leaky(d1[2]);
+          f32x4 d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a20, h0, c2, 0, 0, 0);
+          d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a21, h1, d2, 0, 0, 0);
+          d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a22, h2, d2, 0, 0, 0);
+          double y = (double)d2[0] * orng + omin;
+          if (g != 0) y = fmax(0.0, y);
+          if (ok) out_g[(long long)k * lev + base] = y;
+        }
+      }
+    }
+  }
+}
+
+// STRICT form: thread = one column of one member, swept top-down with the level above in registers (in place for the same reason);
+// k_mlp_strict's / k_mlp_stencil_strict's expressions, grid row y = one model, its weights from LDS as in k_surrogate_eval_strict.
+template <int NIN>
+__global__ __launch_bounds__(256) void k_members_apply_strict(const StencilRef *__restrict__ bank, ApplyMap map, int nz, long long ncol, int nens,
+                                                              ApplyFields F) {
+#pragma clang fp contract(off)
+  __shared__ StencilRef P;
+  for (int i = threadIdx.x; i < (int)(sizeof(StencilRef) / 4); i += 256) ((unsigned *)&P)[i] = ((const unsigned *)(bank + blockIdx.y))[i];
+  __syncthreads();
+  const int e = map.member[blockIdx.y];
+  const long long lev = ncol * nens;
+  for (long long col = (long long)blockIdx.x * 256 + threadIdx.x; col < ncol; col += (long long)gridDim.x * 256) {
+    const long long base = col * nens + e;
+    double ab[4];                                                         // temp, rho_v, rho_c, rho_r of level min(nz - 1, k + 1) as they were
+    for (int k = nz - 1; k >= 0; k--) {
+      const long long c = (long long)k * lev + base;
+      double in[9] = {F.f[0][c], F.f[1][c], F.f[2][c], F.f[3][c], F.f[4][c], 0.0, 0.0, 0.0, 0.0};
+      if (k == nz - 1) { ab[0] = in[0]; ab[1] = in[2]; ab[2] = in[3]; ab[3] = in[4]; }
+      if (NIN == 9) { in[5] = ab[0]; in[6] = ab[1]; in[7] = ab[2]; in[8] = ab[3]; }
+      ab[0] = in[0]; ab[1] = in[2]; ab[2] = in[3]; ab[3] = in[4];
+      float x[NIN], h[10], y[4];
+#pragma unroll
+      for (int i = 0; i < NIN; i++) x[i] = (float)((in[i] - P.in_min[i]) / P.in_rng[i]);
+#pragma unroll
+      for (int o = 0; o < 10; o++) {
+        float a = 0.f;
+#pragma unroll
+        for (int i = 0; i < NIN; i++) a += x[i] * P.W1[i * 10 + o];
+        a = a + P.b1[o];
+        h[o] = a > 0.f ? a : 0.1f * a;
+      }
+#pragma unroll
+      for (int o = 0; o < 4; o++) {
+        float a = 0.f;
+#pragma unroll
+        for (int i = 0; i < 10; i++) a += h[i] * P.W2[i * 4 + o];
+        y[o] = a + P.b2[o];
+      }
+      F.f[0][c] =           y[0] * P.out_rng[0] + P.out_min[0];
+      F.f[2][c] = fmax(0.0, y[1] * P.out_rng[1] + P.out_min[1]);
+      F.f[3][c] = fmax(0.0, y[2] * P.out_rng[2] + P.out_min[2]);
+      F.f[4][c] = fmax(0.0, y[3] * P.out_rng[3] + P.out_min[3]);
+    }
+  }
+}
+
+} // namespace mw
+
+extern "C" int mw_surrogate_members_apply(mw_surrogate_bank_t b, const int *members, int nz, long long ncol, int nens, double *const *fields5,
+                                          void *stream) {
+  if (!b || !members || !fields5) MW_FAIL("surrogate_members_apply: null pointer");
+  if (nz < 1 || ncol < 1 || nens < 1) MW_FAIL("surrogate_members_apply: nz, ncol and nens must be >= 1");
+  const int models = b->models;
+  if (models > APPLY_MAX_MEMBERS) MW_FAIL("surrogate_members_apply: the bank has " + std::to_string(models) + " models, at most " +
+                                          std::to_string(APPLY_MAX_MEMBERS) + " can be members of one call");
+  ApplyMap map;
+  memset(&map, 0, sizeof(map));
+  for (int j = 0; j < models; j++) {
+    if (members[j] < 0 || members[j] >= nens) MW_FAIL("surrogate_members_apply: member " + std::to_string(members[j]) + " of model " + std::to_string(j) +
+                                                      " is outside [0, " + std::to_string(nens) + ")");
+    for (int i = 0; i < j; i++) if (members[i] == members[j]) MW_FAIL("surrogate_members_apply: member " + std::to_string(members[j]) + " is given to two models");
+    map.member[j] = members[j];
+  }
+  ApplyFields F;
+  for (int i = 0; i < 5; i++) { if (!fields5[i]) MW_FAIL("surrogate_members_apply: null field"); F.f[i] = fields5[i]; }
+  if ((double)nz * (double)ncol * (double)nens > 9.0e18) MW_FAIL("surrogate_members_apply: the fields are too large");
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  hipStream_t st = (hipStream_t)stream;
+  const long long ncells = (long long)nz * ncol;
+  if (g_mlp_strict) {
+    const long long blocks = std::max<long long>(1, std::min<long long>((ncol + 255) / 256, APPLY_MAX_BLOCKS));
+    const dim3 grid((unsigned)blocks, (unsigned)models);
+    if (b->n_in == 5) hipLaunchKernelGGL(k_members_apply_strict<5>, grid, dim3(256), 0, st, b->refs, map, nz, ncol, nens, F);
+    else              hipLaunchKernelGGL(k_members_apply_strict<9>, grid, dim3(256), 0, st, b->refs, map, nz, ncol, nens, F);
+    MW_LAUNCH_CHECK();
+    return 0;
+  }
+  constexpr int TILES = 4, U = 4;
+  const int mpb = apply_mpb(models), slots = 4 / mpb;
+  const unsigned gy = (unsigned)((models + mpb - 1) / mpb);
+  if (b->n_in == 5) {
+    const long long groups = ((ncells + 15) / 16 + TILES - 1) / TILES;
+    const long long blocks = std::max<long long>(1, std::min<long long>((groups + slots - 1) / slots, APPLY_MAX_BLOCKS));
+    hipLaunchKernelGGL(k_members_apply<TILES>, dim3((unsigned)blocks, gy), dim3(256), 0, st, b->images, models, map, ncells, nens, F);
+  } else {
+    const long long tiles = (ncol + 15) / 16;
+    const long long blocks = std::max<long long>(1, std::min<long long>((tiles + slots - 1) / slots, APPLY_MAX_BLOCKS));
+    hipLaunchKernelGGL(k_members_apply_stencil<U>, dim3((unsigned)blocks, gy), dim3(256), 0, st, b->images, models, map, nz, ncol, nens, F);
+  }
+  MW_LAUNCH_CHECK();
+  return 0;
+}

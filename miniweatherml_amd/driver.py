@@ -11,6 +11,7 @@ inference_ponni       experiments/supercell_kessler_surrogate/inference_ponni.cp
 gather_statistics     experiments/supercell_kessler_surrogate/gather_statistics.cpp      dycore, Kessler (+ active-cell ratio), sponge, nudger
 generate_micro_data   experiments/supercell_kessler_surrogate/generate_micro_data.cpp    dycore, Kessler (+ training samples), sponge, nudger
 evaluate_surrogates   (none: gather_statistics' loop)                                    dycore, Kessler (+ scores of candidate networks), sponge, nudger
+rollout_surrogates    (none: the same loop, one ensemble member per candidate)           dycore, Kessler | network | nothing per member, sponge, nudger
 
 The YAML keys are the reference's (sim_time, nens, nx_glob, ny_glob, nz, xlen, ylen, zlen, dt_phys, out_prefix, init_data,
 out_freq, enable_gravity, file_per_process; keras_weights_h5 / nn_input_scaling / nn_output_scaling for the surrogate).  The
@@ -24,6 +25,13 @@ evaluate_surrogates scores the networks of a YAML list against the Kessler schem
       - ...                                   # (keras_weights_h5 instead of keras_weights_txt for a Keras file; both widths may be mixed)
     eval_interval: 1                          # evaluate every n-th step (default 1)
 and writes surrogate_evaluation.json (the report and the per-call history) into the working directory.  One rank only.
+
+rollout_surrogates reads the same list and runs every network ONLINE, as an ensemble member of its own beside Kessler (member 0; members
+1 .. K the list's models in its order, modules.Microphysics_Rollout): each member's output is fed back through the dycore, and every
+eval_interval-th step all eight coupler fields of every member are scored against the Kessler member (modules.RolloutScorer).
+    persistence_member: true                  # a last member without microphysics, the skill's denominator (default true)
+nens is derived from the list (1 + K, + 1 with the persistence member); a `nens:` key that disagrees is an error.  Writes
+surrogate_rollout.json.  One rank only.
 """
 import argparse
 import os
@@ -33,7 +41,7 @@ import time
 import yaml
 
 EXPERIMENTS = ("supercell_example", "community_benchmark", "simple_city", "inference_ponni", "gather_statistics", "generate_micro_data",
-               "evaluate_surrogates")
+               "evaluate_surrogates", "rollout_surrogates")
 
 
 def load_config(path):
@@ -49,13 +57,14 @@ def load_config(path):
             raise KeyError("ERROR: missing key '%s' in the YAML input file" % key)
         out[key] = typ(cfg[key])
     out["nens"] = int(cfg.get("nens", 1))
+    out["_nens_given"] = "nens" in cfg                                         # (rollout_surrogates derives nens: rollout_config)
     out["enable_gravity"] = bool(cfg.get("enable_gravity", True))
     out["file_per_process"] = bool(cfg.get("file_per_process", False))
     for key in ("keras_weights_h5", "keras_weights_txt", "nn_input_scaling", "nn_output_scaling"):
         if key in cfg:
             out[key] = str(cfg[key])
     out["_dir"] = os.path.dirname(os.path.abspath(path))
-    for key in ("surrogate_models", "eval_interval"):                          # read by evaluate_surrogates alone (surrogate_config)
+    for key in ("surrogate_models", "eval_interval", "persistence_member"):    # read by surrogate_config / rollout_config alone
         if key in cfg:
             out[key] = cfg[key]
     return out
@@ -70,6 +79,27 @@ def surrogate_config(cfg):
     if interval < 1:
         raise ValueError("ERROR: eval_interval must be >= 1")
     return _surrogate_models(cfg["surrogate_models"], cfg["_dir"]), interval
+
+
+def rollout_config(cfg):
+    """(models, eval_interval, persistence, nens) of a loaded configuration for rollout_surrogates: surrogate_config's list and interval,
+    `persistence_member` (default true) and the member count they imply -- Kessler, one member per model, persistence.  A `nens` in the
+    YAML that disagrees is an error, and so is a list longer than the dycore steps members in one call."""
+    from . import capi
+    models, interval = surrogate_config(cfg)
+    persistence = cfg.get("persistence_member", True)
+    if not isinstance(persistence, bool):
+        raise ValueError("ERROR: persistence_member must be true or false")
+    nens = 1 + len(models) + (1 if persistence else 0)
+    if nens > capi.MW_ROLLOUT_MAX_MEMBERS:
+        raise ValueError("ERROR: %d surrogate_models%s beside Kessler are %d ensemble members, the dycore steps at most %d"
+                         % (len(models), " and the persistence member" if persistence else "", nens, capi.MW_ROLLOUT_MAX_MEMBERS))
+    if cfg.get("_nens_given") and int(cfg["nens"]) != nens:
+        raise ValueError("ERROR: nens = %d in the YAML input file, but %d surrogate_models%s beside Kessler are %d members (leave nens out)"
+                         % (cfg["nens"], len(models), " and the persistence member" if persistence else "", nens))
+    if {"kessler", "persistence"} & {m["name"] for m in models}:
+        raise ValueError("ERROR: 'kessler' and 'persistence' name members of their own: no surrogate model may be called so")
+    return models, interval, persistence, nens
 
 
 def _surrogate_models(entries, yaml_dir):
@@ -180,6 +210,11 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
             raise ValueError("evaluate_surrogates runs on one rank (%d given): SurrogateEvaluator.combine is exact, but the reduction over "
                              "ranks is not built yet" % nranks)
         cfg["surrogate_models"], cfg["eval_interval"] = surrogate_config(cfg)
+    if experiment == "rollout_surrogates":
+        if nranks > 1:
+            raise ValueError("rollout_surrogates runs on one rank (%d given): SurrogateEvaluator.combine is exact, but the reduction over "
+                             "ranks is not built yet" % nranks)
+        cfg["surrogate_models"], cfg["eval_interval"], cfg["persistence_member"], cfg["nens"] = rollout_config(cfg)
     coupler = _coupler(cfg, device, nranks, myrank, yaml_path)
     dycore = modules.Dynamics_Euler_Stratified_WenoFV()
     info = {"experiment": experiment, "nranks": nranks}
@@ -215,6 +250,10 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                 p = rel(cfg.get(k_yaml))
                 kw[k_arg] = p if p and os.path.exists(p) else None             # else: the shipped tables
             micro.init(coupler, **kw)
+        elif experiment == "rollout_surrogates":
+            micro = modules.Microphysics_Rollout()
+            micro.init(coupler, modules.load_surrogate_bank(cfg["surrogate_models"]), cfg["persistence_member"],
+                       [m["name"] for m in cfg["surrogate_models"]])
         else:
             micro = modules.Microphysics_Kessler()
             micro.init(coupler)                                                # supercell_example/driver.cpp:58
@@ -233,6 +272,7 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
         evaluator, eval_calls, eval_step = None, [], [0]
         if experiment == "evaluate_surrogates":
             evaluator, eval_models = _surrogate_evaluator(cfg["surrogate_models"], device)
+        scorer = modules.RolloutScorer(micro.member_names) if experiment == "rollout_surrogates" else None
 
         def body(dt, etime):                                                   # :73-76
             dycore.time_step(coupler, dt)
@@ -261,7 +301,15 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                     print("Relative diff rho_v: %r\nRelative diff rho_c: %r\nRelative diff rho_r: %r\nRelative diff temp : %r" %
                           (d["rho_v"], d["rho_c"], d["rho_r"], d["temp"]), flush=True)
             modules.sponge_layer(coupler, dt)
-            column_nudger.nudge_to_column(coupler, dt)
+            column_nudger.nudge_to_column(coupler, dt)                         # (eager: the scorer reads the nudged fields)
+            if scorer is not None:
+                if eval_step[0] % cfg["eval_interval"] == 0:
+                    before = dict(scorer.diverged_at)
+                    scorer.accumulate(coupler, eval_step[0], etime + dt)
+                    for m, d in scorer.diverged_at.items():                    # the other members do not see it: the run goes on
+                        if d is not None and before[m] is None and not quiet:
+                            print("rollout_surrogates: member %r is non-finite at step %d" % (m, d["step"]), flush=True)
+                eval_step[0] += 1
         if experiment == "community_benchmark":                                # timer "simulation_loop", community_benchmark/driver.cpp:66,82
             torch.cuda.synchronize(device)
             t0 = time.perf_counter()
@@ -287,6 +335,19 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
             info["surrogate_report"] = rep
             if not quiet and rep:
                 print(evaluator.table(rep), flush=True)
+        if scorer is not None:
+            import json
+            rep = scorer.report() if scorer.times else {"times": [], "diverged_at": dict(scorer.diverged_at)}
+            doc = {"experiment": experiment, "yaml": os.path.abspath(yaml_path), "eval_interval": cfg["eval_interval"], "steps": steps,
+                   "members": list(scorer.member_names), "models": [dict(m, member=1 + k) for k, m in enumerate(cfg["surrogate_models"])],
+                   "fields": list(scorer.fields), "statistics": list(modules.ROLLOUT_STATS), "history": scorer.history,
+                   "report": rep["times"], "diverged_at": rep["diverged_at"]}
+            info["surrogate_rollout"] = os.path.join(os.getcwd(), "surrogate_rollout.json")
+            with open(info["surrogate_rollout"], "w") as f:
+                json.dump(doc, f, indent=1, allow_nan=False)
+            info["rollout_report"] = rep
+            if not quiet and scorer.times:
+                print(scorer.table(rep), flush=True)
     torch.cuda.synchronize(device)
     info.update(etime=etime, steps=steps, main_s=time.perf_counter() - t_main, dycore_etime=dycore.etime, num_out=dycore.num_out)
     if not quiet and coupler.is_mainproc():

@@ -571,6 +571,28 @@ class SurrogateBank:
         host = self._buf.cpu().numpy()
         return host[:nout].view(np.float64).reshape(self.models + 1, 2, 4, 4).copy(), host[nout:].copy()
 
+    def members_apply(self, nz, members, fields5):
+        """mw_surrogate_members_apply: model j of the bank replaces temp and the three water fields of ensemble member members[j] of the
+        coupler's member-fastest arrays fields5 = (temp, density_dry, water_vapor, cloud_liquid, precip_liquid), each (nz, ..., nens), in
+        place, with the bits the forward kernels write for that member's own values (self.strict = 1: the thread-per-cell form)."""
+        members = [int(m) for m in members]
+        if len(members) != self.models:
+            endrun("SurrogateBank.members_apply: %d members for %d models" % (len(members), self.models))
+        if len(fields5) != 5 or any(t.shape != fields5[0].shape for t in fields5) or fields5[0].dim() < 2:
+            endrun("SurrogateBank.members_apply: five fields of one shape (nz, ..., nens) expected")
+        nens = int(fields5[0].shape[-1])
+        n = fields5[0].numel() // nens
+        if int(nz) < 1 or n % int(nz) != 0:
+            endrun("SurrogateBank.members_apply: %d cells per member are not a whole number of columns of nz = %d" % (n, nz))
+        if any(t.device != self.device for t in fields5):
+            endrun("SurrogateBank.members_apply: the bank lives on %s, the fields on %s" % (self.device, sorted({str(t.device) for t in fields5})))
+        check(capi.lib().mw_mlp_set_strict(int(bool(self.strict))))
+        with torch.cuda.device(self.device):
+            rc = capi.lib().mw_surrogate_members_apply(self._h, (C.c_int * len(members))(*members), int(nz), n // int(nz), nens,
+                                                       _field_ptr_array(fields5), _stream_ptr(self.device))
+        check(capi.lib().mw_mlp_set_strict(0))
+        check(rc)
+
 
 def json_safe(x):
     """Nested lists of floats with inf / NaN as the strings "inf", "-inf", "nan" (bare tokens are no JSON); finite numbers unchanged."""
@@ -697,6 +719,205 @@ class SurrogateEvaluator:
                     r, q = row[f]["rmse"], row[f]["rmse_over_persistence"]
                     cells.append("%26s" % ("-" if r is None else "%.6e (%s)" % (r, "-" if q is None else "%.4g" % q)))
                 lines.append("%-*s %-8s %12d " % (w, name, cname, row["n"]) + " ".join(cells))
+        return "\n".join(lines)
+
+
+# ---- candidate surrogates rolled out as ensemble members beside Kessler ----------------------------------------------------------------
+ROLLOUT_FIELDS = ("density_dry", "uvel", "vvel", "wvel", "temp", "water_vapor", "cloud_liquid", "precip_liquid")
+ROLLOUT_STATS = ("sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_x", "min_x", "max_x")
+ROLLOUT_WATER = ("water_vapor", "cloud_liquid", "precip_liquid")
+
+
+def rollout_member_names(model_names, persistence=True):
+    """The fixed roles of a rollout's ensemble members: member 0 is Kessler, members 1 .. K the models of the list in its order, an optional
+    last member persistence (no microphysics).  More members than the dycore steps in one call is an error that names the limit."""
+    names = [str(n) for n in model_names]
+    if len(set(names)) != len(names) or {"kessler", "persistence"} & set(names):
+        endrun("rollout: model names must be unique and neither 'kessler' nor 'persistence'")
+    members = ["kessler"] + names + (["persistence"] if persistence else [])
+    if len(members) > capi.MW_ROLLOUT_MAX_MEMBERS:
+        endrun("rollout: %d models%s beside Kessler are %d ensemble members, the dycore steps at most %d"
+               % (len(names), " and persistence" if persistence else "", len(members), capi.MW_ROLLOUT_MAX_MEMBERS))
+    return members
+
+
+class Microphysics_Rollout(Microphysics_Kessler):
+    """One microphysics step that treats every ensemble member differently (no reference counterpart): member 0 is stepped by Kessler,
+    member k by model k - 1 of `models` (its output written back: Microphysics_Kessler_Surrogate.online for that member), the optional last
+    member by nothing.  The dycore, the sponge and the nudger step the members independently, so one run shows how each candidate behaves
+    once its own output is fed back.  Kessler runs on member 0 ALONE, extracted to contiguous arrays: its rain sub-cycle count is a minimum
+    over all the columns of a call.  `precl` is written for member 0 only; the other members' precl keeps whatever it held."""
+
+    mlp_strict = 0        # 1: the thread-per-cell MLP kernels (mw_mlp_set_strict)
+
+    def micro_name(self):
+        return "rollout"
+
+    def init(self, coupler, models, persistence=True, names=None):
+        """models: (W1, b1, W2, b2, scl_in, scl_out) tuples as load_surrogate_weights returns them, single-cell and stencil networks in any
+        order; names: theirs (default model0, model1, ...).  The coupler must have 1 + len(models) (+ 1 with persistence) members."""
+        models = list(models)
+        names = ["model%d" % k for k in range(len(models))] if names is None else list(names)
+        if len(names) != len(models):
+            endrun("Microphysics_Rollout: %d names for %d models" % (len(names), len(models)))
+        self.member_names = rollout_member_names(names, persistence)
+        self.persistence = bool(persistence)
+        if coupler.get_nens() != len(self.member_names):
+            endrun("Microphysics_Rollout: %d models%s beside Kessler need nens = %d, the coupler has %d"
+                   % (len(models), " and persistence" if persistence else "", len(self.member_names), coupler.get_nens()))
+        super().init(coupler)
+        coupler.set_option("micro", "rollout")
+        widths = []
+        for m in models:
+            if int(np.shape(m[0])[0]) not in widths:
+                widths.append(int(np.shape(m[0])[0]))
+        # one bank per width; a model keeps the member its place in the list gives it
+        self.banks = [(SurrogateBank([m for m in models if np.shape(m[0])[0] == w], coupler.device),
+                       [1 + k for k, m in enumerate(models) if np.shape(m[0])[0] == w]) for w in widths]
+        self._m0 = None
+
+    def time_step(self, coupler, dt):
+        dm = coupler.get_data_manager_readwrite()
+        temp, rho_d = dm.get("temp"), dm.get("density_dry", readonly=True)
+        rho_v, rho_c, rho_r, precl = dm.get("water_vapor"), dm.get("cloud_liquid"), dm.get("precip_liquid"), dm.get("precl")
+        nz, nens = coupler.get_nz(), coupler.get_nens()
+        ncol = coupler.get_ny() * coupler.get_nx()
+        n = nz * ncol
+        L = capi.lib()
+        if self._m0 is None or self._m0[0][0].numel() != n or self._m0[1].numel() != ncol:
+            self._m0 = ([torch.empty(n, dtype=torch.float64, device=coupler.device) for _ in range(5)],
+                        torch.empty(ncol, dtype=torch.float64, device=coupler.device))
+        (v0, c0, r0, d0, t0), p0 = self._m0
+        nbytes = L.mw_kessler_workspace_bytes(nz, ncol)
+        if self._ws is None or self._ws.numel() * 8 < nbytes:
+            self._ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=coupler.device)
+        st = _stream_ptr(coupler.device)
+        check(L.mw_kessler_set_strict(self.strict))
+        with torch.cuda.device(coupler.device):
+            check(L.mw_member_extract(n, nens, 0, 5, _field_ptr_array([rho_v, rho_c, rho_r, rho_d, temp]), _field_ptr_array([v0, c0, r0, d0, t0]), st))
+            check(L.mw_kessler_time_step(nz, ncol, coupler.get_dz(), float(dt), _ptr(v0), _ptr(c0), _ptr(r0), _ptr(d0), _ptr(t0), _ptr(p0),
+                                         _ptr(self._ws), None, st))
+            check(L.mw_member_insert(n, nens, 0, 4, _field_ptr_array([v0, c0, r0, t0]), _field_ptr_array([rho_v, rho_c, rho_r, temp]), st))
+            check(L.mw_member_insert(ncol, nens, 0, 1, _field_ptr_array([p0]), _field_ptr_array([precl]), st))
+        for bank, members in self.banks:
+            bank.strict = self.mlp_strict
+            bank.members_apply(nz, members, [temp, rho_d, rho_v, rho_c, rho_r])
+
+
+def member_divergence(coupler, names):
+    """mw_member_divergence of the coupler's fields `names` (at most 16, each (..., nens)): the raw arrays (stats, nonfinite) --
+    stats (nens, len(names), 7) fp64 in the order of ROLLOUT_STATS (d = member - member 0 for the first four, the member's own values for
+    the last three), nonfinite (nens, len(names)) int64, the member's NaN or inf elements -- from one device-to-host copy."""
+    dm = coupler.get_data_manager_readonly()
+    fields = [dm.get(n, True) for n in names]
+    nens = coupler.get_nens()
+    n = fields[0].numel() // nens
+    if any(t.numel() != n * nens or t.shape[-1] != nens for t in fields):
+        endrun("member_divergence: the fields must have one size and the members last")
+    L = capi.lib()
+    nf = len(fields)
+    nbytes = L.mw_member_divergence_workspace_bytes(n, nens, nf)
+    if nbytes <= 0:
+        endrun("member_divergence: %d fields of %d cells x %d members are out of range (at most %d fields)" % (nf, n, nens, capi.MW_MAX_TRACERS))
+    ws = getattr(coupler, "_ws_divergence", None)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = coupler._ws_divergence = torch.empty(nbytes // 8, dtype=torch.float64, device=coupler.device)
+    buf = torch.empty(nens * nf * 8, dtype=torch.int64, device=coupler.device)             # the statistics' bytes, then the counts
+    nout = nens * nf * 7
+    with torch.cuda.device(coupler.device):
+        check(L.mw_member_divergence(n, nens, nf, _field_ptr_array(fields), _ptr(ws), C.c_void_p(buf.data_ptr()),
+                                     C.c_void_p(buf.data_ptr() + 8 * nout), _stream_ptr(coupler.device)))
+    host = buf.cpu().numpy()
+    return host[:nout].view(np.float64).reshape(nens, nf, 7).copy(), host[nout:].reshape(nens, nf).copy()
+
+
+def rollout_report(stats, nonfinite, ncells, member_names, fields, cell_volume=1.0, persistence=None):
+    """One scoring time's raw arrays (member_divergence) as a report -- pure numpy.  Per member and field: bias = sum d / n, mae, rmse and
+    max_abs of d = member - Kessler member, rmse_over_persistence (None without a persistence member `persistence`, or when its rmse is
+    0), the member's own mean, min, max and its count of non-finite elements.  A statistic that is inf or NaN is None and the field
+    carries "finite": False.  Per member: total_water = cell_volume * sum of the three water fields (None unless all three are scored
+    and finite) and finite = no field has a non-finite element or statistic."""
+    stats = np.asarray(stats, dtype=np.float64)
+    nonfinite = np.asarray(nonfinite, dtype=np.int64)
+    if stats.shape != (len(member_names), len(fields), 7) or nonfinite.shape != stats.shape[:2]:
+        endrun("rollout_report: stats must be (%d members, %d fields, 7) and nonfinite (%d, %d)" % ((len(member_names), len(fields)) * 2))
+    n = float(ncells)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        rmse = np.sqrt(stats[..., 2] / n)
+        skill = rmse / rmse[persistence] if persistence is not None else None
+    rep = {}
+    for m, mname in enumerate(member_names):
+        row, ok_member = {}, True
+        for f, fname in enumerate(fields):
+            q = None
+            if persistence is not None and rmse[persistence, f] > 0:
+                q = float(skill[m, f])
+            cell = {"bias": float(stats[m, f, 0] / n), "mae": float(stats[m, f, 1] / n), "rmse": float(rmse[m, f]), "max_abs": float(stats[m, f, 3]),
+                    "rmse_over_persistence": q, "mean": float(stats[m, f, 4] / n), "min": float(stats[m, f, 5]), "max": float(stats[m, f, 6]),
+                    "nonfinite": int(nonfinite[m, f])}
+            if nonfinite[m, f] != 0 or not all(x is None or np.isfinite(x) for x in cell.values()):
+                cell = {k: (x if x is not None and np.isfinite(x) else None) for k, x in cell.items()}
+                cell["finite"] = False
+                ok_member = False
+            row[fname] = cell
+        water = None
+        if all(w in fields for w in ROLLOUT_WATER):
+            water = float(sum(stats[m, list(fields).index(w), 4] for w in ROLLOUT_WATER) * cell_volume)
+            water = water if np.isfinite(water) else None
+        rep[mname] = {"fields": row, "total_water": water, "finite": ok_member}
+    return rep
+
+
+class RolloutScorer:
+    """Online skill of a rollout's members: accumulate(coupler, step, etime) at every scoring time, report() / table() at the end.
+    member_names: rollout_member_names' list (a last member called persistence is the skill's denominator); fields: the coupler fields
+    to score."""
+
+    def __init__(self, member_names, fields=ROLLOUT_FIELDS):
+        self.member_names = [str(m) for m in member_names]
+        self.fields = [str(f) for f in fields]
+        self.persistence = len(self.member_names) - 1 if self.member_names[-1] == "persistence" else None
+        self.history = []               # per scoring time: step, etime, the raw arrays
+        self.times = []                 # per scoring time: step, etime, rollout_report
+        self.diverged_at = {m: None for m in self.member_names}
+
+    def add(self, stats, nonfinite, ncells, cell_volume, step, etime):
+        """One scoring time from raw arrays (what accumulate does after member_divergence): pure numpy."""
+        rep = rollout_report(stats, nonfinite, ncells, self.member_names, self.fields, cell_volume, self.persistence)
+        self.history.append({"step": int(step), "etime": float(etime), "stats": json_safe(np.asarray(stats, dtype=np.float64).tolist()),
+                             "nonfinite": np.asarray(nonfinite).tolist()})
+        self.times.append({"step": int(step), "etime": float(etime), "members": rep})
+        for m in self.member_names:
+            if self.diverged_at[m] is None and not rep[m]["finite"]:
+                self.diverged_at[m] = {"step": int(step), "etime": float(etime)}
+        return rep
+
+    def accumulate(self, coupler, step, etime):
+        stats, nonfinite = member_divergence(coupler, self.fields)
+        ncells = coupler.get_nz() * coupler.get_ny() * coupler.get_nx()
+        return self.add(stats, nonfinite, ncells, coupler.get_dx() * coupler.get_dy() * coupler.get_dz(), step, etime)
+
+    def report(self):
+        """{"times": one rollout_report per scoring time with its step and etime, "diverged_at": per member the first scoring time at
+        which it showed a non-finite value, or None}."""
+        if not self.times:
+            endrun("RolloutScorer.report: nothing accumulated")
+        return {"times": self.times, "diverged_at": dict(self.diverged_at)}
+
+    def table(self, rep=None):
+        """The last scoring time as text: one line per member, rmse against the Kessler member (/ persistence rmse) per field."""
+        rep = self.report() if rep is None else rep
+        last = rep["times"][-1]
+        w = max(len(m) for m in self.member_names)
+        lines = ["step %d, etime %.6f s" % (last["step"], last["etime"]),
+                 "%-*s " % (w, "member") + " ".join("%26s" % ("%s rmse (/pers.)" % f) for f in self.fields) + "  diverged_at"]
+        for m in self.member_names:
+            cells = []
+            for f in self.fields:
+                r, q = last["members"][m]["fields"][f]["rmse"], last["members"][m]["fields"][f]["rmse_over_persistence"]
+                cells.append("%26s" % ("-" if r is None else "%.6e (%s)" % (r, "-" if q is None else "%.4g" % q)))
+            d = rep["diverged_at"][m]
+            lines.append("%-*s " % (w, m) + " ".join(cells) + "  " + ("-" if d is None else "step %d" % d["step"]))
         return "\n".join(lines)
 
 

@@ -500,7 +500,7 @@ def main(argv=None):
     ap.add_argument("--split-seed", type=int, default=None, help="seed of the pre-shuffle (default: --seed)")
     ap.add_argument("--models", type=int, default=1, help="train seeds seed .. seed+K-1 at once and keep the best (lowest val_loss)")
     ap.add_argument("--keep-all", action="store_true", help="also write weights_<k>.txt for every trained model and print the surrogate_models list "
-                    "for the evaluate_surrogates driver")
+                    "for the evaluate_surrogates and rollout_surrogates drivers")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--stencil", action="store_true", help="train the two-cell stencil model (the cell and the level above: 9 inputs, 144 weights)")
     a = ap.parse_args(argv)
