@@ -534,6 +534,40 @@ long long mw_member_divergence_workspace_bytes(long long n, int nens, int nf);
 int  mw_member_divergence(long long n, int nens, int nf, const double *const *fields, void *workspace, double *out, long long *nonfinite,
                           void *stream);
 
+/* ---- harvesting Kessler labels on the rollout members' own states ---------------------------------------- */
+/* The teacher: what Kessler would do to the state of the listed members, each member ALONE, out of place.  A member-fastest field
+ * (nz, ncol, nens) is a (nz, ncol * nens) array of columns col * nens + e, so the production kernels' column walk is as coalesced on all
+ * members at once as it is on one; every column lowers the rain sub-cycle count of its own member only (nens words in the workspace,
+ * integer atomicMin on the bit pattern, no floating-point atomics).  fields5: HOST array of 5 DEVICE pointers (temp, density_dry,
+ * water_vapor, cloud_liquid, precip_liquid), never written; out4: HOST array of 4 DEVICE pointers of the same (nz, ncol, nens) shape
+ * that receive temp, water_vapor, cloud_liquid, precip_liquid after Kessler (densities) of the nm members in `members` (HOST, distinct,
+ * in [0, nens), nens <= 64) -- for such a member the bits mw_kessler_time_step leaves when it is given that member's columns alone.
+ * Elements of members not listed are NOT written; precl is not produced.  A member's count comes from one decision function
+ * (mw_kessler_teacher_rainsplit below): a member whose state asks for more than max_rainsplit (1 .. 1024) sub-cycles, or whose rain
+ * CFL step is not a positive finite number (a member with inf or NaN rain: 0), is SKIPPED: not computed, not written, count 0.  rainsplit_out: optional HOST
+ * array of nm counts (0 = skipped; forces a stream synchronisation); without it the call is asynchronous on `stream` and may be repeated
+ * on one workspace (DEVICE, mw_kessler_members_teacher_workspace_bytes bytes; 0: arguments out of range).
+ * The production form only: mw_kessler_set_strict is not consulted (the labels end as fp32 samples). */
+long long mw_kessler_members_teacher_workspace_bytes(int nz, long long ncol, int nens);
+int  mw_kessler_members_teacher(int nz, long long ncol, int nens, int nm, const int *members, double dz, double dt, int max_rainsplit,
+                                const double *const *fields5, double *const *out4, int *rainsplit_out, void *workspace, void *stream);
+/* Host only: the teacher's decision function on a member's minimum rain CFL step dt_max -- ceil(dt / dt_max) if dt_max is finite,
+ * > 0 and the quotient is in [1, cap], else 0.  Decided in floating point before any conversion to int. */
+int  mw_kessler_teacher_rainsplit(double dt, double dt_max, int cap);
+/* DataGenerator's sampler on the member layout, between the listed members' own fields5 and their teacher values teacher4 (as above).
+ * mw_member_sample_mask: mask (DEVICE bytes, (nz, ncol, nens)) of element t = (k * ncol + col) * nens + e is 1 if e is listed,
+ * u01(key0 + t) < (active ? thr_active : thr_inactive) with u01 and `active` as mw_micro_sample_mask has them (any of the four
+ * |teacher - input| > 1e-10), and all fourteen values of the element's sample record are finite AS fp32 (a trainer refuses a file that
+ * holds one that is not); 0 otherwise, and 0 for every member not listed.
+ * mw_member_gather_samples: mw_micro_gather_samples' records -- inputs (n, 5, 2), outputs (n, 4), DEVICE fp32 -- for the n flat element
+ * indices `elems` (DEVICE int64) into the member layout; the level above is min(nz - 1, k + 1) of the same column and member, slot (4, 1)
+ * is 0.  An index outside the fields gives a record of zeros.  Both asynchronous on `stream`. */
+int  mw_member_sample_mask(int nz, long long ncol, int nens, int nm, const int *members, const double *const *fields5,
+                           const double *const *teacher4, unsigned long long key0, double thr_active, double thr_inactive,
+                           unsigned char *mask, void *stream);
+int  mw_member_gather_samples(int nz, long long ncol, int nens, const double *const *fields5, const double *const *teacher4,
+                              const long long *elems, long long n, float *inputs, float *outputs, void *stream);
+
 /* ---- DataManager validators ---------------------------------------------------------------------------- */
 /* core::DataManager::validate / validate_nan / validate_inf / validate_pos (model/core/DataManager.h:385-483) -- the reference's only
  * built-in health check: it copies an entry to the host and loops over it.  Here ONE device pass over the entry's `n` elements

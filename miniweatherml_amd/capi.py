@@ -159,6 +159,14 @@ SYMBOLS = {
     "mw_surrogate_members_apply": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "mw_member_divergence_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     "mw_member_divergence": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mw_kessler_members_teacher_workspace_bytes": (C.c_longlong, [C.c_int, C.c_longlong, C.c_int]),
+    "mw_kessler_members_teacher": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double, C.c_int,
+                                             C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
+    "mw_kessler_teacher_rainsplit": (C.c_int, [C.c_double, C.c_double, C.c_int]),
+    "mw_member_sample_mask": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                        C.c_ulonglong, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "mw_member_gather_samples": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_longlong,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "mw_validate_f64": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]),
     "mw_validate_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]),
     "mw_mlp_stencil_forward": (C.c_int, [C.c_int, C.c_longlong] + [C.c_void_p] * 5 + [C.POINTER(C.c_float)] * 4 +

@@ -19,6 +19,7 @@
 #include "../../include/mw_cdna4.h"
 #include "mw_common.h"
 #include "mw_glibc_pow.h"
+#include "mw_kessler_teacher.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -382,6 +383,180 @@ __global__ __launch_bounds__(256) void k_kessler_column(KesP p, double *__restri
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// TEACHER (mw_kessler_members_teacher): the production form above on LISTED ensemble members of the coupler's member-fastest arrays,
+// each member alone, out of place.  A field (nz, ncol, nens) is a (nz, ncol * nens) array of columns i = col * nens + e with the member
+// fastest: a thread that walks i is exactly as coalesced as above, so the three kernels are the three above over p.ncol = ncol * nens
+// columns, with four differences:
+//   member list   lanes of members that are not listed leave before any arithmetic and write nothing;
+//   own count     column i lowers the minimum word of member i % nens only (words[nens], integer atomicMin on the bit pattern); the chunk
+//                 sweep takes the members whose count is 1, the column sweep the others -- both kinds may sit in one wavefront;
+//   bounded count the count comes from kessler_teacher_rainsplit (mw_kessler_teacher.h) and from nowhere else: 0 = skipped (too many
+//                 sub-cycles, or rain / a fall speed that is not finite: the CFL pass sends that member's step to 0);
+//   out of place  the five inputs are const, the four results go to arrays of their own and every computed cell stores all four (the
+//                 "unchanged, so not stored" short cuts above need the in-place form); precl is not produced.
+// kessler_cell / kessler_velqr are the ones above: a listed member gets the bits k_kessler_chunks / k_kessler_column give it alone (their
+// wave-uniform short cuts return exactly what the formulas return, so the other members in the wavefront do not matter).
+// The bodies are written beside the in-place ones, not shared by template: the in-place kernels' code stays as it is.
+// ---------------------------------------------------------------------------------------------------------------
+struct KesTeach {
+  int nens, cap;                    // members per cell; the most rain sub-cycles a member may ask for
+  unsigned long long listed;        // bit e: member e is computed
+  const double *rho_v, *rho_c, *rho_r, *rho_d, *temp;
+  double *o_temp, *o_v, *o_c, *o_r;
+  const unsigned long long *words;  // (nens) minimum rain CFL step per member, bit patterns (all ones: no column lowered it)
+};
+
+__device__ __forceinline__ int kessler_teacher_count(const KesP &p, const KesTeach &t, int e) {
+  return kessler_teacher_rainsplit(p.dt, kessler_teacher_word(t.words[e], p.dt), t.cap);
+}
+
+// k_kessler_prep per member.  A column that could raise its member's count is rare (see k_kessler_prep); a wavefront that holds one
+// reduces per member present, then one atomicMin per (wavefront, member).
+__global__ __launch_bounds__(256) void k_kessler_teacher_prep(KesP p, int nens, unsigned long long listed, const double *__restrict__ rho_r,
+                                                              const double *__restrict__ rho_d, double *__restrict__ flux_top, int chunk,
+                                                              int klevels, unsigned long long *words) {
+#pragma clang fp contract(off)
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int k0 = blockIdx.y * klevels, k1 = min(k0 + klevels, p.nz);
+  const int e = (i < p.ncol) ? (int)(i % nens) : -1;
+  double dtc = p.dt;
+  if (e >= 0 && ((listed >> e) & 1ull)) {
+    const double rho0 = rho_d[i];
+    const double lim = 0.8 * p.dz / p.dt;
+    const double lhs = (36.34 * 36.34) * rho0 * (1.0 + 1.0e-9), lim2 = lim * lim;
+    constexpr int KL = 5;                                     // (= klevels of the launch)
+    double rdv[KL], rrv[KL];
+    bool rain = false;
+#pragma unroll
+    for (int m = 0; m < KL; m++) { const long long idx = (long long)min(k0 + m, p.nz - 1) * p.ncol + i; rrv[m] = rho_r[idx]; }
+#pragma unroll
+    for (int m = 0; m < KL; m++) rain = rain || (rrv[m] != 0.0);
+    if (!__any(rain)) {
+#pragma unroll
+      for (int m = 0; m < KL; m++) {
+        const int k = k0 + m;
+        if (k < k1 && k > 0 && k % chunk == 0) flux_top[(long long)(k / chunk - 1) * p.ncol + i] = 0.0;
+      }
+    } else {
+#pragma unroll
+      for (int m = 0; m < KL; m++) { const long long idx = (long long)min(k0 + m, p.nz - 1) * p.ncol + i; rdv[m] = rho_d[idx]; }
+#pragma unroll
+      for (int m = 0; m < KL; m++) {
+        const int k = k0 + m;
+        if (k >= k1) break;
+        const double rd = rdv[m], rr = rrv[m];
+        const bool boundary = (k > 0 && k % chunk == 0);
+        const bool proven = (0.001 * rr <= 1.0) && (lhs < lim2 * rd);
+        if (boundary || __any(!proven)) {
+          const double ird = rcp64(rd);
+          const double qr = rr * ird, r = 0.001 * rd;
+          const double velqr = kessler_velqr(rr, rd, ird, rho0);
+          if (boundary) flux_top[(long long)(k / chunk - 1) * p.ncol + i] = r * qr * velqr;
+          // rain or a fall speed that is inf or NaN, at any level: the member cannot be labelled.  Its step is 0, which
+          // kessler_teacher_rainsplit refuses.  (Left alone such a cell looks harmless: kes_log(inf) is NaN, kes_exp's clamp drops the NaN,
+          // the fall speed comes out as 0 and the cell contributes dt.  Such rain is never "proven", so it always gets here.)
+          if (!(fabs(rr) <= 1.7976931348623157e308) || !(fabs(velqr) <= 1.7976931348623157e308)) dtc = 0.0;
+          if (k < p.nz - 1) {
+            const double zk = (k + 0.5) * p.dz, zk1 = (k + 1 + 0.5) * p.dz;
+            const double c = (velqr > 1.e-10) ? 0.8 * (zk1 - zk) / velqr : p.dt;
+            dtc = fmin(dtc, c);                               // (fmin drops a NaN c: dtc stays in [0, dt])
+          }
+        }
+      }
+    }
+  }
+  // all 64 lanes are here again.  dtc is in [0, dt] and never NaN: its bit pattern orders like the value.
+  const bool has = dtc < p.dt;
+  unsigned long long todo = __ballot(has);
+  const int lane = threadIdx.x & 63;
+  while (todo) {                                              // one round per member that has something to say
+    const int leader = __ffsll((long long)todo) - 1;
+    const int e0 = __shfl(e, leader, 64);
+    const bool mine = has && e == e0;
+    double m = mine ? dtc : p.dt;
+    for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(m, off, 64); m = fmin(m, o); }
+    if (lane == leader) atomicMin(words + e0, (unsigned long long)__double_as_longlong(m));
+    todo &= ~__ballot(mine);
+  }
+}
+
+// k_kessler_chunks for the listed members whose count is 1: thread = (column i, z chunk c), top-down.
+__global__ __launch_bounds__(256) void k_kessler_teacher_chunks(KesP p, KesTeach t, const double *__restrict__ flux_top, int chunk) {
+#pragma clang fp contract(off)
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.ncol) return;
+  const int e = (int)(i % t.nens);
+  if (!((t.listed >> e) & 1ull)) return;
+  if (kessler_teacher_count(p, t, e) != 1) return;            // > 1: k_kessler_teacher_column; 0: skipped
+  const int c = blockIdx.y;
+  const int k_lo = c * chunk, k_hi = min(k_lo + chunk, p.nz) - 1;
+  const double dt0 = p.dt / 1.0;
+  const double rho0 = t.rho_d[i];
+  double precl_acc = 0;                                       // (kessler_cell's; not stored)
+  double flux_above = (k_hi < p.nz - 1) ? flux_top[(long long)c * p.ncol + i] : 0.0;
+  long long idx = (long long)k_hi * p.ncol + i;
+  double rd = t.rho_d[idx], T_in = t.temp[idx], rv_in = t.rho_v[idx], rc_in = t.rho_c[idx], rr_in = t.rho_r[idx];
+  for (int k = k_hi; k >= k_lo; k--) {
+    idx = (long long)k * p.ncol + i;
+    const long long nidx = (long long)max(k - 1, k_lo) * p.ncol + i;
+    const double rd_n = t.rho_d[nidx], T_n = t.temp[nidx], rv_n = t.rho_v[nidx], rc_n = t.rho_c[nidx], rr_n = t.rho_r[nidx];
+    double pressure = p.R_d * rd * T_in + p.R_v * rv_in * T_in;
+    const double pp0 = pressure * (1.0 / p.p0);
+    const double ird = rcp64(rd);
+    double qv = rv_in * ird, qc = rc_in * ird, qr = rr_in * ird;
+    double T = T_in;
+    double velqr = kessler_velqr(rr_in, rd, ird, rho0);
+    flux_above = kessler_cell(p, k, rd, rho0, pp0, dt0, flux_above, T, qv, qc, qr, velqr, precl_acc);
+    t.o_v[idx] = qv * rd; t.o_c[idx] = qc * rd; t.o_r[idx] = qr * rd;
+    t.o_temp[idx] = T;
+    rd = rd_n; T_in = T_n; rv_in = rv_n; rc_in = rc_n; rr_in = rr_n;
+  }
+}
+
+// k_kessler_column for the listed members whose count is 2 .. cap: thread = column, all sub-cycles, top-down.  Between the sub-cycles
+// the member's own output elements hold T, qv, qc, qr (they are overwritten with the results in the last one); the fall speed is kept
+// in w_velqr (nz, ncol).
+__global__ __launch_bounds__(256) void k_kessler_teacher_column(KesP p, KesTeach t, double *__restrict__ w_velqr) {
+#pragma clang fp contract(off)
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.ncol) return;
+  const int e = (int)(i % t.nens);
+  if (!((t.listed >> e) & 1ull)) return;
+  const int rainsplit = kessler_teacher_count(p, t, e);       // <= cap: the only bound of the loop below
+  if (rainsplit < 2) return;                                  // 1: k_kessler_teacher_chunks; 0: skipped
+  const double dt0 = p.dt / (double)rainsplit;
+  const int nz = p.nz;
+  // the column's own base pointers (in vector registers: nine uniform bases beside kessler_cell's constants do not fit the scalar file)
+  const double *c_d = t.rho_d + i, *c_T = t.temp + i, *c_v = t.rho_v + i, *c_c = t.rho_c + i, *c_r = t.rho_r + i;
+  double *o_T = t.o_temp + i, *o_v = t.o_v + i, *o_c = t.o_c + i, *o_r = t.o_r + i, *w_q = w_velqr + i;
+  const double rho0 = c_d[0];
+  double precl_acc = 0;
+  for (int nt = 0; nt < rainsplit; nt++) {
+    const bool first = (nt == 0), lastp = (nt == rainsplit - 1);
+    double flux_above = 0;
+    for (int k = nz - 1; k >= 0; k--) {
+      const long long idx = (long long)k * p.ncol;
+      const double rd = c_d[idx];
+      const double T_in = c_T[idx], rv_in = c_v[idx];
+      double pressure = p.R_d * rd * T_in + p.R_v * rv_in * T_in;
+      const double pp0 = pressure / p.p0;
+      double T, qv, qc, qr, velqr;
+      if (first) {
+        const double ird = rcp64(rd);
+        qv = rv_in * ird; qc = c_c[idx] * ird; qr = c_r[idx] * ird;
+        T = T_in;
+        velqr = kessler_velqr(c_r[idx], rd, ird, rho0);
+      } else { T = o_T[idx]; qv = o_v[idx]; qc = o_c[idx]; qr = o_r[idx]; velqr = w_q[idx]; }
+      flux_above = kessler_cell(p, k, rd, rho0, pp0, dt0, flux_above, T, qv, qc, qr, velqr, precl_acc);
+      if (lastp) {
+        o_v[idx] = qv * rd; o_c[idx] = qc * rd; o_r[idx] = qr * rd;
+        o_T[idx] = T;
+      } else { o_T[idx] = T; o_v[idx] = qv; o_c[idx] = qc; o_r[idx] = qr; w_q[idx] = velqr; }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // STRICT path (mw_kessler_set_strict(1)): the reference's formulas in the reference's operation order -- theta form, IEEE divisions,
 // no contraction -- with glibc's pow and exp (mw_glibc_pow.h): BIT-identical to the CPU oracle (and, with it, to the reference on a
 // glibc host).  Not a performance path: two launches, thread = cell for K1-K3 and thread = column for the sub-cycles.
@@ -598,6 +773,65 @@ int mw_kessler_time_step(int nz, long long ncol, double dz, double dt, double *r
     MW_HIP(hipStreamSynchronize(st));
     double dt_max; memcpy(&dt_max, &hb, 8);
     *rainsplit_out = (int)std::ceil(dt / dt_max);
+  }
+  return 0;
+}
+
+// workspace (bytes): [0, 512) the members' minimum words (64 of them) | w_velqr (nz, ncol * nens) | flux_top (nz / 4 + 1, ncol * nens)
+long long mw_kessler_members_teacher_workspace_bytes(int nz, long long ncol, int nens) {
+  if (nz < 2 || ncol < 1 || nens < 1 || nens > 64) return 0;
+  return 512 + (long long)sizeof(double) * ((long long)nz + (long long)nz / 4 + 1) * ncol * nens;
+}
+
+int mw_kessler_teacher_rainsplit(double dt, double dt_max, int cap) {
+  unsigned long long bits;
+  memcpy(&bits, &dt_max, 8);
+  return kessler_teacher_rainsplit(dt, bits, cap);
+}
+
+int mw_kessler_members_teacher(int nz, long long ncol, int nens, int nm, const int *members, double dz, double dt, int max_rainsplit,
+                               const double *const *fields5, double *const *out4, int *rainsplit_out, void *workspace, void *stream) {
+  if (nz < 2 || ncol < 1) MW_FAIL("kessler_members_teacher: need nz >= 2 and ncol >= 1");
+  if (nens < 1 || nens > 64) MW_FAIL("kessler_members_teacher: nens must be in [1, 64]");
+  if (dt <= 0) MW_FAIL("kessler_members_teacher: called with nonpositive dt");
+  if (max_rainsplit < 1 || max_rainsplit > 1024) MW_FAIL("kessler_members_teacher: max_rainsplit must be in [1, 1024]");
+  if (!members || !fields5 || !out4 || !workspace) MW_FAIL("kessler_members_teacher: null pointer");
+  if (nm < 1 || nm > nens) MW_FAIL("kessler_members_teacher: nm must be in [1, nens]");
+  unsigned long long listed = 0;
+  for (int j = 0; j < nm; j++) {
+    const int e = members[j];
+    if (e < 0 || e >= nens) MW_FAIL("kessler_members_teacher: member " + std::to_string(e) + " is outside [0, " + std::to_string(nens) + ")");
+    if ((listed >> e) & 1ull) MW_FAIL("kessler_members_teacher: member " + std::to_string(e) + " is listed twice");
+    listed |= 1ull << e;
+  }
+  for (int f = 0; f < 5; f++) if (!fields5[f]) MW_FAIL("kessler_members_teacher: null field");
+  for (int f = 0; f < 4; f++) if (!out4[f]) MW_FAIL("kessler_members_teacher: null field");
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  hipStream_t st = (hipStream_t)stream;
+  const long long NC = ncol * nens;                           // the kernels' columns: col * nens + member
+  KesP p; p.nz = nz; p.ncol = NC; p.dz = dz; p.dt = dt; p.R_d = 287.; p.cp_d = 1003.; p.R_v = 461.; p.p0 = 1.e5;
+  unsigned long long *words = (unsigned long long *)workspace;
+  double *w_velqr = (double *)((char *)workspace + 512), *flux_top = w_velqr + (long long)nz * NC;
+  KesTeach t;
+  t.nens = nens; t.cap = max_rainsplit; t.listed = listed; t.words = words;
+  t.temp = fields5[0]; t.rho_d = fields5[1]; t.rho_v = fields5[2]; t.rho_c = fields5[3]; t.rho_r = fields5[4];
+  t.o_temp = out4[0]; t.o_v = out4[1]; t.o_c = out4[2]; t.o_r = out4[3];
+  // every call starts its words from the all-ones pattern, in stream order (no host synchronisation, any number of calls in flight)
+  MW_HIP(hipMemsetAsync(words, 0xFF, 512, st));
+  int chunk = nz;                                             // (mw_kessler_time_step's rule, on the columns of all members)
+  for (int c : {25, 20, 16, 12, 10, 8, 5, 4}) if (c < nz) { chunk = c; if (((NC + 63) / 64) * ((nz + c - 1) / c) >= 16384) break; }
+  const int nchunks = (nz + chunk - 1) / chunk;
+  const int klevels = 5;                                      // (k_kessler_teacher_prep: KL)
+  const unsigned gx = (unsigned)((NC + 255) / 256);
+  hipLaunchKernelGGL(k_kessler_teacher_prep, dim3(gx, (unsigned)((nz + klevels - 1) / klevels)), dim3(256), 0, st, p, nens, listed, t.rho_r,
+                     t.rho_d, flux_top, chunk, klevels, words); MW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_kessler_teacher_chunks, dim3(gx, (unsigned)nchunks), dim3(256), 0, st, p, t, (const double *)flux_top, chunk); MW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_kessler_teacher_column, dim3(gx), dim3(256), 0, st, p, t, w_velqr); MW_LAUNCH_CHECK();
+  if (rainsplit_out) {
+    unsigned long long hw[64];
+    MW_HIP(hipMemcpyAsync(hw, words, 8 * (size_t)nens, hipMemcpyDeviceToHost, st));
+    MW_HIP(hipStreamSynchronize(st));
+    for (int j = 0; j < nm; j++) rainsplit_out[j] = kessler_teacher_rainsplit(dt, kessler_teacher_word(hw[members[j]], dt), max_rainsplit);
   }
   return 0;
 }

@@ -2,10 +2,12 @@
 // mw_member.hip -- passes over the coupler's member-fastest arrays (cell c, ensemble member e at c * nens + e) that treat the members
 // differently: one member out to contiguous arrays and back (mw_member_extract / mw_member_insert: the rollout's Kessler member is stepped
 // alone), and how far every member has moved from member 0 (mw_member_divergence).  No reference counterpart: the reference's ensemble
-// members never meet.
+// members never meet.  mw_member_sample_mask / mw_member_gather_samples are DataGenerator's sampler (k_sample_mask / k_gather_samples of
+// mw_output.hip, which see member 0 only) on the member layout, between a member's own state and its Kessler teacher values.
 // =====================================================================================================
 #include "../../include/mw_cdna4.h"
 #include "mw_common.h"
+#include "mw_sample_key.h"
 #include <algorithm>
 #include <string>
 
@@ -99,6 +101,53 @@ static long long divergence_blocks(long long n, int nens) {
   return std::max<long long>(1, std::min<long long>((n + C - 1) / C, DIV_MAX_BLOCKS));
 }
 
+// ---- mw_member_sample_mask / mw_member_gather_samples --------------------------------------------------------------------------------
+struct MemberSample { const double *in[5]; const double *teach[4]; };       // temp, density_dry, vapor, cloud, rain | temp, vapor, cloud, rain
+
+__device__ __forceinline__ bool f32_finite(double x) { const float f = (float)x; return f - f == 0.0f; }
+
+// thread = flat element t = (k * ncol + col) * nens + e.  A listed member's element is taken if its draw u01(key0 + t) is below the
+// threshold of its class (active: any of the four |teacher - input| > 1e-10, StatisticsGatherer::is_active) AND all fourteen values of its
+// sample record -- the five inputs, the four of the level above, the four teacher values -- are finite as fp32.
+__global__ __launch_bounds__(256) void k_member_sample_mask(MemberSample f, long long n, long long plane, int nens, unsigned long long listed,
+                                                            unsigned long long key0, double thr_active, double thr_inactive,
+                                                            unsigned char *__restrict__ mask) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= n) return;
+  const int e = (int)(t % nens);
+  if (!((listed >> e) & 1ull)) { mask[t] = 0; return; }
+  const long long up = (t + plane < n) ? t + plane : t;                     // level min(nz - 1, k + 1) of the same column and member
+  const int before[4] = {0, 2, 3, 4};                                       // the input that teacher value v replaces
+  bool act = false, fin = f32_finite(f.in[1][t]);
+  for (int v = 0; v < 4; v++) {
+    const double a = f.in[before[v]][t], b = f.teach[v][t];
+    act = act || (fabs(b - a) > 1.e-10);
+    fin = fin && f32_finite(a) && f32_finite(b) && f32_finite(f.in[before[v]][up]);
+  }
+  const double thresh = act ? thr_active : thr_inactive;
+  mask[t] = (fin && u01_from_key(key0 + (unsigned long long)t) < thresh) ? 1 : 0;
+}
+
+// k_gather_samples' records (n, 5, 2) / (n, 4) fp32 for flat element indices of the member layout
+__global__ __launch_bounds__(256) void k_member_gather_samples(MemberSample f, const long long *__restrict__ elems, long long n, long long nelem,
+                                                               long long plane, float *__restrict__ inputs, float *__restrict__ outputs) {
+  const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (s >= n) return;
+  const long long c = elems[s];
+  float *in = inputs + s * 10, *out = outputs + s * 4;
+  if (c < 0 || c >= nelem) {                                                // (an index outside the fields: a record of zeros, no load)
+    for (int v = 0; v < 10; v++) in[v] = 0.0f;
+    for (int v = 0; v < 4; v++) out[v] = 0.0f;
+    return;
+  }
+  const long long up = (c + plane < nelem) ? c + plane : c;
+  in[0] = (float)f.in[0][c];  in[2] = (float)f.in[1][c];  in[4] = (float)f.in[2][c];
+  in[6] = (float)f.in[3][c];  in[8] = (float)f.in[4][c];
+  in[1] = (float)f.in[0][up]; in[3] = (float)f.in[2][up]; in[5] = (float)f.in[3][up];
+  in[7] = (float)f.in[4][up]; in[9] = 0.0f;
+  for (int v = 0; v < 4; v++) out[v] = (float)f.teach[v][c];
+}
+
 } // namespace mw
 
 using namespace mw;
@@ -152,6 +201,53 @@ extern "C" int mw_member_divergence(long long n, int nens, int nf, const double 
   MW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_member_divergence_final, dim3((unsigned)((nf * nens * DIV_ROW + 255) / 256)), dim3(256), 0, st, (int)blocks, nf, nens,
                      (const double *)workspace, out, nonfinite);
+  MW_LAUNCH_CHECK();
+  return 0;
+}
+
+static int member_sample_fields(const char *who, int nz, long long ncol, int nens, const double *const *fields5, const double *const *teacher4,
+                                MemberSample *f) {
+  if (!fields5 || !teacher4) MW_FAIL(std::string(who) + ": null pointer");
+  if (nz < 1 || ncol < 1) MW_FAIL(std::string(who) + ": nz and ncol must be >= 1");
+  if (nens < 1 || nens > 64) MW_FAIL(std::string(who) + ": nens must be in [1, 64]");
+  for (int v = 0; v < 5; v++) { if (!fields5[v]) MW_FAIL(std::string(who) + ": null field"); f->in[v] = fields5[v]; }
+  for (int v = 0; v < 4; v++) { if (!teacher4[v]) MW_FAIL(std::string(who) + ": null field"); f->teach[v] = teacher4[v]; }
+  return 0;
+}
+
+extern "C" int mw_member_sample_mask(int nz, long long ncol, int nens, int nm, const int *members, const double *const *fields5,
+                                     const double *const *teacher4, unsigned long long key0, double thr_active, double thr_inactive,
+                                     unsigned char *mask, void *stream) {
+  MemberSample f;
+  if (member_sample_fields("member_sample_mask", nz, ncol, nens, fields5, teacher4, &f)) return 1;
+  if (!members || !mask) MW_FAIL("member_sample_mask: null pointer");
+  if (nm < 1 || nm > nens) MW_FAIL("member_sample_mask: nm must be in [1, nens]");
+  unsigned long long listed = 0;
+  for (int j = 0; j < nm; j++) {
+    const int e = members[j];
+    if (e < 0 || e >= nens) MW_FAIL("member_sample_mask: member " + std::to_string(e) + " is outside [0, " + std::to_string(nens) + ")");
+    if ((listed >> e) & 1ull) MW_FAIL("member_sample_mask: member " + std::to_string(e) + " is listed twice");
+    listed |= 1ull << e;
+  }
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  const long long plane = ncol * nens, n = plane * nz;
+  hipLaunchKernelGGL(k_member_sample_mask, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f, n, plane, nens, listed, key0,
+                     thr_active, thr_inactive, mask);
+  MW_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mw_member_gather_samples(int nz, long long ncol, int nens, const double *const *fields5, const double *const *teacher4,
+                                        const long long *elems, long long n, float *inputs, float *outputs, void *stream) {
+  MemberSample f;
+  if (member_sample_fields("member_gather_samples", nz, ncol, nens, fields5, teacher4, &f)) return 1;
+  if (n < 0) MW_FAIL("member_gather_samples: n must be >= 0");
+  if (n == 0) return 0;
+  if (!elems || !inputs || !outputs) MW_FAIL("member_gather_samples: null pointer");
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  const long long plane = ncol * nens;
+  hipLaunchKernelGGL(k_member_gather_samples, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f, elems, n, plane * nz, plane,
+                     inputs, outputs);
   MW_LAUNCH_CHECK();
   return 0;
 }

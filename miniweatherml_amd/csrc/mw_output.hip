@@ -9,6 +9,7 @@
 #include "../../include/mw_cdna4.h"
 #include "mw_common.h"
 #include "mw_glibc_pow.h"
+#include "mw_sample_key.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -94,13 +95,7 @@ __global__ __launch_bounds__(256) void k_active_count(Eight f, long long ncell, 
 // custom_modules::DataGenerator::generate_samples_stencil, generate_micro_surrogate_data.h:83-101: which cells to sample.
 // The reference draws yakl::Random(key).genFP<double>() with key = (seed+myrank)*nz*ny*nx + k*ny*nx + j*nx + i; YAKL's generator
 // is not available, so the same key goes through the splitmix64 finaliser (53 random bits -> [0,1)).
-__device__ __forceinline__ double u01_from_key(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
-  return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
+// (u01_from_key: mw_sample_key.h, shared with the member-layout sampler of mw_member.hip)
 __global__ __launch_bounds__(256) void k_sample_mask(Eight f, long long ncell, int nens, unsigned long long key0, double thr_active,
                                                      double thr_inactive, unsigned char *__restrict__ mask) {
   long long t = (long long)blockIdx.x * 256 + threadIdx.x;

@@ -32,6 +32,10 @@ eval_interval-th step all eight coupler fields of every member are scored agains
     persistence_member: true                  # a last member without microphysics, the skill's denominator (default true)
 nens is derived from the list (1 + K, + 1 with the persistence member); a `nens:` key that disagrees is an error.  Writes
 surrogate_rollout.json.  One rank only.
+    harvest: {interval: 10, samples_per_step: 50, ratio_active: 0.5, seed: 1, max_rainsplit: 64, members: [seed0]}
+adds data aggregation to the rollout (modules.RolloutHarvester): every interval-th step (default eval_interval) Kessler is asked what it
+would have done to each listed model member's OWN state (default: all models), and samples of that go to rollout_samples_<name>.nc in the
+working directory -- DataGenerator's format, so `surrogate_train --init DIR` continues a model on the old and the new files together.
 """
 import argparse
 import os
@@ -64,7 +68,7 @@ def load_config(path):
         if key in cfg:
             out[key] = str(cfg[key])
     out["_dir"] = os.path.dirname(os.path.abspath(path))
-    for key in ("surrogate_models", "eval_interval", "persistence_member"):    # read by surrogate_config / rollout_config alone
+    for key in ("surrogate_models", "eval_interval", "persistence_member", "harvest"):    # read by surrogate_config / rollout_config / harvest_config alone
         if key in cfg:
             out[key] = cfg[key]
     return out
@@ -100,6 +104,49 @@ def rollout_config(cfg):
     if {"kessler", "persistence"} & {m["name"] for m in models}:
         raise ValueError("ERROR: 'kessler' and 'persistence' name members of their own: no surrogate model may be called so")
     return models, interval, persistence, nens
+
+
+HARVEST_KEYS = ("interval", "samples_per_step", "ratio_active", "seed", "max_rainsplit", "members")
+
+
+def harvest_config(cfg):
+    """The checked `harvest:` block of a loaded configuration for rollout_surrogates, or None without one: interval (default
+    eval_interval), samples_per_step (50), ratio_active (0.5), seed (None: the clock), max_rainsplit (64), members (model names; default all
+    models of the list).  Only that experiment calls it, after rollout_config's checks."""
+    if "harvest" not in cfg:
+        return None
+    h = cfg["harvest"]
+    h = {} if h is None else h
+    if not isinstance(h, dict):
+        raise ValueError("ERROR: harvest must be a mapping")
+    unknown = sorted(set(h) - set(HARVEST_KEYS))
+    if unknown:
+        raise ValueError("ERROR: unknown key(s) %s in harvest (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(HARVEST_KEYS)))
+    models, eval_interval = surrogate_config(cfg)
+    names = [m["name"] for m in models]
+    out = {"interval": h.get("interval", eval_interval), "samples_per_step": h.get("samples_per_step", 50),
+           "ratio_active": h.get("ratio_active", 0.5), "seed": h.get("seed"), "max_rainsplit": h.get("max_rainsplit", 64),
+           "members": h.get("members", names)}
+    for key in ("interval", "max_rainsplit"):
+        if isinstance(out[key], bool) or not isinstance(out[key], int) or out[key] < 1:
+            raise ValueError("ERROR: harvest.%s must be an integer >= 1" % key)
+    if out["max_rainsplit"] > 1024:
+        raise ValueError("ERROR: harvest.max_rainsplit must be at most 1024")
+    if isinstance(out["samples_per_step"], bool) or not isinstance(out["samples_per_step"], (int, float)) or not out["samples_per_step"] > 0:
+        raise ValueError("ERROR: harvest.samples_per_step must be a number > 0")
+    if isinstance(out["ratio_active"], bool) or not isinstance(out["ratio_active"], (int, float)) or not 0.0 < out["ratio_active"] < 1.0:
+        raise ValueError("ERROR: harvest.ratio_active must be in (0, 1)")
+    if out["seed"] is not None and (isinstance(out["seed"], bool) or not isinstance(out["seed"], int) or out["seed"] < 0):
+        raise ValueError("ERROR: harvest.seed must be an integer >= 0")
+    if not isinstance(out["members"], list) or not out["members"]:
+        raise ValueError("ERROR: harvest.members must be a non-empty list of model names")
+    out["members"] = [str(n) for n in out["members"]]
+    for n in out["members"]:
+        if n not in names:
+            raise ValueError("ERROR: harvest.members names %r, which is no surrogate model (%s)" % (n, ", ".join(names)))
+    if len(set(out["members"])) != len(out["members"]):
+        raise ValueError("ERROR: harvest.members names a model twice")
+    return out
 
 
 def _surrogate_models(entries, yaml_dir):
@@ -214,6 +261,7 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
         if nranks > 1:
             raise ValueError("rollout_surrogates runs on one rank (%d given): SurrogateEvaluator.combine is exact, but the reduction over "
                              "ranks is not built yet" % nranks)
+        harvest = harvest_config(cfg)
         cfg["surrogate_models"], cfg["eval_interval"], cfg["persistence_member"], cfg["nens"] = rollout_config(cfg)
     coupler = _coupler(cfg, device, nranks, myrank, yaml_path)
     dycore = modules.Dynamics_Euler_Stratified_WenoFV()
@@ -273,6 +321,11 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
         if experiment == "evaluate_surrogates":
             evaluator, eval_models = _surrogate_evaluator(cfg["surrogate_models"], device)
         scorer = modules.RolloutScorer(micro.member_names) if experiment == "rollout_surrogates" else None
+        harvester = None
+        if experiment == "rollout_surrogates" and harvest is not None:
+            harvester = micro.harvester = modules.RolloutHarvester()
+            harvester.init(coupler, harvest["members"], [micro.member_names.index(n) for n in harvest["members"]], os.getcwd(),
+                           harvest["samples_per_step"], harvest["ratio_active"], seed=harvest["seed"], max_rainsplit=harvest["max_rainsplit"])
 
         def body(dt, etime):                                                   # :73-76
             dycore.time_step(coupler, dt)
@@ -295,6 +348,8 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                 else:
                     info["samples"] += datagen.generate_samples_stencil(inp, coupler, dt, etime)
             else:
+                if harvester is not None:                                      # (eval_step counts the steps of a rollout)
+                    micro.harvest_now, micro.harvest_etime = eval_step[0] % harvest["interval"] == 0, etime
                 micro.time_step(coupler, dt)
                 if experiment == "inference_ponni" and not quiet and coupler.is_mainproc():
                     d = micro.mean_diffs(coupler)                              # microphysics_kessler_ponni.h:266-269
@@ -342,6 +397,10 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                    "members": list(scorer.member_names), "models": [dict(m, member=1 + k) for k, m in enumerate(cfg["surrogate_models"])],
                    "fields": list(scorer.fields), "statistics": list(modules.ROLLOUT_STATS), "history": scorer.history,
                    "report": rep["times"], "diverged_at": rep["diverged_at"]}
+            if harvester is not None:
+                doc["harvest"] = dict(harvest, files=dict(harvester.files), samples=dict(harvester.samples), skipped=dict(harvester.skipped),
+                                      calls=harvester.calls)
+                info["harvest"] = doc["harvest"]
             info["surrogate_rollout"] = os.path.join(os.getcwd(), "surrogate_rollout.json")
             with open(info["surrogate_rollout"], "w") as f:
                 json.dump(doc, f, indent=1, allow_nan=False)

@@ -726,6 +726,7 @@ class SurrogateEvaluator:
 ROLLOUT_FIELDS = ("density_dry", "uvel", "vvel", "wvel", "temp", "water_vapor", "cloud_liquid", "precip_liquid")
 ROLLOUT_STATS = ("sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_x", "min_x", "max_x")
 ROLLOUT_WATER = ("water_vapor", "cloud_liquid", "precip_liquid")
+ROLLOUT_IN5 = ("temp", "density_dry", "water_vapor", "cloud_liquid", "precip_liquid")     # fields5 of members_apply and of the teacher
 
 
 def rollout_member_names(model_names, persistence=True):
@@ -746,9 +747,14 @@ class Microphysics_Rollout(Microphysics_Kessler):
     member k by model k - 1 of `models` (its output written back: Microphysics_Kessler_Surrogate.online for that member), the optional last
     member by nothing.  The dycore, the sponge and the nudger step the members independently, so one run shows how each candidate behaves
     once its own output is fed back.  Kessler runs on member 0 ALONE, extracted to contiguous arrays: its rain sub-cycle count is a minimum
-    over all the columns of a call.  `precl` is written for member 0 only; the other members' precl keeps whatever it held."""
+    over all the columns of a call.  `precl` is written for member 0 only; the other members' precl keeps whatever it held.
+    With a `harvester` (RolloutHarvester) and `harvest_now` set, the step harvests Kessler labels on the model members' own states
+    between the Kessler member's step and the models'; harvesting reads the state and never writes it."""
 
     mlp_strict = 0        # 1: the thread-per-cell MLP kernels (mw_mlp_set_strict)
+    harvester = None      # a RolloutHarvester: time_step harvests when harvest_now is set (the driver sets it, and harvest_etime, per step)
+    harvest_now = False
+    harvest_etime = 0.0
 
     def micro_name(self):
         return "rollout"
@@ -799,9 +805,129 @@ class Microphysics_Rollout(Microphysics_Kessler):
                                          _ptr(self._ws), None, st))
             check(L.mw_member_insert(n, nens, 0, 4, _field_ptr_array([v0, c0, r0, t0]), _field_ptr_array([rho_v, rho_c, rho_r, temp]), st))
             check(L.mw_member_insert(ncol, nens, 0, 1, _field_ptr_array([p0]), _field_ptr_array([precl]), st))
+        if self.harvester is not None and self.harvest_now:                    # the teacher sees the state each model is about to replace
+            self.last_harvest = self.harvester.harvest(coupler, dt, self.harvest_etime)
         for bank, members in self.banks:
             bank.strict = self.mlp_strict
             bank.members_apply(nz, members, [temp, rho_d, rho_v, rho_c, rho_r])
+
+
+def kessler_members_teacher(coupler, members, dt, max_rainsplit=64, outs=None, return_rainsplit=False):
+    """mw_kessler_members_teacher on the coupler's member-fastest fields: what Kessler would do to the state of every member in `members`,
+    each member alone, out of place.  Returns the four teacher tensors (temp, water_vapor, cloud_liquid, precip_liquid after Kessler), each
+    (nz, ny, nx, nens); only the listed members' elements are written (outs: four tensors to write into, default new uninitialised ones).
+    A member whose own state asks for more than max_rainsplit rain sub-cycles, or whose rain CFL step is not a positive finite number, is
+    skipped: not computed, not written.  return_rainsplit=True: (tensors, counts per listed member, 0 = skipped), at the price of a
+    stream synchronisation.  The coupler's fields are read only."""
+    dm = coupler.get_data_manager_readonly()
+    f5 = [dm.get(n, True) for n in ROLLOUT_IN5]
+    members = [int(m) for m in members]
+    nz, nens = coupler.get_nz(), coupler.get_nens()
+    ncol = coupler.get_ny() * coupler.get_nx()
+    if outs is None:
+        outs = [torch.empty_like(f5[0]) for _ in range(4)]
+    if len(outs) != 4 or any(o.shape != f5[0].shape or o.device != f5[0].device for o in outs):
+        endrun("kessler_members_teacher: outs must be four tensors of the fields' shape on their device")
+    L = capi.lib()
+    nbytes = L.mw_kessler_members_teacher_workspace_bytes(nz, ncol, nens)
+    if nbytes <= 0:
+        endrun("kessler_members_teacher: nz = %d, %d columns and %d members are out of range (nz >= 2, at most 64 members)" % (nz, ncol, nens))
+    ws = getattr(coupler, "_ws_teacher", None)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = coupler._ws_teacher = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=coupler.device)
+    rs = (C.c_int * max(1, len(members)))()
+    with torch.cuda.device(coupler.device):
+        check(L.mw_kessler_members_teacher(nz, ncol, nens, len(members), (C.c_int * max(1, len(members)))(*members), coupler.get_dz(), float(dt),
+                                           int(max_rainsplit), _field_ptr_array(f5), _field_ptr_array(outs), rs if return_rainsplit else None,
+                                           _ptr(ws), _stream_ptr(coupler.device)))
+    return (outs, [int(rs[j]) for j in range(len(members))]) if return_rainsplit else outs
+
+
+class RolloutHarvester:
+    """Data aggregation for the rollout (no reference counterpart): while the candidate models run online as ensemble members, ask the
+    teacher -- Kessler -- what it would have done to each model member's OWN state, and keep (state, label) samples of it in one file per
+    member, `rollout_samples_<name>.nc`, with exactly DataGenerator's dimensions and variables (surrogate_train.read_samples takes them
+    unchanged).  harvest() is teacher -> mask -> nonzero -> gather -> append; the coupler's state is read, never written."""
+
+    def init(self, coupler, member_names, members, directory, samples_per_step=50, ratio_active=0.5, prior_active=0.4, seed=None,
+             max_rainsplit=64):
+        """member_names / members: the harvested model members' names and ensemble indices.  samples_per_step, ratio_active: the wanted
+        samples per call and member and the wanted share of active cells among them (DataGenerator's 50 and 0.5); prior_active: the share
+        of active cells assumed when the thresholds are set (DataGenerator's 0.4); seed: call c draws with seed + c (default: the clock)."""
+        import time as _time
+        self.member_names, self.members = [str(n) for n in member_names], [int(m) for m in members]
+        if len(self.member_names) != len(self.members) or not self.members or len(set(self.members)) != len(self.members) or \
+                len(set(self.member_names)) != len(self.members):
+            endrun("RolloutHarvester: as many distinct names as distinct members, at least one")
+        if any(not 0 <= m < coupler.get_nens() for m in self.members):
+            endrun("RolloutHarvester: members %r outside [0, %d)" % (self.members, coupler.get_nens()))
+        if not (samples_per_step > 0 and 0.0 < ratio_active < 1.0 and 0.0 < prior_active < 1.0 and 1 <= int(max_rainsplit) <= 1024):
+            endrun("RolloutHarvester: samples_per_step > 0, ratio_active and prior_active in (0, 1), max_rainsplit in [1, 1024]")
+        self.samples_per_step, self.ratio_active, self.prior_active = float(samples_per_step), float(ratio_active), float(prior_active)
+        self.max_rainsplit = int(max_rainsplit)
+        self.seed = int(_time.time()) if seed is None else int(seed)
+        self.files = {n: os.path.join(directory, "rollout_samples_%s.nc" % n) for n in self.member_names}
+        for f in self.files.values():
+            _sample_file_create(f)
+        self.samples = {n: 0 for n in self.member_names}
+        self.skipped = {n: 0 for n in self.member_names}
+        self.calls = 0
+        self._meta_written = False
+        self._teacher = None
+        self.last_elems = None
+
+    def thresholds(self, coupler):
+        """DataGenerator's two formulas (generate_micro_surrogate_data.h:58-62) per member, clamped to 1."""
+        ncell = coupler.get_nz() * coupler.get_ny() * coupler.get_nx()
+        thr_act = self.ratio_active * self.samples_per_step / (self.prior_active * ncell)
+        thr_inact = (1 - self.ratio_active) * self.samples_per_step / ((1 - self.prior_active) * ncell)
+        return min(1.0, thr_act), min(1.0, thr_inact)
+
+    def harvest(self, coupler, dt, etime):
+        """One call: {name: samples added}.  A member the teacher skipped adds none and counts in `skipped`."""
+        dm = coupler.get_data_manager_readonly()
+        f5 = [dm.get(n, True) for n in ROLLOUT_IN5]
+        nz, nens = coupler.get_nz(), coupler.get_nens()
+        ncol = coupler.get_ny() * coupler.get_nx()
+        nelem = nz * ncol * nens
+        dev = coupler.device
+        if self._teacher is None or self._teacher[0].shape != f5[0].shape:
+            self._teacher = [torch.empty_like(f5[0]) for _ in range(4)]
+        teacher, rs = kessler_members_teacher(coupler, self.members, dt, self.max_rainsplit, self._teacher, return_rainsplit=True)
+        live = [(n, m) for n, m, r in zip(self.member_names, self.members, rs) if r > 0]
+        for n, r in zip(self.member_names, rs):
+            self.skipped[n] += int(r == 0)
+        thr_act, thr_inact = self.thresholds(coupler)
+        max_mag = (2 ** 64 - 1) // (1 + nelem)
+        key0 = (((self.seed + self.calls) % max_mag) * nelem) % (2 ** 64)
+        self.calls += 1
+        added = {n: 0 for n in self.member_names}
+        write_meta, self._meta_written = not self._meta_written, True
+        ins = outs = which = None
+        if live:
+            L = capi.lib()
+            mask = torch.empty(nelem, dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                check(L.mw_member_sample_mask(nz, ncol, nens, len(live), (C.c_int * len(live))(*[m for _, m in live]), _field_ptr_array(f5),
+                                              _field_ptr_array(teacher), key0, thr_act, thr_inact, C.c_void_p(mask.data_ptr()), _stream_ptr(dev)))
+                elems = torch.nonzero(mask).flatten().contiguous()             # ascending, as DataGenerator compacts
+                n = int(elems.numel())
+                ins = torch.empty((n, 5, 2), dtype=torch.float32, device=dev)
+                outs = torch.empty((n, 4), dtype=torch.float32, device=dev)
+                check(L.mw_member_gather_samples(nz, ncol, nens, _field_ptr_array(f5), _field_ptr_array(teacher), C.c_void_p(elems.data_ptr()), n,
+                                                 C.c_void_p(ins.data_ptr()), C.c_void_p(outs.data_ptr()), _stream_ptr(dev)))
+            self.last_elems = elems.cpu().numpy()                              # (k * ncol + col) * nens + member of the samples (diagnostic)
+            ins, outs, which = ins.cpu().numpy(), outs.cpu().numpy(), self.last_elems % nens
+        else:
+            self.last_elems = np.zeros(0, dtype=np.int64)
+        for name, m in zip(self.member_names, self.members):
+            sel = (which == m) if which is not None else np.zeros(0, dtype=bool)
+            a = ins[sel] if which is not None else np.zeros((0, 5, 2), dtype=np.float32)
+            b = outs[sel] if which is not None else np.zeros((0, 4), dtype=np.float32)
+            _sample_file_append(self.files[name], coupler, dt, a, b, write_meta)
+            added[name] = int(a.shape[0])
+            self.samples[name] += added[name]
+        return added
 
 
 def member_divergence(coupler, names):
@@ -1363,6 +1489,37 @@ class StatisticsGatherer:
         self.print(coupler)
 
 
+def _sample_file_create(fname):
+    """An empty sample file: DataGenerator's dimensions and variables (generate_micro_surrogate_data.h:17-33), all defined at once."""
+    nc = _NcFile(fname, True, 5)
+    ds, dvi, dst, dvo = nc.def_dim("nsamples", 0), nc.def_dim("num_vars_in", 5), nc.def_dim("sten_size", 2), nc.def_dim("num_vars_out", 4)
+    for n in ("time_step_size", "dx", "dy", "dz", "xlen", "ylen", "zlen"):
+        nc.def_var_typed(n, 6, [])
+    nc.def_var_typed("only_two_dimensions", 4, [])
+    nc.def_var_typed("inputs", 5, [ds, dvi, dst])
+    nc.def_var_typed("outputs", 5, [ds, dvo])
+    nc.enddef()
+    nc.close()
+
+
+def _sample_file_append(fname, coupler, dt, ins, outs, write_meta):
+    """Appends host records ins (n, 5, 2), outs (n, 4) fp32 to a sample file (:116-153); write_meta: the grid's scalars first (:118-125,
+    `if (!nc.varExists(..)) nc.write(..)`)."""
+    n = int(ins.shape[0])
+    nc = _NcFile(fname, False)
+    ul = nc.dimlen("nsamples")                                                 # :116
+    if write_meta:
+        for name, val in (("time_step_size", dt), ("dx", coupler.get_dx()), ("dy", coupler.get_dy()), ("dz", coupler.get_dz()),
+                          ("xlen", coupler.get_xlen()), ("ylen", coupler.get_ylen()), ("zlen", coupler.get_zlen())):
+            nc.put_typed(nc.varid(name), [], [], np.array([val], dtype=np.float64))
+        nc.put_typed(nc.varid("only_two_dimensions"), [], [], np.array([0 if coupler.get_ny_glob() == 1 else 1], dtype=np.int32))
+    if n:
+        nc.put_typed(nc.varid("inputs"), [ul, 0, 0], [n, 5, 2], np.ascontiguousarray(ins))
+        nc.put_typed(nc.varid("outputs"), [ul, 0], [n, 4], np.ascontiguousarray(outs))
+        nc.set_numrecs(ul + n)
+    nc.close()
+
+
 class DataGenerator:
     """custom_modules::DataGenerator, experiments/supercell_kessler_surrogate/custom_modules/generate_micro_surrogate_data.h:11-156:
     samples (5 inputs x 2-cell vertical stencil, 4 outputs; fp32) of the microphysics' effect, about half of them from active
@@ -1375,15 +1532,7 @@ class DataGenerator:
 
     def init(self, coupler, directory="."):                                    # :17-33
         self.fname = os.path.join(directory, "supercell_kessler_data_task_%d.nc" % coupler.get_myrank())
-        nc = _NcFile(self.fname, True, 5)
-        ds, dvi, dst, dvo = nc.def_dim("nsamples", 0), nc.def_dim("num_vars_in", 5), nc.def_dim("sten_size", 2), nc.def_dim("num_vars_out", 4)
-        for n in ("time_step_size", "dx", "dy", "dz", "xlen", "ylen", "zlen"):
-            nc.def_var_typed(n, 6, [])
-        nc.def_var_typed("only_two_dimensions", 4, [])
-        nc.def_var_typed("inputs", 5, [ds, dvi, dst])
-        nc.def_var_typed("outputs", 5, [ds, dvo])
-        nc.enddef()
-        nc.close()
+        _sample_file_create(self.fname)
         self._meta_written = False
         if coupler.is_mainproc():
             with open(os.path.join(directory, "supercell_kessler_metadata.txt"), "w") as f:
@@ -1420,19 +1569,8 @@ class DataGenerator:
                                             C.c_void_p(cells.data_ptr()), n, C.c_void_p(ins.data_ptr()), C.c_void_p(outs.data_ptr()),
                                             _stream_ptr(dev)))
         self.last_cells = cells.cpu().numpy()                                 # k*ny*nx + j*nx + i of the samples (diagnostic)
-        nc = _NcFile(self.fname, False)
-        ul = nc.dimlen("nsamples")                                             # :116
-        if not self._meta_written:                                             # :118-125 (`if (!nc.varExists(..)) nc.write(..)`)
-            for name, val in (("time_step_size", dt), ("dx", inp.get_dx()), ("dy", inp.get_dy()), ("dz", inp.get_dz()),
-                              ("xlen", inp.get_xlen()), ("ylen", inp.get_ylen()), ("zlen", inp.get_zlen())):
-                nc.put_typed(nc.varid(name), [], [], np.array([val], dtype=np.float64))
-            nc.put_typed(nc.varid("only_two_dimensions"), [], [], np.array([0 if inp.get_ny_glob() == 1 else 1], dtype=np.int32))
-            self._meta_written = True
-        if n:
-            nc.put_typed(nc.varid("inputs"), [ul, 0, 0], [n, 5, 2], ins.cpu().numpy())
-            nc.put_typed(nc.varid("outputs"), [ul, 0], [n, 4], outs.cpu().numpy())
-            nc.set_numrecs(ul + n)
-        nc.close()
+        _sample_file_append(self.fname, inp, dt, ins.cpu().numpy(), outs.cpu().numpy(), not self._meta_written)
+        self._meta_written = True
         return n
 
 

@@ -191,8 +191,9 @@ def read_samples(sample_files, stencil=False):
     return inputs, outputs, meta
 
 
-def data_scaling(inputs, outputs):
-    """Refuses unusable data and returns the min-max tables scl_in (5 | 9, 2), scl_out (4, 2) (fp64 arrays holding the fp32 extremes)."""
+def data_scaling(inputs, outputs, allow_constant=False):
+    """Refuses unusable data and returns the min-max tables scl_in (5 | 9, 2), scl_out (4, 2) (fp64 arrays holding the fp32 extremes).
+    allow_constant (a warm start, whose tables are the continued model's): a constant variable is no refusal."""
     if inputs.shape[0] == 0:
         raise SurrogateTrainError("the sample files hold zero samples")
     for arr, what in ((inputs, "inputs"), (outputs, "outputs")):
@@ -203,11 +204,32 @@ def data_scaling(inputs, outputs):
     for arr, names, what in ((inputs, STENCIL_IN_NAMES if inputs.shape[1] == 9 else IN_NAMES, "input"), (outputs, OUT_NAMES, "output")):
         lo, hi = arr.min(axis=0), arr.max(axis=0)
         for v in range(arr.shape[1]):
-            if not hi[v] > lo[v]:
+            if not hi[v] > lo[v] and not allow_constant:
                 raise SurrogateTrainError("%s variable %d (%s) is constant (min = max = %r): its scaling (x - min) / (max - min) would "
                                           "divide by zero" % (what, v, names[v], float(lo[v])))
         tabs.append(np.ascontiguousarray(np.stack([lo, hi], axis=1).astype(np.float64)))
     return tabs[0], tabs[1]
+
+
+def load_init(init, stencil=False):
+    """The model a warm start continues: (weights (104 | 144,) fp32 in Keras order, scl_in, scl_out) from DIR/weights.txt,
+    input_scaling.txt and output_scaling.txt (the files write_outputs leaves), read by modules.load_surrogate_weights.  Host only.  The
+    width must be the one that is trained."""
+    from .modules import MWError, load_surrogate_weights
+    paths = [os.path.join(os.fspath(init), f) for f in ("weights.txt", "input_scaling.txt", "output_scaling.txt")]
+    for path in paths:
+        if not os.path.exists(path):
+            raise SurrogateTrainError("init: no file %s" % path)
+    try:
+        W1, b1, W2, b2, scl_in, scl_out = load_surrogate_weights(weights_txt=paths[0], in_scaling_txt=paths[1], out_scaling_txt=paths[2])
+    except MWError as e:
+        raise SurrogateTrainError("init: %s" % e)
+    w = np.concatenate([np.ravel(W1), np.ravel(b1), np.ravel(W2), np.ravel(b2)]).astype(np.float32)
+    if w.size != n_params(stencil):
+        raise SurrogateTrainError("init: %s holds the %s model (%d parameters), but the %s model (%d) is trained%s"
+                                  % (init, "stencil" if w.size == 144 else "single-cell", w.size, "stencil" if stencil else "single-cell",
+                                     n_params(stencil), "" if stencil else " (--stencil trains the other)"))
+    return w, np.ascontiguousarray(scl_in, dtype=np.float64), np.ascontiguousarray(scl_out, dtype=np.float64)
 
 
 def check_arguments(n, epochs, batch_size, test_split, validation_split, models):
@@ -293,7 +315,7 @@ class Trainer:
     data: raw_in (n, 5) trains the single-cell model (104 parameters), raw_in (n, 9) the stencil model (144)."""
 
     def __init__(self, raw_in, raw_out, scl_in, scl_out, n_split, seed=0, split_seed=None, models=1, batch_size=1024, epochs=10,
-                 learning_rate=1e-3):
+                 learning_rate=1e-3, initial=None):
         import torch
         from . import capi
         self.torch, self.L = torch, capi.lib()
@@ -322,7 +344,13 @@ class Trainer:
         self.params = self.buf[:self.K * NP * 4].view(f32).view(self.K, NP)
         self.tstats = self.buf[self.K * NP * 4:self.K * (NP * 4 + 16)].view(torch.float64).view(self.K, 2)
         self.vstats = self.buf[self.K * (NP * 4 + 16):].view(torch.float64).view(self.K, 24)
-        self.params.copy_(torch.from_numpy(initial_weights(self.seed, self.K, stencil=self.n_in == 9)))
+        if initial is None:
+            w0 = initial_weights(self.seed, self.K, stencil=self.n_in == 9)
+        else:                                                              # a warm start: (K, npar), the moments and the step counter at zero
+            w0 = np.ascontiguousarray(initial, dtype=np.float32)
+            if w0.shape != (self.K, NP):
+                raise SurrogateTrainError("Trainer: initial weights %r; expected (%d, %d)" % (w0.shape, self.K, NP))
+        self.params.copy_(torch.from_numpy(w0))
         self.m1 = torch.zeros((self.K, NP), dtype=f32, device=dev)
         self.m2 = torch.zeros((self.K, NP), dtype=f32, device=dev)
         self.lr = float(learning_rate)
@@ -407,7 +435,7 @@ def _metrics(s):
 
 
 def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test_split=0.2, validation_split=0.2, learning_rate=1e-3,
-                    seed=0, models=1, device="cuda:0", split_seed=None, verbose=False, stencil=False, keep_all=False):
+                    seed=0, models=1, device="cuda:0", split_seed=None, verbose=False, stencil=False, keep_all=False, init=None):
     """Trains `models` surrogates (seeds seed .. seed + models - 1; the pre-shuffle / split uses split_seed, default seed) on the samples of
     `sample_files` and returns a dict: per-model `history` (Keras' loss, mean_absolute_error, val_loss, val_mean_absolute_error per
     epoch), `weights` (models, 104) fp32, `best_model` (lowest final val_loss, ties to the lowest index), `test_metrics` of the best model
@@ -415,16 +443,24 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     out_dir: also writes the best model's weights.txt, input_scaling.txt, output_scaling.txt and history.json there.
     stencil=True: the two-cell stencil model (9 inputs, `weights` (models, 144), `"inputs": "stencil"` in the result and history.json).
     keep_all=True (with out_dir): also weights_<k>.txt for every trained model, and `surrogate_models` in the result: the list the
-    evaluate_surrogates driver takes (names seed<seed>; the scaling files are the shared ones)."""
+    evaluate_surrogates driver takes (names seed<seed>; the scaling files are the shared ones).
+    init=DIR (a warm start, e.g. on the old sample files and a rollout's harvested ones together): every model starts from DIR/weights.txt
+    instead of its seeded draw -- the models then differ by their epoch shuffles only -- and the scaling tables are DIR's, not the data's
+    (samples outside the old range scale outside [0, 1]); the Nadam moments and the step counter start at zero.  The result gains `init`
+    and `initial_weights` (models, 104 | 144)."""
     inputs, outputs, meta = read_samples(sample_files, stencil=stencil)
-    scl_in, scl_out = data_scaling(inputs, outputs)
+    scl_in, scl_out = data_scaling(inputs, outputs, allow_constant=init is not None)
     n = inputs.shape[0]
     n_split = check_arguments(n, epochs, batch_size, test_split, validation_split, models)
+    initial = None
+    if init is not None:
+        w0, scl_in, scl_out = load_init(init, stencil)
+        initial = np.repeat(w0[None, :], int(models), axis=0)
     import torch
     dev = torch.device(device)
     raw_in = torch.from_numpy(inputs).to(dev)
     raw_out = torch.from_numpy(outputs).to(dev)
-    tr = Trainer(raw_in, raw_out, scl_in, scl_out, n_split, seed, split_seed, models, batch_size, epochs, learning_rate)
+    tr = Trainer(raw_in, raw_out, scl_in, scl_out, n_split, seed, split_seed, models, batch_size, epochs, learning_rate, initial=initial)
     del raw_in, raw_out
     K, (n_train, n_val, n_test) = int(models), n_split
     hist = [{"loss": [], "mean_absolute_error": [], "val_loss": [], "val_mean_absolute_error": []} for _ in range(K)]
@@ -471,6 +507,8 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
               "batch_size": int(batch_size), "epochs": int(epochs), "learning_rate": float(learning_rate),
               "inputs": "stencil" if stencil else "single_cell"}
     result.update({k: meta[k] for k in ("time_step_size", "dx", "dy", "dz", "files")})
+    if init is not None:
+        result["init"], result["initial_weights"] = os.fspath(init), initial
     if verbose:
         print("Max relative errors:  ", metrics["max_relative_error"])
         print("Mean relative errors: ", metrics["mean_relative_error"])
@@ -502,11 +540,13 @@ def main(argv=None):
     ap.add_argument("--keep-all", action="store_true", help="also write weights_<k>.txt for every trained model and print the surrogate_models list "
                     "for the evaluate_surrogates and rollout_surrogates drivers")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--init", default=None, metavar="DIR", help="warm start: continue DIR/weights.txt with DIR's scaling tables (all models start there)")
     ap.add_argument("--stencil", action="store_true", help="train the two-cell stencil model (the cell and the level above: 9 inputs, 144 weights)")
     a = ap.parse_args(argv)
     try:
         r = train_surrogate(a.files, a.out, a.epochs, a.batch_size, a.test_split, a.validation_split, a.learning_rate, a.seed, a.models,
-                            a.device, a.split_seed, verbose=True, stencil=a.stencil, keep_all=a.keep_all)
+                            a.device, a.split_seed, verbose=True, stencil=a.stencil, keep_all=a.keep_all,
+                            init=a.init)
     except SurrogateTrainError as e:
         print("ERROR: %s" % e, file=sys.stderr)
         return 2
