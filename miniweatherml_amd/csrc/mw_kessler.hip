@@ -4,7 +4,7 @@
 //
 // Three kernels, no host synchronisation (rainsplit is read from device memory by the kernels themselves, so the
 // reference's device->host minval sync (:276) disappears; the kernel that does not apply returns at once):
-//   k_kessler_prep   [K1,K2,K3]  per cell: r, rhalf, velqr, CFL limit; block min -> one 64-bit atomicMin.  Also stores the
+//   k_kessler_prep_t [K1,K2,K3] per cell: r, rhalf, velqr, CFL limit; block min -> one 64-bit atomicMin.  Also stores the
 //                                pre-update rain flux r*qr*velqr of the levels that sit just above a z chunk.
 //   k_kessler_chunks [K4,K5]     rainsplit == 1 (the normal case: the rain CFL step is ~16 s, the dycore's < 1 s): the
 //                                reference's "all sed(k) first, then adjust" (:288-335) only needs the PRE-update value of
@@ -142,15 +142,26 @@ __device__ __forceinline__ double kessler_velqr(double rho_r, double rd, double 
 // is PROVEN harmless without any transcendental: for 0.001 rho_r <= 1 the power (qr r)^0.1364 is <= 1, so
 // velqr <= 36.34 sqrt(rho0 / rho) < limit  <=>  36.34^2 rho0 (1 + 1e-9) < limit^2 rho.  Only wavefronts with an unproven cell -- or on a
 // chunk-boundary level, whose flux the sweep needs -- evaluate the fall speed (:260).  The pass is then a stream over two fields.
-__global__ __launch_bounds__(256) void k_kessler_prep(KesP p, const double *__restrict__ rho_r, const double *__restrict__ rho_d,
-                                                      double *__restrict__ flux_top, int chunk, int klevels,
-                                                      unsigned long long *dtmax_bits, unsigned long long *next_bits) {
+// TEACH (k_kessler_prep_t<true>, the teacher's CFL pass, see TEACHER below): p.ncol = ncol * nens columns with the member fastest, only
+// columns of `listed` members take part, `words` holds one minimum word per member and a column lowers the word of member i % nens only;
+// next_bits is not used.  A column that could raise its member's count is rare (see above); a wavefront that holds one reduces per
+// member present, then one atomicMin per (wavefront, member).
+template <bool TEACH>
+__global__ __launch_bounds__(256) void k_kessler_prep_t(KesP p, const double *__restrict__ rho_r, const double *__restrict__ rho_d,
+                                                        double *__restrict__ flux_top, int chunk, int klevels,
+                                                        unsigned long long *words, unsigned long long *next_bits,
+                                                        int nens, unsigned long long listed) {
 #pragma clang fp contract(off)
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *next_bits = MW_KES_INF;      // the NEXT call's word (see MW_KES_INF)
+  if constexpr (!TEACH)
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *next_bits = MW_KES_INF;    // the NEXT call's word (see MW_KES_INF)
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   const int k0 = blockIdx.y * klevels, k1 = min(k0 + klevels, p.nz);
+  int e = -1;                                                 // the column's member (TEACH)
+  if constexpr (TEACH) e = (i < p.ncol) ? (int)(i % nens) : -1;
   double dtc = p.dt;                                          // every cell's contribution is capped at dt (see above)
-  if (i < p.ncol) {
+  bool takes_part = i < p.ncol;
+  if constexpr (TEACH) takes_part = e >= 0 && ((listed >> e) & 1ull);
+  if (takes_part) {
     const double rho0 = rho_d[i];
     const double lim = 0.8 * p.dz / p.dt;
     const double lhs = (36.34 * 36.34) * rho0 * (1.0 + 1.0e-9), lim2 = lim * lim;
@@ -172,38 +183,59 @@ __global__ __launch_bounds__(256) void k_kessler_prep(KesP p, const double *__re
       }
     } else {
 #pragma unroll
-    for (int m = 0; m < KL; m++) { const long long idx = (long long)min(k0 + m, p.nz - 1) * p.ncol + i; rdv[m] = rho_d[idx]; }
+      for (int m = 0; m < KL; m++) { const long long idx = (long long)min(k0 + m, p.nz - 1) * p.ncol + i; rdv[m] = rho_d[idx]; }
 #pragma unroll
-    for (int m = 0; m < KL; m++) {
-      const int k = k0 + m;
-      if (k >= k1) break;
-      const double rd = rdv[m], rr = rrv[m];
-      const bool boundary = (k > 0 && k % chunk == 0);        // block-uniform
-      const bool proven = (0.001 * rr <= 1.0) && (lhs < lim2 * rd);
-      if (boundary || __any(!proven)) {
-        const double ird = rcp64(rd);
-        const double qr = rr * ird, r = 0.001 * rd;           // :140, :256
-        const double velqr = kessler_velqr(rr, rd, ird, rho0);   // :257-260
-        if (boundary) flux_top[(long long)(k / chunk - 1) * p.ncol + i] = r * qr * velqr;   // flux entering the chunk below
-        if (k < p.nz - 1) {                                   // :262-268
-          const double zk = (k + 0.5) * p.dz, zk1 = (k + 1 + 0.5) * p.dz;   // zmid, :137
-          const double c = (velqr > 1.e-10) ? 0.8 * (zk1 - zk) / velqr : p.dt;
-          dtc = fmin(dtc, c);
+      for (int m = 0; m < KL; m++) {
+        const int k = k0 + m;
+        if (k >= k1) break;
+        const double rd = rdv[m], rr = rrv[m];
+        const bool boundary = (k > 0 && k % chunk == 0);      // block-uniform
+        const bool proven = (0.001 * rr <= 1.0) && (lhs < lim2 * rd);
+        if (boundary || __any(!proven)) {
+          const double ird = rcp64(rd);
+          const double qr = rr * ird, r = 0.001 * rd;         // :140, :256
+          const double velqr = kessler_velqr(rr, rd, ird, rho0);   // :257-260
+          if (boundary) flux_top[(long long)(k / chunk - 1) * p.ncol + i] = r * qr * velqr;   // flux entering the chunk below
+          // TEACH: rain or a fall speed that is inf or NaN, at any level: the member cannot be labelled.  Its step is 0, which
+          // kessler_teacher_rainsplit refuses.  (Left alone such a cell looks harmless: kes_log(inf) is NaN, kes_exp's clamp drops the NaN,
+          // the fall speed comes out as 0 and the cell contributes dt.  Such rain is never "proven", so it always gets here.)
+          if constexpr (TEACH)
+            if (!(fabs(rr) <= 1.7976931348623157e308) || !(fabs(velqr) <= 1.7976931348623157e308)) dtc = 0.0;
+          if (k < p.nz - 1) {                                 // :262-268
+            const double zk = (k + 0.5) * p.dz, zk1 = (k + 1 + 0.5) * p.dz;   // zmid, :137
+            const double c = (velqr > 1.e-10) ? 0.8 * (zk1 - zk) / velqr : p.dt;
+            dtc = fmin(dtc, c);                               // (fmin drops a NaN c: dtc stays in [0, dt])
+          }
         }
       }
     }
-    }
   }
-  // block min (wave shuffle, then LDS across the 4 waves); positive doubles order like their bit patterns
-  for (int off = 32; off > 0; off >>= 1) { double o = __shfl_down(dtc, off, 64); dtc = fmin(dtc, o); }
-  __shared__ double smin[4];
-  int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) smin[wv] = dtc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double m = fmin(fmin(smin[0], smin[1]), fmin(smin[2], smin[3]));
-    if (m < p.dt || (blockIdx.x == 0 && blockIdx.y == 0))                    // one word, one atomic per block that has something to say
-      atomicMin(dtmax_bits, (unsigned long long)__double_as_longlong(m));     // :276 minval(dt2d), capped at dt
+  if constexpr (TEACH) {
+    // all 64 lanes are here again.  dtc is in [0, dt] and never NaN: its bit pattern orders like the value.
+    const bool has = dtc < p.dt;
+    unsigned long long todo = __ballot(has);
+    const int lane = threadIdx.x & 63;
+    while (todo) {                                            // one round per member that has something to say
+      const int leader = __ffsll((long long)todo) - 1;
+      const int e0 = __shfl(e, leader, 64);
+      const bool mine = has && e == e0;
+      double m = mine ? dtc : p.dt;
+      for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(m, off, 64); m = fmin(m, o); }
+      if (lane == leader) atomicMin(words + e0, (unsigned long long)__double_as_longlong(m));
+      todo &= ~__ballot(mine);
+    }
+  } else {
+    // block min (wave shuffle, then LDS across the 4 waves); positive doubles order like their bit patterns
+    for (int off = 32; off > 0; off >>= 1) { double o = __shfl_down(dtc, off, 64); dtc = fmin(dtc, o); }
+    __shared__ double smin[4];
+    int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) smin[wv] = dtc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double m = fmin(fmin(smin[0], smin[1]), fmin(smin[2], smin[3]));
+      if (m < p.dt || (blockIdx.x == 0 && blockIdx.y == 0))                  // one word, one atomic per block that has something to say
+        atomicMin(words, (unsigned long long)__double_as_longlong(m));        // :276 minval(dt2d), capped at dt
+    }
   }
 }
 
@@ -265,11 +297,17 @@ __device__ __forceinline__ double kessler_cell(const KesP &p, int k, double rd, 
   return flux_here;
 }
 
-// rainsplit == 1: thread = (column i, z chunk c), top-down over the chunk's levels.
+// Where a sweep stores its four results.  The in-place kernels write the fields they read and do not look at it; the teacher's
+// kernels (TEACH, see TEACHER below) read the fields and write here.
+struct KesOut { double *T, *v, *c, *r; };
+
+// rainsplit == 1: thread = (column i, z chunk c), top-down over the chunk's levels.  TEACH: out of place -- the five fields are only
+// read, every computed cell stores all four results to o (the "unchanged, so not stored" short cuts need the in-place form), no precl.
+template <bool TEACH>
 __device__ __forceinline__ void kessler_chunks_body(const KesP &p, double *__restrict__ rho_v, double *__restrict__ rho_c,
                                                     double *__restrict__ rho_r, const double *__restrict__ rho_d,
                                                     double *__restrict__ temp, double *__restrict__ precl,
-                                                    const double *__restrict__ flux_top, int chunk) {
+                                                    const double *__restrict__ flux_top, int chunk, const KesOut &o) {
 #pragma clang fp contract(off)
   long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= p.ncol) return;
@@ -291,57 +329,67 @@ __device__ __forceinline__ void kessler_chunks_body(const KesP &p, double *__res
     const double ird = rcp64(rd);
     double qv = rv_in * ird, qc = rc_in * ird, qr = rr_in * ird;         // :138-140
     double T = T_in;                                                     // (temperature form: see kessler_cell)
-    double velqr = kessler_velqr(rr_in, rd, ird, rho0);                  // :260 (as k_kessler_prep saw it)
+    double velqr = kessler_velqr(rr_in, rd, ird, rho0);                  // :260 (as k_kessler_prep_t saw it)
     flux_above = kessler_cell(p, k, rd, rho0, pp0, dt0, flux_above, T, qv, qc, qr, velqr, precl_acc);
     // :154-161 [K5].  (Round 5: cloud / rain that came in as zero and go out as zero over a whole wavefront -- most of the domain -- are not
     //  stored again: 16 of the 72 bytes a cell costs.  Wave-uniform, so that no cache line is written in part.)
     const double rc_out = qc * rd, rr_out = qr * rd;
-    rho_v[idx] = qv * rd;
-    if (__any(rc_in != 0.0 || rc_out != 0.0)) rho_c[idx] = rc_out;
-    if (__any(rr_in != 0.0 || rr_out != 0.0)) rho_r[idx] = rr_out;
-    if (__any(T != T_in)) temp[idx] = T;                                 // (no phase change anywhere in the wavefront: the temperature comes back bit for bit)
+    (TEACH ? o.v : rho_v)[idx] = qv * rd;
+    if (TEACH || __any(rc_in != 0.0 || rc_out != 0.0)) (TEACH ? o.c : rho_c)[idx] = rc_out;
+    if (TEACH || __any(rr_in != 0.0 || rr_out != 0.0)) (TEACH ? o.r : rho_r)[idx] = rr_out;
+    if (TEACH || __any(T != T_in)) (TEACH ? o.T : temp)[idx] = T;        // (no phase change anywhere in the wavefront: the temperature comes back bit for bit)
     rd = rd_n; T_in = T_n; rv_in = rv_n; rc_in = rc_n; rr_in = rr_n;
   }
-  if (c == 0) precl[i] = precl_acc / 1.0;                                // :332-334
+  if (!TEACH && c == 0) precl[i] = precl_acc / 1.0;                      // :332-334
 }
 
-// rainsplit > 1: thread = column, all sub-cycles, top-down.
+// rainsplit > 1: thread = column, all sub-cycles, top-down.  TEACH: between the sub-cycles the member's own output elements hold T, qv,
+// qc, qr (they are overwritten with the results in the last one) and ws (nz, ncol) holds the fall speed alone; no precl.
+// b / ci: the in-place form indexes uniform bases with k * ncol + i; the teacher's kernel needs its nine per-column bases (field + i) in
+// vector registers and indexes them with k * ncol -- nine uniform bases beside kessler_cell's constants do not fit its scalar file (142
+// VGPRs and 3 waves per SIMD instead of 124 and 4).  One body writes base + b and k * ncol + ci, and one of the two is the constant 0.
+template <bool TEACH>
 __device__ __forceinline__ void kessler_column_body(const KesP &p, int rainsplit, double *__restrict__ rho_v, double *__restrict__ rho_c,
                                                     double *__restrict__ rho_r, const double *__restrict__ rho_d,
-                                                    double *__restrict__ temp, double *__restrict__ precl, double *__restrict__ ws) {
+                                                    double *__restrict__ temp, double *__restrict__ precl, double *__restrict__ ws,
+                                                    const KesOut &o) {
 #pragma clang fp contract(off)
   long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= p.ncol) return;
   const long long n = (long long)p.nz * p.ncol;
-  double *w_velqr = ws, *w_theta = ws + n, *w_qv = ws + 2 * n, *w_qc = ws + 3 * n, *w_qr = ws + 4 * n;
+  const long long b = TEACH ? i : 0, ci = TEACH ? 0 : i;
+  double *w_velqr = ws + b, *w_theta = TEACH ? o.T + b : ws + n, *w_qv = TEACH ? o.v + b : ws + 2 * n, *w_qc = TEACH ? o.c + b : ws + 3 * n,
+         *w_qr = TEACH ? o.r + b : ws + 4 * n;
   const double dt0 = p.dt / (double)rainsplit;                // :280
   const int nz = p.nz;
-  const double rho0 = rho_d[i];
+  const double *c_d = rho_d + b, *c_T = temp + b, *c_v = rho_v + b, *c_c = rho_c + b, *c_r = rho_r + b;
+  double *o_T = TEACH ? w_theta : temp, *o_v = TEACH ? w_qv : rho_v, *o_c = TEACH ? w_qc : rho_c, *o_r = TEACH ? w_qr : rho_r;
+  const double rho0 = c_d[ci];
   double precl_acc = 0;                                       // :270-272
   for (int nt = 0; nt < rainsplit; nt++) {
     const bool first = (nt == 0), lastp = (nt == rainsplit - 1);
     double flux_above = 0;                                    // r(k+1)*qr(k+1)*velqr(k+1), pre-update
     for (int k = nz - 1; k >= 0; k--) {
-      long long idx = (long long)k * p.ncol + i;
-      double rd = rho_d[idx];
-      double T_in = temp[idx], rv_in = rho_v[idx];
+      long long idx = (long long)k * p.ncol + ci;
+      double rd = c_d[idx];
+      double T_in = c_T[idx], rv_in = c_v[idx];
       double pressure = p.R_d * rd * T_in + p.R_v * rv_in * T_in;        // :141
       const double pp0 = pressure / p.p0;                                // (of the call's input state, like the reference's pk, :141-142)
       double T, qv, qc, qr, velqr;
       if (first) {
         const double ird = rcp64(rd);
-        qv = rv_in * ird; qc = rho_c[idx] * ird; qr = rho_r[idx] * ird;   // :138-140
+        qv = rv_in * ird; qc = c_c[idx] * ird; qr = c_r[idx] * ird;       // :138-140
         T = T_in;                                                         // (temperature form: see kessler_cell)
-        velqr = kessler_velqr(rho_r[idx], rd, ird, rho0);                 // :260 (as k_kessler_prep saw it)
+        velqr = kessler_velqr(c_r[idx], rd, ird, rho0);                   // :260 (as k_kessler_prep_t saw it)
       } else { T = w_theta[idx]; qv = w_qv[idx]; qc = w_qc[idx]; qr = w_qr[idx]; velqr = w_velqr[idx]; }
       flux_above = kessler_cell(p, k, rd, rho0, pp0, dt0, flux_above, T, qv, qc, qr, velqr, precl_acc);
       if (lastp) {                                                        // :154-161 [K5]
-        rho_v[idx] = qv * rd; rho_c[idx] = qc * rd; rho_r[idx] = qr * rd;
-        temp[idx] = T;
+        o_v[idx] = qv * rd; o_c[idx] = qc * rd; o_r[idx] = qr * rd;
+        o_T[idx] = T;
       } else { w_theta[idx] = T; w_qv[idx] = qv; w_qc[idx] = qc; w_qr[idx] = qr; w_velqr[idx] = velqr; }
     }
   }
-  precl[i] = precl_acc / (double)rainsplit;                               // :332-334
+  if (!TEACH) precl[i] = precl_acc / (double)rainsplit;                   // :332-334
 }
 
 // K4 + K5 in ONE launch (round 5; two launches before, one of them a no-op): the grid of the z-chunk sweep; with rainsplit == 1 every
@@ -362,8 +410,8 @@ void k_kessler_sweep(KesP p, double *__restrict__ rho_v, double *__restrict__ rh
 #pragma clang fp contract(off)
   const double dt_max = __longlong_as_double((long long)*dtmax_bits);
   const int rainsplit = (int)ceil(p.dt / dt_max);             // :279
-  if (rainsplit == 1) kessler_chunks_body(p, rho_v, rho_c, rho_r, rho_d, temp, precl, flux_top, chunk);
-  else if (blockIdx.y == 0) kessler_column_body(p, rainsplit, rho_v, rho_c, rho_r, rho_d, temp, precl, ws);
+  if (rainsplit == 1) kessler_chunks_body<false>(p, rho_v, rho_c, rho_r, rho_d, temp, precl, flux_top, chunk, KesOut{});
+  else if (blockIdx.y == 0) kessler_column_body<false>(p, rainsplit, rho_v, rho_c, rho_r, rho_d, temp, precl, ws, KesOut{});
 }
 
 __global__ __launch_bounds__(256) void k_kessler_chunks(KesP p, double *__restrict__ rho_v, double *__restrict__ rho_c, double *__restrict__ rho_r,
@@ -371,7 +419,7 @@ __global__ __launch_bounds__(256) void k_kessler_chunks(KesP p, double *__restri
                                                         const unsigned long long *dtmax_bits, const double *__restrict__ flux_top, int chunk) {
   const double dt_max = __longlong_as_double((long long)*dtmax_bits);
   if ((int)ceil(p.dt / dt_max) != 1) return;                  // k_kessler_column handles rainsplit > 1
-  kessler_chunks_body(p, rho_v, rho_c, rho_r, rho_d, temp, precl, flux_top, chunk);
+  kessler_chunks_body<false>(p, rho_v, rho_c, rho_r, rho_d, temp, precl, flux_top, chunk, KesOut{});
 }
 __global__ __launch_bounds__(256) void k_kessler_column(KesP p, double *__restrict__ rho_v, double *__restrict__ rho_c, double *__restrict__ rho_r,
                                                         const double *__restrict__ rho_d, double *__restrict__ temp, double *__restrict__ precl,
@@ -379,7 +427,7 @@ __global__ __launch_bounds__(256) void k_kessler_column(KesP p, double *__restri
   const double dt_max = __longlong_as_double((long long)*dtmax_bits);
   const int rainsplit = (int)ceil(p.dt / dt_max);             // :279
   if (rainsplit == 1) return;                                 // done by k_kessler_chunks
-  kessler_column_body(p, rainsplit, rho_v, rho_c, rho_r, rho_d, temp, precl, ws);
+  kessler_column_body<false>(p, rainsplit, rho_v, rho_c, rho_r, rho_d, temp, precl, ws, KesOut{});
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -392,11 +440,20 @@ __global__ __launch_bounds__(256) void k_kessler_column(KesP p, double *__restri
 //                 sweep takes the members whose count is 1, the column sweep the others -- both kinds may sit in one wavefront;
 //   bounded count the count comes from kessler_teacher_rainsplit (mw_kessler_teacher.h) and from nowhere else: 0 = skipped (too many
 //                 sub-cycles, or rain / a fall speed that is not finite: the CFL pass sends that member's step to 0);
-//   out of place  the five inputs are const, the four results go to arrays of their own and every computed cell stores all four (the
-//                 "unchanged, so not stored" short cuts above need the in-place form); precl is not produced.
-// kessler_cell / kessler_velqr are the ones above: a listed member gets the bits k_kessler_chunks / k_kessler_column give it alone (their
-// wave-uniform short cuts return exactly what the formulas return, so the other members in the wavefront do not matter).
-// The bodies are written beside the in-place ones, not shared by template: the in-place kernels' code stays as it is.
+//   out of place  the five inputs are const, the four results go to arrays of their own and every computed cell stores all four; precl
+//                 is not produced.
+// ONE copy of the arithmetic serves both: the CFL pass is k_kessler_prep_t<true>, the two sweeps do their member and count tests and
+// call kessler_chunks_body<true> / kessler_column_body<true>, so a listed member gets the bits k_kessler_chunks / k_kessler_column give
+// it alone (the wave-uniform short cuts of kessler_cell / kessler_velqr return exactly what the formulas return, so the other members in
+// the wavefront do not matter).  The in-place instantiations must keep the code they had before the sharing (tools/compare_device_code.py
+// against the commit before), and three choices that look arbitrary are what keeps it:
+//   * the bodies keep their __restrict__ field parameters and take the out-of-place targets as one trailing KesOut; a body with separate
+//     non-restrict `const double *in` / `double *out` parameters, the in-place kernels passing each field twice, changes the code of
+//     k_kessler_chunks, k_kessler_column and k_kessler_sweep.  The teacher's const inputs therefore come in through a const_cast;
+//   * b / ci in kessler_column_body (see there): per-column bases in vector registers for the teacher, uniform bases for the in-place form;
+//   * the CFL pass is a template KERNEL whose two teacher arguments come LAST.  The same text in a __forceinline__ function that two
+//     kernels call changes the in-place kernel (even unedited, and more so when dtc is returned or passed by reference), and arguments
+//     in the middle shift four kernarg offsets of the in-place instance.
 // ---------------------------------------------------------------------------------------------------------------
 struct KesTeach {
   int nens, cap;                    // members per cell; the most rain sub-cycles a member may ask for
@@ -410,76 +467,6 @@ __device__ __forceinline__ int kessler_teacher_count(const KesP &p, const KesTea
   return kessler_teacher_rainsplit(p.dt, kessler_teacher_word(t.words[e], p.dt), t.cap);
 }
 
-// k_kessler_prep per member.  A column that could raise its member's count is rare (see k_kessler_prep); a wavefront that holds one
-// reduces per member present, then one atomicMin per (wavefront, member).
-__global__ __launch_bounds__(256) void k_kessler_teacher_prep(KesP p, int nens, unsigned long long listed, const double *__restrict__ rho_r,
-                                                              const double *__restrict__ rho_d, double *__restrict__ flux_top, int chunk,
-                                                              int klevels, unsigned long long *words) {
-#pragma clang fp contract(off)
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int k0 = blockIdx.y * klevels, k1 = min(k0 + klevels, p.nz);
-  const int e = (i < p.ncol) ? (int)(i % nens) : -1;
-  double dtc = p.dt;
-  if (e >= 0 && ((listed >> e) & 1ull)) {
-    const double rho0 = rho_d[i];
-    const double lim = 0.8 * p.dz / p.dt;
-    const double lhs = (36.34 * 36.34) * rho0 * (1.0 + 1.0e-9), lim2 = lim * lim;
-    constexpr int KL = 5;                                     // (= klevels of the launch)
-    double rdv[KL], rrv[KL];
-    bool rain = false;
-#pragma unroll
-    for (int m = 0; m < KL; m++) { const long long idx = (long long)min(k0 + m, p.nz - 1) * p.ncol + i; rrv[m] = rho_r[idx]; }
-#pragma unroll
-    for (int m = 0; m < KL; m++) rain = rain || (rrv[m] != 0.0);
-    if (!__any(rain)) {
-#pragma unroll
-      for (int m = 0; m < KL; m++) {
-        const int k = k0 + m;
-        if (k < k1 && k > 0 && k % chunk == 0) flux_top[(long long)(k / chunk - 1) * p.ncol + i] = 0.0;
-      }
-    } else {
-#pragma unroll
-      for (int m = 0; m < KL; m++) { const long long idx = (long long)min(k0 + m, p.nz - 1) * p.ncol + i; rdv[m] = rho_d[idx]; }
-#pragma unroll
-      for (int m = 0; m < KL; m++) {
-        const int k = k0 + m;
-        if (k >= k1) break;
-        const double rd = rdv[m], rr = rrv[m];
-        const bool boundary = (k > 0 && k % chunk == 0);
-        const bool proven = (0.001 * rr <= 1.0) && (lhs < lim2 * rd);
-        if (boundary || __any(!proven)) {
-          const double ird = rcp64(rd);
-          const double qr = rr * ird, r = 0.001 * rd;
-          const double velqr = kessler_velqr(rr, rd, ird, rho0);
-          if (boundary) flux_top[(long long)(k / chunk - 1) * p.ncol + i] = r * qr * velqr;
-          // rain or a fall speed that is inf or NaN, at any level: the member cannot be labelled.  Its step is 0, which
-          // kessler_teacher_rainsplit refuses.  (Left alone such a cell looks harmless: kes_log(inf) is NaN, kes_exp's clamp drops the NaN,
-          // the fall speed comes out as 0 and the cell contributes dt.  Such rain is never "proven", so it always gets here.)
-          if (!(fabs(rr) <= 1.7976931348623157e308) || !(fabs(velqr) <= 1.7976931348623157e308)) dtc = 0.0;
-          if (k < p.nz - 1) {
-            const double zk = (k + 0.5) * p.dz, zk1 = (k + 1 + 0.5) * p.dz;
-            const double c = (velqr > 1.e-10) ? 0.8 * (zk1 - zk) / velqr : p.dt;
-            dtc = fmin(dtc, c);                               // (fmin drops a NaN c: dtc stays in [0, dt])
-          }
-        }
-      }
-    }
-  }
-  // all 64 lanes are here again.  dtc is in [0, dt] and never NaN: its bit pattern orders like the value.
-  const bool has = dtc < p.dt;
-  unsigned long long todo = __ballot(has);
-  const int lane = threadIdx.x & 63;
-  while (todo) {                                              // one round per member that has something to say
-    const int leader = __ffsll((long long)todo) - 1;
-    const int e0 = __shfl(e, leader, 64);
-    const bool mine = has && e == e0;
-    double m = mine ? dtc : p.dt;
-    for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(m, off, 64); m = fmin(m, o); }
-    if (lane == leader) atomicMin(words + e0, (unsigned long long)__double_as_longlong(m));
-    todo &= ~__ballot(mine);
-  }
-}
-
 // k_kessler_chunks for the listed members whose count is 1: thread = (column i, z chunk c), top-down.
 __global__ __launch_bounds__(256) void k_kessler_teacher_chunks(KesP p, KesTeach t, const double *__restrict__ flux_top, int chunk) {
 #pragma clang fp contract(off)
@@ -488,72 +475,23 @@ __global__ __launch_bounds__(256) void k_kessler_teacher_chunks(KesP p, KesTeach
   const int e = (int)(i % t.nens);
   if (!((t.listed >> e) & 1ull)) return;
   if (kessler_teacher_count(p, t, e) != 1) return;            // > 1: k_kessler_teacher_column; 0: skipped
-  const int c = blockIdx.y;
-  const int k_lo = c * chunk, k_hi = min(k_lo + chunk, p.nz) - 1;
-  const double dt0 = p.dt / 1.0;
-  const double rho0 = t.rho_d[i];
-  double precl_acc = 0;                                       // (kessler_cell's; not stored)
-  double flux_above = (k_hi < p.nz - 1) ? flux_top[(long long)c * p.ncol + i] : 0.0;
-  long long idx = (long long)k_hi * p.ncol + i;
-  double rd = t.rho_d[idx], T_in = t.temp[idx], rv_in = t.rho_v[idx], rc_in = t.rho_c[idx], rr_in = t.rho_r[idx];
-  for (int k = k_hi; k >= k_lo; k--) {
-    idx = (long long)k * p.ncol + i;
-    const long long nidx = (long long)max(k - 1, k_lo) * p.ncol + i;
-    const double rd_n = t.rho_d[nidx], T_n = t.temp[nidx], rv_n = t.rho_v[nidx], rc_n = t.rho_c[nidx], rr_n = t.rho_r[nidx];
-    double pressure = p.R_d * rd * T_in + p.R_v * rv_in * T_in;
-    const double pp0 = pressure * (1.0 / p.p0);
-    const double ird = rcp64(rd);
-    double qv = rv_in * ird, qc = rc_in * ird, qr = rr_in * ird;
-    double T = T_in;
-    double velqr = kessler_velqr(rr_in, rd, ird, rho0);
-    flux_above = kessler_cell(p, k, rd, rho0, pp0, dt0, flux_above, T, qv, qc, qr, velqr, precl_acc);
-    t.o_v[idx] = qv * rd; t.o_c[idx] = qc * rd; t.o_r[idx] = qr * rd;
-    t.o_temp[idx] = T;
-    rd = rd_n; T_in = T_n; rv_in = rv_n; rc_in = rc_n; rr_in = rr_n;
-  }
+  // const_cast: the TEACH instantiation never writes through its five field parameters (nor through precl)
+  kessler_chunks_body<true>(p, const_cast<double *>(t.rho_v), const_cast<double *>(t.rho_c), const_cast<double *>(t.rho_r), t.rho_d,
+                            const_cast<double *>(t.temp), nullptr, flux_top, chunk, KesOut{t.o_temp, t.o_v, t.o_c, t.o_r});
 }
 
-// k_kessler_column for the listed members whose count is 2 .. cap: thread = column, all sub-cycles, top-down.  Between the sub-cycles
-// the member's own output elements hold T, qv, qc, qr (they are overwritten with the results in the last one); the fall speed is kept
-// in w_velqr (nz, ncol).
+// k_kessler_column for the listed members whose count is 2 .. cap: thread = column, all sub-cycles, top-down; w_velqr (nz, ncol).
 __global__ __launch_bounds__(256) void k_kessler_teacher_column(KesP p, KesTeach t, double *__restrict__ w_velqr) {
 #pragma clang fp contract(off)
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= p.ncol) return;
   const int e = (int)(i % t.nens);
   if (!((t.listed >> e) & 1ull)) return;
-  const int rainsplit = kessler_teacher_count(p, t, e);       // <= cap: the only bound of the loop below
+  const int rainsplit = kessler_teacher_count(p, t, e);       // <= cap: the only bound of the body's loop
   if (rainsplit < 2) return;                                  // 1: k_kessler_teacher_chunks; 0: skipped
-  const double dt0 = p.dt / (double)rainsplit;
-  const int nz = p.nz;
-  // the column's own base pointers (in vector registers: nine uniform bases beside kessler_cell's constants do not fit the scalar file)
-  const double *c_d = t.rho_d + i, *c_T = t.temp + i, *c_v = t.rho_v + i, *c_c = t.rho_c + i, *c_r = t.rho_r + i;
-  double *o_T = t.o_temp + i, *o_v = t.o_v + i, *o_c = t.o_c + i, *o_r = t.o_r + i, *w_q = w_velqr + i;
-  const double rho0 = c_d[0];
-  double precl_acc = 0;
-  for (int nt = 0; nt < rainsplit; nt++) {
-    const bool first = (nt == 0), lastp = (nt == rainsplit - 1);
-    double flux_above = 0;
-    for (int k = nz - 1; k >= 0; k--) {
-      const long long idx = (long long)k * p.ncol;
-      const double rd = c_d[idx];
-      const double T_in = c_T[idx], rv_in = c_v[idx];
-      double pressure = p.R_d * rd * T_in + p.R_v * rv_in * T_in;
-      const double pp0 = pressure / p.p0;
-      double T, qv, qc, qr, velqr;
-      if (first) {
-        const double ird = rcp64(rd);
-        qv = rv_in * ird; qc = c_c[idx] * ird; qr = c_r[idx] * ird;
-        T = T_in;
-        velqr = kessler_velqr(c_r[idx], rd, ird, rho0);
-      } else { T = o_T[idx]; qv = o_v[idx]; qc = o_c[idx]; qr = o_r[idx]; velqr = w_q[idx]; }
-      flux_above = kessler_cell(p, k, rd, rho0, pp0, dt0, flux_above, T, qv, qc, qr, velqr, precl_acc);
-      if (lastp) {
-        o_v[idx] = qv * rd; o_c[idx] = qc * rd; o_r[idx] = qr * rd;
-        o_T[idx] = T;
-      } else { o_T[idx] = T; o_v[idx] = qv; o_c[idx] = qc; o_r[idx] = qr; w_q[idx] = velqr; }
-    }
-  }
+  // const_cast: as in k_kessler_teacher_chunks
+  kessler_column_body<true>(p, rainsplit, const_cast<double *>(t.rho_v), const_cast<double *>(t.rho_c), const_cast<double *>(t.rho_r), t.rho_d,
+                            const_cast<double *>(t.temp), nullptr, w_velqr, KesOut{t.o_temp, t.o_v, t.o_c, t.o_r});
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -721,6 +659,17 @@ static int kessler_min_words(hipStream_t st, const void *workspace, unsigned lon
   return 0;
 }
 
+static KesP kessler_params(int nz, long long ncol, double dz, double dt) {
+  KesP p; p.nz = nz; p.ncol = ncol; p.dz = dz; p.dt = dt; p.R_d = 287.; p.cp_d = 1003.; p.R_v = 461.; p.p0 = 1.e5;
+  return p;
+}
+// z chunks of the rainsplit == 1 path: enough (column, chunk) threads to fill the chip, at least 4 levels per chunk
+static int kessler_chunk(int nz, long long columns) {
+  int chunk = nz;
+  for (int c : {25, 20, 16, 12, 10, 8, 5, 4}) if (c < nz) { chunk = c; if (((columns + 63) / 64) * ((nz + c - 1) / c) >= 16384) break; }
+  return chunk;
+}
+
 int mw_kessler_set_strict(int strict) { g_kessler_strict = strict ? 1 : 0; return 0; }
 
 int mw_kessler_time_step(int nz, long long ncol, double dz, double dt, double *rho_v, double *rho_c, double *rho_r,
@@ -730,7 +679,7 @@ int mw_kessler_time_step(int nz, long long ncol, double dz, double dt, double *r
   if (!rho_v || !rho_c || !rho_r || !rho_d || !temp || !precl || !workspace) MW_FAIL("kessler: null pointer");
   if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
   hipStream_t st = (hipStream_t)stream;
-  KesP p; p.nz = nz; p.ncol = ncol; p.dz = dz; p.dt = dt; p.R_d = 287.; p.cp_d = 1003.; p.R_v = 461.; p.p0 = 1.e5;
+  const KesP p = kessler_params(nz, ncol, dz, dt);
   unsigned long long *bits = nullptr, *next_bits = nullptr;
   if (kessler_min_words(st, workspace, &bits, &next_bits)) return 1;
   double *ws = (double *)workspace + 16;
@@ -740,33 +689,23 @@ int mw_kessler_time_step(int nz, long long ncol, double dz, double dt, double *r
     if (kessler_min_words(st, workspace, nullptr, nullptr, true)) return 1;
     hipLaunchKernelGGL(k_kessler_strict_column, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, st, p, rho_v, rho_c, rho_r, rho_d, temp,
                        precl, bits, ws); MW_LAUNCH_CHECK();
-    if (rainsplit_out) {
-      unsigned long long hb = 0;
-      MW_HIP(hipMemcpyAsync(&hb, bits, 8, hipMemcpyDeviceToHost, st));
-      MW_HIP(hipStreamSynchronize(st));
-      double dt_max; memcpy(&dt_max, &hb, 8);
-      *rainsplit_out = (int)std::ceil(dt / dt_max);
-    }
-    return 0;
-  }
-  // z chunks of the rainsplit == 1 path: enough (column, chunk) threads to fill the chip, at least 4 levels per chunk
-  int chunk = nz;
-  for (int c : {25, 20, 16, 12, 10, 8, 5, 4}) if (c < nz) { chunk = c; if (((ncol + 63) / 64) * ((nz + c - 1) / c) >= 16384) break; }
-  const int nchunks = (nz + chunk - 1) / chunk;
-  double *flux_top = ws + 5ll * nz * ncol;                    // (nchunks-1, ncol)
-  const int klevels = 5;                                        // levels per thread of the CFL pass (k_kessler_prep: KL)
-  hipLaunchKernelGGL(k_kessler_prep, dim3((unsigned)((ncol + 255) / 256), (unsigned)((nz + klevels - 1) / klevels)), dim3(256), 0, st, p,
-                     rho_r, rho_d, flux_top, chunk, klevels, bits, next_bits); MW_LAUNCH_CHECK();
-  if (kessler_min_words(st, workspace, nullptr, nullptr, true)) return 1;
+  } else {
+    const int chunk = kessler_chunk(nz, ncol), nchunks = (nz + chunk - 1) / chunk;
+    double *flux_top = ws + 5ll * nz * ncol;                  // (nchunks-1, ncol)
+    const int klevels = 5;                                      // levels per thread of the CFL pass (k_kessler_prep_t: KL)
+    hipLaunchKernelGGL(k_kessler_prep_t<false>, dim3((unsigned)((ncol + 255) / 256), (unsigned)((nz + klevels - 1) / klevels)), dim3(256), 0, st, p,
+                       rho_r, rho_d, flux_top, chunk, klevels, bits, next_bits, 0, 0ull); MW_LAUNCH_CHECK();
+    if (kessler_min_words(st, workspace, nullptr, nullptr, true)) return 1;
 #if MW_KES_SWEEP
-  hipLaunchKernelGGL(k_kessler_sweep, dim3((unsigned)((ncol + 255) / 256), (unsigned)nchunks), dim3(256), 0, st, p, rho_v, rho_c, rho_r,
-                     rho_d, temp, precl, bits, ws, flux_top, chunk); MW_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_kessler_sweep, dim3((unsigned)((ncol + 255) / 256), (unsigned)nchunks), dim3(256), 0, st, p, rho_v, rho_c, rho_r,
+                       rho_d, temp, precl, bits, ws, flux_top, chunk); MW_LAUNCH_CHECK();
 #else
-  hipLaunchKernelGGL(k_kessler_chunks, dim3((unsigned)((ncol + 255) / 256), (unsigned)nchunks), dim3(256), 0, st, p, rho_v, rho_c, rho_r,
-                     rho_d, temp, precl, bits, flux_top, chunk); MW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_kessler_column, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, st, p, rho_v, rho_c, rho_r, rho_d, temp,
-                     precl, bits, ws); MW_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_kessler_chunks, dim3((unsigned)((ncol + 255) / 256), (unsigned)nchunks), dim3(256), 0, st, p, rho_v, rho_c, rho_r,
+                       rho_d, temp, precl, bits, flux_top, chunk); MW_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_kessler_column, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, st, p, rho_v, rho_c, rho_r, rho_d, temp,
+                       precl, bits, ws); MW_LAUNCH_CHECK();
 #endif
+  }
   if (rainsplit_out) {
     unsigned long long hb = 0;
     MW_HIP(hipMemcpyAsync(&hb, bits, 8, hipMemcpyDeviceToHost, st));
@@ -809,7 +748,7 @@ int mw_kessler_members_teacher(int nz, long long ncol, int nens, int nm, const i
   if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
   hipStream_t st = (hipStream_t)stream;
   const long long NC = ncol * nens;                           // the kernels' columns: col * nens + member
-  KesP p; p.nz = nz; p.ncol = NC; p.dz = dz; p.dt = dt; p.R_d = 287.; p.cp_d = 1003.; p.R_v = 461.; p.p0 = 1.e5;
+  const KesP p = kessler_params(nz, NC, dz, dt);
   unsigned long long *words = (unsigned long long *)workspace;
   double *w_velqr = (double *)((char *)workspace + 512), *flux_top = w_velqr + (long long)nz * NC;
   KesTeach t;
@@ -818,13 +757,11 @@ int mw_kessler_members_teacher(int nz, long long ncol, int nens, int nm, const i
   t.o_temp = out4[0]; t.o_v = out4[1]; t.o_c = out4[2]; t.o_r = out4[3];
   // every call starts its words from the all-ones pattern, in stream order (no host synchronisation, any number of calls in flight)
   MW_HIP(hipMemsetAsync(words, 0xFF, 512, st));
-  int chunk = nz;                                             // (mw_kessler_time_step's rule, on the columns of all members)
-  for (int c : {25, 20, 16, 12, 10, 8, 5, 4}) if (c < nz) { chunk = c; if (((NC + 63) / 64) * ((nz + c - 1) / c) >= 16384) break; }
-  const int nchunks = (nz + chunk - 1) / chunk;
-  const int klevels = 5;                                      // (k_kessler_teacher_prep: KL)
+  const int chunk = kessler_chunk(nz, NC), nchunks = (nz + chunk - 1) / chunk;     // (on the columns of all members)
+  const int klevels = 5;                                      // (k_kessler_prep_t: KL)
   const unsigned gx = (unsigned)((NC + 255) / 256);
-  hipLaunchKernelGGL(k_kessler_teacher_prep, dim3(gx, (unsigned)((nz + klevels - 1) / klevels)), dim3(256), 0, st, p, nens, listed, t.rho_r,
-                     t.rho_d, flux_top, chunk, klevels, words); MW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_kessler_prep_t<true>, dim3(gx, (unsigned)((nz + klevels - 1) / klevels)), dim3(256), 0, st, p, t.rho_r, t.rho_d,
+                     flux_top, chunk, klevels, words, (unsigned long long *)nullptr, nens, listed); MW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_kessler_teacher_chunks, dim3(gx, (unsigned)nchunks), dim3(256), 0, st, p, t, (const double *)flux_top, chunk); MW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_kessler_teacher_column, dim3(gx), dim3(256), 0, st, p, t, w_velqr); MW_LAUNCH_CHECK();
   if (rainsplit_out) {

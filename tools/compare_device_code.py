@@ -1,12 +1,14 @@
 """Is the gfx950 code of every kernel the same in two checkouts?  (no GPU needed; for refactors that move kernels between units)
 
-    python tools/compare_device_code.py --base <other checkout>/miniweatherml_amd/csrc [--csrc DIR] [--jobs N] [--keep DIR]
+    python tools/compare_device_code.py --base <other checkout>/miniweatherml_amd/csrc [--csrc DIR] [--jobs N] [--keep DIR] [--rename OLD=NEW ...]
 
 Compiles every *.hip of both csrc directories to device assembly (hipcc -S --offload-device-only, the flags of build.py, with
 -Rpass-analysis=kernel-resource-usage) and compares, per function of the code objects (kernels and the out-of-line device functions):
   * the instruction stream, after stripping comments, directives and the function number of block labels (.LBB<fn>_<n>);
   * the resource remark: VGPRs, AGPRs, SGPRs, spills, scratch, occupancy, LDS.
 A kernel that one side defines in more than one unit is reported (without relocatable device code it would sit in the library twice).
+--rename OLD=NEW (mangled names, may be repeated): the base's function OLD is compared with the new side's NEW -- a kernel that only
+changed its name, say into a template instance.
 Exit status 0 when everything is equal.
 """
 import os
@@ -82,7 +84,11 @@ def side(csrc, jobs, keep, tag):
 def main():
     args = sys.argv[1:]
     opt = {"--csrc": os.path.join(ROOT, "miniweatherml_amd", "csrc"), "--base": None, "--jobs": "8", "--keep": None}
+    renames = {}
     for i in range(0, len(args), 2):
+        if i + 1 < len(args) and args[i] == "--rename" and "=" in args[i + 1]:
+            old, new = args[i + 1].split("=", 1)
+            renames[old] = new; continue
         if args[i] not in opt or i + 1 >= len(args):
             sys.exit(__doc__)
         opt[args[i]] = args[i + 1]
@@ -92,6 +98,15 @@ def main():
     os.makedirs(keep, exist_ok=True)
     b_code, b_res, b_where, b_k = side(opt["--base"], int(opt["--jobs"]), keep, "base")
     n_code, n_res, n_where, n_k = side(opt["--csrc"], int(opt["--jobs"]), keep, "new")
+    for old, new in renames.items():
+        if old not in b_code:
+            sys.exit("--rename: the base has no function %s" % old)
+        print("RENAMED: %s -> %s" % (old, new))
+        for d in (b_code, b_res, b_where):
+            if old in d:
+                d[new] = d.pop(old)
+        if old in b_k:
+            b_k = (b_k - {old}) | {new}
     bad = 0
     for name in sorted(set(b_k) | set(n_k)):
         if name not in n_k or name not in b_k:
