@@ -524,6 +524,31 @@ int  mw_member_insert(long long n, int nens, int member, int nf, const double *c
  * out-of-place one and no workspace is needed.  Asynchronous on `stream`. */
 int  mw_surrogate_members_apply(mw_surrogate_bank_t b, const int *members, int nz, long long ncol, int nens, double *const *fields5,
                                 void *stream);
+/* A COMMITTEE: the mean of n_sel (1 .. MW_COMMITTEE_MAX_MODELS) distinct models sel[0 .. n_sel) of one bank, and their spread, in one pass
+ * over the state whatever n_sel is (the selected models sit in LDS once per workgroup: 16 x 2,080 B).  For every cell and output field,
+ * y_j is bit for bit what mw_mlp_forward (n_in 5) / mw_mlp_stencil_forward (n_in 9) writes for model sel[j] -- per-model scaling and the
+ * max(0, .) clamp of the three water fields included, mw_mlp_set_strict honoured -- and
+ *   out   = (((y_0 + y_1) + y_2) + ...) / (double)n_sel      fp64, in the order of sel, no contraction, a true division
+ *   range = hi - lo                                          hi / lo: the largest / smallest y_j, NaN if any y_j is
+ * so a committee of one returns its model's own bits, and a NaN in any member makes both NaN at that cell and field alone.
+ * in5: HOST array of 5 DEVICE pointers (temp, density_dry, water_vapor, cloud_liquid, precip_liquid); out4, range4 (optional: NULL):
+ * HOST arrays of 4 DEVICE pointers (temp, water_vapor, cloud_liquid, precip_liquid); all member-fastest (nz, ncol, nens), and only the
+ * elements of `member` are read and written (nens = 1, member = 0: plain contiguous fields).  out4[f] is either the matching input field
+ * (in place) or overlaps no input; range4 overlaps nothing; anything else is refused.  The stencil kernels sweep a column top-down and
+ * carry the level above raw in registers, so in place and out of place give the same bits without a workspace.  density_dry and the other
+ * members are never written.  Asynchronous on `stream`. */
+#define MW_COMMITTEE_MAX_MODELS 16
+int  mw_surrogate_committee_apply(mw_surrogate_bank_t b, int n_sel, const int *sel, int member, int nz, long long ncol, int nens,
+                                  const double *const *in5, double *const *out4, double *const *range4, void *stream);
+/* Scores a committee on contiguous (nz, ncol) DEVICE fields: with d = pred4 - truth4 and r = range4, per class (0 inactive, 1 active, as
+ * mw_surrogate_eval decides it from in5 and truth4) and field, out (DEVICE fp64 (2, 4, 7)) receives sum d, sum |d|, sum d^2, max |d|
+ * (the statistics of an mw_surrogate_eval row), sum r, sum r^2, sum r |d|.  counts: DEVICE int64 [10] = the cells per class [2], then the
+ * cells with |d| <= r per class and field (2, 4).  NaN reaches the sums and the maximum (and is never covered).  One fixed reduction
+ * order, no floating-point atomics.  workspace: DEVICE, mw_committee_score_workspace_bytes(nz, ncol) bytes (0: arguments out of range).
+ * Asynchronous on `stream`. */
+long long mw_committee_score_workspace_bytes(int nz, long long ncol);
+int  mw_committee_score(int nz, long long ncol, const double *const *in5, const double *const *truth4, const double *const *pred4,
+                        const double *const *range4, void *workspace, double *out, long long *counts, void *stream);
 /* How far every member has moved from member 0, and the member's own totals, for nf (<= MW_MAX_TRACERS) member-fastest DEVICE fp64 fields
  * of n cells x nens (<= 256) members.  fields: HOST array of nf DEVICE pointers.  out: DEVICE fp64 (nens, nf, 7) = sum d, sum |d|,
  * sum d^2, max |d| of d = member - member 0 over the cells, then sum x, min x, max x of the member itself; nonfinite: DEVICE int64

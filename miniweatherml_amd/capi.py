@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("MW_LIB_PATH") or os.path.join(_HERE, "libmw_cdna4.so"
 MW_MAX_TRACERS = 16
 MW_SURROGATE_MAX_MODELS = 256
 MW_ROLLOUT_MAX_MEMBERS = 30
+MW_COMMITTEE_MAX_MODELS = 16
 DATA_THERMAL, DATA_SUPERCELL, DATA_CITY, DATA_BUILDING = 0, 1, 2, 3
 BC_PERIODIC, BC_OPEN, BC_WALL = 0, 1, 2
 INIT_IDS = {"thermal": DATA_THERMAL, "supercell": DATA_SUPERCELL, "city": DATA_CITY, "building": DATA_BUILDING}
@@ -157,6 +158,10 @@ SYMBOLS = {
     "mw_member_extract": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
     "mw_member_insert": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
     "mw_surrogate_members_apply": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
+    "mw_surrogate_committee_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_longlong, C.c_int,
+                                              C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
+    "mw_committee_score_workspace_bytes": (C.c_longlong, [C.c_int, C.c_longlong]),
+    "mw_committee_score": (C.c_int, [C.c_int, C.c_longlong] + [C.POINTER(C.c_void_p)] * 4 + [C.c_void_p] * 4),
     "mw_member_divergence_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     "mw_member_divergence": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mw_kessler_members_teacher_workspace_bytes": (C.c_longlong, [C.c_int, C.c_longlong, C.c_int]),

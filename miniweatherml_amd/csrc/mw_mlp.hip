@@ -1302,3 +1302,421 @@ extern "C" int mw_surrogate_members_apply(mw_surrogate_bank_t b, const int *memb
   MW_LAUNCH_CHECK();
   return 0;
 }
+
+// =====================================================================================================
+// COMMITTEE of a bank's models (mw_surrogate_committee_apply): the mean of n <= MW_COMMITTEE_MAX_MODELS selected models and their spread,
+// one pass over the state whatever n is.  For a cell and an output field, y_j is what the forward kernels store for model sel[j] (per
+// model scaling, un-scaling and clip included); mean = (((y_0 + y_1) + y_2) + ...) / (double)n in the order of sel, range = hi - lo with the
+// NaN-propagating extrema of eval_max.  All n models sit in LDS once per workgroup (16 x sizeof(EvalModel) = 33,280 B) and the loop over
+// models is INSIDE the cell / level loop: a lane keeps sum, hi, lo of its (cell, field) in registers.
+//
+// k_committee_apply / k_committee_apply_stencil are k_members_apply's / k_members_apply_stencil's tiles on one member of the member-fastest
+// layout, with the models inside as in k_surrogate_eval*: what the stencil kernel carries from level to level is carried RAW and scaled per
+// model.  A tile (stencil: a level of the wave's columns) is loaded whole before it is stored and nobody else reads it, so an output may be
+// its own input field.
+// =====================================================================================================
+namespace mw {
+
+constexpr int COMMITTEE_MAX = MW_COMMITTEE_MAX_MODELS;
+struct CommitteeSel { int n; int model[COMMITTEE_MAX]; };
+struct CommitteeFields { const double *in[5]; double *out[4]; double *range[4]; };   // range[*]: all null or all set
+
+// the smaller of two values, NaN if either is (eval_max's mirror)
+__device__ __forceinline__ double eval_min(double a, double b) { return (b < a || b != b) ? b : a; }
+
+template <typename T>
+__device__ __forceinline__ void committee_load(T *sm, const T *__restrict__ bank, const CommitteeSel &S) {
+  constexpr int W = (int)(sizeof(T) / 4);
+  for (int i = threadIdx.x; i < S.n * W; i += 256) ((unsigned *)sm)[i] = ((const unsigned *)(bank + S.model[i / W]))[i % W];
+  __syncthreads();
+}
+
+template <int TILES>
+__global__ __launch_bounds__(256) void k_committee_apply(const EvalModel *__restrict__ bank, CommitteeSel S, int member, long long ncells, int nens,
+                                                         CommitteeFields F) {
+#pragma clang fp contract(off)
+  __shared__ EvalModel sm[COMMITTEE_MAX];
+  committee_load(sm, bank, S);
+  const int lane = threadIdx.x & 63;
+  const int g = lane >> 4, cidx = lane & 15;
+  const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
+  const long long nwaves = ((long long)gridDim.x * 256) >> 6;
+  const double *in_g = F.in[g], *rho_r = F.in[4];
+  double *out_g = F.out[g], *rng_g = F.range[g];
+  const double dn = (double)S.n;
+  const long long ntiles = (ncells + 15) / 16;
+  for (long long t0 = wave * TILES; t0 < ntiles; t0 += nwaves * TILES) {
+    double xin[TILES], xin4[TILES], sum[TILES], hi[TILES], lo[TILES];
+#pragma unroll
+    for (int u = 0; u < TILES; u++) {
+      const long long cell = (t0 + u) * 16 + cidx;
+      const bool ok = cell < ncells;
+      xin[u]  = ok ? in_g[cell * nens + member] : 0.0;
+      xin4[u] = (ok && g == 0) ? rho_r[cell * nens + member] : 0.0;
+      sum[u] = hi[u] = lo[u] = 0.0;
+    }
+    for (int j = 0; j < S.n; j++) {
+      const EvalModel &M = sm[j];
+      const double imin = M.in_min[g], irng = M.in_irng[g], imin4 = M.in_min[4], irng4 = M.in_irng[4];
+      const double omin = M.out_min[g], orng = M.out_rng[g];
+      const float a10 = M.a1[0][lane], a11 = M.a1[1][lane];
+      const float a20 = M.a2[0][lane], a21 = M.a2[1][lane], a22 = M.a2[2][lane];
+      const f32x4 c1 = {M.c1[g][0], M.c1[g][1], M.c1[g][2], M.c1[g][3]};
+      const f32x4 c2 = {M.c2[g], 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int u = 0; u < TILES; u++) {                                     // k_mlp's cell, expression for expression
+        float b0 = (float)((xin[u] - imin) * irng);
+        float b1 = (g == 0) ? (float)((xin4[u] - imin4) * irng4) : 0.f;
+        f32x4 d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a10, b0, c1, 0, 0, 0);
+        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a11, b1, d1, 0, 0, 0);
+        float h0 = leaky(d1[0]), h1 = leaky(d1[1]), h2 = leaky(d1[2]);
+        f32x4 d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a20, h0, c2, 0, 0, 0);
+        d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a21, h1, d2, 0, 0, 0);
+        d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a22, h2, d2, 0, 0, 0);
+        double y = (double)d2[0] * orng + omin;
+        if (g != 0) y = fmax(0.0, y);
+        sum[u] = j == 0 ? y : sum[u] + y;                                   // (the first addend as it is: a committee of one keeps its bits)
+        hi[u]  = j == 0 ? y : eval_max(hi[u], y);
+        lo[u]  = j == 0 ? y : eval_min(lo[u], y);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < TILES; u++) {
+      const long long cell = (t0 + u) * 16 + cidx;
+      if (cell < ncells) {
+        out_g[cell * nens + member] = sum[u] / dn;
+        if (rng_g) rng_g[cell * nens + member] = hi[u] - lo[u];
+      }
+    }
+  }
+}
+
+// k_members_apply_stencil's sweep (a wave owns 16 columns of the member, all nz levels, top-down) with the models inside
+template <int U>
+__global__ __launch_bounds__(256) void k_committee_apply_stencil(const EvalModel *__restrict__ bank, CommitteeSel S, int member, int nz, long long ncol,
+                                                                 int nens, CommitteeFields F) {
+#pragma clang fp contract(off)
+  __shared__ EvalModel sm[COMMITTEE_MAX];
+  committee_load(sm, bank, S);
+  const int lane = threadIdx.x & 63;
+  const int g = lane >> 4, cidx = lane & 15;
+  const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
+  const long long nwaves = ((long long)gridDim.x * 256) >> 6;
+  const double *in_g = F.in[g], *rho_r = F.in[4];
+  double *out_g = F.out[g], *rng_g = F.range[g];
+  const int fa = (g == 0) ? 5 : (g == 2) ? 6 : (g == 3) ? 7 : 1;          // k_mlp_stencil: the feature this lane's field is one level down
+  const double dn = (double)S.n;
+  const long long ntiles = (ncol + 15) / 16, lev = ncol * nens;           // lev: doubles from level k to level k + 1
+  for (long long t = wave; t < ntiles; t += nwaves) {
+    const long long col = t * 16 + cidx;
+    const bool ok = col < ncol;
+    const long long base = col * nens + member;
+    const int k_hi = nz - 1;
+    double above = 0.0, rr = 0.0;                                         // raw: the level above of this lane's field, this group's latest rho_r
+    if (ok) {
+      above = in_g[(long long)k_hi * lev + base];                         // the model top is its own level above
+      if (g == ((k_hi & 1) ^ 1)) rr = rho_r[(long long)k_hi * lev + base];
+    }
+    for (int k0 = k_hi; k0 >= 0; k0 -= U) {
+      double xin[U], xab[U], xrr[U], sum[U], hi[U], lo[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int k = k0 - u;
+        const bool lv = ok && k >= 0;
+        xin[u] = lv ? in_g[(long long)k * lev + base] : 0.0;
+        xrr[u] = (lv && g == (k & 1)) ? rho_r[(long long)k * lev + base] : 0.0;
+        sum[u] = hi[u] = lo[u] = 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int k = k0 - u;
+        if (k >= 0) {                                                     // (wave-uniform)
+          if (g == (k & 1)) rr = xrr[u];
+          xrr[u] = rr; xab[u] = above; above = xin[u];                    // level k is level k - 1's level above
+        } else { xab[u] = 0.0; }
+      }
+      for (int j = 0; j < S.n; j++) {
+        const EvalModel &M = sm[j];
+        const double imin = M.in_min[g], irng = M.in_irng[g], amin = M.in_min[fa], arng = M.in_irng[fa];
+        const double rmin = M.in_min[4], rrng = M.in_irng[4], ramin = M.in_min[8], rarng = M.in_irng[8];
+        const double omin = M.out_min[g], orng = M.out_rng[g];
+        const float a10 = M.a1[0][lane], a11 = M.a1[1][lane], a12e = M.a1[2][lane], a12o = M.a1[3][lane];
+        const float a20 = M.a2[0][lane], a21 = M.a2[1][lane], a22 = M.a2[2][lane];
+        const f32x4 c1 = {M.c1[g][0], M.c1[g][1], M.c1[g][2], M.c1[g][3]};
+        const f32x4 c2 = {M.c2[g], 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          const int k = k0 - u;
+          if (k >= 0) {                                                   // (wave-uniform)
+            const bool mine = g == (k & 1);
+            const float b0 = (float)((xin[u] - imin) * irng);
+            const float ab = (float)((xab[u] - amin) * arng);
+            const float b2 = (g < 2) ? (mine ? (float)((xrr[u] - rmin) * rrng) : (float)((xrr[u] - ramin) * rarng)) : 0.f;
+            f32x4 d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a10, b0, c1, 0, 0, 0);
+            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a11, ab, d1, 0, 0, 0);
+            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32((k & 1) ? a12o : a12e, b2, d1, 0, 0, 0);
+            const float h0 = leaky(d1[0]), h1 = leaky(d1[1]), h2 = leaky(d1[2]);
+            f32x4 d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a20, h0, c2, 0, 0, 0);
+            d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a21, h1, d2, 0, 0, 0);
+            d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a22, h2, d2, 0, 0, 0);
+            double y = (double)d2[0] * orng + omin;
+            if (g != 0) y = fmax(0.0, y);
+            sum[u] = j == 0 ? y : sum[u] + y;
+            hi[u]  = j == 0 ? y : eval_max(hi[u], y);
+            lo[u]  = j == 0 ? y : eval_min(lo[u], y);
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int k = k0 - u;
+        if (ok && k >= 0) {
+          out_g[(long long)k * lev + base] = sum[u] / dn;
+          if (rng_g) rng_g[(long long)k * lev + base] = hi[u] - lo[u];
+        }
+      }
+    }
+  }
+}
+
+// STRICT form: thread = one column of the member, swept top-down with the level above in registers (k_members_apply_strict), the models
+// inside the level loop, their weights from LDS; k_mlp_strict's / k_mlp_stencil_strict's expressions.
+template <int NIN>
+__global__ __launch_bounds__(256) void k_committee_apply_strict(const StencilRef *__restrict__ bank, CommitteeSel S, int member, int nz, long long ncol,
+                                                                int nens, CommitteeFields F) {
+#pragma clang fp contract(off)
+  __shared__ StencilRef sm[COMMITTEE_MAX];
+  committee_load(sm, bank, S);
+  const long long lev = ncol * nens;
+  const double dn = (double)S.n;
+  for (long long col = (long long)blockIdx.x * 256 + threadIdx.x; col < ncol; col += (long long)gridDim.x * 256) {
+    const long long base = col * nens + member;
+    double ab[4];                                                         // temp, rho_v, rho_c, rho_r of level min(nz - 1, k + 1) as they were
+    for (int k = nz - 1; k >= 0; k--) {
+      const long long c = (long long)k * lev + base;
+      double in[9] = {F.in[0][c], F.in[1][c], F.in[2][c], F.in[3][c], F.in[4][c], 0.0, 0.0, 0.0, 0.0};
+      if (k == nz - 1) { ab[0] = in[0]; ab[1] = in[2]; ab[2] = in[3]; ab[3] = in[4]; }
+      if (NIN == 9) { in[5] = ab[0]; in[6] = ab[1]; in[7] = ab[2]; in[8] = ab[3]; }
+      ab[0] = in[0]; ab[1] = in[2]; ab[2] = in[3]; ab[3] = in[4];
+      double sum[4], hi[4], lo[4];
+      for (int j = 0; j < S.n; j++) {
+        const StencilRef &P = sm[j];
+        float x[NIN], h[10], y[4];
+#pragma unroll
+        for (int i = 0; i < NIN; i++) x[i] = (float)((in[i] - P.in_min[i]) / P.in_rng[i]);
+#pragma unroll
+        for (int o = 0; o < 10; o++) {
+          float a = 0.f;
+#pragma unroll
+          for (int i = 0; i < NIN; i++) a += x[i] * P.W1[i * 10 + o];
+          a = a + P.b1[o];
+          h[o] = a > 0.f ? a : 0.1f * a;
+        }
+#pragma unroll
+        for (int o = 0; o < 4; o++) {
+          float a = 0.f;
+#pragma unroll
+          for (int i = 0; i < 10; i++) a += h[i] * P.W2[i * 4 + o];
+          y[o] = a + P.b2[o];
+        }
+        double p[4];
+        p[0] =           y[0] * P.out_rng[0] + P.out_min[0];
+        p[1] = fmax(0.0, y[1] * P.out_rng[1] + P.out_min[1]);
+        p[2] = fmax(0.0, y[2] * P.out_rng[2] + P.out_min[2]);
+        p[3] = fmax(0.0, y[3] * P.out_rng[3] + P.out_min[3]);
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+          sum[v] = j == 0 ? p[v] : sum[v] + p[v];
+          hi[v]  = j == 0 ? p[v] : eval_max(hi[v], p[v]);
+          lo[v]  = j == 0 ? p[v] : eval_min(lo[v], p[v]);
+        }
+      }
+#pragma unroll
+      for (int v = 0; v < 4; v++) {
+        F.out[v][c] = sum[v] / dn;
+        if (F.range[v]) F.range[v][c] = hi[v] - lo[v];
+      }
+    }
+  }
+}
+
+// ---- scoring a committee (mw_committee_score): d = pred - truth and r = range per class and field ----
+constexpr int SCORE_STATS = 7;                       // sum d, sum |d|, sum d^2, max |d|, sum r, sum r^2, sum r |d|
+constexpr int SCORE_ROW = 2 * 4 * SCORE_STATS;       // doubles of a result: [class][field][statistic]
+constexpr int SCORE_CNT = 9;                         // int64 per block: active cells, then covered [class][field]
+constexpr int SCORE_MAX_BLOCKS = 1024;
+struct ScoreFields { const double *in[5], *truth[4], *pred[4], *range[4]; };
+
+__global__ __launch_bounds__(256) void k_committee_score(long long n, ScoreFields F, double *__restrict__ partial, long long *__restrict__ cpartial) {
+#pragma clang fp contract(off)
+  __shared__ double red[4][SCORE_ROW];
+  __shared__ long long cred[4][SCORE_CNT];
+  double acc[2][4][SCORE_STATS];
+  long long cnt[SCORE_CNT];
+#pragma unroll
+  for (int i = 0; i < SCORE_ROW; i++) (&acc[0][0][0])[i] = 0.0;
+#pragma unroll
+  for (int i = 0; i < SCORE_CNT; i++) cnt[i] = 0;
+  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < n; c += (long long)gridDim.x * 256) {
+    const double before[4] = {F.in[0][c], F.in[2][c], F.in[3][c], F.in[4][c]};
+    double tr[4];
+    bool act = false;
+#pragma unroll
+    for (int v = 0; v < 4; v++) { tr[v] = F.truth[v][c]; act = act || fabs(tr[v] - before[v]) > 1.e-10; }      // gather_micro_statistics.h:61-74
+    cnt[0] += act ? 1 : 0;
+#pragma unroll
+    for (int v = 0; v < 4; v++) {
+      const double d = F.pred[v][c] - tr[v], r = F.range[v][c];
+      const bool cov = fabs(d) <= r;
+#pragma unroll
+      for (int cl = 0; cl < 2; cl++) {                                     // adding +0.0 to the other class leaves its bits alone (eval_add)
+        const bool in = cl == (act ? 1 : 0);
+        const double dc = in ? d : 0.0, rc = in ? r : 0.0, ad = fabs(dc);
+        double *a = acc[cl][v];
+        a[0] += dc; a[1] += ad; a[2] += dc * dc; a[3] = eval_max(a[3], ad);
+        a[4] += rc; a[5] += rc * rc; a[6] += rc * ad;
+        cnt[1 + cl * 4 + v] += (in && cov) ? 1 : 0;
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < SCORE_ROW; i++) {
+    const double q = eval_lane_tree<64>((&acc[0][0][0])[i], i % SCORE_STATS == 3);
+    if (lane == 0) red[wv][i] = q;
+  }
+#pragma unroll
+  for (int i = 0; i < SCORE_CNT; i++) {
+    long long q = cnt[i];
+    for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off, 64);
+    if (lane == 0) cred[wv][i] = q;
+  }
+  __syncthreads();
+  if (threadIdx.x < SCORE_ROW) {
+    const int i = threadIdx.x;
+    double q = red[0][i];
+#pragma unroll
+    for (int w = 1; w < 4; w++) q = i % SCORE_STATS == 3 ? eval_max(q, red[w][i]) : q + red[w][i];
+    partial[(long long)blockIdx.x * SCORE_ROW + i] = q;
+  }
+  if (threadIdx.x >= 64 && threadIdx.x < 64 + SCORE_CNT) {
+    const int i = threadIdx.x - 64;
+    cpartial[(long long)blockIdx.x * SCORE_CNT + i] = cred[0][i] + cred[1][i] + cred[2][i] + cred[3][i];
+  }
+}
+
+// the blocks' partial rows in block order (k_surrogate_eval_final's scheme)
+__global__ __launch_bounds__(64) void k_committee_score_final(int nblocks, long long n, const double *__restrict__ partial,
+                                                              const long long *__restrict__ cpartial, double *__restrict__ out,
+                                                              long long *__restrict__ counts) {
+  const int e = threadIdx.x;
+  if (e < SCORE_ROW) {
+    double q = 0.0;
+    for (int b = 0; b < nblocks; b++) {
+      const double o = partial[(long long)b * SCORE_ROW + e];
+      q = e % SCORE_STATS == 3 ? eval_max(q, o) : q + o;
+    }
+    out[e] = q;
+  }
+  if (e < SCORE_CNT) {
+    long long a = 0;
+    for (int b = 0; b < nblocks; b++) a += cpartial[(long long)b * SCORE_CNT + e];
+    if (e == 0) { counts[0] = n - a; counts[1] = a; }
+    else counts[1 + e] = a;
+  }
+}
+
+} // namespace mw
+
+static bool committee_overlap(const double *a, const double *b, long long n) { return a < b + n && b < a + n; }
+
+extern "C" int mw_surrogate_committee_apply(mw_surrogate_bank_t b, int n_sel, const int *sel, int member, int nz, long long ncol, int nens,
+                                            const double *const *in5, double *const *out4, double *const *range4, void *stream) {
+  if (!b || !sel || !in5 || !out4) MW_FAIL("surrogate_committee_apply: null pointer");
+  if (n_sel < 1 || n_sel > MW_COMMITTEE_MAX_MODELS) MW_FAIL("surrogate_committee_apply: a committee has 1 to " + std::to_string(MW_COMMITTEE_MAX_MODELS) +
+                                                            " models, got " + std::to_string(n_sel));
+  if (nz < 1 || ncol < 1 || nens < 1) MW_FAIL("surrogate_committee_apply: nz, ncol and nens must be >= 1");
+  if (member < 0 || member >= nens) MW_FAIL("surrogate_committee_apply: member " + std::to_string(member) + " is outside [0, " + std::to_string(nens) + ")");
+  CommitteeSel S;
+  memset(&S, 0, sizeof(S));
+  S.n = n_sel;
+  for (int j = 0; j < n_sel; j++) {
+    if (sel[j] < 0 || sel[j] >= b->models) MW_FAIL("surrogate_committee_apply: model " + std::to_string(sel[j]) + " is outside the bank's [0, " +
+                                                   std::to_string(b->models) + ")");
+    for (int i = 0; i < j; i++) if (sel[i] == sel[j]) MW_FAIL("surrogate_committee_apply: model " + std::to_string(sel[j]) + " is given twice");
+    S.model[j] = sel[j];
+  }
+  if ((double)nz * (double)ncol * (double)nens > 9.0e18) MW_FAIL("surrogate_committee_apply: the fields are too large");
+  const long long total = (long long)nz * ncol * nens;
+  CommitteeFields F;
+  for (int i = 0; i < 5; i++) { if (!in5[i]) MW_FAIL("surrogate_committee_apply: null field"); F.in[i] = in5[i]; }
+  for (int v = 0; v < 4; v++) { if (!out4[v]) MW_FAIL("surrogate_committee_apply: null field"); F.out[v] = out4[v]; F.range[v] = nullptr; }
+  if (range4) for (int v = 0; v < 4; v++) { if (!range4[v]) MW_FAIL("surrogate_committee_apply: null field"); F.range[v] = range4[v]; }
+  // an output is its own input field (in place) or overlaps no input; outputs and ranges overlap nothing else
+  const int own[4] = {0, 2, 3, 4};
+  for (int v = 0; v < 4; v++) {
+    for (int i = 0; i < 5; i++) {
+      if (!(F.out[v] == F.in[i] && i == own[v]) && committee_overlap(F.out[v], F.in[i], total)) MW_FAIL("surrogate_committee_apply: an output must be its own input field (in place) or overlap no input");
+      if (F.range[v] && committee_overlap(F.range[v], F.in[i], total)) MW_FAIL("surrogate_committee_apply: a range field must not overlap an input");
+    }
+    for (int w = 0; w < 4; w++) {
+      if (w != v && committee_overlap(F.out[v], F.out[w], total)) MW_FAIL("surrogate_committee_apply: the outputs must not overlap each other");
+      if (F.range[v] && committee_overlap(F.range[v], F.out[w], total)) MW_FAIL("surrogate_committee_apply: a range field must not overlap an output");
+      if (F.range[v] && w != v && committee_overlap(F.range[v], F.range[w], total)) MW_FAIL("surrogate_committee_apply: the range fields must not overlap each other");
+    }
+  }
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  hipStream_t st = (hipStream_t)stream;
+  const long long ncells = (long long)nz * ncol;
+  if (g_mlp_strict) {
+    const long long blocks = std::max<long long>(1, std::min<long long>((ncol + 255) / 256, APPLY_MAX_BLOCKS));
+    if (b->n_in == 5) hipLaunchKernelGGL(k_committee_apply_strict<5>, dim3((unsigned)blocks), dim3(256), 0, st, b->refs, S, member, nz, ncol, nens, F);
+    else              hipLaunchKernelGGL(k_committee_apply_strict<9>, dim3((unsigned)blocks), dim3(256), 0, st, b->refs, S, member, nz, ncol, nens, F);
+    MW_LAUNCH_CHECK();
+    return 0;
+  }
+  constexpr int TILES = 4, U = 4;
+  if (b->n_in == 5) {
+    const long long groups = ((ncells + 15) / 16 + TILES - 1) / TILES;
+    const long long blocks = std::max<long long>(1, std::min<long long>((groups + 3) / 4, APPLY_MAX_BLOCKS));
+    hipLaunchKernelGGL(k_committee_apply<TILES>, dim3((unsigned)blocks), dim3(256), 0, st, b->images, S, member, ncells, nens, F);
+  } else {
+    const long long tiles = (ncol + 15) / 16;
+    const long long blocks = std::max<long long>(1, std::min<long long>((tiles + 3) / 4, APPLY_MAX_BLOCKS));
+    hipLaunchKernelGGL(k_committee_apply_stencil<U>, dim3((unsigned)blocks), dim3(256), 0, st, b->images, S, member, nz, ncol, nens, F);
+  }
+  MW_LAUNCH_CHECK();
+  return 0;
+}
+
+static long long committee_score_blocks(int nz, long long ncol) {
+  if (nz < 1 || ncol < 1 || (double)nz * (double)ncol > 9.0e18) return 0;
+  return std::max<long long>(1, std::min<long long>(((long long)nz * ncol + 255) / 256, SCORE_MAX_BLOCKS));
+}
+
+extern "C" long long mw_committee_score_workspace_bytes(int nz, long long ncol) {
+  return committee_score_blocks(nz, ncol) * (long long)(SCORE_ROW * sizeof(double) + SCORE_CNT * sizeof(long long));
+}
+
+extern "C" int mw_committee_score(int nz, long long ncol, const double *const *in5, const double *const *truth4, const double *const *pred4,
+                                  const double *const *range4, void *workspace, double *out, long long *counts, void *stream) {
+  if (!in5 || !truth4 || !pred4 || !range4 || !workspace || !out || !counts) MW_FAIL("committee_score: null pointer");
+  const long long blocks = committee_score_blocks(nz, ncol);
+  if (blocks < 1) MW_FAIL("committee_score: nz and ncol must be >= 1");
+  ScoreFields F;
+  for (int i = 0; i < 5; i++) { if (!in5[i]) MW_FAIL("committee_score: null field"); F.in[i] = in5[i]; }
+  for (int v = 0; v < 4; v++) {
+    if (!truth4[v] || !pred4[v] || !range4[v]) MW_FAIL("committee_score: null field");
+    F.truth[v] = truth4[v]; F.pred[v] = pred4[v]; F.range[v] = range4[v];
+  }
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  hipStream_t st = (hipStream_t)stream;
+  const long long n = (long long)nz * ncol;
+  double *partial = (double *)workspace;
+  long long *cpartial = (long long *)(partial + blocks * SCORE_ROW);
+  hipLaunchKernelGGL(k_committee_score, dim3((unsigned)blocks), dim3(256), 0, st, n, F, partial, cpartial);
+  MW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_committee_score_final, dim3(1), dim3(64), 0, st, (int)blocks, n, (const double *)partial, (const long long *)cpartial, out, counts);
+  MW_LAUNCH_CHECK();
+  return 0;
+}

@@ -36,6 +36,12 @@ surrogate_rollout.json.  One rank only.
 adds data aggregation to the rollout (modules.RolloutHarvester): every interval-th step (default eval_interval) Kessler is asked what it
 would have done to each listed model member's OWN state (default: all models), and samples of that go to rollout_samples_<name>.nc in the
 working directory -- DataGenerator's format, so `surrogate_train --init DIR` continues a model on the old and the new files together.
+    surrogate_committees:
+      - {name: mean3, members: [seed0, seed1, seed2]}      # 1 .. 16 models of the list above, all of one width
+makes committees of the listed models (committee_config; modules.SurrogateBank.committee_apply: the mean of the members' outputs in the
+listed order, and their range).  rollout_surrogates rolls each committee out as one more member after the models (nens counts them; a
+committee cannot be harvested), evaluate_surrogates scores each one (modules.CommitteeEvaluator; `committees` in the JSON and the table),
+and inference_ponni runs the committee instead of one network when the YAML names exactly one and no keras_weights_* key.
 """
 import argparse
 import os
@@ -68,7 +74,7 @@ def load_config(path):
         if key in cfg:
             out[key] = str(cfg[key])
     out["_dir"] = os.path.dirname(os.path.abspath(path))
-    for key in ("surrogate_models", "eval_interval", "persistence_member", "harvest"):    # read by surrogate_config / rollout_config / harvest_config alone
+    for key in ("surrogate_models", "eval_interval", "persistence_member", "harvest", "surrogate_committees"):    # read by surrogate_config / rollout_config / harvest_config / committee_config alone
         if key in cfg:
             out[key] = cfg[key]
     return out
@@ -85,22 +91,74 @@ def surrogate_config(cfg):
     return _surrogate_models(cfg["surrogate_models"], cfg["_dir"]), interval
 
 
+COMMITTEE_KEYS = ("name", "members")
+
+
+def _model_width(m):
+    """5 (single cell) or 9 (stencil): the rows of a checked surrogate model's input scaling table (load_surrogate_weights' rule)."""
+    with open(m["nn_input_scaling"]) as f:
+        return sum(1 for ln in f if ln.split("#")[0].strip())
+
+
+def committee_config(cfg):
+    """The checked `surrogate_committees:` list of a loaded configuration, [] without the key: entries {name, members: [model names]} --
+    1 .. 16 distinct models of `surrogate_models`, all of one width; committee names unique and no model's name, 'kessler' or
+    'persistence'.  Returns [{"name", "members"}] in the YAML's order."""
+    from . import capi
+    if "surrogate_committees" not in cfg:
+        return []
+    models, _ = surrogate_config(cfg)
+    names = [m["name"] for m in models]
+    entries = cfg["surrogate_committees"]
+    if not isinstance(entries, list) or not entries:
+        raise ValueError("ERROR: surrogate_committees must be a non-empty list")
+    out = []
+    for e in entries:
+        if not isinstance(e, dict) or "name" not in e or "members" not in e:
+            raise KeyError("ERROR: every entry of surrogate_committees needs a 'name' and 'members'")
+        unknown = sorted(set(e) - set(COMMITTEE_KEYS))
+        if unknown:
+            raise ValueError("ERROR: unknown key(s) %s in a surrogate_committees entry (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(COMMITTEE_KEYS)))
+        cname = str(e["name"])
+        if not isinstance(e["members"], list) or not e["members"]:
+            raise ValueError("ERROR: committee %r: members must be a non-empty list of model names" % cname)
+        members = [str(n) for n in e["members"]]
+        for n in members:
+            if n not in names:
+                raise ValueError("ERROR: committee %r names %r, which is no surrogate model (%s)" % (cname, n, ", ".join(names)))
+        if len(set(members)) != len(members):
+            raise ValueError("ERROR: committee %r names a model twice" % cname)
+        if len(members) > capi.MW_COMMITTEE_MAX_MODELS:
+            raise ValueError("ERROR: committee %r has %d models, a committee holds at most %d" % (cname, len(members), capi.MW_COMMITTEE_MAX_MODELS))
+        if len({_model_width(models[names.index(n)]) for n in members}) != 1:
+            raise ValueError("ERROR: committee %r mixes single-cell and stencil models: a committee has one width" % cname)
+        if cname in names or cname in ("kessler", "persistence"):
+            raise ValueError("ERROR: committee name %r collides with a surrogate model, 'kessler' or 'persistence'" % cname)
+        out.append({"name": cname, "members": members})
+    if len({c["name"] for c in out}) != len(out):
+        raise ValueError("ERROR: the names of surrogate_committees must be unique")
+    return out
+
+
 def rollout_config(cfg):
     """(models, eval_interval, persistence, nens) of a loaded configuration for rollout_surrogates: surrogate_config's list and interval,
-    `persistence_member` (default true) and the member count they imply -- Kessler, one member per model, persistence.  A `nens` in the
-    YAML that disagrees is an error, and so is a list longer than the dycore steps members in one call."""
+    `persistence_member` (default true) and the member count they imply -- Kessler, one member per model, one per committee of
+    `surrogate_committees` (committee_config), persistence.  A `nens` in the YAML that disagrees is an error, and so are more members than
+    the dycore steps in one call."""
     from . import capi
     models, interval = surrogate_config(cfg)
     persistence = cfg.get("persistence_member", True)
     if not isinstance(persistence, bool):
         raise ValueError("ERROR: persistence_member must be true or false")
-    nens = 1 + len(models) + (1 if persistence else 0)
+    ncom = len(committee_config(cfg))
+    com = (", %d surrogate_committees" % ncom) if ncom else ""
+    nens = 1 + len(models) + ncom + (1 if persistence else 0)
     if nens > capi.MW_ROLLOUT_MAX_MEMBERS:
-        raise ValueError("ERROR: %d surrogate_models%s beside Kessler are %d ensemble members, the dycore steps at most %d"
-                         % (len(models), " and the persistence member" if persistence else "", nens, capi.MW_ROLLOUT_MAX_MEMBERS))
+        raise ValueError("ERROR: %d surrogate_models%s%s beside Kessler are %d ensemble members, the dycore steps at most %d"
+                         % (len(models), com, " and the persistence member" if persistence else "", nens, capi.MW_ROLLOUT_MAX_MEMBERS))
     if cfg.get("_nens_given") and int(cfg["nens"]) != nens:
-        raise ValueError("ERROR: nens = %d in the YAML input file, but %d surrogate_models%s beside Kessler are %d members (leave nens out)"
-                         % (cfg["nens"], len(models), " and the persistence member" if persistence else "", nens))
+        raise ValueError("ERROR: nens = %d in the YAML input file, but %d surrogate_models%s%s beside Kessler are %d members (leave nens out)"
+                         % (cfg["nens"], len(models), com, " and the persistence member" if persistence else "", nens))
     if {"kessler", "persistence"} & {m["name"] for m in models}:
         raise ValueError("ERROR: 'kessler' and 'persistence' name members of their own: no surrogate model may be called so")
     return models, interval, persistence, nens
@@ -141,7 +199,10 @@ def harvest_config(cfg):
     if not isinstance(out["members"], list) or not out["members"]:
         raise ValueError("ERROR: harvest.members must be a non-empty list of model names")
     out["members"] = [str(n) for n in out["members"]]
+    committee_names = [c["name"] for c in committee_config(cfg)]
     for n in out["members"]:
+        if n in committee_names:
+            raise ValueError("ERROR: harvest.members names %r, which is a committee: only single models are harvested (%s)" % (n, ", ".join(names)))
         if n not in names:
             raise ValueError("ERROR: harvest.members names %r, which is no surrogate model (%s)" % (n, ", ".join(names)))
     if len(set(out["members"])) != len(out["members"]):
@@ -256,12 +317,20 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
         if nranks > 1:
             raise ValueError("evaluate_surrogates runs on one rank (%d given): SurrogateEvaluator.combine is exact, but the reduction over "
                              "ranks is not built yet" % nranks)
+        committees = committee_config(cfg)
         cfg["surrogate_models"], cfg["eval_interval"] = surrogate_config(cfg)
+    if experiment == "inference_ponni" and "surrogate_committees" in cfg and not ("keras_weights_h5" in cfg or "keras_weights_txt" in cfg):
+        committees = committee_config(cfg)
+        if len(committees) != 1:
+            raise ValueError("ERROR: inference_ponni runs one committee, surrogate_committees lists %d" % len(committees))
+        cfg["surrogate_models"], _ = surrogate_config(cfg)
+        cfg["_committee"] = committees[0]
     if experiment == "rollout_surrogates":
         if nranks > 1:
             raise ValueError("rollout_surrogates runs on one rank (%d given): SurrogateEvaluator.combine is exact, but the reduction over "
                              "ranks is not built yet" % nranks)
         harvest = harvest_config(cfg)
+        committees = committee_config(cfg)
         cfg["surrogate_models"], cfg["eval_interval"], cfg["persistence_member"], cfg["nens"] = rollout_config(cfg)
     coupler = _coupler(cfg, device, nranks, myrank, yaml_path)
     dycore = modules.Dynamics_Euler_Stratified_WenoFV()
@@ -289,6 +358,9 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
         if experiment == "inference_ponni":
             micro = modules.Microphysics_Kessler_Surrogate()
             base = cfg["_dir"]
+            if "_committee" in cfg:                                                # the mean of the committee's models is what runs
+                by_name = {m["name"]: m for m in cfg["surrogate_models"]}
+                micro.init(coupler, committee=modules.load_surrogate_bank([by_name[n] for n in cfg["_committee"]["members"]]))
 
             def rel(p):
                 return p if p is None or os.path.isabs(p) else os.path.normpath(os.path.join(os.getcwd(), p))
@@ -297,11 +369,12 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
             for k_yaml, k_arg in (("nn_input_scaling", "in_scaling_txt"), ("nn_output_scaling", "out_scaling_txt")):
                 p = rel(cfg.get(k_yaml))
                 kw[k_arg] = p if p and os.path.exists(p) else None             # else: the shipped tables
-            micro.init(coupler, **kw)
+            if "_committee" not in cfg:
+                micro.init(coupler, **kw)
         elif experiment == "rollout_surrogates":
             micro = modules.Microphysics_Rollout()
             micro.init(coupler, modules.load_surrogate_bank(cfg["surrogate_models"]), cfg["persistence_member"],
-                       [m["name"] for m in cfg["surrogate_models"]])
+                       [m["name"] for m in cfg["surrogate_models"]], [(c["name"], c["members"]) for c in committees])
         else:
             micro = modules.Microphysics_Kessler()
             micro.init(coupler)                                                # supercell_example/driver.cpp:58
@@ -320,6 +393,14 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
         evaluator, eval_calls, eval_step = None, [], [0]
         if experiment == "evaluate_surrogates":
             evaluator, eval_models = _surrogate_evaluator(cfg["surrogate_models"], device)
+            committee_evals = []                                               # (committee, its evaluator on the bank of its width)
+            for c in committees:
+                places = [[m["name"] for m in eval_models].index(n) for n in c["members"]]
+                first = 0
+                for bank in evaluator.banks:
+                    if first <= places[0] < first + bank.models:
+                        committee_evals.append((c, modules.CommitteeEvaluator(bank, [i - first for i in places])))
+                    first += bank.models
         scorer = modules.RolloutScorer(micro.member_names) if experiment == "rollout_surrogates" else None
         harvester = None
         if experiment == "rollout_surrogates" and harvest is not None:
@@ -335,6 +416,8 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                     coupler.clone_into(inp)
                     micro.time_step(coupler, dt)
                     evaluator.accumulate(inp, coupler)
+                    for _, ce in committee_evals:
+                        ce.accumulate(inp, coupler)
                     eval_calls.append({"step": eval_step[0], "etime": etime})
                 else:
                     micro.time_step(coupler, dt)
@@ -384,12 +467,18 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                    "statistics": ["sum_d", "sum_abs_d", "sum_d2", "max_abs_d"], "fields": list(modules.EVAL_FIELDS),
                    "classes": list(modules.EVAL_CLASSES), "report": rep,
                    "history": [dict(c, banks=h) for c, h in zip(eval_calls, evaluator.history)]}
+            if committee_evals:
+                doc["committees"] = [dict(c, n_in=ce.bank.n_in, statistics=["sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_r", "sum_r2", "sum_r_abs_d"],
+                                          report=ce.report() if eval_calls else {}, history=ce.history) for c, ce in committee_evals]
+                info["committee_reports"] = {c["name"]: d["report"] for (c, _), d in zip(committee_evals, doc["committees"])}
             info["surrogate_evaluation"] = os.path.join(os.getcwd(), "surrogate_evaluation.json")
             with open(info["surrogate_evaluation"], "w") as f:
                 json.dump(doc, f, indent=1)
             info["surrogate_report"] = rep
             if not quiet and rep:
                 print(evaluator.table(rep), flush=True)
+                for c, ce in committee_evals:
+                    print(ce.table(name=c["name"]), flush=True)
         if scorer is not None:
             import json
             rep = scorer.report() if scorer.times else {"times": [], "diverged_at": dict(scorer.diverged_at)}
@@ -397,6 +486,8 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                    "members": list(scorer.member_names), "models": [dict(m, member=1 + k) for k, m in enumerate(cfg["surrogate_models"])],
                    "fields": list(scorer.fields), "statistics": list(modules.ROLLOUT_STATS), "history": scorer.history,
                    "report": rep["times"], "diverged_at": rep["diverged_at"]}
+            if committees:
+                doc["committees"] = [dict(c, member=scorer.member_names.index(c["name"])) for c in committees]
             if harvester is not None:
                 doc["harvest"] = dict(harvest, files=dict(harvester.files), samples=dict(harvester.samples), skipped=dict(harvester.skipped),
                                       calls=harvester.calls)

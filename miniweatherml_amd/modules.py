@@ -449,17 +449,43 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
     online = False        # True = the four deep_copy_to lines :273-276 un-commented: the NN result replaces Kessler's
     mlp_strict = 0        # 1: the thread-per-cell MLP that accumulates in index order (bit-identical to the CPU restatement; tests)
 
-    def init(self, coupler, weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None):
+    want_range = False    # with a committee: time_step also fills last_range, the four fields of the members' spread
+    last_range = None
+
+    def init(self, coupler, weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None, committee=None):
+        """committee: a list of 1 .. 16 (W1, b1, W2, b2, scl_in, scl_out) tuples of one width (load_surrogate_weights' form).  The network's
+        result is then the committee's mean (SurrogateBank.committee_apply), and the weight file arguments are not read."""
         super().init(coupler)
+        self._nn_out = None
+        self._committee = None
+        if committee is not None:
+            committee = list(committee)
+            if any(k is not None for k in (weights_txt, in_scaling_txt, out_scaling_txt, weights_h5)):
+                endrun("Microphysics_Kessler_Surrogate: a committee brings its own weights and scaling tables: give no file beside it")
+            if not 1 <= len(committee) <= capi.MW_COMMITTEE_MAX_MODELS:
+                endrun("Microphysics_Kessler_Surrogate: a committee has 1 to %d models, got %d" % (capi.MW_COMMITTEE_MAX_MODELS, len(committee)))
+            self._committee = SurrogateBank(committee, coupler.device)
+            self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out = committee[0]
+            return
         self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out = load_surrogate_weights(weights_txt, in_scaling_txt,
                                                                                               out_scaling_txt, weights_h5)
-        self._nn_out = None
 
     def time_step(self, coupler, dt):
         dm = coupler.get_data_manager_readwrite()
         temp, rho_d = dm.get("temp"), dm.get("density_dry", readonly=True)
         rho_v, rho_c, rho_r = dm.get("water_vapor"), dm.get("cloud_liquid"), dm.get("precip_liquid")
-        if self.W1.shape[0] == 9:                                              # the stencil model: what load_surrogate_weights found
+        if getattr(self, "_committee", None) is not None:
+            if self._nn_out is None:
+                self._nn_out = [torch.empty_like(temp) for _ in range(4)]
+            if self.want_range and self.last_range is None:
+                self.last_range = [torch.empty_like(temp) for _ in range(4)]
+            self._committee.strict = self.mlp_strict
+            # the coupler's fields are (nz, ny, nx, nens): every member is one more column, so the whole array is one member of nens = 1
+            flat = [t.reshape(coupler.get_nz(), -1, 1) for t in (temp, rho_d, rho_v, rho_c, rho_r)]
+            self._committee.committee_apply(coupler.get_nz(), range(self._committee.models), 0, flat,
+                                            [t.reshape(coupler.get_nz(), -1, 1) for t in self._nn_out],
+                                            [t.reshape(coupler.get_nz(), -1, 1) for t in self.last_range] if self.want_range else None)
+        elif self.W1.shape[0] == 9:                                            # the stencil model: what load_surrogate_weights found
             self._nn_out = mlp_stencil_forward(coupler.get_nz(), temp, rho_d, rho_v, rho_c, rho_r, self.W1, self.b1, self.W2, self.b2,
                                                self.scl_in, self.scl_out, self._nn_out, strict=self.mlp_strict)
         else:
@@ -593,6 +619,34 @@ class SurrogateBank:
         check(capi.lib().mw_mlp_set_strict(0))
         check(rc)
 
+    def committee_apply(self, nz, sel, member, in5, out4, range4=None):
+        """mw_surrogate_committee_apply: the mean of the bank's models sel (1 .. 16 distinct indices, summed in that order) on ensemble
+        member `member` of the member-fastest fields in5 = (temp, density_dry, water_vapor, cloud_liquid, precip_liquid), each
+        (nz, ..., nens), written to out4 = (temp, water_vapor, cloud_liquid, precip_liquid) of the same shape -- each the matching input
+        tensor (in place) or a tensor of its own -- and, with range4, the members' largest minus smallest value per cell and field.  Only
+        elements of `member` are read and written (self.strict = 1: the thread-per-column form)."""
+        sel = [int(s) for s in sel]
+        if len(in5) != 5 or len(out4) != 4 or (range4 is not None and len(range4) != 4):
+            endrun("SurrogateBank.committee_apply: five input fields, four output fields and (optionally) four range fields expected")
+        every = list(in5) + list(out4) + (list(range4) if range4 is not None else [])
+        if any(t.shape != in5[0].shape for t in every) or in5[0].dim() < 2:
+            endrun("SurrogateBank.committee_apply: fields of one shape (nz, ..., nens) expected")
+        if any(t.dtype != torch.float64 or not t.is_contiguous() for t in every):
+            endrun("SurrogateBank.committee_apply: contiguous float64 fields expected")
+        nens = int(in5[0].shape[-1])
+        n = in5[0].numel() // nens
+        if int(nz) < 1 or n % int(nz) != 0:
+            endrun("SurrogateBank.committee_apply: %d cells per member are not a whole number of columns of nz = %d" % (n, nz))
+        if any(t.device != self.device for t in every):
+            endrun("SurrogateBank.committee_apply: the bank lives on %s, the fields on %s" % (self.device, sorted({str(t.device) for t in every})))
+        check(capi.lib().mw_mlp_set_strict(int(bool(self.strict))))
+        with torch.cuda.device(self.device):
+            rc = capi.lib().mw_surrogate_committee_apply(self._h, len(sel), (C.c_int * max(1, len(sel)))(*sel), int(member), int(nz), n // int(nz), nens,
+                                                         _field_ptr_array(in5), _field_ptr_array(out4),
+                                                         _field_ptr_array(range4) if range4 is not None else None, _stream_ptr(self.device))
+        check(capi.lib().mw_mlp_set_strict(0))
+        check(rc)
+
 
 def json_safe(x):
     """Nested lists of floats with inf / NaN as the strings "inf", "-inf", "nan" (bare tokens are no JSON); finite numbers unchanged."""
@@ -722,6 +776,148 @@ class SurrogateEvaluator:
         return "\n".join(lines)
 
 
+class _CommitteeRow:
+    models = 1            # what SurrogateEvaluator.report reads of a bank: the committee is the one "model" beside the persistence row
+
+
+def committee_score(nz, in5, truth4, pred4, range4, workspace=None):
+    """mw_committee_score on contiguous fp64 CUDA fields of nz levels: returns (stats (2, 4, 7) fp64 = [class][field][sum d, sum |d|,
+    sum d^2, max |d|, sum r, sum r^2, sum r |d|], counts (2,) int64 cells per class, covered (2, 4) int64 cells with |d| <= r), d = pred -
+    truth, r = range; classes as SurrogateBank.evaluate -- one device-to-host copy."""
+    every = list(in5) + list(truth4) + list(pred4) + list(range4)
+    if (len(in5), len(truth4), len(pred4), len(range4)) != (5, 4, 4, 4):
+        endrun("committee_score: five input fields and four truth, prediction and range fields expected")
+    n, dev = in5[0].numel(), in5[0].device
+    if int(nz) < 1 or n % int(nz) != 0 or any(t.numel() != n for t in every):
+        endrun("committee_score: the seventeen fields must have one size, a whole number of columns of nz = %d levels" % nz)
+    if any(t.device != dev or t.dtype != torch.float64 or not t.is_contiguous() for t in every):
+        endrun("committee_score: contiguous float64 fields of one device expected")
+    L = capi.lib()
+    nbytes = L.mw_committee_score_workspace_bytes(int(nz), n // int(nz))
+    if workspace is None or workspace.numel() * 8 < nbytes:
+        workspace = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    buf = torch.empty(56 + 10, dtype=torch.int64, device=dev)                   # the statistics' bytes, then the ten counts
+    with torch.cuda.device(dev):
+        check(L.mw_committee_score(int(nz), n // int(nz), _field_ptr_array(in5), _field_ptr_array(truth4), _field_ptr_array(pred4),
+                                   _field_ptr_array(range4), _ptr(workspace), C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr() + 8 * 56),
+                                   _stream_ptr(dev)))
+    host = buf.cpu().numpy()
+    return host[:56].view(np.float64).reshape(2, 4, 7).copy(), host[56:58].copy(), host[58:].reshape(2, 4).copy()
+
+
+def _exact_units_array(x):
+    """(exact integers in units of 2^-1074, the non-finite values apart) of an fp64 array: surrogate_scores' split."""
+    x = np.asarray(x, dtype=np.float64)
+    fin = np.isfinite(x)
+    units = np.zeros(x.shape, dtype=object)
+    flat, ff, src = units.reshape(-1), fin.reshape(-1), x.reshape(-1)
+    for i in range(flat.size):
+        flat[i] = _exact_sum_units(src[i]) if ff[i] else 0
+    return units, np.where(fin, 0.0, x)
+
+
+def range_error_correlation(n, sum_r, sum_r2, sum_a, sum_a2, sum_ra):
+    """Pearson's r of the range r and the error |d| over n cells from their six sums; None when a sum is not finite or a variance is not
+    positive (a constant range, a perfect prediction, an empty class)."""
+    vals = (sum_r, sum_r2, sum_a, sum_a2, sum_ra)
+    if n < 1 or not all(np.isfinite(v) for v in vals):
+        return None
+    mr, ma = sum_r / n, sum_a / n
+    vr, va = sum_r2 / n - mr * mr, sum_a2 / n - ma * ma
+    if not (vr > 0.0 and va > 0.0):
+        return None
+    q = (sum_ra / n - mr * ma) / np.sqrt(vr * va)
+    return float(min(1.0, max(-1.0, q))) if np.isfinite(q) else None
+
+
+class CommitteeEvaluator:
+    """Scores the committee `sel` of a bank against the microphysics in charge, call after call, as SurrogateEvaluator scores single
+    models: accumulate(inp, out) runs the committee forward into scratch fields (mean and range) and mw_committee_score on them, report()
+    gives per class (inactive, active, all) and field the evaluator's row (bias, mae, rmse, max_abs, rmse_over_persistence) plus mean_range,
+    coverage (the fraction of cells with |d| <= range) and range_error_correlation (range_error_correlation above)."""
+
+    def __init__(self, bank, sel):
+        self.bank, self.sel = bank, [int(i) for i in sel]
+        if not 1 <= len(self.sel) <= capi.MW_COMMITTEE_MAX_MODELS:
+            endrun("CommitteeEvaluator: a committee has 1 to %d models, got %d" % (capi.MW_COMMITTEE_MAX_MODELS, len(self.sel)))
+        if len(set(self.sel)) != len(self.sel) or any(not 0 <= i < bank.models for i in self.sel):
+            endrun("CommitteeEvaluator: the committee must name distinct models of the bank's %d" % bank.models)
+        self.total = None
+        self.history = []
+        self._scratch = None
+        self._ws = None
+
+    def accumulate(self, inp, out):
+        """One call: the committee's mean and range from `inp`, scored against `out`; added to the running total.  Returns the call's raw
+        (stats (2, 2, 4, 7) = [committee | persistence], counts (2,), covered (2, 4))."""
+        names5 = ("temp", "density_dry", "water_vapor", "cloud_liquid", "precip_liquid")
+        nz = inp.get_nz()
+        in5 = [inp.get_data_manager_readonly().get(n, True) for n in names5]
+        truth4 = [out.get_data_manager_readonly().get(n, True) for n in EVAL_FIELDS]
+        if self._scratch is None or self._scratch[0].shape != in5[0].shape:
+            self._scratch = [torch.empty_like(in5[0]) for _ in range(8)]
+        pred4, range4 = self._scratch[:4], self._scratch[4:]
+        as1 = lambda ts: [t.reshape(nz, -1, 1) for t in ts]                     # noqa: E731   (every member is one more column)
+        self.bank.committee_apply(nz, self.sel, 0, as1(in5), as1(pred4), as1(range4))
+        if self._ws is None:
+            self._ws = torch.empty((capi.lib().mw_committee_score_workspace_bytes(nz, in5[0].numel() // nz) + 7) // 8, dtype=torch.float64,
+                                   device=in5[0].device)
+        stats, counts, covered = committee_score(nz, in5, truth4, pred4, range4, self._ws)
+        pstats, _, _ = committee_score(nz, in5, truth4, [in5[0], in5[2], in5[3], in5[4]], range4, self._ws)      # persistence: prediction = input
+        both = np.stack([stats, pstats])
+        self.history.append({"stats": json_safe(both.tolist()), "counts": counts.tolist(), "covered": covered.tolist()})
+        units, nonf = _exact_units_array(stats[..., 4:])
+        one = {"scores": [surrogate_scores(both[..., :4], counts)], "rsums": units, "rnonfinite": nonf, "covered": covered.astype(np.int64)}
+        if self.total is None:
+            self.total = one
+        else:
+            t = self.total
+            self.total = {"scores": SurrogateEvaluator.combine(t["scores"], one["scores"]), "rsums": t["rsums"] + units,
+                          "rnonfinite": t["rnonfinite"] + nonf, "covered": t["covered"] + one["covered"]}
+        return both, counts, covered
+
+    def report(self):
+        if self.total is None:
+            endrun("CommitteeEvaluator.report: nothing accumulated")
+        t = self.total
+        base = SurrogateEvaluator([_CommitteeRow()], ["committee"]).report(t["scores"])["committee"]
+        sc = t["scores"][0]
+        counts = np.concatenate([sc["counts"], [sc["counts"].sum()]])
+        with3 = lambda a: np.concatenate([a, a.sum(axis=0, keepdims=True)], axis=0)      # noqa: E731   class axis -> (inactive, active, all)
+        rs = _sums_to_float(with3(t["rsums"]), with3(t["rnonfinite"]))                 # (3, 4, 3): sum r, sum r^2, sum r |d|
+        ds = _sums_to_float(with3(sc["sums"][0]), with3(sc["nonfinite"][0]))           # (3, 4, 3): sum d, sum |d|, sum d^2
+        cov = with3(t["covered"])
+        rep = {}
+        for c, cname in enumerate(EVAL_CLASSES + ("all",)):
+            n = int(counts[c])
+            row = {"n": n}
+            for v, fname in enumerate(EVAL_FIELDS):
+                f = dict(base[cname][fname])
+                if n > 0:
+                    mr = rs[c, v, 0] / n
+                    f["mean_range"] = float(mr) if np.isfinite(mr) else None
+                    f["coverage"] = int(cov[c, v]) / n
+                    f["range_error_correlation"] = range_error_correlation(n, rs[c, v, 0], rs[c, v, 1], ds[c, v, 1], ds[c, v, 2], rs[c, v, 2])
+                    if f["mean_range"] is None:
+                        f["finite"] = False
+                else:
+                    f.update(mean_range=None, coverage=None, range_error_correlation=None)
+                row[fname] = f
+            rep[cname] = row
+        return rep
+
+    def table(self, rep=None, name="committee"):
+        """report() as text: one line per class; rmse / persistence rmse, mean range and coverage per field."""
+        rep = self.report() if rep is None else rep
+        lines = ["%-16s %-8s %12s " % ("committee", "class", "n") + " ".join("%40s" % ("%s rmse (/pers.) range cover" % f) for f in EVAL_FIELDS)]
+        fmt = lambda x, p: "-" if x is None else p % x                                # noqa: E731
+        for cname, row in rep.items():
+            cells = ["%40s" % ("%s (%s) %s %s" % (fmt(row[f]["rmse"], "%.4e"), fmt(row[f]["rmse_over_persistence"], "%.4g"),
+                                                   fmt(row[f]["mean_range"], "%.3e"), fmt(row[f]["coverage"], "%.3f"))) for f in EVAL_FIELDS]
+            lines.append("%-16s %-8s %12d " % (name, cname, row["n"]) + " ".join(cells))
+        return "\n".join(lines)
+
+
 # ---- candidate surrogates rolled out as ensemble members beside Kessler ----------------------------------------------------------------
 ROLLOUT_FIELDS = ("density_dry", "uvel", "vvel", "wvel", "temp", "water_vapor", "cloud_liquid", "precip_liquid")
 ROLLOUT_STATS = ("sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_x", "min_x", "max_x")
@@ -729,16 +925,21 @@ ROLLOUT_WATER = ("water_vapor", "cloud_liquid", "precip_liquid")
 ROLLOUT_IN5 = ("temp", "density_dry", "water_vapor", "cloud_liquid", "precip_liquid")     # fields5 of members_apply and of the teacher
 
 
-def rollout_member_names(model_names, persistence=True):
-    """The fixed roles of a rollout's ensemble members: member 0 is Kessler, members 1 .. K the models of the list in its order, an optional
-    last member persistence (no microphysics).  More members than the dycore steps in one call is an error that names the limit."""
+def rollout_member_names(model_names, persistence=True, committees=()):
+    """The fixed roles of a rollout's ensemble members: member 0 is Kessler, members 1 .. K the models of the list in its order, then one
+    member per committee (names of `committees`, in its order), an optional last member persistence (no microphysics).  More members than
+    the dycore steps in one call is an error that names the limit."""
     names = [str(n) for n in model_names]
     if len(set(names)) != len(names) or {"kessler", "persistence"} & set(names):
         endrun("rollout: model names must be unique and neither 'kessler' nor 'persistence'")
-    members = ["kessler"] + names + (["persistence"] if persistence else [])
+    cnames = [str(n) for n in committees]
+    if len(set(cnames)) != len(cnames) or ({"kessler", "persistence"} | set(names)) & set(cnames):
+        endrun("rollout: committee names must be unique and neither a model's name nor 'kessler' nor 'persistence'")
+    members = ["kessler"] + names + cnames + (["persistence"] if persistence else [])
     if len(members) > capi.MW_ROLLOUT_MAX_MEMBERS:
-        endrun("rollout: %d models%s beside Kessler are %d ensemble members, the dycore steps at most %d"
-               % (len(names), " and persistence" if persistence else "", len(members), capi.MW_ROLLOUT_MAX_MEMBERS))
+        endrun("rollout: %d models%s%s beside Kessler are %d ensemble members, the dycore steps at most %d"
+               % (len(names), (", %d committees" % len(cnames)) if cnames else "", " and persistence" if persistence else "", len(members),
+                  capi.MW_ROLLOUT_MAX_MEMBERS))
     return members
 
 
@@ -759,18 +960,29 @@ class Microphysics_Rollout(Microphysics_Kessler):
     def micro_name(self):
         return "rollout"
 
-    def init(self, coupler, models, persistence=True, names=None):
+    def init(self, coupler, models, persistence=True, names=None, committees=()):
         """models: (W1, b1, W2, b2, scl_in, scl_out) tuples as load_surrogate_weights returns them, single-cell and stencil networks in any
-        order; names: theirs (default model0, model1, ...).  The coupler must have 1 + len(models) (+ 1 with persistence) members."""
+        order; names: theirs (default model0, model1, ...).  committees: (name, [model names]) pairs; each is one more member after the
+        models, replaced in place from its OWN state by the mean of its models (1 .. 16 of one width, SurrogateBank.committee_apply on that
+        width's bank).  The coupler must have 1 + len(models) + len(committees) (+ 1 with persistence) members."""
         models = list(models)
-        names = ["model%d" % k for k in range(len(models))] if names is None else list(names)
+        names = ["model%d" % k for k in range(len(models))] if names is None else [str(n) for n in names]
         if len(names) != len(models):
             endrun("Microphysics_Rollout: %d names for %d models" % (len(names), len(models)))
-        self.member_names = rollout_member_names(names, persistence)
+        committees = [(str(c[0]), [str(n) for n in c[1]]) for c in committees]
+        self.member_names = rollout_member_names(names, persistence, [c[0] for c in committees])
         self.persistence = bool(persistence)
         if coupler.get_nens() != len(self.member_names):
-            endrun("Microphysics_Rollout: %d models%s beside Kessler need nens = %d, the coupler has %d"
-                   % (len(models), " and persistence" if persistence else "", len(self.member_names), coupler.get_nens()))
+            endrun("Microphysics_Rollout: %d models%s%s beside Kessler need nens = %d, the coupler has %d"
+                   % (len(models), (", %d committees" % len(committees)) if committees else "", " and persistence" if persistence else "",
+                      len(self.member_names), coupler.get_nens()))
+        for cname, cmodels in committees:
+            if not 1 <= len(cmodels) <= capi.MW_COMMITTEE_MAX_MODELS:
+                endrun("Microphysics_Rollout: committee %r has %d models, a committee has 1 to %d" % (cname, len(cmodels), capi.MW_COMMITTEE_MAX_MODELS))
+            if len(set(cmodels)) != len(cmodels) or any(n not in names for n in cmodels):
+                endrun("Microphysics_Rollout: committee %r must name distinct models of the list (%s)" % (cname, ", ".join(names)))
+            if len({int(np.shape(models[names.index(n)][0])[0]) for n in cmodels}) != 1:
+                endrun("Microphysics_Rollout: committee %r mixes single-cell and stencil models: a committee has one width" % cname)
         super().init(coupler)
         coupler.set_option("micro", "rollout")
         widths = []
@@ -780,6 +992,12 @@ class Microphysics_Rollout(Microphysics_Kessler):
         # one bank per width; a model keeps the member its place in the list gives it
         self.banks = [(SurrogateBank([m for m in models if np.shape(m[0])[0] == w], coupler.device),
                        [1 + k for k, m in enumerate(models) if np.shape(m[0])[0] == w]) for w in widths]
+        # a committee runs on its width's bank: (bank, its models' places in that bank, its member)
+        self.committees = []
+        for ci, (cname, cmodels) in enumerate(committees):
+            w = int(np.shape(models[names.index(cmodels[0])][0])[0])
+            in_bank = [k for k, m in enumerate(models) if np.shape(m[0])[0] == w]
+            self.committees.append((self.banks[widths.index(w)][0], [in_bank.index(names.index(n)) for n in cmodels], 1 + len(models) + ci))
         self._m0 = None
 
     def time_step(self, coupler, dt):
@@ -810,6 +1028,9 @@ class Microphysics_Rollout(Microphysics_Kessler):
         for bank, members in self.banks:
             bank.strict = self.mlp_strict
             bank.members_apply(nz, members, [temp, rho_d, rho_v, rho_c, rho_r])
+        for bank, sel, member in getattr(self, "committees", ()):
+            bank.strict = self.mlp_strict
+            bank.committee_apply(nz, sel, member, [temp, rho_d, rho_v, rho_c, rho_r], [temp, rho_v, rho_c, rho_r])
 
 
 def kessler_members_teacher(coupler, members, dt, max_rainsplit=64, outs=None, return_rainsplit=False):

@@ -524,6 +524,13 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     return result
 
 
+def committee_snippet(names, name="committee"):
+    """The `surrogate_committees:` lines that make one committee of the named models (the drivers' committee_config reads them)."""
+    if len(names) > 16:
+        raise SurrogateTrainError("--committee: %d models were trained, a committee holds at most 16" % len(names))
+    return "surrogate_committees:\n  - {name: %s, members: [%s]}" % (name, ", ".join(names))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m miniweatherml_amd.surrogate_train",
                                  description="Train the Kessler surrogate (5 -> 10 -> 4, or 9 -> 10 -> 4 with --stencil) on DataGenerator sample files, on the GPU.")
@@ -539,6 +546,8 @@ def main(argv=None):
     ap.add_argument("--models", type=int, default=1, help="train seeds seed .. seed+K-1 at once and keep the best (lowest val_loss)")
     ap.add_argument("--keep-all", action="store_true", help="also write weights_<k>.txt for every trained model and print the surrogate_models list "
                     "for the evaluate_surrogates and rollout_surrogates drivers")
+    ap.add_argument("--committee", action="store_true", help="with --keep-all: also print a surrogate_committees list that names all trained models "
+                    "(at most 16 form a committee)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--init", default=None, metavar="DIR", help="warm start: continue DIR/weights.txt with DIR's scaling tables (all models start there)")
     ap.add_argument("--stencil", action="store_true", help="train the two-cell stencil model (the cell and the level above: 9 inputs, 144 weights)")
@@ -555,6 +564,8 @@ def main(argv=None):
         print("surrogate_models:")
         for m in r["surrogate_models"]:
             print("  - {%s}" % ", ".join("%s: %s" % kv for kv in m.items()))
+        if a.committee:
+            print(committee_snippet([m["name"] for m in r["surrogate_models"]]))
     return 0
 
 
