@@ -30,7 +30,7 @@ constexpr int DIV_STATS = 7;               // sum d, sum |d|, sum d^2, max |d|, 
 constexpr int DIV_ROW = 8;                 // ... and the non-finite count (as int64 bits) in the workspace rows
 constexpr int DIV_MAX_BLOCKS = 512;        // grid.x: grid-stride beyond two blocks per CU (grid.y carries the fields)
 
-// the larger / smaller of two values, NaN if either is (mw_mlp.hip: eval_max)
+// the larger / smaller of two values, NaN if either is (mw_mlp_net.h: eval_max)
 __device__ __forceinline__ double div_max(double a, double b) { return (b > a || b != b) ? b : a; }
 __device__ __forceinline__ double div_min(double a, double b) { return (b < a || b != b) ? b : a; }
 __device__ __forceinline__ double div_join(int s, double a, double b) { return (s == 3 || s == 6) ? div_max(a, b) : s == 5 ? div_min(a, b) : a + b; }
