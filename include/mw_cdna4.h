@@ -275,6 +275,14 @@ int  mw_kessler_time_step(int nz, long long ncol, double dz, double dt, double *
  * contraction) with glibc's pow and exp (csrc/mw_glibc_pow.h): the bits microphysics_kessler.h:99-162, :234-339 produces on a glibc
  * host (YAKL serial backend).  0 (default): the production kernels (1e-12 from it).  Process-wide, like the module's constants. */
 int  mw_kessler_set_strict(int strict);
+/* Host only, no device needed: the z-chunk length of the rainsplit == 1 sweep for nz levels and `columns` kernel columns (ncol, or
+ * ncol * nens for the teacher).  It is nz (one chunk) or one of 25, 20, 16, 12, 10, 8, 5, 4 below nz, so a column is cut into at most
+ * nz / 4 + 1 chunks -- the bound the flux_top rows of the two workspace formulas rest on. */
+int  mw_kessler_chunk(int nz, long long columns);
+/* Test aid, per calling thread like mw_kessler_set_strict: replaces that rule in mw_kessler_time_step and mw_kessler_members_teacher.
+ * 0 restores the rule; one of 4, 5, 8, 10, 12, 16, 20, 25 is used where it is < nz (else the column is one chunk); any value >= 1024
+ * forces one chunk.  Anything else is an error: a chunk below 4 would overrun the flux_top rows.  The results do not depend on it. */
+int  mw_kessler_debug_set_chunk(int chunk);
 
 /* ponni::load_h5_weights<N>(file, group, dataset), microphysics_kessler_ponni.h:103-107: one 32-bit float dataset of an HDF5 file
  * (the Keras weight file `keras_weights_h5`: "/dense_6/dense_6" "kernel:0" (5,10), "bias:0" (10), "/dense_7/dense_7" ...), read by a

@@ -95,6 +95,8 @@ SYMBOLS = {
     "mw_weno5_edges": (C.c_int, [C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "mw_kessler_workspace_bytes": (C.c_longlong, [C.c_int, C.c_longlong]),
     "mw_kessler_set_strict": (C.c_int, [C.c_int]),
+    "mw_kessler_chunk": (C.c_int, [C.c_int, C.c_longlong]),
+    "mw_kessler_debug_set_chunk": (C.c_int, [C.c_int]),
     "mw_mlp_set_strict": (C.c_int, [C.c_int]),
     "mw_column_set_strict": (C.c_int, [C.c_int]),
     "mw_kessler_time_step": (C.c_int, [C.c_int, C.c_longlong, C.c_double, C.c_double] + [C.c_void_p] * 7 +

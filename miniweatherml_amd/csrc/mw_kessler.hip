@@ -664,13 +664,33 @@ static KesP kessler_params(int nz, long long ncol, double dz, double dt) {
   return p;
 }
 // z chunks of the rainsplit == 1 path: enough (column, chunk) threads to fill the chip, at least 4 levels per chunk
+// (the result is nz or a list value below nz, never a chunk shorter than 4 that is not the whole column: a column is cut into at most
+//  nz / 4 + 1 chunks, which is what the flux_top rows of the two workspace formulas rest on; tests/test_kessler_chunk_cpu.py)
 static int kessler_chunk(int nz, long long columns) {
   int chunk = nz;
   for (int c : {25, 20, 16, 12, 10, 8, 5, 4}) if (c < nz) { chunk = c; if (((columns + 63) / 64) * ((nz + c - 1) / c) >= 16384) break; }
   return chunk;
 }
+// test aid (mw_kessler_debug_set_chunk): 0 = the rule above; a list value or >= 1024 (one chunk) replaces it, per calling thread
+static thread_local int g_kessler_chunk_override = 0;
+static int kessler_chunk_used(int nz, long long columns) {
+  const int c = g_kessler_chunk_override;
+  if (c == 0) return kessler_chunk(nz, columns);
+  return c < nz ? c : nz;
+}
 
 int mw_kessler_set_strict(int strict) { g_kessler_strict = strict ? 1 : 0; return 0; }
+
+int mw_kessler_chunk(int nz, long long columns) { return kessler_chunk(nz, columns); }
+
+int mw_kessler_debug_set_chunk(int chunk) {
+  bool ok = (chunk == 0 || chunk >= 1024);
+  for (int c : {25, 20, 16, 12, 10, 8, 5, 4}) ok = ok || chunk == c;
+  if (!ok) MW_FAIL("kessler_debug_set_chunk: " + std::to_string(chunk) + " is not 0, one of 4, 5, 8, 10, 12, 16, 20, 25, or >= 1024 "
+                   "(a chunk below 4 would overrun the workspace's flux_top rows)");
+  g_kessler_chunk_override = chunk;
+  return 0;
+}
 
 int mw_kessler_time_step(int nz, long long ncol, double dz, double dt, double *rho_v, double *rho_c, double *rho_r,
                          const double *rho_d, double *temp, double *precl, void *workspace, int *rainsplit_out, void *stream) {
@@ -690,7 +710,7 @@ int mw_kessler_time_step(int nz, long long ncol, double dz, double dt, double *r
     hipLaunchKernelGGL(k_kessler_strict_column, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, st, p, rho_v, rho_c, rho_r, rho_d, temp,
                        precl, bits, ws); MW_LAUNCH_CHECK();
   } else {
-    const int chunk = kessler_chunk(nz, ncol), nchunks = (nz + chunk - 1) / chunk;
+    const int chunk = kessler_chunk_used(nz, ncol), nchunks = (nz + chunk - 1) / chunk;
     double *flux_top = ws + 5ll * nz * ncol;                  // (nchunks-1, ncol)
     const int klevels = 5;                                      // levels per thread of the CFL pass (k_kessler_prep_t: KL)
     hipLaunchKernelGGL(k_kessler_prep_t<false>, dim3((unsigned)((ncol + 255) / 256), (unsigned)((nz + klevels - 1) / klevels)), dim3(256), 0, st, p,
@@ -757,7 +777,7 @@ int mw_kessler_members_teacher(int nz, long long ncol, int nens, int nm, const i
   t.o_temp = out4[0]; t.o_v = out4[1]; t.o_c = out4[2]; t.o_r = out4[3];
   // every call starts its words from the all-ones pattern, in stream order (no host synchronisation, any number of calls in flight)
   MW_HIP(hipMemsetAsync(words, 0xFF, 512, st));
-  const int chunk = kessler_chunk(nz, NC), nchunks = (nz + chunk - 1) / chunk;     // (on the columns of all members)
+  const int chunk = kessler_chunk_used(nz, NC), nchunks = (nz + chunk - 1) / chunk;     // (on the columns of all members)
   const int klevels = 5;                                      // (k_kessler_prep_t: KL)
   const unsigned gx = (unsigned)((NC + 255) / 256);
   hipLaunchKernelGGL(k_kessler_prep_t<true>, dim3(gx, (unsigned)((nz + klevels - 1) / klevels)), dim3(256), 0, st, p, t.rho_r, t.rho_d,
