@@ -112,7 +112,10 @@ int  mw_dycore_set_strict(mw_dycore_t h, int strict);
  * Launch shapes: "chunk_y", "chunk_yt", "chunk_z", "chunk_f" (cells per chunk, 0 = the chunk model), "chunk_model".  Built-in transport
  * (read when mw_dycore_use_rccl / _self installs it): "rccl_lanes" (0 = process default | 1 | 2), "rccl_two_comms" (-1 | 0 | 1), "rccl_prio" (1: side streams at the highest priority), "rccl_inline" (1: the group runs on the caller's stream, no side stream),
  * "xchg_fuzz" (seed of random delays around the sends / receives; a test aid), "debug_no_patch" (a test aid: the y-face correction pass of the
- * fused tracer stage is not launched -- the negative control of the FCT tests).  Unknown keys and out-of-range values are errors.  (The
+ * fused tracer stage is not launched -- the negative control of the FCT tests).  "vapour_state" (default 1; the folded supercell configuration
+ * with one member and WENO-5 on the one-stream schedule behind k_y_all, ignored elsewhere: the water vapour is advanced by the x/z state kernel and the
+ * tracer stage works on cloud and rain only; a stage in which a vapour cell fails the limiter test is redone by the three-tracer tracer stage;
+ * results are bit for bit those of 0), "debug_vapour_redo" (a test aid: every stage takes that redo).  Unknown keys and out-of-range values are errors.  (The
  * experiment builds of rounds 4-5 -- the fused x-y-z state kernel, the balanced launch lists, the timing hooks -- left the tree in round 6.) */
 int  mw_dycore_set_option(mw_dycore_t h, const char *key, long long value);
 int  mw_dycore_get_option(mw_dycore_t h, const char *key, long long *value);
@@ -203,6 +206,14 @@ long long mw_debug_zero_maps(mw_dycore_t h, unsigned int *out_host, long long ca
  * the coupler's arrays / the slab the converting y launch fills) is not all zero.  Returns the sum of the four counters since the handle was
  * created (out4, may be NULL: the four), -1 when the option never ran.  No reference counterpart. */
 long long mw_debug_zero_violations(mw_dycore_t h, unsigned long long *out4);
+/* Test aid: how many RK stages of the last time step redid their water vapour in the tracer stage's three-tracer form (option "vapour_state":
+ * a cell failed the limiter test in the x/z state kernel, or "debug_vapour_redo" asked for it); 0 when no stage ran the vapour form, -1 for a
+ * null handle.  No reference counterpart. */
+long long mw_debug_vapour_redo(mw_dycore_t h);
+/* Test aid: the fused tracer stage's per-cell flag bytes ("this cell scaled its south / north face of tracer v": bits 2v / 2v + 1) as the
+ * last launch left them, index (k * ny + j) * nx * nens + x; at most cap bytes go to out_host (host memory).  Returns the number of cells,
+ * -1 on error.  No reference counterpart. */
+long long mw_debug_tracer_flags(mw_dycore_t h, unsigned char *out_host, long long cap);
 
 /* modules::perturb_temperature(coupler, thermal=true, random=false), perturb_temperature.h:41-66 */
 int  mw_perturb_temperature(const mw_grid_t *g, double *temp, void *stream);

@@ -869,10 +869,10 @@ int mw_dycore_create(mw_dycore_t *h, const mw_grid_t *g, const unsigned char *tr
       hipMalloc(&d->tendY, (size_t)5 * p.nC * sizeof(double)) != hipSuccess || hipMalloc(&d->FX, fxb) != hipSuccess ||
       hipMalloc(&d->FY, fyb) != hipSuccess || hipMalloc(&d->FZ, fzb) != hipSuccess ||
       hipMalloc(&d->imm, (size_t)p.nC * sizeof(double)) != hipSuccess || hipMalloc(&d->flags, (size_t)p.nC) != hipSuccess ||
-      hipMalloc(&d->dirty, 4 * sizeof(unsigned int)) != hipSuccess) {
+      hipMalloc(&d->dirty, MW_DIRTY_WORDS * sizeof(unsigned int)) != hipSuccess) {
     set_error("hipMalloc(workspace) failed"); return fail(); }
   (void)hipMemsetAsync(d->flags, 0, (size_t)p.nC, d->stream);
-  (void)hipMemsetAsync(d->dirty, 0, 4 * sizeof(unsigned int), d->stream);
+  (void)hipMemsetAsync(d->dirty, 0, MW_DIRTY_WORDS * sizeof(unsigned int), d->stream);
   d->fused = (g->num_tracers <= 4 && g->nens <= 12) ? 1 : 0;       // (option "fused_tracers" = 0: the unfused tracer stage)
   // zero everything once: halo corners are never written and the flux arrays start at 0 (:1677-1682)
   (void)hipMemsetAsync(d->S0, 0, slab, d->stream); (void)hipMemsetAsync(d->S1, 0, slab, d->stream);
@@ -956,6 +956,10 @@ const OptDesc OPTS[] = {
   {"xchg_fuzz", &DyOpts::xchg_fuzz, 0, 0x7fffffff, 0}, {"rccl_prio", &DyOpts::rccl_prio, 0, 1, 0}, {"rccl_inline", &DyOpts::rccl_inline, 0, 1, 0},
   {"debug_no_patch", &DyOpts::debug_no_patch, 0, 1, 0},
 };
+// (round 7's two keys, beside the table like "fused_tracers": tests/test_capi_host.py ties every table entry to the DEFAULTS of
+//  tests/test_gpu_options.py; the defaults of these two are under test in tests/test_gpu_vapour_state.py)
+struct OptDesc2 { const char *key; int DyOpts::*field; };
+const OptDesc2 OPTS_VAPOUR[] = {{"vapour_state", &DyOpts::vapour_state}, {"debug_vapour_redo", &DyOpts::debug_vapour_redo}};
 constexpr int BUILD_FLAGS = 0;      // (no optional parts any more: mw_build_flags stays in the ABI and says so)
 }
 int mw_build_flags(void) { return BUILD_FLAGS; }
@@ -965,6 +969,12 @@ int mw_dycore_set_option(mw_dycore_t d, const char *key, long long value) {
     if (value != 0 && value != 1) MW_FAIL("option fused_tracers must be 0 or 1");
     if (value && !(d->g.num_tracers <= 4 && d->g.nens <= 12)) MW_FAIL("option fused_tracers = 1 needs at most 4 tracers and 12 members");
     d->fused = (int)value;
+    return 0;
+  }
+  for (const OptDesc2 &od : OPTS_VAPOUR) {
+    if (strcmp(key, od.key)) continue;
+    if (value != 0 && value != 1) MW_FAIL(std::string("option ") + key + " must be 0 or 1");
+    d->o.*(od.field) = (int)value;
     return 0;
   }
   for (const OptDesc &od : OPTS) {
@@ -979,6 +989,7 @@ int mw_dycore_set_option(mw_dycore_t d, const char *key, long long value) {
 int mw_dycore_get_option(mw_dycore_t d, const char *key, long long *value) {
   if (!d || !key || !value) MW_FAIL("mw_dycore_get_option: null argument");
   if (!strcmp(key, "fused_tracers")) { *value = d->fused; return 0; }
+  for (const OptDesc2 &od : OPTS_VAPOUR) if (!strcmp(key, od.key)) { *value = d->o.*(od.field); return 0; }
   for (const OptDesc &od : OPTS) if (!strcmp(key, od.key)) { *value = d->o.*(od.field); return 0; }
   MW_FAIL(std::string("unknown option: ") + key);
 }
@@ -1243,6 +1254,7 @@ int mw_dycore_time_step(mw_dycore_t d, double *rho_d, double *u, double *v, doub
     if (lazy) { d->p.pinc = d->pinc; d->pinc_on = false; d->pinc_lazy++; }
     else if (flush_pending(d)) return 1;
   }
+  if (d->vap_used) { MW_HIP(hipMemsetAsync(d->dirty + MW_VREDO_RING + 8, 0, sizeof(unsigned int), d->stream)); d->vap_used = false; }   // the redo counter counts the stages of one time step
   d->pre_lo = d->pre_hi = 0;
   d->entry_marked = false;
   if (pipe_conv && d->ev_pipe[6]) { MW_HIP(hipEventRecord(d->ev_pipe[6], d->stream)); d->entry_marked = true; }   // the coupler's arrays are ready here (see rk_stage_pipe: the row scan runs beside the strip conversion)

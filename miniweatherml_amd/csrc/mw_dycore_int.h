@@ -58,6 +58,8 @@ struct DyOpts {
   int rccl_inline = 1;         // ... the send / receive group on the caller's stream instead of a side stream of the transport's own
   int xchg_fuzz = 0;           // test aid: seeded random delays (spin kernels) around the built-in transport's sends / receives
   int debug_no_patch = 0;      // test aid: the y-face correction pass of the fused tracer stage is not launched (the negative control of the FCT tests)
+  int vapour_state = 1;        // folded supercell configuration, nens == 1, WENO-5, one-stream schedule behind k_y_all: the water vapour is advanced by k_xz_state (0: by the tracer stage; A/B)
+  int debug_vapour_redo = 0;   // test aid: every stage's redo word is set by hand -- the tracer stage recomputes the vapour in its three-tracer form
 };
 
 struct mw_dycore_s {
@@ -87,7 +89,9 @@ struct mw_dycore_s {
   int chunk_y = 0, chunk_yt = 0, chunk_z = 0, chunk_f = 0;
   bool first_cycle = false;                // the running sub-cycle is the time step's first (zero_rows_build)
   bool conv_pending = false;               // time_step: the coupler -> slab conversion is still to be done by stage 1's k_y_state
-  unsigned int *dirty = nullptr;           // two words: "a y face was scaled in this / the next fused tracer launch"
+  long long vap_last_gs = -2;              // ... the last stage (gstage) that did
+  bool vap_used = false;                   // ... some stage since the last reset of the redo counter did
+  unsigned int *dirty = nullptr;           // [0], [1]: "a y face was scaled in this / the next fused tracer launch"; [2]: scratch; [MW_VREDO_RING ..+7]: "a vapour cell of stage gs & 7 failed the limiter test"; [MW_VREDO_RING + 8]: stages of this time step that took the redo
   unsigned long long fused_launches = 0;
   unsigned char *flags = nullptr;          // fused tracer stage: per-cell "a y face of this cell was FCT-scaled" bits
   double *zrx = nullptr;                   // ... and the message buffers of a decomposed block's map exchange (own | rW | rE | sS | sN | rS | rN)
@@ -161,6 +165,8 @@ int n_views(const mw_dycore_s *d);
 View view(const mw_dycore_s *d, int e);
 MemberOff member_off(const mw_dycore_s *d);
 
+#define MW_VREDO_RING 4                                        // first word of the vapour redo ring in mw_dycore_s::dirty (8 words + the counter)
+#define MW_DIRTY_WORDS 16
 #define MW_Y_EDGE 4                                            // rows of an edge strip of the pipelined schedule (>= 4: the converting inner launch requests coupler rows up to row_end + 3 < ny)
 
 // ---- mw_dycore.hip
@@ -179,12 +185,13 @@ int launch_y_tracers(mw_dycore_s *d, const double *S, int par, hipStream_t st, b
 // ---- mw_march_xz.hip, mw_march_tracers.hip: instantiated there for the four (STAGE, MODE) of an SSPRK3 cycle -- (1, 0), (2, 0), (3, 0), (3, 1)
 int xz_grid(mw_dycore_s *d, const DyP &p, dim3 &grid, int &chunk, int &tiles_x);
 template <int STAGE, int MODE>
-int launch_xz_state(mw_dycore_s *d, const double *S, const double *Sn, double *Sout, double dt_stage, double dt_dyn, int par, const CouplerPtrs &c);
+int launch_xz_state(mw_dycore_s *d, const double *S, const double *Sn, double *Sout, double dt_stage, double dt_dyn, int par, const CouplerPtrs &c, int vap_slot = -1);
+// (vap_slot >= 0, both launchers: the stage advances the water vapour in k_xz_state -- rk_stage_march decides -- and this is its word of the redo ring)
 int launch_xz_tracers(mw_dycore_s *d, const double *S, int par, double dt, hipStream_t st);
 template <int STAGE, int MODE>
 int launch_tracer_update(mw_dycore_s *d, const double *Sstar, const double *Sn, double *Sout, double dt_dyn, const CouplerPtrs &c, hipStream_t st);
 template <int STAGE, int MODE>
-int launch_tracers_fused(mw_dycore_s *d, const double *S, const double *Sn, double *Sout, int par, double dt, double dt_dyn, const CouplerPtrs &c, hipStream_t st);
+int launch_tracers_fused(mw_dycore_s *d, const double *S, const double *Sn, double *Sout, int par, double dt, double dt_dyn, const CouplerPtrs &c, hipStream_t st, int vap_slot = -1);
 // ---- mw_march_sched.hip
 int rk_cycle_march(mw_dycore_s *d, double **Q, double dt_dyn, bool last, const CouplerPtrs &c);
 void zero_rows_forget(mw_dycore_s *d, const double *S);

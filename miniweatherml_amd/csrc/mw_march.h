@@ -1207,6 +1207,66 @@ __device__ __forceinline__ void x_neighbours(double c0, const double *__restrict
   } else { m2 = lvl[om2]; m1 = lvl[om1]; p1 = lvl[op1]; p2 = lvl[op2]; }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The statements of the tracer stage that two kernels evaluate: k_tracers_fused (S2 / S3) for every tracer, and k_xz_state's vapour form
+// (VAP) for the water vapour it advances beside the state variables.  One definition each, contraction off inside: both kernels produce
+// the same bits (a `#pragma clang fp contract` binds lexically; these helpers carry their own).
+// ---------------------------------------------------------------------------------------------------------------
+// what leaves a cell through the face pair (f_lo, f_hi) of one direction, per unit volume (:506-511)
+__device__ __forceinline__ double tr_out_pair(double f_hi, double f_lo, double rd) {
+#pragma clang fp contract(off)
+  return (fmax(f_hi, 0.0) - fmin(f_lo, 0.0)) * rd;
+}
+__device__ __forceinline__ double tr_out_xy(double out_x, double out_y) {
+#pragma clang fp contract(off)
+  return out_x + out_y;
+}
+__device__ __forceinline__ double tr_mass_available(double q, double rho) {
+#pragma clang fp contract(off)
+  return fmax(q * rho, 0.0);
+}
+__device__ __forceinline__ double tr_mass_out(double out_xy, double out_z, double dt) {
+#pragma clang fp contract(off)
+  return (out_xy + out_z) * dt;
+}
+// x and y part of the tendency from the (scaled) faces
+__device__ __forceinline__ double tr_partial_xy(double fe, double fw, double yn, double ys, double rdx, double rdy) {
+#pragma clang fp contract(off)
+  return -(fe - fw) * rdx - (yn - ys) * rdy;
+}
+__device__ __forceinline__ double tr_tend(double P, double fz_hi, double fz_lo, double rdz) {
+#pragma clang fp contract(off)
+  return P - (fz_hi - fz_lo) * rdz;
+}
+// SSPRK3 combine + clip (D11 / D12) of the conserved tracer density
+template <int STAGE>
+__device__ __forceinline__ double tr_combine(double q_n, double q_s, double tend, double cdt, bool positive) {
+#pragma clang fp contract(off)
+  double qnew;
+  if (STAGE == 1)      qnew = q_n + cdt * tend;
+  else if (STAGE == 2) qnew = (3.0 / 4.0) * q_n + (1.0 / 4.0) * q_s + cdt * tend;
+  else                 qnew = (1.0 / 3.0) * q_n + (2.0 / 3.0) * q_s + cdt * tend;
+  if (positive) qnew = fmax(0.0, qnew);
+  return qnew;
+}
+// conserved density = slab value * rho, and back
+__device__ __forceinline__ double tr_times(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+// D13's temperature (:1935) from the pressure and the dry / vapour densities
+__device__ __forceinline__ double tr_d13_temp(double press, double rho_dry, double rho_v, double R_d, double R_v) {
+#pragma clang fp contract(off)
+  return press / (rho_dry * R_d + rho_v * R_v);
+}
+// what k_xz_state's vapour form needs beyond the state kernel's own arguments
+struct XzVap {
+  const double *FY;      // the vapour's y fluxes (face (k, j) at [k fyK + j fyJ + x])
+  double *cq;            // MODE 1: the coupler's water_vapor ...
+  double *crho, *ctemp;  // ... density_dry and temp: D13 is finished here where the tracer stage's storing iteration is lean
+  unsigned *redo;        // the stage's "a vapour cell failed the limiter test" word
+};
+
 // Member-co-located form (MT) of the two kernels that write the coupler's arrays in the last stage of a time step (D13), for a
 // member-major handle with 2 or 4 members.  The coupler keeps the ensemble index fastest, a marching wave holds ONE member's x row:
 // its D13 values go out as 8-byte stores nens doubles apart.  Issued from one launch per member those quarter sectors never met in
@@ -1221,14 +1281,27 @@ __device__ __forceinline__ void x_neighbours(double c0, const double *__restrict
 
 // MODE 1 (last stage of the last cycle): u, v, w also go to the coupler's arrays (D13, :1929-1932: the slab holds (rho u)/rho
 // already), so that the tracer stage, which finishes D13, neither re-reads nor re-writes them.
-template <int STAGE, bool N1, int MODE, int HPL, int K, int ORD, bool MT = false>
+// VAP (the folded supercell configuration, nens == 1, behind k_y_all): the water vapour -- tracer 0, which cannot vanish -- is advanced HERE,
+// optimistically, next to the five state variables: a z window of its own, the x reconstruction through the same DPP shifts, fluxes =
+// m_upw * upwind edge value from the face's own Riemann solve, and when a cell's top face is known the limiter test, the SSPRK3 combine, the
+// clip and the storage divide with the tracer stage's own statements (the tr_* helpers above).  No neighbour's multiplier enters: a cell
+// that fails the limiter test ORs the stage's word va.redo, and k_tracers_fused<.., VS = 1> then redoes the stage's vapour with its VS = 0
+// three-tracer form from the untouched inputs.  With the word clear every multiplier of the stage's vapour is exactly 1 and what is stored
+// here is bit for bit what the tracer stage stores.  MODE 1: where the tracer kernel's iteration that stores the cell is LEAN by the stage's
+// row map (word min(k + 2, nz - 1) of the row, the tile's segment mask: cloud and rain are and stay zero there) this kernel finishes D13
+// itself -- water_vapor, density_dry and temp from registers -- and the tracer kernel has nothing to do for the cell; elsewhere (full
+// iterations, or no maps) it stores water_vapor only and the tracer kernel finishes D13, reading the vapour back.  Its per-cell carries and its z window live in LDS behind the background table (dynamic LDS).
+// WENO-5 only.  (Tried at WENO-3 too: weno3_edges_fast leaves the compiler a choice of which product of a sum of two it contracts, the two
+// kernels' x reconstructions chose differently and a wind-torn vapour field differed in its last bit -- that order keeps the tracer stage.)
+template <int STAGE, bool N1, int MODE, int HPL, int K, int ORD, bool MT = false, bool VAP = false>
 __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__restrict__ S, const double *__restrict__ Sn,
                                                   double *__restrict__ Sout, double *__restrict__ MX, double *__restrict__ MZ,
                                                   unsigned char *__restrict__ UPX, unsigned char *__restrict__ UPZ,
                                                   const double *__restrict__ tendY, double dt_stage, double dt_dyn, int chunk,
                                                   int tiles_x, double *__restrict__ cu, double *__restrict__ cv, double *__restrict__ cw,
-                                                  MemberOff mo) {
+                                                  MemberOff mo, XzVap va) {
   static_assert(!MT || (N1 && HPL && MODE == 1), "the member-co-located form is the D13 variant of the nens == 1 kernel");
+  static_assert(!VAP || (N1 && HPL && K == 1 && !MT && ORD == 5), "the vapour form exists for the folded supercell configuration with nens == 1, WENO-5");
   constexpr int HS = (ORD - 1) / 2;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   int mt_e = 0, mt_sub = 0;
@@ -1258,11 +1331,16 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
     else for (int i = threadIdx.x; i < nrow * 8; i += 256) lds_hp[i] = p.hypk[(long long)g.kstart * 8 + i];     // (nens == 1: row k at k*8)
     if (threadIdx.x < 8) {
       const double cdt = (STAGE == 1) ? dt_dyn : (STAGE == 2) ? (1.0 / 4.0) * dt_dyn : (2.0 / 3.0) * dt_dyn;
-      lds_c[threadIdx.x] = threadIdx.x == 0 ? p.rdx : threadIdx.x == 1 ? p.rdz : threadIdx.x == 2 ? cdt : threadIdx.x == 3 ? -p.grav : 0.0;
+      lds_c[threadIdx.x] = threadIdx.x == 0 ? p.rdx : threadIdx.x == 1 ? p.rdz : threadIdx.x == 2 ? cdt : threadIdx.x == 3 ? -p.grav :
+                           (VAP && threadIdx.x == 4) ? p.rdy : (VAP && threadIdx.x == 5) ? dt_stage : 0.0;
     }
     __syncthreads();
   }
   if (!g.valid) return;
+  // (VAP: the vapour's carries behind the chunk + 2 table rows, one private slot each per thread: the x + y part of the tendency [0, 1] and
+  //  out_x + out_y of the limiter test [2, 3], both by level parity -- cell k's are parked as soon as the level's loads have landed, while
+  //  cell k-1's are still to be read, so that the x flux and the two y fluxes are dead before the finalisation -- and the lower z-face flux [4])
+  double *lds_q = lds_hp_all + (chunk + 2) * 8 + threadIdx.x;
   const int n = g.n, lane = g.lane, NXI = g.NXI, j = g.j, q = g.q, e = g.e;
   const double *col = S + (long long)(j + p.HY) * p.sJ + (long long)p.HX * n + g.qa;           // level k at col + (k+HZ)*sK
   const long long cell0 = (long long)j * NXI + g.qc;                                           // + k*ny*NXI
@@ -1278,8 +1356,27 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
 #pragma unroll
     for (int s = 0; s < ORD; s++) w[v][s] = load_zlevel<K>(p, col + (long long)v * p.sV, g.kstart - HS + s, v == idW);
   }
+  // (WENO-5: the vapour's z window is a ring of five LDS slots per thread behind the carries -- the kernel has no ten VGPRs left for it, and the
+  //  five window moves per level go with it.  Level kl lives in slot (kl + ORD) % ORD; qr = the slot of the window's lowest level, k - HS.)
+  // (MODE 1: the x segments of the row maps that the tracer kernel's wave for this tile overlaps -- its lanes, halo lanes and patch cells)
+  const bool vzq_on = VAP && MODE == 1 && (p.zq != nullptr) && p.zero_skip;
+  unsigned vzseg = 0;
+  if (VAP && MODE == 1) { const int tx_ = (q + (HS + 1) - lane) ; vzseg = zr_seg_mask(tx_ - (HS + 2), tx_ - (HS + 1) + 63 + 1, NXI, p.wrap_x != 0); }
+  double wq[ORD], nxtq = 0, ctq = 0;
+  int qr = (g.kstart - HS + ORD) % ORD;
+#define MW_QSLOT(s_) (lds_q[(5 + ((qr + (s_)) >= ORD ? qr + (s_) - ORD : qr + (s_))) * 256])
+  if (VAP) {
+    lds_q[0] = 0; lds_q[256] = 0; lds_q[512] = 0; lds_q[768] = 0; lds_q[1024] = 0;
+#pragma unroll
+    for (int s = 0; s < ORD; s++) wq[s] = load_zlevel<K>(p, col + (long long)5 * p.sV, g.kstart - HS + s, false);
+  }
 #pragma unroll
   for (int v = 0; v < 5; v++) landed(w[v]);
+  if (VAP) landed(wq);
+  if (VAP) {
+#pragma unroll
+    for (int s = 0; s < ORD; s++) MW_QSLOT(s) = wq[s];
+  }
   for (int k = g.kstart; k <= g.kb; k++) {
     const bool top = (k == p.nz);                              // only the boundary face nz, no cell to reconstruct
     const bool xwork = (k >= g.ka) && (k < g.kb);              // cells of this chunk (ghost levels only do z)
@@ -1290,6 +1387,7 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
       const int kn = min(k + HS + 1, p.nz + p.HZ - 1);
 #pragma unroll
       for (int v = 0; v < 5; v++) nxt[v] = load_zlevel<K>(p, col + (long long)v * p.sV, kn, v == idW);
+      if (VAP) nxtq = load_zlevel<K>(p, col + (long long)5 * p.sV, kn, false);
     }
     // (unconditional, at levels clamped into the chunk: a ghost iteration loads values nobody uses, and no default values have to be
     //  materialised for a skipped load -- ten v_mov_b64 per level)
@@ -1306,13 +1404,21 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
       for (int l = 0; l < 5; l++) tyv[l] = tendY[(long long)l * p.nC + cell0 + (long long)kxc * planeC];
     }
     if (Cf<K>::immersed(p)) immv = p.imm[cpl(p, cell0 + (long long)kfc * planeC)];
+    bool vlean = false;                                        // VAP, MODE 1: the tracer kernel's storing iteration of cell k-1 is lean
+    if (VAP && MODE == 1 && vzq_on) vlean = (p.zq[(long long)min(kfc + 2, p.nz - 1) * p.zq_ld + j + MW_ZR_HALO] & vzseg) == 0u;
+    double qnv = 0, fysq = 0, fynq = 0;                        // VAP: q^n of the vapour (level k-1), its y fluxes south / north of cell k
+    if (VAP) {
+      if (STAGE != 1) qnv = Sn[(long long)5 * p.sV + slab0 + (long long)(kfc + p.HZ) * p.sK];
+      const double *fy = va.FY + (long long)kxc * p.fyK + (long long)j * p.fyJ + g.qc;
+      fysq = fy[0]; fynq = fy[p.fyJ];
+    }
     double hpl[8];
     if (HPL) {
 #pragma unroll
       for (int f = 0; f < 8; f++) hpl[f] = lds_hp[(k - g.kstart) * 8 + f];
     }
     // ------------------------------------------------ X direction (cell k = window centre)
-    double fxs[5];
+    double fxs[5], fxq = 0;
     int upx = 0;
     if (xwork) {
       const double *hp = p.hypk + (long long)(k * n + e) * 8;
@@ -1351,6 +1457,15 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
       fxs[idR] = fs.m_upw; fxs[idU] = fn; fxs[idT] = fT;
       fxs[idV] = fs.m_upw * (up ? we[idV] : Lv[idV]);
       fxs[idW] = fs.m_upw * (up ? we[idW] : Lv[idW]);
+      if (VAP) {                                               // the vapour's x flux, as k_tracers_fused S1 forms it
+        const double c0 = MW_QSLOT(HS);
+        double m2, m1, p1, p2, weq, eeq;
+        m1 = from_west<true>(c0, lane, n); p1 = from_east<true>(c0, lane, n);
+        m2 = from_west<true>(m1, lane, n); p2 = from_east<true>(p1, lane, n);
+        weno5_edges_fast(m2, m1, c0, p1, p2, weq, eeq);
+        const double Lq = from_west<N1>(eeq, lane, n);
+        fxq = fs.m_upw * (up ? weq : Lq);
+      }
       upx = up;                                                // (stored below, behind landed())
     }
     // ------------------------------------------------ Z direction: reconstruct cell k, solve face k
@@ -1361,7 +1476,7 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
     for (int v = 0; v < 5; v++) weno_window_edges<ORD>(w[v], be[v], te[v]);
     // (also on the ghost iteration below the chunk, whose face belongs to the chunk underneath: its flux is never stored and never
     //  enters a tendency -- the first cell that is finalised is ka, with the faces ka and ka + 1)
-    double fzs[5];
+    double fzs[5], fzq = 0, teq = 0;
     int upz = 0;
     {
       const double *hp = p.hypk + (long long)(k * n + e) * 8;
@@ -1381,10 +1496,27 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
       fzs[idR] = fs.m_upw; fzs[idW] = fn; fzs[idT] = fT;
       fzs[idU] = fs.m_upw * (up ? be[idU] : ct[idU]);
       fzs[idV] = fs.m_upw * (up ? be[idV] : ct[idV]);
+      if (VAP) {
+#pragma unroll
+        for (int s = 0; s < ORD; s++) wq[s] = MW_QSLOT(s);
+        double beq; weno_window_edges<ORD>(wq, beq, teq); fzq = fs.m_upw * (up ? beq : ctq);
+      }
       upz = up;
     }
     // ------------------------------------------------ all loads of this iteration have landed (see landed()); its stores follow
     landed(nxt); landed(snv); landed(tyv); landed(immv);
+    if (VAP) {
+      landed(nxtq); landed(qnv); landed(fysq); landed(fynq);
+      // level k + HS + 1 takes the slot of level k - HS.  Safe HERE only because nobody reads slot 0 any more in this iteration: the z
+      // reconstruction above has read all five, and the finalisation below reads slot wi = HS - 1 = 1 (WENO-5; at WENO-3 wi would be 0 and
+      // this store would have to move behind the finalisation -- the static_assert on ORD stands guard)
+      if (!top) MW_QSLOT(0) = nxtq;
+      if (xwork) {
+        const double feq = from_east<N1>(fxq, lane, n);
+        lds_q[(k & 1) * 256] = tr_partial_xy(feq, fxq, fynq, fysq, lds_c[0], lds_c[4]);
+        lds_q[(2 + (k & 1)) * 256] = tr_out_xy(tr_out_pair(feq, fxq, lds_c[0]), tr_out_pair(fynq, fysq, lds_c[4]));
+      }
+    }
     if (xwork && g.owns_face && (g.owns_cell || q >= NXI)) {
       const long long fo = (long long)k * p.fxK + (long long)j * p.fxJ + q;
       MX[fo] = fxs[idR];  UPX[fo] = (unsigned char)upx;
@@ -1408,6 +1540,8 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
       double xpart[5], fzprev[5];                              // the LDS reads in one batch: one exposed LDS latency, not five
 #pragma unroll
       for (int l = 0; l < 5; l++) { xpart[l] = lds_xpart[l][threadIdx.x]; fzprev[l] = lds_fzprev[l][threadIdx.x]; }
+      double Pq = 0, oxyq = 0, fzpq = 0, rho_new_q = 0, press_q = 0;
+      if (VAP) { Pq = lds_q[(kc & 1) * 256]; oxyq = lds_q[(2 + (kc & 1)) * 256]; fzpq = lds_q[1024]; }
 #pragma unroll
       for (int l = 0; l < 5; l++) {
         double raw_s = w[l][wi];
@@ -1427,6 +1561,7 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
         else if (STAGE == 2) qnew = (3.0 / 4.0) * q_n + (1.0 / 4.0) * q_s + cdt * tend;
         else                 qnew = (1.0 / 3.0) * q_n + (2.0 / 3.0) * q_s + cdt * tend;
         if (l == idR) inv_rho_new = fast_rcp(qnew + hyc);
+        if (VAP && MODE == 1 && l == idR) rho_new_q = qnew + hyc;
         double stored = (l == idR || l == idT) ? qnew : qnew * inv_rho_new;
         // (MODE 1: what the result slab's (rho theta)' slot is read for afterwards is D13's pressure, :1935 -- by the tracer stage of
         //  this stage and its correction pass; the next time_step starts from the coupler's fields.  The series is evaluated HERE,
@@ -1435,6 +1570,7 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
         if (MODE == 1 && l == idT) {
           const double *hq = HPL ? lds_hp + (kc - g.kstart) * 8 : p.hypk + (long long)(kc * n + e) * 8;
           stored = pressure_fast<K>(p, qnew, hq[1], hq[2], hq[3]);
+          if (VAP) press_q = stored;
         }
         // (MODE 1, the last stage of a time step: u, v, w go to the coupler's arrays only.  Nobody reads the result slab's velocities
         //  any more -- the tracer stage of this stage needs rho' and (rho theta)', and the next time_step starts from the coupler's
@@ -1442,6 +1578,24 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
         if (g.owns_cell && !(MODE == 1 && (l == idU || l == idV || l == idW))) so[(long long)l * p.sV] = stored;
         if (MODE == 1 && g.owns_cell && (l == idU || l == idV || l == idW))
           (l == idU ? cu : l == idV ? cv : cw)[cpl(p, cell0 + (long long)kc * planeC)] = stored;
+      }
+      if (VAP) {                                               // cell k-1 of the vapour: k_tracers_fused's S2 test and S3 update, every multiplier taken as 1
+        const double qs_raw = MW_QSLOT(wi);
+        const double mass_available = tr_mass_available(qs_raw, rho_s);
+        const double mass_out = tr_mass_out(oxyq, tr_out_pair(fzq, fzpq, lds_c[1]), lds_c[5]);
+        if (__builtin_expect(g.owns_cell && mass_out > mass_available, 0)) *va.redo = 1u;
+        const double q_s = tr_times(qs_raw, rho_s);
+        const double q_n = (STAGE == 1) ? q_s : tr_times(qnv, rho_n);
+        const double qnew = tr_combine<STAGE>(q_n, q_s, tr_tend(Pq, fzq, fzpq, lds_c[1]), lds_c[2], true);
+        if (g.owns_cell) {
+          if (MODE == 0) so[(long long)5 * p.sV] = tr_times(qnew, inv_rho_new);
+          else           va.cq[cpl(p, cell0 + (long long)kc * planeC)] = qnew;
+          if (MODE == 1 && vlean) {                              // D13 with cloud and rain zero: k_tracers_fused S3's statements, rho_dry -= vapour first
+            const double rho_dry = rho_new_q - qnew;
+            va.crho[cpl(p, cell0 + (long long)kc * planeC)] = rho_dry;
+            va.ctemp[cpl(p, cell0 + (long long)kc * planeC)] = tr_d13_temp(press_q, rho_dry, qnew, p.R_d, p.R_v);
+          }
+        }
       }
     }
     // ------------------------------------------------ carries for the next level
@@ -1452,6 +1606,7 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
         lds_xpart[l][threadIdx.x] = -(fe - fxs[l]) * (HPL ? lds_c[0] : p.rdx) + tyv[l];
       }
     }
+    if (VAP) lds_q[1024] = fzq;
 #pragma unroll
     for (int l = 0; l < 5; l++) lds_fzprev[l][threadIdx.x] = fzs[l];
     if (!top) {
@@ -1462,8 +1617,13 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
         for (int s = 0; s + 1 < ORD; s++) w[v][s] = w[v][s + 1];
         w[v][ORD - 1] = nxt[v];
       }
+      if (VAP) {
+        ctq = teq;
+        qr = (qr + 1 == ORD) ? 0 : qr + 1;                     // (the entering level is in its slot already)
+      }
     }
   }
+#undef MW_QSLOT
 }
 
 // XZ pass, tracers, with the FCT positivity step (D10, :498-516) folded in.
@@ -1678,14 +1838,27 @@ __global__ __launch_bounds__(256) void k_tracer_update(DyP p, const double *Ssta
 //   reconstructions at k = ka-2 and kb+1, S2 / S3 before their first cell -- save 1 % at run time but cost 30-40 VGPRs (spills in
 //   the MODE 1 variant) and the kernel as a whole became 15 % slower.  The loop body stays branch-free.)
 // ---------------------------------------------------------------------------------------------------------------
-template <int STAGE, int MODE, int T, bool N1, int K, int ORD, bool MT = false>
+//   VS = 1 (the folded supercell configuration behind k_xz_state<.., VAP>): tracer 0, the water vapour, has been advanced by the state kernel.
+//   With the stage's word vr[vslot] clear the kernel works on cloud and rain only -- FULL iterations on tracers 1 and 2, LEAN ones on nothing
+//   (their flag bytes are still stored: k_tracer_patch scans the bytes of neighbouring rows, none may be stale); D13 reads the vapour back.
+//   With the word set (a vapour cell failed the limiter test) it takes the VS = 0 (three-tracer) bodies and overwrites what the state kernel
+//   stored: the inputs are untouched, so the redo is exact.  One wave-uniform branch per iteration, no host synchronisation.
+//   Thread 0 of the launch clears the next stage's word and counts the stages that took the redo (vr[8]; mw_debug_vapour_redo).
+template <int STAGE, int MODE, int T, bool N1, int K, int ORD, bool MT = false, int VS = 0>
 __global__ __launch_bounds__(256, 2) void k_tracers_fused(DyP p, const double *__restrict__ S, const double *__restrict__ Sn, double *Sout,
                                                        const double *__restrict__ FY, const double *__restrict__ MX,
                                                        const double *__restrict__ MZ, const unsigned char *__restrict__ UPX,
                                                        const unsigned char *__restrict__ UPZ, double *__restrict__ DS,
                                                        double *__restrict__ DN, unsigned char *__restrict__ flags, unsigned int *__restrict__ dirty,
-                                                       double dt, double dt_dyn, CouplerPtrs c, int chunk, int tiles_x, int rows4, MemberOff mo) {
+                                                       double dt, double dt_dyn, CouplerPtrs c, int chunk, int tiles_x, int rows4, MemberOff mo,
+                                                       unsigned *vr, int vslot) {
   static_assert(N1 || ORD == 5, "the neighbour-load form exists for WENO-5 only");
+  static_assert(!VS || (N1 && K == 1 && T == 3 && !MT && ORD == 5), "the form without the vapour exists for the folded supercell configuration with nens == 1, WENO-5");
+  bool vredo = true;
+  if (VS) {
+    vredo = __builtin_amdgcn_readfirstlane((int)vr[vslot]) != 0;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { vr[(vslot + 1) & 7] = 0u; if (vredo) atomicAdd(&vr[8], 1u); }
+  }
   static_assert(!MT || (N1 && MODE == 1), "the member-co-located form (see MemberOff) is the D13 variant of the nens == 1 kernel");
   constexpr int HS = (ORD - 1) / 2;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -1752,6 +1925,27 @@ __global__ __launch_bounds__(256, 2) void k_tracers_fused(DyP p, const double *_
   const int k_lo = max(ka - 1, 0);                            // cells k_lo .. k_hi get all six fluxes (FCT multiplier)
   const int k_hi = min(kb, p.nz - 1);
   const int kstart = max(ka - 2, 0);
+#if MW_ZERO_SKIP
+  // VS, no redo: a wave whose iterations are all lean by the stage's row map, and that has no zeros to store over rows that may hold something
+  // (zc_mask below), has nothing to load or compute -- MODE 1: k_xz_state has finished D13 for its cells -- and leaves.  Not without its cells'
+  // flag bytes: k_tracer_patch scans the bytes of neighbouring rows whenever any y face of the stage was scaled, and a byte this wave set in an
+  // earlier stage must not be found there.  (Lane i looks at iteration kstart + i; chunks of more than 62 levels take the loop.)
+  if (VS && !vredo && (p.zq != nullptr) && p.zero_skip && kb + 1 - kstart < 64) {
+    const unsigned zseg_ = zr_seg_mask(tx * U - (hw + 1) * n, tx * U - hw * n + 63 + n, NXI, p.wrap_x != 0);
+    const int kit = kstart + lane;
+    const bool in_it = kit <= kb + 1, st_it = (kit - 2 >= ka) && (kit - 2 < kb);
+    bool busy = in_it && (p.zq[(long long)min(kit, p.nz - 1) * p.zq_ld + j + MW_ZR_HALO] & zseg_) != 0u;
+    const unsigned *zc_ = (MODE == 1) ? p.zqc : p.zqp;
+    if (zc_ != nullptr) {
+      const int kq_ = (MODE == 1) ? min(max(kit - 2, ka), kb - 1) : min(kit, p.nz - 1);
+      busy = busy || (st_it && (zc_[(long long)kq_ * p.zq_ld + j + MW_ZR_HALO] & zseg_) != 0u);
+    } else busy = true;
+    if (!__any(busy)) {
+      if (upd && do_y) for (int kp = ka; kp < kb; kp++) flags[(long long)(kp * p.ny + j) * NXI + q] = (unsigned char)0;
+      return;
+    }
+  }
+#endif
   double w[T][ORD], nxt[T], ct[T];
   double fxp[T], fzp[T], multp[T], szf[T], P[T];
   double wkm2[T];                                             // WENO-3: level k-2 has left the 3-level window and is carried instead
@@ -1822,8 +2016,9 @@ __global__ __launch_bounds__(256, 2) void k_tracers_fused(DyP p, const double *_
   // before touched (their carries are zero then): those tracers issue no load and no arithmetic, their new value is 0.  The stage's
   // row map says so (zq_mask).  ACT = the tracers the form works on; one wave-uniform branch per iteration picks the form.
   constexpr unsigned FULLM = (1u << T) - 1u, VANM = (K == 1) ? (FULLM & ~1u) : FULLM;     // (VANM = tracer_may_vanish<K>)
-  auto body = [&](auto act_c, const int k) __attribute__((always_inline)) {
-    constexpr unsigned ACT = decltype(act_c)::value;
+  // (EXT: the tracers somebody else has advanced -- their value is in place and is only read back for D13)
+  auto body = [&](auto act_c, auto ext_c, const int k) __attribute__((always_inline)) {
+    constexpr unsigned ACT = decltype(act_c)::value, EXT = decltype(ext_c)::value;
 #define MW_ACT(v_) ((ACT >> (v_)) & 1u)
     const bool cell = (k < p.nz);
     const int kp = k - 1, ku = k - 2;
@@ -1873,6 +2068,9 @@ __global__ __launch_bounds__(256, 2) void k_tracers_fused(DyP p, const double *_
       for (int v = 0; v < T; v++) if (MW_ACT(v)) qn_[v] = Sn[so + (5 + t0 + v) * p.sV];
     }
     if (MODE == 1) st_T = Sout[so + idT * p.sV];              // (u, v, w were written to the coupler by k_xz_state<3, ., 1>)
+    double qext[T];
+#pragma unroll
+    for (int v = 0; v < T; v++) { qext[v] = 0; if (MODE == 1 && ACT != 0u && ((EXT >> v) & 1u)) qext[v] = c.tr[v][cpl(p, (long long)(kuc * p.ny + j) * NXI + qm)]; }
     // nens > 1: the x-stencil neighbours of level k come from memory (issued here, with the iteration's other loads)
     double nbw2[T], nbw1[T], nbe1[T], nbe2[T];
 #pragma unroll
@@ -1946,11 +2144,11 @@ __global__ __launch_bounds__(256, 2) void k_tracers_fused(DyP p, const double *_
         double mult = 1.0;
         {
           // the cell volume dx dy dz multiplies both sides of the reference's test (:506-511) and cancels in the multiplier
-          const double mass_available = fmax(w[v][HS - 1] * rhop, 0.0);      // (window slot HS - 1 = level k-1)
-          const double out_x = (fmax(fe, 0.0) - fmin(fxp[v], 0.0)) * (LC ? lds_c[0] : p.rdx);
-          const double out_y = (fmax(fyn[v], 0.0) - fmin(fys[v], 0.0)) * (LC ? lds_c[1] : p.rdy);
-          const double out_z = (fmax(fzn[v], 0.0) - fmin(fzp[v], 0.0)) * (LC ? lds_c[2] : p.rdz);
-          const double mass_out = (out_x + out_y + out_z) * (LC ? lds_c[3] : dt);
+          const double mass_available = tr_mass_available(w[v][HS - 1], rhop);      // (window slot HS - 1 = level k-1)
+          const double out_x = tr_out_pair(fe, fxp[v], LC ? lds_c[0] : p.rdx);
+          const double out_y = tr_out_pair(fyn[v], fys[v], LC ? lds_c[1] : p.rdy);
+          const double out_z = tr_out_pair(fzn[v], fzp[v], LC ? lds_c[2] : p.rdz);
+          const double mass_out = tr_mass_out(tr_out_xy(out_x, out_y), out_z, LC ? lds_c[3] : dt);
           if (__builtin_expect(s2cell && has_mult && Cf<K>::positive(p, t0 + v) && mass_out > mass_available, 0))
             mult = mass_available / mass_out;
         }
@@ -1962,7 +2160,7 @@ __global__ __launch_bounds__(256, 2) void k_tracers_fused(DyP p, const double *_
         szn[v] = (G > 0) ? G * multp[v] : G * mult;                          // z face kp, scaled by its donor
         const double ys = (fys[v] < 0) ? fys[v] * mult : fys[v];             // outgoing y faces scaled, incoming provisional
         const double yn = (fyn[v] > 0) ? fyn[v] * mult : fyn[v];
-        Pn[v] = -(sFe - sFw) * (LC ? lds_c[0] : p.rdx) - (yn - ys) * (LC ? lds_c[1] : p.rdy);
+        Pn[v] = tr_partial_xy(sFe, sFw, yn, ys, LC ? lds_c[0] : p.rdx, LC ? lds_c[1] : p.rdy);
         if (__builtin_expect(rec && mult < 1.0, 0)) {
           if (fys[v] < 0) { DS[(long long)(5 + t0 + v) * p.fxV + (long long)kp * p.fxK + (long long)j * p.fxJ + q] = ys - fys[v]; fl |= 1u << (2 * v); }
           if (fyn[v] > 0) { DN[(long long)(5 + t0 + v) * p.fzV + (long long)kp * p.fzK + (long long)j * p.fzJ + q] = yn - fyn[v]; fl |= 2u << (2 * v); }
@@ -1972,6 +2170,8 @@ __global__ __launch_bounds__(256, 2) void k_tracers_fused(DyP p, const double *_
 #pragma unroll
       for (int v = 0; v < T; v++) if (MW_ACT(v)) { landed(nxt[v]); landed(xpn[v]); landed(qn_[v]); }   // in front of the iteration's stores (see landed())
       landed(rho_new); landed(rho_n); landed(st_T);
+#pragma unroll
+      for (int v = 0; v < T; v++) if (MODE == 1 && ACT != 0u && ((EXT >> v) & 1u)) landed(qext[v]);
       if (rec && do_y) flags[(long long)(kp * p.ny + j) * NXI + q] = (unsigned char)fl;     // 2 bits per tracer: (south, north) face scaled
       if (__builtin_expect(fl != 0u, 0)) *dirty = 1u;           // (only set inside `rec`) lets k_tracer_patch return at once when nothing was scaled
     }
@@ -1984,33 +2184,34 @@ __global__ __launch_bounds__(256, 2) void k_tracers_fused(DyP p, const double *_
       double rho_dry = rho_new, rho_v = 0;
 #pragma unroll
       for (int v = 0; v < T; v++) {
+        if ((EXT >> v) & 1u) {                                   // advanced by k_xz_state<.., VAP>: in place already
+          if (MODE == 1) { if (Cf<K>::is_wv(p, v)) rho_v = qext[v]; if (Cf<K>::adds_mass(p, v)) rho_dry -= qext[v]; }
+          continue;
+        }
         if (!MW_ACT(v)) {                                        // LEAN form: the tracer is zero and stays zero
           if (MODE == 0) { if (st && zc_store) Sout[so + (5 + t0 + v) * p.sV] = 0.0; }     // (not over a row that is zero already: see zc_mask)
           else           { if (st && zc_store) c.tr[v][cpl(p, ci)] = 0.0; }
           continue;
         }
-        const double q_s = (ORD == 3 ? wkm2[v] : w[v][0]) * rhos2;           // level k-2
-        const double q_n = (STAGE == 1) ? q_s : qn_[v] * rho_n;
-        const double tend = P[v] - (szn[v] - szf[v]) * (LC ? lds_c[2] : p.rdz);
-        double qnew;
+        const double q_s = tr_times(ORD == 3 ? wkm2[v] : w[v][0], rhos2);    // level k-2
+        const double q_n = (STAGE == 1) ? q_s : tr_times(qn_[v], rho_n);
+        const double tend = tr_tend(P[v], szn[v], szf[v], LC ? lds_c[2] : p.rdz);
         const double cdt = LC ? lds_c[4] : (STAGE == 1) ? dt_dyn : (STAGE == 2) ? (1.0 / 4.0) * dt_dyn : (2.0 / 3.0) * dt_dyn;   // (one product, as before)
-        if (STAGE == 1)      qnew = q_n + cdt * tend;
-        else if (STAGE == 2) qnew = (3.0 / 4.0) * q_n + (1.0 / 4.0) * q_s + cdt * tend;
-        else                 qnew = (1.0 / 3.0) * q_n + (2.0 / 3.0) * q_s + cdt * tend;
-        if (Cf<K>::positive(p, t0 + v)) qnew = fmax(0.0, qnew);
-        if (MODE == 0) { if (st) Sout[so + (5 + t0 + v) * p.sV] = qnew * inv_rho_new; }
+        const double qnew = tr_combine<STAGE>(q_n, q_s, tend, cdt, Cf<K>::positive(p, t0 + v));
+        if (MODE == 0) { if (st) Sout[so + (5 + t0 + v) * p.sV] = tr_times(qnew, inv_rho_new); }
         else {
           if (st) c.tr[v][cpl(p, ci)] = qnew;
           if (Cf<K>::is_wv(p, v)) rho_v = qnew;
           if (Cf<K>::adds_mass(p, v)) rho_dry -= qnew;
         }
       }
-      if (MODE == 1 && st) {
+      // (EXT != 0 and nothing active: the lean form of the kernel without the vapour -- k_xz_state<3, ., 1, .., VAP> has finished D13 for this cell)
+      if (MODE == 1 && st && !(EXT != 0u && ACT == 0u)) {
         // D13 (:1929-1935): p = C0 (rho theta)^gamma with rho theta = hy + (rho theta)' -- the same series around the hydrostatic
         // state as in the Riemann solver (device pow for large perturbations); rho*(rho theta / rho) differs from rho theta by rounding
         const double press = st_T;                             // (k_xz_state<3, ., 1> left p in the (rho theta)' slot)
         c.rho_d[cpl(p, ci)] = rho_dry;
-        c.temp[cpl(p, ci)] = press / (rho_dry * p.R_d + rho_v * p.R_v);
+        c.temp[cpl(p, ci)] = tr_d13_temp(press, rho_dry, rho_v, p.R_d, p.R_v);
       }
     }
     // ------------------------------------------------ carries
@@ -2044,8 +2245,14 @@ __global__ __launch_bounds__(256, 2) void k_tracers_fused(DyP p, const double *_
       lean = !((zq_mask >> (it & 63)) & 1ull);
       zc_store = (zc_mask >> (it & 63)) & 1ull; }
 #endif
-    if (lean) body(std::integral_constant<unsigned, (FULLM & ~VANM)>{}, k);
-    else      body(std::integral_constant<unsigned, FULLM>{}, k);
+    using M0 = std::integral_constant<unsigned, 0u>;
+    if (VS && !vredo) {                                          // tracer 0 is k_xz_state's: cloud and rain, or nothing
+      if (lean) body(M0{}, std::integral_constant<unsigned, 1u>{}, k);
+      else      body(std::integral_constant<unsigned, (FULLM & ~1u)>{}, std::integral_constant<unsigned, 1u>{}, k);
+      continue;
+    }
+    if (lean) body(std::integral_constant<unsigned, (FULLM & ~VANM)>{}, M0{}, k);
+    else      body(std::integral_constant<unsigned, FULLM>{}, M0{}, k);
   }
 }
 

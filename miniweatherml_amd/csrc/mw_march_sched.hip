@@ -66,12 +66,21 @@ static int rk_stage_march(mw_dycore_s *d, double *Sin, const double *Sn, double 
   const bool yall = y_all_ok(d) && !(conv && ((d->member_major && !mm_conv_ok) || !d->o.y_all_conv));   // y faces of state variables and tracers in one launch
   if (STAGE == 1) { if (conv) zero_rows_conv(d, Sin, false, ss); else zero_rows_forget(d, Sin); }   // (what is known about the rows of the slab that is about to be written)
   if (STAGE == 3 && MODE == 0) zero_rows_forget(d, Sout);
+  // The water vapour rides along in k_xz_state (option vapour_state): the folded supercell configuration with nens == 1 and WENO-5 on this schedule's
+  // one-stream form, behind k_y_all (the vapour's y fluxes are complete before the x/z launch starts) and in front of the fused tracer stage.
+  const bool vap = yall && d->o.vapour_state && d->fused && !d->overlap && !d->member_major && d->p.nens == 1 && d->ord == 5 && marching_config(d, d->p) == 1;
+  const int vap_slot = vap ? slot : -1;
   {
   if (conv && zero_rows_verify(d, 1, Sin, nullptr, false, c, ss)) return 1;
   if (yall) { if (halo_fill(d, Sin, 5, T, ts, 1, true) || launch_y_all(d, Sin, conv ? &c : nullptr)) return 1; }
   else if (launch_y_state(d, Sin, par, conv ? &c : nullptr)) return 1;             // y faces: m_upw, selector, y tendencies
   if (STAGE == 1 && conv) zero_rows_conv(d, Sin, true, ss);
-  if (launch_xz_state<STAGE, MODE>(d, Sin, Sn, Sout, dt_stage, dt_dyn, par, c)) return 1;   // x,z faces + finished state variables
+  if (vap) {
+    // (the word of stage gs is cleared by the tracer kernel of stage gs - 1 when that stage ran this form too; otherwise here)
+    if (d->vap_last_gs != gs - 1) MW_HIP(hipMemsetAsync(d->dirty + MW_VREDO_RING + slot, 0, sizeof(unsigned int), ss));
+    d->vap_last_gs = gs; d->vap_used = true;
+  }
+  if (launch_xz_state<STAGE, MODE>(d, Sin, Sn, Sout, dt_stage, dt_dyn, par, c, vap_slot)) return 1;   // x,z faces + finished state variables (+ the vapour)
   }
   if (STAGE == 1 && d->member_major && !d->overlap) {           // the members' maps, from the slab the y launch has just completed
     if (zero_rows_build(d, Sin, c, false, ss, d->first_cycle)) return 1;
@@ -88,7 +97,7 @@ static int rk_stage_march(mw_dycore_s *d, double *Sin, const double *Sn, double 
   if (!yall && launch_y_tracers(d, Sin, par, ts)) return 1;                   // tracer fluxes (public arrays)
   if (d->fused) {
     if (zero_rows_verify(d, 0, Sin, Sout, MODE == 1, c, ts)) return 1;
-    if (launch_tracers_fused<STAGE, MODE>(d, Sin, Sn, Sout, par, dt_stage, dt_dyn, c, ts)) return 1;   // x/z fluxes + D10 + D11/D12 (+ D13)
+    if (launch_tracers_fused<STAGE, MODE>(d, Sin, Sn, Sout, par, dt_stage, dt_dyn, c, ts, vap_slot)) return 1;   // x/z fluxes + D10 + D11/D12 (+ D13)
   } else {
     if (launch_xz_tracers(d, Sin, par, dt_stage, ts)) return 1;               // x/z fluxes + D10 (FCT)
     if (launch_tracer_update<STAGE, MODE>(d, Sin, Sn, Sout, dt_dyn, c, ts)) return 1;
@@ -475,5 +484,25 @@ long long mw_debug_zero_violations(mw_dycore_t d, unsigned long long *out4) {
   if (hipMemcpy(h, d->zviol, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   if (out4) for (int i = 0; i < 4; i++) out4[i] = h[i];
   return (long long)(h[0] + h[1] + h[2] + h[3]);
+}
+// Test aid: the fused tracer stage's per-cell flag bytes as its last launch left them (bits 2v / 2v + 1: tracer v's south / north face was
+// scaled by this cell), index (k * ny + j) * nx * nens + x.  Returns the number of cells; copies at most `cap` bytes to out_host.
+long long mw_debug_tracer_flags(mw_dycore_t d, unsigned char *out_host, long long cap) {
+  if (!d || !d->flags) return -1;
+  (void)hipStreamSynchronize(d->stream);
+  if (d->tstream) (void)hipStreamSynchronize(d->tstream);
+  const long long n = (long long)d->p.nC;
+  if (out_host && cap > 0 && hipMemcpy(out_host, d->flags, (size_t)std::min(n, cap), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return n;
+}
+// Test aid: how many RK stages of the last time step redid their water vapour in the tracer stage's three-tracer form because a cell failed the
+// limiter test in k_xz_state's vapour form (or option debug_vapour_redo set the word); 0 also when no stage ran the vapour form.  -1: null handle.
+long long mw_debug_vapour_redo(mw_dycore_t d) {
+  if (!d || !d->dirty) return -1;
+  (void)hipStreamSynchronize(d->stream);
+  if (d->tstream) (void)hipStreamSynchronize(d->tstream);
+  unsigned int n = 0;
+  if (hipMemcpy(&n, d->dirty + MW_VREDO_RING + 8, sizeof(n), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return (long long)n;
 }
 } // extern "C"

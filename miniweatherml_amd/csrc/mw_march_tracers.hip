@@ -50,18 +50,19 @@ int launch_tracer_update(mw_dycore_s *d, const double *Sstar, const double *Sn, 
   return 0;
 }
 
-template <int STAGE, int MODE, int T, bool N1, int K, int ORD = 5>
+template <int STAGE, int MODE, int T, bool N1, int K, int ORD = 5, int VS = 0>
 static void launch_tracers_fused_t(mw_dycore_s *d, const View &v, const double *S, const double *Sn, double *Sout, dim3 grid, int chunk, int tiles_x, int par,
-                                   double dt, double dt_dyn, const CouplerPtrs &c, int rows4, hipStream_t st) {
+                                   double dt, double dt_dyn, const CouplerPtrs &c, int rows4, hipStream_t st, int vap_slot) {
   const int e = v.e;
-  MW_KLAUNCH((k_tracers_fused<STAGE, MODE, T, N1, K, ORD>), grid, dim3(256), 0, st, v.p, v.S(S), v.S(Sn), v.S(Sout), d->FY + e * v.f[1],
+  MW_KLAUNCH((k_tracers_fused<STAGE, MODE, T, N1, K, ORD, false, VS>), grid, dim3(256), 0, st, v.p, v.S(S), v.S(Sn), v.S(Sout), d->FY + e * v.f[1],
                      d->M[par][0] + e * v.m[0], d->M[par][2] + e * v.m[2], d->UP[par][0] + e * v.m[0], d->UP[par][2] + e * v.m[2],
-                     d->FX + e * v.f[0], d->FZ + e * v.f[2], d->flags + e * v.cells, d->dirty + (d->fused_launches & 1), dt, dt_dyn, c, chunk, tiles_x, rows4, MemberOff());
+                     d->FX + e * v.f[0], d->FZ + e * v.f[2], d->flags + e * v.cells, d->dirty + (d->fused_launches & 1), dt, dt_dyn, c, chunk, tiles_x, rows4, MemberOff(),
+                     VS ? d->dirty + MW_VREDO_RING : nullptr, VS ? vap_slot : 0);
 }
 // x/z tracer fluxes + FCT + update in one kernel, then the (normally empty) y-face correction
 template <int STAGE, int MODE>
 int launch_tracers_fused(mw_dycore_s *d, const double *S, const double *Sn, double *Sout, int par, double dt, double dt_dyn,
-                                const CouplerPtrs &c, hipStream_t st) {
+                                const CouplerPtrs &c, hipStream_t st, int vap_slot) {
   {
     ProfScope ps(d, 7, st);
     bool direct = false;
@@ -77,7 +78,7 @@ int launch_tracers_fused(mw_dycore_s *d, const double *S, const double *Sn, doub
 #define MW_FUSED_MT(TT) case TT: MW_FUSED_MTK(TT, 0) break;
 #define MW_FUSED_MTK(TT, K_) { if (d->ord == 3) MW_FUSED_MTO(TT, K_, 3); else MW_FUSED_MTO(TT, K_, 5); }
 #define MW_FUSED_MTO(TT, K_, O_) MW_KLAUNCH((k_tracers_fused<3, 1, TT, true, K_, O_, true>), grid, dim3(256), 0, st, p, S, Sn, Sout, d->FY, d->M[par][0], d->M[par][2], \
-                                 d->UP[par][0], d->UP[par][2], d->FX, d->FZ, d->flags, d->dirty + (d->fused_launches & 1), dt, dt_dyn, c, chunk, tiles_x, 0, mo)
+                                 d->UP[par][0], d->UP[par][2], d->FX, d->FZ, d->flags, d->dirty + (d->fused_launches & 1), dt, dt_dyn, c, chunk, tiles_x, 0, mo, nullptr, 0)
       if (marching_config(d, p) == 1) MW_FUSED_MTK(3, 1)
       else switch (p.nt) { MW_FUSED_MT(1) MW_FUSED_MT(2) MW_FUSED_MT(3) MW_FUSED_MT(4) default: MW_FAIL("fused tracer stage needs 1..4 tracers"); }
 #undef MW_FUSED_MT
@@ -94,13 +95,15 @@ int launch_tracers_fused(mw_dycore_s *d, const double *S, const double *Sn, doub
       const long long waves = (long long)p.ny * tiles_x;
       const int chunk = d->chunk_f ? d->chunk_f : (d->chunk_f = balanced_chunk(d, p.nz, waves, d->o.chunk_f, 10000, 2, 4.5, true));
       dim3 grid(rows4 ? (unsigned)(((p.ny + 3) / 4) * tiles_x) : (unsigned)((waves + 3) / 4), (unsigned)((p.nz + chunk - 1) / chunk));
-#define MW_FUSED_ARGS d, v, S, Sn, Sout, grid, chunk, tiles_x, par, dt, dt_dyn, c, rows4, st
+#define MW_FUSED_ARGS d, v, S, Sn, Sout, grid, chunk, tiles_x, par, dt, dt_dyn, c, rows4, st, vap_slot
 #define MW_FUSED_CASE(TT) \
       case TT: if (p.nens != 1)     launch_tracers_fused_t<STAGE, MODE, TT, false, 0>(MW_FUSED_ARGS); \
                else if (d->ord == 3) launch_tracers_fused_t<STAGE, MODE, TT, true, 0, 3>(MW_FUSED_ARGS); \
                else                  launch_tracers_fused_t<STAGE, MODE, TT, true, 0>(MW_FUSED_ARGS); break;
       const int K = marching_config(d, p);
-      if (K == 1)      { if (d->ord == 3) launch_tracers_fused_t<STAGE, MODE, 3, true, 1, 3>(MW_FUSED_ARGS); else launch_tracers_fused_t<STAGE, MODE, 3, true, 1>(MW_FUSED_ARGS); }
+      if (K == 1 && vap_slot >= 0) {                               // the vapour was advanced by k_xz_state<.., VAP>: cloud and rain here, or the redo
+        launch_tracers_fused_t<STAGE, MODE, 3, true, 1, 5, 1>(MW_FUSED_ARGS); }
+      else if (K == 1) { if (d->ord == 3) launch_tracers_fused_t<STAGE, MODE, 3, true, 1, 3>(MW_FUSED_ARGS); else launch_tracers_fused_t<STAGE, MODE, 3, true, 1>(MW_FUSED_ARGS); }
       else if (K == 2) { if (d->ord == 3) launch_tracers_fused_t<STAGE, MODE, 1, true, 2, 3>(MW_FUSED_ARGS); else launch_tracers_fused_t<STAGE, MODE, 1, true, 2>(MW_FUSED_ARGS); }
       else switch (p.nt) { MW_FUSED_CASE(1) MW_FUSED_CASE(2) MW_FUSED_CASE(3) MW_FUSED_CASE(4) default: MW_FAIL("fused tracer stage needs 1..4 tracers"); }
 #undef MW_FUSED_CASE
@@ -129,10 +132,10 @@ int launch_tracers_fused(mw_dycore_s *d, const double *S, const double *Sn, doub
 
 // the four (STAGE, MODE) of an SSPRK3 cycle (rk_stage_march / rk_stage_pipe in mw_march_sched.hip)
 template int launch_tracer_update<1, 0>(mw_dycore_s *, const double *, const double *, double *, double, const CouplerPtrs &, hipStream_t);
-template int launch_tracers_fused<1, 0>(mw_dycore_s *, const double *, const double *, double *, int, double, double, const CouplerPtrs &, hipStream_t);
+template int launch_tracers_fused<1, 0>(mw_dycore_s *, const double *, const double *, double *, int, double, double, const CouplerPtrs &, hipStream_t, int);
 template int launch_tracer_update<2, 0>(mw_dycore_s *, const double *, const double *, double *, double, const CouplerPtrs &, hipStream_t);
-template int launch_tracers_fused<2, 0>(mw_dycore_s *, const double *, const double *, double *, int, double, double, const CouplerPtrs &, hipStream_t);
+template int launch_tracers_fused<2, 0>(mw_dycore_s *, const double *, const double *, double *, int, double, double, const CouplerPtrs &, hipStream_t, int);
 template int launch_tracer_update<3, 0>(mw_dycore_s *, const double *, const double *, double *, double, const CouplerPtrs &, hipStream_t);
-template int launch_tracers_fused<3, 0>(mw_dycore_s *, const double *, const double *, double *, int, double, double, const CouplerPtrs &, hipStream_t);
+template int launch_tracers_fused<3, 0>(mw_dycore_s *, const double *, const double *, double *, int, double, double, const CouplerPtrs &, hipStream_t, int);
 template int launch_tracer_update<3, 1>(mw_dycore_s *, const double *, const double *, double *, double, const CouplerPtrs &, hipStream_t);
-template int launch_tracers_fused<3, 1>(mw_dycore_s *, const double *, const double *, double *, int, double, double, const CouplerPtrs &, hipStream_t);
+template int launch_tracers_fused<3, 1>(mw_dycore_s *, const double *, const double *, double *, int, double, double, const CouplerPtrs &, hipStream_t, int);

@@ -25,7 +25,7 @@ int xz_grid(mw_dycore_s *d, const DyP &p, dim3 &grid, int &chunk, int &tiles_x) 
 
 template <int STAGE, int MODE>
 int launch_xz_state(mw_dycore_s *d, const double *S, const double *Sn, double *Sout, double dt_stage, double dt_dyn, int par,
-                           const CouplerPtrs &c) {
+                           const CouplerPtrs &c, int vap_slot) {
   ProfScope ps(d, 0);
   if constexpr (STAGE == 3 && MODE == 1) {
     if (d->mm_direct) {                                         // all members in one launch: workgroup = the nens members of 4 / nens tiles
@@ -43,7 +43,7 @@ int launch_xz_state(mw_dycore_s *d, const double *S, const double *Sn, double *S
       const size_t lds = (size_t)(chunk + 2) * 64 * 4;
 #define MW_XZ_MT(K_) { if (d->ord == 3) MW_XZ_MTO(K_, 3); else MW_XZ_MTO(K_, 5); }
 #define MW_XZ_MTO(K_, O_) MW_KLAUNCH((k_xz_state<3, true, 1, 1, K_, O_, true>), grid, dim3(256), lds, d->stream, p, S, Sn, Sout, d->M[par][0], d->M[par][2], \
-                                        d->UP[par][0], d->UP[par][2], d->tendY, dt_stage, dt_dyn, chunk, tiles_x, c.u, c.v, c.w, mo)
+                                        d->UP[par][0], d->UP[par][2], d->tendY, dt_stage, dt_dyn, chunk, tiles_x, c.u, c.v, c.w, mo, XzVap())
       if (marching_config(d, p) == 1) MW_XZ_MT(1) else MW_XZ_MT(0)
 #undef MW_XZ_MT
 #undef MW_XZ_MTO
@@ -61,9 +61,18 @@ int launch_xz_state(mw_dycore_s *d, const double *S, const double *Sn, double *S
     // nens == 1 (also: one member of a member-major handle): the per-level background values come through LDS
     // (k_xz_state<.., HPL = 1>; dynamic LDS = the chunk's rows)
 #define MW_XZ(N1_, HPL_, K_, O_, lds) MW_KLAUNCH((k_xz_state<STAGE, N1_, MODE, HPL_, K_, O_>), grid, dim3(256), (lds), d->stream, p, v.S(S), v.S(Sn), v.S(Sout), \
-                                                 MX, MZ, UX, UZ, tY, dt_stage, dt_dyn, chunk, tiles_x, c.u, c.v, c.w, MemberOff())
+                                                 MX, MZ, UX, UZ, tY, dt_stage, dt_dyn, chunk, tiles_x, c.u, c.v, c.w, MemberOff(), XzVap())
 #define MW_XZ_K(K_) { if (d->ord == 3) MW_XZ(true, 1, K_, 3, hpl_bytes); else MW_XZ(true, 1, K_, 5, hpl_bytes); }
     const size_t hpl_bytes = (size_t)(chunk + 2) * 64;
+    if (vap_slot >= 0) {
+      // the water vapour rides along (rk_stage_march decided: K = 1, nens == 1, WENO-5, behind k_y_all): its per-thread carries behind the table rows
+      const XzVap va = {d->FY + (long long)5 * p.fyV, c.tr[0], c.rho_d, c.temp, d->dirty + MW_VREDO_RING + vap_slot};
+      const size_t lds = hpl_bytes + (size_t)(5 + 5) * 256 * sizeof(double);   // (five carry slots + the five slots of the window ring)
+      MW_KLAUNCH((k_xz_state<STAGE, true, MODE, 1, 1, 5, false, true>), grid, dim3(256), lds, d->stream, p, v.S(S), v.S(Sn), v.S(Sout),
+                 MX, MZ, UX, UZ, tY, dt_stage, dt_dyn, chunk, tiles_x, c.u, c.v, c.w, MemberOff(), va);
+      // (test aid debug_vapour_redo: the stage's word set by hand, so that the tracer stage redoes a vapour that needs no redo)
+      if (d->o.debug_vapour_redo) MW_HIP(hipMemsetAsync(d->dirty + MW_VREDO_RING + vap_slot, 0xFF, sizeof(unsigned int), d->stream));
+    } else
     if (p.nens == 1) {
       switch (marching_config(d, p)) { case 1: MW_XZ_K(1) break; case 2: MW_XZ_K(2) break; default: MW_XZ_K(0) break; }
     } else MW_XZ(false, 0, 0, 5, 0);                          // (the fused-layout form for nens > 1: WENO-5 only, see time_step)
@@ -75,7 +84,7 @@ int launch_xz_state(mw_dycore_s *d, const double *S, const double *Sn, double *S
 }
 
 // the four (STAGE, MODE) of an SSPRK3 cycle (rk_stage_march / rk_stage_pipe in mw_march_sched.hip)
-template int launch_xz_state<1, 0>(mw_dycore_s *, const double *, const double *, double *, double, double, int, const CouplerPtrs &);
-template int launch_xz_state<2, 0>(mw_dycore_s *, const double *, const double *, double *, double, double, int, const CouplerPtrs &);
-template int launch_xz_state<3, 0>(mw_dycore_s *, const double *, const double *, double *, double, double, int, const CouplerPtrs &);
-template int launch_xz_state<3, 1>(mw_dycore_s *, const double *, const double *, double *, double, double, int, const CouplerPtrs &);
+template int launch_xz_state<1, 0>(mw_dycore_s *, const double *, const double *, double *, double, double, int, const CouplerPtrs &, int);
+template int launch_xz_state<2, 0>(mw_dycore_s *, const double *, const double *, double *, double, double, int, const CouplerPtrs &, int);
+template int launch_xz_state<3, 0>(mw_dycore_s *, const double *, const double *, double *, double, double, int, const CouplerPtrs &, int);
+template int launch_xz_state<3, 1>(mw_dycore_s *, const double *, const double *, double *, double, double, int, const CouplerPtrs &, int);

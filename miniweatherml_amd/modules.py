@@ -230,6 +230,19 @@ class Dynamics_Euler_Stratified_WenoFV:
         n = capi.lib().mw_debug_zero_violations(self.h, out)
         return n, [int(v) for v in out]
 
+    def vapour_redo(self):
+        """How many RK stages of the last time step redid their water vapour in the tracer stage's three-tracer form (mw_debug_vapour_redo; a
+        test aid of option vapour_state)."""
+        return int(capi.lib().mw_debug_vapour_redo(self.h))
+
+    def tracer_flags(self):
+        """The fused tracer stage's per-cell flag bytes as its last launch left them (mw_debug_tracer_flags; a test aid): uint8, cell (k, j, x) at (k * ny + j) * nx * nens + x."""
+        n = int(capi.lib().mw_debug_tracer_flags(self.h, None, 0))
+        buf = np.zeros(max(n, 0), dtype=np.uint8)
+        if n < 0 or capi.lib().mw_debug_tracer_flags(self.h, buf.ctypes.data_as(C.c_void_p), n) != n:
+            raise MWError("mw_debug_tracer_flags failed")
+        return buf
+
     def set_bc(self, coupler, bc_x, bc_y, bc_z):
         check(capi.lib().mw_dycore_set_bc(self.h, bc_x, bc_y, bc_z))
         coupler.set_option("bc_x", bc_x); coupler.set_option("bc_y", bc_y); coupler.set_option("bc_z", bc_z)
