@@ -57,16 +57,16 @@ struct DyP {                      // kernel parameter block (by value)
   Stride32 fxJ, fxK, fxV, fyJ, fyK, fyV, fzJ, fzK, fzV;   // flux strides
   int sim2d, bc_x, bc_y, bc_z, px, py, nproc_x, nproc_y;
   int v0;                         // halo/pack kernels: index of the first variable of the group being processed
-  int cst, ce;                    // coupler-side stride / member offset (1, 0; member-major mode: nens, member) -- see cpl() in mw_march.h
+  int cst, ce;                    // coupler-side stride / member offset (1, 0; member-major mode: nens, member) -- see cpl() below
   int wrap_x, wrap_y;             // production path, periodic direction owned by one rank: the marching kernels wrap their x / row index
                                   // instead of reading halo cells, and that halo is not filled
   int enable_gravity, use_immersed, idWV;
   int zero_skip;                  // marching kernels: skip the reconstructions of a tracer that is exactly zero over a wavefront's stencil (mw_march.h)
-  // zero-row map of the current RK stage (mw_march.h: k_zero_rows), nullptr = none: one word per (level, row), bit v = "tracer v may be
+  // zero-row map of the current RK stage (mw_zero_rows.h), nullptr = none: one word per (level, row), bit v = "tracer v may be
   // non-zero in what iterations k-3 .. k of the row's marching wave touch"; word of (k, j) at [k * zq_ld + j + HY]
   const unsigned *zq;
   const unsigned *zqk;            // ... the converting y launch: the rows of the slab it writes that hold zeros already
-  const unsigned *zqp, *zqc;      // ... "the row an iteration stores to holds zeros already": the previous sub-cycle's map of this stage / the coupler's rows (mw_march.h)
+  const unsigned *zqp, *zqc;      // ... "the row an iteration stores to holds zeros already": the previous sub-cycle's map of this stage / the coupler's rows (mw_zero_rows.h)
   int zq_ld;
   // parked column increments (mw_nudge_to_column_deferred): inc[(l * nz + k) * nens + e] for l = density_dry, uvel, vvel, temp, water_vapor, added to
   // the coupler's values while the converting y launch loads them; nullptr = none
@@ -87,6 +87,14 @@ struct CouplerPtrs {
   double *rho_d, *u, *v, *w, *temp;
   double *tr[MW_MAX_TRACERS];
 };
+
+// Index into a COUPLER-layout array (nz,ny,nx,nens) from an index `ci` of the handle's internal cell numbering.  Normally the two
+// coincide (cst = 1, ce = 0).  Member-major mode (nens > 1, production path): the handle's arrays hold one member after the other and
+// every kernel runs its nens = 1 form on member ce; the coupler's arrays keep their member-fastest layout: cst = nens doubles apart.
+__device__ __forceinline__ long long cpl(const DyP &p, long long ci) { return ci * p.cst + p.ce; }
+// Periodic direction owned by one rank (DyP::wrap_x / wrap_y): the interior index that a halo index stands for.
+__device__ __forceinline__ int wrap_xq(const DyP &p, int q, int NXI) { return p.wrap_x ? (q < 0 ? q + NXI : (q >= NXI ? q - NXI : q)) : q; }
+__device__ __forceinline__ int wrap_row(const DyP &p, int j) { return p.wrap_y ? (j < 0 ? j + p.ny : (j >= p.ny ? j - p.ny : j)) : j; }
 
 // Compile-time configuration of the marching kernels (mw_march.h).  The run-time switches of DyP that are wave-uniform and fixed
 // for a whole run cost SGPRs (the marching kernels have none to spare: every SGPR spilled to a VGPR lane comes back as a
@@ -221,8 +229,5 @@ struct MemberOff {
   long long zq;                                                // ... and words, for the members' zero-row maps
   int n, sh;                                                   // members per workgroup (2 or 4) and log2 of it
 };
-
-// zero-row maps (mw_march.h: k_zero_rows, k_zero_dilate): maps per set -- M0, Q1..Q3, FN1..FN3, QY1..QY3
-#define MW_ZR_MAPS 10
 
 } // namespace mw

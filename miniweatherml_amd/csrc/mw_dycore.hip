@@ -612,7 +612,7 @@ View view(const mw_dycore_s *d, int e) {
   q.hyc = m; q.hytc = m + q.nz; q.p0c = m + 2 * q.nz; q.ihytc = m + 3 * q.nz; q.hypk = m + 4 * q.nz;
   q.hye = q.hyte = q.p0e = q.ihyte = nullptr;              // (edge tables: only through hypk on this path)
   if (q.zq) {                                                  // the member's own zero-row maps (zero_rows_build)
-    const long long mstride = (2 * MW_ZR_MAPS + 3) * d->zr_msz;
+    const long long mstride = d->zr.member_words();
     q.zq += e * mstride; if (q.zqp) q.zqp += e * mstride;
     q.zqc = q.zqk = nullptr;
   }
@@ -629,7 +629,7 @@ MemberOff member_off(const mw_dycore_s *d) {
   mo.slab = v.slab; mo.tend = v.tend; mo.mx = v.m[0]; mo.my = v.m[1]; mo.mz = v.m[2]; mo.fx = v.f[0]; mo.fy = v.f[1]; mo.fz = v.f[2];
   mo.cells = v.cells; mo.per = 4 * (long long)v.p.nz + 8 * (long long)(v.p.nz + 1);
   mo.n = d->p.nens; mo.sh = d->p.nens == 4 ? 2 : 1;
-  mo.zq = (2 * MW_ZR_MAPS + 3) * d->zr_msz;
+  mo.zq = d->zr.member_words();
   return mo;
 }
 
@@ -912,9 +912,7 @@ void mw_dycore_destroy(mw_dycore_t d) {
   for (double *ptr : {d->S0, d->S1, d->S2, d->S3, d->tendY, d->FX, d->FY, d->FZ, d->hy_dev, d->imm}) if (ptr) (void)hipFree(ptr);
   if (d->flags) (void)hipFree(d->flags);
   if (d->dirty) (void)hipFree(d->dirty);
-  if (d->zr) (void)hipFree(d->zr);
-  if (d->zrx) (void)hipFree(d->zrx);
-  if (d->zviol) (void)hipFree(d->zviol);
+  zero_rows_free(d);
   if (d->pinc) (void)hipFree(d->pinc);
   for (int b = 0; b < 2; b++) for (int a = 0; a < 3; a++) { if (d->M[b][a]) (void)hipFree(d->M[b][a]); if (d->UP[b][a]) (void)hipFree(d->UP[b][a]); }
   for (int i = 0; i < 8; i++) { if (d->ev_state[i]) (void)hipEventDestroy(d->ev_state[i]); if (d->ev_tr[i]) (void)hipEventDestroy(d->ev_tr[i]); }
@@ -1017,7 +1015,7 @@ int mw_dycore_set_order(mw_dycore_t d, int ord) {
         return rollback();
       }
     }
-    d->zr_prev_ok = false; d->kz_buf[0] = d->kz_buf[1] = nullptr;
+    zero_rows_invalidate(d); zero_rows_forget(d, nullptr);     // (the slabs are replaced)
     double **S[4] = {&d->S0, &d->S1, &d->S2, &d->S3};
     for (int i = 0; i < 4; i++) { if (*S[i]) (void)hipFree(*S[i]); *S[i] = fresh[i]; }
     d->flux_src = nullptr;                                      // pointed into a slab that no longer exists
@@ -1064,7 +1062,7 @@ int mw_dycore_get_fluxes(mw_dycore_t d, double **out6) {
   if (d->flux_src) {     // production path: the state-variable fluxes of the last stage were never written; rebuild all six
     if (d->member_major) {   // the retained stage input is member-major: bring it into the fused layout the general kernels read (S1 is free)
       const long long n = (long long)d->p.V * d->p.sV;
-      d->zr_prev_ok = false;
+      zero_rows_invalidate(d);                                  // (S1 is written without maps)
       MW_KLAUNCH(k_member_to_fused, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d->stream, d->p, d->flux_src, d->S1);
       MW_LAUNCH_CHECK();
       d->flux_src = d->S1;
@@ -1284,7 +1282,7 @@ int mw_dycore_time_step(mw_dycore_t d, double *rho_d, double *u, double *v, doub
       continue;
     }
     // stage 1 (:119-132)
-    d->zr_prev_ok = false; zero_rows_forget(d, nullptr);        // (the general path writes the slabs without maps)
+    zero_rows_invalidate(d); zero_rows_forget(d, nullptr);     // (the general path writes the slabs without maps)
     if (halo_fill(d, d->S0)) return 1;
     if (launch_flux(d, d->S0)) return 1;
     if (launch_fct(d, d->S0, dt_dyn)) return 1;

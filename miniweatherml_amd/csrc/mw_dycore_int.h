@@ -6,16 +6,19 @@
 //   mw_march_y.hip         launchers of k_y_state / k_y_all / k_y_tracers                      }
 //   mw_march_xz.hip        launchers of k_xz_state                                             }  the kernels' text is in mw_march.h;
 //   mw_march_tracers.hip   launchers of k_xz_tracers / k_tracer_update / k_tracers_fused       }  these units hold launch code only
-//   mw_march_sched.hip     the three schedules of an RK stage, the zero-row maps, conversions  }
+//   mw_march_sched.hip     the three schedules of an RK stage, conversion passes               }
+//   mw_zero_rows.hip       the zero-row maps: their kernels (text there too) and host side (interface: mw_zero_rows.h)
 //   mw_dycore_init.hip     the four initial states and the temperature perturbations
 //   mw_dycore_aids.hip     calibration launchers (mw_calib.h) and test aids
 //
 // One definition per kernel: without relocatable device code every unit is a code object of its own, and a kernel that two units
 // instantiate (or a non-template kernel in a header that two units include) is emitted twice.  So every kernel family is launched from
-// exactly one unit, and the non-template kernels of mw_march.h are compiled by mw_march_sched.hip alone (MW_MARCH_SCHED_KERNELS).
+// exactly one unit; the non-template kernels of mw_march.h are compiled by mw_march_sched.hip alone (MW_MARCH_SCHED_KERNELS), and the zero-row
+// kernels are defined in mw_zero_rows.hip, not in a header.
 // =====================================================================================================
 #pragma once
 #include "mw_common.h"
+#include "mw_zero_rows.h"
 #include <string>
 #include <vector>
 #include <algorithm>
@@ -48,7 +51,7 @@ struct DyOpts {
   int chunk_model = 1;
   int tf_rows4 = 1;            // tracer stage: workgroup = 4 rows of one x tile (0: 4 tiles of one row)
   int zero_skip = 1;           // wave-uniform short-cut for tracers that are exactly zero over a wavefront's stencil (bit-neutral; 0: A/B)
-  int zero_rows = 1;           // ... and the zero-row maps on top of it: rows of a tracer that are known to be zero are not loaded (mw_march.h: k_zero_rows)
+  int zero_rows = 1;           // ... and the zero-row maps on top of it: rows of a tracer that are known to be zero are not loaded (mw_zero_rows.h)
   int pipe_maps_early = 1;     // pipelined schedule, first stage: local zero-row maps in front of its y launches, two strip exchanges (0: one exchange, maps beside the y launch; A/B)
   int zero_stores = 1;         // ... and zeros are not stored over rows that hold zeros already (the coupler's arrays, slabs S1 / S2; 0: A/B)
   int zero_verify = 0;         // test aid: check the maps' claims against the data in front of every launch that relies on them (k_zero_verify; mw_debug_zero_violations)
@@ -66,62 +69,64 @@ struct mw_dycore_s {
   mw_grid_t g;
   DyOpts o;
   unsigned char pos[MW_MAX_TRACERS], adds[MW_MAX_TRACERS];
-  hipStream_t stream;
   DyP p;
-  double *S0 = nullptr, *S1 = nullptr, *S2 = nullptr, *S3 = nullptr;   // q^n and three stage slabs (rotated, never aliased)
-  double *M[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};          // upwind mass flux of every x/y/z face,
-  unsigned char *UP[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};  // upwind selector; double-buffered by stage parity
-  hipStream_t tstream = nullptr;                        // tracer pipeline (runs one stage behind / beside the state pipeline)
-  hipEvent_t ev_state[8] = {nullptr}, ev_tr[8] = {nullptr}, ev_misc = nullptr;
-  long long gstage = 0;                                 // global stage counter (event ring index, buffer parity)
-  int overlap = 1;
-  int pre_lo = 0, pre_hi = 0;                // pipelined schedule: rows outside [pre_lo, pre_hi) (and the W / E strip columns) were converted up front
+  bool strides_ok = true;                    // fill_params: every stride of DyP fits its Stride32
+  int ord = 5;                               // WENO order (3, 7, 9: the reference's -DMW_ORD builds; they run on the general kernels)
+  int hxw = HXc, hzw = HZc;                  // halo widths of the slabs: hs + 1 in x / y, hs in z (3 / 2 up to order 5)
+  double etime = 0;
+  int strict = 0;
   int last_march = 0;                        // the last time_step ran on the marching kernels (mw_dycore_schedule)
   std::string path;                          // what the dispatcher chose for the last time_step, spelled out (mw_dycore_path)
-  int pipe = 0;                              // blocks of a decomposed domain: pipelined one-stream schedule (rk_stage_pipe)
-  bool pipe_ready = false;                   // ... the next stage's input strips are already on their way (event ev_pipe[2])
-  bool pipe_edge_done = false;               // ... and its two edge strips of the y launch were issued behind them on the exchange stream
-  hipEvent_t ev_pipe[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool entry_marked = false;                 // ev_pipe[6] was recorded at this time step's entry   // [0], [1]: compute -> exchange stream; [2]: state strips + state edge rows ready; [3]: tracer strips + tracer edge faces ready; [4]: zero-row maps ready; [5]: the block's local zero-row maps ready (exchange -> compute stream); [6]: time_step entered (the coupler's arrays are ready)
-  double *tendY = nullptr;                              // (5,nz,ny,nx,nens) y part of the state tendencies
+  // ---- slabs, face arrays, background
+  double *S0 = nullptr, *S1 = nullptr, *S2 = nullptr, *S3 = nullptr;   // q^n and three stage slabs (rotated, never aliased)
+  int member_major = 0;                      // production path with nens > 1: the handle's arrays hold one member after the other (View)
+  int mm_direct = 0;                         // member-major: D13 written from the last stage's kernels (MemberOff: 2 or 4 members per workgroup), no k_member_to_coupler pass
+  double *M[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};          // upwind mass flux of every x/y/z face,
+  unsigned char *UP[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};  // upwind selector; double-buffered by stage parity
+  double *tendY = nullptr;                   // (5,nz,ny,nx,nens) y part of the state tendencies
   double *FX = nullptr, *FY = nullptr, *FZ = nullptr;
   const double *flux_src = nullptr; double flux_dt = 0; // stage input + dt of the last stage (state fluxes on demand)
   int chunk_y = 0, chunk_yt = 0, chunk_z = 0, chunk_f = 0;
-  bool first_cycle = false;                // the running sub-cycle is the time step's first (zero_rows_build)
-  bool conv_pending = false;               // time_step: the coupler -> slab conversion is still to be done by stage 1's k_y_state
-  long long vap_last_gs = -2;              // ... the last stage (gstage) that did
-  bool vap_used = false;                   // ... some stage since the last reset of the redo counter did
-  unsigned int *dirty = nullptr;           // [0], [1]: "a y face was scaled in this / the next fused tracer launch"; [2]: scratch; [MW_VREDO_RING ..+7]: "a vapour cell of stage gs & 7 failed the limiter test"; [MW_VREDO_RING + 8]: stages of this time step that took the redo
+  double *hy_dev = nullptr;                  // hyc | hytc | hye | hyte | p0c | ihytc | p0e | ihyte | packed rows (see DyP::hypk)
+  std::vector<double> hy_host;               // same packing (the last four are derived in upload_background)
+  double *imm = nullptr;
+  // ---- streams, events and where a time step stands
+  hipStream_t stream;
+  hipStream_t tstream = nullptr;             // tracer pipeline (runs one stage behind / beside the state pipeline); the pipelined schedule's exchange stream
+  hipEvent_t ev_state[8] = {nullptr}, ev_tr[8] = {nullptr}, ev_misc = nullptr;
+  long long gstage = 0;                      // global stage counter (event ring index, buffer parity)
+  int overlap = 1;                           // two-stream schedule (state | tracer pipelines)
+  bool conv_pending = false;                 // time_step: the coupler -> slab conversion is still to be done by stage 1's y launch
+  bool first_cycle = false;                  // the running sub-cycle is the time step's first
+  // ---- pipelined schedule
+  int pipe = 0;                              // blocks of a decomposed domain: pipelined one-stream schedule (rk_stage_pipe)
+  bool pipe_ready = false;                   // ... the next stage's input strips are already on their way (event ev_pipe[2])
+  bool pipe_edge_done = false;               // ... and its two edge strips of the y launch were issued behind them on the exchange stream
+  int pre_lo = 0, pre_hi = 0;                // ... rows outside [pre_lo, pre_hi) (and the W / E strip columns) were converted up front
+  // [0], [1]: compute -> exchange stream; [2]: state strips + state edge rows ready; [3]: tracer strips + tracer edge faces ready; [4]: zero-row
+  // maps ready; [5]: the block's local zero-row maps ready (exchange -> compute stream); [6]: time_step entered (the coupler's arrays are ready)
+  hipEvent_t ev_pipe[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool entry_marked = false;                 // ev_pipe[6] was recorded at this time step's entry
+  // ---- fused tracer stage, vapour redo, zero-row maps
+  int fused = 0;                             // 1: fused tracer stage (k_tracers_fused + k_tracer_patch)
   unsigned long long fused_launches = 0;
-  unsigned char *flags = nullptr;          // fused tracer stage: per-cell "a y face of this cell was FCT-scaled" bits
-  double *zrx = nullptr;                   // ... and the message buffers of a decomposed block's map exchange (own | rW | rE | sS | sN | rS | rN)
-  const double *kz_buf[2] = {nullptr, nullptr};   // ... and, for the two slabs that take turns as q^n, "the rows the last conversion into it left zero" (maps behind MC; nullptr: unknown)
-  int zr_cur = 0;                          // ... double-buffered: set zr_cur belongs to the running sub-cycle, the other one to the one before
-  bool zr_prev_ok = false, zr_prev_use = false;   // the other set describes what slabs S1 / S2 hold now (the sub-cycle before ran with maps, nothing else wrote the slabs since) / ... and is handed to this sub-cycle's kernels
-  unsigned long long *zviol = nullptr;     // option zero_verify: four violation counters (k_zero_verify)
+  unsigned char *flags = nullptr;            // fused tracer stage: per-cell "a y face of this cell was FCT-scaled" bits
+  unsigned int *dirty = nullptr;             // [0], [1]: "a y face was scaled in this / the next fused tracer launch"; [2]: scratch; [MW_VREDO_RING ..+7]: "a vapour cell of stage gs & 7 failed the limiter test"; [MW_VREDO_RING + 8]: stages of this time step that took the redo
+  long long vap_last_gs = -2;                // the last stage (gstage) that advanced the water vapour in k_xz_state (option vapour_state)
+  bool vap_used = false;                     // some stage since the last reset of the redo counter did
+  ZeroRows zr;                               // zero-row maps (mw_zero_rows.h); touched by mw_zero_rows.hip and, reading `on`, the schedules
+  // ---- parked column increments
   double *pinc = nullptr; bool pinc_on = false; double *pinc_fields[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // parked column increments (mw_nudge_to_column_deferred) and the five arrays they belong to
   unsigned long long pinc_lazy = 0, pinc_eager = 0;             // how often parked increments rode on the conversion / were applied by a pass
-  unsigned *zr = nullptr; long long zr_msz = 0; bool zr_on = false;   // zero-row maps (M0 and the six of k_zero_dilate) of the running sub-cycle (mw_march.h: k_zero_rows), zr_msz words each
-  bool strides_ok = true;                  // fill_params: every stride of DyP fits its Stride32
-  int fused = 0;                           // 1: fused tracer stage (k_tracers_fused + k_tracer_patch)
-  double *hy_dev = nullptr;                  // hyc | hytc | hye | hyte | p0c | ihytc | p0e | ihyte | packed rows (see DyP::hypk)
-  double *imm = nullptr;
-  std::vector<double> hy_host;               // same packing (the last four are derived in upload_background)
-  double etime = 0;
-  int strict = 0;
-  int mm_direct = 0;                         // ... and D13 written from the last stage's kernels (MemberOff: 2 or 4 members per workgroup), no k_member_to_coupler pass
-  int member_major = 0;                      // production path with nens > 1: the handle's arrays hold one member after the other (View)
-  int ord = 5;                               // WENO order (3, 7, 9: the reference's -DMW_ORD builds; they run on the general kernels)
-  int hxw = HXc, hzw = HZc;                  // halo widths of the slabs: hs + 1 in x / y, hs in z (3 / 2 up to order 5)
-  // halo exchange
+  // ---- halo exchange
   mw_exchange_fn xchg = nullptr; void *xchg_ctx = nullptr;
+  void (*xchg_free)(void *) = nullptr;       // set when the handle owns xchg_ctx (the built-in RCCL transport, mw_rccl.cpp)
   double *bufs[2][8] = {{nullptr}, {nullptr}};   // [group: 0 state (or all), 1 tracers][sW sE sS sN rW rE rS rN]
   long long nWE1 = 0, nSN1 = 0;                  // per variable
-  // profiling
+  // ---- profiling
   int prof = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[12];      // kernel classes 0..7; 8 = one whole RK stage (all its launches); 9 = one whole time_step; 10 / 11 = the compute stream's waits for the state / tracer strips (pipelined schedule)
   size_t ev_used[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  void (*xchg_free)(void *) = nullptr;       // set when the handle owns xchg_ctx (the built-in RCCL transport, mw_rccl.cpp)
 };
 
 // Workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share an L2).  Padding the blocks-per-plane count to a
@@ -152,7 +157,7 @@ struct ProfScope {
 // k_xz_state is 36 % slower per cell at nens = 4.  The handle's INTERNAL arrays (slabs, tendY, M/UP, FY, side arrays, flags) are
 // ours to lay out, so with nens > 1 they hold one member after the other and every production kernel is launched once per member
 // in its nens = 1 form (View: the member's parameter block and base pointers); only the coupler-side accesses -- conversion in,
-// D13 out, immersed proportion -- are strided (DyP::cst / ce, cpl() in mw_march.h).  The general kernels keep the fused layout in
+// D13 out, immersed proportion -- are strided (DyP::cst / ce, cpl() in mw_common.h).  The general kernels keep the fused layout in
 // the same allocations (a handle runs one path or the other within a time_step; get_fluxes transposes the retained stage input).
 // ---------------------------------------------------------------------------------------------------------------------
 struct View {
@@ -194,7 +199,6 @@ template <int STAGE, int MODE>
 int launch_tracers_fused(mw_dycore_s *d, const double *S, const double *Sn, double *Sout, int par, double dt, double dt_dyn, const CouplerPtrs &c, hipStream_t st, int vap_slot = -1);
 // ---- mw_march_sched.hip
 int rk_cycle_march(mw_dycore_s *d, double **Q, double dt_dyn, bool last, const CouplerPtrs &c);
-void zero_rows_forget(mw_dycore_s *d, const double *S);
 int launch_coupler_to_slab(mw_dycore_s *d, const CouplerPtrs &c, int ylo, int yhi, bool strips);
 
 #pragma GCC visibility pop

@@ -16,6 +16,7 @@
 // reference: dynamics_euler_stratified_wenofv.h:271-388 (D6), :395-485 (D9), :519-551 (D11), :121-174 (D12).
 // =====================================================================================================
 #pragma once
+#include "mw_zero_rows.h"     // the zero-row maps the marching kernels read: constants, word layout, zr_seg_mask, tracer_may_vanish
 #ifndef MW_XCD_SWIZZLE
 #define MW_XCD_SWIZZLE 1
 #endif
@@ -103,10 +104,6 @@ __device__ __forceinline__ void block_segment(int chunk, int len, Segment &sg) {
   const BlockXY blk = xcd_block(); sg.col = blk.x; sg.a = (int)blk.y * chunk; sg.b = min(sg.a + chunk, len);
 }
 
-// Periodic direction owned by one rank (DyP::wrap_x / wrap_y): the interior index that a halo index stands for.
-__device__ __forceinline__ int wrap_xq(const DyP &p, int q, int NXI) { return p.wrap_x ? (q < 0 ? q + NXI : (q >= NXI ? q - NXI : q)) : q; }
-__device__ __forceinline__ int wrap_row(const DyP &p, int j) { return p.wrap_y ? (j < 0 ? j + p.ny : (j >= p.ny ? j - p.ny : j)) : j; }
-
 // Level kl of a marching column (kl may lie in the z halo, -3..nz+2) with the z boundary rule (:752-781) applied on the fly: halo
 // levels repeat the nearest interior level, w is 0 behind a wall.  The marching kernels therefore never read the slab's z halo
 // and the production path does not fill it (k is wave-uniform: the clamp is scalar work).
@@ -119,12 +116,8 @@ __device__ __forceinline__ double load_zlevel(const DyP &p, const double *__rest
 }
 
 #ifndef MW_ZERO_SKIP
-#define MW_ZERO_SKIP 1
+#define MW_ZERO_SKIP 1                                           // (which tracers the short-cut applies to: tracer_may_vanish, mw_zero_rows.h)
 #endif
-// Tracers that can be identically zero over large parts of a domain (see the zero short-cut of k_tracers_fused): everything but the
-// water vapour of the supercell set-ups; simple_city's vapour IS zero (its only tracer); with the switches at run time: all of them.
-// (DyP::zero_skip = the handle's option zero_skip: 0 switches the short-cut off at run time -- the bitwise A/B of tests/ and tools/)
-template <int K> __device__ __forceinline__ bool tracer_may_vanish(const DyP &p, int v) { return p.zero_skip && (K == 1 ? v != 0 : true); }
 
 struct FaceState {   // what the passive variables need from the Riemann solve of one face
   double m_upw;      // upwind mass flux (= flux of idR)
@@ -209,11 +202,6 @@ __device__ __forceinline__ double inv_gamma_series_default(double dl) {
   acc = acc * dl + 0x1.6d7ed9f857ccfp-1;
   return acc;
 }
-// Index into a COUPLER-layout array (nz,ny,nx,nens) from an index `ci` of the handle's internal cell numbering.  Normally the two
-// coincide (cst = 1, ce = 0).  Member-major mode (nens > 1, production path): the handle's arrays hold one member after the other and
-// every kernel runs its nens = 1 form on member ce; the coupler's arrays keep their member-fastest layout: cst = nens doubles apart.
-__device__ __forceinline__ long long cpl(const DyP &p, long long ci) { return ci * p.cst + p.ce; }
-
 // One cell of the coupler, as loaded (the marching kernel requests row j+3 at the top of iteration j and converts it at the end).
 struct CouplerCell { double rho_d, u, v, w, temp, tr[4]; };
 // (ldmask: wave-uniform; bit tr clear = tracer tr is known to be zero in this row -- the zero-row maps -- and is not loaded)
@@ -271,123 +259,9 @@ __device__ __forceinline__ void convert_cell_tracers(const DyP &p, const Coupler
   for (int tr = 0; tr < 4; tr++) if (tr < Cf<K>::ntr(p)) s[(long long)(5 + tr) * sV] = r.tr[tr] * inv_den;
 }
 // ---------------------------------------------------------------------------------------------------------------
-// Zero-row maps (round 5).  Cloud water and rain are exactly zero over most of a supercell domain (all of it at the start), and after
-// the zero short-cut (MW_ZERO_SKIP) the fused tracer kernel is bound by the HBM traffic of values that are all zero.  The maps let it
-// not issue those loads at all:
-//   M0[k][j], bit v : tracer v is non-zero somewhere in the x row (k, j) of the sub-cycle's input q^n   (k_zero_rows: one pass over the
-//                     tracers that can vanish, 16 bytes per cell of the ~500 a stage moves)
-//   Qs[k][j], bit v : (s = 1, 2, 3) tracer v may be non-zero in something that iterations k-3 .. k of row j's marching wave touch in RK
-//                     stage s: the OR of M0 over rows j-3s .. j+3s (periodic) and levels k-3s-5 .. k+3s+1 (clamped)  (k_zero_dilate)
-// One RK stage moves a tracer by at most 3 cells per direction (cell (k, j) is updated from the faces j, j+1 / k, k+1, whose upwind
-// WENO-5 stencils reach rows j-3 .. j+3 / levels k-3 .. k+3; an FCT multiplier only scales a flux, the y-face correction of
-// k_tracer_patch is a difference of scaled and unscaled flux, and every stage adds q^n's own row), and a flux of zeros is zero: a row
-// that is non-zero in the input of stage s (its output, its y fluxes) lies within 3(s-1) (3s) rows and levels of a non-zero row of q^n.
-// Iteration k of k_tracers_fused reads input levels k-2 .. k+3, y fluxes of levels k-1 .. k+1 and q^n of levels k-2 .. k+2, and its
-// carries come from the three iterations before (input levels from k-5, y fluxes from k-5): with Qs[k][j]'s bit clear all of that is
-// exactly zero, and so is the tracer's new value.  The maps are a SUPERSET of the non-zero rows -- a set bit costs the loads, nothing
-// else -- and results equal the run without them (tests/: bitwise up to the sign of a zero; a skipped value enters as +0.0).
-// Handles: x and y periodic, the fused tracer stage; nens == 1 on one rank or as the blocks of a decomposed domain on the pipelined schedule,
-// member-major handles (nens > 1) on one rank with one map set per member (host side: zero_rows_ok / zero_rows_build in mw_march_sched.hip).
-// ---------------------------------------------------------------------------------------------------------------
-#define MW_ZR_REACH 3
-#define MW_ZR_HALO (3 * MW_ZR_REACH)                              // rows a tracer can travel in one sub-cycle = halo rows of the maps
-// x SEGMENTS (round 6).  A storm covers a fifth of the x rows but a fourteenth of the 58-cell tiles a marching wave works on (bench.py:
-// storm.extent), so a word also says WHERE in its row something can be:
-//   bits 0 .. 3   tracer v may be non-zero somewhere in the row (as before; the y kernel's store decision, the tests)
-//   bits 4 .. 29  segment s of the row -- cells [s L, (s + 1) L), L = ceil(NXI / 26) -- may hold a non-zero value of a tracer that can vanish.
-//                 Set at SCAN time for every segment within MW_ZR_HALO = 9 cells of a non-zero cell (what a whole sub-cycle can move it in
-//                 x; periodic when one rank owns the direction), so that the row / level growth of k_zero_dilate -- a plain OR of words --
-//                 carries the segments along.  A wave is lean when the segments its lanes (halo lanes and patch cells included) overlap are clear.
-//   bits 30, 31   (the compact copy a block sends to its west / east neighbours only) the grown set touches the block's west / east edge:
-//                 the neighbour then sets the segments of its first / last 9 cells (k_zero_merge).
-// Per cell the invariants are the old ones -- "bit clear => the cell is zero" -- so the zero-store rules hold cell by cell whatever the tiling.
-#define MW_ZR_SEGS 26
-#define MW_ZR_SEG_SHIFT 4
-#define MW_ZR_ROWBITS 0xFu
-#define MW_ZR_TOUCH_W 0x40000000u
-#define MW_ZR_TOUCH_E 0x80000000u
-__host__ __device__ __forceinline__ int zr_seg_len(int NXI) { return (NXI + MW_ZR_SEGS - 1) / MW_ZR_SEGS; }
-// segment bits (in place: shifted) of the cells [a, b], 0 <= a <= b < NXI
-__host__ __device__ __forceinline__ unsigned zr_seg_span(int a, int b, int L) { return ((2u << (b / L)) - (1u << (a / L))) << MW_ZR_SEG_SHIFT; }
-// ... of the cells [lo, hi] of a row of NXI cells (lo may be < 0, hi >= NXI): periodic images when `wrap`, else clamped into the row
-__host__ __device__ __forceinline__ unsigned zr_seg_mask(int lo, int hi, int NXI, bool wrap) {
-  const int L = zr_seg_len(NXI);
-  if (hi - lo + 1 >= NXI) return zr_seg_span(0, NXI - 1, L);
-  if (!wrap) return zr_seg_span(max(lo, 0), min(hi, NXI - 1), L);
-  if (lo < 0) return zr_seg_span(lo + NXI, NXI - 1, L) | zr_seg_span(0, hi, L);
-  if (hi >= NXI) return zr_seg_span(lo, NXI - 1, L) | zr_seg_span(0, hi - NXI, L);
-  return zr_seg_span(lo, hi, L);
-}
-// Map layout: word of (k, j) at [k * zq_ld + j + MW_ZR_HALO], zq_ld = ny + 2 MW_ZR_HALO (j = -9 .. ny+8: the rows beyond the block's
-// south / north edge -- its own rows again when it owns the periodic y direction, the neighbours' rows otherwise).
-// Blocks of a decomposed domain (pipelined schedule): a row's x halo holds the west / east neighbour's cells and its tracer can come
-// from there, so M0 is OR-ed with the neighbours' M0 of the same row (k_zero_merge; whole rows: coarse, but a superset), and the rows
-// beyond the y edges come from the south / north neighbours' merged maps -- two small messages per sub-cycle through the handle's
-// halo transport, on the exchange stream beside the stage's y and x/z kernels.
-// k_zero_rows: wave = one x row (k, j).  SLAB: the tracers of slab S (later sub-cycles of a step, or after a conversion pass); else the
-// coupler's arrays.  vmask: the tracers that can vanish -- the others are flagged non-zero without being read.  ldo / offo: layout of
-// `out` (compact [k][ny] for k_zero_merge, or the map's own); wrap: also write the row's periodic images into the map's halo rows.
-template <bool SLAB>
-// (wrap == 2: the halo rows are marked "may be non-zero" instead -- the LOCAL maps of a decomposed block, used by the first stage's y launches
-//  before the neighbours' maps have arrived; out2: a second, compact [k][ny] copy for k_zero_merge)
-__global__ __launch_bounds__(256) void k_zero_rows(DyP p, CouplerPtrs c, const double *__restrict__ S, unsigned *__restrict__ out, unsigned vmask,
-                                                   int ldo, int offo, int wrap, unsigned *__restrict__ out2) {
-  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (long long)p.nz * p.ny) return;
-  const int k = (int)(row / p.ny), j = (int)(row - (long long)k * p.ny), lane = threadIdx.x & 63;
-  const int NXI = p.nx * p.nens;
-  // (all tracers' values of eight 64-cell pieces are requested before the first one is tested: the kernel is a latency-bound stream otherwise)
-  const double *src[4];
-#pragma unroll
-  for (int v = 0; v < 4; v++) {
-    const int vv = min(v, p.nt - 1);
-    src[v] = SLAB ? S + (long long)(5 + vv) * p.sV + (long long)(k + p.HZ) * p.sK + (long long)(j + p.HY) * p.sJ + (long long)p.HX * p.nens
-                  : c.tr[vv] + ((long long)k * p.ny + j) * NXI;
-  }
-  const unsigned scan = vmask & ((1u << min(p.nt, 4)) - 1u);
-  bool nz[4] = {false, false, false, false};
-  unsigned segb = 0;                                              // this lane's part of the segment bits (+ the edge flags)
-  const bool xwrap = p.wrap_x != 0;
-  for (int base = 0; base < NXI; base += 512) {
-    double a[4][8];
-#pragma unroll
-    for (int v = 0; v < 4; v++) {
-      if (!((scan >> v) & 1u)) continue;                        // (wave-uniform)
-#pragma unroll
-      for (int u = 0; u < 8; u++) { const int ie = base + u * 64 + lane; a[v][u] = src[v][min(ie, NXI - 1)]; }
-    }
-    bool cellnz[8] = {false, false, false, false, false, false, false, false};
-#pragma unroll
-    for (int v = 0; v < 4; v++) {
-      if (!((scan >> v) & 1u)) continue;
-#pragma unroll
-      for (int u = 0; u < 8; u++) { const bool b = (a[v][u] != 0.0); nz[v] = nz[v] || b; cellnz[u] = cellnz[u] || b; }
-    }
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      if (!cellnz[u]) continue;
-      const int ie = min(base + u * 64 + lane, NXI - 1);
-      segb |= zr_seg_mask(ie - MW_ZR_HALO, ie + MW_ZR_HALO, NXI, xwrap);
-      if (!xwrap && ie - MW_ZR_HALO < 0) segb |= MW_ZR_TOUCH_W;
-      if (!xwrap && ie + MW_ZR_HALO >= NXI) segb |= MW_ZR_TOUCH_E;
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) segb |= (unsigned)__shfl_xor((int)segb, off, 64);
-  unsigned word = ((1u << min(p.nt, 4)) - 1u) & ~vmask;           // the tracers that cannot vanish
-#pragma unroll
-  for (int v = 0; v < 4; v++) if (((scan >> v) & 1u) && __any(nz[v])) word |= 1u << v;
-  word |= segb;                                                  // (with the two edge flags when x is decomposed: k_zero_merge of the neighbours reads them; nobody else looks at bits 30, 31)
-  if (lane == 0) {
-    unsigned *o = out + (long long)k * ldo + offo;
-    o[j] = word;
-    if (wrap && j < MW_ZR_HALO) o[p.ny + j] = (wrap == 2) ? ~0u : word;
-    if (wrap && j >= p.ny - MW_ZR_HALO) o[j - p.ny] = (wrap == 2) ? ~0u : word;
-    if (out2) out2[(long long)k * p.ny + j] = word;
-  }
-}
-// ---------------------------------------------------------------------------------------------------------------
-// The NON-TEMPLATE kernels of this header.  A kernel is emitted into the code object of every unit that sees its definition (`inline` does
-// not apply to kernels), so exactly one unit may: mw_march_sched.hip defines MW_MARCH_SCHED_KERNELS and launches all of them.
+// The NON-TEMPLATE kernels of this header: the three conversion passes between the coupler's arrays and the slabs.  A kernel is emitted into
+// the code object of every unit that sees its definition (`inline` does not apply to kernels), so exactly one unit may: mw_march_sched.hip
+// defines MW_MARCH_SCHED_KERNELS and launches all of them.  (The zero-row maps' kernels have a unit of their own: mw_zero_rows.hip.)
 // ---------------------------------------------------------------------------------------------------------------
 #ifdef MW_MARCH_SCHED_KERNELS
 // stand-alone form (2-D runs, walls / open boundaries or a neighbour exchange in y, two-stream schedule)
@@ -420,172 +294,6 @@ __global__ __launch_bounds__(256) void k_coupler_to_state_fast(DyP p, CouplerPtr
   for (int v = 0; v < 5; v++) s[(long long)v * p.sV] = s5[v];
   convert_cell_tracers(p, r, inv_den, s, p.sV);
 }
-
-// Decomposed block: M = own rows (compact) OR the west / east neighbours' (rW / rE, nullptr: x is not decomposed); the merged rows next
-// to the south / north edge are packed for those neighbours (sS / sN, nullptr: y is not decomposed -- the halo rows are then the block's
-// own periodic images).
-__global__ __launch_bounds__(256) void k_zero_merge(DyP p, const unsigned *__restrict__ own, const unsigned *__restrict__ rW, const unsigned *__restrict__ rE,
-                                                    unsigned *__restrict__ M, unsigned *__restrict__ sS, unsigned *__restrict__ sN) {
-  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (t >= (long long)p.nz * p.ny) return;
-  const int k = (int)(t / p.ny), j = (int)(t - (long long)k * p.ny);
-  unsigned wd = own[t];
-  if (rW) {
-    // the neighbours' rows: their row bits as before (coarse, but a superset -- the y kernel's store decision looks at them); of their
-    // segments only what can cross the shared edge within a sub-cycle: a grown set that touches the neighbour's edge reaches my first / last 9 cells
-    const unsigned w = rW[t], e = rE[t];
-    const int NXI = p.nx * p.nens;
-    wd |= (w | e) & MW_ZR_ROWBITS;
-    if (w & MW_ZR_TOUCH_E) wd |= zr_seg_mask(0, MW_ZR_HALO - 1, NXI, false);
-    if (e & MW_ZR_TOUCH_W) wd |= zr_seg_mask(NXI - MW_ZR_HALO, NXI - 1, NXI, false);
-  }
-  unsigned *o = M + (long long)k * p.zq_ld + MW_ZR_HALO;
-  o[j] = wd;
-  if (sS) {
-    if (j < MW_ZR_HALO) sS[k * MW_ZR_HALO + j] = wd;
-    if (j >= p.ny - MW_ZR_HALO) sN[k * MW_ZR_HALO + j - (p.ny - MW_ZR_HALO)] = wd;
-  } else {
-    if (j < MW_ZR_HALO) o[p.ny + j] = wd;
-    if (j >= p.ny - MW_ZR_HALO) o[j - p.ny] = wd;
-  }
-}
-// ... and the rows beyond the y edges from what the south / north neighbours packed (their northernmost / southernmost rows)
-__global__ __launch_bounds__(256) void k_zero_halo(DyP p, unsigned *__restrict__ M, const unsigned *__restrict__ rS, const unsigned *__restrict__ rN) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= p.nz * MW_ZR_HALO) return;
-  const int k = t / MW_ZR_HALO, h = t - k * MW_ZR_HALO;
-  unsigned *o = M + (long long)k * p.zq_ld + MW_ZR_HALO;
-  o[h - MW_ZR_HALO] = rS[t];
-  o[p.ny + h] = rN[t];
-}
-// M0 -> Q1, Q2, Q3 (Q_s at M + s * msz), separably through LDS: rows first (three radii), then levels; and
-//   FNs[k][j] at M + (3 + s) * msz = the OR of Qs[k-1 .. k+1][j]: "row j's tracer kernel may load its y fluxes of level k" (its iteration k'
-//   reads level k'-1, clamped into the chunk: k' = k-1, k or k+1) -- k_y_all does not store the fluxes of a face whose two rows are clear.
-#define MW_ZR_BEFORE 5                                            // levels below: the three iterations whose carries an iteration inherits
-#define MW_ZR_AFTER 1                                             // levels above: the y fluxes of level k+1 (chunk ends clamp k-1 upwards)
-//   QYs[k][j] at M + (6 + s) * msz = M0 dilated by 3s rows and 3(s-1) levels = the input of stage s, three more rows either way: what
-//   iteration j of k_y_all's wave at level k touches (the window of face j, the row that enters it, the edge value carried from j-1).
-// Zeros are not stored over zeros either (DyP::zqc / zqp, host side: zero_rows_build):
-//   MC (zqc) = M0 of the time step's FIRST sub-cycle = which rows of the coupler's own tracer arrays are zero (nothing writes them before the
-//   last sub-cycle's D13): a lean iteration of the last stage does not store there;
-//   the PREVIOUS sub-cycle's Qs (zqp; s = 1, 2 -- slabs S1 and S2 always take the output of stages 1 and 2): level k of a row is stored by
-//   iteration k+2, in the lean form (zeros) exactly when Qs[k+2][j] was clear -- for every x tile of the row alike, the form follows from the
-//   row's word alone -- so where the previous Qs is clear the slab row holds zeros already and a lean iteration leaves it alone.  The host
-//   hands the previous maps over only when the previous sub-cycle ran with maps and nothing else has written the slabs since.
-// (MW_ZR_MAPS, the number of maps per set: mw_common.h)
-// (fn_ones: FNs = "store" everywhere -- the local maps of a decomposed block cannot know what the neighbours make the tracer kernel read)
-__global__ __launch_bounds__(256) void k_zero_dilate(DyP p, unsigned *__restrict__ M, long long msz, int fn_ones) {
-  constexpr int TK = 16, TJ = 64, R = MW_ZR_HALO, LO = R + MW_ZR_BEFORE + 1, HI = R + MW_ZR_AFTER + 1, EK = TK + LO + HI, EJ = TJ + 2 * R;
-  __shared__ unsigned a[EK][EJ];
-  __shared__ unsigned b[3][EK][TJ];
-  const int k0 = blockIdx.y * TK, j0 = blockIdx.x * TJ, tid = threadIdx.x;
-  for (int t = tid; t < EK * EJ; t += 256) {
-    const int kk = t / EJ, jj = t - kk * EJ;
-    const int k = min(max(k0 + kk - LO, 0), p.nz - 1);
-    const int j = j0 + jj - R;                                   // -9 .. ny+8 are rows of the map; beyond (the last tile's overhang): nobody's
-    a[kk][jj] = (j < p.ny + R) ? M[(long long)k * p.zq_ld + j + MW_ZR_HALO] : 0u;
-  }
-  __syncthreads();
-  for (int t = tid; t < EK * TJ; t += 256) {
-    const int kk = t / TJ, jj = t - kk * TJ, cc = jj + R;
-    unsigned o = a[kk][cc];
-#pragma unroll
-    for (int r = 1; r <= R; r++) {
-      o |= a[kk][cc - r] | a[kk][cc + r];
-      if (r % MW_ZR_REACH == 0) b[r / MW_ZR_REACH - 1][kk][jj] = o;
-    }
-  }
-  __syncthreads();
-  for (int t = tid; t < TK * TJ; t += 256) {
-    const int kk = t / TJ, jj = t - kk * TJ, k = k0 + kk, j = j0 + jj;
-    if (k >= p.nz || j >= p.ny) continue;
-#pragma unroll
-    for (int m = 0; m < 3; m++) {
-      const int r = MW_ZR_REACH * (m + 1);
-      const int ry = MW_ZR_REACH * m;
-      unsigned o = 0, fn = 0, qy = 0;
-      for (int dd = -r - MW_ZR_BEFORE - 1; dd <= r + MW_ZR_AFTER + 1; dd++) {
-        const unsigned v = b[m][kk + LO + dd][jj];
-        fn |= v;
-        if (dd >= -r - MW_ZR_BEFORE && dd <= r + MW_ZR_AFTER) o |= v;
-        if (dd >= -ry && dd <= ry) qy |= v;
-      }
-      M[(long long)(m + 1) * msz + (long long)k * p.zq_ld + j + MW_ZR_HALO] = o;
-      M[(long long)(m + 4) * msz + (long long)k * p.zq_ld + j + MW_ZR_HALO] = fn_ones ? ~0u : fn;
-      M[(long long)(m + 7) * msz + (long long)k * p.zq_ld + j + MW_ZR_HALO] = qy;
-    }
-  }
-}
-
-// Test aid (option zero_verify, any build): the CLAIMS the maps make, checked against the data right in front of the launches that rely on
-// them.  wave = one x row (k, j) of the block; viol[] counts rows:
-//   [0] a tracer that can vanish is non-zero in row (k, j) of the stage's INPUT slab although Qs[k'][j] is clear for one of the iterations
-//       k' = k-3 .. k+2 (clamped) of the row's tracer wave that touch level k  (k_tracers_fused would not have loaded it);
-//   [1] ... although QYs[k][j'] is clear for one of the rows j' = j-3 .. j+3 whose y-marching iteration touches row j  (k_y_all);
-//   [2] a destination row whose store of zeros the tracer kernel is about to SKIP (its storing iteration is lean and the map handed over as
-//       "the destination holds zeros already" is clear -- zqp: slab S1 / S2; zqc: the coupler's arrays) is NOT all zero: a non-zero value
-//       would be left standing;
-//   [3] likewise a row of the slab that the converting y launch is about to skip (zqk).
-// dst == nullptr / the map pointers == nullptr: that claim is not made in this launch and not checked.
-__global__ __launch_bounds__(256) void k_zero_verify(DyP p, CouplerPtrs c, const double *__restrict__ Sin, const double *__restrict__ Sdst, int dst_coupler,
-                                                     const double *__restrict__ Skz, long long msz, unsigned vmask, unsigned long long *__restrict__ viol) {
-  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (long long)p.nz * p.ny) return;
-  const int k = (int)(row / p.ny), j = (int)(row - (long long)k * p.ny), lane = threadIdx.x & 63;
-  const int NXI = p.nx * p.nens;
-  const unsigned scan = vmask & ((1u << min(p.nt, 4)) - 1u);
-  unsigned in_nz = 0, dst_nz = 0, kz_nz = 0;
-  unsigned in_sg = 0, dst_sg = 0, kz_sg = 0;                      // ... and the x segments (exact: no growth) that hold a non-zero cell
-  const long long so = (long long)(k + p.HZ) * p.sK + (long long)(j + p.HY) * p.sJ + (long long)p.HX * p.nens;
-  const long long ci = ((long long)k * p.ny + j) * NXI;
-  for (int v = 0; v < 4; v++) {
-    if (!((scan >> v) & 1u)) continue;
-    bool a = false, b = false, e = false;
-    for (int ie = lane; ie < NXI; ie += 64) {
-      const unsigned sg = zr_seg_mask(ie, ie, NXI, false);
-      if (Sin && Sin[(long long)(5 + v) * p.sV + so + ie] != 0.0) { a = true; in_sg |= sg; }
-      if (Sdst && !dst_coupler && Sdst[(long long)(5 + v) * p.sV + so + ie] != 0.0) { b = true; dst_sg |= sg; }
-      if (dst_coupler && c.tr[v][cpl(p, ci + ie)] != 0.0) { b = true; dst_sg |= sg; }
-      if (Skz && Skz[(long long)(5 + v) * p.sV + so + ie] != 0.0) { e = true; kz_sg |= sg; }
-    }
-    if (__any(a)) in_nz |= 1u << v;
-    if (__any(b)) dst_nz |= 1u << v;
-    if (__any(e)) kz_nz |= 1u << v;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    in_sg |= (unsigned)__shfl_xor((int)in_sg, off, 64); dst_sg |= (unsigned)__shfl_xor((int)dst_sg, off, 64); kz_sg |= (unsigned)__shfl_xor((int)kz_sg, off, 64);
-  }
-  // (a segment's claim is a claim about its cells: checked with the same rules as the row bits, the segment bits beside them)
-  in_nz |= in_sg; dst_nz |= dst_sg; kz_nz |= kz_sg;
-  if (lane != 0) return;
-  const long long ld = p.zq_ld;
-  if (p.zq && in_nz) {
-    bool bad0 = false, bad1 = false;
-    for (int kk = max(k - 3, 0); kk <= min(k + 2, p.nz - 1); kk++) bad0 = bad0 || ((in_nz & ~p.zq[(long long)kk * ld + j + MW_ZR_HALO]) != 0u);
-    const unsigned *qy = p.zq + 6 * msz;
-    // (the derived maps hold the block's own rows only -- the kernels index them behind wrap_row: rows beyond a decomposed y edge belong to
-    //  the neighbour's maps and are not checked here)
-    for (int dj = -MW_ZR_REACH; dj <= MW_ZR_REACH; dj++) {
-      const int jj = wrap_row(p, j + dj);
-      if (jj >= 0 && jj < p.ny) bad1 = bad1 || ((in_nz & ~qy[(long long)k * ld + jj + MW_ZR_HALO]) != 0u);
-    }
-    if (bad0) atomicAdd(&viol[0], 1ull);
-    if (bad1) atomicAdd(&viol[1], 1ull);
-  }
-  // (the store of level k is skipped by the iteration k + 2 of the row's wave -- word min(k + 2, nz - 1) -- when that iteration is LEAN and
-  //  the destination's map is clear; the converting y launch skips row j when the iteration that converts it, j - 3, is lean and zqk is clear)
-  if (dst_nz && p.zq) {
-    const unsigned *m = dst_coupler ? p.zqc : p.zqp;
-    const int kq = min(k + 2, p.nz - 1);
-    if (m && (dst_nz & ~p.zq[(long long)kq * ld + j + MW_ZR_HALO] & ~m[(long long)(dst_coupler ? k : kq) * ld + j + MW_ZR_HALO])) atomicAdd(&viol[2], 1ull);
-  }
-  if (kz_nz && p.zqk && p.zq) {
-    const unsigned *qy = p.zq + 6 * msz;
-    const int jl = wrap_row(p, j - MW_ZR_REACH);                 // the iteration that converts row j; beyond a decomposed edge: never lean
-    if (jl >= 0 && jl < p.ny && (kz_nz & ~qy[(long long)k * ld + jl + MW_ZR_HALO] & ~p.zqk[(long long)k * ld + j + MW_ZR_HALO])) atomicAdd(&viol[3], 1ull);
-  }
-}
-
 // Member-major handles (nens > 1, see View in mw_dycore_int.h): the two conversions between the coupler's member-fastest arrays and
 // the member-after-member slabs, as coalesced passes.  thread = one cell in the COUPLER's order (fused x, member fastest): the
 // coupler side is a unit-stride stream, the slab side 16-lane segments of nens different members.  (Done from inside the

@@ -1,13 +1,12 @@
 // =====================================================================================================
-// mw_march_sched.hip -- the schedules of an RK stage on the marching kernels (one stream, two streams, pipelined), the zero-row maps and the
-// coupler <-> slab conversion passes.  The one unit that compiles the non-template kernels of mw_march.h.
+// mw_march_sched.hip -- the schedules of an RK stage on the marching kernels (one stream, two streams, pipelined) and the coupler <-> slab
+// conversion passes.  The one unit that compiles the non-template kernels of mw_march.h.
 // (unit map and the one-definition rule: mw_dycore_int.h)
 // =====================================================================================================
 #include "mw_dycore_int.h"
 #include "mw_weno.h"
 #define MW_MARCH_SCHED_KERNELS
 #include "mw_march.h"
-#include <cstring>
 
 // ---------------------------------------------------------------------------------------------------------------------
 // One RK stage on the production path, as two pipelines on two HIP streams:
@@ -18,35 +17,6 @@
 // mass fluxes / selectors / new density of their stage (event ev_state); the state pipeline may not run more than
 // one stage ahead because the M/UP buffers are double-buffered and the four slabs rotate (event ev_tr of stage s-2).
 // ---------------------------------------------------------------------------------------------------------------------
-static void zero_rows_stage(mw_dycore_s *d, int stage);
-static void zero_rows_conv(mw_dycore_s *d, const double *S, bool done, hipStream_t st);
-static int zero_rows_build(mw_dycore_s *d, const double *S0, const CouplerPtrs &c, bool from_coupler, hipStream_t st, bool first_cycle);
-static bool zero_rows_ok(const mw_dycore_s *d);
-static int zero_rows_local(mw_dycore_s *d, const double *S0, const CouplerPtrs &c, bool from_coupler, hipStream_t st);
-static int zero_rows_merge(mw_dycore_s *d, hipStream_t st, bool first_cycle);
-// Option zero_verify (test aid): the maps' claims against the data, on stream `st`, in front of the launches that rely on them.
-//   what = 0: in front of the stage's tracer kernel -- the stage's input slab against Qs / QYs, the destination (slab Sout, or the coupler's
-//             arrays in the last stage of a time step) against the "holds zeros already" map the kernel was handed;
-//   what = 1: in front of the converting y launch -- the slab it fills against zqk.
-// Uses the parameter block as the next launch will see it (zero_rows_stage / zero_rows_conv have run).  Counters: mw_debug_zero_violations.
-static int zero_rows_verify(mw_dycore_s *d, int what, const double *Sin, const double *Sout, bool dst_coupler, const CouplerPtrs &c, hipStream_t st) {
-  if (!d->o.zero_verify || !d->zr_on) return 0;
-  if (!d->zviol) { MW_HIP(hipMalloc(&d->zviol, 4 * sizeof(unsigned long long))); MW_HIP(hipMemsetAsync(d->zviol, 0, 4 * sizeof(unsigned long long), st)); }
-  for (int e = 0; e < n_views(d); e++) {
-    const View v = view(d, e);
-    const DyP &p = v.p;
-    if (what == 0 && !p.zq) continue;
-    if (what == 1 && !p.zqk) continue;
-    const unsigned vmask = (marching_config(d, p) == 1) ? 0x6u : 0xFu;
-    const long long nrow = (long long)p.nz * p.ny;
-    const bool dstc = what == 0 && dst_coupler && p.zqc != nullptr;
-    const double *dst = (what == 0 && !dst_coupler && p.zqp) ? v.S(Sout) : nullptr;
-    MW_KLAUNCH(k_zero_verify, dim3((unsigned)((nrow + 3) / 4)), dim3(256), 0, st, p, c, what == 0 ? v.S(Sin) : nullptr, dst, dstc ? 1 : 0,
-               what == 1 ? v.S(Sin) : nullptr, d->zr_msz, vmask, d->zviol);
-    MW_LAUNCH_CHECK();
-  }
-  return 0;
-}
 template <int STAGE, int MODE>
 static int rk_stage_march(mw_dycore_s *d, double *Sin, const double *Sn, double *Sout, double dt_stage, double dt_dyn,
                           const CouplerPtrs &c) {
@@ -165,7 +135,7 @@ static int rk_stage_pipe(mw_dycore_s *d, double *Sin, const double *Sn, double *
     MW_HIP(hipEventRecord(d->ev_pipe[3], xs));
     d->pipe_edge_done = true;
     if (zero_rows_merge(d, xs, d->first_cycle)) return 1;
-    if (d->zr_on) MW_HIP(hipEventRecord(d->ev_pipe[4], xs));
+    if (d->zr.on) MW_HIP(hipEventRecord(d->ev_pipe[4], xs));
     zero_rows_stage(d, 1);                                      // the local maps, for this stage's inner y rows
     if (conv) zero_rows_conv(d, Sin, false, ss); else zero_rows_forget(d, Sin);
   } else
@@ -179,7 +149,7 @@ static int rk_stage_pipe(mw_dycore_s *d, double *Sin, const double *Sn, double *
     if (STAGE == 1) {                                           // the sub-cycle's zero-row maps, behind the strips: needed by the tracer kernel only
       if (zero_rows_build(d, Sin, c, conv, xs, d->first_cycle)) return 1;
       if (conv) zero_rows_conv(d, Sin, true, xs); else zero_rows_forget(d, Sin);
-      if (d->zr_on) MW_HIP(hipEventRecord(d->ev_pipe[4], xs));
+      if (d->zr.on) MW_HIP(hipEventRecord(d->ev_pipe[4], xs));
     }
   }
   if (STAGE != 1) zero_rows_stage(d, STAGE);                    // (stage 1 without the early maps: its y launches run BESIDE the map build -- the maps are handed over in front of the tracer kernel)
@@ -203,7 +173,7 @@ static int rk_stage_pipe(mw_dycore_s *d, double *Sin, const double *Sn, double *
   }
   { ProfScope wait_scope(d, 11, ss);                           // (profile class 11)
     MW_HIP(hipStreamWaitEvent(ss, d->ev_pipe[3], 0)); }        // tracer strips + the edge faces' tracer fluxes of this stage's input
-  if (STAGE == 1 && d->zr_on) {
+  if (STAGE == 1 && d->zr.on) {
     MW_HIP(hipStreamWaitEvent(ss, d->ev_pipe[4], 0)); zero_rows_stage(d, 1);
     if (maps_early && conv) zero_rows_conv(d, Sin, true, ss);     // (the slab's row map changes BEHIND the converting launch that reads it)
   }
@@ -220,216 +190,23 @@ static int rk_stage_pipe(mw_dycore_s *d, double *Sin, const double *Sn, double *
   }
   return 0;
 }
-// Zero-row maps (mw_march.h: k_zero_rows).  Which handles: nens == 1, fused tracer stage, x and y periodic; one rank on the one-stream
-// schedule, or the blocks of a decomposed domain on the pipelined schedule.  The ranks of a decomposed domain exchange maps, so all of
-// them must decide alike: the size test looks at the smallest block of the decomposition, not at this rank's.
-static bool zero_rows_ok(const mw_dycore_s *d) {
-  const DyP &p = d->p;
-  // (nens > 1: the member-major layout on one rank -- every member has its own maps and the per-member launches read them; the launches
-  //  that hold all members of a tile in one workgroup run without)
-  if (!(d->o.zero_skip && d->o.zero_rows && d->fused && (p.nens == 1 || (d->member_major && !d->xchg)) && p.nt >= 1 && p.nt <= 4 && !p.sim2d &&
-        p.nz >= 2 && p.bc_x == MW_BC_PERIODIC && p.bc_y == MW_BC_PERIODIC)) return false;
-  const long long nx_min = d->g.nx_glob / std::max(1, p.nproc_x), ny_min = d->g.ny_glob / std::max(1, p.nproc_y);
-  if (ny_min < MW_ZR_HALO || nx_min < 2 * MW_ZR_HALO) return false;   // (a tracer must not cross a whole block in one sub-cycle)
-  if (!d->xchg) return !d->overlap && !d->pipe;
-  return d->pipe != 0;
-}
-// ... built at the start of a sub-cycle from its input on stream `st`: the coupler's arrays while the conversion is still pending (it
-// happens inside the first y launch), slab S0 otherwise.  Blocks of a decomposed domain: + the neighbours' maps (see k_zero_merge).
-static int zero_rows_build(mw_dycore_s *d, const double *S0, const CouplerPtrs &c, bool from_coupler, hipStream_t st, bool first_cycle) {
-  d->zr_on = zero_rows_ok(d);
-  if (!d->zr_on) return 0;
-  DyP &p = d->p;
-  const int ld = p.ny + 2 * MW_ZR_HALO;
-  const long long msz = (long long)p.nz * ld;
-  const bool ex_x = d->xchg && p.nproc_x > 1, ex_y = d->xchg && p.nproc_y > 1;
-  const long long nrow = (long long)p.nz * p.ny, nedge = (long long)p.nz * MW_ZR_HALO;
-  const long long dWE = (nrow + 1) / 2, dSN = (nedge + 1) / 2;   // message lengths in doubles (the transport's unit)
-  if (!d->zr || d->zr_msz != msz) {
-    if (d->zr) { MW_HIP(hipDeviceSynchronize()); (void)hipFree(d->zr); d->zr = nullptr; }
-    if (d->zrx) { (void)hipFree(d->zrx); d->zrx = nullptr; }
-    if (hipMalloc(&d->zr, (2 * MW_ZR_MAPS + 3) * (size_t)msz * sizeof(unsigned) * (size_t)p.nens) != hipSuccess) {   // per member: two sets + MC + the two q^n slabs' maps
-      (void)hipGetLastError(); d->zr = nullptr; d->zr_on = false;
-      if (d->xchg) MW_FAIL("zero-row maps: out of device memory");   // (a decomposed block: the other ranks are about to exchange maps -- an error, not a fall-back)
-      return 0; }
-    d->zr_msz = msz; d->zr_prev_ok = false; d->kz_buf[0] = d->kz_buf[1] = nullptr;
-  }
-  if (d->member_major) {                                        // one map set per member, from the member's slab (the caller runs this behind the first y launch)
-    d->zr_cur ^= 1;
-    d->zr_prev_use = d->zr_prev_ok && d->o.zero_stores;
-    const long long mstride = (2 * MW_ZR_MAPS + 3) * msz;
-    const int K = marching_config(d, view(d, 0).p);
-    const unsigned vmask = (K == 1) ? 0x6u : 0xFu;
-    ProfScope ps(d, 4, st);
-    for (int e = 0; e < n_views(d); e++) {
-      const View v = view(d, e);
-      DyP q = v.p; q.zq_ld = ld;
-      unsigned *zr = d->zr + e * mstride + (long long)d->zr_cur * MW_ZR_MAPS * msz;
-      MW_KLAUNCH(k_zero_rows<true>, dim3((unsigned)((nrow + 3) / 4)), dim3(256), 0, st, q, c, v.S(S0), zr, vmask, ld, MW_ZR_HALO, 1, nullptr);
-      MW_KLAUNCH(k_zero_dilate, dim3((unsigned)((p.ny + 63) / 64), (unsigned)((p.nz + 15) / 16)), dim3(256), 0, st, q, zr, msz, 0);
-    }
-    MW_LAUNCH_CHECK();
-    return 0;
-  }
-  d->zr_cur ^= 1;                                               // build into the other set; the one of the sub-cycle before stays readable
-  d->zr_prev_use = d->zr_prev_ok && d->o.zero_stores;
-  unsigned *const zr = d->zr + (long long)d->zr_cur * MW_ZR_MAPS * msz;
-  if ((ex_x || ex_y) && !d->zrx) {
-    if (hipMalloc(&d->zrx, (size_t)(3 * dWE + 4 * dSN) * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); MW_FAIL("zero-row maps: out of device memory"); }
-    // (a failure here is an error, not a fall-back: the other ranks are about to exchange maps)
-  }
-  p.zq_ld = ld;
-  const int K = marching_config(d, p);
-  const unsigned vmask = (K == 1) ? 0x6u : 0xFu;                // = tracer_may_vanish<K>
-  ProfScope ps(d, 4, st);
-  const dim3 g((unsigned)((nrow + 3) / 4));
-  const bool local = !ex_x && !ex_y;
-  unsigned *own = local ? zr : (unsigned *)d->zrx;
-  const int ldo = local ? ld : p.ny, offo = local ? MW_ZR_HALO : 0;
-  if (from_coupler) MW_KLAUNCH(k_zero_rows<false>, g, dim3(256), 0, st, p, c, S0, own, vmask, ldo, offo, local ? 1 : 0, nullptr);
-  else              MW_KLAUNCH(k_zero_rows<true>, g, dim3(256), 0, st, p, c, S0, own, vmask, ldo, offo, local ? 1 : 0, nullptr);
-  MW_LAUNCH_CHECK();
-  if (!local) {
-    double *rW = d->zrx + dWE, *rE = d->zrx + 2 * dWE, *sS = d->zrx + 3 * dWE, *sN = sS + dSN, *rS = sN + dSN, *rN = rS + dSN;
-    if (ex_x && d->xchg(d->xchg_ctx, d->zrx, d->zrx, nullptr, nullptr, rW, rE, nullptr, nullptr, dWE, 0, st)) MW_FAIL("zero-row maps: exchange callback failed");
-    MW_KLAUNCH(k_zero_merge, dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, st, p, own, ex_x ? (const unsigned *)rW : nullptr, (const unsigned *)rE, zr,
-               ex_y ? (unsigned *)sS : nullptr, (unsigned *)sN);
-    MW_LAUNCH_CHECK();
-    if (ex_y) {
-      if (d->xchg(d->xchg_ctx, nullptr, nullptr, sS, sN, nullptr, nullptr, rS, rN, 0, dSN, st)) MW_FAIL("zero-row maps: exchange callback failed");
-      MW_KLAUNCH(k_zero_halo, dim3((unsigned)((nedge + 255) / 256)), dim3(256), 0, st, p, zr, (const unsigned *)rS, (const unsigned *)rN);
-      MW_LAUNCH_CHECK();
-    }
-  }
-  // the first sub-cycle's M0 doubles as "which rows of the coupler's tracer arrays are zero" until the last sub-cycle's D13 (map MC)
-  if (first_cycle) MW_HIP(hipMemcpyAsync(d->zr + 2 * MW_ZR_MAPS * msz, zr, (size_t)msz * sizeof(unsigned), hipMemcpyDeviceToDevice, st));
-  MW_KLAUNCH(k_zero_dilate, dim3((unsigned)((p.ny + 63) / 64), (unsigned)((p.nz + 15) / 16)), dim3(256), 0, st, p, zr, msz, 0);
-  MW_LAUNCH_CHECK();
-  return 0;
-}
-// The same in two halves for the first stage of the pipelined schedule (round 5, profiles/r05_selfloop_timeline_maps.txt): LOCAL maps on the
-// compute stream in front of the stage's y launches -- the y kernel reads no x halo, its inner rows only the block's own rows; the rows
-// beyond a decomposed y edge count as "may be non-zero", and FNs as "store" -- ...
-static int zero_rows_local(mw_dycore_s *d, const double *S0, const CouplerPtrs &c, bool from_coupler, hipStream_t st) {
-  d->zr_on = zero_rows_ok(d);
-  if (!d->zr_on) return 0;
-  DyP &p = d->p;
-  const int ld = p.ny + 2 * MW_ZR_HALO;
-  const long long msz = (long long)p.nz * ld;
-  const bool ex_x = d->xchg && p.nproc_x > 1, ex_y = d->xchg && p.nproc_y > 1;
-  const long long nrow = (long long)p.nz * p.ny, nedge = (long long)p.nz * MW_ZR_HALO;
-  const long long dWE = (nrow + 1) / 2, dSN = (nedge + 1) / 2;
-  if (!d->zr || d->zr_msz != msz) {
-    if (d->zr) { MW_HIP(hipDeviceSynchronize()); (void)hipFree(d->zr); d->zr = nullptr; }
-    if (d->zrx) { (void)hipFree(d->zrx); d->zrx = nullptr; }
-    if (hipMalloc(&d->zr, (2 * MW_ZR_MAPS + 3) * (size_t)msz * sizeof(unsigned) * (size_t)p.nens) != hipSuccess) {
-      (void)hipGetLastError(); d->zr = nullptr; d->zr_on = false;
-      if (d->xchg) MW_FAIL("zero-row maps: out of device memory");   // (as in zero_rows_build: the neighbours still post their map exchanges)
-      return 0; }
-    d->zr_msz = msz; d->zr_prev_ok = false; d->kz_buf[0] = d->kz_buf[1] = nullptr;
-  }
-  if (!d->zrx && hipMalloc(&d->zrx, (size_t)(3 * dWE + 4 * dSN) * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); MW_FAIL("zero-row maps: out of device memory"); }
-  d->zr_cur ^= 1;
-  d->zr_prev_use = d->zr_prev_ok && d->o.zero_stores;
-  unsigned *const zr = d->zr + (long long)d->zr_cur * MW_ZR_MAPS * msz;
-  p.zq_ld = ld;
-  const unsigned vmask = (marching_config(d, p) == 1) ? 0x6u : 0xFu;
-  ProfScope ps(d, 4, st);
-  const dim3 g((unsigned)((nrow + 3) / 4));
-  const int wrap = ex_y ? 2 : 1;
-  if (from_coupler) MW_KLAUNCH(k_zero_rows<false>, g, dim3(256), 0, st, p, c, S0, zr, vmask, ld, MW_ZR_HALO, wrap, (unsigned *)d->zrx);
-  else              MW_KLAUNCH(k_zero_rows<true>, g, dim3(256), 0, st, p, c, S0, zr, vmask, ld, MW_ZR_HALO, wrap, (unsigned *)d->zrx);
-  MW_KLAUNCH(k_zero_dilate, dim3((unsigned)((p.ny + 63) / 64), (unsigned)((p.nz + 15) / 16)), dim3(256), 0, st, p, zr, msz, (ex_x || ex_y) ? 1 : 0);
-  MW_LAUNCH_CHECK();
-  return 0;
-}
-// ... and the neighbours' maps merged in on the exchange stream, for the tracer kernel and everything after it.  (The y launches of the first
-// stage may read either version of a word while this runs: both describe their rows correctly, the merged one only knows more.)
-static int zero_rows_merge(mw_dycore_s *d, hipStream_t st, bool first_cycle) {
-  if (!d->zr_on) return 0;
-  DyP &p = d->p;
-  const long long msz = d->zr_msz;
-  const bool ex_x = d->xchg && p.nproc_x > 1, ex_y = d->xchg && p.nproc_y > 1;
-  const long long nrow = (long long)p.nz * p.ny, nedge = (long long)p.nz * MW_ZR_HALO;
-  const long long dWE = (nrow + 1) / 2, dSN = (nedge + 1) / 2;
-  unsigned *const zr = d->zr + (long long)d->zr_cur * MW_ZR_MAPS * msz;
-  ProfScope ps(d, 4, st);
-  if (ex_x || ex_y) {
-    double *rW = d->zrx + dWE, *rE = d->zrx + 2 * dWE, *sS = d->zrx + 3 * dWE, *sN = sS + dSN, *rS = sN + dSN, *rN = rS + dSN;
-    if (ex_x && d->xchg(d->xchg_ctx, d->zrx, d->zrx, nullptr, nullptr, rW, rE, nullptr, nullptr, dWE, 0, st)) MW_FAIL("zero-row maps: exchange callback failed");
-    MW_KLAUNCH(k_zero_merge, dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, st, p, (const unsigned *)d->zrx, ex_x ? (const unsigned *)rW : nullptr, (const unsigned *)rE, zr,
-               ex_y ? (unsigned *)sS : nullptr, (unsigned *)sN);
-    MW_LAUNCH_CHECK();
-    if (ex_y) {
-      if (d->xchg(d->xchg_ctx, nullptr, nullptr, sS, sN, nullptr, nullptr, rS, rN, 0, dSN, st)) MW_FAIL("zero-row maps: exchange callback failed");
-      MW_KLAUNCH(k_zero_halo, dim3((unsigned)((nedge + 255) / 256)), dim3(256), 0, st, p, zr, (const unsigned *)rS, (const unsigned *)rN);
-      MW_LAUNCH_CHECK();
-    }
-  }
-  if (first_cycle) MW_HIP(hipMemcpyAsync(d->zr + 2 * MW_ZR_MAPS * msz, zr, (size_t)msz * sizeof(unsigned), hipMemcpyDeviceToDevice, st));
-  if (ex_x || ex_y) { MW_KLAUNCH(k_zero_dilate, dim3((unsigned)((p.ny + 63) / 64), (unsigned)((p.nz + 15) / 16)), dim3(256), 0, st, p, zr, msz, 0); MW_LAUNCH_CHECK(); }
-  return 0;
-}
-// ... and handed to the kernels of RK stage `stage` (1..3) through the parameter block
-static void zero_rows_stage(mw_dycore_s *d, int stage) {
-  DyP &p = d->p;
-  p.zqk = nullptr;
-  if (!d->zr_on || stage < 1) { p.zq = p.zqp = p.zqc = nullptr; p.zq_ld = 0; return; }
-  const long long set = (long long)MW_ZR_MAPS * d->zr_msz;
-  p.zq = d->zr + d->zr_cur * set + (long long)stage * d->zr_msz;
-  p.zqp = (d->zr_prev_use && stage <= 2) ? d->zr + (d->zr_cur ^ 1) * set + (long long)stage * d->zr_msz : nullptr;   // (S1, S2: the slab of stage s is always the same one)
-  p.zqc = (d->o.zero_stores && !d->member_major) ? d->zr + 2 * set : nullptr;      // (member-major: the coupler's arrays are written by launches that read no maps)
-  // (member-major: these are member 0's; view() moves them on to its member)
-  p.zq_ld = p.ny + 2 * MW_ZR_HALO;
-}
-// The converting y launch (first stage of a time step, conversion inside k_y_all) writes slab S: before it, hand over what is known about S's
-// rows (written by the last conversion into S, untouched since); after it (`done`), S's rows are zero exactly where the coupler's are: map MC.
-static void zero_rows_conv(mw_dycore_s *d, const double *S, bool done, hipStream_t st) {
-  const long long msz = d->zr_msz;
-  int sl = (d->kz_buf[0] == S) ? 0 : (d->kz_buf[1] == S) ? 1 : -1;
-  if (!done) { d->p.zqk = (sl >= 0 && d->zr_on && d->o.zero_stores) ? d->zr + (2 * MW_ZR_MAPS + 1 + sl) * msz : nullptr; return; }
-  d->p.zqk = nullptr;
-  if (!d->zr_on) { if (sl >= 0) d->kz_buf[sl] = nullptr; return; }
-  if (sl < 0) {                                                 // a free slot, else the one of a slab that is not one of the two q^n slabs any more
-    const double *other = (S == d->S0) ? d->S3 : d->S0;
-    sl = (d->kz_buf[0] == nullptr) ? 0 : (d->kz_buf[1] == nullptr) ? 1 : (d->kz_buf[0] != other) ? 0 : 1;
-  }
-  (void)hipMemcpyAsync(d->zr + (2 * MW_ZR_MAPS + 1 + sl) * msz, d->zr + 2 * MW_ZR_MAPS * msz, (size_t)msz * sizeof(unsigned), hipMemcpyDeviceToDevice, st);
-  d->kz_buf[sl] = S;
-}
-void zero_rows_forget(mw_dycore_s *d, const double *S) {   // slab S is about to be written by something that keeps no map
-  for (int i = 0; i < 2; i++) if (!S || d->kz_buf[i] == S) d->kz_buf[i] = nullptr;
+template <int STAGE, int MODE>   // one RK stage on the handle's schedule
+static int rk_stage(mw_dycore_s *d, double *Sin, const double *Sn, double *Sout, double dt_stage, double dt_dyn, const CouplerPtrs &c) {
+  return d->pipe ? rk_stage_pipe<STAGE, MODE>(d, Sin, Sn, Sout, dt_stage, dt_dyn, c) : rk_stage_march<STAGE, MODE>(d, Sin, Sn, Sout, dt_stage, dt_dyn, c);
 }
 // One SSPRK3 sub-cycle.  Slabs: Q[0] = q^n, Q[1..3] scratch; on return the new q^n is in Q[3] (caller rotates).
 int rk_cycle_march(mw_dycore_s *d, double **Q, double dt_dyn, bool last, const CouplerPtrs &c) {
   const double dt2 = (1.0 / 4.0) * dt_dyn, dt3 = (2.0 / 3.0) * dt_dyn;
-  d->zr_on = false;
+  d->zr.on = false;
+  if (d->pipe) { d->pipe_ready = false; d->pipe_edge_done = false; }   // blocks of a decomposed domain, pipelined schedule
   if (!d->pipe && !d->member_major && zero_rows_build(d, Q[0], c, d->conv_pending, d->stream, d->first_cycle)) return 1;   // (pipelined schedule: inside its first stage, on the exchange stream; member-major: behind the first y launch, from the slab)
-  if (d->pipe) {                                              // blocks of a decomposed domain, pipelined schedule
-    d->pipe_ready = false; d->pipe_edge_done = false;
-    if (rk_stage_pipe<1, 0>(d, Q[0], Q[0], Q[1], dt_dyn, dt_dyn, c)) return 1;
-    if (rk_stage_pipe<2, 0>(d, Q[1], Q[0], Q[2], dt2, dt_dyn, c)) return 1;
-    const bool pass13p = d->member_major && !d->mm_direct;
-    if (last && !pass13p) { if (rk_stage_pipe<3, 1>(d, Q[2], Q[0], Q[3], dt3, dt_dyn, c)) return 1; }
-    else                  { if (rk_stage_pipe<3, 0>(d, Q[2], Q[0], Q[3], dt3, dt_dyn, c)) return 1; }
-    if (last && pass13p) {
-      ProfScope ps(d, 4, d->stream);
-      const View v = view(d, 0);
-      const MemberStrides ms = {v.p.sJ, v.p.sK, v.p.sV, v.slab};
-      MW_KLAUNCH(k_member_to_coupler, plane_grid((long long)d->p.ny * d->p.nx * d->p.nens, d->p.nz), dim3(256), 0, d->stream, d->p, Q[3], c, ms);
-      MW_LAUNCH_CHECK();
-    }
-    d->flux_src = Q[2]; d->flux_dt = dt3;
-    d->zr_prev_ok = d->zr_on; d->zr_on = false; zero_rows_stage(d, 0);
-    return 0;
-  }
-  if (rk_stage_march<1, 0>(d, Q[0], Q[0], Q[1], dt_dyn, dt_dyn, c)) return 1;                        // stage 1 (:119-132)
-  if (rk_stage_march<2, 0>(d, Q[1], Q[0], Q[2], dt2, dt_dyn, c)) return 1;                           // stage 2 (:136-153)
+  if (rk_stage<1, 0>(d, Q[0], Q[0], Q[1], dt_dyn, dt_dyn, c)) return 1;                        // stage 1 (:119-132)
+  if (rk_stage<2, 0>(d, Q[1], Q[0], Q[2], dt2, dt_dyn, c)) return 1;                           // stage 2 (:136-153)
   const bool pass13 = d->member_major && !d->mm_direct;        // D13 as a pass over the result slab
-  if (last && !pass13) { if (rk_stage_march<3, 1>(d, Q[2], Q[0], Q[3], dt3, dt_dyn, c)) return 1; }   // stage 3 (:157-174) + :178
-  else                 { if (rk_stage_march<3, 0>(d, Q[2], Q[0], Q[3], dt3, dt_dyn, c)) return 1; }
+  if (last && !pass13) { if (rk_stage<3, 1>(d, Q[2], Q[0], Q[3], dt3, dt_dyn, c)) return 1; }   // stage 3 (:157-174) + :178
+  else                 { if (rk_stage<3, 0>(d, Q[2], Q[0], Q[3], dt3, dt_dyn, c)) return 1; }
   if (last && pass13) {                              // D13 (:178) as one coalesced pass over the result slab
-    hipStream_t ts = d->overlap ? d->tstream : d->stream;     // the tracer pipeline finishes the stage
+    hipStream_t ts = d->overlap ? d->tstream : d->stream;     // the tracer pipeline finishes the stage (the pipelined schedule has none: overlap == 0)
     ProfScope ps(d, 4, ts);
     const View v = view(d, 0);
     const MemberStrides ms = {v.p.sJ, v.p.sK, v.p.sV, v.slab};
@@ -438,7 +215,7 @@ int rk_cycle_march(mw_dycore_s *d, double **Q, double dt_dyn, bool last, const C
     if (d->overlap) MW_HIP(hipEventRecord(d->ev_tr[(d->gstage - 1) & 7], ts));     // the step's join waits for this event
   }
   d->flux_src = Q[2]; d->flux_dt = dt3;
-  d->zr_prev_ok = d->zr_on; d->zr_on = false; zero_rows_stage(d, 0);
+  zero_rows_end_cycle(d);
   return 0;
 }
 
@@ -461,30 +238,6 @@ int launch_coupler_to_slab(mw_dycore_s *d, const CouplerPtrs &c, int ylo, int yh
 }
 
 extern "C" {
-// Test aid: the zero-row maps of the last sub-cycle, on the host (include/mw_cdna4.h).
-long long mw_debug_zero_maps(mw_dycore_t d, unsigned int *out_host, long long cap_words, int *dims2) {
-  if (!d) return 0;
-  if (!d->zr || !d->zr_prev_ok || d->member_major) return 0;    // (zr_prev_ok: the last sub-cycle ran with maps; member-major handles keep one set per member)
-  (void)hipStreamSynchronize(d->stream);
-  if (d->tstream) (void)hipStreamSynchronize(d->tstream);
-  const long long n = (long long)MW_ZR_MAPS * d->zr_msz;
-  if (dims2) { dims2[0] = d->p.nz; dims2[1] = d->p.ny + 2 * MW_ZR_HALO; }
-  if (out_host && cap_words > 0)
-    (void)hipMemcpy(out_host, d->zr + (long long)d->zr_cur * n, (size_t)std::min(n, cap_words) * sizeof(unsigned), hipMemcpyDeviceToHost);
-  return n;
-}
-// Test aid: the four violation counters of option zero_verify (k_zero_verify, mw_march.h) since the handle was created; -1: the option
-// never ran.  out4: [0] input row non-zero under a clear Qs word, [1] ... under a clear QYs word, [2] a destination row the tracer kernel
-// was told holds zeros does not, [3] likewise a row of the slab the converting y launch fills.
-long long mw_debug_zero_violations(mw_dycore_t d, unsigned long long *out4) {
-  if (!d || !d->zviol) return -1;
-  (void)hipStreamSynchronize(d->stream);
-  if (d->tstream) (void)hipStreamSynchronize(d->tstream);
-  unsigned long long h[4] = {0, 0, 0, 0};
-  if (hipMemcpy(h, d->zviol, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  if (out4) for (int i = 0; i < 4; i++) out4[i] = h[i];
-  return (long long)(h[0] + h[1] + h[2] + h[3]);
-}
 // Test aid: the fused tracer stage's per-cell flag bytes as its last launch left them (bits 2v / 2v + 1: tracer v's south / north face was
 // scaled by this cell), index (k * ny + j) * nx * nens + x.  Returns the number of cells; copies at most `cap` bytes to out_host.
 long long mw_debug_tracer_flags(mw_dycore_t d, unsigned char *out_host, long long cap) {

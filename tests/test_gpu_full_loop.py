@@ -134,7 +134,7 @@ def test_default_2d_run_reaches_the_recorded_state_at_step_800(mw):
 
 
 def test_zero_row_maps_through_a_developing_storm(mw):
-    """The zero-row maps (option zero_rows, mw_march.h: k_zero_rows) under the real thing: the complete supercell loop in 3-D -- dycore,
+    """The zero-row maps (option zero_rows, mw_zero_rows.hip: k_zero_rows) under the real thing: the complete supercell loop in 3-D -- dycore,
     Kessler, sponge, nudger -- from the cloud-free initial state through the first condensation to a storm with cloud and rain, two handles in
     lockstep, one with the maps and one without.  Every field equal at every 25th step and at the end (the maps are a superset of where
     cloud and rain are, whatever Kessler creates between two dycore steps); on the way the map-driven lean form must have been in use

@@ -358,7 +358,19 @@ def _specks(coupler, nxg, nyg, nz, extra=()):
     dm.get("precip_liquid").copy_(pr * rho)
 
 
-def _specks_blocks(layout, zero_rows, fuzz, nz=12, extra=(), factors=(1.0, 2.3, 1.0)):
+def _zero_maps(dycore):
+    """The ten maps of the handle's last sub-cycle (mw_debug_zero_maps), (10, nz, ny + 18)."""
+    from miniweatherml_amd import capi
+    L, dims = capi.lib(), (C.c_int * 2)()
+    n = L.mw_debug_zero_maps(dycore.h, None, 0, dims)
+    assert n > 0 and n == 10 * dims[0] * dims[1]
+    buf = np.zeros(n, dtype=np.uint32)
+    assert L.mw_debug_zero_maps(dycore.h, buf.ctypes.data_as(C.c_void_p), n, dims) == n
+    return buf.reshape(10, dims[0], dims[1])
+
+
+def _specks_blocks(layout, zero_rows, fuzz, nz=12, extra=(), factors=(1.0, 2.3, 1.0), opts=None, maps=None):
+    """opts: options set on every rank's dycore before the exchange is installed; maps (a list): takes every rank's _zero_maps at the end."""
     from miniweatherml_amd import capi, modules
     from util import StreamExchanger
     nranks, nxg, nyg = layout
@@ -372,6 +384,8 @@ def _specks_blocks(layout, zero_rows, fuzz, nz=12, extra=(), factors=(1.0, 2.3, 
             _specks(coupler, nxg, nyg, nz, extra)
             dycore.set_option("zero_rows", zero_rows)
             dycore.set_option("zero_verify", zero_rows)              # (every claim of the maps against the data, on every block)
+            for name, val in (opts or {}).items():
+                dycore.set_option(name, val)
             cb = ex.make_cb(rank, coupler.grid)
             keep.append(cb)
             capi.check(capi.lib().mw_dycore_set_exchange(dycore.h, cb, None))
@@ -380,6 +394,8 @@ def _specks_blocks(layout, zero_rows, fuzz, nz=12, extra=(), factors=(1.0, 2.3, 
                 dycore.time_step(coupler, dt * factors[n])
             torch.cuda.synchronize()
             results[rank] = (coupler.grid.i_beg, coupler.grid.j_beg, gpu_fields(coupler), dycore.path())
+            if maps is not None:
+                maps[rank] = _zero_maps(dycore)
             if zero_rows:
                 nviol, kinds = dycore.zero_violations()
                 if nviol != 0:
@@ -418,7 +434,7 @@ def test_zero_row_maps_on_random_decompositions(mw, seed):
 
 @pytest.mark.parametrize("layout", [(4, 96, 64), (8, 160, 40), (2, 40, 72), (2, 40, 31), (4, 96, 31)])
 def test_zero_row_maps_on_decomposed_blocks(mw, layout):
-    """The zero-row maps (mw_march.h: k_zero_rows) of a decomposed domain: every block ORs its neighbours' maps into its own (k_zero_merge:
+    """The zero-row maps (mw_zero_rows.hip: k_zero_rows) of a decomposed domain: every block ORs its neighbours' maps into its own (k_zero_merge:
     west / east, whole rows; k_zero_halo: the south / north neighbours' edge rows, two small messages per sub-cycle through the halo
     transport).  Cloud and rain are single cells next to the seams and in the corners, so whether a block's wave may skip a row is decided
     by what the NEIGHBOUR holds; the transport delays its copies at random.  Same bits as the same decomposition WITHOUT the maps; three
@@ -438,3 +454,38 @@ def test_zero_row_maps_on_decomposed_blocks(mw, layout):
             assert np.array_equal(a, ref[k]), (k, ib, jb)
         nonzero += int((ref["tracer1"] != 0).sum()); cells += ref["tracer1"].size
     assert 0 < nonzero < (0.5 if layout[2] >= 40 else 1.0) * cells      # (the 31-row layouts are small: the seam cells' cloud reaches most of them)
+
+
+_MAPS_ON = {}      # (layout, options) -> (results, maps) of the run with maps: computed once, read by the cases that compare against it
+
+
+def _specks_blocks_on(layout, opts):
+    key = (layout, tuple(sorted(opts.items())))
+    if key not in _MAPS_ON:
+        maps = [None] * layout[0]
+        _MAPS_ON[key] = (_specks_blocks(layout, 1, 7, opts=opts, maps=maps), maps)
+    return _MAPS_ON[key]
+
+
+@pytest.mark.parametrize("opts", [{}, {"pipe_maps_early": 0}, {"pipe_split_edges": 0}], ids=["default", "maps_late", "edges_unsplit"])
+@pytest.mark.parametrize("layout", [(2, 40, 72), (4, 96, 64)])
+def test_zero_row_maps_early_and_late_builds(mw, layout, opts):
+    """The two ways a decomposed block gets its maps in the first stage of a sub-cycle: in two halves -- local maps in front of the y launches,
+    the neighbours' merged in behind the strips (the default on blocks of at least 4 * MW_Y_EDGE rows) -- or all at once behind the strips
+    (pipe_maps_early = 0, and pipe_split_edges = 0, which the early maps need).  The smallest layouts with a y seam alone and with x and y seams
+    whose blocks pass that row test.  With each: the maps on, every claim verified (zero_verify, no violations), give the same bits as the maps
+    off in every field of every block; and the merged maps are a function of the sub-cycle's input alone, so the ten maps of every block built
+    all at once equal those built in halves (the blocks' own rows of all ten, and the rows beyond the y edges of M0, which the derived maps do
+    not have)."""
+    on, maps = _specks_blocks_on(layout, opts)
+    off = _specks_blocks(layout, 0, 0, opts=opts)
+    for (ib, jb, blk, path), (ib0, jb0, ref, _) in zip(on, off):
+        assert " pipe " in path and (ib, jb) == (ib0, jb0)
+        for k, a in blk.items():
+            assert np.array_equal(a, ref[k]), (k, ib, jb, opts)
+    if opts == {"pipe_maps_early": 0}:
+        _, halves = _specks_blocks_on(layout, {})
+        for r, (late, early) in enumerate(zip(maps, halves)):
+            assert late.shape == early.shape
+            assert np.array_equal(late[:, :, 9:-9], early[:, :, 9:-9]), ("own rows", r, np.argwhere(late[:, :, 9:-9] != early[:, :, 9:-9])[:4])
+            assert np.array_equal(late[0], early[0]), ("M0 with its halo rows", r)

@@ -122,7 +122,7 @@ def test_zero_tracer_shortcut_is_bit_neutral(mw, case):
 @pytest.mark.parametrize("case", ["cloud_free", "one_storm", "specks", "city", "ord3", "ragged", "nens4", "nens3", "nens2_specks"])
 def test_zero_row_maps_are_bit_neutral(mw, case):
     """Option zero_rows (default 1, round 5): per (level, row) and tracer a bit "may be non-zero", scanned from the sub-cycle's input and
-    dilated by 3 rows / levels per RK stage (mw_march.h: k_zero_rows, k_zero_dilate); k_y_all and k_tracers_fused do not load rows whose bit
+    dilated by 3 rows / levels per RK stage (mw_zero_rows.hip: k_zero_rows, k_zero_dilate); k_y_all and k_tracers_fused do not load rows whose bit
     is clear, k_y_all does not store y fluxes nobody loads.  The maps must be a superset of the non-zero rows: the same bits as with the
     maps switched off, and as with the whole zero short-cut switched off -- on a cloud-free state, on one box of cloud and rain, on single
     non-zero cells in the corners, on the faces and next to the periodic seams (a too small dilation shows here), on the city, at WENO-3;
@@ -280,7 +280,7 @@ def test_zero_row_maps_on_random_configurations(mw, seed):
 
 
 def test_zero_row_maps_are_exactly_what_the_design_says(mw):
-    """The ten maps of a sub-cycle (mw_debug_zero_maps) against a numpy restatement of their definition (mw_march.h): M0 = the rows
+    """The ten maps of a sub-cycle (mw_debug_zero_maps) against a numpy restatement of their definition (mw_zero_rows.h): M0 = the rows
     in which a tracer that can vanish is non-zero (water vapour of the folded supercell configuration: always set), and per RK stage s the OR of
     M0 over 3s rows (periodic) and, for Qs / FNs / QYs, over levels k-3s-5 .. k+3s+1 / k-3s-6 .. k+3s+2 / k-3(s-1) .. k+3(s-1) (clamped).
     Equality both ways: a map that misses a row would be a wrong result (the bit-neutrality tests), a map that marks too much only a slower one
