@@ -2,7 +2,8 @@
 
     capi      ctypes binding of libmw_cdna4.so (include/mw_cdna4.h)
     coupler   host-side mirror of core::Coupler / DataManager
-    modules   Dynamics_Euler_Stratified_WenoFV, Microphysics_Kessler, surrogate MLP, perturb_temperature
+    modules   every host-side module under one name; defined by topic in dycore, exchange, mlp, microphysics, surrogate_eval, rollout,
+              column, ncio, city, sampling and experiments
     build     hipcc build of the shared library (python -m miniweatherml_amd.build)
 """
 from . import capi  # noqa: F401

@@ -19,7 +19,7 @@ Keras HDF5 file named by `keras_weights_h5` is read by the library's own reader 
 (`keras_weights_txt`, tools/export_mlp_weights.sh) is accepted too; without either, the reference's shipped weight file
 (miniweatherml_amd/data/) is used.
 
-evaluate_surrogates scores the networks of a YAML list against the Kessler scheme that runs the simulation (modules.SurrogateEvaluator):
+evaluate_surrogates scores the networks of a YAML list against the Kessler scheme that runs the simulation (surrogate_eval.SurrogateEvaluator):
     surrogate_models:
       - {name: seed0, keras_weights_txt: out/weights_0.txt, nn_input_scaling: out/input_scaling.txt, nn_output_scaling: out/output_scaling.txt}
       - ...                                   # (keras_weights_h5 instead of keras_weights_txt for a Keras file; both widths may be mixed)
@@ -27,20 +27,20 @@ evaluate_surrogates scores the networks of a YAML list against the Kessler schem
 and writes surrogate_evaluation.json (the report and the per-call history) into the working directory.  One rank only.
 
 rollout_surrogates reads the same list and runs every network ONLINE, as an ensemble member of its own beside Kessler (member 0; members
-1 .. K the list's models in its order, modules.Microphysics_Rollout): each member's output is fed back through the dycore, and every
-eval_interval-th step all eight coupler fields of every member are scored against the Kessler member (modules.RolloutScorer).
+1 .. K the list's models in its order, rollout.Microphysics_Rollout): each member's output is fed back through the dycore, and every
+eval_interval-th step all eight coupler fields of every member are scored against the Kessler member (rollout.RolloutScorer).
     persistence_member: true                  # a last member without microphysics, the skill's denominator (default true)
 nens is derived from the list (1 + K, + 1 with the persistence member); a `nens:` key that disagrees is an error.  Writes
 surrogate_rollout.json.  One rank only.
     harvest: {interval: 10, samples_per_step: 50, ratio_active: 0.5, seed: 1, max_rainsplit: 64, members: [seed0]}
-adds data aggregation to the rollout (modules.RolloutHarvester): every interval-th step (default eval_interval) Kessler is asked what it
+adds data aggregation to the rollout (rollout.RolloutHarvester): every interval-th step (default eval_interval) Kessler is asked what it
 would have done to each listed model member's OWN state (default: all models), and samples of that go to rollout_samples_<name>.nc in the
 working directory -- DataGenerator's format, so `surrogate_train --init DIR` continues a model on the old and the new files together.
     surrogate_committees:
       - {name: mean3, members: [seed0, seed1, seed2]}      # 1 .. 16 models of the list above, all of one width
-makes committees of the listed models (committee_config; modules.SurrogateBank.committee_apply: the mean of the members' outputs in the
+makes committees of the listed models (committee_config; surrogate_eval.SurrogateBank.committee_apply: the mean of the members' outputs in the
 listed order, and their range).  rollout_surrogates rolls each committee out as one more member after the models (nens counts them; a
-committee cannot be harvested), evaluate_surrogates scores each one (modules.CommitteeEvaluator; `committees` in the JSON and the table),
+committee cannot be harvested), evaluate_surrogates scores each one (surrogate_eval.CommitteeEvaluator; `committees` in the JSON and the table),
 and inference_ponni runs the committee instead of one network when the YAML names exactly one and no keras_weights_* key.
 """
 import argparse
@@ -241,15 +241,15 @@ def _surrogate_models(entries, yaml_dir):
 
 def _surrogate_evaluator(entries, device):
     """One bank per width, in the order the widths first appear; the models' names bank after bank."""
-    from . import modules
-    weights = modules.load_surrogate_bank(entries)
+    from . import mlp, surrogate_eval
+    weights = mlp.load_surrogate_bank(entries)
     widths = []
     for w in weights:
         if w[0].shape[0] not in widths:
             widths.append(w[0].shape[0])
     order = [i for n_in in widths for i, w in enumerate(weights) if w[0].shape[0] == n_in]
-    banks = [modules.SurrogateBank([w for w in weights if w[0].shape[0] == n_in], device) for n_in in widths]
-    return modules.SurrogateEvaluator(banks, [entries[i]["name"] for i in order]), [entries[i] for i in order]
+    banks = [surrogate_eval.SurrogateBank([w for w in weights if w[0].shape[0] == n_in], device) for n_in in widths]
+    return surrogate_eval.SurrogateEvaluator(banks, [entries[i]["name"] for i in order]), [entries[i] for i in order]
 
 
 def _distributed(device):
@@ -287,8 +287,8 @@ def _coupler(cfg, device, nranks, myrank, yaml_path):
 
 
 def _exchange(dycore, coupler):
-    from . import modules
-    return modules.install_exchange(dycore, coupler)             # all ranks agree on one transport (RCCL, else torch p2p)
+    from . import exchange
+    return exchange.install_exchange(dycore, coupler)            # all ranks agree on one transport (RCCL, else torch p2p)
 
 
 def _time_loop(cfg, dycore, coupler, body, max_steps):
@@ -308,7 +308,8 @@ def _time_loop(cfg, dycore, coupler, body, max_steps):
 
 def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
     import torch
-    from . import modules
+    from . import city, column, microphysics, mlp, rollout, sampling, surrogate_eval
+    from .dycore import Dynamics_Euler_Stratified_WenoFV, perturb_temperature
     if experiment not in EXPERIMENTS:
         raise ValueError("unknown experiment %r (one of %s)" % (experiment, ", ".join(EXPERIMENTS)))
     cfg = load_config(yaml_path)
@@ -333,11 +334,11 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
         committees = committee_config(cfg)
         cfg["surrogate_models"], cfg["eval_interval"], cfg["persistence_member"], cfg["nens"] = rollout_config(cfg)
     coupler = _coupler(cfg, device, nranks, myrank, yaml_path)
-    dycore = modules.Dynamics_Euler_Stratified_WenoFV()
+    dycore = Dynamics_Euler_Stratified_WenoFV()
     info = {"experiment": experiment, "nranks": nranks}
     t_main = time.perf_counter()
     if experiment == "simple_city":
-        horiz_sponge, time_averager = modules.Horizontal_Sponge(), modules.Time_Averager()
+        horiz_sponge, time_averager = city.Horizontal_Sponge(), city.Time_Averager()
         coupler.add_tracer("water_vapor", "water_vapor", True, True)           # simple_city/driver.cpp:55-56
         coupler.get_data_manager_readwrite().get("water_vapor").zero_()
         dycore.init(coupler)
@@ -348,19 +349,19 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
         def body(dt, etime):                                                   # :72-75
             horiz_sponge.apply(coupler, dt, True, True, False, False)
             dycore.time_step(coupler, dt)
-            modules.sponge_layer(coupler, dt, 1)
+            column.sponge_layer(coupler, dt, 1)
             time_averager.accumulate(coupler, dt)
         etime, steps = _time_loop(cfg, dycore, coupler, body, max_steps)
         time_averager.finalize(coupler)                                        # :82 -> time_averaged_fields.nc
     else:
-        column_nudger = modules.ColumnNudger()
+        column_nudger = column.ColumnNudger()
         stats = None
         if experiment == "inference_ponni":
-            micro = modules.Microphysics_Kessler_Surrogate()
+            micro = microphysics.Microphysics_Kessler_Surrogate()
             base = cfg["_dir"]
             if "_committee" in cfg:                                                # the mean of the committee's models is what runs
                 by_name = {m["name"]: m for m in cfg["surrogate_models"]}
-                micro.init(coupler, committee=modules.load_surrogate_bank([by_name[n] for n in cfg["_committee"]["members"]]))
+                micro.init(coupler, committee=mlp.load_surrogate_bank([by_name[n] for n in cfg["_committee"]["members"]]))
 
             def rel(p):
                 return p if p is None or os.path.isabs(p) else os.path.normpath(os.path.join(os.getcwd(), p))
@@ -372,22 +373,22 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
             if "_committee" not in cfg:
                 micro.init(coupler, **kw)
         elif experiment == "rollout_surrogates":
-            micro = modules.Microphysics_Rollout()
-            micro.init(coupler, modules.load_surrogate_bank(cfg["surrogate_models"]), cfg["persistence_member"],
+            micro = rollout.Microphysics_Rollout()
+            micro.init(coupler, mlp.load_surrogate_bank(cfg["surrogate_models"]), cfg["persistence_member"],
                        [m["name"] for m in cfg["surrogate_models"]], [(c["name"], c["members"]) for c in committees])
         else:
-            micro = modules.Microphysics_Kessler()
+            micro = microphysics.Microphysics_Kessler()
             micro.init(coupler)                                                # supercell_example/driver.cpp:58
         dycore.init(coupler)                                                   # :59
         _exchange(dycore, coupler)
         column_nudger.set_column(coupler)                                      # :60
-        modules.perturb_temperature(coupler)                                   # :61
+        perturb_temperature(coupler)                                           # :61
         from .coupler import Coupler
         datagen = None
         if experiment == "gather_statistics":
-            stats = modules.StatisticsGatherer()
+            stats = sampling.StatisticsGatherer()
         if experiment == "generate_micro_data":
-            datagen = modules.DataGenerator()
+            datagen = sampling.DataGenerator()
             datagen.init(coupler, os.getcwd())                                 # generate_micro_data.cpp:66
             info["samples"] = 0
         evaluator, eval_calls, eval_step = None, [], [0]
@@ -399,12 +400,12 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                 first = 0
                 for bank in evaluator.banks:
                     if first <= places[0] < first + bank.models:
-                        committee_evals.append((c, modules.CommitteeEvaluator(bank, [i - first for i in places])))
+                        committee_evals.append((c, surrogate_eval.CommitteeEvaluator(bank, [i - first for i in places])))
                     first += bank.models
-        scorer = modules.RolloutScorer(micro.member_names) if experiment == "rollout_surrogates" else None
+        scorer = rollout.RolloutScorer(micro.member_names) if experiment == "rollout_surrogates" else None
         harvester = None
         if experiment == "rollout_surrogates" and harvest is not None:
-            harvester = micro.harvester = modules.RolloutHarvester()
+            harvester = micro.harvester = rollout.RolloutHarvester()
             harvester.init(coupler, harvest["members"], [micro.member_names.index(n) for n in harvest["members"]], os.getcwd(),
                            harvest["samples_per_step"], harvest["ratio_active"], seed=harvest["seed"], max_rainsplit=harvest["max_rainsplit"])
 
@@ -438,7 +439,7 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                     d = micro.mean_diffs(coupler)                              # microphysics_kessler_ponni.h:266-269
                     print("Relative diff rho_v: %r\nRelative diff rho_c: %r\nRelative diff rho_r: %r\nRelative diff temp : %r" %
                           (d["rho_v"], d["rho_c"], d["rho_r"], d["temp"]), flush=True)
-            modules.sponge_layer(coupler, dt)
+            column.sponge_layer(coupler, dt)
             column_nudger.nudge_to_column(coupler, dt)                         # (eager: the scorer reads the nudged fields)
             if scorer is not None:
                 if eval_step[0] % cfg["eval_interval"] == 0:
@@ -464,8 +465,8 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
             doc = {"experiment": experiment, "yaml": os.path.abspath(yaml_path), "eval_interval": cfg["eval_interval"], "steps": steps,
                    "models": [dict(m, bank=ib, n_in=b.n_in) for ib, b in enumerate(evaluator.banks)
                               for m in eval_models[sum(x.models for x in evaluator.banks[:ib]):][:b.models]],
-                   "statistics": ["sum_d", "sum_abs_d", "sum_d2", "max_abs_d"], "fields": list(modules.EVAL_FIELDS),
-                   "classes": list(modules.EVAL_CLASSES), "report": rep,
+                   "statistics": ["sum_d", "sum_abs_d", "sum_d2", "max_abs_d"], "fields": list(surrogate_eval.EVAL_FIELDS),
+                   "classes": list(surrogate_eval.EVAL_CLASSES), "report": rep,
                    "history": [dict(c, banks=h) for c, h in zip(eval_calls, evaluator.history)]}
             if committee_evals:
                 doc["committees"] = [dict(c, n_in=ce.bank.n_in, statistics=["sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_r", "sum_r2", "sum_r_abs_d"],
@@ -484,7 +485,7 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
             rep = scorer.report() if scorer.times else {"times": [], "diverged_at": dict(scorer.diverged_at)}
             doc = {"experiment": experiment, "yaml": os.path.abspath(yaml_path), "eval_interval": cfg["eval_interval"], "steps": steps,
                    "members": list(scorer.member_names), "models": [dict(m, member=1 + k) for k, m in enumerate(cfg["surrogate_models"])],
-                   "fields": list(scorer.fields), "statistics": list(modules.ROLLOUT_STATS), "history": scorer.history,
+                   "fields": list(scorer.fields), "statistics": list(rollout.ROLLOUT_STATS), "history": scorer.history,
                    "report": rep["times"], "diverged_at": rep["diverged_at"]}
             if committees:
                 doc["committees"] = [dict(c, member=scorer.member_names.index(c["name"])) for c in committees]

@@ -1,0 +1,142 @@
+"""The microphysics in charge of a run, thin drivers of mw_kessler_time_step and of the surrogate's forward passes:
+
+  Microphysics_Kessler               model/modules/microphysics_kessler.h:8-346
+  Microphysics_Kessler_Surrogate     experiments/supercell_kessler_surrogate/custom_modules/microphysics_kessler_ponni.h:149-278
+
+No arithmetic happens in Python: everything runs in libmw_cdna4.so on the GPU (no fallback)."""
+import ctypes as C
+
+import torch
+
+from . import capi
+from ._ffi import _ptr, _stream_ptr, grown_workspace
+from .capi import check
+from .coupler import endrun
+from .mlp import load_surrogate_weights, mlp_forward, mlp_stencil_forward
+from .surrogate_eval import SurrogateBank
+
+
+class Microphysics_Kessler:
+    num_tracers = 3
+    ID_V, ID_C, ID_R = 0, 1, 2
+
+    def __init__(self):                                                        # microphysics_kessler.h:29-41
+        self.R_d, self.cp_d = 287., 1003.
+        self.cv_d = self.cp_d - self.R_d
+        self.gamma_d = self.cp_d / self.cv_d
+        self.kappa_d = self.R_d / self.cp_d
+        self.R_v, self.cp_v = 461., 1859.
+        self.cv_v = self.R_v - self.cp_v
+        self.p0, self.grav = 1.e5, 9.81
+        self._ws = None
+        self.strict = 0          # 1: the strict path (reference operation order, glibc's pow / exp): bit-identical to the CPU oracle
+
+    def set_strict(self, strict):
+        self.strict = int(bool(strict))
+
+    @staticmethod
+    def get_num_tracers():
+        return 3
+
+    def micro_name(self):
+        return "kessler"
+
+    def init(self, coupler):                                                   # :51-96
+        coupler.add_tracer("water_vapor", "Water Vapor", True, True)
+        coupler.add_tracer("cloud_liquid", "Cloud liquid", True, True)
+        coupler.add_tracer("precip_liquid", "precip_liquid", True, True)
+        dm = coupler.get_data_manager_readwrite()
+        dm.register_and_allocate("precl", "precipitation rate", (coupler.get_ny(), coupler.get_nx(), coupler.get_nens()),
+                                 ["y", "x", "nens"])
+        coupler.set_option("micro", "kessler")
+        for k in ("R_d", "cp_d", "cv_d", "gamma_d", "kappa_d", "R_v", "cp_v", "cv_v", "p0", "grav"):
+            coupler.set_option(k, getattr(self, k))
+
+    def time_step(self, coupler, dt, return_rainsplit=False):                  # :99-162
+        dm = coupler.get_data_manager_readwrite()
+        rho_v, rho_c, rho_r = dm.get("water_vapor"), dm.get("cloud_liquid"), dm.get("precip_liquid")
+        rho_d, temp, precl = dm.get("density_dry", readonly=True), dm.get("temp"), dm.get("precl")
+        nz = coupler.get_nz()
+        ncol = coupler.get_ny() * coupler.get_nx() * coupler.get_nens()
+        L = capi.lib()
+        ws = grown_workspace(self, "_ws", L.mw_kessler_workspace_bytes(nz, ncol), coupler.device)
+        rs = C.c_int(0)
+        check(L.mw_kessler_set_strict(self.strict))
+        with torch.cuda.device(coupler.device):
+            check(L.mw_kessler_time_step(nz, ncol, coupler.get_dz(), float(dt), _ptr(rho_v), _ptr(rho_c), _ptr(rho_r), _ptr(rho_d),
+                                         _ptr(temp), _ptr(precl), _ptr(ws), C.byref(rs) if return_rainsplit else None,
+                                         _stream_ptr(coupler.device)))
+        return rs.value if return_rainsplit else None
+
+
+class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
+    """custom_modules::Microphysics_Kessler of the surrogate experiment: NN inference beside the true Kessler
+    (microphysics_kessler_ponni.h:149-278).  The NN result is returned (and diffed) but not written back,
+    exactly like the reference with lines :273-276 commented out."""
+
+    online = False        # True = the four deep_copy_to lines :273-276 un-commented: the NN result replaces Kessler's
+    mlp_strict = 0        # 1: the thread-per-cell MLP that accumulates in index order (bit-identical to the CPU restatement; tests)
+
+    want_range = False    # with a committee: time_step also fills last_range, the four fields of the members' spread
+    last_range = None
+
+    def init(self, coupler, weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None, committee=None):
+        """committee: a list of 1 .. 16 (W1, b1, W2, b2, scl_in, scl_out) tuples of one width (load_surrogate_weights' form).  The network's
+        result is then the committee's mean (SurrogateBank.committee_apply), and the weight file arguments are not read."""
+        super().init(coupler)
+        self._nn_out = None
+        self._committee = None
+        if committee is not None:
+            committee = list(committee)
+            if any(k is not None for k in (weights_txt, in_scaling_txt, out_scaling_txt, weights_h5)):
+                endrun("Microphysics_Kessler_Surrogate: a committee brings its own weights and scaling tables: give no file beside it")
+            if not 1 <= len(committee) <= capi.MW_COMMITTEE_MAX_MODELS:
+                endrun("Microphysics_Kessler_Surrogate: a committee has 1 to %d models, got %d" % (capi.MW_COMMITTEE_MAX_MODELS, len(committee)))
+            self._committee = SurrogateBank(committee, coupler.device)
+            self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out = committee[0]
+            return
+        self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out = load_surrogate_weights(weights_txt, in_scaling_txt,
+                                                                                              out_scaling_txt, weights_h5)
+
+    def time_step(self, coupler, dt):
+        dm = coupler.get_data_manager_readwrite()
+        temp, rho_d = dm.get("temp"), dm.get("density_dry", readonly=True)
+        rho_v, rho_c, rho_r = dm.get("water_vapor"), dm.get("cloud_liquid"), dm.get("precip_liquid")
+        if getattr(self, "_committee", None) is not None:
+            if self._nn_out is None:
+                self._nn_out = [torch.empty_like(temp) for _ in range(4)]
+            if self.want_range and self.last_range is None:
+                self.last_range = [torch.empty_like(temp) for _ in range(4)]
+            self._committee.strict = self.mlp_strict
+            # the coupler's fields are (nz, ny, nx, nens): every member is one more column, so the whole array is one member of nens = 1
+            flat = [t.reshape(coupler.get_nz(), -1, 1) for t in (temp, rho_d, rho_v, rho_c, rho_r)]
+            self._committee.committee_apply(coupler.get_nz(), range(self._committee.models), 0, flat,
+                                            [t.reshape(coupler.get_nz(), -1, 1) for t in self._nn_out],
+                                            [t.reshape(coupler.get_nz(), -1, 1) for t in self.last_range] if self.want_range else None)
+        elif self.W1.shape[0] == 9:                                            # the stencil model: what load_surrogate_weights found
+            self._nn_out = mlp_stencil_forward(coupler.get_nz(), temp, rho_d, rho_v, rho_c, rho_r, self.W1, self.b1, self.W2, self.b2,
+                                               self.scl_in, self.scl_out, self._nn_out, strict=self.mlp_strict)
+        else:
+            self._nn_out = mlp_forward(temp, rho_d, rho_v, rho_c, rho_r, self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out,
+                                       self._nn_out, strict=self.mlp_strict)
+        super().time_step(coupler, dt)
+        if self.online:                                                        # :273-276
+            self._diffs = self.mean_diffs(coupler)                             # (the prints of :266-269 come first)
+            for dst, src in zip((temp, rho_v, rho_c, rho_r), self._nn_out):
+                dst.copy_(src)
+        return self._nn_out            # (temp_tmp, rho_v_tmp, rho_c_tmp, rho_r_tmp)
+
+    def mean_diffs(self, coupler):
+        """The four 'Relative diff' prints (:266-269): mean(NN - Kessler)."""
+        dm = coupler.get_data_manager_readonly()
+        t, v, c, r = self._nn_out
+        if getattr(self, "_ws_mean", None) is None:
+            self._ws_mean = torch.empty(1024, dtype=torch.float64, device=coupler.device)
+        out = {}
+        with torch.cuda.device(coupler.device):
+            for key, nn, name in (("rho_v", v, "water_vapor"), ("rho_c", c, "cloud_liquid"), ("rho_r", r, "precip_liquid"), ("temp", t, "temp")):
+                m = C.c_double(0.0)
+                check(capi.lib().mw_mean_diff(nn.numel(), _ptr(nn), _ptr(dm.get(name, True)), _ptr(self._ws_mean), C.byref(m),
+                                              _stream_ptr(coupler.device)))
+                out[key] = m.value
+        return out

@@ -1,0 +1,167 @@
+"""The Kessler surrogate network: its weight files and its forward passes, thin drivers of mw_mlp_* / mw_ponni_forward.
+
+  load_h5_weights, load_surrogate_weights   experiments/supercell_kessler_surrogate/custom_modules/microphysics_kessler_ponni.h:97-135
+  mlp_forward, mlp_stencil_forward          model.forward_batch_parallel with the fused scaling, :176-202
+  ponni_forward, _PonniLayer                ponni::create_inference_model / Inference::forward_batch_parallel, :109, :189
+
+IN5 and OUT4 name the network's five input and four output fields in its order; every module that feeds or scores it takes them here."""
+import contextlib
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+
+from . import capi
+from ._ffi import _ptr, _stream_ptr
+from .capi import check
+from .coupler import endrun
+
+_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
+
+IN5 = ("temp", "density_dry", "water_vapor", "cloud_liquid", "precip_liquid")
+OUT4 = ("temp", "water_vapor", "cloud_liquid", "precip_liquid")
+
+
+@contextlib.contextmanager
+def strict_mode(strict):
+    """mw_mlp_set_strict(strict) for the calls inside and 0 again behind them, also when one raises.  The caller checks a call's return
+    code behind the block: the reset comes first."""
+    check(capi.lib().mw_mlp_set_strict(int(bool(strict))))
+    try:
+        yield
+    finally:
+        check(capi.lib().mw_mlp_set_strict(0))
+
+
+# (mlp_forward and mlp_stencil_forward below set the mode with a bare call and leave it set, as they always have -- every forward call sets
+#  its own first.  That is kept on purpose: they do not use strict_mode.)
+def load_h5_weights(fname, group, dataset):
+    """ponni::load_h5_weights<N> (microphysics_kessler_ponni.h:103-107): one float32 dataset of a Keras HDF5 weight file, through the
+    library's dependency-free reader (mw_h5.cpp)."""
+    L = capi.lib()
+    dims, nd = (C.c_longlong * 8)(), C.c_int(0)
+    fb, gb, db = str(fname).encode(), group.encode(), dataset.encode()
+    check(L.mw_h5_read_f32(fb, gb, db, None, 0, dims, C.byref(nd)))
+    shape = tuple(int(dims[i]) for i in range(nd.value))
+    out = np.empty(shape, dtype=np.float32)
+    check(L.mw_h5_read_f32(fb, gb, db, out.ctypes.data_as(C.POINTER(C.c_float)), out.size, dims, C.byref(nd)))
+    return out
+
+
+def load_surrogate_weights(weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None):
+    """The Keras weights + min/max scaling tables (microphysics_kessler_ponni.h:97-135).  weights_h5: the reference's
+    `keras_weights_h5` file, read like ponni::load_h5_weights does (:103-107); weights_txt: a text export of the 104 values
+    (tools/export_mlp_weights.sh).  Default: the reference's shipped weight file (miniweatherml_amd/data/).
+    The model is inferred from the text files: 5 scaling rows + 104 weights = the single-cell model (W1 (5,10)), 9 rows + 144 weights = the
+    two-cell stencil model (W1 (9,10); surrogate_train --stencil).  Any other pairing is refused; so is an .h5 file of a stencil model."""
+    if weights_txt is None and weights_h5 is None:
+        weights_h5 = os.path.join(_DATA, "supercell_kessler_singlecell_model_weights.h5")
+    if weights_h5 is not None:
+        W1 = load_h5_weights(weights_h5, "/dense_6/dense_6", "kernel:0")       # Matvec 1   (in, out) = (5, 10)
+        b1 = load_h5_weights(weights_h5, "/dense_6/dense_6", "bias:0")
+        W2 = load_h5_weights(weights_h5, "/dense_7/dense_7", "kernel:0")       # Matvec 2   (10, 4)
+        b2 = load_h5_weights(weights_h5, "/dense_7/dense_7", "bias:0")
+        if W1.shape != (5, 10) or b1.shape != (10,) or W2.shape != (10, 4) or b2.shape != (4,):
+            endrun("surrogate weight file: expected Dense(5->10) and Dense(10->4) (an .h5 file of the stencil model is not supported: "
+                   "use the text files surrogate_train writes)")
+        nw = 104
+    else:
+        w = np.loadtxt(weights_txt, dtype=np.float64, comments="#").astype(np.float32).ravel()
+        nw = w.size
+    scl_in = np.atleast_2d(np.loadtxt(in_scaling_txt or os.path.join(_DATA, "kessler_surrogate_input_scaling.txt")))
+    rows = scl_in.shape[0] if scl_in.shape[1:] == (2,) else -1
+    if (rows, nw) not in ((5, 104), (9, 144)):
+        endrun("surrogate files: %d input scaling rows with %d weights; expected 5 rows + 104 weights (single-cell model) or 9 rows + 144 "
+               "weights (stencil model)" % (rows if rows >= 0 else scl_in.size // 2, nw))
+    if weights_h5 is None:
+        a = 10 * rows
+        W1, b1, W2, b2 = w[:a].reshape(rows, 10).copy(), w[a:a + 10].copy(), w[a + 10:a + 50].reshape(10, 4).copy(), w[a + 50:a + 54].copy()
+    scl_out = np.loadtxt(out_scaling_txt or os.path.join(_DATA, "kessler_surrogate_output_scaling.txt")).reshape(4, 2)
+    return W1, b1, W2, b2, np.ascontiguousarray(scl_in), np.ascontiguousarray(scl_out)
+
+
+def mlp_forward(temp, rho_d, rho_v, rho_c, rho_r, W1, b1, W2, b2, scl_in, scl_out, outs=None, strict=0):
+    """model.forward_batch_parallel with the fused scaling (microphysics_kessler_ponni.h:176-202).  strict = 1: the thread-per-cell
+    form that accumulates in index order (bit-identical to the CPU restatement) instead of the MFMA kernels."""
+    fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+    if outs is None:
+        outs = [torch.empty_like(temp) for _ in range(4)]
+    check(capi.lib().mw_mlp_set_strict(int(bool(strict))))
+    with torch.cuda.device(temp.device):
+        check(capi.lib().mw_mlp_forward(temp.numel(), _ptr(temp), _ptr(rho_d), _ptr(rho_v), _ptr(rho_c), _ptr(rho_r),
+                                        W1.ctypes.data_as(fp), b1.ctypes.data_as(fp), W2.ctypes.data_as(fp), b2.ctypes.data_as(fp),
+                                        scl_in.ctypes.data_as(dp), scl_out.ctypes.data_as(dp), *[_ptr(o) for o in outs],
+                                        _stream_ptr(temp.device)))
+    return outs
+
+
+def mlp_stencil_forward(nz, temp, rho_d, rho_v, rho_c, rho_r, W1, b1, W2, b2, scl_in, scl_out, outs=None, strict=0):
+    """mlp_forward for the two-cell stencil model (W1 (9,10), scl_in (9,2)): the fields are whole coupler arrays (nz, ...) and features
+    5..8 come from level min(nz - 1, k + 1) of the same column (stencil_features states the order).  The outputs never alias the inputs."""
+    fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+    if W1.shape != (9, 10) or scl_in.shape != (9, 2):
+        endrun("mlp_stencil_forward: W1 must be (9, 10) and scl_in (9, 2), got %r and %r" % (W1.shape, scl_in.shape))
+    if temp.numel() % int(nz) != 0:
+        endrun("mlp_stencil_forward: %d cells are not a whole number of columns of nz = %d" % (temp.numel(), nz))
+    if outs is None:
+        outs = [torch.empty_like(temp) for _ in range(4)]
+    check(capi.lib().mw_mlp_set_strict(int(bool(strict))))
+    with torch.cuda.device(temp.device):
+        check(capi.lib().mw_mlp_stencil_forward(int(nz), temp.numel() // int(nz), _ptr(temp), _ptr(rho_d), _ptr(rho_v), _ptr(rho_c), _ptr(rho_r),
+                                                W1.ctypes.data_as(fp), b1.ctypes.data_as(fp), W2.ctypes.data_as(fp), b2.ctypes.data_as(fp),
+                                                scl_in.ctypes.data_as(dp), scl_out.ctypes.data_as(dp), *[_ptr(o) for o in outs],
+                                                _stream_ptr(temp.device)))
+    return outs
+
+
+def stencil_features(fields, nz):
+    """The nine inputs of the stencil model on the host (pure numpy): fields = (temp, density_dry, water_vapor, cloud_liquid, precip_liquid),
+    arrays whose first axis is the nz levels (any trailing shape: (ny, nx, nens) or flat columns).  Returns (9, ncells) in C order of the
+    fields: rows 0..4 the cell's five, rows 5..8 temp, water_vapor, cloud_liquid, precip_liquid of level min(nz - 1, k + 1) of the same
+    column and ensemble member (DataGenerator's inputs(:, :, 0) and inputs(:, 0:4, 1))."""
+    f = [np.asarray(a).reshape(int(nz), -1) for a in fields]
+    if len(f) != 5 or any(a.shape != f[0].shape for a in f):
+        endrun("stencil_features: five fields of one shape (nz, ...) expected")
+    up = np.minimum(np.arange(int(nz)) + 1, int(nz) - 1)
+    rows = f + [f[i][up] for i in (0, 2, 3, 4)]
+    return np.stack([r.reshape(-1) for r in rows])
+
+
+class _PonniLayer(C.Structure):
+    """mw_ponni_layer_t"""
+    _fields_ = [("kind", C.c_int), ("n_in", C.c_int), ("n_out", C.c_int), ("negative_slope", C.c_float), ("offset", C.c_int)]
+
+
+def ponni_forward(layers, x, strict=0):
+    """ponni::Inference::forward_batch_parallel (microphysics_kessler_ponni.h:189) for a stack of ponni layers on a float32 CUDA tensor
+    x of shape (num_in, batch), batch fastest -> (num_out, batch).  layers: ("matvec", W (in, out)) | ("bias", b) | ("relu", n, slope)
+    in the order of ponni::create_inference_model's arguments (:109).  The C++ mirror is miniweatherml_amd/host/mw_ponni.h."""
+    recs, params = [], []
+    for l in layers:
+        kind = {"matvec": 0, "bias": 1, "relu": 2}[l[0]]
+        off = sum(p.size for p in params)
+        if kind == 0:
+            W = np.ascontiguousarray(l[1], dtype=np.float32); params.append(W.ravel()); recs.append((0, W.shape[0], W.shape[1], 0.0, off))
+        elif kind == 1:
+            b = np.ascontiguousarray(l[1], dtype=np.float32); params.append(b.ravel()); recs.append((1, b.size, b.size, 0.0, off))
+        else:
+            recs.append((2, int(l[1]), int(l[1]), float(l[2]) if len(l) > 2 else 0.0, off))
+    arr = (_PonniLayer * len(recs))(*[_PonniLayer(*r) for r in recs])
+    flat = np.concatenate(params).astype(np.float32) if params else np.zeros(1, np.float32)
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or not x.is_contiguous():
+        endrun("ponni_forward: x must be a contiguous float32 (num_in, batch) tensor")
+    out = torch.empty((recs[-1][2], x.shape[1]), dtype=torch.float32, device=x.device)
+    with strict_mode(strict), torch.cuda.device(x.device):
+        rc = capi.lib().mw_ponni_forward(C.cast(arr, C.c_void_p), len(recs), flat.ctypes.data_as(C.POINTER(C.c_float)),
+                                         int(sum(p.size for p in params)), x.shape[1], C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()),
+                                         _stream_ptr(x.device))
+    check(rc)
+    return out
+
+
+def load_surrogate_bank(entries):
+    """The models of a `surrogate_models:` list (dicts with keras_weights_txt | keras_weights_h5, nn_input_scaling, nn_output_scaling; `name`
+    and other keys are ignored) as the list of load_surrogate_weights tuples that SurrogateBank takes."""
+    return [load_surrogate_weights(weights_txt=e.get("keras_weights_txt"), in_scaling_txt=e.get("nn_input_scaling"),
+                                   out_scaling_txt=e.get("nn_output_scaling"), weights_h5=e.get("keras_weights_h5")) for e in entries]

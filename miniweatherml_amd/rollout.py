@@ -1,0 +1,353 @@
+"""Candidate surrogates rolled out as ensemble members beside Kessler (no reference counterpart; the sample files are those of
+experiments/supercell_kessler_surrogate/custom_modules/generate_micro_surrogate_data.h:17-33, the thresholds its :58-62):
+
+  Microphysics_Rollout       one microphysics step that treats every ensemble member differently (mw_member_*, SurrogateBank)
+  kessler_members_teacher    mw_kessler_members_teacher: what Kessler would do to each member's own state
+  RolloutHarvester           (state, label) samples of the teacher on the model members' states, one file per member
+  member_divergence, rollout_report, RolloutScorer    mw_member_divergence and its reports"""
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+
+from . import capi
+from ._ffi import StatsAndCounts, _field_ptr_array, _ptr, _stream_ptr, grown_workspace
+from .capi import check
+from .coupler import endrun
+from .microphysics import Microphysics_Kessler
+from .mlp import IN5
+from .ncio import sample_file_append, sample_file_create
+from .sampling import sample_buffers, sample_thresholds
+from .surrogate_eval import SurrogateBank, finite_or_none, json_safe, skill_cell
+
+ROLLOUT_FIELDS = ("density_dry", "uvel", "vvel", "wvel", "temp", "water_vapor", "cloud_liquid", "precip_liquid")
+ROLLOUT_STATS = ("sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_x", "min_x", "max_x")
+ROLLOUT_WATER = ("water_vapor", "cloud_liquid", "precip_liquid")
+ROLLOUT_IN5 = IN5                 # fields5 of members_apply and of the teacher
+
+
+def rollout_member_names(model_names, persistence=True, committees=()):
+    """The fixed roles of a rollout's ensemble members: member 0 is Kessler, members 1 .. K the models of the list in its order, then one
+    member per committee (names of `committees`, in its order), an optional last member persistence (no microphysics).  More members than
+    the dycore steps in one call is an error that names the limit."""
+    names = [str(n) for n in model_names]
+    if len(set(names)) != len(names) or {"kessler", "persistence"} & set(names):
+        endrun("rollout: model names must be unique and neither 'kessler' nor 'persistence'")
+    cnames = [str(n) for n in committees]
+    if len(set(cnames)) != len(cnames) or ({"kessler", "persistence"} | set(names)) & set(cnames):
+        endrun("rollout: committee names must be unique and neither a model's name nor 'kessler' nor 'persistence'")
+    members = ["kessler"] + names + cnames + (["persistence"] if persistence else [])
+    if len(members) > capi.MW_ROLLOUT_MAX_MEMBERS:
+        endrun("rollout: %d models%s%s beside Kessler are %d ensemble members, the dycore steps at most %d"
+               % (len(names), (", %d committees" % len(cnames)) if cnames else "", " and persistence" if persistence else "", len(members),
+                  capi.MW_ROLLOUT_MAX_MEMBERS))
+    return members
+
+
+class Microphysics_Rollout(Microphysics_Kessler):
+    """One microphysics step that treats every ensemble member differently (no reference counterpart): member 0 is stepped by Kessler,
+    member k by model k - 1 of `models` (its output written back: Microphysics_Kessler_Surrogate.online for that member), the optional last
+    member by nothing.  The dycore, the sponge and the nudger step the members independently, so one run shows how each candidate behaves
+    once its own output is fed back.  Kessler runs on member 0 ALONE, extracted to contiguous arrays: its rain sub-cycle count is a minimum
+    over all the columns of a call.  `precl` is written for member 0 only; the other members' precl keeps whatever it held.
+    With a `harvester` (RolloutHarvester) and `harvest_now` set, the step harvests Kessler labels on the model members' own states
+    between the Kessler member's step and the models'; harvesting reads the state and never writes it."""
+
+    mlp_strict = 0        # 1: the thread-per-cell MLP kernels (mw_mlp_set_strict)
+    harvester = None      # a RolloutHarvester: time_step harvests when harvest_now is set (the driver sets it, and harvest_etime, per step)
+    harvest_now = False
+    harvest_etime = 0.0
+
+    def micro_name(self):
+        return "rollout"
+
+    def init(self, coupler, models, persistence=True, names=None, committees=()):
+        """models: (W1, b1, W2, b2, scl_in, scl_out) tuples as load_surrogate_weights returns them, single-cell and stencil networks in any
+        order; names: theirs (default model0, model1, ...).  committees: (name, [model names]) pairs; each is one more member after the
+        models, replaced in place from its OWN state by the mean of its models (1 .. 16 of one width, SurrogateBank.committee_apply on that
+        width's bank).  The coupler must have 1 + len(models) + len(committees) (+ 1 with persistence) members."""
+        models = list(models)
+        names = ["model%d" % k for k in range(len(models))] if names is None else [str(n) for n in names]
+        if len(names) != len(models):
+            endrun("Microphysics_Rollout: %d names for %d models" % (len(names), len(models)))
+        committees = [(str(c[0]), [str(n) for n in c[1]]) for c in committees]
+        self.member_names = rollout_member_names(names, persistence, [c[0] for c in committees])
+        self.persistence = bool(persistence)
+        if coupler.get_nens() != len(self.member_names):
+            endrun("Microphysics_Rollout: %d models%s%s beside Kessler need nens = %d, the coupler has %d"
+                   % (len(models), (", %d committees" % len(committees)) if committees else "", " and persistence" if persistence else "",
+                      len(self.member_names), coupler.get_nens()))
+        for cname, cmodels in committees:
+            if not 1 <= len(cmodels) <= capi.MW_COMMITTEE_MAX_MODELS:
+                endrun("Microphysics_Rollout: committee %r has %d models, a committee has 1 to %d" % (cname, len(cmodels), capi.MW_COMMITTEE_MAX_MODELS))
+            if len(set(cmodels)) != len(cmodels) or any(n not in names for n in cmodels):
+                endrun("Microphysics_Rollout: committee %r must name distinct models of the list (%s)" % (cname, ", ".join(names)))
+            if len({int(np.shape(models[names.index(n)][0])[0]) for n in cmodels}) != 1:
+                endrun("Microphysics_Rollout: committee %r mixes single-cell and stencil models: a committee has one width" % cname)
+        super().init(coupler)
+        coupler.set_option("micro", "rollout")
+        widths = []
+        for m in models:
+            if int(np.shape(m[0])[0]) not in widths:
+                widths.append(int(np.shape(m[0])[0]))
+        # one bank per width; a model keeps the member its place in the list gives it
+        self.banks = [(SurrogateBank([m for m in models if np.shape(m[0])[0] == w], coupler.device),
+                       [1 + k for k, m in enumerate(models) if np.shape(m[0])[0] == w]) for w in widths]
+        # a committee runs on its width's bank: (bank, its models' places in that bank, its member)
+        self.committees = []
+        for ci, (cname, cmodels) in enumerate(committees):
+            w = int(np.shape(models[names.index(cmodels[0])][0])[0])
+            in_bank = [k for k, m in enumerate(models) if np.shape(m[0])[0] == w]
+            self.committees.append((self.banks[widths.index(w)][0], [in_bank.index(names.index(n)) for n in cmodels], 1 + len(models) + ci))
+        self._m0 = None
+
+    def time_step(self, coupler, dt):
+        dm = coupler.get_data_manager_readwrite()
+        temp, rho_d = dm.get("temp"), dm.get("density_dry", readonly=True)
+        rho_v, rho_c, rho_r, precl = dm.get("water_vapor"), dm.get("cloud_liquid"), dm.get("precip_liquid"), dm.get("precl")
+        nz, nens = coupler.get_nz(), coupler.get_nens()
+        ncol = coupler.get_ny() * coupler.get_nx()
+        n = nz * ncol
+        L = capi.lib()
+        if self._m0 is None or self._m0[0][0].numel() != n or self._m0[1].numel() != ncol:
+            self._m0 = ([torch.empty(n, dtype=torch.float64, device=coupler.device) for _ in range(5)],
+                        torch.empty(ncol, dtype=torch.float64, device=coupler.device))
+        (v0, c0, r0, d0, t0), p0 = self._m0
+        ws = grown_workspace(self, "_ws", L.mw_kessler_workspace_bytes(nz, ncol), coupler.device)
+        st = _stream_ptr(coupler.device)
+        check(L.mw_kessler_set_strict(self.strict))
+        with torch.cuda.device(coupler.device):
+            check(L.mw_member_extract(n, nens, 0, 5, _field_ptr_array([rho_v, rho_c, rho_r, rho_d, temp]), _field_ptr_array([v0, c0, r0, d0, t0]), st))
+            check(L.mw_kessler_time_step(nz, ncol, coupler.get_dz(), float(dt), _ptr(v0), _ptr(c0), _ptr(r0), _ptr(d0), _ptr(t0), _ptr(p0),
+                                         _ptr(ws), None, st))
+            check(L.mw_member_insert(n, nens, 0, 4, _field_ptr_array([v0, c0, r0, t0]), _field_ptr_array([rho_v, rho_c, rho_r, temp]), st))
+            check(L.mw_member_insert(ncol, nens, 0, 1, _field_ptr_array([p0]), _field_ptr_array([precl]), st))
+        if self.harvester is not None and self.harvest_now:                    # the teacher sees the state each model is about to replace
+            self.last_harvest = self.harvester.harvest(coupler, dt, self.harvest_etime)
+        for bank, members in self.banks:
+            bank.strict = self.mlp_strict
+            bank.members_apply(nz, members, [temp, rho_d, rho_v, rho_c, rho_r])
+        for bank, sel, member in getattr(self, "committees", ()):
+            bank.strict = self.mlp_strict
+            bank.committee_apply(nz, sel, member, [temp, rho_d, rho_v, rho_c, rho_r], [temp, rho_v, rho_c, rho_r])
+
+
+def kessler_members_teacher(coupler, members, dt, max_rainsplit=64, outs=None, return_rainsplit=False):
+    """mw_kessler_members_teacher on the coupler's member-fastest fields: what Kessler would do to the state of every member in `members`,
+    each member alone, out of place.  Returns the four teacher tensors (temp, water_vapor, cloud_liquid, precip_liquid after Kessler), each
+    (nz, ny, nx, nens); only the listed members' elements are written (outs: four tensors to write into, default new uninitialised ones).
+    A member whose own state asks for more than max_rainsplit rain sub-cycles, or whose rain CFL step is not a positive finite number, is
+    skipped: not computed, not written.  return_rainsplit=True: (tensors, counts per listed member, 0 = skipped), at the price of a
+    stream synchronisation.  The coupler's fields are read only."""
+    dm = coupler.get_data_manager_readonly()
+    f5 = [dm.get(n, True) for n in ROLLOUT_IN5]
+    members = [int(m) for m in members]
+    nz, nens = coupler.get_nz(), coupler.get_nens()
+    ncol = coupler.get_ny() * coupler.get_nx()
+    if outs is None:
+        outs = [torch.empty_like(f5[0]) for _ in range(4)]
+    if len(outs) != 4 or any(o.shape != f5[0].shape or o.device != f5[0].device for o in outs):
+        endrun("kessler_members_teacher: outs must be four tensors of the fields' shape on their device")
+    L = capi.lib()
+    nbytes = L.mw_kessler_members_teacher_workspace_bytes(nz, ncol, nens)
+    if nbytes <= 0:
+        endrun("kessler_members_teacher: nz = %d, %d columns and %d members are out of range (nz >= 2, at most 64 members)" % (nz, ncol, nens))
+    ws = grown_workspace(coupler, "_ws_teacher", nbytes, coupler.device)
+    rs = (C.c_int * max(1, len(members)))()
+    with torch.cuda.device(coupler.device):
+        check(L.mw_kessler_members_teacher(nz, ncol, nens, len(members), (C.c_int * max(1, len(members)))(*members), coupler.get_dz(), float(dt),
+                                           int(max_rainsplit), _field_ptr_array(f5), _field_ptr_array(outs), rs if return_rainsplit else None,
+                                           _ptr(ws), _stream_ptr(coupler.device)))
+    return (outs, [int(rs[j]) for j in range(len(members))]) if return_rainsplit else outs
+
+
+class RolloutHarvester:
+    """Data aggregation for the rollout (no reference counterpart): while the candidate models run online as ensemble members, ask the
+    teacher -- Kessler -- what it would have done to each model member's OWN state, and keep (state, label) samples of it in one file per
+    member, `rollout_samples_<name>.nc`, with exactly DataGenerator's dimensions and variables (surrogate_train.read_samples takes them
+    unchanged).  harvest() is teacher -> mask -> nonzero -> gather -> append; the coupler's state is read, never written."""
+
+    def init(self, coupler, member_names, members, directory, samples_per_step=50, ratio_active=0.5, prior_active=0.4, seed=None,
+             max_rainsplit=64):
+        """member_names / members: the harvested model members' names and ensemble indices.  samples_per_step, ratio_active: the wanted
+        samples per call and member and the wanted share of active cells among them (DataGenerator's 50 and 0.5); prior_active: the share
+        of active cells assumed when the thresholds are set (DataGenerator's 0.4); seed: call c draws with seed + c (default: the clock)."""
+        import time as _time
+        self.member_names, self.members = [str(n) for n in member_names], [int(m) for m in members]
+        if len(self.member_names) != len(self.members) or not self.members or len(set(self.members)) != len(self.members) or \
+                len(set(self.member_names)) != len(self.members):
+            endrun("RolloutHarvester: as many distinct names as distinct members, at least one")
+        if any(not 0 <= m < coupler.get_nens() for m in self.members):
+            endrun("RolloutHarvester: members %r outside [0, %d)" % (self.members, coupler.get_nens()))
+        if not (samples_per_step > 0 and 0.0 < ratio_active < 1.0 and 0.0 < prior_active < 1.0 and 1 <= int(max_rainsplit) <= 1024):
+            endrun("RolloutHarvester: samples_per_step > 0, ratio_active and prior_active in (0, 1), max_rainsplit in [1, 1024]")
+        self.samples_per_step, self.ratio_active, self.prior_active = float(samples_per_step), float(ratio_active), float(prior_active)
+        self.max_rainsplit = int(max_rainsplit)
+        self.seed = int(_time.time()) if seed is None else int(seed)
+        self.files = {n: os.path.join(directory, "rollout_samples_%s.nc" % n) for n in self.member_names}
+        for f in self.files.values():
+            sample_file_create(f)
+        self.samples = {n: 0 for n in self.member_names}
+        self.skipped = {n: 0 for n in self.member_names}
+        self.calls = 0
+        self._meta_written = False
+        self._teacher = None
+        self.last_elems = None
+
+    def thresholds(self, coupler):
+        """DataGenerator's two formulas (generate_micro_surrogate_data.h:58-62) per member, clamped to 1."""
+        thr_act, thr_inact = sample_thresholds(self.ratio_active * self.samples_per_step, (1 - self.ratio_active) * self.samples_per_step,
+                                               self.prior_active, coupler.get_nz() * coupler.get_ny() * coupler.get_nx())
+        return min(1.0, thr_act), min(1.0, thr_inact)
+
+    def harvest(self, coupler, dt, etime):
+        """One call: {name: samples added}.  A member the teacher skipped adds none and counts in `skipped`."""
+        dm = coupler.get_data_manager_readonly()
+        f5 = [dm.get(n, True) for n in ROLLOUT_IN5]
+        nz, nens = coupler.get_nz(), coupler.get_nens()
+        ncol = coupler.get_ny() * coupler.get_nx()
+        nelem = nz * ncol * nens
+        dev = coupler.device
+        if self._teacher is None or self._teacher[0].shape != f5[0].shape:
+            self._teacher = [torch.empty_like(f5[0]) for _ in range(4)]
+        teacher, rs = kessler_members_teacher(coupler, self.members, dt, self.max_rainsplit, self._teacher, return_rainsplit=True)
+        live = [(n, m) for n, m, r in zip(self.member_names, self.members, rs) if r > 0]
+        for n, r in zip(self.member_names, rs):
+            self.skipped[n] += int(r == 0)
+        thr_act, thr_inact = self.thresholds(coupler)
+        max_mag = (2 ** 64 - 1) // (1 + nelem)
+        key0 = (((self.seed + self.calls) % max_mag) * nelem) % (2 ** 64)
+        self.calls += 1
+        added = {n: 0 for n in self.member_names}
+        write_meta, self._meta_written = not self._meta_written, True
+        ins = outs = which = None
+        if live:
+            L = capi.lib()
+            mask = torch.empty(nelem, dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                check(L.mw_member_sample_mask(nz, ncol, nens, len(live), (C.c_int * len(live))(*[m for _, m in live]), _field_ptr_array(f5),
+                                              _field_ptr_array(teacher), key0, thr_act, thr_inact, C.c_void_p(mask.data_ptr()), _stream_ptr(dev)))
+                elems, n, ins, outs = sample_buffers(mask)                     # ascending, as DataGenerator compacts
+                check(L.mw_member_gather_samples(nz, ncol, nens, _field_ptr_array(f5), _field_ptr_array(teacher), C.c_void_p(elems.data_ptr()), n,
+                                                 C.c_void_p(ins.data_ptr()), C.c_void_p(outs.data_ptr()), _stream_ptr(dev)))
+            self.last_elems = elems.cpu().numpy()                              # (k * ncol + col) * nens + member of the samples (diagnostic)
+            ins, outs, which = ins.cpu().numpy(), outs.cpu().numpy(), self.last_elems % nens
+        else:
+            self.last_elems = np.zeros(0, dtype=np.int64)
+        for name, m in zip(self.member_names, self.members):
+            sel = (which == m) if which is not None else np.zeros(0, dtype=bool)
+            a = ins[sel] if which is not None else np.zeros((0, 5, 2), dtype=np.float32)
+            b = outs[sel] if which is not None else np.zeros((0, 4), dtype=np.float32)
+            sample_file_append(self.files[name], coupler, dt, a, b, write_meta)
+            added[name] = int(a.shape[0])
+            self.samples[name] += added[name]
+        return added
+
+
+def member_divergence(coupler, names):
+    """mw_member_divergence of the coupler's fields `names` (at most 16, each (..., nens)): the raw arrays (stats, nonfinite) --
+    stats (nens, len(names), 7) fp64 in the order of ROLLOUT_STATS (d = member - member 0 for the first four, the member's own values for
+    the last three), nonfinite (nens, len(names)) int64, the member's NaN or inf elements -- from one device-to-host copy."""
+    dm = coupler.get_data_manager_readonly()
+    fields = [dm.get(n, True) for n in names]
+    nens = coupler.get_nens()
+    n = fields[0].numel() // nens
+    if any(t.numel() != n * nens or t.shape[-1] != nens for t in fields):
+        endrun("member_divergence: the fields must have one size and the members last")
+    L = capi.lib()
+    nf = len(fields)
+    nbytes = L.mw_member_divergence_workspace_bytes(n, nens, nf)
+    if nbytes <= 0:
+        endrun("member_divergence: %d fields of %d cells x %d members are out of range (at most %d fields)" % (nf, n, nens, capi.MW_MAX_TRACERS))
+    ws = grown_workspace(coupler, "_ws_divergence", nbytes, coupler.device)
+    buf = StatsAndCounts(nens * nf * 7, nens * nf, coupler.device)
+    with torch.cuda.device(coupler.device):
+        check(L.mw_member_divergence(n, nens, nf, _field_ptr_array(fields), _ptr(ws), buf.stats_ptr, buf.counts_ptr, _stream_ptr(coupler.device)))
+    stats, nonfinite = buf.host()
+    return stats.reshape(nens, nf, 7), nonfinite.reshape(nens, nf)
+
+
+def rollout_report(stats, nonfinite, ncells, member_names, fields, cell_volume=1.0, persistence=None):
+    """One scoring time's raw arrays (member_divergence) as a report -- pure numpy.  Per member and field: bias = sum d / n, mae, rmse and
+    max_abs of d = member - Kessler member, rmse_over_persistence (None without a persistence member `persistence`, or when its rmse is
+    0), the member's own mean, min, max and its count of non-finite elements.  A statistic that is inf or NaN is None and the field
+    carries "finite": False.  Per member: total_water = cell_volume * sum of the three water fields (None unless all three are scored
+    and finite) and finite = no field has a non-finite element or statistic."""
+    stats = np.asarray(stats, dtype=np.float64)
+    nonfinite = np.asarray(nonfinite, dtype=np.int64)
+    if stats.shape != (len(member_names), len(fields), 7) or nonfinite.shape != stats.shape[:2]:
+        endrun("rollout_report: stats must be (%d members, %d fields, 7) and nonfinite (%d, %d)" % ((len(member_names), len(fields)) * 2))
+    n = float(ncells)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        rmse = np.sqrt(stats[..., 2] / n)
+        skill = rmse / rmse[persistence] if persistence is not None else None
+    rep = {}
+    for m, mname in enumerate(member_names):
+        row, ok_member = {}, True
+        for f, fname in enumerate(fields):
+            q = None
+            if persistence is not None and rmse[persistence, f] > 0:
+                q = float(skill[m, f])
+            row[fname] = finite_or_none({"bias": float(stats[m, f, 0] / n), "mae": float(stats[m, f, 1] / n), "rmse": float(rmse[m, f]),
+                                         "max_abs": float(stats[m, f, 3]), "rmse_over_persistence": q, "mean": float(stats[m, f, 4] / n),
+                                         "min": float(stats[m, f, 5]), "max": float(stats[m, f, 6]), "nonfinite": int(nonfinite[m, f])},
+                                        bad=nonfinite[m, f] != 0)
+            ok_member = ok_member and "finite" not in row[fname]
+        water = None
+        if all(w in fields for w in ROLLOUT_WATER):
+            water = float(sum(stats[m, list(fields).index(w), 4] for w in ROLLOUT_WATER) * cell_volume)
+            water = water if np.isfinite(water) else None
+        rep[mname] = {"fields": row, "total_water": water, "finite": ok_member}
+    return rep
+
+
+class RolloutScorer:
+    """Online skill of a rollout's members: accumulate(coupler, step, etime) at every scoring time, report() / table() at the end.
+    member_names: rollout_member_names' list (a last member called persistence is the skill's denominator); fields: the coupler fields
+    to score."""
+
+    def __init__(self, member_names, fields=ROLLOUT_FIELDS):
+        self.member_names = [str(m) for m in member_names]
+        self.fields = [str(f) for f in fields]
+        self.persistence = len(self.member_names) - 1 if self.member_names[-1] == "persistence" else None
+        self.history = []               # per scoring time: step, etime, the raw arrays
+        self.times = []                 # per scoring time: step, etime, rollout_report
+        self.diverged_at = {m: None for m in self.member_names}
+
+    def add(self, stats, nonfinite, ncells, cell_volume, step, etime):
+        """One scoring time from raw arrays (what accumulate does after member_divergence): pure numpy."""
+        rep = rollout_report(stats, nonfinite, ncells, self.member_names, self.fields, cell_volume, self.persistence)
+        self.history.append({"step": int(step), "etime": float(etime), "stats": json_safe(np.asarray(stats, dtype=np.float64).tolist()),
+                             "nonfinite": np.asarray(nonfinite).tolist()})
+        self.times.append({"step": int(step), "etime": float(etime), "members": rep})
+        for m in self.member_names:
+            if self.diverged_at[m] is None and not rep[m]["finite"]:
+                self.diverged_at[m] = {"step": int(step), "etime": float(etime)}
+        return rep
+
+    def accumulate(self, coupler, step, etime):
+        stats, nonfinite = member_divergence(coupler, self.fields)
+        ncells = coupler.get_nz() * coupler.get_ny() * coupler.get_nx()
+        return self.add(stats, nonfinite, ncells, coupler.get_dx() * coupler.get_dy() * coupler.get_dz(), step, etime)
+
+    def report(self):
+        """{"times": one rollout_report per scoring time with its step and etime, "diverged_at": per member the first scoring time at
+        which it showed a non-finite value, or None}."""
+        if not self.times:
+            endrun("RolloutScorer.report: nothing accumulated")
+        return {"times": self.times, "diverged_at": dict(self.diverged_at)}
+
+    def table(self, rep=None):
+        """The last scoring time as text: one line per member, rmse against the Kessler member (/ persistence rmse) per field."""
+        rep = self.report() if rep is None else rep
+        last = rep["times"][-1]
+        w = max(len(m) for m in self.member_names)
+        lines = ["step %d, etime %.6f s" % (last["step"], last["etime"]),
+                 "%-*s " % (w, "member") + " ".join("%26s" % ("%s rmse (/pers.)" % f) for f in self.fields) + "  diverged_at"]
+        for m in self.member_names:
+            row = last["members"][m]["fields"]
+            cells = [skill_cell(row[f]["rmse"], row[f]["rmse_over_persistence"]) for f in self.fields]
+            d = rep["diverged_at"][m]
+            lines.append("%-*s " % (w, m) + " ".join(cells) + "  " + ("-" if d is None else "step %d" % d["step"]))
+        return "\n".join(lines)

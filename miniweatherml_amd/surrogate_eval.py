@@ -1,0 +1,407 @@
+"""In-loop evaluation of candidate surrogate networks against the microphysics in charge (no reference counterpart; the networks are
+those of experiments/supercell_kessler_surrogate/custom_modules/microphysics_kessler_ponni.h:97-202):
+
+  SurrogateBank                        mw_surrogate_bank_t: K networks of one width on the device; evaluate, members_apply, committee_apply
+  surrogate_scores, SurrogateEvaluator exact accumulation of mw_surrogate_eval's statistics, report and table
+  committee_score, CommitteeEvaluator  mw_committee_score: the committee's mean and range against the truth
+  json_safe, finite_or_none, skill_cell, the exact-sum helpers: pure numpy / Python, shared with the rollout's reports"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import capi
+from ._ffi import StatsAndCounts, _field_ptr_array, _ptr, _stream_ptr, fit_workspace, grown_workspace
+from .capi import check
+from .coupler import endrun
+from .mlp import IN5, OUT4, strict_mode
+
+EVAL_FIELDS = OUT4
+EVAL_CLASSES = ("inactive", "active")
+_EXACT_ONE = 1 << 1074            # sums are kept as integers in units of 2^-1074, the spacing of the smallest doubles: exact addition
+
+
+class SurrogateBank:
+    """mw_surrogate_bank_t: K candidate networks of one width (all single-cell or all stencil), each with its own scaling tables, uploaded
+    once to `device`; evaluate() refuses fields of another device.  models: a list of (W1, b1, W2, b2, scl_in, scl_out) as
+    load_surrogate_weights returns them."""
+
+    def __init__(self, models, device="cuda:0"):
+        self._h = None
+        self.device = torch.device(device)
+        models = list(models)
+        if len(models) < 1:
+            endrun("SurrogateBank: no models")
+        if len(models) > capi.MW_SURROGATE_MAX_MODELS:
+            endrun("SurrogateBank: %d models, at most %d fit one bank" % (len(models), capi.MW_SURROGATE_MAX_MODELS))
+        widths = sorted({int(np.asarray(m[0]).shape[0]) for m in models})
+        if len(widths) != 1:
+            endrun("SurrogateBank: models of different widths (%s inputs) cannot share a bank: one bank per width" % ", ".join(map(str, widths)))
+        self.n_in, self.models = widths[0], len(models)
+        a = 10 * self.n_in
+        for W1, b1, W2, b2, si, so in models:
+            if np.shape(W1) != (self.n_in, 10) or np.shape(b1) != (10,) or np.shape(W2) != (10, 4) or np.shape(b2) != (4,) or \
+                    np.shape(si) != (self.n_in, 2) or np.shape(so) != (4, 2):
+                endrun("SurrogateBank: a model is not Dense(%d->10), Dense(10->4) with (%d, 2) and (4, 2) scaling tables" % (self.n_in, self.n_in))
+        params = np.ascontiguousarray([np.concatenate([np.ravel(m[0]), np.ravel(m[1]), np.ravel(m[2]), np.ravel(m[3])]) for m in models], dtype=np.float32)
+        scl_in = np.ascontiguousarray([m[4] for m in models], dtype=np.float64)
+        scl_out = np.ascontiguousarray([m[5] for m in models], dtype=np.float64)
+        h = C.c_void_p()
+        if capi.lib().mw_device_count() < 1:
+            endrun("SurrogateBank: no HIP device available: libmw_cdna4 has no CPU fallback")
+        with torch.cuda.device(self.device):                              # the handle's allocations live on the current device
+            check(capi.lib().mw_surrogate_bank_create(C.byref(h), self.n_in, self.models, params.ctypes.data_as(C.POINTER(C.c_float)),
+                                                      scl_in.ctypes.data_as(C.POINTER(C.c_double)), scl_out.ctypes.data_as(C.POINTER(C.c_double))))
+        self._h = h
+        self.group = int(capi.lib().mw_surrogate_eval_group(h))           # models per pass over the state
+        self.strict = 0                                                   # 1: the thread-per-cell kernels (mw_mlp_set_strict)
+        self._buf = None
+
+    def __del__(self):
+        try:                                                              # (at interpreter exit the module's globals may be gone)
+            if getattr(self, "_h", None):
+                with torch.cuda.device(self.device):
+                    capi.lib().mw_surrogate_bank_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def evaluate(self, nz, in5, truth4):
+        """in5: the five fields before the microphysics call (temp, density_dry, water_vapor, cloud_liquid, precip_liquid), truth4: the four
+        after it (EVAL_FIELDS); fp64 CUDA tensors of nz levels.  Returns (stats, counts): the raw (K + 1, 2, 4, 4) fp64 array
+        [model | persistence][inactive, active][field][sum d, sum |d|, sum d^2, max |d|], d = prediction - truth, and the int64 cells per
+        class -- one device-to-host copy for both."""
+        if len(in5) != 5 or len(truth4) != 4:
+            endrun("SurrogateBank.evaluate: five input fields and four truth fields expected")
+        n = in5[0].numel()
+        if int(nz) < 1 or n % int(nz) != 0 or any(t.numel() != n for t in list(in5) + list(truth4)):
+            endrun("SurrogateBank.evaluate: the nine fields must have one size, a whole number of columns of nz = %d levels" % nz)
+        dev = self.device
+        if any(t.device != dev for t in list(in5) + list(truth4)):
+            endrun("SurrogateBank.evaluate: the bank lives on %s, the fields on %s" % (dev, sorted({str(t.device) for t in list(in5) + list(truth4)})))
+        buf = StatsAndCounts((self.models + 1) * 32, 2, dev, self._buf)
+        self._buf = buf.buf                                               # (the int64 tensor itself: kept from call to call)
+        with strict_mode(self.strict), torch.cuda.device(dev):
+            rc = capi.lib().mw_surrogate_eval(self._h, int(nz), n // int(nz), _field_ptr_array(in5), _field_ptr_array(truth4),
+                                              buf.stats_ptr, buf.counts_ptr, _stream_ptr(dev))
+        check(rc)
+        stats, counts = buf.host()
+        return stats.reshape(self.models + 1, 2, 4, 4), counts
+
+    def _member_layout(self, who, nz, fields):
+        """(columns per member, nens) of member-fastest fields of one shape (nz, ..., nens); refuses, in the caller's name `who`, cells that
+        are no whole number of columns and fields off the bank's device."""
+        nens = int(fields[0].shape[-1])
+        n = fields[0].numel() // nens
+        if int(nz) < 1 or n % int(nz) != 0:
+            endrun(who + "%d cells per member are not a whole number of columns of nz = %d" % (n, nz))
+        if any(t.device != self.device for t in fields):
+            endrun(who + "the bank lives on %s, the fields on %s" % (self.device, sorted({str(t.device) for t in fields})))
+        return n // int(nz), nens
+
+    def members_apply(self, nz, members, fields5):
+        """mw_surrogate_members_apply: model j of the bank replaces temp and the three water fields of ensemble member members[j] of the
+        coupler's member-fastest arrays fields5 = (temp, density_dry, water_vapor, cloud_liquid, precip_liquid), each (nz, ..., nens), in
+        place, with the bits the forward kernels write for that member's own values (self.strict = 1: the thread-per-cell form)."""
+        members = [int(m) for m in members]
+        if len(members) != self.models:
+            endrun("SurrogateBank.members_apply: %d members for %d models" % (len(members), self.models))
+        if len(fields5) != 5 or any(t.shape != fields5[0].shape for t in fields5) or fields5[0].dim() < 2:
+            endrun("SurrogateBank.members_apply: five fields of one shape (nz, ..., nens) expected")
+        ncol, nens = self._member_layout("SurrogateBank.members_apply: ", nz, fields5)
+        with strict_mode(self.strict), torch.cuda.device(self.device):
+            rc = capi.lib().mw_surrogate_members_apply(self._h, (C.c_int * len(members))(*members), int(nz), ncol, nens,
+                                                       _field_ptr_array(fields5), _stream_ptr(self.device))
+        check(rc)
+
+    def committee_apply(self, nz, sel, member, in5, out4, range4=None):
+        """mw_surrogate_committee_apply: the mean of the bank's models sel (1 .. 16 distinct indices, summed in that order) on ensemble
+        member `member` of the member-fastest fields in5 = (temp, density_dry, water_vapor, cloud_liquid, precip_liquid), each
+        (nz, ..., nens), written to out4 = (temp, water_vapor, cloud_liquid, precip_liquid) of the same shape -- each the matching input
+        tensor (in place) or a tensor of its own -- and, with range4, the members' largest minus smallest value per cell and field.  Only
+        elements of `member` are read and written (self.strict = 1: the thread-per-column form)."""
+        sel = [int(s) for s in sel]
+        if len(in5) != 5 or len(out4) != 4 or (range4 is not None and len(range4) != 4):
+            endrun("SurrogateBank.committee_apply: five input fields, four output fields and (optionally) four range fields expected")
+        every = list(in5) + list(out4) + (list(range4) if range4 is not None else [])
+        if any(t.shape != in5[0].shape for t in every) or in5[0].dim() < 2:
+            endrun("SurrogateBank.committee_apply: fields of one shape (nz, ..., nens) expected")
+        if any(t.dtype != torch.float64 or not t.is_contiguous() for t in every):
+            endrun("SurrogateBank.committee_apply: contiguous float64 fields expected")
+        ncol, nens = self._member_layout("SurrogateBank.committee_apply: ", nz, every)
+        with strict_mode(self.strict), torch.cuda.device(self.device):
+            rc = capi.lib().mw_surrogate_committee_apply(self._h, len(sel), (C.c_int * max(1, len(sel)))(*sel), int(member), int(nz), ncol, nens,
+                                                         _field_ptr_array(in5), _field_ptr_array(out4),
+                                                         _field_ptr_array(range4) if range4 is not None else None, _stream_ptr(self.device))
+        check(rc)
+
+
+def json_safe(x):
+    """Nested lists of floats with inf / NaN as the strings "inf", "-inf", "nan" (bare tokens are no JSON); finite numbers unchanged."""
+    if isinstance(x, list):
+        return [json_safe(v) for v in x]
+    return x if np.isfinite(x) else str(float(x))
+
+
+def finite_or_none(row, bad=False):
+    """A report's row of statistics (numbers or None): unchanged when every number is finite and `bad` is not set; else the row with None
+    for each statistic that is inf or NaN (a diverged model) and "finite": False behind them."""
+    if not bad and all(x is None or np.isfinite(x) for x in row.values()):
+        return row
+    row = {k: (x if x is not None and np.isfinite(x) else None) for k, x in row.items()}
+    row["finite"] = False
+    return row
+
+
+def or_dash(x, fmt):
+    return "-" if x is None else fmt % x
+
+
+def skill_cell(rmse, ratio):
+    """The cell of a skill table: the rmse and, in brackets, the rmse over the persistence row's."""
+    return "%26s" % ("-" if rmse is None else "%.6e (%s)" % (rmse, or_dash(ratio, "%.4g")))
+
+
+def _exact_sum_units(x):
+    n, d = float(x).as_integer_ratio()
+    return n * (_EXACT_ONE // d)
+
+
+def _exact_units_array(x):
+    """An fp64 array as (exact integers in units of 2^-1074, the non-finite values apart): a sum that is inf or NaN lives in the second
+    array and its integer is 0."""
+    x = np.asarray(x, dtype=np.float64)
+    fin = np.isfinite(x)
+    units = np.zeros(x.shape, dtype=object)
+    flat, ff, src = units.reshape(-1), fin.reshape(-1), x.reshape(-1)
+    for i in range(flat.size):
+        flat[i] = _exact_sum_units(src[i]) if ff[i] else 0
+    return units, np.where(fin, 0.0, x)
+
+
+def surrogate_scores(stats, counts):
+    """One raw result of SurrogateBank.evaluate as the accumulating form SurrogateEvaluator.combine adds: `sums` (K + 1, 2, 4, 3) exact
+    integers in units of 2^-1074, `nonfinite` the same shape in fp64 (a sum that is inf or NaN -- a diverged model -- lives here and its
+    integer is 0), `max` (K + 1, 2, 4), `counts` (2,) and the number of calls."""
+    stats = np.asarray(stats, dtype=np.float64)
+    sums, nonfinite = _exact_units_array(stats[..., :3])
+    return {"sums": sums, "nonfinite": nonfinite, "max": stats[..., 3].copy(), "counts": np.asarray(counts, dtype=np.int64).copy(), "calls": 1}
+
+
+def _sums_to_float(sums, nonfinite):
+    out = np.array([v / _EXACT_ONE for v in sums.reshape(-1)], dtype=np.float64).reshape(sums.shape)      # int / int: correctly rounded
+    return np.where(nonfinite != 0.0, nonfinite, out)
+
+
+class SurrogateEvaluator:
+    """Scores every model of several banks (one per width) against the microphysics in charge, call after call: accumulate(inp, out) with
+    the coupler cloned before micro.time_step and the stepped one (the pair gather_micro_statistics takes), report() at the end.
+    names: the models' names, bank after bank."""
+
+    def __init__(self, banks, names):
+        self.banks = list(banks)
+        self.names = [str(n) for n in names]
+        if len(self.names) != sum(b.models for b in self.banks):
+            endrun("SurrogateEvaluator: %d names for %d models" % (len(self.names), sum(b.models for b in self.banks)))
+        if len(set(self.names)) != len(self.names):
+            endrun("SurrogateEvaluator: model names must be unique")
+        self.total = None
+        self.history = []               # per call: the raw statistics and counts of every bank
+
+    @staticmethod
+    def combine(a, b):
+        """Two results (lists with one surrogate_scores dict per bank) as one: sums add, maxima take the larger, counts and calls add.  The
+        sums are exact integers, so the order of combination cannot matter: (a + b) + c == a + (b + c), also across ranks; by convention
+        `a` is the earlier result."""
+        if len(a) != len(b):
+            endrun("SurrogateEvaluator.combine: results of different evaluators")
+        out = []
+        for x, y in zip(a, b):
+            if x["sums"].shape != y["sums"].shape:
+                endrun("SurrogateEvaluator.combine: results of different banks")
+            out.append({"sums": x["sums"] + y["sums"], "nonfinite": x["nonfinite"] + y["nonfinite"], "max": np.maximum(x["max"], y["max"]),
+                        "counts": x["counts"] + y["counts"], "calls": x["calls"] + y["calls"]})
+        return out
+
+    def accumulate(self, inp, out):
+        """Runs every bank on (inp, out) and adds the call to the running total; returns the call's own result."""
+        in5 = [inp.get_data_manager_readonly().get(n, True) for n in IN5]
+        truth4 = [out.get_data_manager_readonly().get(n, True) for n in EVAL_FIELDS]
+        raw = [bank.evaluate(inp.get_nz(), in5, truth4) for bank in self.banks]
+        self.history.append([{"stats": json_safe(s.tolist()), "counts": c.tolist()} for s, c in raw])
+        one = [surrogate_scores(s, c) for s, c in raw]
+        self.total = one if self.total is None else self.combine(self.total, one)
+        return one
+
+    def report(self, result=None):
+        """Per model (and `persistence:<bank>`), per class (inactive, active, all) and field: n, bias = sum d / n, mae, rmse, max_abs and
+        rmse_over_persistence (the skill's denominator: the same class and field of the bank's persistence row).  An empty class has n = 0
+        and None for every statistic; so has a ratio whose persistence rmse is 0.  A statistic that is inf or NaN (a diverged model: NaN reaches
+        the sums AND max_abs) is None too, and its field carries "finite": False."""
+        result = self.total if result is None else result
+        if result is None:
+            endrun("SurrogateEvaluator.report: nothing accumulated")
+        rep, first = {}, 0
+        for ib, (bank, r) in enumerate(zip(self.banks, result)):
+            sums, nonf = r["sums"], r["nonfinite"]
+            # class axis -> (inactive, active, all)
+            s3 = _sums_to_float(np.concatenate([sums, sums.sum(axis=1, keepdims=True)], axis=1),
+                                np.concatenate([nonf, nonf.sum(axis=1, keepdims=True)], axis=1))
+            mx = np.concatenate([r["max"], r["max"].max(axis=1, keepdims=True)], axis=1)
+            n = np.concatenate([r["counts"], [r["counts"].sum()]]).astype(np.float64)
+            some = n > 0
+            with np.errstate(divide="ignore", invalid="ignore"):
+                per = s3 / np.where(some, n, 1.0)[None, :, None, None]
+                rmse = np.sqrt(per[..., 2])
+                skill = rmse / rmse[-1:]
+            ok_skill = some[None, :, None] & (rmse[-1:] > 0)
+            for m in range(bank.models + 1):
+                name = self.names[first + m] if m < bank.models else "persistence:%d" % ib
+                rep[name] = {}
+                for c, cname in enumerate(EVAL_CLASSES + ("all",)):
+                    row = {"n": int(n[c])}
+                    for v, fname in enumerate(EVAL_FIELDS):
+                        if some[c]:
+                            row[fname] = finite_or_none({"bias": float(per[m, c, v, 0]), "mae": float(per[m, c, v, 1]), "rmse": float(rmse[m, c, v]),
+                                                         "max_abs": float(mx[m, c, v]),
+                                                         "rmse_over_persistence": float(skill[m, c, v]) if ok_skill[0, c, v] else None})
+                        else:
+                            row[fname] = {"bias": None, "mae": None, "rmse": None, "max_abs": None, "rmse_over_persistence": None}
+                    rep[name][cname] = row
+            first += bank.models
+        return rep
+
+    def table(self, rep=None):
+        """report() as text: one line per model and class, rmse / persistence rmse per field (the skill: < 1 beats doing nothing)."""
+        rep = self.report() if rep is None else rep
+        w = max(len(k) for k in rep)
+        lines = ["%-*s %-8s %12s " % (w, "model", "class", "n") + " ".join("%26s" % ("%s rmse (/pers.)" % f) for f in EVAL_FIELDS)]
+        for name, classes in rep.items():
+            for cname, row in classes.items():
+                cells = [skill_cell(row[f]["rmse"], row[f]["rmse_over_persistence"]) for f in EVAL_FIELDS]
+                lines.append("%-*s %-8s %12d " % (w, name, cname, row["n"]) + " ".join(cells))
+        return "\n".join(lines)
+
+
+class _CommitteeRow:
+    models = 1            # what SurrogateEvaluator.report reads of a bank: the committee is the one "model" beside the persistence row
+
+
+def committee_score(nz, in5, truth4, pred4, range4, workspace=None):
+    """mw_committee_score on contiguous fp64 CUDA fields of nz levels: returns (stats (2, 4, 7) fp64 = [class][field][sum d, sum |d|,
+    sum d^2, max |d|, sum r, sum r^2, sum r |d|], counts (2,) int64 cells per class, covered (2, 4) int64 cells with |d| <= r), d = pred -
+    truth, r = range; classes as SurrogateBank.evaluate -- one device-to-host copy."""
+    every = list(in5) + list(truth4) + list(pred4) + list(range4)
+    if (len(in5), len(truth4), len(pred4), len(range4)) != (5, 4, 4, 4):
+        endrun("committee_score: five input fields and four truth, prediction and range fields expected")
+    n, dev = in5[0].numel(), in5[0].device
+    if int(nz) < 1 or n % int(nz) != 0 or any(t.numel() != n for t in every):
+        endrun("committee_score: the seventeen fields must have one size, a whole number of columns of nz = %d levels" % nz)
+    if any(t.device != dev or t.dtype != torch.float64 or not t.is_contiguous() for t in every):
+        endrun("committee_score: contiguous float64 fields of one device expected")
+    L = capi.lib()
+    ws = fit_workspace(workspace, L.mw_committee_score_workspace_bytes(int(nz), n // int(nz)), dev)
+    buf = StatsAndCounts(56, 10, dev)                                           # the ten counts: cells per class, then covered
+    with torch.cuda.device(dev):
+        check(L.mw_committee_score(int(nz), n // int(nz), _field_ptr_array(in5), _field_ptr_array(truth4), _field_ptr_array(pred4),
+                                   _field_ptr_array(range4), _ptr(ws), buf.stats_ptr, buf.counts_ptr, _stream_ptr(dev)))
+    stats, counts = buf.host()
+    return stats.reshape(2, 4, 7), counts[:2], counts[2:].reshape(2, 4)
+
+
+def range_error_correlation(n, sum_r, sum_r2, sum_a, sum_a2, sum_ra):
+    """Pearson's r of the range r and the error |d| over n cells from their six sums; None when a sum is not finite or a variance is not
+    positive (a constant range, a perfect prediction, an empty class)."""
+    vals = (sum_r, sum_r2, sum_a, sum_a2, sum_ra)
+    if n < 1 or not all(np.isfinite(v) for v in vals):
+        return None
+    mr, ma = sum_r / n, sum_a / n
+    vr, va = sum_r2 / n - mr * mr, sum_a2 / n - ma * ma
+    if not (vr > 0.0 and va > 0.0):
+        return None
+    q = (sum_ra / n - mr * ma) / np.sqrt(vr * va)
+    return float(min(1.0, max(-1.0, q))) if np.isfinite(q) else None
+
+
+class CommitteeEvaluator:
+    """Scores the committee `sel` of a bank against the microphysics in charge, call after call, as SurrogateEvaluator scores single
+    models: accumulate(inp, out) runs the committee forward into scratch fields (mean and range) and mw_committee_score on them, report()
+    gives per class (inactive, active, all) and field the evaluator's row (bias, mae, rmse, max_abs, rmse_over_persistence) plus mean_range,
+    coverage (the fraction of cells with |d| <= range) and range_error_correlation (range_error_correlation above)."""
+
+    def __init__(self, bank, sel):
+        self.bank, self.sel = bank, [int(i) for i in sel]
+        if not 1 <= len(self.sel) <= capi.MW_COMMITTEE_MAX_MODELS:
+            endrun("CommitteeEvaluator: a committee has 1 to %d models, got %d" % (capi.MW_COMMITTEE_MAX_MODELS, len(self.sel)))
+        if len(set(self.sel)) != len(self.sel) or any(not 0 <= i < bank.models for i in self.sel):
+            endrun("CommitteeEvaluator: the committee must name distinct models of the bank's %d" % bank.models)
+        self.total = None
+        self.history = []
+        self._scratch = None
+        self._ws = None
+
+    def accumulate(self, inp, out):
+        """One call: the committee's mean and range from `inp`, scored against `out`; added to the running total.  Returns the call's raw
+        (stats (2, 2, 4, 7) = [committee | persistence], counts (2,), covered (2, 4))."""
+        nz = inp.get_nz()
+        in5 = [inp.get_data_manager_readonly().get(n, True) for n in IN5]
+        truth4 = [out.get_data_manager_readonly().get(n, True) for n in EVAL_FIELDS]
+        if self._scratch is None or self._scratch[0].shape != in5[0].shape:
+            self._scratch = [torch.empty_like(in5[0]) for _ in range(8)]
+        pred4, range4 = self._scratch[:4], self._scratch[4:]
+        as1 = lambda ts: [t.reshape(nz, -1, 1) for t in ts]                     # noqa: E731   (every member is one more column)
+        self.bank.committee_apply(nz, self.sel, 0, as1(in5), as1(pred4), as1(range4))
+        ws = grown_workspace(self, "_ws", capi.lib().mw_committee_score_workspace_bytes(nz, in5[0].numel() // nz), in5[0].device)
+        stats, counts, covered = committee_score(nz, in5, truth4, pred4, range4, ws)
+        pstats, _, _ = committee_score(nz, in5, truth4, [in5[0], in5[2], in5[3], in5[4]], range4, ws)      # persistence: prediction = input
+        both = np.stack([stats, pstats])
+        self.history.append({"stats": json_safe(both.tolist()), "counts": counts.tolist(), "covered": covered.tolist()})
+        units, nonf = _exact_units_array(stats[..., 4:])
+        one = {"scores": [surrogate_scores(both[..., :4], counts)], "rsums": units, "rnonfinite": nonf, "covered": covered.astype(np.int64)}
+        if self.total is None:
+            self.total = one
+        else:
+            t = self.total
+            self.total = {"scores": SurrogateEvaluator.combine(t["scores"], one["scores"]), "rsums": t["rsums"] + units,
+                          "rnonfinite": t["rnonfinite"] + nonf, "covered": t["covered"] + one["covered"]}
+        return both, counts, covered
+
+    def report(self):
+        if self.total is None:
+            endrun("CommitteeEvaluator.report: nothing accumulated")
+        t = self.total
+        base = SurrogateEvaluator([_CommitteeRow()], ["committee"]).report(t["scores"])["committee"]
+        sc = t["scores"][0]
+        counts = np.concatenate([sc["counts"], [sc["counts"].sum()]])
+        with3 = lambda a: np.concatenate([a, a.sum(axis=0, keepdims=True)], axis=0)      # noqa: E731   class axis -> (inactive, active, all)
+        rs = _sums_to_float(with3(t["rsums"]), with3(t["rnonfinite"]))                 # (3, 4, 3): sum r, sum r^2, sum r |d|
+        ds = _sums_to_float(with3(sc["sums"][0]), with3(sc["nonfinite"][0]))           # (3, 4, 3): sum d, sum |d|, sum d^2
+        cov = with3(t["covered"])
+        rep = {}
+        for c, cname in enumerate(EVAL_CLASSES + ("all",)):
+            n = int(counts[c])
+            row = {"n": n}
+            for v, fname in enumerate(EVAL_FIELDS):
+                f = dict(base[cname][fname])
+                if n > 0:
+                    mr = rs[c, v, 0] / n
+                    f["mean_range"] = float(mr) if np.isfinite(mr) else None
+                    f["coverage"] = int(cov[c, v]) / n
+                    f["range_error_correlation"] = range_error_correlation(n, rs[c, v, 0], rs[c, v, 1], ds[c, v, 1], ds[c, v, 2], rs[c, v, 2])
+                    if f["mean_range"] is None:
+                        f["finite"] = False
+                else:
+                    f.update(mean_range=None, coverage=None, range_error_correlation=None)
+                row[fname] = f
+            rep[cname] = row
+        return rep
+
+    def table(self, rep=None, name="committee"):
+        """report() as text: one line per class; rmse / persistence rmse, mean range and coverage per field."""
+        rep = self.report() if rep is None else rep
+        lines = ["%-16s %-8s %12s " % ("committee", "class", "n") + " ".join("%40s" % ("%s rmse (/pers.) range cover" % f) for f in EVAL_FIELDS)]
+        for cname, row in rep.items():
+            cells = ["%40s" % ("%s (%s) %s %s" % (or_dash(row[f]["rmse"], "%.4e"), or_dash(row[f]["rmse_over_persistence"], "%.4g"),
+                                                   or_dash(row[f]["mean_range"], "%.3e"), or_dash(row[f]["coverage"], "%.3f"))) for f in EVAL_FIELDS]
+            lines.append("%-16s %-8s %12d " % (name, cname, row["n"]) + " ".join(cells))
+        return "\n".join(lines)

@@ -160,17 +160,17 @@ def kernel_nadam_table(steps, learning_rate=1e-3, first_step=0):
 # data and arguments (host checks: they run before anything reaches the device)
 def read_samples(sample_files, stencil=False):
     """Concatenates the files DataGenerator writes (CDF-5: inputs (nsamples, 5, 2), outputs (nsamples, 4) fp32) in the order given, through
-    modules._NcFile.  Returns inputs (n, 5) = slot 0 of the stencil (the single-cell model), outputs (n, 4), and the grid metadata.
+    ncio.NcFile.  Returns inputs (n, 5) = slot 0 of the stencil (the single-cell model), outputs (n, 4), and the grid metadata.
     stencil=True: inputs (n, 9) = slot 0, then rows 0..3 of slot 1 (temperature, vapor, cloud and precipitation of the level above; its
     row 4 is never assigned and is not read)."""
-    from .modules import _NcFile
+    from .ncio import NcFile
     if isinstance(sample_files, (str, os.PathLike)):
         sample_files = [sample_files]
     if not sample_files:
         raise SurrogateTrainError("no sample files given")
     ins, outs, meta = [], [], None
     for path in sample_files:
-        nc = _NcFile(os.fspath(path), False)
+        nc = NcFile(os.fspath(path), False)
         try:
             i3, o2 = nc.get("inputs"), nc.get("outputs")
             m = {k: float(nc.get(k)) for k in ("time_step_size", "dx", "dy", "dz")}
@@ -213,9 +213,10 @@ def data_scaling(inputs, outputs, allow_constant=False):
 
 def load_init(init, stencil=False):
     """The model a warm start continues: (weights (104 | 144,) fp32 in Keras order, scl_in, scl_out) from DIR/weights.txt,
-    input_scaling.txt and output_scaling.txt (the files write_outputs leaves), read by modules.load_surrogate_weights.  Host only.  The
+    input_scaling.txt and output_scaling.txt (the files write_outputs leaves), read by mlp.load_surrogate_weights.  Host only.  The
     width must be the one that is trained."""
-    from .modules import MWError, load_surrogate_weights
+    from .capi import MWError
+    from .mlp import load_surrogate_weights
     paths = [os.path.join(os.fspath(init), f) for f in ("weights.txt", "input_scaling.txt", "output_scaling.txt")]
     for path in paths:
         if not os.path.exists(path):
@@ -369,8 +370,8 @@ class Trainer:
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
     def _predict(self, w104, x, out):
-        from .modules import _PonniLayer
         from .capi import check
+        from .mlp import _PonniLayer
         lay = (_PonniLayer * 5)(*[_PonniLayer(*r) for r in _layers(self.n_in)])
         w = np.ascontiguousarray(w104, dtype=np.float32)
         check(self.L.mw_ponni_forward(C.cast(lay, C.c_void_p), 5, w.ctypes.data_as(C.POINTER(C.c_float)), self.npar, x.shape[1], self._p(x),

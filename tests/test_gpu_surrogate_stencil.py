@@ -351,15 +351,15 @@ def test_stencil_cli_then_inference_ponni_driver(mw, oracle, tmp_path, monkeypat
     """python -m miniweatherml_amd.surrogate_train FILES --stencil --out DIR, then driver inference_ponni with keras_weights_txt /
     nn_input_scaling pointing into DIR: no new YAML key; the module runs the stencil network."""
     from test_gpu_driver import write_yaml
-    from miniweatherml_amd import driver, modules, surrogate_train as st
+    from miniweatherml_amd import driver, microphysics, surrogate_train as st
     from util import gpu_fields
     gen, _, _, _ = rainy_samples(oracle, tmp_path, 32, 32, 16)
     monkeypatch.chdir(tmp_path)
     assert st.main([gen.fname, "--stencil", "--out", "trained", "--epochs", "2", "--batch-size", "256"]) == 0
     assert "wrote" in capsys.readouterr().out and len(np.loadtxt("trained/weights.txt", comments="#")) == 144
     seen = []
-    real = modules.mlp_stencil_forward
-    monkeypatch.setattr(modules, "mlp_stencil_forward", lambda *a, **k: (seen.append(a[6].shape), real(*a, **k))[1])
+    real = microphysics.mlp_stencil_forward                              # where Microphysics_Kessler_Surrogate.time_step looks the name up
+    monkeypatch.setattr(microphysics, "mlp_stencil_forward", lambda *a, **k: (seen.append(a[6].shape), real(*a, **k))[1])
     path, _ = write_yaml(tmp_path, nx=32, ny=1, nz=20, xlen=32000., extra='keras_weights_txt: "trained/weights.txt"\n'
                          'nn_input_scaling: "trained/input_scaling.txt"\nnn_output_scaling: "trained/output_scaling.txt"')
     coupler, dycore, info = driver.run("inference_ponni", path, max_steps=3, quiet=True)
