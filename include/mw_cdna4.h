@@ -598,6 +598,33 @@ int  mw_kessler_members_teacher(int nz, long long ncol, int nens, int nm, const 
 /* Host only: the teacher's decision function on a member's minimum rain CFL step dt_max -- ceil(dt / dt_max) if dt_max is finite,
  * > 0 and the quotient is in [1, cap], else 0.  Decided in floating point before any conversion to int. */
 int  mw_kessler_teacher_rainsplit(double dt, double dt_max, int cap);
+
+/* ---- guarded committee: Kessler takes the columns where the committee's models disagree ------------------ */
+/* Three passes that, between an out-of-place mw_surrogate_committee_apply and the state, make the member "the committee's mean where its
+ * models agree, Kessler where they do not" (DESIGN.md 13.7).  All member-fastest (nz, ncol, nens), all asynchronous on `stream`.
+ * mw_committee_guard_flags: column col of `member` is flagged iff, at some level k and for some field f of temp, water_vapor,
+ * cloud_liquid, precip_liquid, !(range4[f] <= thr4[f]) or mean4[f] is not finite -- so a NaN range flags, a range EQUAL to its threshold
+ * does not, and thr4[f] = +inf means that field never flags by size.  mean4 / range4: HOST arrays of 4 DEVICE pointers (what
+ * committee_apply wrote); thr4: HOST, 4 thresholds >= 0 (negative or NaN: refused).  flags: DEVICE bytes (ncol, nens), byte
+ * col * nens + member receives 0 or 1 for every column of `member`, no other byte is touched.  counts: DEVICE int64 [2]; [0] is SET to
+ * this call's number of flagged columns, [1] is INCREASED by it (integer atomics: run-to-run identical).  One pass over the member's
+ * 64 bytes per cell. */
+int  mw_committee_guard_flags(int nz, long long ncol, int nens, int member, const double *const *mean4, const double *const *range4,
+                              const double *thr4, unsigned char *flags, long long *counts, void *stream);
+/* mw_kessler_members_teacher with "column col * nens + e takes part iff flags[col * nens + e] != 0" in place of the member list: for
+ * the flagged columns F of a member, in ascending order, out4 receives the bits mw_kessler_time_step leaves when it is given those
+ * columns alone as contiguous (nz, |F|) fields -- the rain sub-cycle count is the minimum over F only, decided by
+ * mw_kessler_teacher_rainsplit.  A member whose count is 0 (more than max_rainsplit sub-cycles, or inf / NaN rain or fall speed in a
+ * FLAGGED column) is skipped: nothing of it is written.  Elements of unflagged columns of out4 are never written; fields5 is never
+ * written; precl is not produced.  rainsplit_out: optional HOST array of nens counts (a member without a flagged column: 1; forces a
+ * stream synchronisation).  The same workspace layout, start-of-call memset and repeatability as the members teacher.  A wavefront
+ * without a flagged lane leaves after one byte load per lane. */
+long long mw_kessler_columns_teacher_workspace_bytes(int nz, long long ncol, int nens);
+int  mw_kessler_columns_teacher(int nz, long long ncol, int nens, const unsigned char *flags, double dz, double dt, int max_rainsplit,
+                                const double *const *fields5, double *const *out4, int *rainsplit_out, void *workspace, void *stream);
+/* dst[f][c * nens + e] = src[f][c * nens + e] for the n cells c, the nm members e in `members` (HOST, distinct, nens <= 64) and the nf
+ * (<= MW_MAX_TRACERS) fields: the commit of a scratch result into the state.  Elements of other members are not touched. */
+int  mw_members_copy(long long n, int nens, int nm, const int *members, int nf, const double *const *src, double *const *dst, void *stream);
 /* DataGenerator's sampler on the member layout, between the listed members' own fields5 and their teacher values teacher4 (as above).
  * mw_member_sample_mask: mask (DEVICE bytes, (nz, ncol, nens)) of element t = (k * ncol + col) * nens + e is 1 if e is listed,
  * u01(key0 + t) < (active ? thr_active : thr_inactive) with u01 and `active` as mw_micro_sample_mask has them (any of the four

@@ -172,6 +172,13 @@ SYMBOLS = {
     "mw_kessler_members_teacher": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double, C.c_int,
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
     "mw_kessler_teacher_rainsplit": (C.c_int, [C.c_double, C.c_double, C.c_int]),
+    "mw_committee_guard_flags": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mw_kessler_columns_teacher_workspace_bytes": (C.c_longlong, [C.c_int, C.c_longlong, C.c_int]),
+    "mw_kessler_columns_teacher": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int,
+                                             C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
+    "mw_members_copy": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                  C.c_void_p]),
     "mw_member_sample_mask": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                         C.c_ulonglong, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "mw_member_gather_samples": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_longlong,

@@ -144,13 +144,13 @@ __device__ __forceinline__ double kessler_velqr(double rho_r, double rd, double 
 // chunk-boundary level, whose flux the sweep needs -- evaluate the fall speed (:260).  The pass is then a stream over two fields.
 // TEACH (k_kessler_prep_t<true>, the teacher's CFL pass, see TEACHER below): p.ncol = ncol * nens columns with the member fastest, only
 // columns of `listed` members take part, `words` holds one minimum word per member and a column lowers the word of member i % nens only;
-// next_bits is not used.  A column that could raise its member's count is rare (see above); a wavefront that holds one reduces per
+// next_bits is not used; flags is null or the columns teacher's (below).  A column that could raise its member's count is rare (see above); a wavefront that holds one reduces per
 // member present, then one atomicMin per (wavefront, member).
 template <bool TEACH>
 __global__ __launch_bounds__(256) void k_kessler_prep_t(KesP p, const double *__restrict__ rho_r, const double *__restrict__ rho_d,
                                                         double *__restrict__ flux_top, int chunk, int klevels,
                                                         unsigned long long *words, unsigned long long *next_bits,
-                                                        int nens, unsigned long long listed) {
+                                                        int nens, unsigned long long listed, const unsigned char *flags) {
 #pragma clang fp contract(off)
   if constexpr (!TEACH)
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *next_bits = MW_KES_INF;    // the NEXT call's word (see MW_KES_INF)
@@ -160,7 +160,13 @@ __global__ __launch_bounds__(256) void k_kessler_prep_t(KesP p, const double *__
   if constexpr (TEACH) e = (i < p.ncol) ? (int)(i % nens) : -1;
   double dtc = p.dt;                                          // every cell's contribution is capped at dt (see above)
   bool takes_part = i < p.ncol;
-  if constexpr (TEACH) takes_part = e >= 0 && ((listed >> e) & 1ull);
+  if constexpr (TEACH) {
+    takes_part = e >= 0 && ((listed >> e) & 1ull);
+    // COLUMNS teacher (mw_kessler_columns_teacher): flags holds one byte per column i -- null for the members teacher.  Only flagged
+    // columns take part: an unflagged one neither lowers its member's word nor sends it to 0.  (The argument comes last, after the
+    // teacher's two: it moves no kernarg offset of the in-place instance; see TEACHER below.)
+    if (takes_part && flags) takes_part = flags[i] != 0;
+  }
   if (takes_part) {
     const double rho0 = rho_d[i];
     const double lim = 0.8 * p.dz / p.dt;
@@ -451,7 +457,7 @@ __global__ __launch_bounds__(256) void k_kessler_column(KesP p, double *__restri
 //     non-restrict `const double *in` / `double *out` parameters, the in-place kernels passing each field twice, changes the code of
 //     k_kessler_chunks, k_kessler_column and k_kessler_sweep.  The teacher's const inputs therefore come in through a const_cast;
 //   * b / ci in kessler_column_body (see there): per-column bases in vector registers for the teacher, uniform bases for the in-place form;
-//   * the CFL pass is a template KERNEL whose two teacher arguments come LAST.  The same text in a __forceinline__ function that two
+//   * the CFL pass is a template KERNEL whose teacher arguments come LAST.  The same text in a __forceinline__ function that two
 //     kernels call changes the in-place kernel (even unedited, and more so when dtc is returned or passed by reference), and arguments
 //     in the middle shift four kernarg offsets of the in-place instance.
 // ---------------------------------------------------------------------------------------------------------------
@@ -490,6 +496,38 @@ __global__ __launch_bounds__(256) void k_kessler_teacher_column(KesP p, KesTeach
   const int rainsplit = kessler_teacher_count(p, t, e);       // <= cap: the only bound of the body's loop
   if (rainsplit < 2) return;                                  // 1: k_kessler_teacher_chunks; 0: skipped
   // const_cast: as in k_kessler_teacher_chunks
+  kessler_column_body<true>(p, rainsplit, const_cast<double *>(t.rho_v), const_cast<double *>(t.rho_c), const_cast<double *>(t.rho_r), t.rho_d,
+                            const_cast<double *>(t.temp), nullptr, w_velqr, KesOut{t.o_temp, t.o_v, t.o_c, t.o_r});
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// COLUMNS teacher (mw_kessler_columns_teacher): the teacher with "column i takes part iff flags[i] != 0" in place of the member list --
+// what a guarded committee runs on the columns where its models disagree.  The same three launches: k_kessler_prep_t<true> with every
+// member listed and the flags as its last argument, then the two sweeps below, which are the teacher's with the flag test in front.  A
+// wavefront without a flagged lane leaves after one byte load per lane, so a call costs what the wavefronts that hold a flagged column
+// cost; a member's count is the minimum over ITS flagged columns (no flagged column: the word is never lowered, the count is 1 and
+// nothing of the member is written).
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_kessler_columns_chunks(KesP p, KesTeach t, const unsigned char *__restrict__ flags,
+                                                                const double *__restrict__ flux_top, int chunk) {
+#pragma clang fp contract(off)
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.ncol) return;
+  if (!flags[i]) return;
+  if (kessler_teacher_count(p, t, (int)(i % t.nens)) != 1) return;          // > 1: k_kessler_columns_column; 0: skipped
+  // const_cast: as in k_kessler_teacher_chunks
+  kessler_chunks_body<true>(p, const_cast<double *>(t.rho_v), const_cast<double *>(t.rho_c), const_cast<double *>(t.rho_r), t.rho_d,
+                            const_cast<double *>(t.temp), nullptr, flux_top, chunk, KesOut{t.o_temp, t.o_v, t.o_c, t.o_r});
+}
+
+__global__ __launch_bounds__(256) void k_kessler_columns_column(KesP p, KesTeach t, const unsigned char *__restrict__ flags,
+                                                                double *__restrict__ w_velqr) {
+#pragma clang fp contract(off)
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.ncol) return;
+  if (!flags[i]) return;
+  const int rainsplit = kessler_teacher_count(p, t, (int)(i % t.nens));     // <= cap: the only bound of the body's loop
+  if (rainsplit < 2) return;                                                // 1: k_kessler_columns_chunks; 0: skipped
   kessler_column_body<true>(p, rainsplit, const_cast<double *>(t.rho_v), const_cast<double *>(t.rho_c), const_cast<double *>(t.rho_r), t.rho_d,
                             const_cast<double *>(t.temp), nullptr, w_velqr, KesOut{t.o_temp, t.o_v, t.o_c, t.o_r});
 }
@@ -714,7 +752,7 @@ int mw_kessler_time_step(int nz, long long ncol, double dz, double dt, double *r
     double *flux_top = ws + 5ll * nz * ncol;                  // (nchunks-1, ncol)
     const int klevels = 5;                                      // levels per thread of the CFL pass (k_kessler_prep_t: KL)
     hipLaunchKernelGGL(k_kessler_prep_t<false>, dim3((unsigned)((ncol + 255) / 256), (unsigned)((nz + klevels - 1) / klevels)), dim3(256), 0, st, p,
-                       rho_r, rho_d, flux_top, chunk, klevels, bits, next_bits, 0, 0ull); MW_LAUNCH_CHECK();
+                       rho_r, rho_d, flux_top, chunk, klevels, bits, next_bits, 0, 0ull, (const unsigned char *)nullptr); MW_LAUNCH_CHECK();
     if (kessler_min_words(st, workspace, nullptr, nullptr, true)) return 1;
 #if MW_KES_SWEEP
     hipLaunchKernelGGL(k_kessler_sweep, dim3((unsigned)((ncol + 255) / 256), (unsigned)nchunks), dim3(256), 0, st, p, rho_v, rho_c, rho_r,
@@ -781,7 +819,7 @@ int mw_kessler_members_teacher(int nz, long long ncol, int nens, int nm, const i
   const int klevels = 5;                                      // (k_kessler_prep_t: KL)
   const unsigned gx = (unsigned)((NC + 255) / 256);
   hipLaunchKernelGGL(k_kessler_prep_t<true>, dim3(gx, (unsigned)((nz + klevels - 1) / klevels)), dim3(256), 0, st, p, t.rho_r, t.rho_d,
-                     flux_top, chunk, klevels, words, (unsigned long long *)nullptr, nens, listed); MW_LAUNCH_CHECK();
+                     flux_top, chunk, klevels, words, (unsigned long long *)nullptr, nens, listed, (const unsigned char *)nullptr); MW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_kessler_teacher_chunks, dim3(gx, (unsigned)nchunks), dim3(256), 0, st, p, t, (const double *)flux_top, chunk); MW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_kessler_teacher_column, dim3(gx), dim3(256), 0, st, p, t, w_velqr); MW_LAUNCH_CHECK();
   if (rainsplit_out) {
@@ -789,6 +827,46 @@ int mw_kessler_members_teacher(int nz, long long ncol, int nens, int nm, const i
     MW_HIP(hipMemcpyAsync(hw, words, 8 * (size_t)nens, hipMemcpyDeviceToHost, st));
     MW_HIP(hipStreamSynchronize(st));
     for (int j = 0; j < nm; j++) rainsplit_out[j] = kessler_teacher_rainsplit(dt, kessler_teacher_word(hw[members[j]], dt), max_rainsplit);
+  }
+  return 0;
+}
+
+long long mw_kessler_columns_teacher_workspace_bytes(int nz, long long ncol, int nens) {
+  return mw_kessler_members_teacher_workspace_bytes(nz, ncol, nens);         // the same words, w_velqr and flux_top
+}
+
+int mw_kessler_columns_teacher(int nz, long long ncol, int nens, const unsigned char *flags, double dz, double dt, int max_rainsplit,
+                               const double *const *fields5, double *const *out4, int *rainsplit_out, void *workspace, void *stream) {
+  if (nz < 2 || ncol < 1) MW_FAIL("kessler_columns_teacher: need nz >= 2 and ncol >= 1");
+  if (nens < 1 || nens > 64) MW_FAIL("kessler_columns_teacher: nens must be in [1, 64]");
+  if (!(dt > 0)) MW_FAIL("kessler_columns_teacher: called with nonpositive dt");
+  if (max_rainsplit < 1 || max_rainsplit > 1024) MW_FAIL("kessler_columns_teacher: max_rainsplit must be in [1, 1024]");
+  if (!flags || !fields5 || !out4 || !workspace) MW_FAIL("kessler_columns_teacher: null pointer");
+  for (int f = 0; f < 5; f++) if (!fields5[f]) MW_FAIL("kessler_columns_teacher: null field");
+  for (int f = 0; f < 4; f++) if (!out4[f]) MW_FAIL("kessler_columns_teacher: null field");
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  hipStream_t st = (hipStream_t)stream;
+  const long long NC = ncol * nens;                           // the kernels' columns: col * nens + member, and the flags' index
+  const KesP p = kessler_params(nz, NC, dz, dt);
+  unsigned long long *words = (unsigned long long *)workspace;
+  double *w_velqr = (double *)((char *)workspace + 512), *flux_top = w_velqr + (long long)nz * NC;
+  KesTeach t;
+  t.nens = nens; t.cap = max_rainsplit; t.listed = ~0ull; t.words = words;
+  t.temp = fields5[0]; t.rho_d = fields5[1]; t.rho_v = fields5[2]; t.rho_c = fields5[3]; t.rho_r = fields5[4];
+  t.o_temp = out4[0]; t.o_v = out4[1]; t.o_c = out4[2]; t.o_r = out4[3];
+  MW_HIP(hipMemsetAsync(words, 0xFF, 512, st));               // as the members teacher: every call starts its words in stream order
+  const int chunk = kessler_chunk_used(nz, NC), nchunks = (nz + chunk - 1) / chunk;
+  const int klevels = 5;                                      // (k_kessler_prep_t: KL)
+  const unsigned gx = (unsigned)((NC + 255) / 256);
+  hipLaunchKernelGGL(k_kessler_prep_t<true>, dim3(gx, (unsigned)((nz + klevels - 1) / klevels)), dim3(256), 0, st, p, t.rho_r, t.rho_d,
+                     flux_top, chunk, klevels, words, (unsigned long long *)nullptr, nens, t.listed, flags); MW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_kessler_columns_chunks, dim3(gx, (unsigned)nchunks), dim3(256), 0, st, p, t, flags, (const double *)flux_top, chunk); MW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_kessler_columns_column, dim3(gx), dim3(256), 0, st, p, t, flags, w_velqr); MW_LAUNCH_CHECK();
+  if (rainsplit_out) {
+    unsigned long long hw[64];
+    MW_HIP(hipMemcpyAsync(hw, words, 8 * (size_t)nens, hipMemcpyDeviceToHost, st));
+    MW_HIP(hipStreamSynchronize(st));
+    for (int e = 0; e < nens; e++) rainsplit_out[e] = kessler_teacher_rainsplit(dt, kessler_teacher_word(hw[e], dt), max_rainsplit);
   }
   return 0;
 }

@@ -4,6 +4,8 @@
 // alone), and how far every member has moved from member 0 (mw_member_divergence).  No reference counterpart: the reference's ensemble
 // members never meet.  mw_member_sample_mask / mw_member_gather_samples are DataGenerator's sampler (k_sample_mask / k_gather_samples of
 // mw_output.hip, which see member 0 only) on the member layout, between a member's own state and its Kessler teacher values.
+// mw_committee_guard_flags / mw_members_copy are the guarded committee's two passes that are not Kessler's: which columns
+// of a member go to Kessler, and the commit of the scratch result into the state.
 // =====================================================================================================
 #include "../../include/mw_cdna4.h"
 #include "mw_common.h"
@@ -148,6 +150,57 @@ __global__ __launch_bounds__(256) void k_member_gather_samples(MemberSample f, c
   for (int v = 0; v < 4; v++) out[v] = (float)f.teach[v][c];
 }
 
+// ---- mw_committee_guard_flags / mw_members_copy ---------------------------------------------------------------------------------------
+struct GuardFields { const double *mean[4], *range[4]; double thr[4]; };
+
+// A workgroup takes 64 consecutive columns of the member; lane l of each of its four wavefronts holds column 64 * block + l, and wavefront
+// g the levels g, g + 4, ...  The member's elements of a level are nens doubles apart, so a wavefront's load touches the same 64-byte
+// lines whichever way threads are laid over columns (a line holds 8 / nens of them, every line of the level for nens <= 8): the lines
+// cannot be fewer.  An iteration loads the eight values of TWO levels into registers before it tests any of them, and the tests are
+// joined with | on integers, not ||: with short-circuit tests every load waits for the test before it (one 8-byte load in flight per
+// lane, and a lane that has flagged stops reading).  So a wavefront has sixteen loads in flight, a block four times that.  The OR over
+// levels is order-free; the count is a popcount of the block's 64-bit mask and one integer atomicAdd per word.
+__global__ __launch_bounds__(256) void k_committee_guard_flags(int nz, long long ncol, int nens, int member, GuardFields G,
+                                                               unsigned char *__restrict__ flags, unsigned long long *__restrict__ counts) {
+  __shared__ unsigned long long masks[4];
+  const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const long long c = (long long)blockIdx.x * 64 + lane;
+  int bad = 0;
+  if (c < ncol) {
+    const long long plane = ncol * nens, base = c * nens + member;
+    for (int k = g; k < nz; k += 8) {
+      const long long idx0 = (long long)k * plane + base;
+      const long long idx1 = (long long)(k + 4 < nz ? k + 4 : k) * plane + base;       // past the top: level k again, which an OR may see twice
+      double r[8], m[8];
+#pragma unroll
+      for (int f = 0; f < 4; f++) { r[f] = G.range[f][idx0]; m[f] = G.mean[f][idx0]; r[4 + f] = G.range[f][idx1]; m[4 + f] = G.mean[f][idx1]; }
+#pragma unroll
+      for (int f = 0; f < 8; f++)                                                       // NaN flags; a range equal to its threshold does not
+        bad |= (int)!(r[f] <= G.thr[f & 3]) | (int)!(fabs(m[f]) <= 1.7976931348623157e308);
+    }
+  }
+  const bool flag = bad != 0;
+  const unsigned long long mine = __ballot(flag);
+  if (lane == 0) masks[g] = mine;
+  __syncthreads();
+  if (g != 0) return;
+  const unsigned long long all = masks[0] | masks[1] | masks[2] | masks[3];
+  if (c < ncol) flags[c * nens + member] = (unsigned char)((all >> lane) & 1ull);
+  if (lane == 0 && all) {
+    const unsigned long long q = (unsigned long long)__popcll(all);
+    atomicAdd(counts, q);
+    atomicAdd(counts + 1, q);
+  }
+}
+
+// thread = flat element t = cell * nens + e, grid row y = field: the listed members' elements from src to dst
+__global__ __launch_bounds__(256) void k_members_copy(long long total, int nens, unsigned long long listed, MemberFields src, MemberFields dst) {
+  const double *a = src.f[blockIdx.y];
+  double *b = dst.f[blockIdx.y];
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256)
+    if ((listed >> (int)(t % nens)) & 1ull) b[t] = a[t];
+}
+
 } // namespace mw
 
 using namespace mw;
@@ -248,6 +301,56 @@ extern "C" int mw_member_gather_samples(int nz, long long ncol, int nens, const 
   const long long plane = ncol * nens;
   hipLaunchKernelGGL(k_member_gather_samples, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f, elems, n, plane * nz, plane,
                      inputs, outputs);
+  MW_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mw_committee_guard_flags(int nz, long long ncol, int nens, int member, const double *const *mean4, const double *const *range4,
+                                        const double *thr4, unsigned char *flags, long long *counts, void *stream) {
+  if (!mean4 || !range4 || !thr4 || !flags || !counts) MW_FAIL("committee_guard_flags: null pointer");
+  if (nz < 1 || ncol < 1 || nens < 1) MW_FAIL("committee_guard_flags: nz, ncol and nens must be >= 1");
+  if (member < 0 || member >= nens) MW_FAIL("committee_guard_flags: member " + std::to_string(member) + " is outside [0, " + std::to_string(nens) + ")");
+  if ((double)nz * (double)ncol * (double)nens > 9.0e18) MW_FAIL("committee_guard_flags: the fields are too large");
+  GuardFields G;
+  for (int f = 0; f < 4; f++) {
+    if (!mean4[f] || !range4[f]) MW_FAIL("committee_guard_flags: null field");
+    if (!(thr4[f] >= 0.0)) MW_FAIL("committee_guard_flags: threshold " + std::to_string(f) + " is negative or NaN (+inf: the field never flags by size)");
+    G.mean[f] = mean4[f]; G.range[f] = range4[f]; G.thr[f] = thr4[f];
+  }
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  hipStream_t st = (hipStream_t)stream;
+  MW_HIP(hipMemsetAsync(counts, 0, 8, st));                                 // counts[0]: this call's count; counts[1] goes on accumulating
+  hipLaunchKernelGGL(k_committee_guard_flags, dim3((unsigned)((ncol + 63) / 64)), dim3(256), 0, st, nz, ncol, nens, member, G, flags,
+                     (unsigned long long *)counts);
+  MW_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mw_members_copy(long long n, int nens, int nm, const int *members, int nf, const double *const *src, double *const *dst,
+                               void *stream) {
+  if (!members || !src || !dst) MW_FAIL("members_copy: null pointer");
+  if (n < 1) MW_FAIL("members_copy: n must be >= 1");
+  if (nens < 1 || nens > 64) MW_FAIL("members_copy: nens must be in [1, 64]");
+  if (nm < 1 || nm > nens) MW_FAIL("members_copy: nm must be in [1, nens]");
+  if (nf < 1 || nf > MW_MAX_TRACERS) MW_FAIL("members_copy: nf must be in [1, " + std::to_string(MW_MAX_TRACERS) + "]");
+  if ((double)n * (double)nens > 9.0e18) MW_FAIL("members_copy: the fields are too large");
+  unsigned long long listed = 0;
+  for (int j = 0; j < nm; j++) {
+    const int e = members[j];
+    if (e < 0 || e >= nens) MW_FAIL("members_copy: member " + std::to_string(e) + " is outside [0, " + std::to_string(nens) + ")");
+    if ((listed >> e) & 1ull) MW_FAIL("members_copy: member " + std::to_string(e) + " is listed twice");
+    listed |= 1ull << e;
+  }
+  MemberFields A, B;
+  for (int f = 0; f < MW_MAX_TRACERS; f++) { A.f[f] = nullptr; B.f[f] = nullptr; }
+  for (int f = 0; f < nf; f++) {
+    if (!src[f] || !dst[f]) MW_FAIL("members_copy: null field");
+    A.f[f] = (double *)src[f]; B.f[f] = dst[f];
+  }
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  const long long total = n * nens;
+  const long long blocks = std::max<long long>(1, std::min<long long>((total + 255) / 256, 256 * 16));
+  hipLaunchKernelGGL(k_members_copy, dim3((unsigned)blocks, (unsigned)nf), dim3(256), 0, (hipStream_t)stream, total, nens, listed, A, B);
   MW_LAUNCH_CHECK();
   return 0;
 }

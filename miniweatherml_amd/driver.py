@@ -42,6 +42,12 @@ makes committees of the listed models (committee_config; surrogate_eval.Surrogat
 listed order, and their range).  rollout_surrogates rolls each committee out as one more member after the models (nens counts them; a
 committee cannot be harvested), evaluate_surrogates scores each one (surrogate_eval.CommitteeEvaluator; `committees` in the JSON and the table),
 and inference_ponni runs the committee instead of one network when the YAML names exactly one and no keras_weights_* key.
+      - {name: guarded3, members: [seed0, seed1, seed2], guard: {precip_liquid: 1.0e-5, temp: 0.5, max_rainsplit: 64}}
+is a GUARDED committee: where the range of its models exceeds a threshold at some level of a column (field units; a
+field left out never flags by size; a non-finite mean always flags), Kessler takes that column in that step, with rain sub-cycles from
+the flagged columns alone (more than max_rainsplit, default 64: the mean stays).  surrogate_rollout.json gets a `guard` block per
+guarded committee: the thresholds, `columns`, `flagged_total`, and `flagged` / `rainsplit` at every scoring step.  inference_ponni runs
+the guarded step when its one committee has a guard; evaluate_surrogates, which scores the mean, refuses an entry with a guard.
 """
 import argparse
 import os
@@ -91,7 +97,7 @@ def surrogate_config(cfg):
     return _surrogate_models(cfg["surrogate_models"], cfg["_dir"]), interval
 
 
-COMMITTEE_KEYS = ("name", "members")
+COMMITTEE_KEYS = ("name", "members", "guard")
 
 
 def _model_width(m):
@@ -103,8 +109,11 @@ def _model_width(m):
 def committee_config(cfg):
     """The checked `surrogate_committees:` list of a loaded configuration, [] without the key: entries {name, members: [model names]} --
     1 .. 16 distinct models of `surrogate_models`, all of one width; committee names unique and no model's name, 'kessler' or
-    'persistence'.  Returns [{"name", "members"}] in the YAML's order."""
+    'persistence'.  An entry may carry `guard:` (surrogate_eval.guard_config: thresholds per field and max_rainsplit), which makes it a
+    guarded committee; a guarded and an unguarded committee of the same models may stand side by side under two names.  Returns
+    [{"name", "members"}] in the YAML's order, with "guard" (the checked mapping) where the entry has one."""
     from . import capi
+    from .surrogate_eval import guard_config
     if "surrogate_committees" not in cfg:
         return []
     models, _ = surrogate_config(cfg)
@@ -135,9 +144,22 @@ def committee_config(cfg):
         if cname in names or cname in ("kessler", "persistence"):
             raise ValueError("ERROR: committee name %r collides with a surrogate model, 'kessler' or 'persistence'" % cname)
         out.append({"name": cname, "members": members})
+        if "guard" in e:
+            out[-1]["guard"] = guard_config(e["guard"], "the guard of committee %r" % cname)
     if len({c["name"] for c in out}) != len(out):
         raise ValueError("ERROR: the names of surrogate_committees must be unique")
     return out
+
+
+def evaluation_committees(cfg):
+    """committee_config for evaluate_surrogates, which scores a committee's mean and range against the microphysics in charge and has no
+    guarded step to score: an entry with a `guard:` is refused, not scored without it under a name that claims one."""
+    committees = committee_config(cfg)
+    for c in committees:
+        if "guard" in c:
+            raise ValueError("ERROR: evaluate_surrogates scores a committee's mean and does not apply a guard: committee %r has one "
+                             "(rollout_surrogates and inference_ponni run guarded committees)" % c["name"])
+    return committees
 
 
 def rollout_config(cfg):
@@ -318,7 +340,7 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
         if nranks > 1:
             raise ValueError("evaluate_surrogates runs on one rank (%d given): SurrogateEvaluator.combine is exact, but the reduction over "
                              "ranks is not built yet" % nranks)
-        committees = committee_config(cfg)
+        committees = evaluation_committees(cfg)
         cfg["surrogate_models"], cfg["eval_interval"] = surrogate_config(cfg)
     if experiment == "inference_ponni" and "surrogate_committees" in cfg and not ("keras_weights_h5" in cfg or "keras_weights_txt" in cfg):
         committees = committee_config(cfg)
@@ -361,7 +383,8 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
             base = cfg["_dir"]
             if "_committee" in cfg:                                                # the mean of the committee's models is what runs
                 by_name = {m["name"]: m for m in cfg["surrogate_models"]}
-                micro.init(coupler, committee=mlp.load_surrogate_bank([by_name[n] for n in cfg["_committee"]["members"]]))
+                micro.init(coupler, committee=mlp.load_surrogate_bank([by_name[n] for n in cfg["_committee"]["members"]]),
+                           guard=cfg["_committee"].get("guard"))
 
             def rel(p):
                 return p if p is None or os.path.isabs(p) else os.path.normpath(os.path.join(os.getcwd(), p))
@@ -375,7 +398,7 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
         elif experiment == "rollout_surrogates":
             micro = rollout.Microphysics_Rollout()
             micro.init(coupler, mlp.load_surrogate_bank(cfg["surrogate_models"]), cfg["persistence_member"],
-                       [m["name"] for m in cfg["surrogate_models"]], [(c["name"], c["members"]) for c in committees])
+                       [m["name"] for m in cfg["surrogate_models"]], [(c["name"], c["members"], c["guard"]) if "guard" in c else (c["name"], c["members"]) for c in committees])
         else:
             micro = microphysics.Microphysics_Kessler()
             micro.init(coupler)                                                # supercell_example/driver.cpp:58
@@ -445,6 +468,7 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                 if eval_step[0] % cfg["eval_interval"] == 0:
                     before = dict(scorer.diverged_at)
                     scorer.accumulate(coupler, eval_step[0], etime + dt)
+                    micro.guard_record(eval_step[0], dt)                       # (the only host read of the guards' counts)
                     for m, d in scorer.diverged_at.items():                    # the other members do not see it: the run goes on
                         if d is not None and before[m] is None and not quiet:
                             print("rollout_surrogates: member %r is non-finite at step %d" % (m, d["step"]), flush=True)
@@ -489,6 +513,9 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                    "report": rep["times"], "diverged_at": rep["diverged_at"]}
             if committees:
                 doc["committees"] = [dict(c, member=scorer.member_names.index(c["name"])) for c in committees]
+                for c, g in zip(doc["committees"], micro.guard_reports()):
+                    if g is not None:
+                        c["guard"] = g
             if harvester is not None:
                 doc["harvest"] = dict(harvest, files=dict(harvester.files), samples=dict(harvester.samples), skipped=dict(harvester.skipped),
                                       calls=harvester.calls)

@@ -12,7 +12,7 @@ from . import capi
 from ._ffi import _ptr, _stream_ptr, grown_workspace
 from .capi import check
 from .coupler import endrun
-from .mlp import load_surrogate_weights, mlp_forward, mlp_stencil_forward
+from .mlp import OUT4, load_surrogate_weights, mlp_forward, mlp_stencil_forward
 from .surrogate_eval import SurrogateBank
 
 
@@ -80,12 +80,20 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
     want_range = False    # with a committee: time_step also fills last_range, the four fields of the members' spread
     last_range = None
 
-    def init(self, coupler, weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None, committee=None):
+    def init(self, coupler, weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None, committee=None, guard=None):
         """committee: a list of 1 .. 16 (W1, b1, W2, b2, scl_in, scl_out) tuples of one width (load_surrogate_weights' form).  The network's
-        result is then the committee's mean (SurrogateBank.committee_apply), and the weight file arguments are not read."""
+        result is then the committee's mean (SurrogateBank.committee_apply), and the weight file arguments are not read.  guard
+        (surrogate_eval.guard_config's mapping; with a committee only): the result is the GUARDED committee's step of the state before the
+        call -- the mean, and on the columns where the models' range exceeds a threshold what Kessler leaves on those columns alone."""
         super().init(coupler)
         self._nn_out = None
         self._committee = None
+        self._guard_cfg = self._guard = None
+        if guard is not None:
+            if committee is None:
+                endrun("Microphysics_Kessler_Surrogate: a guard needs a committee")
+            from .surrogate_eval import guard_config
+            self._guard_cfg = guard_config(guard, "the committee's guard")
         if committee is not None:
             committee = list(committee)
             if any(k is not None for k in (weights_txt, in_scaling_txt, out_scaling_txt, weights_h5)):
@@ -103,13 +111,25 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
         temp, rho_d = dm.get("temp"), dm.get("density_dry", readonly=True)
         rho_v, rho_c, rho_r = dm.get("water_vapor"), dm.get("cloud_liquid"), dm.get("precip_liquid")
         if getattr(self, "_committee", None) is not None:
-            if self._nn_out is None:
+            guarded = getattr(self, "_guard_cfg", None) is not None            # (the guard's scratch holds the result and the range)
+            if self._nn_out is None and not guarded:
                 self._nn_out = [torch.empty_like(temp) for _ in range(4)]
-            if self.want_range and self.last_range is None:
+            if self.want_range and self.last_range is None and not guarded:
                 self.last_range = [torch.empty_like(temp) for _ in range(4)]
             self._committee.strict = self.mlp_strict
             # the coupler's fields are (nz, ny, nx, nens): every member is one more column, so the whole array is one member of nens = 1
             flat = [t.reshape(coupler.get_nz(), -1, 1) for t in (temp, rho_d, rho_v, rho_c, rho_r)]
+            if guarded:
+                from .surrogate_eval import CommitteeGuard
+                g = self._guard_cfg
+                if self._guard is None:
+                    self._guard = CommitteeGuard(flat[0], coupler.get_nz())
+                self._committee.committee_guard_flag(coupler.get_nz(), range(self._committee.models), 0, flat, [g[f] for f in OUT4], self._guard)
+                self._guard.commit(coupler.get_nz(), [0], flat, g["max_rainsplit"], coupler.get_dz(), dt, copy=False)   # Kessler below writes the state
+                self._nn_out = [t.reshape(temp.shape) for t in self._guard.mean4]
+                if self.want_range:
+                    self.last_range = [t.reshape(temp.shape) for t in self._guard.range4]
+                return self._finish_step(coupler, dt, temp, rho_v, rho_c, rho_r)
             self._committee.committee_apply(coupler.get_nz(), range(self._committee.models), 0, flat,
                                             [t.reshape(coupler.get_nz(), -1, 1) for t in self._nn_out],
                                             [t.reshape(coupler.get_nz(), -1, 1) for t in self.last_range] if self.want_range else None)
@@ -119,6 +139,9 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
         else:
             self._nn_out = mlp_forward(temp, rho_d, rho_v, rho_c, rho_r, self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out,
                                        self._nn_out, strict=self.mlp_strict)
+        return self._finish_step(coupler, dt, temp, rho_v, rho_c, rho_r)
+
+    def _finish_step(self, coupler, dt, temp, rho_v, rho_c, rho_r):
         super().time_step(coupler, dt)
         if self.online:                                                        # :273-276
             self._diffs = self.mean_diffs(coupler)                             # (the prints of :266-269 come first)

@@ -20,5 +20,5 @@ from .ncio import dycore_output  # noqa: F401
 from .rollout import (ROLLOUT_FIELDS, ROLLOUT_IN5, ROLLOUT_STATS, ROLLOUT_WATER, Microphysics_Rollout, RolloutHarvester,  # noqa: F401
                       RolloutScorer, kessler_members_teacher, member_divergence, rollout_member_names, rollout_report)
 from .sampling import DataGenerator, StatisticsGatherer  # noqa: F401
-from .surrogate_eval import (EVAL_CLASSES, EVAL_FIELDS, CommitteeEvaluator, SurrogateBank, SurrogateEvaluator, _sums_to_float,  # noqa: F401
-                             committee_score, json_safe, range_error_correlation, surrogate_scores)
+from .surrogate_eval import (EVAL_CLASSES, EVAL_FIELDS, CommitteeEvaluator, CommitteeGuard, SurrogateBank, SurrogateEvaluator, _sums_to_float,  # noqa: F401
+                             committee_score, guard_config, json_safe, range_error_correlation, surrogate_scores)

@@ -16,14 +16,15 @@ from ._ffi import StatsAndCounts, _field_ptr_array, _ptr, _stream_ptr, grown_wor
 from .capi import check
 from .coupler import endrun
 from .microphysics import Microphysics_Kessler
-from .mlp import IN5
+from .mlp import IN5, OUT4
 from .ncio import sample_file_append, sample_file_create
 from .sampling import sample_buffers, sample_thresholds
-from .surrogate_eval import SurrogateBank, finite_or_none, json_safe, skill_cell
+from .surrogate_eval import CommitteeGuard, SurrogateBank, finite_or_none, guard_config, json_safe, skill_cell
 
 ROLLOUT_FIELDS = ("density_dry", "uvel", "vvel", "wvel", "temp", "water_vapor", "cloud_liquid", "precip_liquid")
 ROLLOUT_STATS = ("sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_x", "min_x", "max_x")
 ROLLOUT_WATER = ("water_vapor", "cloud_liquid", "precip_liquid")
+GUARD_FIELDS = OUT4               # the order of a guard's four thresholds
 ROLLOUT_IN5 = IN5                 # fields5 of members_apply and of the teacher
 
 
@@ -66,11 +67,18 @@ class Microphysics_Rollout(Microphysics_Kessler):
         """models: (W1, b1, W2, b2, scl_in, scl_out) tuples as load_surrogate_weights returns them, single-cell and stencil networks in any
         order; names: theirs (default model0, model1, ...).  committees: (name, [model names]) pairs; each is one more member after the
         models, replaced in place from its OWN state by the mean of its models (1 .. 16 of one width, SurrogateBank.committee_apply on that
-        width's bank).  The coupler must have 1 + len(models) + len(committees) (+ 1 with persistence) members."""
+        width's bank).  A third entry, (name, [model names], guard), makes the committee a GUARDED one (guard: surrogate_eval.guard_config's
+        mapping of thresholds and max_rainsplit): its member is the committee's mean where its models agree and Kessler on the columns
+        where they do not (SurrogateBank.committee_guard_apply's step).  All guarded members share one scratch (CommitteeGuard) and one
+        columns-teacher call per step, so they share one max_rainsplit; every other member keeps the bits it has without the guard.
+        The coupler must have 1 + len(models) + len(committees) (+ 1 with persistence) members."""
         models = list(models)
         names = ["model%d" % k for k in range(len(models))] if names is None else [str(n) for n in names]
         if len(names) != len(models):
             endrun("Microphysics_Rollout: %d names for %d models" % (len(names), len(models)))
+        guards = [guard_config(c[2], "the guard of committee %r" % str(c[0])) if len(c) > 2 and c[2] is not None else None for c in committees]
+        if len({g["max_rainsplit"] for g in guards if g is not None}) > 1:
+            endrun("Microphysics_Rollout: the guarded committees share one columns-teacher call per step: give them one max_rainsplit")
         committees = [(str(c[0]), [str(n) for n in c[1]]) for c in committees]
         self.member_names = rollout_member_names(names, persistence, [c[0] for c in committees])
         self.persistence = bool(persistence)
@@ -100,6 +108,9 @@ class Microphysics_Rollout(Microphysics_Kessler):
             w = int(np.shape(models[names.index(cmodels[0])][0])[0])
             in_bank = [k for k, m in enumerate(models) if np.shape(m[0])[0] == w]
             self.committees.append((self.banks[widths.index(w)][0], [in_bank.index(names.index(n)) for n in cmodels], 1 + len(models) + ci))
+        self.guards = guards                                                   # per committee: the checked guard or None
+        self._guard = None                                                     # the CommitteeGuard all guarded members share
+        self._guard_steps = [[] for _ in committees]
         self._m0 = None
 
     def time_step(self, coupler, dt):
@@ -128,9 +139,45 @@ class Microphysics_Rollout(Microphysics_Kessler):
         for bank, members in self.banks:
             bank.strict = self.mlp_strict
             bank.members_apply(nz, members, [temp, rho_d, rho_v, rho_c, rho_r])
-        for bank, sel, member in getattr(self, "committees", ()):
+        guards = getattr(self, "guards", None) or [None] * len(getattr(self, "committees", ()))
+        guarded = [ci for ci, g in enumerate(guards) if g is not None]
+        in5 = [temp, rho_d, rho_v, rho_c, rho_r]
+        if guarded and self._guard is None:
+            self._guard = CommitteeGuard(temp, nz, len(guarded))
+        for ci, (bank, sel, member) in enumerate(getattr(self, "committees", ())):
             bank.strict = self.mlp_strict
-            bank.committee_apply(nz, sel, member, [temp, rho_d, rho_v, rho_c, rho_r], [temp, rho_v, rho_c, rho_r])
+            if guards[ci] is None:
+                bank.committee_apply(nz, sel, member, in5, [temp, rho_v, rho_c, rho_r])
+            else:                                                              # mean, range and flags of this member; the state is not written yet
+                bank.committee_guard_flag(nz, sel, member, in5, [guards[ci][f] for f in GUARD_FIELDS], self._guard, guarded.index(ci))
+        if guarded:                                                            # Kessler on every flagged column, then the guarded members' commit
+            self._guard.commit(nz, [self.committees[ci][2] for ci in guarded], in5, guards[guarded[0]]["max_rainsplit"], coupler.get_dz(), dt)
+
+    def guard_record(self, step, dt):
+        """At a scoring step, after time_step: fetches every guarded member's flagged columns and rain sub-cycle count of that step (the only
+        host read of them; no other step synchronises for the guards)."""
+        guarded = [ci for ci, g in enumerate(getattr(self, "guards", ())) if g is not None]
+        if not guarded or self._guard is None:
+            return
+        counts, rs = self._guard.read(dt, [self.committees[ci][2] for ci in guarded])
+        for slot, ci in enumerate(guarded):
+            self._guard_steps[ci].append({"step": int(step), "flagged": counts[slot][0], "rainsplit": rs[slot], "flagged_total": counts[slot][1]})
+
+    def guard_reports(self):
+        """Per committee, in the list's order: None, or the guarded member's `guard` block of surrogate_rollout.json -- thresholds (inf as the
+        string "inf"), max_rainsplit, columns, flagged_total (the device accumulator at the last scoring step), and steps: {step, flagged,
+        rainsplit} per scoring step (rainsplit 0: the Kessler part was skipped)."""
+        out = []
+        for ci, g in enumerate(getattr(self, "guards", ())):
+            if g is None:
+                out.append(None)
+                continue
+            steps = self._guard_steps[ci]
+            out.append({"thresholds": {f: json_safe(g[f]) for f in GUARD_FIELDS}, "max_rainsplit": g["max_rainsplit"],
+                        "columns": self._guard.ncol if self._guard is not None else None,
+                        "flagged_total": steps[-1]["flagged_total"] if steps else 0,
+                        "steps": [{k: s[k] for k in ("step", "flagged", "rainsplit")} for s in steps]})
+        return out
 
 
 def kessler_members_teacher(coupler, members, dt, max_rainsplit=64, outs=None, return_rainsplit=False):

@@ -135,6 +135,123 @@ class SurrogateBank:
                                                          _field_ptr_array(range4) if range4 is not None else None, _stream_ptr(self.device))
         check(rc)
 
+    def committee_guard_flag(self, nz, sel, member, in5, thr4, guard, slot=0):
+        """Steps 1 and 2 of a guarded committee's step for ensemble member `member`: committee_apply of the models sel out
+        of place into guard.mean4 / guard.range4, then mw_committee_guard_flags with the thresholds thr4 (temp, water_vapor, cloud_liquid,
+        precip_liquid; each >= 0, inf: never by size) into guard.flags and row `slot` of guard.counts.  The state is only read."""
+        if len(in5) != 5 or len(thr4) != 4:
+            endrun("SurrogateBank.committee_guard_flag: five input fields and four thresholds expected")
+        ncol, nens = self._member_layout("SurrogateBank.committee_guard_flag: ", nz, list(in5))
+        guard.check_layout("SurrogateBank.committee_guard_flag: ", nz, in5[0], slot)
+        self.committee_apply(nz, sel, member, in5, guard.mean4, guard.range4)
+        thr = (C.c_double * 4)(*[float(t) for t in thr4])
+        with torch.cuda.device(self.device):
+            rc = capi.lib().mw_committee_guard_flags(int(nz), ncol, nens, int(member), _field_ptr_array(guard.mean4), _field_ptr_array(guard.range4),
+                                                     thr, C.c_void_p(guard.flags.data_ptr()), C.c_void_p(guard.counts[slot].data_ptr()),
+                                                     _stream_ptr(self.device))
+        check(rc)
+        guard.flagged_members.add(int(member))
+
+    def committee_guard_apply(self, nz, sel, member, in5, thr4, max_rainsplit, dz, dt, scratch):
+        """One step of a guarded committee on ensemble member `member` of the member-fastest fields in5 = (temp, density_dry, water_vapor,
+        cloud_liquid, precip_liquid), each (nz, ..., nens), in place: the committee's mean (committee_apply of the models sel) where its
+        models agree, Kessler where they do not.  In order: committee_apply out of place into the scratch's mean4 and range4; column flags
+        (some level has !(range <= thr4[f]) or a non-finite mean); mw_kessler_columns_teacher on the flagged columns of the state with
+        out4 = mean4 -- the bits Kessler leaves on those columns alone, rain sub-cycles from them alone, at most max_rainsplit or the
+        member's Kessler part is skipped; mw_members_copy of mean4 into the four fields.  density_dry and every other member are never
+        written.  scratch: a CommitteeGuard for fields of this shape -- eight fields of the state's shape (64 bytes per element of ALL
+        members, allocated once), one flag byte per column and member, the columns teacher's workspace and two int64 counts per slot.
+        No host synchronisation; scratch.read(dt) fetches the counts.  A scratch used for another member before has that member's flag bytes
+        cleared first: the columns teacher runs on every flagged column of the state, whichever member it belongs to."""
+        if scratch.flagged_members - {int(member)}:
+            scratch.flags.zero_()
+            scratch.flagged_members.clear()
+        self.committee_guard_flag(nz, sel, member, in5, thr4, scratch)
+        scratch.commit(nz, [member], in5, max_rainsplit, dz, dt)
+
+
+GUARD_KEYS = OUT4 + ("max_rainsplit",)
+
+
+def guard_config(guard, who="guard"):
+    """A committee's checked guard: a mapping with any of temp, water_vapor, cloud_liquid, precip_liquid -- the range above which a column
+    goes to Kessler, a number >= 0 in the field's units, a missing field never flags by size -- and max_rainsplit (1 .. 1024, default
+    64).  Unknown keys, a negative, NaN or non-numeric threshold and a guard without any threshold are refused (ValueError).  Returns
+    {"temp", "water_vapor", "cloud_liquid", "precip_liquid": floats (inf where missing), "max_rainsplit": int} -- pure Python."""
+    if not isinstance(guard, dict):
+        raise ValueError("ERROR: %s must be a mapping" % who)
+    unknown = sorted(set(guard) - set(GUARD_KEYS), key=str)
+    if unknown:
+        raise ValueError("ERROR: unknown key(s) %s in %s (known: %s)" % (", ".join(map(repr, unknown)), who, ", ".join(GUARD_KEYS)))
+    if not any(f in guard for f in OUT4):
+        raise ValueError("ERROR: %s holds no threshold (one of %s)" % (who, ", ".join(OUT4)))
+    out = {}
+    for f in OUT4:
+        t = guard.get(f, float("inf"))
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not t >= 0:
+            raise ValueError("ERROR: %s.%s must be a number >= 0, got %r" % (who, f, t))
+        out[f] = float(t)
+    cap = guard.get("max_rainsplit", 64)
+    if isinstance(cap, bool) or not isinstance(cap, int) or not 1 <= cap <= 1024:
+        raise ValueError("ERROR: %s.max_rainsplit must be an integer in [1, 1024], got %r" % (who, cap))
+    out["max_rainsplit"] = cap
+    return out
+
+
+class CommitteeGuard:
+    """What the guarded committees of one state share (no reference counterpart): mean4 and range4, eight member-fastest scratch fields of
+    the state's shape (nz, ..., nens) -- 64 bytes per element of all members, allocated here once; flags, one byte per column and member
+    (zero for members that are not guarded: mw_committee_guard_flags writes its own member's bytes only); the columns teacher's workspace;
+    counts, int64 (slots, 2): per guarded member this step's flagged columns and their running total."""
+
+    def __init__(self, like, nz, slots=1):
+        if like.dim() < 2 or like.dtype != torch.float64 or not like.is_contiguous() or int(nz) < 2 or like.numel() % (int(nz) * like.shape[-1]) != 0:
+            endrun("CommitteeGuard: a contiguous float64 field (nz, ..., nens) with nz >= 2 expected")
+        self.nz, self.nens, self.shape, self.device = int(nz), int(like.shape[-1]), tuple(like.shape), like.device
+        self.ncol = like.numel() // (self.nz * self.nens)
+        nbytes = capi.lib().mw_kessler_columns_teacher_workspace_bytes(self.nz, self.ncol, self.nens)
+        if nbytes <= 0:
+            endrun("CommitteeGuard: nz = %d, %d columns and %d members are out of range (nz >= 2, at most 64 members)" % (self.nz, self.ncol, self.nens))
+        self.mean4 = [torch.empty_like(like) for _ in range(4)]
+        self.range4 = [torch.empty_like(like) for _ in range(4)]
+        self.flags = torch.zeros(self.ncol * self.nens, dtype=torch.uint8, device=like.device)
+        self.counts = torch.zeros((int(slots), 2), dtype=torch.int64, device=like.device)
+        self.workspace = fit_workspace(None, nbytes, like.device)
+        self.max_rainsplit = None                                         # of the last commit (read() decides the counts with it)
+        self.flagged_members = set()                                      # the members whose flag bytes may be set
+
+    def check_layout(self, who, nz, field, slot=0):
+        if int(nz) != self.nz or tuple(field.shape) != self.shape or field.device != self.device or not 0 <= int(slot) < self.counts.shape[0]:
+            endrun(who + "the CommitteeGuard was made for fields %r of nz = %d on %s with %d slot(s)" % (self.shape, self.nz, self.device, self.counts.shape[0]))
+
+    def commit(self, nz, members, in5, max_rainsplit, dz, dt, copy=True):
+        """Steps 3 to 5 for the guarded members `members`, whose mean4 and flags are in place: ONE mw_kessler_columns_teacher call on every
+        flagged column of the state in5 with out4 = mean4, then mw_members_copy of the members' mean4 into temp and the three water fields
+        (copy=False: the result stays in mean4 and the state is not written)."""
+        self.check_layout("CommitteeGuard.commit: ", nz, in5[0])
+        members = [int(m) for m in members]
+        L = capi.lib()
+        with torch.cuda.device(self.device):
+            st = _stream_ptr(self.device)
+            check(L.mw_kessler_columns_teacher(self.nz, self.ncol, self.nens, C.c_void_p(self.flags.data_ptr()), float(dz), float(dt), int(max_rainsplit),
+                                               _field_ptr_array(list(in5)), _field_ptr_array(self.mean4), None, _ptr(self.workspace), st))
+            if copy:
+                check(L.mw_members_copy(self.nz * self.ncol, self.nens, len(members), (C.c_int * max(1, len(members)))(*members), 4,
+                                        _field_ptr_array(self.mean4), _field_ptr_array([in5[0], in5[2], in5[3], in5[4]]), st))
+        self.max_rainsplit = int(max_rainsplit)
+
+    def read(self, dt, members=(0,)):
+        """After a commit, with two small device-to-host copies: per slot (flagged columns of the last step, their running total), and the
+        rain sub-cycle count of each of `members` in that step (0: its Kessler part was skipped)."""
+        counts = self.counts.cpu().numpy()
+        words = self.workspace[:self.nens].cpu().numpy().view(np.uint64)
+        dt_bits = int(np.float64(dt).view(np.uint64))
+        rs = []
+        for m in members:
+            w = min(int(words[int(m)]), dt_bits)                          # a word no column lowered stands for dt (kessler_teacher_word)
+            rs.append(int(capi.lib().mw_kessler_teacher_rainsplit(float(dt), float(np.uint64(w).view(np.float64)), int(self.max_rainsplit))))
+        return [(int(a), int(b)) for a, b in counts], rs
+
 
 def json_safe(x):
     """Nested lists of floats with inf / NaN as the strings "inf", "-inf", "nan" (bare tokens are no JSON); finite numbers unchanged."""
