@@ -39,6 +39,8 @@ __device__ __forceinline__ double fast_rcp(double x) {
 // waits for that store's write acknowledgement.  The marching kernels issue a level's loads at the top of the iteration and its
 // stores at the bottom; landed() names the loaded values in front of the first store, which puts the (by then free) wait
 // there, and in front of the loop for the prologue's loads, whose pending state would otherwise leak into every iteration.
+// (A loaded value that is CONSUMED where it is declared -- a compare, a mask -- gets its wait there: vmcnt(0) behind the loads the
+// level has just issued.  tools/loop_wait_audit.py lists where the waits of every loop stand.)
 // A fence for the instruction scheduler.  With its run-time switches folded (Cf<K>, K != 0) a marching loop body loses the rare
 // branches that used to cut it into basic blocks and becomes one block of ~500 instructions, which the scheduler then re-orders
 // as a whole -- it sank the loads of k_tracers_fused towards their uses and the kernel became 8 % SLOWER than the unspecialised
@@ -1070,6 +1072,16 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
   const bool vzq_on = VAP && MODE == 1 && (p.zq != nullptr) && p.zero_skip;
   unsigned vzseg = 0;
   if (VAP && MODE == 1) { const int tx_ = (q + (HS + 1) - lane) ; vzseg = zr_seg_mask(tx_ - (HS + 2), tx_ - (HS + 1) + 63 + 1, NXI, p.wrap_x != 0); }
+  // (bit i of vlean_mask = "the tracer kernel's iteration that stores cell kc0 + i is lean": lane i fetches the cell's word HERE, in front of the
+  //  loop and with the prologue's loads, and the loop tests a scalar bit -- like zq_mask in k_tracers_fused.  Fetched inside the loop the word's
+  //  wait stood where the predicate is formed, at the top of the iteration: vmcnt(0) behind the level's loads, one exposed round trip per level.
+  //  No maps: nothing is lean.  All 64 lanes are here.)
+  unsigned long long vlean_mask = 0ull;
+  auto vlean_fetch = [&](int kc0) __attribute__((always_inline)) {
+    const unsigned wz = p.zq[(long long)min(kc0 + lane + 2, p.nz - 1) * p.zq_ld + j + MW_ZR_HALO];
+    vlean_mask = __ballot((wz & vzseg) == 0u);
+  };
+  if (VAP && MODE == 1 && vzq_on) vlean_fetch(g.ka);
   double wq[ORD], nxtq = 0, ctq = 0;
   int qr = (g.kstart - HS + ORD) % ORD;
 #define MW_QSLOT(s_) (lds_q[(5 + ((qr + (s_)) >= ORD ? qr + (s_) - ORD : qr + (s_))) * 256])
@@ -1090,6 +1102,12 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
     const bool xwork = (k >= g.ka) && (k < g.kb);              // cells of this chunk (ghost levels only do z)
     const bool zface = (k >= g.ka);                            // face k belongs to this chunk (k == kb: closing face)
     const bool fin = (k > g.ka);                               // cell k-1 gets finalised in this iteration
+    bool vlean = false;                                        // VAP, MODE 1: the tracer kernel's storing iteration of cell k-1 is lean
+    if (VAP && MODE == 1 && vzq_on) {
+      const int ic = max(k - 1, g.ka) - g.ka;
+      if (ic > 0 && (ic & 63) == 0) vlean_fetch(g.ka + ic);    // (chunks of more than 64 levels: the next 64 words, in front of the level's loads)
+      vlean = (vlean_mask >> (ic & 63)) & 1ull;
+    }
     // ---------------- issue this iteration's global loads
     {
       const int kn = min(k + HS + 1, p.nz + p.HZ - 1);
@@ -1112,8 +1130,6 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
       for (int l = 0; l < 5; l++) tyv[l] = tendY[(long long)l * p.nC + cell0 + (long long)kxc * planeC];
     }
     if (Cf<K>::immersed(p)) immv = p.imm[cpl(p, cell0 + (long long)kfc * planeC)];
-    bool vlean = false;                                        // VAP, MODE 1: the tracer kernel's storing iteration of cell k-1 is lean
-    if (VAP && MODE == 1 && vzq_on) vlean = (p.zq[(long long)min(kfc + 2, p.nz - 1) * p.zq_ld + j + MW_ZR_HALO] & vzseg) == 0u;
     double qnv = 0, fysq = 0, fynq = 0;                        // VAP: q^n of the vapour (level k-1), its y fluxes south / north of cell k
     if (VAP) {
       if (STAGE != 1) qnv = Sn[(long long)5 * p.sV + slab0 + (long long)(kfc + p.HZ) * p.sK];
