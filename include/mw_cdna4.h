@@ -578,6 +578,40 @@ long long mw_member_divergence_workspace_bytes(long long n, int nens, int nf);
 int  mw_member_divergence(long long n, int nens, int nf, const double *const *fields, void *workspace, double *out, long long *nonfinite,
                           void *stream);
 
+/* ---- surface rain of every member from its column water budget -------------------------- */
+/* The tracers are densities and in Kessler water leaves a column only through the ground, so what a microphysics step removes from a
+ * column's water is that member's surface precipitation -- also for a member that a network steps, which emits no precl.
+ * mw_member_column_water: w (DEVICE fp64 (ncol, nens)) of element t = col * nens + e is
+ *   w[t] = dz * sum_{k = 0 .. nz-1} ((rho_v + rho_c) + rho_r)[(k * ncol + col) * nens + e]              kg / m^2
+ * with exactly that association: k ascending in ONE fp64 accumulator that starts from +0.0, no contraction, dz applied once at the end,
+ * no atomics -- a host loop over k reproduces the bits.  water3: HOST array of 3 DEVICE pointers (water_vapor, cloud_liquid,
+ * precip_liquid), member-fastest (nz, ncol, nens), never written.  One thread per t walks the levels at stride ncol * nens, so the loads
+ * are coalesced whatever nens is.  A NaN or inf of a cell reaches its own w[t] alone.
+ * mw_member_surface_rain: the same sweep on the state AFTER the step, fused with the finish.  For a member e in `members`,
+ *   precl[t] = (w_before[t] - W_after[t]) / (1000.0 * dt)                                                m of water / s
+ * (1000: rhoqr of microphysics_kessler.h:247; the unit of Kessler's own precl).  The sign is kept: a step that creates water shows a
+ * negative rate.  Then, for a member e in `accum` (any set; usually all members), rain_total[t] = rain_total[t] + dt * precl[t] with
+ * whatever precl[t] holds NOW -- so a member in accum alone accumulates the precl another module wrote (Kessler's own, for the Kessler
+ * member).  Elements of members in neither list are neither read nor written.  members / accum: HOST arrays of nm / na (0 .. nens)
+ * distinct indices in [0, nens), nens <= 64; w_before, precl, rain_total: DEVICE fp64 (ncol, nens); w_before may be NULL when nm = 0,
+ * rain_total when na = 0.  With a top level that holds rain the identity does not hold for Kessler itself (its top-cell formula, :294,
+ * does not telescope).  Refused, with nothing launched: null pointers, nz or ncol < 1, nens outside [1, 64], members out of range or
+ * repeated, dz or dt not positive and finite.  Both asynchronous on `stream`. */
+int  mw_member_column_water(int nz, long long ncol, int nens, const double *const *water3, double dz, double *w, void *stream);
+int  mw_member_surface_rain(int nz, long long ncol, int nens, int nm, const int *members, int na, const int *accum,
+                            const double *const *water3, double dz, double dt, const double *w_before, double *precl, double *rain_total,
+                            void *stream);
+/* The contingency table of nf (1 .. 4) member-fastest DEVICE fp64 fields (ncol, nens) against member 0, the observation.  Field f has
+ * nt[f] (1 .. 8) thresholds, finite and strictly ascending: thresholds is a HOST (nf, 8) fp64 array whose row f holds them first (the
+ * rest is not read); nt: HOST.  An event is x >= thr.  counts: DEVICE int64 (nf, 8, nens, 5) = hits (member and member 0 both have the
+ * event), misses (member 0 alone), false alarms (the member alone), correct negatives, non-finite -- a column where the member's or
+ * member 0's value is NaN or inf (x - x != 0) counts as non-finite only, so the five sum to ncol for every field, threshold j < nt[f]
+ * and member; rows j >= nt[f] are zeros.  Integer sums: any order gives the same numbers.  workspace: DEVICE,
+ * mw_member_rain_table_workspace_bytes(ncol, nens, nf) bytes (0: arguments out of range; nens <= 64).  Asynchronous on `stream`. */
+long long mw_member_rain_table_workspace_bytes(long long ncol, int nens, int nf);
+int  mw_member_rain_table(long long ncol, int nens, int nf, const double *const *fields, const int *nt, const double *thresholds,
+                          void *workspace, long long *counts, void *stream);
+
 /* ---- harvesting Kessler labels on the rollout members' own states ---------------------------------------- */
 /* The teacher: what Kessler would do to the state of the listed members, each member ALONE, out of place.  A member-fastest field
  * (nz, ncol, nens) is a (nz, ncol * nens) array of columns col * nens + e, so the production kernels' column walk is as coalesced on all

@@ -13,6 +13,7 @@ MW_MAX_TRACERS = 16
 MW_SURROGATE_MAX_MODELS = 256
 MW_ROLLOUT_MAX_MEMBERS = 30
 MW_COMMITTEE_MAX_MODELS = 16
+MW_RAIN_MAX_FIELDS, MW_RAIN_MAX_THRESHOLDS = 4, 8          # mw_member_rain_table
 DATA_THERMAL, DATA_SUPERCELL, DATA_CITY, DATA_BUILDING = 0, 1, 2, 3
 BC_PERIODIC, BC_OPEN, BC_WALL = 0, 1, 2
 INIT_IDS = {"thermal": DATA_THERMAL, "supercell": DATA_SUPERCELL, "city": DATA_CITY, "building": DATA_BUILDING}
@@ -168,7 +169,13 @@ SYMBOLS = {
     "mw_committee_score": (C.c_int, [C.c_int, C.c_longlong] + [C.POINTER(C.c_void_p)] * 4 + [C.c_void_p] * 4),
     "mw_member_divergence_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     "mw_member_divergence": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mw_kessler_members_teacher_workspace_bytes": (C.c_longlong, [C.c_int, C.c_longlong, C.c_int]),
+    "mw_member_column_water": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_void_p, C.c_void_p]),
+    "mw_member_surface_rain": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mw_member_rain_table_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
+    "mw_member_rain_table": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mw_kessler_members_teacher_workspace_bytes":(C.c_longlong, [C.c_int, C.c_longlong, C.c_int]),
     "mw_kessler_members_teacher": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double, C.c_int,
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
     "mw_kessler_teacher_rainsplit": (C.c_int, [C.c_double, C.c_double, C.c_int]),

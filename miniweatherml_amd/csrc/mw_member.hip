@@ -5,7 +5,8 @@
 // members never meet.  mw_member_sample_mask / mw_member_gather_samples are DataGenerator's sampler (k_sample_mask / k_gather_samples of
 // mw_output.hip, which see member 0 only) on the member layout, between a member's own state and its Kessler teacher values.
 // mw_committee_guard_flags / mw_members_copy are the guarded committee's two passes that are not Kessler's: which columns
-// of a member go to Kessler, and the commit of the scratch result into the state.
+// of a member go to Kessler, and the commit of the scratch result into the state.  mw_member_column_water / mw_member_surface_rain /
+// mw_member_rain_table are every member's surface rain from its column water budget and its contingency table.
 // =====================================================================================================
 #include "../../include/mw_cdna4.h"
 #include "mw_common.h"
@@ -201,6 +202,130 @@ __global__ __launch_bounds__(256) void k_members_copy(long long total, int nens,
     if ((listed >> (int)(t % nens)) & 1ull) b[t] = a[t];
 }
 
+// ---- mw_member_column_water / mw_member_surface_rain ------------------------------------------------------------------------------------
+struct WaterFields { const double *v, *c, *r; };
+constexpr int WATER_AHEAD = 4;             // levels whose loads are issued ahead of their adds
+
+// dz * sum over k of ((v + c) + r)[k * plane + t]: one fp64 accumulator from +0.0, k ascending, no contraction.  Thread t is one (column,
+// member) of the plane, so a wavefront's loads of a level are 64 consecutive doubles per field whatever nens is.  The twelve loads of
+// WATER_AHEAD levels are issued before the first add; the adds keep the order of k.
+__device__ __forceinline__ double column_water(int nz, long long plane, long long t, const WaterFields &F, double dz) {
+#pragma clang fp contract(off)
+  double acc = 0.0;
+  int k = 0;
+  for (; k + WATER_AHEAD <= nz; k += WATER_AHEAD) {
+    double v[WATER_AHEAD], c[WATER_AHEAD], r[WATER_AHEAD];
+#pragma unroll
+    for (int j = 0; j < WATER_AHEAD; j++) {
+      const long long i = (long long)(k + j) * plane + t;
+      v[j] = F.v[i]; c[j] = F.c[i]; r[j] = F.r[i];
+    }
+#pragma unroll
+    for (int j = 0; j < WATER_AHEAD; j++) acc = acc + ((v[j] + c[j]) + r[j]);
+  }
+  for (; k < nz; k++) {
+    const long long i = (long long)k * plane + t;
+    acc = acc + ((F.v[i] + F.c[i]) + F.r[i]);
+  }
+  return dz * acc;
+}
+
+__global__ __launch_bounds__(256) void k_member_column_water(int nz, long long plane, WaterFields F, double dz, double *__restrict__ w) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t < plane) w[t] = column_water(nz, plane, t, F, dz);
+}
+
+// The same sweep on the state after the step, and the finish: a listed member's precl is what the step took out of its column, signed;
+// a member of `accum` adds dt * (whatever precl holds now) to its total.  Elements of members in neither set are not read or written.
+__global__ __launch_bounds__(256) void k_member_surface_rain(int nz, long long plane, int nens, unsigned long long listed, unsigned long long accum,
+                                                             WaterFields F, double dz, double dt, double per_rate,
+                                                             const double *__restrict__ w_before, double *__restrict__ precl,
+                                                             double *__restrict__ rain_total) {
+#pragma clang fp contract(off)
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= plane) return;
+  const int e = (int)(t % nens);
+  const bool mine = (listed >> e) & 1ull, sums = (accum >> e) & 1ull;
+  if (!mine && !sums) return;
+  double p;
+  if (mine) {
+    p = (w_before[t] - column_water(nz, plane, t, F, dz)) / per_rate;       // per_rate = 1000.0 * dt: kg / m^2 to m of water per second
+    precl[t] = p;
+  } else {
+    p = precl[t];
+  }
+  if (sums) rain_total[t] = rain_total[t] + dt * p;
+}
+
+// ---- mw_member_rain_table -----------------------------------------------------------------------------------------------------------
+constexpr int RAIN_MAX_FIELDS = 4, RAIN_MAX_THR = 8;
+constexpr int RAIN_OUT = 5;                // hits, misses, false alarms, correct negatives, non-finite
+constexpr int RAIN_ROW = 3 * RAIN_MAX_THR + 2;   // per lane: hits, misses, false alarms per threshold, then non-finite and finite columns
+constexpr int RAIN_MAX_BLOCKS = 512;
+
+struct RainFields { const double *f[RAIN_MAX_FIELDS]; int nt[RAIN_MAX_FIELDS]; double thr[RAIN_MAX_FIELDS][RAIN_MAX_THR]; };
+
+// k_member_divergence's layout: a workgroup reads nens * C consecutive doubles per iteration, lane l always member l % nens.  The counts
+// are integers: per lane, then the C lanes of a member, then k_member_rain_table_final over the blocks -- any order gives the same numbers.
+__global__ __launch_bounds__(256) void k_member_rain_table(long long n, int nens, RainFields R, long long *__restrict__ partial) {
+  __shared__ int red[256][RAIN_ROW + 1];                                    // (+ 1: rows on different banks)
+  const int fi = blockIdx.y, nt = R.nt[fi];
+  const double *x = R.f[fi];
+  const int C = 256 / nens, l = threadIdx.x, e = l % nens, cl = l / nens;
+  int cnt[RAIN_ROW];
+#pragma unroll
+  for (int s = 0; s < RAIN_ROW; s++) cnt[s] = 0;
+  for (long long c0 = (long long)blockIdx.x * C; c0 < n; c0 += (long long)gridDim.x * C) {
+    const long long c = c0 + cl;
+    if (cl < C && c < n) {
+      const double v = x[c * nens + e], v0 = x[c * nens];
+      const bool fin = (v - v == 0.0) && (v0 - v0 == 0.0);                  // a NaN or inf of the member or of member 0 takes the column out
+      cnt[3 * RAIN_MAX_THR] += fin ? 0 : 1;
+      cnt[3 * RAIN_MAX_THR + 1] += fin ? 1 : 0;
+#pragma unroll
+      for (int j = 0; j < RAIN_MAX_THR; j++) {
+        const bool on = fin && j < nt, fc = v >= R.thr[fi][j], ob = v0 >= R.thr[fi][j];
+        cnt[3 * j] += (on && fc && ob) ? 1 : 0;
+        cnt[3 * j + 1] += (on && !fc && ob) ? 1 : 0;
+        cnt[3 * j + 2] += (on && fc && !ob) ? 1 : 0;
+      }
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < RAIN_ROW; s++) red[l][s] = cnt[s];
+  __syncthreads();
+  for (int t = l; t < nens * RAIN_ROW; t += 256) {
+    const int m = t / RAIN_ROW, s = t % RAIN_ROW;
+    long long q = 0;
+    for (int c = 0; c < C; c++) q += red[c * nens + m][s];
+    partial[(((long long)blockIdx.x * gridDim.y + fi) * nens + m) * RAIN_ROW + s] = q;
+  }
+}
+
+// thread = one (field, threshold, member): the blocks' rows summed, the correct negatives as what is left of the finite columns
+__global__ __launch_bounds__(256) void k_member_rain_table_final(int nblocks, int nf, int nens, RainFields R, const long long *__restrict__ partial,
+                                                                 long long *__restrict__ counts) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= nf * RAIN_MAX_THR * nens) return;
+  const int m = t % nens, j = (t / nens) % RAIN_MAX_THR, f = t / (nens * RAIN_MAX_THR);
+  long long q[5] = {0, 0, 0, 0, 0};                                         // hits, misses, false alarms, non-finite, finite
+  if (j < R.nt[f]) {
+    const long long stride = (long long)nf * nens * RAIN_ROW;
+    const long long *p = partial + ((long long)f * nens + m) * RAIN_ROW;
+    for (int b = 0; b < nblocks; b++) {
+      const long long *row = p + b * stride;
+      q[0] += row[3 * j]; q[1] += row[3 * j + 1]; q[2] += row[3 * j + 2]; q[3] += row[3 * RAIN_MAX_THR]; q[4] += row[3 * RAIN_MAX_THR + 1];
+    }
+  }
+  long long *out = counts + (long long)t * RAIN_OUT;
+  out[0] = q[0]; out[1] = q[1]; out[2] = q[2]; out[3] = q[4] - q[0] - q[1] - q[2]; out[4] = q[3];
+}
+
+static long long rain_table_blocks(long long n, int nens) {
+  const long long C = 256 / nens;
+  return std::max<long long>(1, std::min<long long>((n + C - 1) / C, RAIN_MAX_BLOCKS));
+}
+
 } // namespace mw
 
 using namespace mw;
@@ -351,6 +476,103 @@ extern "C" int mw_members_copy(long long n, int nens, int nm, const int *members
   const long long total = n * nens;
   const long long blocks = std::max<long long>(1, std::min<long long>((total + 255) / 256, 256 * 16));
   hipLaunchKernelGGL(k_members_copy, dim3((unsigned)blocks, (unsigned)nf), dim3(256), 0, (hipStream_t)stream, total, nens, listed, A, B);
+  MW_LAUNCH_CHECK();
+  return 0;
+}
+
+static bool positive_finite(double x) { return x > 0.0 && x - x == 0.0; }
+
+// the bit set of a member list: distinct indices in [0, nens), nens <= 64
+static int member_bits(const char *who, const char *what, int nens, int n, const int *list, unsigned long long *bits) {
+  if (n < 0 || n > nens) MW_FAIL(std::string(who) + ": " + what + " holds " + std::to_string(n) + " members, not 0 to nens");
+  if (n > 0 && !list) MW_FAIL(std::string(who) + ": null pointer");
+  *bits = 0;
+  for (int j = 0; j < n; j++) {
+    const int e = list[j];
+    if (e < 0 || e >= nens) MW_FAIL(std::string(who) + ": member " + std::to_string(e) + " is outside [0, " + std::to_string(nens) + ")");
+    if ((*bits >> e) & 1ull) MW_FAIL(std::string(who) + ": member " + std::to_string(e) + " is listed twice in " + what);
+    *bits |= 1ull << e;
+  }
+  return 0;
+}
+
+static int water_fields(const char *who, int nz, long long ncol, int nens, const double *const *water3, double dz, WaterFields *F) {
+  if (!water3) MW_FAIL(std::string(who) + ": null pointer");
+  if (nz < 1 || ncol < 1) MW_FAIL(std::string(who) + ": nz and ncol must be >= 1");
+  if (nens < 1 || nens > 64) MW_FAIL(std::string(who) + ": nens must be in [1, 64]");
+  if ((double)nz * (double)ncol * (double)nens > 9.0e18) MW_FAIL(std::string(who) + ": the fields are too large");
+  if (!positive_finite(dz)) MW_FAIL(std::string(who) + ": dz must be positive and finite");
+  for (int f = 0; f < 3; f++) if (!water3[f]) MW_FAIL(std::string(who) + ": null field");
+  F->v = water3[0]; F->c = water3[1]; F->r = water3[2];
+  return 0;
+}
+
+extern "C" int mw_member_column_water(int nz, long long ncol, int nens, const double *const *water3, double dz, double *w, void *stream) {
+  WaterFields F;
+  if (water_fields("member_column_water", nz, ncol, nens, water3, dz, &F)) return 1;
+  if (!w) MW_FAIL("member_column_water: null pointer");
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  const long long plane = ncol * nens;
+  hipLaunchKernelGGL(k_member_column_water, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nz, plane, F, dz, w);
+  MW_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mw_member_surface_rain(int nz, long long ncol, int nens, int nm, const int *members, int na, const int *accum,
+                                      const double *const *water3, double dz, double dt, const double *w_before, double *precl,
+                                      double *rain_total, void *stream) {
+  WaterFields F;
+  if (water_fields("member_surface_rain", nz, ncol, nens, water3, dz, &F)) return 1;
+  if (!positive_finite(dt)) MW_FAIL("member_surface_rain: dt must be positive and finite");
+  unsigned long long listed = 0, sums = 0;
+  if (member_bits("member_surface_rain", "members", nens, nm, members, &listed)) return 1;
+  if (member_bits("member_surface_rain", "accum", nens, na, accum, &sums)) return 1;
+  if (!precl || (nm > 0 && !w_before) || (na > 0 && !rain_total)) MW_FAIL("member_surface_rain: null pointer");
+  if (nm == 0 && na == 0) return 0;
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  const long long plane = ncol * nens;
+  hipLaunchKernelGGL(k_member_surface_rain, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nz, plane, nens, listed, sums, F,
+                     dz, dt, 1000.0 * dt, w_before, precl, rain_total);
+  MW_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" long long mw_member_rain_table_workspace_bytes(long long ncol, int nens, int nf) {
+  if (ncol < 1 || nens < 1 || nens > 64 || nf < 1 || nf > RAIN_MAX_FIELDS) return 0;
+  return rain_table_blocks(ncol, nens) * nf * nens * RAIN_ROW * 8;
+}
+
+extern "C" int mw_member_rain_table(long long ncol, int nens, int nf, const double *const *fields, const int *nt, const double *thresholds,
+                                    void *workspace, long long *counts, void *stream) {
+  if (!fields || !nt || !thresholds || !workspace || !counts) MW_FAIL("member_rain_table: null pointer");
+  if (ncol < 1) MW_FAIL("member_rain_table: ncol must be >= 1");
+  if (nens < 1 || nens > 64) MW_FAIL("member_rain_table: nens must be in [1, 64]");
+  if (nf < 1 || nf > RAIN_MAX_FIELDS) MW_FAIL("member_rain_table: nf must be in [1, " + std::to_string(RAIN_MAX_FIELDS) + "]");
+  if ((double)ncol * (double)nens > 9.0e18) MW_FAIL("member_rain_table: the fields are too large");
+  RainFields R;
+  for (int f = 0; f < RAIN_MAX_FIELDS; f++) {
+    R.f[f] = nullptr; R.nt[f] = 0;
+    for (int j = 0; j < RAIN_MAX_THR; j++) R.thr[f][j] = 0.0;
+  }
+  for (int f = 0; f < nf; f++) {
+    if (!fields[f]) MW_FAIL("member_rain_table: null field");
+    if (nt[f] < 1 || nt[f] > RAIN_MAX_THR) MW_FAIL("member_rain_table: a field has 1 to " + std::to_string(RAIN_MAX_THR) + " thresholds, field " +
+                                                   std::to_string(f) + " has " + std::to_string(nt[f]));
+    R.f[f] = fields[f]; R.nt[f] = nt[f];
+    for (int j = 0; j < nt[f]; j++) {
+      const double thr = thresholds[f * RAIN_MAX_THR + j];
+      if (thr - thr != 0.0) MW_FAIL("member_rain_table: threshold " + std::to_string(j) + " of field " + std::to_string(f) + " is not finite");
+      if (j > 0 && !(thr > R.thr[f][j - 1])) MW_FAIL("member_rain_table: the thresholds of field " + std::to_string(f) + " are not strictly ascending");
+      R.thr[f][j] = thr;
+    }
+  }
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  hipStream_t st = (hipStream_t)stream;
+  const long long blocks = rain_table_blocks(ncol, nens);
+  hipLaunchKernelGGL(k_member_rain_table, dim3((unsigned)blocks, (unsigned)nf), dim3(256), 0, st, ncol, nens, R, (long long *)workspace);
+  MW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_member_rain_table_final, dim3((unsigned)((nf * RAIN_MAX_THR * nens + 255) / 256)), dim3(256), 0, st, (int)blocks, nf, nens, R,
+                     (const long long *)workspace, counts);
   MW_LAUNCH_CHECK();
   return 0;
 }

@@ -48,6 +48,12 @@ field left out never flags by size; a non-finite mean always flags), Kessler tak
 the flagged columns alone (more than max_rainsplit, default 64: the mean stays).  surrogate_rollout.json gets a `guard` block per
 guarded committee: the thresholds, `columns`, `flagged_total`, and `flagged` / `rainsplit` at every scoring step.  inference_ponni runs
 the guarded step when its one committee has a guard; evaluate_surrogates, which scores the mean, refuses an entry with a guard.
+    surface_rain: {thresholds_mm_h: [0.1, 1, 5, 10, 25], thresholds_mm: [0.1, 1, 5, 10, 25], map: true}
+makes rollout_surrogates score rain at the ground: every member's precl becomes what its microphysics step removed from
+its column's water (the Kessler member keeps Kessler's own), and surrogate_rollout.json gets a `surface_rain` block -- the thresholds and,
+per scoring step and member, the statistics of the rate (mm/h) and of the accumulated rain (mm) against the Kessler member with a
+contingency table per threshold (rollout.RainScorer).  `map: true` writes surrogate_rollout_rain.npy, float64 (nens, ny, nx), mm, at
+the end.  `surface_rain: true` means these defaults; false or absent: off, and the document is what it is without the key.
 """
 import argparse
 import os
@@ -80,7 +86,7 @@ def load_config(path):
         if key in cfg:
             out[key] = str(cfg[key])
     out["_dir"] = os.path.dirname(os.path.abspath(path))
-    for key in ("surrogate_models", "eval_interval", "persistence_member", "harvest", "surrogate_committees"):    # read by surrogate_config / rollout_config / harvest_config / committee_config alone
+    for key in ("surrogate_models", "eval_interval", "persistence_member", "harvest", "surrogate_committees", "surface_rain"):    # read by surrogate_config / rollout_config / harvest_config / committee_config / surface_rain_config alone
         if key in cfg:
             out[key] = cfg[key]
     return out
@@ -232,6 +238,31 @@ def harvest_config(cfg):
     return out
 
 
+SURFACE_RAIN_KEYS = ("thresholds_mm_h", "thresholds_mm", "map")
+
+
+def surface_rain_config(cfg):
+    """The checked `surface_rain:` block of a loaded configuration for rollout_surrogates, or None when it is absent or false:
+    thresholds_mm_h (the events of the rain rate) and thresholds_mm (of the accumulated rain), each 1 .. 8 positive numbers, strictly
+    ascending (default 0.1, 1, 5, 10, 25), and map (default true: write surrogate_rollout_rain.npy).  `surface_rain: true` means the
+    defaults."""
+    from .rollout import RAIN_DEFAULT_THRESHOLDS, rain_thresholds
+    b = cfg.get("surface_rain", False)
+    if b is False or b is None:
+        return None
+    b = {} if b is True else b
+    if not isinstance(b, dict):
+        raise ValueError("ERROR: surface_rain must be true, false or a mapping")
+    unknown = sorted(set(b) - set(SURFACE_RAIN_KEYS))
+    if unknown:
+        raise ValueError("ERROR: unknown key(s) %s in surface_rain (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(SURFACE_RAIN_KEYS)))
+    out = {key: rain_thresholds(b.get(key, list(RAIN_DEFAULT_THRESHOLDS)), "surface_rain." + key) for key in SURFACE_RAIN_KEYS[:2]}
+    out["map"] = b.get("map", True)
+    if not isinstance(out["map"], bool):
+        raise ValueError("ERROR: surface_rain.map must be true or false")
+    return out
+
+
 def _surrogate_models(entries, yaml_dir):
     """The `surrogate_models:` list: every entry names a model and its three files (relative paths: from the working directory, as the
     other file keys, else from the YAML file's directory)."""
@@ -353,6 +384,7 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
             raise ValueError("rollout_surrogates runs on one rank (%d given): SurrogateEvaluator.combine is exact, but the reduction over "
                              "ranks is not built yet" % nranks)
         harvest = harvest_config(cfg)
+        rain_cfg = surface_rain_config(cfg)
         committees = committee_config(cfg)
         cfg["surrogate_models"], cfg["eval_interval"], cfg["persistence_member"], cfg["nens"] = rollout_config(cfg)
     coupler = _coupler(cfg, device, nranks, myrank, yaml_path)
@@ -426,6 +458,10 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                         committee_evals.append((c, surrogate_eval.CommitteeEvaluator(bank, [i - first for i in places])))
                     first += bank.models
         scorer = rollout.RolloutScorer(micro.member_names) if experiment == "rollout_surrogates" else None
+        rain = None
+        if experiment == "rollout_surrogates" and rain_cfg is not None:
+            micro.surface_rain = {}                                            # every member but Kessler from its water budget
+            rain = rollout.RainScorer(micro.member_names, rain_cfg["thresholds_mm_h"], rain_cfg["thresholds_mm"])
         harvester = None
         if experiment == "rollout_surrogates" and harvest is not None:
             harvester = micro.harvester = rollout.RolloutHarvester()
@@ -469,6 +505,8 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                     before = dict(scorer.diverged_at)
                     scorer.accumulate(coupler, eval_step[0], etime + dt)
                     micro.guard_record(eval_step[0], dt)                       # (the only host read of the guards' counts)
+                    if rain is not None:
+                        rain.accumulate(coupler, micro, eval_step[0], etime + dt)
                     for m, d in scorer.diverged_at.items():                    # the other members do not see it: the run goes on
                         if d is not None and before[m] is None and not quiet:
                             print("rollout_surrogates: member %r is non-finite at step %d" % (m, d["step"]), flush=True)
@@ -520,12 +558,21 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                 doc["harvest"] = dict(harvest, files=dict(harvester.files), samples=dict(harvester.samples), skipped=dict(harvester.skipped),
                                       calls=harvester.calls)
                 info["harvest"] = doc["harvest"]
+            if rain is not None:
+                doc["surface_rain"] = dict(rain_cfg, report=rain.times)
+                info["surface_rain_report"], info["rain_total"] = rain.times, micro.rain_total
+                if rain_cfg["map"] and micro.rain_total is not None:           # (nens, ny, nx) fp64, mm since the start of the run
+                    import numpy as np
+                    info["surface_rain_map"] = os.path.join(os.getcwd(), "surrogate_rollout_rain.npy")
+                    np.save(info["surface_rain_map"], np.ascontiguousarray((1000.0 * micro.rain_total).permute(2, 0, 1).cpu().numpy()))
             info["surrogate_rollout"] = os.path.join(os.getcwd(), "surrogate_rollout.json")
             with open(info["surrogate_rollout"], "w") as f:
                 json.dump(doc, f, indent=1, allow_nan=False)
             info["rollout_report"] = rep
             if not quiet and scorer.times:
                 print(scorer.table(rep), flush=True)
+                if rain is not None and rain.times:
+                    print(rain.table(), flush=True)
     torch.cuda.synchronize(device)
     info.update(etime=etime, steps=steps, main_s=time.perf_counter() - t_main, dycore_etime=dycore.etime, num_out=dycore.num_out)
     if not quiet and coupler.is_mainproc():

@@ -9,11 +9,34 @@ import ctypes as C
 import torch
 
 from . import capi
-from ._ffi import _ptr, _stream_ptr, grown_workspace
+from ._ffi import _field_ptr_array, _ptr, _stream_ptr, grown_workspace
 from .capi import check
 from .coupler import endrun
 from .mlp import OUT4, load_surrogate_weights, mlp_forward, mlp_stencil_forward
 from .surrogate_eval import SurrogateBank
+
+
+def column_water(water3, nz, ncol, nens, dz, out=None):
+    """mw_member_column_water of three member-fastest (nz, ncol, nens) tensors (water_vapor, cloud_liquid, precip_liquid): the
+    (ncol * nens,) tensor of dz * sum_k ((rho_v + rho_c) + rho_r), kg / m^2, written into `out` if given."""
+    dev = water3[0].device
+    if out is None:
+        out = torch.empty(ncol * nens, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(capi.lib().mw_member_column_water(nz, ncol, nens, _field_ptr_array(water3), float(dz), _ptr(out), _stream_ptr(dev)))
+    return out
+
+
+def surface_rain_finish(water3, nz, ncol, nens, members, accum, dz, dt, w_before, precl, rain_total=None):
+    """mw_member_surface_rain: precl of the members in `members` becomes (w_before - column water of water3 now) / (1000 dt), then
+    rain_total of the members in `accum` grows by dt * precl.  Every other element keeps its bits."""
+    dev = water3[0].device
+    members, accum = [int(m) for m in members], [int(m) for m in accum]
+    with torch.cuda.device(dev):
+        check(capi.lib().mw_member_surface_rain(nz, ncol, nens, len(members), (C.c_int * max(1, len(members)))(*members), len(accum),
+                                                (C.c_int * max(1, len(accum)))(*accum), _field_ptr_array(water3), float(dz), float(dt),
+                                                _ptr(w_before) if w_before is not None else None, _ptr(precl),
+                                                _ptr(rain_total) if rain_total is not None else None, _stream_ptr(dev)))
 
 
 class Microphysics_Kessler:
@@ -72,13 +95,15 @@ class Microphysics_Kessler:
 class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
     """custom_modules::Microphysics_Kessler of the surrogate experiment: NN inference beside the true Kessler
     (microphysics_kessler_ponni.h:149-278).  The NN result is returned (and diffed) but not written back,
-    exactly like the reference with lines :273-276 commented out."""
+    exactly like the reference with lines :273-276 commented out.  With `online` the result replaces the state, and `precl` would still
+    be Kessler's; `surface_rain = True` then makes it the column water budget of the state that stays."""
 
     online = False        # True = the four deep_copy_to lines :273-276 un-commented: the NN result replaces Kessler's
     mlp_strict = 0        # 1: the thread-per-cell MLP that accumulates in index order (bit-identical to the CPU restatement; tests)
 
     want_range = False    # with a committee: time_step also fills last_range, the four fields of the members' spread
     last_range = None
+    surface_rain = False  # True (with online only): precl after the step is the column water budget of the state left in the coupler
 
     def init(self, coupler, weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None, committee=None, guard=None):
         """committee: a list of 1 .. 16 (W1, b1, W2, b2, scl_in, scl_out) tuples of one width (load_surrogate_weights' form).  The network's
@@ -142,11 +167,24 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
         return self._finish_step(coupler, dt, temp, rho_v, rho_c, rho_r)
 
     def _finish_step(self, coupler, dt, temp, rho_v, rho_c, rho_r):
+        budget = bool(self.surface_rain)
+        if budget:
+            if not self.online:
+                endrun("Microphysics_Kessler_Surrogate: surface_rain needs online = True (offline the state is Kessler's, and so is precl)")
+            # every member is one more column: the whole (ny * nx * nens) plane is one member's columns (the network's result is still
+            # out of place, so this is the state before the call)
+            nz, ncol = coupler.get_nz(), coupler.get_ny() * coupler.get_nx() * coupler.get_nens()
+            held = getattr(self, "_w_before", None)
+            self._w_before = column_water([rho_v, rho_c, rho_r], nz, ncol, 1, coupler.get_dz(),
+                                          held if held is not None and held.numel() == ncol else None)
         super().time_step(coupler, dt)
         if self.online:                                                        # :273-276
             self._diffs = self.mean_diffs(coupler)                             # (the prints of :266-269 come first)
             for dst, src in zip((temp, rho_v, rho_c, rho_r), self._nn_out):
                 dst.copy_(src)
+        if budget:                                                             # Kessler's precl gives way to the budget of the state that stays
+            precl = coupler.get_data_manager_readwrite().get("precl")
+            surface_rain_finish([rho_v, rho_c, rho_r], nz, ncol, 1, [0], [], coupler.get_dz(), dt, self._w_before, precl)
         return self._nn_out            # (temp_tmp, rho_v_tmp, rho_c_tmp, rho_r_tmp)
 
     def mean_diffs(self, coupler):

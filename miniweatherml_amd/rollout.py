@@ -4,7 +4,9 @@ experiments/supercell_kessler_surrogate/custom_modules/generate_micro_surrogate_
   Microphysics_Rollout       one microphysics step that treats every ensemble member differently (mw_member_*, SurrogateBank)
   kessler_members_teacher    mw_kessler_members_teacher: what Kessler would do to each member's own state
   RolloutHarvester           (state, label) samples of the teacher on the model members' states, one file per member
-  member_divergence, rollout_report, RolloutScorer    mw_member_divergence and its reports"""
+  member_divergence, rollout_report, RolloutScorer    mw_member_divergence and its reports
+  member_column_water, member_surface_rain            every member's surface rain from its column water budget
+  member_rain_table, rain_report, RainScorer          its contingency table against the Kessler member and the reports"""
 import ctypes as C
 import os
 
@@ -15,11 +17,11 @@ from . import capi
 from ._ffi import StatsAndCounts, _field_ptr_array, _ptr, _stream_ptr, grown_workspace
 from .capi import check
 from .coupler import endrun
-from .microphysics import Microphysics_Kessler
+from .microphysics import Microphysics_Kessler, column_water, surface_rain_finish
 from .mlp import IN5, OUT4
 from .ncio import sample_file_append, sample_file_create
 from .sampling import sample_buffers, sample_thresholds
-from .surrogate_eval import CommitteeGuard, SurrogateBank, finite_or_none, guard_config, json_safe, skill_cell
+from .surrogate_eval import CommitteeGuard, SurrogateBank, finite_or_none, guard_config, json_safe, or_dash, skill_cell
 
 ROLLOUT_FIELDS = ("density_dry", "uvel", "vvel", "wvel", "temp", "water_vapor", "cloud_liquid", "precip_liquid")
 ROLLOUT_STATS = ("sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_x", "min_x", "max_x")
@@ -51,7 +53,12 @@ class Microphysics_Rollout(Microphysics_Kessler):
     member k by model k - 1 of `models` (its output written back: Microphysics_Kessler_Surrogate.online for that member), the optional last
     member by nothing.  The dycore, the sponge and the nudger step the members independently, so one run shows how each candidate behaves
     once its own output is fed back.  Kessler runs on member 0 ALONE, extracted to contiguous arrays: its rain sub-cycle count is a minimum
-    over all the columns of a call.  `precl` is written for member 0 only; the other members' precl keeps whatever it held.
+    over all the columns of a call.  Without `surface_rain`, `precl` is written for member 0 only and the other members' precl keeps
+    whatever it held.  With `surface_rain` set to a mapping, every budget member's precl is what the step removed from its column's water
+    (mw_member_surface_rain: signed, m of water / s; the persistence member gets exactly +0.0) and `rain_total`, (ny, nx, nens) in
+    metres, accumulates dt * precl of every member -- Kessler's own precl for member 0.  The mapping may hold `budget_members`, the
+    members' names (default: every member but kessler; with kessler in it the budget overwrites Kessler's own precl of member 0, which
+    is the closure check of DESIGN.md 13.8).  The step itself is the same either way: the budget only reads the state.
     With a `harvester` (RolloutHarvester) and `harvest_now` set, the step harvests Kessler labels on the model members' own states
     between the Kessler member's step and the models'; harvesting reads the state and never writes it."""
 
@@ -59,6 +66,9 @@ class Microphysics_Rollout(Microphysics_Kessler):
     harvester = None      # a RolloutHarvester: time_step harvests when harvest_now is set (the driver sets it, and harvest_etime, per step)
     harvest_now = False
     harvest_etime = 0.0
+    surface_rain = None   # a mapping (may be empty; key budget_members): precl of the budget members and rain_total from the water budget
+    _w_before = None
+    rain_total = None     # with surface_rain: (ny, nx, nens) fp64, metres of water since the first step with the option
 
     def micro_name(self):
         return "rollout"
@@ -112,6 +122,7 @@ class Microphysics_Rollout(Microphysics_Kessler):
         self._guard = None                                                     # the CommitteeGuard all guarded members share
         self._guard_steps = [[] for _ in committees]
         self._m0 = None
+        self._w_before = self.rain_total = None
 
     def time_step(self, coupler, dt):
         dm = coupler.get_data_manager_readwrite()
@@ -127,6 +138,9 @@ class Microphysics_Rollout(Microphysics_Kessler):
         (v0, c0, r0, d0, t0), p0 = self._m0
         ws = grown_workspace(self, "_ws", L.mw_kessler_workspace_bytes(nz, ncol), coupler.device)
         st = _stream_ptr(coupler.device)
+        budget = self._budget_members(coupler)
+        if budget is not None:                                                 # W_before of ALL members, before anything is stepped
+            self._w_before = column_water([rho_v, rho_c, rho_r], nz, ncol, nens, coupler.get_dz(), self._w_before)
         check(L.mw_kessler_set_strict(self.strict))
         with torch.cuda.device(coupler.device):
             check(L.mw_member_extract(n, nens, 0, 5, _field_ptr_array([rho_v, rho_c, rho_r, rho_d, temp]), _field_ptr_array([v0, c0, r0, d0, t0]), st))
@@ -152,6 +166,26 @@ class Microphysics_Rollout(Microphysics_Kessler):
                 bank.committee_guard_flag(nz, sel, member, in5, [guards[ci][f] for f in GUARD_FIELDS], self._guard, guarded.index(ci))
         if guarded:                                                            # Kessler on every flagged column, then the guarded members' commit
             self._guard.commit(nz, [self.committees[ci][2] for ci in guarded], in5, guards[guarded[0]]["max_rainsplit"], coupler.get_dz(), dt)
+        if budget is not None:
+            surface_rain_finish([rho_v, rho_c, rho_r], nz, ncol, nens, budget, range(nens), coupler.get_dz(), dt, self._w_before, precl,
+                                self.rain_total)
+
+    def _budget_members(self, coupler):
+        """None without `surface_rain`; else the budget members' indices, with rain_total and the W_before buffer in place."""
+        sr = self.surface_rain
+        if sr is None:
+            return None
+        if not hasattr(sr, "keys") or set(sr.keys()) - {"budget_members"}:
+            endrun("Microphysics_Rollout: surface_rain is None or a mapping whose only key is budget_members")
+        names = sr.get("budget_members")
+        names = [m for m in self.member_names if m != "kessler"] if names is None else [str(m) for m in names]
+        if len(set(names)) != len(names) or any(m not in self.member_names for m in names):
+            endrun("Microphysics_Rollout: surface_rain's budget_members must be distinct members (%s)" % ", ".join(self.member_names))
+        shape = (coupler.get_ny(), coupler.get_nx(), coupler.get_nens())
+        if self.rain_total is None or tuple(self.rain_total.shape) != shape:
+            self.rain_total = torch.zeros(shape, dtype=torch.float64, device=coupler.device)
+            self._w_before = None
+        return [self.member_names.index(m) for m in names]
 
     def guard_record(self, step, dt):
         """At a scoring step, after time_step: fetches every guarded member's flagged columns and rain sub-cycle count of that step (the only
@@ -297,7 +331,11 @@ def member_divergence(coupler, names):
     stats (nens, len(names), 7) fp64 in the order of ROLLOUT_STATS (d = member - member 0 for the first four, the member's own values for
     the last three), nonfinite (nens, len(names)) int64, the member's NaN or inf elements -- from one device-to-host copy."""
     dm = coupler.get_data_manager_readonly()
-    fields = [dm.get(n, True) for n in names]
+    return fields_divergence(coupler, [dm.get(n, True) for n in names])
+
+
+def fields_divergence(coupler, fields):
+    """member_divergence of tensors (each (..., nens), one size) that need not be the coupler's own, such as a microphysics' rain_total."""
     nens = coupler.get_nens()
     n = fields[0].numel() // nens
     if any(t.numel() != n * nens or t.shape[-1] != nens for t in fields):
@@ -397,4 +435,164 @@ class RolloutScorer:
             cells = [skill_cell(row[f]["rmse"], row[f]["rmse_over_persistence"]) for f in self.fields]
             d = rep["diverged_at"][m]
             lines.append("%-*s " % (w, m) + " ".join(cells) + "  " + ("-" if d is None else "step %d" % d["step"]))
+        return "\n".join(lines)
+
+
+# ---- surface rain of every member from its column water budget -----------------------------------------------------------
+RAIN_COUNTS = ("hits", "misses", "false_alarms", "correct_negatives", "nonfinite")
+RAIN_FIELDS = ("rate_mm_h", "accumulation_mm")             # precl and rain_total in a report's units
+RAIN_UNITS = (3.6e6, 1.0e3)                                # m of water / s -> mm / h, m -> mm
+RAIN_DEFAULT_THRESHOLDS = (0.1, 1.0, 5.0, 10.0, 25.0)
+
+
+def _water3(coupler):
+    dm = coupler.get_data_manager_readonly()
+    return [dm.get(n, True) for n in ROLLOUT_WATER]
+
+
+def member_column_water(coupler, out=None):
+    """mw_member_column_water of the coupler's three water tracers: the (ny, nx, nens) tensor of every member's column water,
+    dz * sum over the levels of ((water_vapor + cloud_liquid) + precip_liquid), kg / m^2 (into `out`, of that shape, if given)."""
+    ny, nx, nens = coupler.get_ny(), coupler.get_nx(), coupler.get_nens()
+    if out is not None and (tuple(out.shape) != (ny, nx, nens) or not out.is_contiguous()):
+        endrun("member_column_water: out must be a contiguous (ny, nx, nens) tensor")
+    w = column_water(_water3(coupler), coupler.get_nz(), ny * nx, nens, coupler.get_dz(), None if out is None else out.view(-1))
+    return w.view(ny, nx, nens)
+
+
+def member_surface_rain(coupler, members, accum, dt, w_before, rain_total=None):
+    """mw_member_surface_rain on the coupler's state and its `precl`: for the members in `members` (indices), precl becomes
+    (w_before - member_column_water now) / (1000 dt), m of water / s, signed; then rain_total ((ny, nx, nens), metres; needed only with a
+    non-empty `accum`) of the members in `accum` grows by dt * precl.  w_before: member_column_water before the step."""
+    ny, nx, nens = coupler.get_ny(), coupler.get_nx(), coupler.get_nens()
+    for t, what in ((w_before, "w_before"), (rain_total, "rain_total")):
+        if t is not None and tuple(t.shape) != (ny, nx, nens):
+            endrun("member_surface_rain: %s must be a (ny, nx, nens) tensor" % what)
+    precl = coupler.get_data_manager_readwrite().get("precl")
+    surface_rain_finish(_water3(coupler), coupler.get_nz(), ny * nx, nens, members, accum, coupler.get_dz(), dt, w_before, precl, rain_total)
+
+
+def member_rain_table(coupler, fields, thresholds):
+    """mw_member_rain_table of 1 .. 4 tensors (..., nens) of one size (such as precl and a rain_total) against member 0: per field an
+    int64 array (its thresholds, nens, 5) in the order of RAIN_COUNTS.  thresholds: per field 1 .. 8 finite, strictly ascending numbers
+    in the field's own unit; an event is x >= threshold.  One device-to-host copy."""
+    nens, nf, cap = coupler.get_nens(), len(fields), capi.MW_RAIN_MAX_THRESHOLDS
+    thresholds = [[float(x) for x in row] for row in thresholds]
+    if not 1 <= nf <= capi.MW_RAIN_MAX_FIELDS or len(thresholds) != nf or any(not 1 <= len(row) <= cap for row in thresholds):
+        endrun("member_rain_table: 1 to %d fields, each with 1 to %d thresholds of its own" % (capi.MW_RAIN_MAX_FIELDS, cap))
+    ncol = fields[0].numel() // nens
+    if any(t.numel() != ncol * nens or t.shape[-1] != nens for t in fields):
+        endrun("member_rain_table: the fields must have one size and the members last")
+    L = capi.lib()
+    nbytes = L.mw_member_rain_table_workspace_bytes(ncol, nens, nf)
+    if nbytes <= 0:
+        endrun("member_rain_table: %d fields of %d columns x %d members are out of range (at most 64 members)" % (nf, ncol, nens))
+    ws = grown_workspace(coupler, "_ws_rain_table", nbytes, coupler.device)
+    buf = StatsAndCounts(0, nf * cap * nens * len(RAIN_COUNTS), coupler.device)
+    thr = (C.c_double * (nf * cap))(*[row[j] if j < len(row) else 0.0 for row in thresholds for j in range(cap)])
+    with torch.cuda.device(coupler.device):
+        check(L.mw_member_rain_table(ncol, nens, nf, _field_ptr_array(fields), (C.c_int * nf)(*[len(row) for row in thresholds]), thr, _ptr(ws),
+                                     buf.counts_ptr, _stream_ptr(coupler.device)))
+    counts = buf.host()[1].reshape(nf, cap, nens, len(RAIN_COUNTS))
+    return [counts[f, :len(row)].copy() for f, row in enumerate(thresholds)]
+
+
+def rain_thresholds(values, what):
+    """A checked threshold list of a surface_rain configuration: 1 .. 8 positive finite numbers, strictly ascending (ValueError)."""
+    if not isinstance(values, (list, tuple)) or not 1 <= len(values) <= capi.MW_RAIN_MAX_THRESHOLDS:
+        raise ValueError("ERROR: %s must be a list of 1 to %d numbers" % (what, capi.MW_RAIN_MAX_THRESHOLDS))
+    if any(isinstance(x, bool) or not isinstance(x, (int, float)) or not np.isfinite(x) or not x > 0 for x in values):
+        raise ValueError("ERROR: %s must hold positive finite numbers" % what)
+    out = [float(x) for x in values]
+    if any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError("ERROR: %s must be strictly ascending" % what)
+    return out
+
+
+def _ratio(num, den):
+    return None if den == 0 else float(num) / float(den)
+
+
+def rain_scores(counts):
+    """One threshold's five counts (RAIN_COUNTS' order) as a report row: the counts and csi = h / (h + m + f), pod = h / (h + m),
+    far = f / (h + f), frequency_bias = (h + f) / (h + m), each None where its denominator is 0.  Pure Python."""
+    h, m, f, cn, bad = (int(x) for x in counts)
+    return {"hits": h, "misses": m, "false_alarms": f, "correct_negatives": cn, "nonfinite": bad, "csi": _ratio(h, h + m + f),
+            "pod": _ratio(h, h + m), "far": _ratio(f, h + f), "frequency_bias": _ratio(h + f, h + m)}
+
+
+def rain_report(stats, nonfinite, tables, ncol, member_names, thresholds_mm_h, thresholds_mm):
+    """One scoring time's raw arrays as a report -- pure numpy.  stats (members, 2, 7) / nonfinite (members, 2): member_divergence's arrays
+    of precl (m / s) and rain_total (m); tables: member_rain_table's two arrays.  Per member, RAIN_FIELDS' two blocks -- the rate in
+    mm / h and the accumulation in mm: bias, mae, rmse and max_abs of d = member - Kessler member, the member's own mean, min, max, its
+    count of non-finite columns (a statistic that is inf or NaN is None, and the block carries "finite": False), and `thresholds`: per
+    threshold (in the block's unit) rain_scores' row."""
+    stats = np.asarray(stats, dtype=np.float64)
+    nonfinite = np.asarray(nonfinite, dtype=np.int64)
+    thresholds = ([float(x) for x in thresholds_mm_h], [float(x) for x in thresholds_mm])
+    tables = [np.asarray(t, dtype=np.int64) for t in tables]
+    nm = len(member_names)
+    if stats.shape != (nm, 2, 7) or nonfinite.shape != (nm, 2) or len(tables) != 2 or \
+            any(t.shape != (len(thr), nm, len(RAIN_COUNTS)) for t, thr in zip(tables, thresholds)):
+        endrun("rain_report: stats must be (%d members, 2, 7), nonfinite (%d, 2) and the tables (thresholds, %d, 5)" % (nm, nm, nm))
+    n = float(ncol)
+    rep = {}
+    for m, mname in enumerate(member_names):
+        rep[mname] = {}
+        for f, (fname, unit) in enumerate(zip(RAIN_FIELDS, RAIN_UNITS)):
+            s = stats[m, f]
+            with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+                row = {"bias": float(unit * (s[0] / n)), "mae": float(unit * (s[1] / n)), "rmse": float(unit * np.sqrt(s[2] / n)),
+                       "max_abs": float(unit * s[3]), "mean": float(unit * (s[4] / n)), "min": float(unit * s[5]), "max": float(unit * s[6]),
+                       "nonfinite": int(nonfinite[m, f])}
+            row = finite_or_none(row, bad=nonfinite[m, f] != 0)
+            row["thresholds"] = [dict(threshold=thr, **rain_scores(tables[f][j, m])) for j, thr in enumerate(thresholds[f])]
+            rep[mname][fname] = row
+    return rep
+
+
+class RainScorer:
+    """Every rollout member's surface rain against the Kessler member's: accumulate(coupler, micro, step, etime) at every scoring time,
+    report() / table() at the end.  member_names: rollout_member_names' list; thresholds_mm_h / thresholds_mm: the events of the rate
+    (precl, mm / h) and of the accumulation (micro.rain_total, mm), each 1 .. 8 positive, strictly ascending numbers."""
+
+    def __init__(self, member_names, thresholds_mm_h=RAIN_DEFAULT_THRESHOLDS, thresholds_mm=RAIN_DEFAULT_THRESHOLDS):
+        self.member_names = [str(m) for m in member_names]
+        self.thresholds_mm_h = rain_thresholds(list(thresholds_mm_h), "thresholds_mm_h")
+        self.thresholds_mm = rain_thresholds(list(thresholds_mm), "thresholds_mm")
+        self.times = []                 # per scoring time: step, etime, rain_report
+
+    def add(self, stats, nonfinite, tables, ncol, step, etime):
+        """One scoring time from raw arrays (what accumulate does after the kernels): pure numpy."""
+        rep = rain_report(stats, nonfinite, tables, ncol, self.member_names, self.thresholds_mm_h, self.thresholds_mm)
+        self.times.append({"step": int(step), "etime": float(etime), "members": rep})
+        return rep
+
+    def accumulate(self, coupler, micro, step, etime):
+        if getattr(micro, "rain_total", None) is None:
+            endrun("RainScorer.accumulate: the microphysics holds no rain_total (Microphysics_Rollout.surface_rain is off, or no step ran)")
+        fields = [coupler.get_data_manager_readonly().get("precl", True), micro.rain_total]
+        stats, nonfinite = fields_divergence(coupler, fields)
+        tables = member_rain_table(coupler, fields, [[x / RAIN_UNITS[0] for x in self.thresholds_mm_h],
+                                                     [x / RAIN_UNITS[1] for x in self.thresholds_mm]])
+        return self.add(stats, nonfinite, tables, coupler.get_ny() * coupler.get_nx(), step, etime)
+
+    def report(self):
+        """{"thresholds_mm_h", "thresholds_mm", "times": one rain_report per scoring time with its step and etime}."""
+        if not self.times:
+            endrun("RainScorer.report: nothing accumulated")
+        return {"thresholds_mm_h": list(self.thresholds_mm_h), "thresholds_mm": list(self.thresholds_mm), "times": self.times}
+
+    def table(self, rep=None):
+        """The last scoring time as text, one line per member: mean and rmse (against the Kessler member) of the rate and of the
+        accumulation, and the accumulation's critical success index at its lowest threshold."""
+        rep = self.report() if rep is None else rep
+        last = rep["times"][-1]
+        w = max(len(m) for m in self.member_names)
+        lines = ["surface rain at step %d, etime %.6f s" % (last["step"], last["etime"]),
+                 "%-*s %14s %14s %14s %14s %12s" % (w, "member", "rate mm/h", "rmse", "total mm", "rmse", "csi>=%gmm" % rep["thresholds_mm"][0])]
+        for m in self.member_names:
+            r, a = last["members"][m]["rate_mm_h"], last["members"][m]["accumulation_mm"]
+            lines.append("%-*s %14s %14s %14s %14s %12s" % (w, m, or_dash(r["mean"], "%.6e"), or_dash(r["rmse"], "%.6e"), or_dash(a["mean"], "%.6e"),
+                                                            or_dash(a["rmse"], "%.6e"), or_dash(a["thresholds"][0]["csi"], "%.4f")))
         return "\n".join(lines)
