@@ -115,7 +115,11 @@ int  mw_dycore_set_strict(mw_dycore_t h, int strict);
  * fused tracer stage is not launched -- the negative control of the FCT tests).  "vapour_state" (default 1; the folded supercell configuration
  * with one member and WENO-5 on the one-stream schedule behind k_y_all, ignored elsewhere: the water vapour is advanced by the x/z state kernel and the
  * tracer stage works on cloud and rain only; a stage in which a vapour cell fails the limiter test is redone by the three-tracer tracer stage;
- * results are bit for bit those of 0), "debug_vapour_redo" (a test aid: every stage takes that redo).  Unknown keys and out-of-range values are errors.  (The
+ * results are bit for bit those of 0), "debug_vapour_redo" (a test aid: every stage takes that redo), "lean_stores" (default 1; with
+ * "vapour_state" and the zero-row maps: the x/z state kernel does not store the face fluxes and selectors -- last stage: nor the result slab's
+ * density and pressure slots -- that only the tracer stage's full iterations read where the maps say lean, a replay launch stores them when the
+ * vapour is redone, and all-lean tracer waves leave their zero flag bytes out while the buffer is known to hold zeros; results are bit for bit
+ * those of 0).  Unknown keys and out-of-range values are errors.  (The
  * experiment builds of rounds 4-5 -- the fused x-y-z state kernel, the balanced launch lists, the timing hooks -- left the tree in round 6.) */
 int  mw_dycore_set_option(mw_dycore_t h, const char *key, long long value);
 int  mw_dycore_get_option(mw_dycore_t h, const char *key, long long *value);
@@ -214,6 +218,11 @@ long long mw_debug_vapour_redo(mw_dycore_t h);
  * last launch left them, index (k * ny + j) * nx * nens + x; at most cap bytes go to out_host (host memory).  Returns the number of cells,
  * -1 on error.  No reference counterpart. */
 long long mw_debug_tracer_flags(mw_dycore_t h, unsigned char *out_host, long long cap);
+/* Test aid of option "lean_stores": fills what the x/z state kernel hands to the tracer stage with values no reader survives -- both parities
+ * of the x and z mass-flux arrays with NaN and of their selector bytes with 0xFF, and the density and pressure slots of the slab that the last
+ * stage of the next time step writes (one sub-cycle) with NaN.  A reader that consumes an entry the kernel left out turns its result into
+ * NaN.  Returns 0, 1 on error.  No reference counterpart. */
+int  mw_debug_poison_handoff(mw_dycore_t h);
 
 /* modules::perturb_temperature(coupler, thermal=true, random=false), perturb_temperature.h:41-66 */
 int  mw_perturb_temperature(const mw_grid_t *g, double *temp, void *stream);

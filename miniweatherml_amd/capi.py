@@ -70,6 +70,7 @@ SYMBOLS = {
     "mw_debug_zero_violations": (C.c_longlong, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "mw_debug_vapour_redo": (C.c_longlong, [C.c_void_p]),
     "mw_debug_tracer_flags": (C.c_longlong, [C.c_void_p, C.c_void_p, C.c_longlong]),
+    "mw_debug_poison_handoff": (C.c_int, [C.c_void_p]),
     "mw_dycore_path": (C.c_char_p, [C.c_void_p]),
     "mw_dycore_use_rccl_self": (C.c_int, [C.c_void_p]),
     "mw_rccl_selftest_config": (C.c_int, [C.c_int, C.c_int]),

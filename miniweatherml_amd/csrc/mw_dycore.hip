@@ -958,6 +958,8 @@ const OptDesc OPTS[] = {
 //  tests/test_gpu_options.py; the defaults of these two are under test in tests/test_gpu_vapour_state.py)
 struct OptDesc2 { const char *key; int DyOpts::*field; };
 const OptDesc2 OPTS_VAPOUR[] = {{"vapour_state", &DyOpts::vapour_state}, {"debug_vapour_redo", &DyOpts::debug_vapour_redo}};
+// (round 9's key, in a table of its own for the same reason; its default is under test in tests/test_gpu_lean_stores.py)
+const OptDesc2 OPTS_LEAN[] = {{"lean_stores", &DyOpts::lean_stores}};
 constexpr int BUILD_FLAGS = 0;      // (no optional parts any more: mw_build_flags stays in the ABI and says so)
 }
 int mw_build_flags(void) { return BUILD_FLAGS; }
@@ -969,10 +971,10 @@ int mw_dycore_set_option(mw_dycore_t d, const char *key, long long value) {
     d->fused = (int)value;
     return 0;
   }
-  for (const OptDesc2 &od : OPTS_VAPOUR) {
-    if (strcmp(key, od.key)) continue;
+  for (const OptDesc2 *od : {&OPTS_VAPOUR[0], &OPTS_VAPOUR[1], &OPTS_LEAN[0]}) {
+    if (strcmp(key, od->key)) continue;
     if (value != 0 && value != 1) MW_FAIL(std::string("option ") + key + " must be 0 or 1");
-    d->o.*(od.field) = (int)value;
+    d->o.*(od->field) = (int)value;
     return 0;
   }
   for (const OptDesc &od : OPTS) {
@@ -988,6 +990,7 @@ int mw_dycore_get_option(mw_dycore_t d, const char *key, long long *value) {
   if (!d || !key || !value) MW_FAIL("mw_dycore_get_option: null argument");
   if (!strcmp(key, "fused_tracers")) { *value = d->fused; return 0; }
   for (const OptDesc2 &od : OPTS_VAPOUR) if (!strcmp(key, od.key)) { *value = d->o.*(od.field); return 0; }
+  for (const OptDesc2 &od : OPTS_LEAN) if (!strcmp(key, od.key)) { *value = d->o.*(od.field); return 0; }
   for (const OptDesc &od : OPTS) if (!strcmp(key, od.key)) { *value = d->o.*(od.field); return 0; }
   MW_FAIL(std::string("unknown option: ") + key);
 }

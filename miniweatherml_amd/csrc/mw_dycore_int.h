@@ -63,6 +63,7 @@ struct DyOpts {
   int debug_no_patch = 0;      // test aid: the y-face correction pass of the fused tracer stage is not launched (the negative control of the FCT tests)
   int vapour_state = 1;        // folded supercell configuration, nens == 1, WENO-5, one-stream schedule behind k_y_all: the water vapour is advanced by k_xz_state (0: by the tracer stage; A/B)
   int debug_vapour_redo = 0;   // test aid: every stage's redo word is set by hand -- the tracer stage recomputes the vapour in its three-tracer form
+  int lean_stores = 1;         // with vapour_state and maps: k_xz_state does not store the faces (and, last stage, the slab slots) that only FULL iterations of the tracer stage read where the row map says lean, a replay launch stores them when the vapour is redone; all-lean tracer waves leave their zero flag bytes out while the buffer is known to be zero (0: everything is stored; A/B)
 };
 
 struct mw_dycore_s {

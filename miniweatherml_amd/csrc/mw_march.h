@@ -975,6 +975,9 @@ struct XzVap {
   double *cq;            // MODE 1: the coupler's water_vapor ...
   double *crho, *ctemp;  // ... density_dry and temp: D13 is finished here where the tracer stage's storing iteration is lean
   unsigned *redo;        // the stage's "a vapour cell failed the limiter test" word
+  int lean;              // wave-uniform.  1: what only a FULL iteration of the tracer stage reads is not stored where the stage's row map says lean
+                         // (option lean_stores); 2: the REPLAY launch behind such a launch -- leaves at once unless the stage's word is set, and then
+                         // stores everything (the redo reads all of it); 0: everything is stored
 };
 
 // Member-co-located form (MT) of the two kernels that write the coupler's arrays in the last stage of a time step (D13), for a
@@ -1001,6 +1004,15 @@ struct XzVap {
 // row map (word min(k + 2, nz - 1) of the row, the tile's segment mask: cloud and rain are and stay zero there) this kernel finishes D13
 // itself -- water_vapor, density_dry and temp from registers -- and the tracer kernel has nothing to do for the cell; elsewhere (full
 // iterations, or no maps) it stores water_vapor only and the tracer kernel finishes D13, reading the vapour back.  Its per-cell carries and its z window live in LDS behind the background table (dynamic LDS).
+// Lean stores (va.lean == 1, maps on).  MX / UPX / MZ / UPZ have one reader, k_tracers_fused, and its LEAN iterations read none of them.  The form
+// of its iteration k' follows from word min(k', nz - 1) of the row and the tile's segment mask alone, and a FULL iteration k' reads the faces of
+// level k' or k' + 1 (its addresses are clamped into the chunk) -- so the faces of level k are read only when word k - 1 or word k (clamped to
+// 0 .. nz - 1) has a segment set that the tracer waves of THIS tile or of its two neighbours overlap (their halo lanes read this tile's edge
+// faces; what such a lane multiplies them with is exactly zero when this tile is lean, so the neighbours' segments keep out a non-finite stale
+// value, nothing else).  Where both words are clear on that mask the four face stores of level k are dropped; MODE 1: where the cell is lean, so are the result
+// slab's rho' and pressure slots, which only the tracer stage's D13 reads and this kernel has just finished D13 there.  The vapour redo reads
+// everything: behind a launch with lean stores the same instantiation runs once more with va.lean == 2 and, when the stage's word is set,
+// stores everything -- inputs and outputs are different arrays, so the second run writes the same bits.
 // WENO-5 only.  (Tried at WENO-3 too: weno3_edges_fast leaves the compiler a choice of which product of a sum of two it contracts, the two
 // kernels' x reconstructions chose differently and a wind-torn vapour field differed in its last bit -- that order keeps the tracer stage.)
 template <int STAGE, bool N1, int MODE, int HPL, int K, int ORD, bool MT = false, bool VAP = false>
@@ -1013,6 +1025,7 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
   static_assert(!MT || (N1 && HPL && MODE == 1), "the member-co-located form is the D13 variant of the nens == 1 kernel");
   static_assert(!VAP || (N1 && HPL && K == 1 && !MT && ORD == 5), "the vapour form exists for the folded supercell configuration with nens == 1, WENO-5");
   constexpr int HS = (ORD - 1) / 2;
+  if (VAP && va.lean == 2 && *va.redo == 0u) return;          // the replay launch, no redo: nothing to add (the whole grid, in front of the first barrier)
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   int mt_e = 0, mt_sub = 0;
   if (MT) {
@@ -1071,7 +1084,7 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
   // (MODE 1: the x segments of the row maps that the tracer kernel's wave for this tile overlaps -- its lanes, halo lanes and patch cells)
   const bool vzq_on = VAP && MODE == 1 && (p.zq != nullptr) && p.zero_skip;
   unsigned vzseg = 0;
-  if (VAP && MODE == 1) { const int tx_ = (q + (HS + 1) - lane) ; vzseg = zr_seg_mask(tx_ - (HS + 2), tx_ - (HS + 1) + 63 + 1, NXI, p.wrap_x != 0); }
+  if (VAP && MODE == 1) { const int tx_ = __builtin_amdgcn_readfirstlane(q + (HS + 1) - lane); vzseg = zr_seg_mask(tx_ - (HS + 2), tx_ - (HS + 1) + 63 + 1, NXI, p.wrap_x != 0); }
   // (bit i of vlean_mask = "the tracer kernel's iteration that stores cell kc0 + i is lean": lane i fetches the cell's word HERE, in front of the
   //  loop and with the prologue's loads, and the loop tests a scalar bit -- like zq_mask in k_tracers_fused.  Fetched inside the loop the word's
   //  wait stood where the predicate is formed, at the top of the iteration: vmcnt(0) behind the level's loads, one exposed round trip per level.
@@ -1082,6 +1095,22 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
     vlean_mask = __ballot((wz & vzseg) == 0u);
   };
   if (VAP && MODE == 1 && vzq_on) vlean_fetch(g.ka);
+  // (lean stores: bit i of fst_mask = "the faces of level ka + i have a reader", fetched like vlean_mask -- lane i looks at the words of the levels
+  //  ka + i - 1 and ka + i, on the segments of this tile and of its two neighbours; without maps, and in the replay launch, every bit is set)
+  const bool fst_on = VAP && va.lean == 1 && (p.zq != nullptr) && p.zero_skip;
+  unsigned fseg = 0;
+  if (fst_on) {                                                // (the tile's first cell as a scalar: the mask's divisions stay off the vector unit)
+    const int tx_ = __builtin_amdgcn_readfirstlane(q + (HS + 1) - lane), U_ = 64 - 2 * (HS + 1);
+    fseg = zr_seg_mask(tx_ - U_ - (HS + 2), tx_ + U_ - (HS + 1) + 63 + 1, NXI, p.wrap_x != 0);
+  }
+  unsigned long long fst_mask = ~0ull;
+  auto fst_fetch = [&](int kf0) __attribute__((always_inline)) {
+    const int kf = kf0 + lane;
+    const unsigned w0 = p.zq[(long long)min(max(kf - 1, 0), p.nz - 1) * p.zq_ld + j + MW_ZR_HALO];
+    const unsigned w1 = p.zq[(long long)min(kf, p.nz - 1) * p.zq_ld + j + MW_ZR_HALO];
+    fst_mask = __ballot(((w0 | w1) & fseg) != 0u);
+  };
+  if (fst_on) fst_fetch(g.ka);
   double wq[ORD], nxtq = 0, ctq = 0;
   int qr = (g.kstart - HS + ORD) % ORD;
 #define MW_QSLOT(s_) (lds_q[(5 + ((qr + (s_)) >= ORD ? qr + (s_) - ORD : qr + (s_))) * 256])
@@ -1107,6 +1136,12 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
       const int ic = max(k - 1, g.ka) - g.ka;
       if (ic > 0 && (ic & 63) == 0) vlean_fetch(g.ka + ic);    // (chunks of more than 64 levels: the next 64 words, in front of the level's loads)
       vlean = (vlean_mask >> (ic & 63)) & 1ull;
+    }
+    bool fst = true;                                           // VAP: the faces of level k have a reader
+    if (VAP) {
+      const int fi = max(k - g.ka, 0);
+      if (fst_on && fi > 0 && (fi & 63) == 0) fst_fetch(k);    // (chunks of more than 63 levels: the next 64 levels)
+      fst = (fst_mask >> (fi & 63)) & 1ull;
     }
     // ---------------- issue this iteration's global loads
     {
@@ -1241,11 +1276,11 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
         lds_q[(2 + (k & 1)) * 256] = tr_out_xy(tr_out_pair(feq, fxq, lds_c[0]), tr_out_pair(fynq, fysq, lds_c[4]));
       }
     }
-    if (xwork && g.owns_face && (g.owns_cell || q >= NXI)) {
+    if (xwork && fst && g.owns_face && (g.owns_cell || q >= NXI)) {
       const long long fo = (long long)k * p.fxK + (long long)j * p.fxJ + q;
       MX[fo] = fxs[idR];  UPX[fo] = (unsigned char)upx;
     }
-    if (zface && g.owns_cell) {
+    if (zface && fst && g.owns_cell) {
       const long long fo = (long long)k * p.fzK + (long long)j * p.fzJ + q;
       MZ[fo] = fzs[idR];  UPZ[fo] = (unsigned char)upz;
     }
@@ -1299,7 +1334,8 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
         // (MODE 1, the last stage of a time step: u, v, w go to the coupler's arrays only.  Nobody reads the result slab's velocities
         //  any more -- the tracer stage of this stage needs rho' and (rho theta)', and the next time_step starts from the coupler's
         //  fields (D1) -- so three of the five slab stores are dropped: 24 B per cell and step.)
-        if (g.owns_cell && !(MODE == 1 && (l == idU || l == idV || l == idW))) so[(long long)l * p.sV] = stored;
+        // (lean stores: where the cell is lean this kernel finishes D13 below and nobody reads rho' and p either)
+        if (g.owns_cell && !(MODE == 1 && (l == idU || l == idV || l == idW)) && !(VAP && MODE == 1 && vlean && fst_on)) so[(long long)l * p.sV] = stored;
         if (MODE == 1 && g.owns_cell && (l == idU || l == idV || l == idW))
           (l == idU ? cu : l == idV ? cv : cw)[cpl(p, cell0 + (long long)kc * planeC)] = stored;
       }
@@ -1564,7 +1600,8 @@ __global__ __launch_bounds__(256) void k_tracer_update(DyP p, const double *Ssta
 // ---------------------------------------------------------------------------------------------------------------
 //   VS = 1 (the folded supercell configuration behind k_xz_state<.., VAP>): tracer 0, the water vapour, has been advanced by the state kernel.
 //   With the stage's word vr[vslot] clear the kernel works on cloud and rain only -- FULL iterations on tracers 1 and 2, LEAN ones on nothing
-//   (their flag bytes are still stored: k_tracer_patch scans the bytes of neighbouring rows, none may be stale); D13 reads the vapour back.
+//   (their flag bytes are still stored unless the buffer is known to hold zeros -- dirty_prev below: k_tracer_patch scans the bytes of
+//   neighbouring rows, none may be stale); D13 reads the vapour back.
 //   With the word set (a vapour cell failed the limiter test) it takes the VS = 0 (three-tracer) bodies and overwrites what the state kernel
 //   stored: the inputs are untouched, so the redo is exact.  One wave-uniform branch per iteration, no host synchronisation.
 //   Thread 0 of the launch clears the next stage's word and counts the stages that took the redo (vr[8]; mw_debug_vapour_redo).
@@ -1579,7 +1616,12 @@ __global__ __launch_bounds__(256, 2) void k_tracers_fused(DyP p, const double *_
   static_assert(N1 || ORD == 5, "the neighbour-load form exists for WENO-5 only");
   static_assert(!VS || (N1 && K == 1 && T == 3 && !MT && ORD == 5), "the form without the vapour exists for the folded supercell configuration with nens == 1, WENO-5");
   bool vredo = true;
+  // (VS: vslot = the stage's word of the redo ring + 8 * where the PREVIOUS fused launch's "a non-zero flag byte was stored" word lies -- 1: at
+  //  dirty[1], 2: at dirty[-1], the two words alternate; 0: option lean_stores is off and nobody looks)
+  const unsigned int *dirty_prev = nullptr;
   if (VS) {
+    if (vslot >> 3) dirty_prev = ((vslot >> 3) == 1) ? dirty + 1 : dirty - 1;
+    vslot &= 7;
     vredo = __builtin_amdgcn_readfirstlane((int)vr[vslot]) != 0;
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { vr[(vslot + 1) & 7] = 0u; if (vredo) atomicAdd(&vr[8], 1u); }
   }
@@ -1665,7 +1707,10 @@ __global__ __launch_bounds__(256, 2) void k_tracers_fused(DyP p, const double *_
       busy = busy || (st_it && (zc_[(long long)kq_ * p.zq_ld + j + MW_ZR_HALO] & zseg_) != 0u);
     } else busy = true;
     if (!__any(busy)) {
-      if (upd && do_y) for (int kp = ka; kp < kb; kp++) flags[(long long)(kp * p.ny + j) * NXI + q] = (unsigned char)0;
+      // (lean stores: every launch rewrites every flag byte, so when the launch before stored no non-zero byte -- its word is clear -- the buffer
+      //  holds zeros, a launch that leaves zeros out keeps it so, and the zeros are left out)
+      const bool all_zero = dirty_prev != nullptr && *dirty_prev == 0u;
+      if (!all_zero && upd && do_y) for (int kp = ka; kp < kb; kp++) flags[(long long)(kp * p.ny + j) * NXI + q] = (unsigned char)0;
       return;
     }
   }

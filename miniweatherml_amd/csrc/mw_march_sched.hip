@@ -248,6 +248,24 @@ long long mw_debug_tracer_flags(mw_dycore_t d, unsigned char *out_host, long lon
   if (out_host && cap > 0 && hipMemcpy(out_host, d->flags, (size_t)std::min(n, cap), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   return n;
 }
+// Test aid of option lean_stores: NaN / 0xFF over everything k_xz_state<.., VAP> may leave out -- both parities of MX, MZ, UPX, UPZ and the rho' and
+// pressure slots of the slab that takes the last stage's result when the next time step runs one sub-cycle (S3).  All of it is scratch between
+// time steps: the faces are rewritten by every stage that reads them, and a time step starts from the coupler's arrays.
+int mw_debug_poison_handoff(mw_dycore_t d) {
+  if (!d || !d->S3) MW_FAIL("mw_debug_poison_handoff: null handle");
+  const DyP &p = d->p;
+  const size_t fn[3] = {(size_t)p.fxV, (size_t)p.fyV, (size_t)p.fzV};
+  for (int b = 0; b < 2; b++) for (int a = 0; a < 3; a += 2) {
+    MW_HIP(hipMemsetAsync(d->M[b][a], 0xFF, fn[a] * sizeof(double), d->stream));
+    MW_HIP(hipMemsetAsync(d->UP[b][a], 0xFF, fn[a], d->stream));
+  }
+  for (int e = 0; e < n_views(d); e++) {
+    const View v = view(d, e);
+    for (int l : {(int)idR, (int)idT}) MW_HIP(hipMemsetAsync(v.S(d->S3) + (long long)l * v.p.sV, 0xFF, (size_t)v.p.sV * sizeof(double), d->stream));
+  }
+  if (d->tstream) { MW_HIP(hipStreamSynchronize(d->stream)); }   // (the tracer stream of the two-stream schedule reads the faces too)
+  return 0;
+}
 // Test aid: how many RK stages of the last time step redid their water vapour in the tracer stage's three-tracer form because a cell failed the
 // limiter test in k_xz_state's vapour form (or option debug_vapour_redo set the word); 0 also when no stage ran the vapour form.  -1: null handle.
 long long mw_debug_vapour_redo(mw_dycore_t d) {

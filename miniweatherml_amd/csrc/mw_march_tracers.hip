@@ -54,10 +54,12 @@ template <int STAGE, int MODE, int T, bool N1, int K, int ORD = 5, int VS = 0>
 static void launch_tracers_fused_t(mw_dycore_s *d, const View &v, const double *S, const double *Sn, double *Sout, dim3 grid, int chunk, int tiles_x, int par,
                                    double dt, double dt_dyn, const CouplerPtrs &c, int rows4, hipStream_t st, int vap_slot) {
   const int e = v.e;
+  // (VS, option lean_stores: where the previous fused launch's word lies, seen from this launch's -- the two alternate; see the kernel)
+  const int prev_word = !d->o.lean_stores ? 0 : (d->fused_launches & 1) ? 2 : 1;
   MW_KLAUNCH((k_tracers_fused<STAGE, MODE, T, N1, K, ORD, false, VS>), grid, dim3(256), 0, st, v.p, v.S(S), v.S(Sn), v.S(Sout), d->FY + e * v.f[1],
                      d->M[par][0] + e * v.m[0], d->M[par][2] + e * v.m[2], d->UP[par][0] + e * v.m[0], d->UP[par][2] + e * v.m[2],
                      d->FX + e * v.f[0], d->FZ + e * v.f[2], d->flags + e * v.cells, d->dirty + (d->fused_launches & 1), dt, dt_dyn, c, chunk, tiles_x, rows4, MemberOff(),
-                     VS ? d->dirty + MW_VREDO_RING : nullptr, VS ? vap_slot : 0);
+                     VS ? d->dirty + MW_VREDO_RING : nullptr, VS ? vap_slot + 8 * prev_word : 0);
 }
 // x/z tracer fluxes + FCT + update in one kernel, then the (normally empty) y-face correction
 template <int STAGE, int MODE>

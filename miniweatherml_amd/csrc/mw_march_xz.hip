@@ -66,12 +66,16 @@ int launch_xz_state(mw_dycore_s *d, const double *S, const double *Sn, double *S
     const size_t hpl_bytes = (size_t)(chunk + 2) * 64;
     if (vap_slot >= 0) {
       // the water vapour rides along (rk_stage_march decided: K = 1, nens == 1, WENO-5, behind k_y_all): its per-thread carries behind the table rows
-      const XzVap va = {d->FY + (long long)5 * p.fyV, c.tr[0], c.rho_d, c.temp, d->dirty + MW_VREDO_RING + vap_slot};
+      XzVap va = {d->FY + (long long)5 * p.fyV, c.tr[0], c.rho_d, c.temp, d->dirty + MW_VREDO_RING + vap_slot, d->o.lean_stores ? 1 : 0};
       const size_t lds = hpl_bytes + (size_t)(5 + 5) * 256 * sizeof(double);   // (five carry slots + the five slots of the window ring)
-      MW_KLAUNCH((k_xz_state<STAGE, true, MODE, 1, 1, 5, false, true>), grid, dim3(256), lds, d->stream, p, v.S(S), v.S(Sn), v.S(Sout),
-                 MX, MZ, UX, UZ, tY, dt_stage, dt_dyn, chunk, tiles_x, c.u, c.v, c.w, MemberOff(), va);
+#define MW_XZ_VAP() MW_KLAUNCH((k_xz_state<STAGE, true, MODE, 1, 1, 5, false, true>), grid, dim3(256), lds, d->stream, p, v.S(S), v.S(Sn), v.S(Sout), \
+                               MX, MZ, UX, UZ, tY, dt_stage, dt_dyn, chunk, tiles_x, c.u, c.v, c.w, MemberOff(), va)
+      MW_XZ_VAP();
       // (test aid debug_vapour_redo: the stage's word set by hand, so that the tracer stage redoes a vapour that needs no redo)
       if (d->o.debug_vapour_redo) MW_HIP(hipMemsetAsync(d->dirty + MW_VREDO_RING + vap_slot, 0xFF, sizeof(unsigned int), d->stream));
+      // (lean stores with maps: the launch above may have left out what a redo reads -- the replay launch stores it when the stage's word is set)
+      if (va.lean && p.zq != nullptr && p.zero_skip) { MW_LAUNCH_CHECK(); va.lean = 2; MW_XZ_VAP(); }
+#undef MW_XZ_VAP
     } else
     if (p.nens == 1) {
       switch (marching_config(d, p)) { case 1: MW_XZ_K(1) break; case 2: MW_XZ_K(2) break; default: MW_XZ_K(0) break; }
