@@ -385,6 +385,27 @@ int  mw_mlp_stencil_forward(int nz, long long ncol, const double *temp, const do
 /* The number of levels of one z chunk that mw_mlp_stencil_forward's MFMA kernel uses for (nz, ncol) (nz: a single chunk). */
 int  mw_mlp_stencil_chunk(int nz, long long ncol);
 
+/* The two OUTPUT FORMS of a surrogate model.  MW_FORM_STATE: the network's output is the new state, y = (double)o * rng + min, the water
+ * fields then max(0, y) -- mw_mlp_forward / mw_mlp_stencil_forward, the reference's form.  MW_FORM_TENDENCY: the output is the CHANGE, and
+ * it is added in fp64 to the cell's own temp, rho_v, rho_c, rho_r (input features 0, 2, 3, 4 of the cell's own level, for the stencil
+ * model too; no reference counterpart):
+ *   d_j = (double)o_j * (max_j - min_j) + min_j          scl_out rows: [min, max] of (after - before)
+ *   y_0 = base_0 + d_0 ,  y_j = fmax(0.0, base_j + d_j)  j = 1, 2, 3; fp64, no contraction, this association
+ * The input scaling, both layers, the activation and the order of the fp32 sums are mw_mlp_forward's.  The two functions take the
+ * arguments of mw_mlp_forward / mw_mlp_stencil_forward behind `form` and honour mw_mlp_set_strict; form 0 writes the bits of those
+ * functions (which call these), any other value than the two is an error.  HBM traffic stays 72 B per cell: lane group g > 0 of the MFMA
+ * kernels reads its base from a line that another group of the same wave loads in the same iteration. */
+#define MW_FORM_STATE 0
+#define MW_FORM_TENDENCY 1
+int  mw_mlp_forward_form(int form, long long ncells, const double *temp, const double *rho_d, const double *rho_v,
+                         const double *rho_c, const double *rho_r, const float *W1, const float *b1, const float *W2,
+                         const float *b2, const double *scl_in, const double *scl_out, double *temp_out,
+                         double *rho_v_out, double *rho_c_out, double *rho_r_out, void *stream);
+int  mw_mlp_stencil_forward_form(int form, int nz, long long ncol, const double *temp, const double *rho_d, const double *rho_v,
+                                 const double *rho_c, const double *rho_r, const float *W1, const float *b1, const float *W2, const float *b2,
+                                 const double *scl_in, const double *scl_out, double *temp_out, double *rho_v_out, double *rho_c_out,
+                                 double *rho_r_out, void *stream);
+
 /* ponni's own surface: ponni::Inference<...>::forward_batch_parallel(float2d in(num_in, batch)) -> float2d
  * (num_out, batch), experiments/supercell_kessler_surrogate/custom_modules/microphysics_kessler_ponni.h:40-45,103-110,189, for a stack
  * of ponni::Matvec<float> (kind 0: weights (n_in, n_out) in Keras order, y = x W), ponni::Bias<float> (kind 1) and ponni::Relu<float>(n,
@@ -502,6 +523,14 @@ int  mw_surrogate_train_epoch_v2(int n_in, int models, const float *x, const flo
                                  float eps, double *stats, void *stream);
 int  mw_surrogate_batch_grad_v2(int n_in, const float *params, const float *x, const float *y, int batch, float *grad, float *loss,
                                 void *stream);
+/* mw_surrogate_prepare_v2 with the labels of an output form (MW_FORM_*).  Form 1: y = the scaled CHANGE of the sample,
+ *   (float)((((double)raw_out[j] - (double)raw_in[base(j)]) - min_j) / (max_j - min_j))      base(j) = 0, 2, 3, 4
+ * with scl_out rows [min, max] of (after - before); the x sets are those of _v2.  Form 0 writes the bits of _v2 in every array.  The
+ * sample records are fp32: a change below the fp32 spacing of the value (temperature: 3e-5 K at 300 K) arrives as 0 in the label.  The
+ * epoch, batch-gradient and error-sum functions work in scaled label space and serve both forms as they are. */
+int  mw_surrogate_prepare_form(int form, int n_in, long long n, const float *raw_in, const float *raw_out, const double *scl_in,
+                               const double *scl_out, unsigned long long seed, long long n_train, long long n_val, float *train_x,
+                               float *train_y, float *val_x, float *val_y, float *test_x, float *test_y, void *stream);
 long long mw_surrogate_errors_workspace_bytes(int nsets);
 int  mw_surrogate_errors(long long n, int nsets, const float *pred, const float *y, void *workspace, double *out, void *stream);
 
@@ -516,6 +545,14 @@ int  mw_surrogate_errors(long long n, int nsets, const float *pred, const float 
 typedef struct mw_surrogate_bank_s *mw_surrogate_bank_t;
 int  mw_surrogate_bank_create(mw_surrogate_bank_t *b, int n_in, int models, const float *params, const double *scl_in,
                               const double *scl_out);
+/* The same with an output form per model (MW_FORM_*): forms HOST (models), NULL = all MW_FORM_STATE, which is what
+ * mw_surrogate_bank_create passes.  A bank may hold both forms, as it holds models with different scaling tables; mw_surrogate_eval,
+ * mw_surrogate_members_apply and mw_surrogate_committee_apply then give, per model, the bits of mw_mlp_forward_form /
+ * mw_mlp_stencil_forward_form with that model's form (a mixed committee's mean is still the mean of its models' outputs).  Any other
+ * value is an error.  mw_surrogate_bank_form: model's form, -1 (and the error text) for a null handle or a model outside the bank. */
+int  mw_surrogate_bank_create_forms(mw_surrogate_bank_t *b, int n_in, int models, const float *params, const double *scl_in,
+                                    const double *scl_out, const int *forms);
+int  mw_surrogate_bank_form(mw_surrogate_bank_t b, int model);
 void mw_surrogate_bank_destroy(mw_surrogate_bank_t b);
 /* G: the number of models the MFMA kernels evaluate per pass over the state (more models: ceil(models / G) passes in one launch). */
 int  mw_surrogate_eval_group(mw_surrogate_bank_t b);

@@ -198,6 +198,15 @@ SYMBOLS = {
     "mw_mlp_stencil_chunk": (C.c_int, [C.c_int, C.c_longlong]),
     "mw_mlp_forward": (C.c_int, [C.c_longlong] + [C.c_void_p] * 5 + [C.POINTER(C.c_float)] * 4 +
                        [C.POINTER(C.c_double)] * 2 + [C.c_void_p] * 4 + [C.c_void_p]),
+    "mw_mlp_forward_form": (C.c_int, [C.c_int, C.c_longlong] + [C.c_void_p] * 5 + [C.POINTER(C.c_float)] * 4 +
+                            [C.POINTER(C.c_double)] * 2 + [C.c_void_p] * 4 + [C.c_void_p]),
+    "mw_mlp_stencil_forward_form": (C.c_int, [C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 5 + [C.POINTER(C.c_float)] * 4 +
+                                    [C.POINTER(C.c_double)] * 2 + [C.c_void_p] * 4 + [C.c_void_p]),
+    "mw_surrogate_prepare_form": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                            C.c_ulonglong, C.c_longlong, C.c_longlong] + [C.c_void_p] * 6 + [C.c_void_p]),
+    "mw_surrogate_bank_create_forms": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double),
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "mw_surrogate_bank_form": (C.c_int, [C.c_void_p, C.c_int]),
 }
 
 _lib = None

@@ -26,8 +26,11 @@
 
 namespace mw {
 
-// TILES 16-cell tiles per wave per iteration
-template <int TILES>
+// TILES 16-cell tiles per wave per iteration.  TEND: the tendency form (mw_mlp_net.h: net_out_tendency) -- a template parameter and not
+// a branch on P.form, so that the state form's instantiation is the code it always was.  Lane group g > 0 then needs the field its output
+// replaces (rho_v, rho_c, rho_r), which another group of the wave loads in the same iteration: one more 8-byte load per lane, in the
+// register that only group 0 uses for rho_r, issued with the iteration's other loads and ahead of its stores.
+template <int TILES, bool TEND>
 __global__ __launch_bounds__(256) void k_mlp(MlpP P, long long ncells, const double *__restrict__ temp,
                                              const double *__restrict__ rho_d, const double *__restrict__ rho_v,
                                              const double *__restrict__ rho_c, const double *__restrict__ rho_r,
@@ -41,6 +44,8 @@ __global__ __launch_bounds__(256) void k_mlp(MlpP P, long long ncells, const dou
   // per-lane constants
   const double *in_g = (g == 0) ? temp : (g == 1) ? rho_d : (g == 2) ? rho_v : rho_c;
   double *out_g = (g == 0) ? o_temp : (g == 1) ? o_rv : (g == 2) ? o_rc : o_rr;
+  constexpr bool LOADB = TEND && !MW_TENDENCY_ROTATE_FORWARD;                    // the base of groups 1..3 by a load (else, TEND: by the rotate)
+  const double *in_s = (!LOADB || g == 0) ? rho_r : (g == 1) ? rho_v : (g == 2) ? rho_c : rho_r;     // group 0: rho_r for the network; else the base
   Net5 N;
   net5_ops(N, P, lane, g);
   const long long ntiles = (ncells + 15) / 16;
@@ -51,12 +56,13 @@ __global__ __launch_bounds__(256) void k_mlp(MlpP P, long long ncells, const dou
       long long cell = (t0 + u) * 16 + cidx;
       bool ok = cell < ncells;
       xin[u]  = ok ? in_g[cell] : N.imin;
-      xin4[u] = (ok && g == 0) ? rho_r[cell] : N.imin4;
+      xin4[u] = (ok && (LOADB || g == 0)) ? in_s[cell] : N.imin4;
     }
 #pragma unroll
     for (int u = 0; u < TILES; u++) {
       long long cell = (t0 + u) * 16 + cidx;
-      const double y = net5_cell(N, g, xin[u], xin4[u]);
+      if (TEND && !LOADB) xin4[u] = net5_rotate_base(g, xin[u], xin4[u]);
+      const double y = net5_cell_form<TEND>(N, g, xin[u], xin4[u], MW_FORM_TENDENCY);
       if (cell < ncells) out_g[cell] = y;
     }
   }
@@ -67,7 +73,7 @@ __global__ __launch_bounds__(256) void k_mlp(MlpP P, long long ncells, const dou
 // cells of the span form one MFMA tile, the odd cells the next (a tile is any 16 cells).  ncells must be a multiple of 32 here;
 // the launcher hands the remainder to k_mlp.
 typedef double f64x2 __attribute__((ext_vector_type(2)));
-template <int PAIRS>
+template <int PAIRS, bool TEND>
 __global__ __launch_bounds__(256) void k_mlp_x2(MlpP P, long long ncells, const double *__restrict__ temp,
                                                 const double *__restrict__ rho_d, const double *__restrict__ rho_v,
                                                 const double *__restrict__ rho_c, const double *__restrict__ rho_r,
@@ -80,6 +86,8 @@ __global__ __launch_bounds__(256) void k_mlp_x2(MlpP P, long long ncells, const 
   const long long nwaves = ((long long)gridDim.x * 256) >> 6;
   const double *in_g = (g == 0) ? temp : (g == 1) ? rho_d : (g == 2) ? rho_v : rho_c;
   double *out_g = (g == 0) ? o_temp : (g == 1) ? o_rv : (g == 2) ? o_rc : o_rr;
+  constexpr bool LOADB = TEND && !MW_TENDENCY_ROTATE_FORWARD;                    // (as in k_mlp)
+  const double *in_s = (!LOADB || g == 0) ? rho_r : (g == 1) ? rho_v : (g == 2) ? rho_c : rho_r;
   Net5 N;
   net5_ops(N, P, lane, g);
   const long long nspans = ncells / 32;
@@ -89,13 +97,16 @@ __global__ __launch_bounds__(256) void k_mlp_x2(MlpP P, long long ncells, const 
     for (int u = 0; u < PAIRS; u++) {
       const long long cell = min(s0 + u, nspans - 1) * 32 + 2 * cidx;          // (clamped: the tail spans are recomputed, not stored)
       xin[u] = *(const f64x2 *)(in_g + cell);
-      xin4[u] = (g == 0) ? *(const f64x2 *)(rho_r + cell) : (f64x2){N.imin4, N.imin4};
+      xin4[u] = (LOADB || g == 0) ? *(const f64x2 *)(in_s + cell) : (f64x2){N.imin4, N.imin4};
     }
 #pragma unroll
     for (int u = 0; u < PAIRS; u++) {
       f64x2 y2;
 #pragma unroll
-      for (int h = 0; h < 2; h++) y2[h] = net5_cell(N, g, xin[u][h], xin4[u][h]);
+      for (int h = 0; h < 2; h++) {
+        if (TEND && !LOADB) xin4[u][h] = net5_rotate_base(g, xin[u][h], xin4[u][h]);
+        y2[h] = net5_cell_form<TEND>(N, g, xin[u][h], xin4[u][h], MW_FORM_TENDENCY);
+      }
       if (s0 + u < nspans) *(f64x2 *)(out_g + (s0 + u) * 32 + 2 * cidx) = y2;
     }
   }
@@ -177,6 +188,7 @@ using namespace mw;
 
 // STRICT form (mw_mlp_set_strict(1)): thread = cell, the index-order loops of MW_STRICT_CELL -- bit-identical to the CPU restatement.
 // (The MFMA kernels sum the same products in the matrix cores' order: 1e-5 on the fp32 outputs.)
+template <bool TEND>
 __global__ __launch_bounds__(256) void k_mlp_strict(MlpRef P, long long n, const double *__restrict__ temp, const double *__restrict__ rho_d,
                                                     const double *__restrict__ rho_v, const double *__restrict__ rho_c, const double *__restrict__ rho_r,
                                                     double *__restrict__ temp_out, double *__restrict__ rho_v_out, double *__restrict__ rho_c_out,
@@ -185,7 +197,7 @@ __global__ __launch_bounds__(256) void k_mlp_strict(MlpRef P, long long n, const
   const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
   if (c >= n) return;
   const double in[5] = {temp[c], rho_d[c], rho_v[c], rho_c[c], rho_r[c]};
-  MW_STRICT_CELL(5, P, in, temp_out[c], rho_v_out[c], rho_c_out[c], rho_r_out[c])
+  MW_STRICT_CELL_FORM(5, P, in, TEND, temp_out[c], rho_v_out[c], rho_c_out[c], rho_r_out[c])
 }
 
 // The MFMA operand images (see the header of this file): A operands per lane, C initialisers = the biases.
@@ -224,18 +236,25 @@ static thread_local int g_mlp_strict = 0;        // per calling thread: a rank h
 extern "C" int mw_mlp_set_strict(int strict) { g_mlp_strict = strict ? 1 : 0; return 0; }
 int mw::mlp_strict() { return g_mlp_strict; }
 
-extern "C" int mw_mlp_forward(long long ncells, const double *temp, const double *rho_d, const double *rho_v, const double *rho_c,
-                              const double *rho_r, const float *W1, const float *b1, const float *W2, const float *b2,
-                              const double *scl_in, const double *scl_out, double *temp_out, double *rho_v_out,
-                              double *rho_c_out, double *rho_r_out, void *stream) {
+static bool form_known(int form) { return form == MW_FORM_STATE || form == MW_FORM_TENDENCY; }
+
+// launches the first kernel where the condition holds, else the second (a kernel template's two instantiations, each in parentheses)
+#define MW_LAUNCH_FORM(cond, KT, KF, ...) do { if (cond) hipLaunchKernelGGL(KT, __VA_ARGS__); else hipLaunchKernelGGL(KF, __VA_ARGS__); } while (0)
+
+extern "C" int mw_mlp_forward_form(int form, long long ncells, const double *temp, const double *rho_d, const double *rho_v, const double *rho_c,
+                                   const double *rho_r, const float *W1, const float *b1, const float *W2, const float *b2,
+                                   const double *scl_in, const double *scl_out, double *temp_out, double *rho_v_out,
+                                   double *rho_c_out, double *rho_r_out, void *stream) {
+  if (!form_known(form)) MW_FAIL("mlp: form must be MW_FORM_STATE (0) or MW_FORM_TENDENCY (1), got " + std::to_string(form));
+  const bool tend = form == MW_FORM_TENDENCY;
   if (ncells < 1) MW_FAIL("mlp: ncells must be >= 1");
   if (!temp || !rho_d || !rho_v || !rho_c || !rho_r || !W1 || !b1 || !W2 || !b2 || !scl_in || !scl_out || !temp_out ||
       !rho_v_out || !rho_c_out || !rho_r_out) MW_FAIL("mlp: null pointer");
   if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
   if (g_mlp_strict) {
     MlpRef R;
-    fill_ref(R, 5, W1, b1, W2, b2, scl_in, scl_out);
-    hipLaunchKernelGGL(k_mlp_strict, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, R, ncells, temp, rho_d, rho_v, rho_c,
+    fill_ref(R, 5, W1, b1, W2, b2, scl_in, scl_out, form);
+    MW_LAUNCH_FORM(tend, (k_mlp_strict<true>), (k_mlp_strict<false>), dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, R, ncells, temp, rho_d, rho_v, rho_c,
                        rho_r, temp_out, rho_v_out, rho_c_out, rho_r_out);
     MW_LAUNCH_CHECK();
     return 0;
@@ -244,6 +263,7 @@ extern "C" int mw_mlp_forward(long long ncells, const double *temp, const double
   net_dense_layer1_images(P.a1, W1, 5);
   net_layer2_images(P.c1, P.a2, P.c2, b1, W2, b2);
   fill_scaling(5, scl_in, scl_out, P.in_min, P.in_rng, P.out_min, P.out_rng);
+  P.form = form;
   constexpr int TILES = 4, PAIRS = 2;
   // bulk: spans of 32 cells with 16-byte accesses (needs 16-byte aligned arrays); remainder (and unaligned callers): k_mlp
   bool aligned = true;
@@ -254,7 +274,7 @@ extern "C" int mw_mlp_forward(long long ncells, const double *temp, const double
     long long waves_needed = (bulk / 32 + PAIRS - 1) / PAIRS;
     long long blocks = (waves_needed + 3) / 4;
     if (blocks > 256 * 16) blocks = 256 * 16;                   // grid-stride beyond 16 blocks per CU
-    hipLaunchKernelGGL(k_mlp_x2<PAIRS>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, bulk, temp, rho_d, rho_v, rho_c,
+    MW_LAUNCH_FORM(tend, (k_mlp_x2<PAIRS, true>), (k_mlp_x2<PAIRS, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, bulk, temp, rho_d, rho_v, rho_c,
                        rho_r, temp_out, rho_v_out, rho_c_out, rho_r_out);
     MW_LAUNCH_CHECK();
   }
@@ -265,11 +285,19 @@ extern "C" int mw_mlp_forward(long long ncells, const double *temp, const double
     long long blocks = (waves_needed + 3) / 4;
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(k_mlp<TILES>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, rest, temp + bulk, rho_d + bulk, rho_v + bulk,
+    MW_LAUNCH_FORM(tend, (k_mlp<TILES, true>), (k_mlp<TILES, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, rest, temp + bulk, rho_d + bulk, rho_v + bulk,
                        rho_c + bulk, rho_r + bulk, temp_out + bulk, rho_v_out + bulk, rho_c_out + bulk, rho_r_out + bulk);
     MW_LAUNCH_CHECK();
   }
   return 0;
+}
+
+extern "C" int mw_mlp_forward(long long ncells, const double *temp, const double *rho_d, const double *rho_v, const double *rho_c,
+                              const double *rho_r, const float *W1, const float *b1, const float *W2, const float *b2,
+                              const double *scl_in, const double *scl_out, double *temp_out, double *rho_v_out,
+                              double *rho_c_out, double *rho_r_out, void *stream) {
+  return mw_mlp_forward_form(MW_FORM_STATE, ncells, temp, rho_d, rho_v, rho_c, rho_r, W1, b1, W2, b2, scl_in, scl_out, temp_out, rho_v_out,
+                             rho_c_out, rho_r_out, stream);
 }
 
 // ponni::Inference<...>::forward_batch_parallel (microphysics_kessler_ponni.h:189) for a stack of ponni layers on fp32 device arrays in
@@ -340,7 +368,7 @@ extern "C" int mw_ponni_forward(const mw_ponni_layer_t *layers, int nlayers, con
 // =====================================================================================================
 namespace mw {
 
-template <int U>
+template <int U, bool TEND>
 __global__ __launch_bounds__(256) void k_mlp_stencil(StencilP P, int nz, long long ncol, int zc, int nchunks,
                                                      const double *__restrict__ temp, const double *__restrict__ rho_d,
                                                      const double *__restrict__ rho_v, const double *__restrict__ rho_c,
@@ -358,6 +386,7 @@ __global__ __launch_bounds__(256) void k_mlp_stencil(StencilP P, int nz, long lo
   const int k_lo = chunk * zc, k_hi = min(nz, k_lo + zc) - 1, k_top = min(nz - 1, k_hi + 1);
   const double *in_g = (g == 0) ? temp : (g == 1) ? rho_d : (g == 2) ? rho_v : rho_c;
   double *out_g = (g == 0) ? o_temp : (g == 1) ? o_rv : (g == 2) ? o_rc : o_rr;
+  const double *in_s = (g == 1) ? rho_v : (g == 2) ? rho_c : rho_r;       // TEND: the field output g replaces (group 0 holds its own, temp)
   Net9 N;
   net9_ops(N, P, lane, g);
   // the level above the chunk's top (the top level itself at the model top): the one level a chunk reads twice
@@ -368,13 +397,14 @@ __global__ __launch_bounds__(256) void k_mlp_stencil(StencilP P, int nz, long lo
     if (g == ((k_hi & 1) ^ 1)) rr_raw = rho_r[(long long)k_top * ncol + col];
   }
   for (int k0 = k_hi; k0 >= k_lo; k0 -= U) {
-    double xin[U], xrr[U];
+    double xin[U], xrr[U], xs[U];
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const int k = k0 - u;
       const bool lv = ok && k >= k_lo;
       xin[u] = lv ? in_g[(long long)k * ncol + col] : N.imin;
       xrr[u] = (lv && g == (k & 1)) ? rho_r[(long long)k * ncol + col] : N.rmin;
+      if (TEND) xs[u] = (lv && g != 0) ? in_s[(long long)k * ncol + col] : xin[u];                  // level k's own value, not the carried level above
     }
 #pragma unroll
     for (int u = 0; u < U; u++) {
@@ -383,7 +413,7 @@ __global__ __launch_bounds__(256) void k_mlp_stencil(StencilP P, int nz, long lo
         if (g == (k & 1)) rr_raw = xrr[u];                                // this group holds rho_r of level k, the other one of level k + 1
         const f32x4 d1 = net9_layer1(N, k, net9_b0(N, xin[u]), above, net9_b2(N, g, k, rr_raw));
         above = net9_above(N, xin[u]);                                    // level k is level k - 1's level above
-        const double y = net_out(N, g, d1);
+        const double y = net_out_form<TEND>(N, g, d1, MW_FORM_TENDENCY, TEND ? xs[u] : 0.0);
         if (ok) out_g[(long long)k * ncol + col] = y;
       }
     }
@@ -391,6 +421,7 @@ __global__ __launch_bounds__(256) void k_mlp_stencil(StencilP P, int nz, long lo
 }
 
 // STRICT form: thread = cell, MW_STRICT_CELL with nine features.
+template <bool TEND>
 __global__ __launch_bounds__(256) void k_mlp_stencil_strict(StencilRef P, int nz, long long ncol, const double *__restrict__ temp,
                                                             const double *__restrict__ rho_d, const double *__restrict__ rho_v,
                                                             const double *__restrict__ rho_c, const double *__restrict__ rho_r,
@@ -402,7 +433,7 @@ __global__ __launch_bounds__(256) void k_mlp_stencil_strict(StencilRef P, int nz
   const long long k = c / ncol;
   const long long ca = (k + 1 < nz) ? c + ncol : c;                       // level min(nz - 1, k + 1), same column
   const double in[9] = {temp[c], rho_d[c], rho_v[c], rho_c[c], rho_r[c], temp[ca], rho_v[ca], rho_c[ca], rho_r[ca]};
-  MW_STRICT_CELL(9, P, in, temp_out[c], rho_v_out[c], rho_c_out[c], rho_r_out[c])
+  MW_STRICT_CELL_FORM(9, P, in, TEND, temp_out[c], rho_v_out[c], rho_c_out[c], rho_r_out[c])
 }
 
 } // namespace mw
@@ -420,10 +451,12 @@ extern "C" int mw_mlp_stencil_chunk(int nz, long long ncol) {
   return (int)((nz + want - 1) / want);
 }
 
-extern "C" int mw_mlp_stencil_forward(int nz, long long ncol, const double *temp, const double *rho_d, const double *rho_v,
-                                      const double *rho_c, const double *rho_r, const float *W1, const float *b1, const float *W2,
-                                      const float *b2, const double *scl_in, const double *scl_out, double *temp_out, double *rho_v_out,
-                                      double *rho_c_out, double *rho_r_out, void *stream) {
+extern "C" int mw_mlp_stencil_forward_form(int form, int nz, long long ncol, const double *temp, const double *rho_d, const double *rho_v,
+                                           const double *rho_c, const double *rho_r, const float *W1, const float *b1, const float *W2,
+                                           const float *b2, const double *scl_in, const double *scl_out, double *temp_out, double *rho_v_out,
+                                           double *rho_c_out, double *rho_r_out, void *stream) {
+  if (!form_known(form)) MW_FAIL("mlp_stencil: form must be MW_FORM_STATE (0) or MW_FORM_TENDENCY (1), got " + std::to_string(form));
+  const bool tend = form == MW_FORM_TENDENCY;
   if (nz < 1 || ncol < 1) MW_FAIL("mlp_stencil: nz and ncol must be >= 1");
   if (!temp || !rho_d || !rho_v || !rho_c || !rho_r || !W1 || !b1 || !W2 || !b2 || !scl_in || !scl_out || !temp_out ||
       !rho_v_out || !rho_c_out || !rho_r_out) MW_FAIL("mlp_stencil: null pointer");
@@ -434,8 +467,8 @@ extern "C" int mw_mlp_stencil_forward(int nz, long long ncol, const double *temp
   if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
   if (g_mlp_strict) {
     StencilRef R;
-    fill_ref(R, 9, W1, b1, W2, b2, scl_in, scl_out);
-    hipLaunchKernelGGL(k_mlp_stencil_strict, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, R, nz, ncol, temp, rho_d,
+    fill_ref(R, 9, W1, b1, W2, b2, scl_in, scl_out, form);
+    MW_LAUNCH_FORM(tend, (k_mlp_stencil_strict<true>), (k_mlp_stencil_strict<false>), dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, R, nz, ncol, temp, rho_d,
                        rho_v, rho_c, rho_r, temp_out, rho_v_out, rho_c_out, rho_r_out);
     MW_LAUNCH_CHECK();
     return 0;
@@ -444,11 +477,20 @@ extern "C" int mw_mlp_stencil_forward(int nz, long long ncol, const double *temp
   net_stencil_layer1_images(P.a1, W1);
   net_layer2_images(P.c1, P.a2, P.c2, b1, W2, b2);
   fill_scaling(9, scl_in, scl_out, P.in_min, P.in_rng, P.out_min, P.out_rng);
+  P.form = form;
   const int zc = mw_mlp_stencil_chunk(nz, ncol), nchunks = (nz + zc - 1) / zc;
   const long long waves = ((ncol + 15) / 16) * nchunks, blocks = (waves + 3) / 4;
   if (blocks > 0x7fffffffll) MW_FAIL("mlp_stencil: grid too large");
-  hipLaunchKernelGGL(k_mlp_stencil<4>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, nz, ncol, zc, nchunks, temp, rho_d, rho_v,
+  MW_LAUNCH_FORM(tend, (k_mlp_stencil<4, true>), (k_mlp_stencil<4, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, nz, ncol, zc, nchunks, temp, rho_d, rho_v,
                      rho_c, rho_r, temp_out, rho_v_out, rho_c_out, rho_r_out);
   MW_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int mw_mlp_stencil_forward(int nz, long long ncol, const double *temp, const double *rho_d, const double *rho_v,
+                                      const double *rho_c, const double *rho_r, const float *W1, const float *b1, const float *W2,
+                                      const float *b2, const double *scl_in, const double *scl_out, double *temp_out, double *rho_v_out,
+                                      double *rho_c_out, double *rho_r_out, void *stream) {
+  return mw_mlp_stencil_forward_form(MW_FORM_STATE, nz, ncol, temp, rho_d, rho_v, rho_c, rho_r, W1, b1, W2, b2, scl_in, scl_out, temp_out,
+                                     rho_v_out, rho_c_out, rho_r_out, stream);
 }

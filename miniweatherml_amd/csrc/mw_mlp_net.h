@@ -14,7 +14,7 @@
 #include <cstring>
 
 // (in the global namespace, as k_mlp_strict is: the kernel's symbol carries its argument types)
-struct MlpRef { float W1[50], b1[10], W2[40], b2[4]; double in_min[5], in_rng[5], out_min[4], out_rng[4]; };
+struct MlpRef { float W1[50], b1[10], W2[40], b2[4]; double in_min[5], in_rng[5], out_min[4], out_rng[4]; int form; };
 
 namespace mw {
 
@@ -28,6 +28,7 @@ struct MlpP {
   float c2[4];          // layer-2 C init for reg 0 of group g (bias of output g)
   double in_min[5], in_rng[5];     // scl_in(:,0), scl_in(:,1)-scl_in(:,0)
   double out_min[4], out_rng[4];
+  int form;                        // MW_FORM_STATE / MW_FORM_TENDENCY: what the un-scaled output is (net_out / net_out_tendency)
 };
 struct StencilP {
   float a1[4][64];      // layer-1 A operands: [0] cell features 0..3, [1] level-above features by group, [2] / [3] rho_r rows for even / odd k
@@ -36,6 +37,7 @@ struct StencilP {
   float c2[4];
   double in_min[9], in_rng[9];
   double out_min[4], out_rng[4];
+  int form;
 };
 struct EvalModel {                         // one model of a bank as the MFMA kernels read it from LDS
   float a1[4][64];                         // n_in 5: MlpP::a1[0..1]; n_in 9: StencilP::a1[0..3]
@@ -44,9 +46,10 @@ struct EvalModel {                         // one model of a bank as the MFMA ke
   float c2[4];
   double in_min[9], in_irng[9];            // in_irng: uploaded as the range, inverted on the device by k_surrogate_bank_recip
   double out_min[4], out_rng[4];
+  int form;                                // per model: a bank may hold both forms, as it holds models with different scaling tables
 };
 // the strict kernels' form: the weights as they are (MlpRef: above, outside the namespace)
-struct StencilRef { float W1[90], b1[10], W2[40], b2[4]; double in_min[9], in_rng[9], out_min[4], out_rng[4]; };
+struct StencilRef { float W1[90], b1[10], W2[40], b2[4]; double in_min[9], in_rng[9], out_min[4], out_rng[4]; int form; };
 
 // ---- host side (defined in mw_mlp.hip) ----
 // the MFMA operand images: layer 1 of the dense form (feature 4m + g in k-slot g of MFMA m: 5 inputs, or ponni's 9), layer 1 of the
@@ -65,8 +68,10 @@ inline void fill_scaling(int n_in, const double *scl_in, const double *scl_out, 
 }
 // a strict kernel's table (MlpRef / StencilRef) of a model with n_in inputs: the weights as they are; what a narrower model leaves is zero
 template <typename R>
-inline void fill_ref(R &ref, int n_in, const float *W1, const float *b1, const float *W2, const float *b2, const double *scl_in, const double *scl_out) {
+inline void fill_ref(R &ref, int n_in, const float *W1, const float *b1, const float *W2, const float *b2, const double *scl_in, const double *scl_out,
+                     int form = MW_FORM_STATE) {
   memset(&ref, 0, sizeof(ref));
+  ref.form = form;
   memcpy(ref.W1, W1, sizeof(float) * 10 * n_in); memcpy(ref.b1, b1, sizeof(ref.b1)); memcpy(ref.W2, W2, sizeof(ref.W2)); memcpy(ref.b2, b2, sizeof(ref.b2));
   fill_scaling(n_in, scl_in, scl_out, ref.in_min, ref.in_rng, ref.out_min, ref.out_rng);
 }
@@ -129,13 +134,49 @@ __device__ __forceinline__ double net_out(const NetOut &n, int g, f32x4 d1) {
   if (g != 0) y = fmax(0.0, y);
   return y;
 }
-// the single-cell network on raw inputs: x = field g, x4 = rho_r (used by group 0)
-__device__ __forceinline__ double net5_cell(const Net5 &n, int g, double x, double x4) {
+// the TENDENCY form of the same: the un-scaled output is the change d of output g, added in fp64 to `base`, the cell's own value of the
+// field that output g replaces (temp, rho_v, rho_c, rho_r: input features 0, 2, 3, 4 of the cell's own level), then the clip.  This
+// association, no contraction: y = base + ((double)o * rng + min).
+__device__ __forceinline__ double net_out_tendency(const NetOut &n, int g, f32x4 d1, double base) {
+#pragma clang fp contract(off)
+  const f32x4 d2 = net_layer2(n, leaky(d1[0]), leaky(d1[1]), leaky(d1[2]));
+  const double d = (double)d2[0] * n.orng + n.omin;
+  double y = base + d;
+  if (g != 0) y = fmax(0.0, y);
+  return y;
+}
+// either, by a wave-uniform flag (TEND: a compile-time switch that leaves the state form's code as it is where it is false)
+template <bool TEND> __device__ __forceinline__ double net_out_form(const NetOut &n, int g, f32x4 d1, int form, double base) {
+  if (TEND && form != MW_FORM_STATE) return net_out_tendency(n, g, d1, base);
+  return net_out(n, g, d1);
+}
+// How the single-cell MFMA kernels bring the base to lane groups 1..3.  0: one more 8-byte load per lane, of a line that
+// another group of the wave loads in the same iteration.  1: a 16-lane rotate of what the wave holds already -- group g's base is group
+// g + 1's own field (rho_v, rho_c) and group 3's is group 0's rho_r: lane l takes it from lane (l + 16) & 63, no memory instruction.
+// Measured (13.9): the rotate is the faster one in the forward kernels k_mlp / k_mlp_x2, the load in k_members_apply; the same bits.
+#ifndef MW_TENDENCY_ROTATE_FORWARD
+#define MW_TENDENCY_ROTATE_FORWARD 1
+#endif
+#ifndef MW_TENDENCY_ROTATE_APPLY
+#define MW_TENDENCY_ROTATE_APPLY 0
+#endif
+// x4 of a tendency cell by the rotate: group 0 keeps rho_r, the others receive their base (every lane of the wave must call it)
+__device__ __forceinline__ double net5_rotate_base(int g, double x, double x4) {
+  const double got = __shfl(g == 0 ? x4 : x, (int)((threadIdx.x + 16) & 63), 64);
+  return g == 0 ? x4 : got;
+}
+// layer 1 of the single-cell network on raw inputs: x = field g, x4 = rho_r (used by group 0)
+__device__ __forceinline__ f32x4 net5_layer1(const Net5 &n, int g, double x, double x4) {
   const float b0 = net_scaled(x, n.imin, n.irng);
   const float b1 = (g == 0) ? net_scaled(x4, n.imin4, n.irng4) : 0.f;
   f32x4 d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(n.a10, b0, n.c1, 0, 0, 0);
-  d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(n.a11, b1, d1, 0, 0, 0);
-  return net_out(n, g, d1);
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(n.a11, b1, d1, 0, 0, 0);
+}
+// the single-cell network: the state form, and either form.  x4 is rho_r in group 0 alone, so in the other groups the same register
+// carries the group's base field (rho_v, rho_c, rho_r): group 0's base is x itself.
+__device__ __forceinline__ double net5_cell(const Net5 &n, int g, double x, double x4) { return net_out(n, g, net5_layer1(n, g, x, x4)); }
+template <bool TEND> __device__ __forceinline__ double net5_cell_form(const Net5 &n, int g, double x, double x4, int form) {
+  return net_out_form<TEND>(n, g, net5_layer1(n, g, x, x4), form, g == 0 ? x : x4);
 }
 // the stencil sweep's operands of level k from raw values: field g of level k, of the level above, and this group's latest rho_r -- of
 // level k (feature 4) in group k & 1, of level k + 1 (feature 8) in the other of groups 0 / 1
@@ -155,12 +196,13 @@ __device__ __forceinline__ f32x4 net9_layer1(const Net9 &n, int k, float b0, flo
 // ---- the strict cell: plain fp32 loops in INDEX ORDER, no contraction -- the order in which the layers are defined (Matvec, Bias, Relu,
 // Matvec, Bias; microphysics_kessler_ponni.h:103-110) and in which the CPU restatement accumulates: bit-identical to it.
 //   NIN: 5 or 9; R: an MlpRef / StencilRef lvalue (kernel argument or LDS); in: the features, double[>= NIN]; y0..y3: the four destinations,
-//   written directly (temp as it is, the three water fields clipped at 0).
+//   written directly (temp as it is, the three water fields clipped at 0).  TEND (MW_STRICT_CELL_FORM): a condition, constant or
+//   uniform; where it holds, y = in[base] + (o * rng + min) in fp64 with base = 0, 2, 3, 4, the same clip.  MW_STRICT_CELL is the state form.
 // A macro and not a function on purpose.  A function takes R by reference, and the table of a kernel that gets it as an ARGUMENT then
 // stays an addressable copy until the call is inlined; the optimiser splits that copy into its 156 scalars before it can see that they
 // are kernel-argument loads (k_mlp_stencil_strict: 164 SGPR spills, occupancy 8 -> 7; every other strict kernel scheduled differently).
 // Expanded in place, the cell is the text the kernels always had, and their code stays what it was. ----
-#define MW_STRICT_CELL(NIN, R, in, y0, y1, y2, y3)                                                                              \
+#define MW_STRICT_CELL_FORM(NIN, R, in, TEND, y0, y1, y2, y3)                                                                   \
   {                                                                                                                             \
     _Pragma("clang fp contract(off)")                                                                                           \
     float x_[NIN], h_[10], o_[4];                                                                                               \
@@ -181,10 +223,18 @@ __device__ __forceinline__ f32x4 net9_layer1(const Net9 &n, int k, float b0, flo
       for (int i_ = 0; i_ < 10; i_++) acc += h_[i_] * (R).W2[i_ * 4 + o];                                                       \
       o_[o] = acc + (R).b2[o];                                                                                                  \
     }                                                                                                                           \
-    (y0) =           o_[0] * (R).out_rng[0] + (R).out_min[0];                                          /* :198-201 */           \
-    (y1) = fmax(0.0, o_[1] * (R).out_rng[1] + (R).out_min[1]);                                                                  \
-    (y2) = fmax(0.0, o_[2] * (R).out_rng[2] + (R).out_min[2]);                                                                  \
-    (y3) = fmax(0.0, o_[3] * (R).out_rng[3] + (R).out_min[3]);                                                                  \
+    if (TEND) {                                 /* the tendency form: the cell's own temp, rho_v, rho_c, rho_r + the un-scaled change */ \
+      (y0) =           (in)[0] + (o_[0] * (R).out_rng[0] + (R).out_min[0]);                                                     \
+      (y1) = fmax(0.0, (in)[2] + (o_[1] * (R).out_rng[1] + (R).out_min[1]));                                                    \
+      (y2) = fmax(0.0, (in)[3] + (o_[2] * (R).out_rng[2] + (R).out_min[2]));                                                    \
+      (y3) = fmax(0.0, (in)[4] + (o_[3] * (R).out_rng[3] + (R).out_min[3]));                                                    \
+    } else {                                                                                                                    \
+      (y0) =           o_[0] * (R).out_rng[0] + (R).out_min[0];                                        /* :198-201 */           \
+      (y1) = fmax(0.0, o_[1] * (R).out_rng[1] + (R).out_min[1]);                                                                \
+      (y2) = fmax(0.0, o_[2] * (R).out_rng[2] + (R).out_min[2]);                                                                \
+      (y3) = fmax(0.0, o_[3] * (R).out_rng[3] + (R).out_min[3]);                                                                \
+    }                                                                                                                           \
   }
+#define MW_STRICT_CELL(NIN, R, in, y0, y1, y2, y3) MW_STRICT_CELL_FORM(NIN, R, in, false, y0, y1, y2, y3)
 
 } // namespace mw

@@ -28,6 +28,10 @@ using namespace mw;
 // Reduction: per lane in loop order, an xor tree over the 16 lanes of a group, the block's four waves in order, then
 // k_surrogate_eval_final over the blocks in order -- no floating-point atomics.  grid.x depends on the shape alone and grid.y carries the
 // groups of models, so a model's row does not depend on the size of the bank or on its place in it.
+// ANYT (every kernel of this unit that runs a model): the bank holds a model of the TENDENCY form.  Then a model's form (EvalModel::form /
+// StencilRef::form, uniform over the wave) picks the epilogue per model; a bank of state models alone runs the instantiation without the
+// branch, which is the code these kernels had before there were two forms.  The base of the tendency form is the field output g replaces,
+// which the eval kernels load anyway (`before`).
 // =====================================================================================================
 namespace mw {
 
@@ -106,7 +110,7 @@ __device__ __forceinline__ void eval_load_models(EvalModel (&sm)[G], const EvalM
   __syncthreads();
 }
 
-template <int G, int TILES>
+template <int G, int TILES, bool ANYT>
 __global__ __launch_bounds__(256) void k_surrogate_eval(const EvalModel *__restrict__ bank, int models, long long ncells, EvalFields F,
                                                         double *__restrict__ partial, long long *__restrict__ cpartial) {
 #pragma clang fp contract(off)
@@ -152,7 +156,7 @@ __global__ __launch_bounds__(256) void k_surrogate_eval(const EvalModel *__restr
         net5_ops(N, sm[j], lane, g);
 #pragma unroll
         for (int u = 0; u < TILES; u++) {
-          const double y = net5_cell(N, g, xin[u], xs[u]);
+          const double y = net5_cell_form<ANYT>(N, g, xin[u], xs[u], ANYT ? sm[j].form : MW_FORM_STATE);
           eval_add(acc[j], y, xt[u], inn[u], ina[u]);
         }
       }
@@ -164,7 +168,7 @@ __global__ __launch_bounds__(256) void k_surrogate_eval(const EvalModel *__restr
 // k_mlp_stencil's sweep (a wave owns 16 columns x one z chunk at a time, top-down) with the models inside.  What that kernel carries from
 // level to level as scaled floats -- the level above, the two groups' rho_r -- is carried RAW here and scaled per model with the same
 // expressions: the scaling tables are the models' own.
-template <int G, int U>
+template <int G, int U, bool ANYT>
 __global__ __launch_bounds__(256) void k_surrogate_eval_stencil(const EvalModel *__restrict__ bank, int models, int nz, long long ncol, int zc,
                                                                 int nchunks, EvalFields F, double *__restrict__ partial,
                                                                 long long *__restrict__ cpartial) {
@@ -229,7 +233,7 @@ __global__ __launch_bounds__(256) void k_surrogate_eval_stencil(const EvalModel 
             const int k = k0 - u;
             if (k >= k_lo) {                                              // (wave-uniform)
               const f32x4 d1 = net9_layer1(N, k, net9_b0(N, xin[u]), net9_above(N, xab[u]), net9_b2(N, g, k, xrr[u]));
-              const double y = net_out(N, g, d1);
+              const double y = net_out_form<ANYT>(N, g, d1, ANYT ? sm[j].form : MW_FORM_STATE, xs[u]);
               eval_add(acc[j], y, xt[u], inn[u], ina[u]);
             }
           }
@@ -242,7 +246,7 @@ __global__ __launch_bounds__(256) void k_surrogate_eval_stencil(const EvalModel 
 
 // STRICT form: thread = cell with k_mlp_strict's / k_mlp_stencil_strict's expressions (index order, no contraction, the quotient form of the
 // scaling), grid row y = one model (row `models`: persistence); the reduction scheme is the MFMA kernels'.
-template <int NIN>
+template <int NIN, bool ANYT>
 __global__ __launch_bounds__(256) void k_surrogate_eval_strict(const StencilRef *__restrict__ bank, int models, int nz, long long ncol, EvalFields F,
                                                                double *__restrict__ partial, long long *__restrict__ cpartial) {
 #pragma clang fp contract(off)
@@ -269,7 +273,7 @@ __global__ __launch_bounds__(256) void k_surrogate_eval_strict(const StencilRef 
     for (int v = 0; v < 4; v++) act = act || fabs(tr[v] - before[v]) > 1.e-10;
     double pred[4] = {before[0], before[1], before[2], before[3]};
     if (m < models) {                                                     // (block-uniform)
-      MW_STRICT_CELL(NIN, P, in, pred[0], pred[1], pred[2], pred[3])
+      MW_STRICT_CELL_FORM(NIN, P, in, ANYT && P.form != MW_FORM_STATE, pred[0], pred[1], pred[2], pred[3])
     }
 #pragma unroll
     for (int v = 0; v < 4; v++) eval_add(acc[v], pred[v], tr[v], !act, act);
@@ -323,7 +327,12 @@ struct mw_surrogate_bank_s {
   double *partial;            // DEVICE (blocks, models + 1, 32), grown on demand
   long long partial_blocks;
   long long *cpartial;        // DEVICE (EVAL_MAX_BLOCKS)
+  std::vector<int> forms;     // HOST (models): MW_FORM_* per model, as the images and refs carry it
+  bool any_tendency;          // some model is of the tendency form: the kernels' ANYT
 };
+
+// launches the first kernel where the condition holds, else the second (a kernel template's two instantiations, each in parentheses)
+#define MW_LAUNCH_ANYT(cond, KT, KF, ...) do { if (cond) hipLaunchKernelGGL(KT, __VA_ARGS__); else hipLaunchKernelGGL(KF, __VA_ARGS__); } while (0)
 
 extern "C" void mw_surrogate_bank_destroy(mw_surrogate_bank_t b) {
   if (!b) return;
@@ -331,8 +340,8 @@ extern "C" void mw_surrogate_bank_destroy(mw_surrogate_bank_t b) {
   delete b;
 }
 
-extern "C" int mw_surrogate_bank_create(mw_surrogate_bank_t *out, int n_in, int models, const float *params, const double *scl_in,
-                                        const double *scl_out) {
+extern "C" int mw_surrogate_bank_create_forms(mw_surrogate_bank_t *out, int n_in, int models, const float *params, const double *scl_in,
+                                              const double *scl_out, const int *forms) {
   if (!out) MW_FAIL("surrogate_bank_create: null pointer");
   *out = nullptr;
   if (n_in != 5 && n_in != 9) MW_FAIL("surrogate_bank_create: n_in must be 5 (single cell) or 9 (stencil), got " + std::to_string(n_in));
@@ -344,6 +353,8 @@ extern "C" int mw_surrogate_bank_create(mw_surrogate_bank_t *out, int n_in, int 
     for (int i = 0; i < 4; i++) if (scl_out[(m * 4 + i) * 2 + 1] == scl_out[(m * 4 + i) * 2])
       MW_FAIL("surrogate_bank_create: model " + std::to_string(m) + ", output scaling row " + std::to_string(i) + " has max == min");
   }
+  if (forms) for (int m = 0; m < models; m++) if (forms[m] != MW_FORM_STATE && forms[m] != MW_FORM_TENDENCY)
+    MW_FAIL("surrogate_bank_create: model " + std::to_string(m) + ": form must be MW_FORM_STATE (0) or MW_FORM_TENDENCY (1), got " + std::to_string(forms[m]));
   if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
   const int npar = 10 * n_in + 54;
   std::vector<EvalModel> img((size_t)models);
@@ -357,9 +368,13 @@ extern "C" int mw_surrogate_bank_create(mw_surrogate_bank_t *out, int n_in, int 
     else           net_stencil_layer1_images(E.a1, W1);
     net_layer2_images(E.c1, E.a2, E.c2, b1, W2, b2);
     fill_scaling(n_in, si, so, E.in_min, E.in_irng, E.out_min, E.out_rng);      // in_irng: the range; k_surrogate_bank_recip inverts it below
-    fill_ref(ref[m], n_in, W1, b1, W2, b2, si, so);
+    E.form = forms ? forms[m] : MW_FORM_STATE;
+    fill_ref(ref[m], n_in, W1, b1, W2, b2, si, so, E.form);
   }
   mw_surrogate_bank_t b = new mw_surrogate_bank_s();
+  b->forms.assign((size_t)models, MW_FORM_STATE);
+  if (forms) b->forms.assign(forms, forms + models);
+  b->any_tendency = std::find(b->forms.begin(), b->forms.end(), (int)MW_FORM_TENDENCY) != b->forms.end();
   b->n_in = n_in; b->models = models; b->images = nullptr; b->refs = nullptr; b->partial = nullptr; b->partial_blocks = 0; b->cpartial = nullptr;
   hipError_t e = hipMalloc(&b->images, sizeof(EvalModel) * (size_t)models);
   if (e == hipSuccess) e = hipMalloc(&b->refs, sizeof(StencilRef) * (size_t)models);
@@ -371,6 +386,17 @@ extern "C" int mw_surrogate_bank_create(mw_surrogate_bank_t *out, int n_in, int 
   if (e != hipSuccess) { mw_surrogate_bank_destroy(b); MW_FAIL(std::string("surrogate_bank_create: ") + hipGetErrorString(e)); }
   *out = b;
   return 0;
+}
+
+extern "C" int mw_surrogate_bank_create(mw_surrogate_bank_t *out, int n_in, int models, const float *params, const double *scl_in,
+                                        const double *scl_out) {
+  return mw_surrogate_bank_create_forms(out, n_in, models, params, scl_in, scl_out, nullptr);
+}
+
+extern "C" int mw_surrogate_bank_form(mw_surrogate_bank_t b, int model) {
+  if (!b) { mw::set_error("surrogate_bank_form: null handle"); return -1; }
+  if (model < 0 || model >= b->models) { mw::set_error("surrogate_bank_form: model " + std::to_string(model) + " is outside the bank's [0, " + std::to_string(b->models) + ")"); return -1; }
+  return b->forms[(size_t)model];
 }
 
 extern "C" int mw_surrogate_eval_group(mw_surrogate_bank_t b) {
@@ -404,14 +430,15 @@ extern "C" int mw_surrogate_eval(mw_surrogate_bank_t b, int nz, long long ncol, 
   }
   if (mlp_strict()) {
     const dim3 grid((unsigned)blocks, (unsigned)rows);
-    if (b->n_in == 5) hipLaunchKernelGGL(k_surrogate_eval_strict<5>, grid, dim3(256), 0, st, b->refs, models, nz, ncol, F, b->partial, b->cpartial);
-    else              hipLaunchKernelGGL(k_surrogate_eval_strict<9>, grid, dim3(256), 0, st, b->refs, models, nz, ncol, F, b->partial, b->cpartial);
+    if (b->n_in == 5) MW_LAUNCH_ANYT(b->any_tendency, (k_surrogate_eval_strict<5, true>), (k_surrogate_eval_strict<5, false>), grid, dim3(256), 0, st, b->refs, models, nz, ncol, F, b->partial, b->cpartial);
+    else              MW_LAUNCH_ANYT(b->any_tendency, (k_surrogate_eval_strict<9, true>), (k_surrogate_eval_strict<9, false>), grid, dim3(256), 0, st, b->refs, models, nz, ncol, F, b->partial, b->cpartial);
   } else {
     const int G = b->n_in == 5 ? EVAL_G5 : EVAL_G9;
     const dim3 grid((unsigned)blocks, (unsigned)((models + G - 1) / G));
-    if (b->n_in == 5) hipLaunchKernelGGL((k_surrogate_eval<EVAL_G5, TILES>), grid, dim3(256), 0, st, b->images, models, ncells, F, b->partial, b->cpartial);
-    else              hipLaunchKernelGGL((k_surrogate_eval_stencil<EVAL_G9, U>), grid, dim3(256), 0, st, b->images, models, nz, ncol, zc, nchunks, F,
-                                         b->partial, b->cpartial);
+    if (b->n_in == 5) MW_LAUNCH_ANYT(b->any_tendency, (k_surrogate_eval<EVAL_G5, TILES, true>), (k_surrogate_eval<EVAL_G5, TILES, false>), grid, dim3(256), 0, st, b->images, models, ncells, F, b->partial,
+                                     b->cpartial);
+    else              MW_LAUNCH_ANYT(b->any_tendency, (k_surrogate_eval_stencil<EVAL_G9, U, true>), (k_surrogate_eval_stencil<EVAL_G9, U, false>), grid, dim3(256), 0, st, b->images, models, nz, ncol, zc, nchunks, F,
+                                     b->partial, b->cpartial);
   }
   MW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_surrogate_eval_final, dim3((unsigned)((rows * EVAL_ROW + 255) / 256)), dim3(256), 0, st, (int)blocks, rows, ncells,
@@ -449,7 +476,9 @@ __device__ __forceinline__ void apply_slot(int models, int &j, int &slot, int &s
 }
 static int apply_mpb(int models) { return models >= 3 ? 4 : models; }
 
-template <int TILES>
+// ANYT and a model of the tendency form: lane group g > 0 also loads the field its output replaces -- the one it stores to -- in the register
+// that only group 0 uses for rho_r (stencil: one more register per level), with the tile's other loads and ahead of its stores.
+template <int TILES, bool ANYT>
 __global__ __launch_bounds__(256) void k_members_apply(const EvalModel *__restrict__ bank, int models, ApplyMap map, long long ncells, int nens,
                                                        ApplyFields F) {
 #pragma clang fp contract(off)
@@ -462,7 +491,10 @@ __global__ __launch_bounds__(256) void k_members_apply(const EvalModel *__restri
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4, cidx = lane & 15;
   const int e = map.member[j];
-  const double *in_g = F.f[g], *rho_r = F.f[4];
+  const int form = ANYT ? sm[j - m0].form : MW_FORM_STATE;               // (wave-uniform)
+  const bool tend = ANYT && form != MW_FORM_STATE;
+  const bool loadb = tend && !MW_TENDENCY_ROTATE_APPLY;                         // the base of groups 1..3 by a load (else, tend: by the rotate)
+  const double *in_g = F.f[g], *rho_r = F.f[(loadb && g != 0) ? g + 1 : 4];  // (loadb: group g > 0 reads its base here)
   double *out_g = F.f[g == 0 ? 0 : g + 1];
   Net5 N;
   net5_ops(N, sm[j - m0], lane, g);
@@ -474,19 +506,20 @@ __global__ __launch_bounds__(256) void k_members_apply(const EvalModel *__restri
       const long long cell = (t0 + u) * 16 + cidx;
       const bool ok = cell < ncells;
       xin[u]  = ok ? in_g[cell * nens + e] : N.imin;
-      xin4[u] = (ok && g == 0) ? rho_r[cell * nens + e] : N.imin4;
+      xin4[u] = (ok && (loadb || g == 0)) ? rho_r[cell * nens + e] : N.imin4;
     }
 #pragma unroll
     for (int u = 0; u < TILES; u++) {
       const long long cell = (t0 + u) * 16 + cidx;
-      const double y = net5_cell(N, g, xin[u], xin4[u]);
+      if (tend && !loadb) xin4[u] = net5_rotate_base(g, xin[u], xin4[u]);    // (wave-uniform: every lane calls it)
+      const double y = net5_cell_form<ANYT>(N, g, xin[u], xin4[u], form);
       if (cell < ncells) out_g[cell * nens + e] = y;
     }
   }
 }
 
 // k_mlp_stencil's sweep with one chunk per column: a wave owns 16 columns of one member, all nz levels
-template <int U>
+template <int U, bool ANYT>
 __global__ __launch_bounds__(256) void k_members_apply_stencil(const EvalModel *__restrict__ bank, int models, ApplyMap map, int nz, long long ncol,
                                                                int nens, ApplyFields F) {
 #pragma clang fp contract(off)
@@ -499,6 +532,8 @@ __global__ __launch_bounds__(256) void k_members_apply_stencil(const EvalModel *
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4, cidx = lane & 15;
   const int e = map.member[j];
+  const int form = ANYT ? sm[j - m0].form : MW_FORM_STATE;               // (wave-uniform)
+  const bool tend = ANYT && form != MW_FORM_STATE;
   const double *in_g = F.f[g], *rho_r = F.f[4];
   double *out_g = F.f[g == 0 ? 0 : g + 1];
   Net9 N;
@@ -516,13 +551,14 @@ __global__ __launch_bounds__(256) void k_members_apply_stencil(const EvalModel *
       if (g == ((k_hi & 1) ^ 1)) rr_raw = rho_r[(long long)k_hi * lev + base];
     }
     for (int k0 = k_hi; k0 >= 0; k0 -= U) {
-      double xin[U], xrr[U];
+      double xin[U], xrr[U], xs[U];
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const int k = k0 - u;
         const bool lv = ok && k >= 0;
         xin[u] = lv ? in_g[(long long)k * lev + base] : N.imin;
         xrr[u] = (lv && g == (k & 1)) ? rho_r[(long long)k * lev + base] : N.rmin;
+        if (ANYT) xs[u] = (lv && tend && g != 0) ? out_g[(long long)k * lev + base] : xin[u];      // level k's own value of the field output g replaces
       }
 #pragma unroll
       for (int u = 0; u < U; u++) {
@@ -531,7 +567,7 @@ __global__ __launch_bounds__(256) void k_members_apply_stencil(const EvalModel *
           if (g == (k & 1)) rr_raw = xrr[u];
           const f32x4 d1 = net9_layer1(N, k, net9_b0(N, xin[u]), above, net9_b2(N, g, k, rr_raw));
           above = net9_above(N, xin[u]);                                  // level k is level k - 1's level above
-          const double y = net_out(N, g, d1);
+          const double y = net_out_form<ANYT>(N, g, d1, form, ANYT ? xs[u] : 0.0);
           if (ok) out_g[(long long)k * lev + base] = y;
         }
       }
@@ -541,7 +577,7 @@ __global__ __launch_bounds__(256) void k_members_apply_stencil(const EvalModel *
 
 // STRICT form: thread = one column of one member, swept top-down with the level above in registers (in place for the same reason);
 // k_mlp_strict's / k_mlp_stencil_strict's expressions, grid row y = one model, its weights from LDS as in k_surrogate_eval_strict.
-template <int NIN>
+template <int NIN, bool ANYT>
 __global__ __launch_bounds__(256) void k_members_apply_strict(const StencilRef *__restrict__ bank, ApplyMap map, int nz, long long ncol, int nens,
                                                               ApplyFields F) {
 #pragma clang fp contract(off)
@@ -559,7 +595,7 @@ __global__ __launch_bounds__(256) void k_members_apply_strict(const StencilRef *
       if (k == nz - 1) { ab[0] = in[0]; ab[1] = in[2]; ab[2] = in[3]; ab[3] = in[4]; }
       if (NIN == 9) { in[5] = ab[0]; in[6] = ab[1]; in[7] = ab[2]; in[8] = ab[3]; }
       ab[0] = in[0]; ab[1] = in[2]; ab[2] = in[3]; ab[3] = in[4];
-      MW_STRICT_CELL(NIN, P, in, F.f[0][c], F.f[2][c], F.f[3][c], F.f[4][c])
+      MW_STRICT_CELL_FORM(NIN, P, in, ANYT && P.form != MW_FORM_STATE, F.f[0][c], F.f[2][c], F.f[3][c], F.f[4][c])
     }
   }
 }
@@ -590,8 +626,8 @@ extern "C" int mw_surrogate_members_apply(mw_surrogate_bank_t b, const int *memb
   if (mlp_strict()) {
     const long long blocks = std::max<long long>(1, std::min<long long>((ncol + 255) / 256, APPLY_MAX_BLOCKS));
     const dim3 grid((unsigned)blocks, (unsigned)models);
-    if (b->n_in == 5) hipLaunchKernelGGL(k_members_apply_strict<5>, grid, dim3(256), 0, st, b->refs, map, nz, ncol, nens, F);
-    else              hipLaunchKernelGGL(k_members_apply_strict<9>, grid, dim3(256), 0, st, b->refs, map, nz, ncol, nens, F);
+    if (b->n_in == 5) MW_LAUNCH_ANYT(b->any_tendency, (k_members_apply_strict<5, true>), (k_members_apply_strict<5, false>), grid, dim3(256), 0, st, b->refs, map, nz, ncol, nens, F);
+    else              MW_LAUNCH_ANYT(b->any_tendency, (k_members_apply_strict<9, true>), (k_members_apply_strict<9, false>), grid, dim3(256), 0, st, b->refs, map, nz, ncol, nens, F);
     MW_LAUNCH_CHECK();
     return 0;
   }
@@ -601,11 +637,11 @@ extern "C" int mw_surrogate_members_apply(mw_surrogate_bank_t b, const int *memb
   if (b->n_in == 5) {
     const long long groups = ((ncells + 15) / 16 + TILES - 1) / TILES;
     const long long blocks = std::max<long long>(1, std::min<long long>((groups + slots - 1) / slots, APPLY_MAX_BLOCKS));
-    hipLaunchKernelGGL(k_members_apply<TILES>, dim3((unsigned)blocks, gy), dim3(256), 0, st, b->images, models, map, ncells, nens, F);
+    MW_LAUNCH_ANYT(b->any_tendency, (k_members_apply<TILES, true>), (k_members_apply<TILES, false>), dim3((unsigned)blocks, gy), dim3(256), 0, st, b->images, models, map, ncells, nens, F);
   } else {
     const long long tiles = (ncol + 15) / 16;
     const long long blocks = std::max<long long>(1, std::min<long long>((tiles + slots - 1) / slots, APPLY_MAX_BLOCKS));
-    hipLaunchKernelGGL(k_members_apply_stencil<U>, dim3((unsigned)blocks, gy), dim3(256), 0, st, b->images, models, map, nz, ncol, nens, F);
+    MW_LAUNCH_ANYT(b->any_tendency, (k_members_apply_stencil<U, true>), (k_members_apply_stencil<U, false>), dim3((unsigned)blocks, gy), dim3(256), 0, st, b->images, models, map, nz, ncol, nens, F);
   }
   MW_LAUNCH_CHECK();
   return 0;
@@ -636,7 +672,8 @@ __device__ __forceinline__ void committee_load(T *sm, const T *__restrict__ bank
   __syncthreads();
 }
 
-template <int TILES>
+// ANYT (some selected model is of the tendency form): the base is loaded once per cell, raw, for all models (k_members_apply's scheme)
+template <int TILES, bool ANYT>
 __global__ __launch_bounds__(256) void k_committee_apply(const EvalModel *__restrict__ bank, CommitteeSel S, int member, long long ncells, int nens,
                                                          CommitteeFields F) {
 #pragma clang fp contract(off)
@@ -646,7 +683,7 @@ __global__ __launch_bounds__(256) void k_committee_apply(const EvalModel *__rest
   const int g = lane >> 4, cidx = lane & 15;
   const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
   const long long nwaves = ((long long)gridDim.x * 256) >> 6;
-  const double *in_g = F.in[g], *rho_r = F.in[4];
+  const double *in_g = F.in[g], *rho_r = F.in[(ANYT && g != 0) ? g + 1 : 4];   // (ANYT: group g > 0 reads its base here)
   double *out_g = F.out[g], *rng_g = F.range[g];
   const double dn = (double)S.n;
   const long long ntiles = (ncells + 15) / 16;
@@ -657,7 +694,7 @@ __global__ __launch_bounds__(256) void k_committee_apply(const EvalModel *__rest
       const long long cell = (t0 + u) * 16 + cidx;
       const bool ok = cell < ncells;
       xin[u]  = ok ? in_g[cell * nens + member] : 0.0;
-      xin4[u] = (ok && g == 0) ? rho_r[cell * nens + member] : 0.0;
+      xin4[u] = (ok && (ANYT || g == 0)) ? rho_r[cell * nens + member] : 0.0;
       sum[u] = hi[u] = lo[u] = 0.0;
     }
     for (int j = 0; j < S.n; j++) {
@@ -665,7 +702,7 @@ __global__ __launch_bounds__(256) void k_committee_apply(const EvalModel *__rest
       net5_ops(N, sm[j], lane, g);
 #pragma unroll
       for (int u = 0; u < TILES; u++) {
-        const double y = net5_cell(N, g, xin[u], xin4[u]);
+        const double y = net5_cell_form<ANYT>(N, g, xin[u], xin4[u], ANYT ? sm[j].form : MW_FORM_STATE);
         sum[u] = j == 0 ? y : sum[u] + y;                                   // (the first addend as it is: a committee of one keeps its bits)
         hi[u]  = j == 0 ? y : eval_max(hi[u], y);
         lo[u]  = j == 0 ? y : eval_min(lo[u], y);
@@ -683,7 +720,7 @@ __global__ __launch_bounds__(256) void k_committee_apply(const EvalModel *__rest
 }
 
 // k_members_apply_stencil's sweep (a wave owns 16 columns of the member, all nz levels, top-down) with the models inside
-template <int U>
+template <int U, bool ANYT>
 __global__ __launch_bounds__(256) void k_committee_apply_stencil(const EvalModel *__restrict__ bank, CommitteeSel S, int member, int nz, long long ncol,
                                                                  int nens, CommitteeFields F) {
 #pragma clang fp contract(off)
@@ -693,7 +730,7 @@ __global__ __launch_bounds__(256) void k_committee_apply_stencil(const EvalModel
   const int g = lane >> 4, cidx = lane & 15;
   const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
   const long long nwaves = ((long long)gridDim.x * 256) >> 6;
-  const double *in_g = F.in[g], *rho_r = F.in[4];
+  const double *in_g = F.in[g], *rho_r = F.in[4], *in_s = F.in[g == 0 ? 0 : g + 1];
   double *out_g = F.out[g], *rng_g = F.range[g];
   const double dn = (double)S.n;
   const long long ntiles = (ncol + 15) / 16, lev = ncol * nens;           // lev: doubles from level k to level k + 1
@@ -708,13 +745,14 @@ __global__ __launch_bounds__(256) void k_committee_apply_stencil(const EvalModel
       if (g == ((k_hi & 1) ^ 1)) rr = rho_r[(long long)k_hi * lev + base];
     }
     for (int k0 = k_hi; k0 >= 0; k0 -= U) {
-      double xin[U], xab[U], xrr[U], sum[U], hi[U], lo[U];
+      double xin[U], xab[U], xrr[U], xs[U], sum[U], hi[U], lo[U];
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const int k = k0 - u;
         const bool lv = ok && k >= 0;
         xin[u] = lv ? in_g[(long long)k * lev + base] : 0.0;
         xrr[u] = (lv && g == (k & 1)) ? rho_r[(long long)k * lev + base] : 0.0;
+        if (ANYT) xs[u] = (lv && g != 0) ? in_s[(long long)k * lev + base] : xin[u];                // level k's own value of the field output g replaces
         sum[u] = hi[u] = lo[u] = 0.0;
       }
 #pragma unroll
@@ -733,7 +771,7 @@ __global__ __launch_bounds__(256) void k_committee_apply_stencil(const EvalModel
           const int k = k0 - u;
           if (k >= 0) {                                                   // (wave-uniform)
             const f32x4 d1 = net9_layer1(N, k, net9_b0(N, xin[u]), net9_above(N, xab[u]), net9_b2(N, g, k, xrr[u]));
-            const double y = net_out(N, g, d1);
+            const double y = net_out_form<ANYT>(N, g, d1, ANYT ? sm[j].form : MW_FORM_STATE, ANYT ? xs[u] : 0.0);
             sum[u] = j == 0 ? y : sum[u] + y;
             hi[u]  = j == 0 ? y : eval_max(hi[u], y);
             lo[u]  = j == 0 ? y : eval_min(lo[u], y);
@@ -754,7 +792,7 @@ __global__ __launch_bounds__(256) void k_committee_apply_stencil(const EvalModel
 
 // STRICT form: thread = one column of the member, swept top-down with the level above in registers (k_members_apply_strict), the models
 // inside the level loop, their weights from LDS; k_mlp_strict's / k_mlp_stencil_strict's expressions.
-template <int NIN>
+template <int NIN, bool ANYT>
 __global__ __launch_bounds__(256) void k_committee_apply_strict(const StencilRef *__restrict__ bank, CommitteeSel S, int member, int nz, long long ncol,
                                                                 int nens, CommitteeFields F) {
 #pragma clang fp contract(off)
@@ -774,7 +812,7 @@ __global__ __launch_bounds__(256) void k_committee_apply_strict(const StencilRef
       double sum[4], hi[4], lo[4];
       for (int j = 0; j < S.n; j++) {
         double p[4];
-        MW_STRICT_CELL(NIN, sm[j], in, p[0], p[1], p[2], p[3])
+        MW_STRICT_CELL_FORM(NIN, sm[j], in, ANYT && sm[j].form != MW_FORM_STATE, p[0], p[1], p[2], p[3])
 #pragma unroll
         for (int v = 0; v < 4; v++) {
           sum[v] = j == 0 ? p[v] : sum[v] + p[v];
@@ -919,10 +957,12 @@ extern "C" int mw_surrogate_committee_apply(mw_surrogate_bank_t b, int n_sel, co
   if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
   hipStream_t st = (hipStream_t)stream;
   const long long ncells = (long long)nz * ncol;
+  bool anyt = false;                                                       // ANYT of this call: a selected model of the tendency form
+  for (int j = 0; j < n_sel; j++) anyt = anyt || b->forms[(size_t)sel[j]] != MW_FORM_STATE;
   if (mlp_strict()) {
     const long long blocks = std::max<long long>(1, std::min<long long>((ncol + 255) / 256, APPLY_MAX_BLOCKS));
-    if (b->n_in == 5) hipLaunchKernelGGL(k_committee_apply_strict<5>, dim3((unsigned)blocks), dim3(256), 0, st, b->refs, S, member, nz, ncol, nens, F);
-    else              hipLaunchKernelGGL(k_committee_apply_strict<9>, dim3((unsigned)blocks), dim3(256), 0, st, b->refs, S, member, nz, ncol, nens, F);
+    if (b->n_in == 5) MW_LAUNCH_ANYT(anyt, (k_committee_apply_strict<5, true>), (k_committee_apply_strict<5, false>), dim3((unsigned)blocks), dim3(256), 0, st, b->refs, S, member, nz, ncol, nens, F);
+    else              MW_LAUNCH_ANYT(anyt, (k_committee_apply_strict<9, true>), (k_committee_apply_strict<9, false>), dim3((unsigned)blocks), dim3(256), 0, st, b->refs, S, member, nz, ncol, nens, F);
     MW_LAUNCH_CHECK();
     return 0;
   }
@@ -930,11 +970,11 @@ extern "C" int mw_surrogate_committee_apply(mw_surrogate_bank_t b, int n_sel, co
   if (b->n_in == 5) {
     const long long groups = ((ncells + 15) / 16 + TILES - 1) / TILES;
     const long long blocks = std::max<long long>(1, std::min<long long>((groups + 3) / 4, APPLY_MAX_BLOCKS));
-    hipLaunchKernelGGL(k_committee_apply<TILES>, dim3((unsigned)blocks), dim3(256), 0, st, b->images, S, member, ncells, nens, F);
+    MW_LAUNCH_ANYT(anyt, (k_committee_apply<TILES, true>), (k_committee_apply<TILES, false>), dim3((unsigned)blocks), dim3(256), 0, st, b->images, S, member, ncells, nens, F);
   } else {
     const long long tiles = (ncol + 15) / 16;
     const long long blocks = std::max<long long>(1, std::min<long long>((tiles + 3) / 4, APPLY_MAX_BLOCKS));
-    hipLaunchKernelGGL(k_committee_apply_stencil<U>, dim3((unsigned)blocks), dim3(256), 0, st, b->images, S, member, nz, ncol, nens, F);
+    MW_LAUNCH_ANYT(anyt, (k_committee_apply_stencil<U, true>), (k_committee_apply_stencil<U, false>), dim3((unsigned)blocks), dim3(256), 0, st, b->images, S, member, nz, ncol, nens, F);
   }
   MW_LAUNCH_CHECK();
   return 0;

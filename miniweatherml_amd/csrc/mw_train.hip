@@ -347,8 +347,10 @@ struct PrepArgs {
   double in_min[9], in_rng[9], out_min[4], out_rng[4];
   float *x[3], *y[3];
 };
-template <int NIN>
+// TEND: the labels of the tendency form -- the sample's change, fp64 difference of the two fp32 records, scaled by the table of the changes
+template <int NIN, bool TEND>
 __global__ __launch_bounds__(TPB) void k_surrogate_prepare(PrepArgs a) {
+#pragma clang fp contract(off)
   const long long stride = (long long)gridDim.x * TPB;
   for (long long p = (long long)blockIdx.x * TPB + threadIdx.x; p < a.n; p += stride) {
     const long long src = feistel_index(a.F, p);
@@ -358,7 +360,11 @@ __global__ __launch_bounds__(TPB) void k_surrogate_prepare(PrepArgs a) {
 #pragma unroll
     for (int f = 0; f < NIN; f++) a.x[set][f * len + q] = (float)(((double)a.raw_in[src * NIN + f] - a.in_min[f]) / a.in_rng[f]);
 #pragma unroll
-    for (int o = 0; o < 4; o++) a.y[set][o * len + q] = (float)(((double)a.raw_out[src * 4 + o] - a.out_min[o]) / a.out_rng[o]);
+    for (int o = 0; o < 4; o++) {
+      const int base = o == 0 ? 0 : o + 1;                                  // temp, rho_v, rho_c, rho_r among the inputs
+      if (TEND) a.y[set][o * len + q] = (float)((((double)a.raw_out[src * 4 + o] - (double)a.raw_in[src * NIN + base]) - a.out_min[o]) / a.out_rng[o]);
+      else      a.y[set][o * len + q] = (float)(((double)a.raw_out[src * 4 + o] - a.out_min[o]) / a.out_rng[o]);
+    }
   }
 }
 
@@ -412,9 +418,11 @@ static int check_n_in(int n_in, const char *who) {
   return 0;
 }
 
-int mw_surrogate_prepare_v2(int n_in, long long n, const float *raw_in, const float *raw_out, const double *scl_in, const double *scl_out,
-                            unsigned long long seed, long long n_train, long long n_val, float *train_x, float *train_y, float *val_x,
-                            float *val_y, float *test_x, float *test_y, void *stream) {
+int mw_surrogate_prepare_form(int form, int n_in, long long n, const float *raw_in, const float *raw_out, const double *scl_in,
+                              const double *scl_out, unsigned long long seed, long long n_train, long long n_val, float *train_x,
+                              float *train_y, float *val_x, float *val_y, float *test_x, float *test_y, void *stream) {
+  if (form != MW_FORM_STATE && form != MW_FORM_TENDENCY)
+    MW_FAIL("surrogate_prepare: form must be MW_FORM_STATE (0) or MW_FORM_TENDENCY (1), got " + std::to_string(form));
   if (check_n_in(n_in, "surrogate_prepare")) return 1;
   if (!raw_in || !raw_out || !scl_in || !scl_out || !train_x || !train_y || !val_x || !val_y || !test_x || !test_y)
     MW_FAIL("surrogate_prepare: null argument");
@@ -430,10 +438,24 @@ int mw_surrogate_prepare_v2(int n_in, long long n, const float *raw_in, const fl
   a.raw_in = raw_in; a.raw_out = raw_out;
   a.x[0] = train_x; a.y[0] = train_y; a.x[1] = val_x; a.y[1] = val_y; a.x[2] = test_x; a.y[2] = test_y;
   const long long blocks = std::max(1ll, std::min((n + TPB - 1) / TPB, 256ll * 16));
-  if (n_in == 5) hipLaunchKernelGGL(k_surrogate_prepare<5>, dim3((unsigned)blocks), dim3(TPB), 0, (hipStream_t)stream, a);
-  else           hipLaunchKernelGGL(k_surrogate_prepare<9>, dim3((unsigned)blocks), dim3(TPB), 0, (hipStream_t)stream, a);
+  const dim3 grid((unsigned)blocks), tpb(TPB);
+  hipStream_t st = (hipStream_t)stream;
+  if (form == MW_FORM_TENDENCY) {
+    if (n_in == 5) hipLaunchKernelGGL((k_surrogate_prepare<5, true>), grid, tpb, 0, st, a);
+    else           hipLaunchKernelGGL((k_surrogate_prepare<9, true>), grid, tpb, 0, st, a);
+  } else {
+    if (n_in == 5) hipLaunchKernelGGL((k_surrogate_prepare<5, false>), grid, tpb, 0, st, a);
+    else           hipLaunchKernelGGL((k_surrogate_prepare<9, false>), grid, tpb, 0, st, a);
+  }
   MW_LAUNCH_CHECK();
   return 0;
+}
+
+int mw_surrogate_prepare_v2(int n_in, long long n, const float *raw_in, const float *raw_out, const double *scl_in, const double *scl_out,
+                            unsigned long long seed, long long n_train, long long n_val, float *train_x, float *train_y, float *val_x,
+                            float *val_y, float *test_x, float *test_y, void *stream) {
+  return mw_surrogate_prepare_form(MW_FORM_STATE, n_in, n, raw_in, raw_out, scl_in, scl_out, seed, n_train, n_val, train_x, train_y, val_x, val_y,
+                                   test_x, test_y, stream);
 }
 
 int mw_surrogate_prepare(long long n, const float *raw_in, const float *raw_out, const double *scl_in, const double *scl_out,

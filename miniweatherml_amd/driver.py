@@ -427,6 +427,10 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                 kw[k_arg] = p if p and os.path.exists(p) else None             # else: the shipped tables
             if "_committee" not in cfg:
                 micro.init(coupler, **kw)
+            # the form travels with the files: the single model's, or every committee model's
+            info["surrogate_form"] = micro._committee.forms if "_committee" in cfg else micro.form
+            if "tendency" in info["surrogate_form"] and not quiet and coupler.is_mainproc():     # (a state model prints what it always did)
+                print("inference_ponni: surrogate output form: %s" % info["surrogate_form"], flush=True)
         elif experiment == "rollout_surrogates":
             micro = rollout.Microphysics_Rollout()
             micro.init(coupler, mlp.load_surrogate_bank(cfg["surrogate_models"]), cfg["persistence_member"],
@@ -525,8 +529,8 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
             import json
             rep = evaluator.report() if eval_calls else {}
             doc = {"experiment": experiment, "yaml": os.path.abspath(yaml_path), "eval_interval": cfg["eval_interval"], "steps": steps,
-                   "models": [dict(m, bank=ib, n_in=b.n_in) for ib, b in enumerate(evaluator.banks)
-                              for m in eval_models[sum(x.models for x in evaluator.banks[:ib]):][:b.models]],
+                   "models": [dict(m, bank=ib, n_in=b.n_in, form=b.forms[k]) for ib, b in enumerate(evaluator.banks)
+                              for k, m in enumerate(eval_models[sum(x.models for x in evaluator.banks[:ib]):][:b.models])],
                    "statistics": ["sum_d", "sum_abs_d", "sum_d2", "max_abs_d"], "fields": list(surrogate_eval.EVAL_FIELDS),
                    "classes": list(surrogate_eval.EVAL_CLASSES), "report": rep,
                    "history": [dict(c, banks=h) for c, h in zip(eval_calls, evaluator.history)]}
@@ -546,7 +550,7 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
             import json
             rep = scorer.report() if scorer.times else {"times": [], "diverged_at": dict(scorer.diverged_at)}
             doc = {"experiment": experiment, "yaml": os.path.abspath(yaml_path), "eval_interval": cfg["eval_interval"], "steps": steps,
-                   "members": list(scorer.member_names), "models": [dict(m, member=1 + k) for k, m in enumerate(cfg["surrogate_models"])],
+                   "members": list(scorer.member_names), "models": [dict(m, member=1 + k, form=micro.model_forms[k]) for k, m in enumerate(cfg["surrogate_models"])],
                    "fields": list(scorer.fields), "statistics": list(rollout.ROLLOUT_STATS), "history": scorer.history,
                    "report": rep["times"], "diverged_at": rep["diverged_at"]}
             if committees:

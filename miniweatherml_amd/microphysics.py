@@ -12,7 +12,7 @@ from . import capi
 from ._ffi import _field_ptr_array, _ptr, _stream_ptr, grown_workspace
 from .capi import check
 from .coupler import endrun
-from .mlp import OUT4, load_surrogate_weights, mlp_forward, mlp_stencil_forward
+from .mlp import OUT4, as_surrogate_model, load_surrogate_model, mlp_forward, mlp_stencil_forward
 from .surrogate_eval import SurrogateBank
 
 
@@ -106,7 +106,9 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
     surface_rain = False  # True (with online only): precl after the step is the column water budget of the state left in the coupler
 
     def init(self, coupler, weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None, committee=None, guard=None):
-        """committee: a list of 1 .. 16 (W1, b1, W2, b2, scl_in, scl_out) tuples of one width (load_surrogate_weights' form).  The network's
+        """Single-model files: the model's output form is the one its output scaling file declares (self.form: "state" | "tendency";
+        mlp.load_surrogate_model).  committee: a list of 1 .. 16 (W1, b1, W2, b2, scl_in, scl_out) tuples of one width (load_surrogate_weights'
+        form, the state form) or SurrogateModel tuples with the form last; a committee may mix the forms.  The network's
         result is then the committee's mean (SurrogateBank.committee_apply), and the weight file arguments are not read.  guard
         (surrogate_eval.guard_config's mapping; with a committee only): the result is the GUARDED committee's step of the state before the
         call -- the mean, and on the columns where the models' range exceeds a threshold what Kessler leaves on those columns alone."""
@@ -126,10 +128,10 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
             if not 1 <= len(committee) <= capi.MW_COMMITTEE_MAX_MODELS:
                 endrun("Microphysics_Kessler_Surrogate: a committee has 1 to %d models, got %d" % (capi.MW_COMMITTEE_MAX_MODELS, len(committee)))
             self._committee = SurrogateBank(committee, coupler.device)
-            self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out = committee[0]
+            self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out, self.form = as_surrogate_model(committee[0])
             return
-        self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out = load_surrogate_weights(weights_txt, in_scaling_txt,
-                                                                                              out_scaling_txt, weights_h5)
+        self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out, self.form = load_surrogate_model(weights_txt, in_scaling_txt,
+                                                                                                        out_scaling_txt, weights_h5)
 
     def time_step(self, coupler, dt):
         dm = coupler.get_data_manager_readwrite()
@@ -158,12 +160,12 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
             self._committee.committee_apply(coupler.get_nz(), range(self._committee.models), 0, flat,
                                             [t.reshape(coupler.get_nz(), -1, 1) for t in self._nn_out],
                                             [t.reshape(coupler.get_nz(), -1, 1) for t in self.last_range] if self.want_range else None)
-        elif self.W1.shape[0] == 9:                                            # the stencil model: what load_surrogate_weights found
+        elif self.W1.shape[0] == 9:                                            # the stencil model: what load_surrogate_model found
             self._nn_out = mlp_stencil_forward(coupler.get_nz(), temp, rho_d, rho_v, rho_c, rho_r, self.W1, self.b1, self.W2, self.b2,
-                                               self.scl_in, self.scl_out, self._nn_out, strict=self.mlp_strict)
+                                               self.scl_in, self.scl_out, self._nn_out, strict=self.mlp_strict, form=getattr(self, "form", "state"))
         else:
             self._nn_out = mlp_forward(temp, rho_d, rho_v, rho_c, rho_r, self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out,
-                                       self._nn_out, strict=self.mlp_strict)
+                                       self._nn_out, strict=self.mlp_strict, form=getattr(self, "form", "state"))
         return self._finish_step(coupler, dt, temp, rho_v, rho_c, rho_r)
 
     def _finish_step(self, coupler, dt, temp, rho_v, rho_c, rho_r):

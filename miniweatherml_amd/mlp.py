@@ -1,10 +1,12 @@
 """The Kessler surrogate network: its weight files and its forward passes, thin drivers of mw_mlp_* / mw_ponni_forward.
 
   load_h5_weights, load_surrogate_weights   experiments/supercell_kessler_surrogate/custom_modules/microphysics_kessler_ponni.h:97-135
+  load_surrogate_model, SurrogateModel      the same files with the model's output form (no reference counterpart: DESIGN.md 13.9)
   mlp_forward, mlp_stencil_forward          model.forward_batch_parallel with the fused scaling, :176-202
   ponni_forward, _PonniLayer                ponni::create_inference_model / Inference::forward_batch_parallel, :109, :189
 
 IN5 and OUT4 name the network's five input and four output fields in its order; every module that feeds or scores it takes them here."""
+import collections
 import contextlib
 import ctypes as C
 import os
@@ -21,6 +23,51 @@ _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 
 IN5 = ("temp", "density_dry", "water_vapor", "cloud_liquid", "precip_liquid")
 OUT4 = ("temp", "water_vapor", "cloud_liquid", "precip_liquid")
+BASE4 = (0, 2, 3, 4)                  # OUT4's fields among IN5: what an output replaces, and the base a tendency model's change is added to
+
+# A model's OUTPUT FORM (MW_FORM_STATE / MW_FORM_TENDENCY, include/mw_cdna4.h): "state" -- the network's un-scaled output is the new state,
+# the reference's form -- or "tendency" -- it is the change, added in fp64 to the cell's own temp, water_vapor, cloud_liquid, precip_liquid.
+# The form travels with the files: a tendency model's output_scaling.txt starts with the comment line FORM_MARKER and its rows are the
+# [min, max] of (after - before).
+FORMS = ("state", "tendency")
+FORM_MARKER = "# form: tendency"
+SurrogateModel = collections.namedtuple("SurrogateModel", ("W1", "b1", "W2", "b2", "scl_in", "scl_out", "form"))
+
+
+def form_code(form):
+    """MW_FORM_* of a form given by name ("state" | "tendency") or by code (0 | 1); anything else is refused."""
+    if isinstance(form, str) and form in FORMS:
+        return FORMS.index(form)
+    if isinstance(form, (int, np.integer)) and not isinstance(form, bool) and 0 <= int(form) < len(FORMS):
+        return int(form)
+    endrun("surrogate form: %r is neither of %r" % (form, FORMS))
+
+
+def as_surrogate_model(model):
+    """A SurrogateModel of what the consumers take: a 6-tuple (W1, b1, W2, b2, scl_in, scl_out) -- load_surrogate_weights' return, the
+    state form -- or 7 fields with the form last."""
+    m = tuple(model)
+    if len(m) == 6:
+        return SurrogateModel(*m, "state")
+    if len(m) == 7:
+        return SurrogateModel(*m[:6], FORMS[form_code(m[6])])
+    endrun("surrogate model: a tuple of 6 (W1, b1, W2, b2, scl_in, scl_out) or 7 (+ form) expected, got %d" % len(m))
+
+
+def read_form(out_scaling_txt):
+    """The form an output scaling file declares: "tendency" if a comment line ahead of its rows is FORM_MARKER, else "state" (the
+    reference's files and every file written before there were two forms carry no marker).  Another `# form:` value is refused."""
+    with open(out_scaling_txt) as f:
+        for line in f:
+            t = line.strip()
+            if t and not t.startswith("#"):
+                break
+            if t.startswith("# form:"):
+                name = t[len("# form:"):].strip()
+                if name not in FORMS:
+                    endrun("%s: unknown output form %r (known: %s)" % (out_scaling_txt, name, ", ".join(FORMS)))
+                return name
+    return "state"
 
 
 @contextlib.contextmanager
@@ -50,11 +97,22 @@ def load_h5_weights(fname, group, dataset):
 
 
 def load_surrogate_weights(weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None):
+    """load_surrogate_model for callers that know only the state form: the six arrays, without the form.  Files of a tendency model are
+    refused -- its marker is a comment, np.loadtxt would skip it, and the model would silently run as a state model."""
+    m = load_surrogate_model(weights_txt, in_scaling_txt, out_scaling_txt, weights_h5)
+    if m.form != "state":
+        endrun("load_surrogate_weights: %s declares the %s form (%r); this function returns state-form models only -- read the files with "
+               "mlp.load_surrogate_model, which returns the form with the arrays" % (out_scaling_txt, m.form, FORM_MARKER))
+    return tuple(m[:6])
+
+
+def load_surrogate_model(weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None):
     """The Keras weights + min/max scaling tables (microphysics_kessler_ponni.h:97-135).  weights_h5: the reference's
     `keras_weights_h5` file, read like ponni::load_h5_weights does (:103-107); weights_txt: a text export of the 104 values
     (tools/export_mlp_weights.sh).  Default: the reference's shipped weight file (miniweatherml_amd/data/).
     The model is inferred from the text files: 5 scaling rows + 104 weights = the single-cell model (W1 (5,10)), 9 rows + 144 weights = the
-    two-cell stencil model (W1 (9,10); surrogate_train --stencil).  Any other pairing is refused; so is an .h5 file of a stencil model."""
+    two-cell stencil model (W1 (9,10); surrogate_train --stencil).  Any other pairing is refused; so is an .h5 file of a stencil model.
+    Returns a SurrogateModel (W1, b1, W2, b2, scl_in, scl_out, form), the form read from the output scaling file (read_form)."""
     if weights_txt is None and weights_h5 is None:
         weights_h5 = os.path.join(_DATA, "supercell_kessler_singlecell_model_weights.h5")
     if weights_h5 is not None:
@@ -77,28 +135,33 @@ def load_surrogate_weights(weights_txt=None, in_scaling_txt=None, out_scaling_tx
     if weights_h5 is None:
         a = 10 * rows
         W1, b1, W2, b2 = w[:a].reshape(rows, 10).copy(), w[a:a + 10].copy(), w[a + 10:a + 50].reshape(10, 4).copy(), w[a + 50:a + 54].copy()
-    scl_out = np.loadtxt(out_scaling_txt or os.path.join(_DATA, "kessler_surrogate_output_scaling.txt")).reshape(4, 2)
-    return W1, b1, W2, b2, np.ascontiguousarray(scl_in), np.ascontiguousarray(scl_out)
+    out_scaling_txt = out_scaling_txt or os.path.join(_DATA, "kessler_surrogate_output_scaling.txt")
+    scl_out = np.loadtxt(out_scaling_txt, comments="#").reshape(4, 2)
+    return SurrogateModel(W1, b1, W2, b2, np.ascontiguousarray(scl_in), np.ascontiguousarray(scl_out), read_form(out_scaling_txt))
 
 
-def mlp_forward(temp, rho_d, rho_v, rho_c, rho_r, W1, b1, W2, b2, scl_in, scl_out, outs=None, strict=0):
+def mlp_forward(temp, rho_d, rho_v, rho_c, rho_r, W1, b1, W2, b2, scl_in, scl_out, outs=None, strict=0, form="state"):
     """model.forward_batch_parallel with the fused scaling (microphysics_kessler_ponni.h:176-202).  strict = 1: the thread-per-cell
-    form that accumulates in index order (bit-identical to the CPU restatement) instead of the MFMA kernels."""
+    form that accumulates in index order (bit-identical to the CPU restatement) instead of the MFMA kernels.  form="tendency": the
+    un-scaled output is the change, added in fp64 to temp, rho_v, rho_c, rho_r of the cell (mw_mlp_forward_form)."""
+    fc = form_code(form)
     fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
     if outs is None:
         outs = [torch.empty_like(temp) for _ in range(4)]
     check(capi.lib().mw_mlp_set_strict(int(bool(strict))))
     with torch.cuda.device(temp.device):
-        check(capi.lib().mw_mlp_forward(temp.numel(), _ptr(temp), _ptr(rho_d), _ptr(rho_v), _ptr(rho_c), _ptr(rho_r),
-                                        W1.ctypes.data_as(fp), b1.ctypes.data_as(fp), W2.ctypes.data_as(fp), b2.ctypes.data_as(fp),
-                                        scl_in.ctypes.data_as(dp), scl_out.ctypes.data_as(dp), *[_ptr(o) for o in outs],
-                                        _stream_ptr(temp.device)))
+        check(capi.lib().mw_mlp_forward_form(fc, temp.numel(), _ptr(temp), _ptr(rho_d), _ptr(rho_v), _ptr(rho_c), _ptr(rho_r),
+                                             W1.ctypes.data_as(fp), b1.ctypes.data_as(fp), W2.ctypes.data_as(fp), b2.ctypes.data_as(fp),
+                                             scl_in.ctypes.data_as(dp), scl_out.ctypes.data_as(dp), *[_ptr(o) for o in outs],
+                                             _stream_ptr(temp.device)))
     return outs
 
 
-def mlp_stencil_forward(nz, temp, rho_d, rho_v, rho_c, rho_r, W1, b1, W2, b2, scl_in, scl_out, outs=None, strict=0):
+def mlp_stencil_forward(nz, temp, rho_d, rho_v, rho_c, rho_r, W1, b1, W2, b2, scl_in, scl_out, outs=None, strict=0, form="state"):
     """mlp_forward for the two-cell stencil model (W1 (9,10), scl_in (9,2)): the fields are whole coupler arrays (nz, ...) and features
-    5..8 come from level min(nz - 1, k + 1) of the same column (stencil_features states the order).  The outputs never alias the inputs."""
+    5..8 come from level min(nz - 1, k + 1) of the same column (stencil_features states the order).  The outputs never alias the inputs.
+    form="tendency": the base of the change is level k's own value (mw_mlp_stencil_forward_form)."""
+    fc = form_code(form)
     fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
     if W1.shape != (9, 10) or scl_in.shape != (9, 2):
         endrun("mlp_stencil_forward: W1 must be (9, 10) and scl_in (9, 2), got %r and %r" % (W1.shape, scl_in.shape))
@@ -108,10 +171,10 @@ def mlp_stencil_forward(nz, temp, rho_d, rho_v, rho_c, rho_r, W1, b1, W2, b2, sc
         outs = [torch.empty_like(temp) for _ in range(4)]
     check(capi.lib().mw_mlp_set_strict(int(bool(strict))))
     with torch.cuda.device(temp.device):
-        check(capi.lib().mw_mlp_stencil_forward(int(nz), temp.numel() // int(nz), _ptr(temp), _ptr(rho_d), _ptr(rho_v), _ptr(rho_c), _ptr(rho_r),
-                                                W1.ctypes.data_as(fp), b1.ctypes.data_as(fp), W2.ctypes.data_as(fp), b2.ctypes.data_as(fp),
-                                                scl_in.ctypes.data_as(dp), scl_out.ctypes.data_as(dp), *[_ptr(o) for o in outs],
-                                                _stream_ptr(temp.device)))
+        check(capi.lib().mw_mlp_stencil_forward_form(fc, int(nz), temp.numel() // int(nz), _ptr(temp), _ptr(rho_d), _ptr(rho_v), _ptr(rho_c),
+                                                     _ptr(rho_r), W1.ctypes.data_as(fp), b1.ctypes.data_as(fp), W2.ctypes.data_as(fp),
+                                                     b2.ctypes.data_as(fp), scl_in.ctypes.data_as(dp), scl_out.ctypes.data_as(dp),
+                                                     *[_ptr(o) for o in outs], _stream_ptr(temp.device)))
     return outs
 
 
@@ -162,6 +225,6 @@ def ponni_forward(layers, x, strict=0):
 
 def load_surrogate_bank(entries):
     """The models of a `surrogate_models:` list (dicts with keras_weights_txt | keras_weights_h5, nn_input_scaling, nn_output_scaling; `name`
-    and other keys are ignored) as the list of load_surrogate_weights tuples that SurrogateBank takes."""
-    return [load_surrogate_weights(weights_txt=e.get("keras_weights_txt"), in_scaling_txt=e.get("nn_input_scaling"),
+    and other keys are ignored) as the list of SurrogateModel tuples that SurrogateBank takes; a model's form is its files'."""
+    return [load_surrogate_model(weights_txt=e.get("keras_weights_txt"), in_scaling_txt=e.get("nn_input_scaling"),
                                    out_scaling_txt=e.get("nn_output_scaling"), weights_h5=e.get("keras_weights_h5")) for e in entries]

@@ -13,8 +13,8 @@ from .exchange import (install_exchange, use_rccl_allreduce, use_rccl_exchange, 
                        use_torch_distributed_exchange)
 from .experiments import make_simple_city, make_supercell, simple_city_step, supercell_step  # noqa: F401
 from .microphysics import Microphysics_Kessler, Microphysics_Kessler_Surrogate  # noqa: F401
-from .mlp import (_PonniLayer, load_h5_weights, load_surrogate_bank, load_surrogate_weights, mlp_forward, mlp_stencil_forward,  # noqa: F401
-                  ponni_forward, stencil_features)
+from .mlp import (FORM_MARKER, FORMS, SurrogateModel, _PonniLayer, load_h5_weights, load_surrogate_bank, load_surrogate_model,  # noqa: F401
+                  load_surrogate_weights, mlp_forward, mlp_stencil_forward, ponni_forward, stencil_features)
 from .ncio import NcFile as _NcFile  # noqa: F401
 from .ncio import dycore_output  # noqa: F401
 from .rollout import (RAIN_COUNTS, RAIN_FIELDS, ROLLOUT_FIELDS, ROLLOUT_IN5, ROLLOUT_STATS, ROLLOUT_WATER, Microphysics_Rollout, RainScorer,  # noqa: F401

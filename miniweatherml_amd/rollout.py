@@ -18,7 +18,7 @@ from ._ffi import StatsAndCounts, _field_ptr_array, _ptr, _stream_ptr, grown_wor
 from .capi import check
 from .coupler import endrun
 from .microphysics import Microphysics_Kessler, column_water, surface_rain_finish
-from .mlp import IN5, OUT4
+from .mlp import IN5, OUT4, as_surrogate_model
 from .ncio import sample_file_append, sample_file_create
 from .sampling import sample_buffers, sample_thresholds
 from .surrogate_eval import CommitteeGuard, SurrogateBank, finite_or_none, guard_config, json_safe, or_dash, skill_cell
@@ -74,15 +74,17 @@ class Microphysics_Rollout(Microphysics_Kessler):
         return "rollout"
 
     def init(self, coupler, models, persistence=True, names=None, committees=()):
-        """models: (W1, b1, W2, b2, scl_in, scl_out) tuples as load_surrogate_weights returns them, single-cell and stencil networks in any
-        order; names: theirs (default model0, model1, ...).  committees: (name, [model names]) pairs; each is one more member after the
+        """models: (W1, b1, W2, b2, scl_in, scl_out) tuples as load_surrogate_weights returns them (the state form) or SurrogateModel
+        tuples with the form last (load_surrogate_model), single-cell and stencil networks and both forms in any order (self.model_forms: the
+        forms by name, in the models' order); names: theirs (default model0, model1, ...).  committees: (name, [model names]) pairs; each is one more member after the
         models, replaced in place from its OWN state by the mean of its models (1 .. 16 of one width, SurrogateBank.committee_apply on that
         width's bank).  A third entry, (name, [model names], guard), makes the committee a GUARDED one (guard: surrogate_eval.guard_config's
         mapping of thresholds and max_rainsplit): its member is the committee's mean where its models agree and Kessler on the columns
         where they do not (SurrogateBank.committee_guard_apply's step).  All guarded members share one scratch (CommitteeGuard) and one
         columns-teacher call per step, so they share one max_rainsplit; every other member keeps the bits it has without the guard.
         The coupler must have 1 + len(models) + len(committees) (+ 1 with persistence) members."""
-        models = list(models)
+        models = [as_surrogate_model(m) for m in models]
+        self.model_forms = [m.form for m in models]
         names = ["model%d" % k for k in range(len(models))] if names is None else [str(n) for n in names]
         if len(names) != len(models):
             endrun("Microphysics_Rollout: %d names for %d models" % (len(names), len(models)))

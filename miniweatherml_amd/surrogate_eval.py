@@ -14,7 +14,7 @@ from . import capi
 from ._ffi import StatsAndCounts, _field_ptr_array, _ptr, _stream_ptr, fit_workspace, grown_workspace
 from .capi import check
 from .coupler import endrun
-from .mlp import IN5, OUT4, strict_mode
+from .mlp import FORMS, IN5, OUT4, as_surrogate_model, strict_mode
 
 EVAL_FIELDS = OUT4
 EVAL_CLASSES = ("inactive", "active")
@@ -24,7 +24,8 @@ _EXACT_ONE = 1 << 1074            # sums are kept as integers in units of 2^-107
 class SurrogateBank:
     """mw_surrogate_bank_t: K candidate networks of one width (all single-cell or all stencil), each with its own scaling tables, uploaded
     once to `device`; evaluate() refuses fields of another device.  models: a list of (W1, b1, W2, b2, scl_in, scl_out) as
-    load_surrogate_weights returns them."""
+    load_surrogate_weights returns them (the state form) or of SurrogateModel tuples with the form last (load_surrogate_model); a bank may
+    hold both forms.  self.forms: the models' forms by name."""
 
     def __init__(self, models, device="cuda:0"):
         self._h = None
@@ -32,6 +33,8 @@ class SurrogateBank:
         models = list(models)
         if len(models) < 1:
             endrun("SurrogateBank: no models")
+        models = [as_surrogate_model(m) for m in models]
+        self.forms = [m.form for m in models]
         if len(models) > capi.MW_SURROGATE_MAX_MODELS:
             endrun("SurrogateBank: %d models, at most %d fit one bank" % (len(models), capi.MW_SURROGATE_MAX_MODELS))
         widths = sorted({int(np.asarray(m[0]).shape[0]) for m in models})
@@ -39,19 +42,21 @@ class SurrogateBank:
             endrun("SurrogateBank: models of different widths (%s inputs) cannot share a bank: one bank per width" % ", ".join(map(str, widths)))
         self.n_in, self.models = widths[0], len(models)
         a = 10 * self.n_in
-        for W1, b1, W2, b2, si, so in models:
+        for W1, b1, W2, b2, si, so, _ in models:
             if np.shape(W1) != (self.n_in, 10) or np.shape(b1) != (10,) or np.shape(W2) != (10, 4) or np.shape(b2) != (4,) or \
                     np.shape(si) != (self.n_in, 2) or np.shape(so) != (4, 2):
                 endrun("SurrogateBank: a model is not Dense(%d->10), Dense(10->4) with (%d, 2) and (4, 2) scaling tables" % (self.n_in, self.n_in))
         params = np.ascontiguousarray([np.concatenate([np.ravel(m[0]), np.ravel(m[1]), np.ravel(m[2]), np.ravel(m[3])]) for m in models], dtype=np.float32)
         scl_in = np.ascontiguousarray([m[4] for m in models], dtype=np.float64)
         scl_out = np.ascontiguousarray([m[5] for m in models], dtype=np.float64)
+        forms = (C.c_int * len(models))(*[FORMS.index(f) for f in self.forms])
         h = C.c_void_p()
         if capi.lib().mw_device_count() < 1:
             endrun("SurrogateBank: no HIP device available: libmw_cdna4 has no CPU fallback")
         with torch.cuda.device(self.device):                              # the handle's allocations live on the current device
-            check(capi.lib().mw_surrogate_bank_create(C.byref(h), self.n_in, self.models, params.ctypes.data_as(C.POINTER(C.c_float)),
-                                                      scl_in.ctypes.data_as(C.POINTER(C.c_double)), scl_out.ctypes.data_as(C.POINTER(C.c_double))))
+            check(capi.lib().mw_surrogate_bank_create_forms(C.byref(h), self.n_in, self.models, params.ctypes.data_as(C.POINTER(C.c_float)),
+                                                            scl_in.ctypes.data_as(C.POINTER(C.c_double)),
+                                                            scl_out.ctypes.data_as(C.POINTER(C.c_double)), forms))
         self._h = h
         self.group = int(capi.lib().mw_surrogate_eval_group(h))           # models per pass over the state
         self.strict = 0                                                   # 1: the thread-per-cell kernels (mw_mlp_set_strict)

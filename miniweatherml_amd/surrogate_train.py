@@ -13,6 +13,9 @@ mw_ponni_forward's MFMA forward.  stencil=True (CLI --stencil) trains the two-ce
 inputs plus temperature, vapor, cloud and precipitation of the level above (STENCIL_IN_NAMES; slot 1 of the sample files), 144 parameters,
 the same fit.  This file holds the host side: reading and checking the data, the permutations' definition (restated
 here so that tests can replay the batch order), the Nadam scalars, the reports and the output files.  DESIGN.md section 13.
+form="tendency" (CLI --tendency, with or without --stencil) trains the network on the CHANGE of the four output fields instead of their
+new values: the labels are (after - before), scaled by the min and max of those differences, and the written model carries the form
+(output_scaling.txt starts with `# form: tendency`); the network, the fit and every other file are the same.  DESIGN.md section 13.9.
 """
 import argparse
 import ctypes as C
@@ -29,6 +32,9 @@ IN_NAMES = ("temperature", "dry air density", "water vapor density", "cloud liqu
 ABOVE_ROWS = (0, 1, 2, 3)            # rows of slot 1 that DataGenerator assigns (generate_micro_surrogate_data.h:139-142): row 4 never is
 STENCIL_IN_NAMES = IN_NAMES + tuple(IN_NAMES[v] + " (level above)" for v in (0, 2, 3, 4))       # slot 1 has no dry density
 OUT_NAMES = ("temperature", "water vapor density", "cloud liquid density", "precipitation density")
+BASE_OF_OUT = (0, 2, 3, 4)           # the input that output j replaces: a tendency model's labels are outputs[:, j] - inputs[:, BASE_OF_OUT[j]]
+FORMS = ("state", "tendency")        # mlp.FORMS / MW_FORM_STATE, MW_FORM_TENDENCY
+FORM_MARKER = "# form: tendency"     # mlp.FORM_MARKER: the first line of a tendency model's output_scaling.txt
 NADAM = dict(beta1=0.9, beta2=0.999, eps=1e-7, schedule_decay=0.004)    # tf.keras.optimizers.Nadam defaults
 M64 = (1 << 64) - 1
 TAG_PRESHUFFLE, TAG_WEIGHTS = M64, M64 - 1                               # stream tags; epoch e shuffles with tag e
@@ -191,9 +197,24 @@ def read_samples(sample_files, stencil=False):
     return inputs, outputs, meta
 
 
-def data_scaling(inputs, outputs, allow_constant=False):
+def _check_form(form):
+    if form not in FORMS:
+        raise SurrogateTrainError("form must be one of %r, got %r" % (FORMS, form))
+    return form
+
+
+def tendencies(inputs, outputs):
+    """(n, 4) fp64: what a tendency model is trained on, float64(outputs) - float64(inputs[:, BASE_OF_OUT]).  The records are fp32, so a
+    change below the fp32 spacing of the value (temperature: 3e-5 K at 300 K) is 0 here."""
+    return np.asarray(outputs, dtype=np.float64) - np.asarray(inputs, dtype=np.float64)[:, list(BASE_OF_OUT)]
+
+
+def data_scaling(inputs, outputs, allow_constant=False, form="state"):
     """Refuses unusable data and returns the min-max tables scl_in (5 | 9, 2), scl_out (4, 2) (fp64 arrays holding the fp32 extremes).
-    allow_constant (a warm start, whose tables are the continued model's): a constant variable is no refusal."""
+    allow_constant (a warm start, whose tables are the continued model's): a constant variable is no refusal.
+    form="tendency": scl_out is taken from tendencies(inputs, outputs), the differences in fp64; a constant difference is refused as a
+    constant output is."""
+    _check_form(form)
     if inputs.shape[0] == 0:
         raise SurrogateTrainError("the sample files hold zero samples")
     for arr, what in ((inputs, "inputs"), (outputs, "outputs")):
@@ -201,7 +222,9 @@ def data_scaling(inputs, outputs, allow_constant=False):
         if bad.any():
             raise SurrogateTrainError("%d non-finite values in the %s (first at sample %d)" % (int(bad.sum()), what, int(np.argwhere(bad)[0][0])))
     tabs = []
-    for arr, names, what in ((inputs, STENCIL_IN_NAMES if inputs.shape[1] == 9 else IN_NAMES, "input"), (outputs, OUT_NAMES, "output")):
+    labels = tendencies(inputs, outputs) if form == "tendency" else outputs
+    for arr, names, what in ((inputs, STENCIL_IN_NAMES if inputs.shape[1] == 9 else IN_NAMES, "input"),
+                             (labels, OUT_NAMES, "output tendency" if form == "tendency" else "output")):
         lo, hi = arr.min(axis=0), arr.max(axis=0)
         for v in range(arr.shape[1]):
             if not hi[v] > lo[v] and not allow_constant:
@@ -214,15 +237,15 @@ def data_scaling(inputs, outputs, allow_constant=False):
 def load_init(init, stencil=False):
     """The model a warm start continues: (weights (104 | 144,) fp32 in Keras order, scl_in, scl_out) from DIR/weights.txt,
     input_scaling.txt and output_scaling.txt (the files write_outputs leaves), read by mlp.load_surrogate_weights.  Host only.  The
-    width must be the one that is trained."""
+    width must be the one that is trained.  The model's form is init_form's."""
     from .capi import MWError
-    from .mlp import load_surrogate_weights
+    from .mlp import load_surrogate_model
     paths = [os.path.join(os.fspath(init), f) for f in ("weights.txt", "input_scaling.txt", "output_scaling.txt")]
     for path in paths:
         if not os.path.exists(path):
             raise SurrogateTrainError("init: no file %s" % path)
     try:
-        W1, b1, W2, b2, scl_in, scl_out = load_surrogate_weights(weights_txt=paths[0], in_scaling_txt=paths[1], out_scaling_txt=paths[2])
+        W1, b1, W2, b2, scl_in, scl_out = load_surrogate_model(weights_txt=paths[0], in_scaling_txt=paths[1], out_scaling_txt=paths[2])[:6]
     except MWError as e:
         raise SurrogateTrainError("init: %s" % e)
     w = np.concatenate([np.ravel(W1), np.ravel(b1), np.ravel(W2), np.ravel(b2)]).astype(np.float32)
@@ -231,6 +254,33 @@ def load_init(init, stencil=False):
                                   % (init, "stencil" if w.size == 144 else "single-cell", w.size, "stencil" if stencil else "single-cell",
                                      n_params(stencil), "" if stencil else " (--stencil trains the other)"))
     return w, np.ascontiguousarray(scl_in, dtype=np.float64), np.ascontiguousarray(scl_out, dtype=np.float64)
+
+
+def init_form(init):
+    """The output form of the model in DIR (load_init's): what its output_scaling.txt declares, "state" without a marker.  Host only."""
+    from .capi import MWError
+    from .mlp import read_form
+    path = os.path.join(os.fspath(init), "output_scaling.txt")
+    if not os.path.exists(path):
+        raise SurrogateTrainError("init: no file %s" % path)
+    try:
+        return read_form(path)
+    except MWError as e:
+        raise SurrogateTrainError("init: %s" % e)
+
+
+def resolve_form(form, init):
+    """The form a run trains: `form` ("state" | "tendency" | None = not asked for) without a warm start; with one, the form of DIR's model,
+    and asking for the other form is refused either way round -- the weights were fitted to the other labels."""
+    if form is not None:
+        _check_form(form)
+    if init is None:
+        return form or "state"
+    have = init_form(init)
+    if form is not None and form != have:
+        raise SurrogateTrainError("init: %s holds a %s-form model; it cannot be continued as a %s-form model%s"
+                                  % (init, have, form, " (drop --tendency)" if form == "tendency" else " (it continues as tendency)"))
+    return have
 
 
 def check_arguments(n, epochs, batch_size, test_split, validation_split, models):
@@ -266,13 +316,16 @@ def _write_weights(path, w, n_in):
             f.writelines(_fmt(x) + "\n" for x in w[lo:hi])
 
 
-def write_outputs(out_dir, weights, scl_in, scl_out, history, all_weights=None, names=None):
+def write_outputs(out_dir, weights, scl_in, scl_out, history, all_weights=None, names=None, form="state"):
     """weights.txt (104 values, the layout of data/kessler_surrogate_weights.txt; 144 for the stencil model), input_scaling.txt /
     output_scaling.txt (`min max` rows, 5 | 9 and 4) and history.json; returns the three paths inference_ponni takes (keras_weights_txt,
     nn_input_scaling, nn_output_scaling).
     all_weights (models, 104 | 144): also weights_<k>.txt for every model k, in the same layout and beside the same two scaling files; the
     return value is then (paths, surrogate_models) with the `surrogate_models:` list of the evaluate_surrogates driver (names: the
-    models' names, default model_<k>)."""
+    models' names, default model_<k>).
+    form="tendency": output_scaling.txt starts with the line FORM_MARKER (its rows are the table of the differences); a state model's files
+    are what they always were.  The readers are mlp.load_surrogate_model / read_form."""
+    _check_form(form)
     os.makedirs(out_dir, exist_ok=True)
     w = np.asarray(weights, dtype=np.float32).ravel()
     n_in = np.asarray(scl_in).shape[0]
@@ -283,6 +336,8 @@ def write_outputs(out_dir, weights, scl_in, scl_out, history, all_weights=None, 
     _write_weights(paths[0], w, n_in)
     for path, tab in ((paths[1], scl_in), (paths[2], scl_out)):
         with open(path, "w") as f:
+            if path == paths[2] and form == "tendency":
+                f.write(FORM_MARKER + "\n")
             f.writelines("%s %s\n" % (_fmt(lo), _fmt(hi)) for lo, hi in np.asarray(tab))
     with open(os.path.join(out_dir, "history.json"), "w") as f:
         json.dump(history, f, indent=1)
@@ -313,14 +368,17 @@ _LAYERS = _layers(5)
 class Trainer:
     """The device state of one training run: the three scaled sets, K models' parameters and moments, the Nadam table.  epoch() is one
     training launch plus the validation pass, with one host synchronisation (the copy of the weights and sums).  The model follows the
-    data: raw_in (n, 5) trains the single-cell model (104 parameters), raw_in (n, 9) the stencil model (144)."""
+    data: raw_in (n, 5) trains the single-cell model (104 parameters), raw_in (n, 9) the stencil model (144).  form="tendency": the y sets
+    are the scaled changes (mw_surrogate_prepare_form) and scl_out is the table of the changes; everything behind the prepare -- epochs,
+    validation, test errors, predict_test -- works in scaled label space and is the same for both forms."""
 
     def __init__(self, raw_in, raw_out, scl_in, scl_out, n_split, seed=0, split_seed=None, models=1, batch_size=1024, epochs=10,
-                 learning_rate=1e-3, initial=None):
+                 learning_rate=1e-3, initial=None, form="state"):
         import torch
         from . import capi
         self.torch, self.L = torch, capi.lib()
         self.device = raw_in.device
+        self.form = _check_form(form)
         self.n_in = int(raw_in.shape[1])
         if self.n_in not in (5, 9) or np.asarray(scl_in).shape != (self.n_in, 2):
             raise SurrogateTrainError("Trainer: inputs (n, %d) with a scaling table %r; expected (n, 5) or (n, 9) and as many scaling rows"
@@ -337,9 +395,9 @@ class Trainer:
         self.scl_in, self.scl_out = np.ascontiguousarray(scl_in, np.float64), np.ascontiguousarray(scl_out, np.float64)
         (tx, ty), (vx, vy), (sx, sy) = self.sets["train"], self.sets["val"], self.sets["test"]
         with torch.cuda.device(dev):
-            capi.check(self.L.mw_surrogate_prepare_v2(self.n_in, raw_in.shape[0], self._p(raw_in), self._p(raw_out), self.scl_in.ctypes.data_as(dp),
-                                                      self.scl_out.ctypes.data_as(dp), self.split_seed & M64, self.n_train, self.n_val,
-                                                      *[self._p(t) for t in (tx, ty, vx, vy, sx, sy)], self._stream()))
+            capi.check(self.L.mw_surrogate_prepare_form(FORMS.index(self.form), self.n_in, raw_in.shape[0], self._p(raw_in), self._p(raw_out),
+                                                        self.scl_in.ctypes.data_as(dp), self.scl_out.ctypes.data_as(dp), self.split_seed & M64,
+                                                        self.n_train, self.n_val, *[self._p(t) for t in (tx, ty, vx, vy, sx, sy)], self._stream()))
         # ONE device buffer for what the host reads each epoch: parameters (K, 104) fp32 | training sums (K, 2) fp64 | validation sums (K, 24)
         self.buf = torch.zeros(self.K * (NP * 4 + 2 * 8 + 24 * 8), dtype=torch.uint8, device=dev)
         self.params = self.buf[:self.K * NP * 4].view(f32).view(self.K, NP)
@@ -419,6 +477,15 @@ class Trainer:
         """The last epoch's validation sums (one more copy)."""
         return self._host()
 
+    def predict_test(self, w104):
+        """The network's output for the test set, (4, n_test) fp32 on the device, in SCALED LABEL space: un-scaled with scl_out it is the
+        new state of a state model, the change of a tendency model."""
+        sx, _ = self.sets["test"]
+        pred = self.torch.empty((4, self.n_test), dtype=self.torch.float32, device=self.device)
+        with self.torch.cuda.device(self.device):
+            self._predict(w104, sx, pred)
+        return pred
+
     def test_errors(self, w104):
         sx, sy = self.sets["test"]
         pred = self.pred[:4 * self.n_test].view(4, self.n_test)
@@ -436,7 +503,7 @@ def _metrics(s):
 
 
 def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test_split=0.2, validation_split=0.2, learning_rate=1e-3,
-                    seed=0, models=1, device="cuda:0", split_seed=None, verbose=False, stencil=False, keep_all=False, init=None):
+                    seed=0, models=1, device="cuda:0", split_seed=None, verbose=False, stencil=False, keep_all=False, init=None, form=None):
     """Trains `models` surrogates (seeds seed .. seed + models - 1; the pre-shuffle / split uses split_seed, default seed) on the samples of
     `sample_files` and returns a dict: per-model `history` (Keras' loss, mean_absolute_error, val_loss, val_mean_absolute_error per
     epoch), `weights` (models, 104) fp32, `best_model` (lowest final val_loss, ties to the lowest index), `test_metrics` of the best model
@@ -448,9 +515,14 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     init=DIR (a warm start, e.g. on the old sample files and a rollout's harvested ones together): every model starts from DIR/weights.txt
     instead of its seeded draw -- the models then differ by their epoch shuffles only -- and the scaling tables are DIR's, not the data's
     (samples outside the old range scale outside [0, 1]); the Nadam moments and the step counter start at zero.  The result gains `init`
-    and `initial_weights` (models, 104 | 144)."""
+    and `initial_weights` (models, 104 | 144).
+    form="tendency": the network is fitted to the change of the four fields (labels and output table from after - before; module
+    docstring); the result, history.json and the written files carry `form`.  The losses and the test metrics are in scaled LABEL space --
+    for a tendency model that is the space of the scaled changes, so they do not compare with a state model's.  form=None: "state", or
+    with init=DIR the form of DIR's model; a form that contradicts DIR's is refused (resolve_form)."""
+    form = resolve_form(form, init)
     inputs, outputs, meta = read_samples(sample_files, stencil=stencil)
-    scl_in, scl_out = data_scaling(inputs, outputs, allow_constant=init is not None)
+    scl_in, scl_out = data_scaling(inputs, outputs, allow_constant=init is not None, form=form)
     n = inputs.shape[0]
     n_split = check_arguments(n, epochs, batch_size, test_split, validation_split, models)
     initial = None
@@ -461,7 +533,10 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     dev = torch.device(device)
     raw_in = torch.from_numpy(inputs).to(dev)
     raw_out = torch.from_numpy(outputs).to(dev)
-    tr = Trainer(raw_in, raw_out, scl_in, scl_out, n_split, seed, split_seed, models, batch_size, epochs, learning_rate, initial=initial)
+    tr = Trainer(raw_in, raw_out, scl_in, scl_out, n_split, seed, split_seed, models, batch_size, epochs, learning_rate, initial=initial, form=form)
+    if verbose:
+        print("output form: %s -- loss, errors and test metrics below are in scaled label space: %s"
+              % (form, "the scaled change (after - before) of each field" if form == "tendency" else "the scaled new value of each field"), flush=True)
     del raw_in, raw_out
     K, (n_train, n_val, n_test) = int(models), n_split
     hist = [{"loss": [], "mean_absolute_error": [], "val_loss": [], "val_mean_absolute_error": []} for _ in range(K)]
@@ -506,7 +581,7 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     result = {"history": hist, "weights": w, "best_model": best, "test_metrics": metrics, "input_scaling": scl_in, "output_scaling": scl_out,
               "seeds": seeds, "split_seed": tr.split_seed, "n_train": n_train, "n_val": n_val, "n_test": n_test, "epoch_seconds": secs,
               "batch_size": int(batch_size), "epochs": int(epochs), "learning_rate": float(learning_rate),
-              "inputs": "stencil" if stencil else "single_cell"}
+              "inputs": "stencil" if stencil else "single_cell", "form": form}
     result.update({k: meta[k] for k in ("time_step_size", "dx", "dy", "dz", "files")})
     if init is not None:
         result["init"], result["initial_weights"] = os.fspath(init), initial
@@ -519,9 +594,9 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
         js["best_weights"] = w[best].astype(np.float64).tolist()
         if keep_all:
             result["files_written"], result["surrogate_models"] = write_outputs(out_dir, w[best], scl_in, scl_out, js, all_weights=w,
-                                                                                    names=["seed%d" % sd for sd in seeds])
+                                                                                    names=["seed%d" % sd for sd in seeds], form=form)
         else:
-            result["files_written"] = write_outputs(out_dir, w[best], scl_in, scl_out, js)
+            result["files_written"] = write_outputs(out_dir, w[best], scl_in, scl_out, js, form=form)
     return result
 
 
@@ -552,11 +627,13 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--init", default=None, metavar="DIR", help="warm start: continue DIR/weights.txt with DIR's scaling tables (all models start there)")
     ap.add_argument("--stencil", action="store_true", help="train the two-cell stencil model (the cell and the level above: 9 inputs, 144 weights)")
+    ap.add_argument("--tendency", action="store_true", help="train the tendency form: the network predicts the change of the four fields, which inference "
+                    "adds to the state in fp64 (with --init DIR the form is DIR's; a state-form DIR is refused)")
     a = ap.parse_args(argv)
     try:
         r = train_surrogate(a.files, a.out, a.epochs, a.batch_size, a.test_split, a.validation_split, a.learning_rate, a.seed, a.models,
                             a.device, a.split_seed, verbose=True, stencil=a.stencil, keep_all=a.keep_all,
-                            init=a.init)
+                            init=a.init, form="tendency" if a.tendency else None)
     except SurrogateTrainError as e:
         print("ERROR: %s" % e, file=sys.stderr)
         return 2
