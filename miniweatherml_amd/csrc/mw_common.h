@@ -68,6 +68,9 @@ struct DyP {                      // kernel parameter block (by value)
   const unsigned *zqk;            // ... the converting y launch: the rows of the slab it writes that hold zeros already
   const unsigned *zqp, *zqc;      // ... "the row an iteration stores to holds zeros already": the previous sub-cycle's map of this stage / the coupler's rows (mw_zero_rows.h)
   int zq_ld;
+  int zq_xper;                    // this rank owns the periodic x direction (bc_x periodic, x not decomposed): the maps' x segments grow and are looked up round
+                                  // the seam.  NOT wrap_x: with option wrap = 0 the kernels read halo cells instead of wrapping their index, and the halo fill
+                                  // puts the far edge's cells there -- a tracer crosses the seam either way
   // parked column increments (mw_nudge_to_column_deferred): inc[(l * nz + k) * nens + e] for l = density_dry, uvel, vvel, temp, water_vapor, added to
   // the coupler's values while the converting y launch loads them; nullptr = none
   const double *pinc;

@@ -538,6 +538,7 @@ void fill_params(mw_dycore_s *d) {
   p.enable_gravity = g.enable_gravity; p.use_immersed = g.use_immersed; p.idWV = g.idWV;
   p.zero_skip = d->o.zero_skip;
   p.zq = p.zqp = p.zqc = p.zqk = nullptr; p.zq_ld = 0;          // (set per RK stage by zero_rows_stage / zero_rows_conv)
+  p.zq_xper = (g.bc_x == MW_BC_PERIODIC && !(d->xchg && g.nproc_x > 1)) ? 1 : 0;
   p.pinc = nullptr;                                             // (set by mw_dycore_time_step when parked increments ride on the conversion)
   p.pos_mask = 0; p.mass_mask = 0;
   for (int t = 0; t < g.num_tracers; t++) { if (d->pos[t]) p.pos_mask |= 1u << t; if (d->adds[t]) p.mass_mask |= 1u << t; }

@@ -1084,7 +1084,7 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
   // (MODE 1: the x segments of the row maps that the tracer kernel's wave for this tile overlaps -- its lanes, halo lanes and patch cells)
   const bool vzq_on = VAP && MODE == 1 && (p.zq != nullptr) && p.zero_skip;
   unsigned vzseg = 0;
-  if (VAP && MODE == 1) { const int tx_ = __builtin_amdgcn_readfirstlane(q + (HS + 1) - lane); vzseg = zr_seg_mask(tx_ - (HS + 2), tx_ - (HS + 1) + 63 + 1, NXI, p.wrap_x != 0); }
+  if (VAP && MODE == 1) { const int tx_ = __builtin_amdgcn_readfirstlane(q + (HS + 1) - lane); vzseg = zr_seg_mask(tx_ - (HS + 2), tx_ - (HS + 1) + 63 + 1, NXI, p.zq_xper != 0); }
   // (bit i of vlean_mask = "the tracer kernel's iteration that stores cell kc0 + i is lean": lane i fetches the cell's word HERE, in front of the
   //  loop and with the prologue's loads, and the loop tests a scalar bit -- like zq_mask in k_tracers_fused.  Fetched inside the loop the word's
   //  wait stood where the predicate is formed, at the top of the iteration: vmcnt(0) behind the level's loads, one exposed round trip per level.
@@ -1101,7 +1101,7 @@ __global__ __launch_bounds__(256, 2) void k_xz_state(DyP p, const double *__rest
   unsigned fseg = 0;
   if (fst_on) {                                                // (the tile's first cell as a scalar: the mask's divisions stay off the vector unit)
     const int tx_ = __builtin_amdgcn_readfirstlane(q + (HS + 1) - lane), U_ = 64 - 2 * (HS + 1);
-    fseg = zr_seg_mask(tx_ - U_ - (HS + 2), tx_ + U_ - (HS + 1) + 63 + 1, NXI, p.wrap_x != 0);
+    fseg = zr_seg_mask(tx_ - U_ - (HS + 2), tx_ + U_ - (HS + 1) + 63 + 1, NXI, p.zq_xper != 0);
   }
   unsigned long long fst_mask = ~0ull;
   auto fst_fetch = [&](int kf0) __attribute__((always_inline)) {
@@ -1697,7 +1697,7 @@ __global__ __launch_bounds__(256, 2) void k_tracers_fused(DyP p, const double *_
   // flag bytes: k_tracer_patch scans the bytes of neighbouring rows whenever any y face of the stage was scaled, and a byte this wave set in an
   // earlier stage must not be found there.  (Lane i looks at iteration kstart + i; chunks of more than 62 levels take the loop.)
   if (VS && !vredo && (p.zq != nullptr) && p.zero_skip && kb + 1 - kstart < 64) {
-    const unsigned zseg_ = zr_seg_mask(tx * U - (hw + 1) * n, tx * U - hw * n + 63 + n, NXI, p.wrap_x != 0);
+    const unsigned zseg_ = zr_seg_mask(tx * U - (hw + 1) * n, tx * U - hw * n + 63 + n, NXI, p.zq_xper != 0);
     const int kit = kstart + lane;
     const bool in_it = kit <= kb + 1, st_it = (kit - 2 >= ka) && (kit - 2 < kb);
     bool busy = in_it && (p.zq[(long long)min(kit, p.nz - 1) * p.zq_ld + j + MW_ZR_HALO] & zseg_) != 0u;
@@ -1758,7 +1758,7 @@ __global__ __launch_bounds__(256, 2) void k_tracers_fused(DyP p, const double *_
   const unsigned *zq_own = p.zq + (MT ? mt_e * mo.zq : 0);       // (members in one workgroup: this wave's member)
   // (the x segments this wave's lanes, halo lanes and patch cells lie in -- k_zero_rows: a segment bit is set when a tracer that can vanish may be
   //  non-zero there; the row's other tiles may be busy while this one is lean)
-  const unsigned zseg = zr_seg_mask(tx * U - (hw + 1) * n, tx * U - hw * n + 63 + n, NXI, p.wrap_x != 0);
+  const unsigned zseg = zr_seg_mask(tx * U - (hw + 1) * n, tx * U - hw * n + 63 + n, NXI, p.zq_xper != 0);
   auto zq_fetch = [&](int k_first) __attribute__((always_inline)) {
     const unsigned wq = zq_own[(long long)min(k_first + lane, p.nz - 1) * p.zq_ld + j + MW_ZR_HALO];
     zq_mask = __ballot((wq & zseg) != 0u) | ~__ballot(true);     // (all 64 lanes are here; a missing one would keep its bit)

@@ -28,7 +28,7 @@ __global__ __launch_bounds__(256) void k_zero_rows(DyP p, CouplerPtrs c, const d
   const unsigned scan = vmask & ((1u << min(p.nt, 4)) - 1u);
   bool nz[4] = {false, false, false, false};
   unsigned segb = 0;                                              // this lane's part of the segment bits (+ the edge flags)
-  const bool xwrap = p.wrap_x != 0;
+  const bool xwrap = p.zq_xper != 0;                             // (one rank owns periodic x -- whether the kernels wrap their index or read filled halo cells)
   for (int base = 0; base < NXI; base += 512) {
     double a[4][8];
 #pragma unroll

@@ -279,7 +279,7 @@ def test_zero_row_maps_on_random_configurations(mw, seed):
         assert np.array_equal(res[0][k], res[1][k]), (k, seed, nx, ny, nz, nens, order, spec, chunks)
 
 
-def test_zero_row_maps_are_exactly_what_the_design_says(mw):
+def _zero_row_maps_against_the_design(wrap):
     """The ten maps of a sub-cycle (mw_debug_zero_maps) against a numpy restatement of their definition (mw_zero_rows.h): M0 = the rows
     in which a tracer that can vanish is non-zero (water vapour of the folded supercell configuration: always set), and per RK stage s the OR of
     M0 over 3s rows (periodic) and, for Qs / FNs / QYs, over levels k-3s-5 .. k+3s+1 / k-3s-6 .. k+3s+2 / k-3(s-1) .. k+3(s-1) (clamped).
@@ -289,6 +289,7 @@ def test_zero_row_maps_are_exactly_what_the_design_says(mw):
     from miniweatherml_amd import capi, modules
     nx, ny, nz = 130, 44, 26
     coupler, dycore, _ = modules.make_supercell(nx, ny, nz, 1, 65000., 22000., 20000.)
+    dycore.set_option("wrap", wrap)
     dm = coupler.get_data_manager_readwrite()
     rho = dm.get("density_dry")
     cl, pr = torch.zeros_like(rho), torch.zeros_like(rho)
@@ -337,3 +338,14 @@ def test_zero_row_maps_are_exactly_what_the_design_says(mw):
     assert float((seg != 0).mean()) == float((maps[1] & 6 != 0).mean())                              # a row bit set <=> some segment set
     busy = seg[seg != 0]
     assert float(np.mean([bin(int(w)).count("1") for w in busy])) < 0.6 * ((nx + Lseg - 1) // Lseg)       # ... and busy rows are busy in part of their segments only
+
+
+def test_zero_row_maps_are_exactly_what_the_design_says(mw):
+    _zero_row_maps_against_the_design(wrap=1)
+
+
+def test_zero_row_maps_are_exactly_what_the_design_says_without_the_index_wrap(mw):
+    """Option wrap = 0: the marching kernels read x halo cells that the halo fill copied from the far edge instead of wrapping their index.  The
+    maps' definition does not know how a kernel addresses its halo -- one rank owns the periodic direction, a segment grows round the seam --
+    so the expected words are the same (cloud in cells 5 and 129 of the 130: segments on both sides of the seam)."""
+    _zero_row_maps_against_the_design(wrap=0)

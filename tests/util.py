@@ -39,6 +39,57 @@ def launched_kernels(reset=True):
     return sorted(set(buf.value.decode().split()))
 
 
+def kernel_forms(names):
+    """Mangled kernel names (launched_kernels) -> {kernel family: set of template-argument tuples}: the integral and bool arguments
+    of every instantiation in declaration order, e.g. k_xz_state<1, true, 0, 1, 1, 5, false, true> -> (1, 1, 0, 1, 1, 5, 0, 1)."""
+    import re
+    out = {}
+    for n in names:
+        m = re.match(r"_ZN2mw(\d+)", n)
+        if not m:
+            continue
+        ln, at = int(m.group(1)), m.end()
+        family, rest = n[at:at + ln], n[at + ln:]
+        args = []
+        if rest.startswith("I"):
+            at = 1
+            while True:
+                a = re.match(r"L[ib](n?)(\d+)E", rest[at:])
+                if not a:
+                    break
+                args.append(-int(a.group(2)) if a.group(1) else int(a.group(2)))
+                at += a.end()
+        out.setdefault(family, set()).add(tuple(args))
+    return out
+
+
+def zero_row_maps(dycore):
+    """The ten zero-row maps of the handle's last sub-cycle (mw_debug_zero_maps): uint32 (10, nz, ny + 18) -- M0, Q1 .. Q3, FN1 .. FN3,
+    QY1 .. QY3, row j at column j + 9; None when the sub-cycle ran without maps (or the handle keeps one set per member)."""
+    from miniweatherml_amd import capi
+    L, dims = capi.lib(), (C.c_int * 2)()
+    n = L.mw_debug_zero_maps(dycore.h, None, 0, dims)
+    if n <= 0:
+        return None
+    buf = np.zeros(n, dtype=np.uint32)
+    assert L.mw_debug_zero_maps(dycore.h, buf.ctypes.data_as(C.c_void_p), n, dims) == n
+    return buf.reshape(10, dims[0], dims[1])
+
+
+def zero_row_seg_mask(lo, hi, nxi):
+    """The segment bits (in place: bits 4 .. 29) of the cells lo .. hi of a PERIODIC row of nxi cells, lo may be < 0 and hi >= nxi
+    (26 segments of ceil(nxi / 26) cells)."""
+    L = (nxi + 25) // 26
+    span = lambda a, b: ((2 << (b // L)) - (1 << (a // L))) << 4   # noqa: E731
+    if hi - lo + 1 >= nxi:
+        return span(0, nxi - 1)
+    if lo < 0:
+        return span(lo + nxi, nxi - 1) | span(0, hi)
+    if hi >= nxi:
+        return span(lo, nxi - 1) | span(0, hi - nxi)
+    return span(lo, hi)
+
+
 def drain_paths():
     """The dispatcher paths (mw_dycore_path) of every time_step since the last drain."""
     from miniweatherml_amd import modules
