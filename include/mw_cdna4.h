@@ -719,6 +719,27 @@ int  mw_member_sample_mask(int nz, long long ncol, int nens, int nm, const int *
 int  mw_member_gather_samples(int nz, long long ncol, int nens, const double *const *fields5, const double *const *teacher4,
                               const long long *elems, long long n, float *inputs, float *outputs, void *stream);
 
+/* ---- training-domain guard: which cells of a member lie outside the box its model was trained in --------- */
+/* One read of the five input fields in5 (temp, density_dry, water_vapor, cloud_liquid, precip_liquid: HOST array of 5 DEVICE pointers,
+ * member-fastest (nz, ncol, nens), never written) of the nm (1 .. 32) listed members (HOST, distinct, in [0, nens), nens <= 64)
+ * against box, a HOST (nm, 5, 2) fp64 array of [lo, hi] per listed member and field (lo <= hi; NaN refused, +-inf allowed; it travels in
+ * the kernel arguments, hence nm <= 32).  A value x of field f is BELOW iff x < lo, ABOVE iff x > hi, NAN iff x != x, else inside: x
+ * equal to a bound, +-inf against an infinite bound and -0.0 against lo = 0.0 are inside.  A column of a member is OUTSIDE iff some
+ * level and field of it holds a below, above or nan value.
+ * counts: DEVICE int64 (nm, 16), SET by the call (a memset in stream order, then integer adds): word 3 f + c the cells of field f in
+ * class c (0 below, 1 above, 2 nan), word 15 the member's outside columns.
+ * flags / slots / flag_counts: all three may be NULL (report only).  slots: HOST, nm entries; for a member with slots[j] >= 0 the byte
+ * col * nens + member of flags (DEVICE, (ncol, nens)) becomes 1 for every outside column and is never set to 0, and
+ * flag_counts[2 slots[j]] and [2 slots[j] + 1] (DEVICE int64, the layout of mw_committee_guard_flags' counts, one pair per slot) are
+ * both INCREASED by the number of that member's bytes this call turned from 0 to 1 -- so after mw_committee_guard_flags on the same
+ * member the pair holds the union.  Bytes of unlisted members and of members with slots[j] < 0 are not touched.
+ * Asynchronous on `stream`, no allocation, no host synchronisation, integer atomics only: every result is independent of order and
+ * run-to-run identical.  Refused, with nothing launched: null in5, counts, box or members; nz or ncol < 1; nens outside [1, 64]; nm
+ * outside [1, 32]; a repeated or out-of-range member; a bad box; a slots[j] >= 0 with flags or flag_counts NULL.  40 bytes per cell of
+ * the listed members. */
+int  mw_member_domain(int nz, long long ncol, int nens, int nm, const int *members, const double *box, const double *const *in5,
+                      long long *counts, unsigned char *flags, const int *slots, long long *flag_counts, void *stream);
+
 /* ---- DataManager validators ---------------------------------------------------------------------------- */
 /* core::DataManager::validate / validate_nan / validate_inf / validate_pos (model/core/DataManager.h:385-483) -- the reference's only
  * built-in health check: it copies an entry to the host and loops over it.  Here ONE device pass over the entry's `n` elements

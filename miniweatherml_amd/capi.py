@@ -14,6 +14,7 @@ MW_SURROGATE_MAX_MODELS = 256
 MW_ROLLOUT_MAX_MEMBERS = 30
 MW_COMMITTEE_MAX_MODELS = 16
 MW_RAIN_MAX_FIELDS, MW_RAIN_MAX_THRESHOLDS = 4, 8          # mw_member_rain_table
+MW_DOMAIN_MAX_MEMBERS, MW_DOMAIN_WORDS = 32, 16            # mw_member_domain
 DATA_THERMAL, DATA_SUPERCELL, DATA_CITY, DATA_BUILDING = 0, 1, 2, 3
 BC_PERIODIC, BC_OPEN, BC_WALL = 0, 1, 2
 INIT_IDS = {"thermal": DATA_THERMAL, "supercell": DATA_SUPERCELL, "city": DATA_CITY, "building": DATA_BUILDING}
@@ -191,6 +192,8 @@ SYMBOLS = {
                                         C.c_ulonglong, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "mw_member_gather_samples": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_longlong,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mw_member_domain": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_void_p),
+                                   C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
     "mw_validate_f64": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]),
     "mw_validate_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]),
     "mw_mlp_stencil_forward": (C.c_int, [C.c_int, C.c_longlong] + [C.c_void_p] * 5 + [C.POINTER(C.c_float)] * 4 +

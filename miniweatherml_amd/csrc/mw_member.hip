@@ -7,6 +7,8 @@
 // mw_committee_guard_flags / mw_members_copy are the guarded committee's two passes that are not Kessler's: which columns
 // of a member go to Kessler, and the commit of the scratch result into the state.  mw_member_column_water / mw_member_surface_rain /
 // mw_member_rain_table are every member's surface rain from its column water budget and its contingency table.
+// mw_member_domain counts the cells of the listed members that lie outside the box their models were trained in, and flags their columns
+// for the guarded committee's Kessler pass.
 // =====================================================================================================
 #include "../../include/mw_cdna4.h"
 #include "mw_common.h"
@@ -326,6 +328,92 @@ static long long rain_table_blocks(long long n, int nens) {
   return std::max<long long>(1, std::min<long long>((n + C - 1) / C, RAIN_MAX_BLOCKS));
 }
 
+// ---- mw_member_domain ---------------------------------------------------------------------------------------------------------------
+constexpr int DOMAIN_MAX_MEMBERS = 32;     // the boxes travel in the kernel arguments: 32 x 80 bytes
+constexpr int DOMAIN_WORDS = 16;           // per listed member: 3 f + c (c: below, above, nan) for the five fields, word 15 the outside columns
+constexpr int DOMAIN_ROW = DOMAIN_WORDS + 1;   // ... and, in LDS only, the flag bytes this block turned from 0 to 1
+
+struct DomainArgs {
+  const double *in[5];
+  double box[DOMAIN_MAX_MEMBERS][5][2];    // [listed member][field][lo, hi]
+  int slot[DOMAIN_MAX_MEMBERS];            // < 0: the member's flag bytes are not touched
+  signed char listed_at[64];               // member e is box / slot / counts row listed_at[e], -1: not listed
+};
+
+// A workgroup takes 64 consecutive elements t = col * nens + e of the (ncol, nens) plane, lane l of each of its four wavefronts element
+// 64 * block + l (k_member_column_water's layout: a wavefront's load of a level is 64 consecutive doubles per field whatever nens is),
+// and wavefront g the levels g, g + 4, ... (k_committee_guard_flags' split: at nens = 1 a 400 x 400 plane is 2,500 wavefronts, a quarter
+// of what the chip holds; the split makes them 10,000).  An iteration issues the ten loads of TWO levels before the first test; the
+// second level past the top is level k again with its counts masked by `on`.  The tests are joined with | on integers (see above).
+// Counts: fifteen registers per lane, then LDS integer adds into the block's row of the lane's member (zero words skipped), then one
+// global atomicAdd per non-zero word and block.  The OR over the four wavefronts' levels goes through ballots as in the flags kernel;
+// wavefront 0 then owns the element's flag byte, so its read-test-write needs no atomic.  Integer adds only: any order, the same numbers.
+__global__ __launch_bounds__(256) void k_member_domain(int nz, long long plane, int nens, int nm, DomainArgs A,
+                                                       unsigned long long *__restrict__ counts, unsigned char *__restrict__ flags,
+                                                       unsigned long long *__restrict__ flag_counts) {
+  __shared__ unsigned long long masks[4];
+  __shared__ unsigned int rows[DOMAIN_MAX_MEMBERS * DOMAIN_ROW];
+  const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const long long t = (long long)blockIdx.x * 64 + lane;
+  for (int w = threadIdx.x; w < nm * DOMAIN_ROW; w += 256) rows[w] = 0u;
+  __syncthreads();
+  const int j = t < plane ? (int)A.listed_at[(int)(t % nens)] : -1;
+  int bad = 0;
+  if (j >= 0) {
+    double lo[5], hi[5];
+#pragma unroll
+    for (int f = 0; f < 5; f++) { lo[f] = A.box[j][f][0]; hi[f] = A.box[j][f][1]; }
+    int cnt[15];
+#pragma unroll
+    for (int w = 0; w < 15; w++) cnt[w] = 0;
+    for (int k = g; k < nz; k += 8) {
+      const int on = k + 4 < nz ? 1 : 0;
+      const long long idx0 = (long long)k * plane + t;
+      const long long idx1 = (long long)(on ? k + 4 : k) * plane + t;
+      double x[10];
+#pragma unroll
+      for (int f = 0; f < 5; f++) { x[f] = A.in[f][idx0]; x[5 + f] = A.in[f][idx1]; }
+      __builtin_amdgcn_sched_barrier(0);                                    // (left alone the scheduler tests after two loads: four in flight)
+#pragma unroll
+      for (int f = 0; f < 5; f++) {
+        const int b0 = (int)(x[f] < lo[f]), a0 = (int)(x[f] > hi[f]), n0 = (int)(x[f] != x[f]);
+        const int b1 = (int)(x[5 + f] < lo[f]) & on, a1 = (int)(x[5 + f] > hi[f]) & on, n1 = (int)(x[5 + f] != x[5 + f]) & on;
+        cnt[3 * f] += b0 + b1; cnt[3 * f + 1] += a0 + a1; cnt[3 * f + 2] += n0 + n1;
+        bad |= b0 | a0 | n0 | b1 | a1 | n1;
+      }
+    }
+#pragma unroll
+    for (int w = 0; w < 15; w++)
+      if (cnt[w]) atomicAdd(&rows[j * DOMAIN_ROW + w], (unsigned int)cnt[w]);
+  }
+  const unsigned long long mine = __ballot(bad != 0);
+  if (lane == 0) masks[g] = mine;
+  __syncthreads();
+  if (g == 0) {
+    const unsigned long long all = masks[0] | masks[1] | masks[2] | masks[3];
+    if (j >= 0 && ((all >> lane) & 1ull)) {
+      atomicAdd(&rows[j * DOMAIN_ROW + 15], 1u);
+      if (A.slot[j] >= 0) {
+        const unsigned char old = flags[t];
+        if (old != 1) flags[t] = 1;
+        if (old == 0) atomicAdd(&rows[j * DOMAIN_ROW + DOMAIN_WORDS], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  for (int w = threadIdx.x; w < nm * DOMAIN_ROW; w += 256) {
+    const unsigned int q = rows[w];
+    if (!q) continue;
+    const int m = w / DOMAIN_ROW, s = w % DOMAIN_ROW;
+    if (s < DOMAIN_WORDS) {
+      atomicAdd(counts + m * DOMAIN_WORDS + s, (unsigned long long)q);
+    } else {
+      atomicAdd(flag_counts + 2 * A.slot[m], (unsigned long long)q);
+      atomicAdd(flag_counts + 2 * A.slot[m] + 1, (unsigned long long)q);
+    }
+  }
+}
+
 } // namespace mw
 
 using namespace mw;
@@ -573,6 +661,47 @@ extern "C" int mw_member_rain_table(long long ncol, int nens, int nf, const doub
   MW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_member_rain_table_final, dim3((unsigned)((nf * RAIN_MAX_THR * nens + 255) / 256)), dim3(256), 0, st, (int)blocks, nf, nens, R,
                      (const long long *)workspace, counts);
+  MW_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mw_member_domain(int nz, long long ncol, int nens, int nm, const int *members, const double *box, const double *const *in5,
+                                long long *counts, unsigned char *flags, const int *slots, long long *flag_counts, void *stream) {
+  if (!in5 || !counts || !box || !members) MW_FAIL("member_domain: null pointer");
+  if (nz < 1 || ncol < 1) MW_FAIL("member_domain: nz and ncol must be >= 1");
+  if (nens < 1 || nens > 64) MW_FAIL("member_domain: nens must be in [1, 64]");
+  if (nm < 1 || nm > DOMAIN_MAX_MEMBERS) MW_FAIL("member_domain: nm must be in [1, " + std::to_string(DOMAIN_MAX_MEMBERS) + "]");
+  if ((double)nz * (double)ncol * (double)nens > 9.0e18 || (double)ncol * (double)nens > 64.0 * 2147483647.0)
+    MW_FAIL("member_domain: the fields are too large");
+  DomainArgs A;
+  for (int e = 0; e < 64; e++) A.listed_at[e] = -1;
+  for (int j = 0; j < DOMAIN_MAX_MEMBERS; j++) {
+    A.slot[j] = -1;
+    for (int f = 0; f < 5; f++) { A.box[j][f][0] = -__builtin_inf(); A.box[j][f][1] = __builtin_inf(); }
+  }
+  for (int j = 0; j < nm; j++) {
+    const int e = members[j];
+    if (e < 0 || e >= nens) MW_FAIL("member_domain: member " + std::to_string(e) + " is outside [0, " + std::to_string(nens) + ")");
+    if (A.listed_at[e] >= 0) MW_FAIL("member_domain: member " + std::to_string(e) + " is listed twice");
+    A.listed_at[e] = (signed char)j;
+    for (int f = 0; f < 5; f++) {
+      const double lo = box[(j * 5 + f) * 2], hi = box[(j * 5 + f) * 2 + 1];
+      if (!(lo <= hi)) MW_FAIL("member_domain: the box of member " + std::to_string(e) + ", field " + std::to_string(f) +
+                               ", is not lo <= hi (NaN is refused, +-inf is allowed)");
+      A.box[j][f][0] = lo; A.box[j][f][1] = hi;
+    }
+    if (slots && slots[j] >= 0) {
+      if (!flags || !flag_counts) MW_FAIL("member_domain: member " + std::to_string(e) + " has a slot, but flags or flag_counts is null");
+      A.slot[j] = slots[j];
+    }
+  }
+  for (int f = 0; f < 5; f++) { if (!in5[f]) MW_FAIL("member_domain: null field"); A.in[f] = in5[f]; }
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  hipStream_t st = (hipStream_t)stream;
+  const long long plane = ncol * nens;
+  MW_HIP(hipMemsetAsync(counts, 0, (size_t)nm * DOMAIN_WORDS * 8, st));     // counts is SET: the adds start from zero
+  hipLaunchKernelGGL(k_member_domain, dim3((unsigned)((plane + 63) / 64)), dim3(256), 0, st, nz, plane, nens, nm, A, (unsigned long long *)counts,
+                     flags, (unsigned long long *)flag_counts);
   MW_LAUNCH_CHECK();
   return 0;
 }

@@ -54,6 +54,18 @@ its column's water (the Kessler member keeps Kessler's own), and surrogate_rollo
 per scoring step and member, the statistics of the rate (mm/h) and of the accumulated rain (mm) against the Kessler member with a
 contingency table per threshold (rollout.RainScorer).  `map: true` writes surrogate_rollout_rain.npy, float64 (nens, ny, nx), mm, at
 the end.  `surface_rain: true` means these defaults; false or absent: off, and the document is what it is without the key.
+    training_domain: true                     # or {margin: 0.05, fields: [temp, water_vapor]}
+makes rollout_surrogates report, at every scoring step and for every network-stepped member, how much of the member's state lies outside
+the box its model was trained in: the rows of a model's input scaling table are the minimum and maximum of each input
+over its training samples, a committee's box is the intersection of its models', `margin` widens it by that fraction of its width and
+`fields` restricts it.  Every entry of `models` and `committees` in surrogate_rollout.json gets a `domain` block: margin, fields, box,
+cells, columns, first_outside_step and, per scoring step, outside_columns and the cells below / above / nan per field.  The report
+only reads the state.  Inside a committee's guard,
+      - {name: boxed, members: [tend0], guard: {domain: {margin: 0.0}}}
+`domain:` (true or the same mapping) hands Kessler every column of the member that holds a cell outside the committee's box, beside the
+columns the thresholds flag (a guard may hold only `domain`: a committee of ONE model then has a guard that acts).  Its guard block
+gains `domain` (margin, fields, box) and outside_columns per scoring step; flagged stays the union.  rollout_surrogates and
+inference_ponni honour it.
 """
 import argparse
 import os
@@ -86,7 +98,7 @@ def load_config(path):
         if key in cfg:
             out[key] = str(cfg[key])
     out["_dir"] = os.path.dirname(os.path.abspath(path))
-    for key in ("surrogate_models", "eval_interval", "persistence_member", "harvest", "surrogate_committees", "surface_rain"):    # read by surrogate_config / rollout_config / harvest_config / committee_config / surface_rain_config alone
+    for key in ("surrogate_models", "eval_interval", "persistence_member", "harvest", "surrogate_committees", "surface_rain", "training_domain"):    # read by surrogate_config / rollout_config / harvest_config / committee_config / surface_rain_config / training_domain_config alone
         if key in cfg:
             out[key] = cfg[key]
     return out
@@ -263,6 +275,16 @@ def surface_rain_config(cfg):
     return out
 
 
+def training_domain_config(cfg):
+    """The checked `training_domain:` key of a loaded configuration for rollout_surrogates, or None when it is absent or false: true
+    (margin 0, all five input fields) or {margin, fields} (surrogate_eval.domain_config)."""
+    from .surrogate_eval import domain_config
+    b = cfg.get("training_domain", False)
+    if b is False or b is None:
+        return None
+    return domain_config(b, "training_domain")
+
+
 def _surrogate_models(entries, yaml_dir):
     """The `surrogate_models:` list: every entry names a model and its three files (relative paths: from the working directory, as the
     other file keys, else from the YAML file's directory)."""
@@ -385,6 +407,7 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                              "ranks is not built yet" % nranks)
         harvest = harvest_config(cfg)
         rain_cfg = surface_rain_config(cfg)
+        domain_cfg = training_domain_config(cfg)
         committees = committee_config(cfg)
         cfg["surrogate_models"], cfg["eval_interval"], cfg["persistence_member"], cfg["nens"] = rollout_config(cfg)
     coupler = _coupler(cfg, device, nranks, myrank, yaml_path)
@@ -466,6 +489,8 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
         if experiment == "rollout_surrogates" and rain_cfg is not None:
             micro.surface_rain = {}                                            # every member but Kessler from its water budget
             rain = rollout.RainScorer(micro.member_names, rain_cfg["thresholds_mm_h"], rain_cfg["thresholds_mm"])
+        if experiment == "rollout_surrogates" and domain_cfg is not None:
+            micro.training_domain = domain_cfg
         harvester = None
         if experiment == "rollout_surrogates" and harvest is not None:
             harvester = micro.harvester = rollout.RolloutHarvester()
@@ -497,6 +522,8 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
             else:
                 if harvester is not None:                                      # (eval_step counts the steps of a rollout)
                     micro.harvest_now, micro.harvest_etime = eval_step[0] % harvest["interval"] == 0, etime
+                if scorer is not None and domain_cfg is not None:              # the report's pass runs at scoring steps only
+                    micro.domain_now = eval_step[0] % cfg["eval_interval"] == 0
                 micro.time_step(coupler, dt)
                 if experiment == "inference_ponni" and not quiet and coupler.is_mainproc():
                     d = micro.mean_diffs(coupler)                              # microphysics_kessler_ponni.h:266-269
@@ -509,6 +536,7 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                     before = dict(scorer.diverged_at)
                     scorer.accumulate(coupler, eval_step[0], etime + dt)
                     micro.guard_record(eval_step[0], dt)                       # (the only host read of the guards' counts)
+                    micro.domain_record(eval_step[0])                          # (and of the training-domain report's)
                     if rain is not None:
                         rain.accumulate(coupler, micro, eval_step[0], etime + dt)
                     for m, d in scorer.diverged_at.items():                    # the other members do not see it: the run goes on
@@ -558,6 +586,11 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                 for c, g in zip(doc["committees"], micro.guard_reports()):
                     if g is not None:
                         c["guard"] = g
+            if domain_cfg is not None:                                         # one block per network-stepped member
+                blocks = micro.domain_reports()
+                for entry in doc["models"] + doc.get("committees", []):
+                    entry["domain"] = blocks[entry["member"]]
+                info["domain_reports"] = {scorer.member_names[m]: b for m, b in enumerate(blocks) if b is not None}
             if harvester is not None:
                 doc["harvest"] = dict(harvest, files=dict(harvester.files), samples=dict(harvester.samples), skipped=dict(harvester.skipped),
                                       calls=harvester.calls)

@@ -111,11 +111,12 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
         form, the state form) or SurrogateModel tuples with the form last; a committee may mix the forms.  The network's
         result is then the committee's mean (SurrogateBank.committee_apply), and the weight file arguments are not read.  guard
         (surrogate_eval.guard_config's mapping; with a committee only): the result is the GUARDED committee's step of the state before the
-        call -- the mean, and on the columns where the models' range exceeds a threshold what Kessler leaves on those columns alone."""
+        call -- the mean, and on the columns where the models' range exceeds a threshold what Kessler leaves on those columns alone.  A
+        guard with `domain` hands Kessler the columns with a cell outside the committee's training box too."""
         super().init(coupler)
         self._nn_out = None
         self._committee = None
-        self._guard_cfg = self._guard = None
+        self._guard_cfg = self._guard = self._guard_box = None
         if guard is not None:
             if committee is None:
                 endrun("Microphysics_Kessler_Surrogate: a guard needs a committee")
@@ -129,6 +130,9 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
                 endrun("Microphysics_Kessler_Surrogate: a committee has 1 to %d models, got %d" % (capi.MW_COMMITTEE_MAX_MODELS, len(committee)))
             self._committee = SurrogateBank(committee, coupler.device)
             self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out, self.form = as_surrogate_model(committee[0])
+            if self._guard_cfg is not None and "domain" in self._guard_cfg:
+                from .surrogate_eval import domain_box
+                self._guard_box = domain_box(committee, self._guard_cfg["domain"]["margin"], self._guard_cfg["domain"]["fields"])
             return
         self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out, self.form = load_surrogate_model(weights_txt, in_scaling_txt,
                                                                                                         out_scaling_txt, weights_h5)
@@ -151,7 +155,8 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
                 g = self._guard_cfg
                 if self._guard is None:
                     self._guard = CommitteeGuard(flat[0], coupler.get_nz())
-                self._committee.committee_guard_flag(coupler.get_nz(), range(self._committee.models), 0, flat, [g[f] for f in OUT4], self._guard)
+                self._committee.committee_guard_flag(coupler.get_nz(), range(self._committee.models), 0, flat, [g[f] for f in OUT4], self._guard,
+                                                     domain_box=getattr(self, "_guard_box", None))
                 self._guard.commit(coupler.get_nz(), [0], flat, g["max_rainsplit"], coupler.get_dz(), dt, copy=False)   # Kessler below writes the state
                 self._nn_out = [t.reshape(temp.shape) for t in self._guard.mean4]
                 if self.want_range:

@@ -20,6 +20,8 @@ from .ncio import dycore_output  # noqa: F401
 from .rollout import (RAIN_COUNTS, RAIN_FIELDS, ROLLOUT_FIELDS, ROLLOUT_IN5, ROLLOUT_STATS, ROLLOUT_WATER, Microphysics_Rollout, RainScorer,  # noqa: F401
                       RolloutHarvester, RolloutScorer, fields_divergence, kessler_members_teacher, member_column_water, member_divergence,
                       member_rain_table, member_surface_rain, rain_report, rain_scores, rain_thresholds, rollout_member_names, rollout_report)
+from .rollout import box_json, domain_report  # noqa: F401
 from .sampling import DataGenerator, StatisticsGatherer  # noqa: F401
 from .surrogate_eval import (EVAL_CLASSES, EVAL_FIELDS, CommitteeEvaluator, CommitteeGuard, SurrogateBank, SurrogateEvaluator, _sums_to_float,  # noqa: F401
                              committee_score, guard_config, json_safe, range_error_correlation, surrogate_scores)
+from .surrogate_eval import DOMAIN_CLASSES, domain_box, domain_config, member_domain  # noqa: F401

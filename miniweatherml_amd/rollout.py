@@ -6,7 +6,8 @@ experiments/supercell_kessler_surrogate/custom_modules/generate_micro_surrogate_
   RolloutHarvester           (state, label) samples of the teacher on the model members' states, one file per member
   member_divergence, rollout_report, RolloutScorer    mw_member_divergence and its reports
   member_column_water, member_surface_rain            every member's surface rain from its column water budget
-  member_rain_table, rain_report, RainScorer          its contingency table against the Kessler member and the reports"""
+  member_rain_table, rain_report, RainScorer          its contingency table against the Kessler member and the reports
+  domain_report                                       a member's cells outside its model's training box, per scoring step"""
 import ctypes as C
 import os
 
@@ -21,7 +22,8 @@ from .microphysics import Microphysics_Kessler, column_water, surface_rain_finis
 from .mlp import IN5, OUT4, as_surrogate_model
 from .ncio import sample_file_append, sample_file_create
 from .sampling import sample_buffers, sample_thresholds
-from .surrogate_eval import CommitteeGuard, SurrogateBank, finite_or_none, guard_config, json_safe, or_dash, skill_cell
+from .surrogate_eval import (DOMAIN_CLASSES, CommitteeGuard, SurrogateBank, domain_box, domain_config, finite_or_none, guard_config, json_safe,
+                             member_domain, or_dash, skill_cell)
 
 ROLLOUT_FIELDS = ("density_dry", "uvel", "vvel", "wvel", "temp", "water_vapor", "cloud_liquid", "precip_liquid")
 ROLLOUT_STATS = ("sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_x", "min_x", "max_x")
@@ -60,7 +62,13 @@ class Microphysics_Rollout(Microphysics_Kessler):
     members' names (default: every member but kessler; with kessler in it the budget overwrites Kessler's own precl of member 0, which
     is the closure check of DESIGN.md 13.8).  The step itself is the same either way: the budget only reads the state.
     With a `harvester` (RolloutHarvester) and `harvest_now` set, the step harvests Kessler labels on the model members' own states
-    between the Kessler member's step and the models'; harvesting reads the state and never writes it."""
+    between the Kessler member's step and the models'; harvesting reads the state and never writes it.
+    With `training_domain` (surrogate_eval.domain_config's mapping, or True) and `domain_now` set, the step counts, for every model member
+    and every committee member, the cells of its five input fields that lie outside the box of its model's (its committee's) input
+    scaling rows -- one mw_member_domain call with every slot -1 at the harvest's place in the step, after the Kessler
+    member's step and before members_apply, so it sees the state the networks are about to replace.  It only reads.  A guarded member
+    listed there gets its flag bytes written NOT in that call but in the guards' own call, in the guard's position of the step (after
+    the loop of committee_guard_flag, before the commit); a committee member's state is the same at both points, so the bits are too."""
 
     mlp_strict = 0        # 1: the thread-per-cell MLP kernels (mw_mlp_set_strict)
     harvester = None      # a RolloutHarvester: time_step harvests when harvest_now is set (the driver sets it, and harvest_etime, per step)
@@ -69,6 +77,8 @@ class Microphysics_Rollout(Microphysics_Kessler):
     surface_rain = None   # a mapping (may be empty; key budget_members): precl of the budget members and rain_total from the water budget
     _w_before = None
     rain_total = None     # with surface_rain: (ny, nx, nens) fp64, metres of water since the first step with the option
+    training_domain = None   # None, True or a domain_config mapping: time_step counts the cells outside the box when domain_now is set
+    domain_now = False       # (the driver sets it at scoring steps)
 
     def micro_name(self):
         return "rollout"
@@ -80,8 +90,11 @@ class Microphysics_Rollout(Microphysics_Kessler):
         models, replaced in place from its OWN state by the mean of its models (1 .. 16 of one width, SurrogateBank.committee_apply on that
         width's bank).  A third entry, (name, [model names], guard), makes the committee a GUARDED one (guard: surrogate_eval.guard_config's
         mapping of thresholds and max_rainsplit): its member is the committee's mean where its models agree and Kessler on the columns
-        where they do not (SurrogateBank.committee_guard_apply's step).  All guarded members share one scratch (CommitteeGuard) and one
-        columns-teacher call per step, so they share one max_rainsplit; every other member keeps the bits it has without the guard.
+        where they do not (SurrogateBank.committee_guard_apply's step).  A guard with `domain` also hands Kessler the columns that
+        hold a cell outside the box of the committee's models (domain_box with the guard's margin and fields); all such members go
+        into ONE mw_member_domain call per step, after the loop of committee_guard_flag.  All guarded members share one scratch
+        (CommitteeGuard) and one columns-teacher call per step, so they share one max_rainsplit; every other member keeps the bits it has
+        without the guard.
         The coupler must have 1 + len(models) + len(committees) (+ 1 with persistence) members."""
         models = [as_surrogate_model(m) for m in models]
         self.model_forms = [m.form for m in models]
@@ -121,6 +134,14 @@ class Microphysics_Rollout(Microphysics_Kessler):
             in_bank = [k for k, m in enumerate(models) if np.shape(m[0])[0] == w]
             self.committees.append((self.banks[widths.index(w)][0], [in_bank.index(names.index(n)) for n in cmodels], 1 + len(models) + ci))
         self.guards = guards                                                   # per committee: the checked guard or None
+        self._models, self._model_names, self._committee_names = models, names, committees
+        # per committee: the box of a guard with `domain` (refused here, before any step, when the models' ranges do not intersect)
+        self._guard_boxes = [self._committee_box(ci, g["domain"]) if g is not None and "domain" in g else None for ci, g in enumerate(guards)]
+        self._guard_domain_counts = None                                       # device (domain-guarded members, 16) of the last step
+        self._domain = None                                                    # the report's (cfg, members, boxes), made at its first step
+        self._domain_counts = self._domain_fresh = None
+        self._domain_steps = []                                                # per domain_record: (step, host counts (members, 16))
+        self._domain_cells = (None, None)                                      # a member's cells and columns, known at the first step
         self._guard = None                                                     # the CommitteeGuard all guarded members share
         self._guard_steps = [[] for _ in committees]
         self._m0 = None
@@ -133,6 +154,7 @@ class Microphysics_Rollout(Microphysics_Kessler):
         nz, nens = coupler.get_nz(), coupler.get_nens()
         ncol = coupler.get_ny() * coupler.get_nx()
         n = nz * ncol
+        self._domain_cells = (n, ncol)
         L = capi.lib()
         if self._m0 is None or self._m0[0][0].numel() != n or self._m0[1].numel() != ncol:
             self._m0 = ([torch.empty(n, dtype=torch.float64, device=coupler.device) for _ in range(5)],
@@ -152,6 +174,10 @@ class Microphysics_Rollout(Microphysics_Kessler):
             check(L.mw_member_insert(ncol, nens, 0, 1, _field_ptr_array([p0]), _field_ptr_array([precl]), st))
         if self.harvester is not None and self.harvest_now:                    # the teacher sees the state each model is about to replace
             self.last_harvest = self.harvester.harvest(coupler, dt, self.harvest_etime)
+        if self.training_domain is not None and self.domain_now:               # (it sees that state too, and only reads it)
+            _, members, boxes = self._domain_setup()
+            self._domain_counts = member_domain(nz, [temp, rho_d, rho_v, rho_c, rho_r], members, boxes, self._domain_counts)
+            self._domain_fresh = True
         for bank, members in self.banks:
             bank.strict = self.mlp_strict
             bank.members_apply(nz, members, [temp, rho_d, rho_v, rho_c, rho_r])
@@ -166,6 +192,10 @@ class Microphysics_Rollout(Microphysics_Kessler):
                 bank.committee_apply(nz, sel, member, in5, [temp, rho_v, rho_c, rho_r])
             else:                                                              # mean, range and flags of this member; the state is not written yet
                 bank.committee_guard_flag(nz, sel, member, in5, [guards[ci][f] for f in GUARD_FIELDS], self._guard, guarded.index(ci))
+        boxed = [ci for ci in guarded if self._guard_boxes[ci] is not None]
+        if boxed:                                                              # every domain-guarded member in one call, flags into its slot
+            self._guard_domain_counts = member_domain(nz, in5, [self.committees[ci][2] for ci in boxed], [self._guard_boxes[ci] for ci in boxed],
+                                                      self._guard_domain_counts, self._guard, [guarded.index(ci) for ci in boxed])
         if guarded:                                                            # Kessler on every flagged column, then the guarded members' commit
             self._guard.commit(nz, [self.committees[ci][2] for ci in guarded], in5, guards[guarded[0]]["max_rainsplit"], coupler.get_dz(), dt)
         if budget is not None:
@@ -189,20 +219,63 @@ class Microphysics_Rollout(Microphysics_Kessler):
             self._w_before = None
         return [self.member_names.index(m) for m in names]
 
+    def _committee_box(self, ci, cfg):
+        cname, cmodels = self._committee_names[ci]
+        return domain_box([self._models[self._model_names.index(n)] for n in cmodels], cfg["margin"], cfg["fields"], names=cmodels)
+
+    def _domain_setup(self):
+        """(the checked training_domain, the network-stepped members, their boxes (members, 5, 2)): every model member with its model's
+        box, every committee member with its committee's."""
+        if self._domain is None or self._domain[3] is not self.training_domain:
+            cfg = domain_config(self.training_domain, "training_domain")
+            boxes = [domain_box([m], cfg["margin"], cfg["fields"], names=[n]) for m, n in zip(self._models, self._model_names)]
+            boxes += [self._committee_box(ci, cfg) for ci in range(len(self._committee_names))]
+            if not boxes or len(boxes) > capi.MW_DOMAIN_MAX_MEMBERS:
+                endrun("Microphysics_Rollout: training_domain reports 1 to %d network-stepped members, this rollout has %d"
+                       % (capi.MW_DOMAIN_MAX_MEMBERS, len(boxes)))
+            self._domain = (cfg, list(range(1, 1 + len(boxes))), np.stack(boxes), self.training_domain)
+            self._domain_counts, self._domain_steps = None, []
+        return self._domain[:3]
+
+    def domain_record(self, step):
+        """At a scoring step, after a time_step with domain_now set: fetches that step's counts of every reported member (the only host
+        read of them; no other step synchronises for the report)."""
+        if self.training_domain is None or not self._domain_fresh:
+            return
+        self._domain_steps.append((int(step), self._domain_counts.cpu().numpy().copy()))
+        self._domain_fresh = False
+
+    def domain_reports(self):
+        """Per member, in member_names' order: None (kessler, persistence, or no training_domain), or the member's `domain` block of
+        surrogate_rollout.json (domain_report)."""
+        out = [None] * len(self.member_names)
+        if self.training_domain is None:
+            return out
+        cfg, members, boxes = self._domain_setup()
+        cells, ncol = self._domain_cells
+        for j, m in enumerate(members):
+            out[m] = domain_report(cfg, boxes[j], cells, ncol, [(step, counts[j]) for step, counts in self._domain_steps])
+        return out
+
     def guard_record(self, step, dt):
         """At a scoring step, after time_step: fetches every guarded member's flagged columns and rain sub-cycle count of that step (the only
-        host read of them; no other step synchronises for the guards)."""
+        host read of them; no other step synchronises for the guards), and with a `domain` in the guard its outside columns."""
         guarded = [ci for ci, g in enumerate(getattr(self, "guards", ())) if g is not None]
         if not guarded or self._guard is None:
             return
         counts, rs = self._guard.read(dt, [self.committees[ci][2] for ci in guarded])
+        boxed = [ci for ci in guarded if self._guard_boxes[ci] is not None]
+        outside = self._guard_domain_counts[:, 15].cpu().tolist() if boxed and self._guard_domain_counts is not None else []
         for slot, ci in enumerate(guarded):
             self._guard_steps[ci].append({"step": int(step), "flagged": counts[slot][0], "rainsplit": rs[slot], "flagged_total": counts[slot][1]})
+            if ci in boxed and outside:
+                self._guard_steps[ci][-1]["outside_columns"] = int(outside[boxed.index(ci)])
 
     def guard_reports(self):
         """Per committee, in the list's order: None, or the guarded member's `guard` block of surrogate_rollout.json -- thresholds (inf as the
         string "inf"), max_rainsplit, columns, flagged_total (the device accumulator at the last scoring step), and steps: {step, flagged,
-        rainsplit} per scoring step (rainsplit 0: the Kessler part was skipped)."""
+        rainsplit} per scoring step (rainsplit 0: the Kessler part was skipped).  A guard with `domain` adds domain: {margin, fields, box}
+        and outside_columns to every step; flagged stays the union of both criteria, from the guard's count word."""
         out = []
         for ci, g in enumerate(getattr(self, "guards", ())):
             if g is None:
@@ -212,8 +285,35 @@ class Microphysics_Rollout(Microphysics_Kessler):
             out.append({"thresholds": {f: json_safe(g[f]) for f in GUARD_FIELDS}, "max_rainsplit": g["max_rainsplit"],
                         "columns": self._guard.ncol if self._guard is not None else None,
                         "flagged_total": steps[-1]["flagged_total"] if steps else 0,
-                        "steps": [{k: s[k] for k in ("step", "flagged", "rainsplit")} for s in steps]})
+                        "steps": [{k: s[k] for k in ("step", "flagged", "rainsplit", "outside_columns") if k in s} for s in steps]})
+            if "domain" in g:
+                out[-1]["domain"] = dict(g["domain"], box=box_json(self._guard_boxes[ci]))
         return out
+
+
+def box_json(box):
+    """A (5, 2) box as {field: [lo, hi]} with inf as a string (json_safe)."""
+    return {f: json_safe([float(box[i][0]), float(box[i][1])]) for i, f in enumerate(IN5)}
+
+
+def domain_report(cfg, box, cells, columns, records):
+    """A member's `domain` block from its raw counts -- pure numpy.  cfg: the checked domain_config; box: its (5, 2) box; cells / columns:
+    the member's cells (nz * ny * nx) and columns; records: (step, 16 int64 words of mw_member_domain) per scoring step.  Returns margin,
+    fields, box ({field: [lo, hi]}, inf as a string), cells, columns, first_outside_step (the first recorded step with an outside column,
+    None if never) and steps: {step, outside_columns, below / above / nan: {field: cells}} over the five fields of IN5."""
+    steps, first = [], None
+    for step, words in records:
+        words = np.asarray(words, dtype=np.int64).reshape(-1)
+        if words.shape != (capi.MW_DOMAIN_WORDS,):
+            endrun("domain_report: %d count words per member and step expected" % capi.MW_DOMAIN_WORDS)
+        row = {"step": int(step), "outside_columns": int(words[15])}
+        for c, cname in enumerate(DOMAIN_CLASSES):
+            row[cname] = {f: int(words[3 * i + c]) for i, f in enumerate(IN5)}
+        steps.append(row)
+        if first is None and words[15] > 0:
+            first = int(step)
+    return {"margin": cfg["margin"], "fields": list(cfg["fields"]), "box": box_json(box), "cells": None if cells is None else int(cells),
+            "columns": None if columns is None else int(columns), "first_outside_step": first, "steps": steps}
 
 
 def kessler_members_teacher(coupler, members, dt, max_rainsplit=64, outs=None, return_rainsplit=False):

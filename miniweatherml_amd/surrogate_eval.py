@@ -140,10 +140,12 @@ class SurrogateBank:
                                                          _field_ptr_array(range4) if range4 is not None else None, _stream_ptr(self.device))
         check(rc)
 
-    def committee_guard_flag(self, nz, sel, member, in5, thr4, guard, slot=0):
+    def committee_guard_flag(self, nz, sel, member, in5, thr4, guard, slot=0, domain_box=None):
         """Steps 1 and 2 of a guarded committee's step for ensemble member `member`: committee_apply of the models sel out
         of place into guard.mean4 / guard.range4, then mw_committee_guard_flags with the thresholds thr4 (temp, water_vapor, cloud_liquid,
-        precip_liquid; each >= 0, inf: never by size) into guard.flags and row `slot` of guard.counts.  The state is only read."""
+        precip_liquid; each >= 0, inf: never by size) into guard.flags and row `slot` of guard.counts.  The state is only read.
+        domain_box (a (5, 2) box, domain_box()): member_domain on that member with the guard's slot follows, so the
+        columns with a cell outside the box are flagged too and the count words hold the union.  None: exactly the calls above."""
         if len(in5) != 5 or len(thr4) != 4:
             endrun("SurrogateBank.committee_guard_flag: five input fields and four thresholds expected")
         ncol, nens = self._member_layout("SurrogateBank.committee_guard_flag: ", nz, list(in5))
@@ -156,8 +158,10 @@ class SurrogateBank:
                                                      _stream_ptr(self.device))
         check(rc)
         guard.flagged_members.add(int(member))
+        if domain_box is not None:
+            guard.domain_counts = member_domain(nz, in5, [member], [domain_box], guard.domain_counts, guard, [slot])
 
-    def committee_guard_apply(self, nz, sel, member, in5, thr4, max_rainsplit, dz, dt, scratch):
+    def committee_guard_apply(self, nz, sel, member, in5, thr4, max_rainsplit, dz, dt, scratch, domain_box=None):
         """One step of a guarded committee on ensemble member `member` of the member-fastest fields in5 = (temp, density_dry, water_vapor,
         cloud_liquid, precip_liquid), each (nz, ..., nens), in place: the committee's mean (committee_apply of the models sel) where its
         models agree, Kessler where they do not.  In order: committee_apply out of place into the scratch's mean4 and range4; column flags
@@ -167,29 +171,93 @@ class SurrogateBank:
         written.  scratch: a CommitteeGuard for fields of this shape -- eight fields of the state's shape (64 bytes per element of ALL
         members, allocated once), one flag byte per column and member, the columns teacher's workspace and two int64 counts per slot.
         No host synchronisation; scratch.read(dt) fetches the counts.  A scratch used for another member before has that member's flag bytes
-        cleared first: the columns teacher runs on every flagged column of the state, whichever member it belongs to."""
+        cleared first: the columns teacher runs on every flagged column of the state, whichever member it belongs to.  domain_box:
+        committee_guard_flag's keyword (columns outside the box go to Kessler too)."""
         if scratch.flagged_members - {int(member)}:
             scratch.flags.zero_()
             scratch.flagged_members.clear()
-        self.committee_guard_flag(nz, sel, member, in5, thr4, scratch)
+        self.committee_guard_flag(nz, sel, member, in5, thr4, scratch, domain_box=domain_box)
         scratch.commit(nz, [member], in5, max_rainsplit, dz, dt)
 
 
-GUARD_KEYS = OUT4 + ("max_rainsplit",)
+GUARD_KEYS = OUT4 + ("max_rainsplit", "domain")
+DOMAIN_KEYS = ("margin", "fields")
+DOMAIN_CLASSES = ("below", "above", "nan")
+STENCIL_ABOVE = {0: 5, 2: 6, 3: 7, 4: 8}     # the stencil model's row of the level above, per IN5 field that has one (mlp.stencil_features)
+
+
+def domain_config(d, who="domain"):
+    """A checked training-domain criterion: True -- margin 0.0, all five fields of IN5 -- or a mapping with `margin` (a
+    number >= 0, not a bool: the box grows by margin times its width on both sides) and `fields` (a non-empty list of distinct IN5
+    names; a field left out is never outside).  Unknown keys and anything else are refused (ValueError).  Returns {"margin": float,
+    "fields": [names in IN5's order]} -- pure Python."""
+    if d is True:
+        d = {}
+    if not isinstance(d, dict):
+        raise ValueError("ERROR: %s must be true or a mapping" % who)
+    unknown = sorted(set(d) - set(DOMAIN_KEYS), key=str)
+    if unknown:
+        raise ValueError("ERROR: unknown key(s) %s in %s (known: %s)" % (", ".join(map(repr, unknown)), who, ", ".join(DOMAIN_KEYS)))
+    m = d.get("margin", 0.0)
+    if isinstance(m, bool) or not isinstance(m, (int, float)) or not m >= 0 or m == float("inf"):
+        raise ValueError("ERROR: %s.margin must be a finite number >= 0, got %r" % (who, m))
+    fields = d.get("fields", list(IN5))
+    if not isinstance(fields, (list, tuple)) or not fields or any(not isinstance(f, str) or f not in IN5 for f in fields) or \
+            len(set(fields)) != len(fields):
+        raise ValueError("ERROR: %s.fields must be a non-empty list of distinct names of %s, got %r" % (who, ", ".join(IN5), fields))
+    return {"margin": float(m), "fields": [f for f in IN5 if f in fields]}
+
+
+def domain_box(models, margin=0.0, fields=IN5, names=None):
+    """The box of a model or a committee: (5, 2) fp64 [lo, hi] per IN5 field from the rows of the models' input scaling
+    tables, which are the minimum and maximum of each input over the training samples.  A single-cell model gives its rows; a stencil
+    model's temp, water_vapor, cloud_liquid and precip_liquid take the intersection of the cell's row and the row of the level above
+    (one interval per field at every level: at level 0, whose "level above" the network never sees below it, stricter than necessary);
+    several models the intersection over them.  Then [lo - margin * (hi - lo), hi + margin * (hi - lo)] in fp64 as written, and
+    [-inf, +inf] for a field not in `fields`.  An empty intersection is refused (ValueError) with the field's and the models' names
+    (names: theirs, default model0, model1, ...)."""
+    models = [as_surrogate_model(m) for m in models]
+    if not models:
+        raise ValueError("ERROR: domain_box: no models")
+    names = ["model%d" % k for k in range(len(models))] if names is None else [str(n) for n in names]
+    tables = [np.asarray(m.scl_in, dtype=np.float64) for m in models]
+    if len({t.shape for t in tables}) != 1 or tables[0].ndim != 2 or tables[0].shape[1] != 2 or tables[0].shape[0] not in (5, 9):
+        raise ValueError("ERROR: domain_box: the models' input scaling tables must be all (5, 2) or all (9, 2)")
+    if not (isinstance(margin, (int, float)) and not isinstance(margin, bool) and 0 <= margin < float("inf")):
+        raise ValueError("ERROR: domain_box: margin must be a finite number >= 0, got %r" % (margin,))
+    fields = [str(f) for f in fields]
+    if any(f not in IN5 for f in fields):
+        raise ValueError("ERROR: domain_box: fields must be names of %s" % ", ".join(IN5))
+    box = np.empty((5, 2), dtype=np.float64)
+    m = np.float64(margin)
+    for f, fname in enumerate(IN5):
+        if fname not in fields:
+            box[f] = (-np.inf, np.inf)
+            continue
+        rows = [t[f] for t in tables] + ([t[STENCIL_ABOVE[f]] for t in tables] if tables[0].shape[0] == 9 and f in STENCIL_ABOVE else [])
+        lo, hi = np.float64(max(r[0] for r in rows)), np.float64(min(r[1] for r in rows))
+        if not lo <= hi:
+            raise ValueError("ERROR: domain_box: the input ranges of field %s of the models %s do not intersect (lo %r > hi %r, or NaN)"
+                             % (fname, ", ".join(names), float(lo), float(hi)))
+        w = hi - lo
+        box[f] = (lo - m * w, hi + m * w)
+    return box
 
 
 def guard_config(guard, who="guard"):
     """A committee's checked guard: a mapping with any of temp, water_vapor, cloud_liquid, precip_liquid -- the range above which a column
-    goes to Kessler, a number >= 0 in the field's units, a missing field never flags by size -- and max_rainsplit (1 .. 1024, default
-    64).  Unknown keys, a negative, NaN or non-numeric threshold and a guard without any threshold are refused (ValueError).  Returns
-    {"temp", "water_vapor", "cloud_liquid", "precip_liquid": floats (inf where missing), "max_rainsplit": int} -- pure Python."""
+    goes to Kessler, a number >= 0 in the field's units, a missing field never flags by size -- max_rainsplit (1 .. 1024, default 64)
+    and domain (domain_config: columns with a cell outside the models' training box go to Kessler too).  Unknown keys, a
+    negative, NaN or non-numeric threshold and a guard with neither a threshold nor a domain are refused (ValueError).  Returns
+    {"temp", "water_vapor", "cloud_liquid", "precip_liquid": floats (inf where missing), "max_rainsplit": int} and, only when the guard
+    has one, "domain": the checked criterion -- pure Python."""
     if not isinstance(guard, dict):
         raise ValueError("ERROR: %s must be a mapping" % who)
     unknown = sorted(set(guard) - set(GUARD_KEYS), key=str)
     if unknown:
         raise ValueError("ERROR: unknown key(s) %s in %s (known: %s)" % (", ".join(map(repr, unknown)), who, ", ".join(GUARD_KEYS)))
-    if not any(f in guard for f in OUT4):
-        raise ValueError("ERROR: %s holds no threshold (one of %s)" % (who, ", ".join(OUT4)))
+    if not any(f in guard for f in OUT4) and "domain" not in guard:
+        raise ValueError("ERROR: %s holds no threshold (one of %s) and no domain" % (who, ", ".join(OUT4)))
     out = {}
     for f in OUT4:
         t = guard.get(f, float("inf"))
@@ -200,7 +268,50 @@ def guard_config(guard, who="guard"):
     if isinstance(cap, bool) or not isinstance(cap, int) or not 1 <= cap <= 1024:
         raise ValueError("ERROR: %s.max_rainsplit must be an integer in [1, 1024], got %r" % (who, cap))
     out["max_rainsplit"] = cap
+    if "domain" in guard:
+        out["domain"] = domain_config(guard["domain"], who + ".domain")
     return out
+
+
+def member_domain(nz, in5, members, boxes, counts=None, guard=None, slots=None):
+    """mw_member_domain on the member-fastest fields in5 = (temp, density_dry, water_vapor, cloud_liquid, precip_liquid), each
+    (nz, ..., nens), contiguous fp64: for member members[j] and its box boxes[j] ((5, 2) [lo, hi], domain_box) the cells of every field
+    below the box, above it or NaN and the member's outside columns.  Returns the DEVICE int64 tensor (len(members), 16) -- word 3 f + c
+    for field f and class c of DOMAIN_CLASSES, word 15 the outside columns -- written into `counts` if given; the call SETs it, reads
+    nothing back and does not synchronise.  With guard (a CommitteeGuard) and slots (one per member, -1: none) the outside columns of
+    a member with a slot get their byte of guard.flags set to 1, and both words of row slots[j] of guard.counts grow by the bytes this
+    call turned from 0 to 1; the member is then added to guard.flagged_members."""
+    members = [int(m) for m in members]
+    boxes = np.ascontiguousarray(boxes, dtype=np.float64)
+    if len(in5) != 5 or any(t.shape != in5[0].shape for t in in5) or in5[0].dim() < 2:
+        endrun("member_domain: five fields of one shape (nz, ..., nens) expected")
+    if any(t.dtype != torch.float64 or not t.is_contiguous() or t.device != in5[0].device for t in in5):
+        endrun("member_domain: contiguous float64 fields of one device expected")
+    nens, dev = int(in5[0].shape[-1]), in5[0].device
+    n = in5[0].numel() // nens
+    if int(nz) < 1 or n % int(nz) != 0:
+        endrun("member_domain: %d cells per member are not a whole number of columns of nz = %d" % (n, nz))
+    if not 1 <= len(members) <= capi.MW_DOMAIN_MAX_MEMBERS or boxes.shape != (len(members), 5, 2):
+        endrun("member_domain: 1 to %d members and one (5, 2) box for each expected" % capi.MW_DOMAIN_MAX_MEMBERS)
+    if counts is None:
+        counts = torch.empty((len(members), capi.MW_DOMAIN_WORDS), dtype=torch.int64, device=dev)
+    if tuple(counts.shape) != (len(members), capi.MW_DOMAIN_WORDS) or counts.dtype != torch.int64 or not counts.is_contiguous() or counts.device != dev:
+        endrun("member_domain: counts must be a contiguous int64 tensor (%d, %d) on the fields' device" % (len(members), capi.MW_DOMAIN_WORDS))
+    flags = fcounts = cslots = None
+    if guard is not None or slots is not None:
+        if guard is None or slots is None or len(slots) != len(members):
+            endrun("member_domain: a guard and one slot per member go together")
+        slots = [int(s) for s in slots]
+        guard.check_layout("member_domain: ", nz, in5[0], max([0] + slots))
+        flags, fcounts = C.c_void_p(guard.flags.data_ptr()), C.c_void_p(guard.counts.data_ptr())
+        cslots = (C.c_int * len(slots))(*slots)
+    with torch.cuda.device(dev):
+        check(capi.lib().mw_member_domain(int(nz), n // int(nz), nens, len(members), (C.c_int * len(members))(*members),
+                                          boxes.ctypes.data_as(C.POINTER(C.c_double)), _field_ptr_array(list(in5)), C.c_void_p(counts.data_ptr()),
+                                          flags, cslots, fcounts, _stream_ptr(dev)))
+    if guard is not None:
+        guard.flagged_members.update(m for m, s in zip(members, slots) if s >= 0)
+    return counts
 
 
 class CommitteeGuard:
@@ -224,6 +335,7 @@ class CommitteeGuard:
         self.workspace = fit_workspace(None, nbytes, like.device)
         self.max_rainsplit = None                                         # of the last commit (read() decides the counts with it)
         self.flagged_members = set()                                      # the members whose flag bytes may be set
+        self.domain_counts = None                                         # committee_guard_flag's mw_member_domain counts, device (1, 16)
 
     def check_layout(self, who, nz, field, slot=0):
         if int(nz) != self.nz or tuple(field.shape) != self.shape or field.device != self.device or not 0 <= int(slot) < self.counts.shape[0]:

@@ -12,6 +12,11 @@
   --science DIR                 : one small table -- a state and a tendency model trained on the same generate_micro_data samples of a small
                                   supercell (same seeds and epochs), then evaluate_surrogates' rmse over persistence per class and field and
                                   rollout_surrogates' diverged_at and temperature rmse against the Kessler member at the last scoring step.
+  --science DIR --domain-guard  : the rollout also carries a committee of ONE, the tendency model, with guard: {domain: {margin: 0.0}}
+                                   beside the free tendency member, and training_domain: true: recorded are both
+                                  members' temperature rmse at the last scoring step, the guarded member's flagged columns over time
+                                  and both members' first_outside_step.  No threshold: whatever it shows.  --science-only skips the
+                                  timings.
 
 Every timing: one warm-up, then --reps repetitions of --calls back-to-back calls between two device events, the variants alternating
 inside a repetition (parent, state, tendency, parent, ...); medians and ranges.
@@ -199,6 +204,7 @@ def science(a, res):
         open(path, "w").write(YAML.format(nens=1, extra="", **kw))
         _, _, info = driver.run("generate_micro_data", path, max_steps=a.science_steps, quiet=True)
         sample_file = os.path.join(work, "supercell_kessler_data_task_0.nc")
+        print("tendency_timing: science: generated %d samples" % int(info["samples"]), flush=True)
         sci = {"grid": [a.science_n, a.science_n, a.science_nz], "dx": a.science_dx, "generate_steps": a.science_steps, "samples": int(info["samples"]), "epochs": a.science_epochs}
         entries = []
         for form in ("state", "tendency"):
@@ -206,6 +212,7 @@ def science(a, res):
             sci[form + "_val_loss_scaled_label_space"] = r["history"][r["best_model"]]["val_loss"][-1]
             p = r["files_written"]
             entries.append('  - {name: %s, keras_weights_txt: "%s", nn_input_scaling: "%s", nn_output_scaling: "%s"}\n' % (form, p[0], p[1], p[2]))
+        print("tendency_timing: science: trained", flush=True)
         x, y, _ = st.read_samples([sample_file])
         d = st.tendencies(x, y)
         sci["share_of_samples_whose_temperature_label_is_zero"] = float(np.mean(d[:, 0] == 0.0))
@@ -217,13 +224,26 @@ def science(a, res):
         sci["evaluate_rmse_over_persistence"] = {m: {c: {f: rep[m][c][f]["rmse_over_persistence"] for f in ("temp", "water_vapor", "cloud_liquid", "precip_liquid")}
                                                      for c in ("inactive", "active")} for m in ("state", "tendency")}
         sci["evaluate_cells"] = {c: rep["state"][c]["n"] for c in ("inactive", "active")}
+        print("tendency_timing: science: evaluated", flush=True)
         path = os.path.join(work, "rollout.yaml")
-        open(path, "w").write(YAML.format(nens=4, extra=extra + "eval_interval: 100\n", **kw))
+        boxed = "surrogate_committees:\n  - {name: tendency_boxed, members: [tendency], guard: {domain: {margin: 0.0}}}\ntraining_domain: true\n"
+        open(path, "w").write(YAML.format(nens=5 if a.domain_guard else 4, extra=extra + "eval_interval: 100\n" + (boxed if a.domain_guard else ""), **kw))
         driver.run("rollout_surrogates", path, max_steps=a.science_steps, quiet=True)
         doc = json.load(open(os.path.join(work, "surrogate_rollout.json")))
         last = doc["report"][-1]
+        scored = ("state", "tendency", "persistence") + (("tendency_boxed",) if a.domain_guard else ())
         sci["rollout"] = {"steps": doc["steps"], "last_scoring_step": last["step"], "diverged_at": doc["diverged_at"],
-                          "temp_rmse_against_kessler": {m: last["members"][m]["fields"]["temp"]["rmse"] for m in ("state", "tendency", "persistence")}}
+                          "temp_rmse_against_kessler": {m: last["members"][m]["fields"]["temp"]["rmse"] for m in scored}}
+        if a.domain_guard:
+            com = doc["committees"][0]
+            free = [m for m in doc["models"] if m["name"] == "tendency"][0]["domain"]
+            sci["domain_guard"] = {"box": com["guard"]["domain"]["box"], "columns": com["guard"]["columns"],
+                                   "first_outside_step": {"tendency": free["first_outside_step"], "tendency_boxed": com["domain"]["first_outside_step"]},
+                                   "flagged_total": com["guard"]["flagged_total"],
+                                   "tendency_boxed_steps": [[s["step"], s["flagged"], s["outside_columns"], s["rainsplit"]] for s in com["guard"]["steps"]],
+                                   "tendency_outside_columns": [[s["step"], s["outside_columns"]] for s in free["steps"]],
+                                   "temp_rmse_over_time": {m: [[t["step"], t["members"][m]["fields"]["temp"]["rmse"]] for t in doc["report"]]
+                                                           for m in ("tendency", "tendency_boxed", "persistence")}}
         res["science"] = sci
         print(json.dumps({"science": sci}), flush=True)
     finally:
@@ -243,14 +263,19 @@ def main():
     ap.add_argument("--science-nz", type=int, default=32)
     ap.add_argument("--science-steps", type=int, default=4000)
     ap.add_argument("--science-epochs", type=int, default=20)
+    ap.add_argument("--domain-guard", action="store_true", help="with --science: a domain-guarded committee of one beside the free tendency member")
+    ap.add_argument("--science-only", action="store_true", help="with --science: skip the timings")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if (a.domain_guard or a.science_only) and not a.science:
+        sys.exit("tendency_timing: --domain-guard and --science-only go with --science DIR")
     import torch
     if not torch.cuda.is_available():
         sys.exit("tendency_timing: no GPU (a CPU run gives no timing)")
     res = {"tag": a.tag, "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "nx": NX, "ny": NY, "nz": NZ, "members": NENS,
            "models": NMODELS, "reps": a.reps, "calls_per_repetition": a.calls, "parent_lib": bool(a.parent_lib)}
-    timings(a, res)
+    if not a.science_only:
+        timings(a, res)
     out = a.out or os.path.join(ROOT, "profiles", "tendency_form_%s.json" % a.tag)
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
 
@@ -265,6 +290,9 @@ def main():
             res["science_error"] = "%s: %s" % (type(e).__name__, e)
             print(json.dumps({"science_error": res["science_error"]}), flush=True)
         write()
+    if a.science_only:
+        print("wrote", out)
+        return
     cols = ("parent", "state", "tendency", "tendency_variant")
     print("%-22s" % "ms per call" + "".join(" %28s" % k for k in cols))
     for key in ("mlp_forward", "mlp_stencil_forward", "members_apply"):
