@@ -740,6 +740,28 @@ int  mw_member_gather_samples(int nz, long long ncol, int nens, const double *co
 int  mw_member_domain(int nz, long long ncol, int nens, int nm, const int *members, const double *box, const double *const *in5,
                       long long *counts, unsigned char *flags, const int *slots, long long *flag_counts, void *stream);
 
+/* ---- harvest outside the training box: the member sampler with a third class --------------------------- */
+/* mw_member_sample_mask with the classes OUTSIDE, ACTIVE, INACTIVE, element t = (k * ncol + col) * nens + e as there.
+ * members: HOST, nm (1 .. 32) distinct members in [0, nens), nens <= 64.  box: HOST (nm, 5, 2) fp64 [lo, hi] per listed member and
+ * fields5 field (mw_member_domain's layout and rule: lo <= hi, NaN refused, +-inf allowed).  above: HOST, nm ints; non-zero: the
+ * member's model reads the level above (a stencil model), and the four values of that level are tested too.  thr: HOST (nm, 3) fp64 in
+ * [0, 1], the rates of the classes outside, active, inactive.  Box, thresholds and bits travel in the kernel arguments (3.5 KB).
+ * An element of listed member members[j] is ELIGIBLE iff all fourteen values of its sample record -- the five inputs at t, the four of
+ * temp, water_vapor, cloud_liquid, precip_liquid at `up` (t + ncol * nens, or t itself at the top level), the four teacher values -- are
+ * finite AS fp32 (mw_member_sample_mask's test).  An eligible element is OUTSIDE iff some fields5[f][t] is < lo or > hi of box[j][f],
+ * or, with above[j], some fields5[f][up], f in {0, 2, 3, 4}, against the same row (a value equal to a bound and -0.0 against lo = 0.0
+ * are inside); otherwise ACTIVE iff any of the four |teacher - input| > 1e-10, else INACTIVE.
+ * counts: DEVICE int64 (nm, 6), SET by the call (a memset in stream order, then integer adds): the eligible elements outside, active,
+ * inactive, then the taken ones in the same order.  An element is taken iff it is eligible and u01(key0 + t) < thr[j][class].
+ * mask: DEVICE bytes (nz, ncol, nens), 1 for a taken element, 0 for every other, unlisted members included; NULL: count only, nothing
+ * but counts is written.
+ * Asynchronous on `stream`, no allocation, no host synchronisation, integer atomics only: every result is independent of order and
+ * run-to-run identical.  Refused, with nothing launched and nothing written: mw_member_sample_mask's refusals (mask apart), a bad box,
+ * a threshold that is NaN or outside [0, 1], counts NULL.  13 eight-byte loads per element of the listed members. */
+int  mw_member_sample_mask_domain(int nz, long long ncol, int nens, int nm, const int *members, const double *box, const int *above,
+                                  const double *const *fields5, const double *const *teacher4, unsigned long long key0, const double *thr,
+                                  unsigned char *mask, long long *counts, void *stream);
+
 /* ---- DataManager validators ---------------------------------------------------------------------------- */
 /* core::DataManager::validate / validate_nan / validate_inf / validate_pos (model/core/DataManager.h:385-483) -- the reference's only
  * built-in health check: it copies an entry to the host and loops over it.  Here ONE device pass over the entry's `n` elements

@@ -15,6 +15,7 @@ MW_ROLLOUT_MAX_MEMBERS = 30
 MW_COMMITTEE_MAX_MODELS = 16
 MW_RAIN_MAX_FIELDS, MW_RAIN_MAX_THRESHOLDS = 4, 8          # mw_member_rain_table
 MW_DOMAIN_MAX_MEMBERS, MW_DOMAIN_WORDS = 32, 16            # mw_member_domain
+MW_SAMPLE_CLASSES, MW_SAMPLE_WORDS = 3, 6                  # mw_member_sample_mask_domain: outside, active, inactive; eligible then taken
 DATA_THERMAL, DATA_SUPERCELL, DATA_CITY, DATA_BUILDING = 0, 1, 2, 3
 BC_PERIODIC, BC_OPEN, BC_WALL = 0, 1, 2
 INIT_IDS = {"thermal": DATA_THERMAL, "supercell": DATA_SUPERCELL, "city": DATA_CITY, "building": DATA_BUILDING}
@@ -190,6 +191,9 @@ SYMBOLS = {
                                   C.c_void_p]),
     "mw_member_sample_mask": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                         C.c_ulonglong, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "mw_member_sample_mask_domain": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                               C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_ulonglong,
+                                               C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mw_member_gather_samples": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_longlong,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "mw_member_domain": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_void_p),

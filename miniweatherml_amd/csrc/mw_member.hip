@@ -8,7 +8,8 @@
 // of a member go to Kessler, and the commit of the scratch result into the state.  mw_member_column_water / mw_member_surface_rain /
 // mw_member_rain_table are every member's surface rain from its column water budget and its contingency table.
 // mw_member_domain counts the cells of the listed members that lie outside the box their models were trained in, and flags their columns
-// for the guarded committee's Kessler pass.
+// for the guarded committee's Kessler pass.  mw_member_sample_mask_domain is the member sampler with a third class, the
+// cells outside the member's box, and the counts of every class that fix its rate.
 // =====================================================================================================
 #include "../../include/mw_cdna4.h"
 #include "mw_common.h"
@@ -414,6 +415,87 @@ __global__ __launch_bounds__(256) void k_member_domain(int nz, long long plane, 
   }
 }
 
+// ---- mw_member_sample_mask_domain ---------------------------------------------------------------------------------------------------
+constexpr int SAMPLE_CLASSES = 3;          // outside the member's box, active, inactive
+constexpr int SAMPLE_WORDS = 2 * SAMPLE_CLASSES;   // per listed member: eligible per class, then taken per class
+
+struct SampleDomainArgs {
+  const double *in[5], *teach[4];
+  double box[DOMAIN_MAX_MEMBERS][5][2];    // [listed member][field][lo, hi]
+  double thr[DOMAIN_MAX_MEMBERS][SAMPLE_CLASSES];
+  unsigned int above;                      // bit j: listed member j's model reads the level above, whose four values are tested too
+  signed char listed_at[64];               // member e is box / thr / counts row listed_at[e], -1: not listed
+};
+// 72 + 2560 + 768 + 4 (+ 4 padding) + 64 = 3472 bytes, and 48 of scalars and pointers beside it: under the 4 KB of kernel arguments
+static_assert(sizeof(SampleDomainArgs) + 48 <= 4096, "SampleDomainArgs no longer fits the kernel arguments: upload it instead");
+
+// lane = flat element t = (k * ncol + col) * nens + e, as in k_member_sample_mask, with a third class in front of its two: an eligible
+// element (all fourteen values of its record finite as fp32) is OUTSIDE if one of its five inputs -- with the member's `above` bit also one
+// of the four values of the level above -- is below lo or above hi of the member's box; otherwise active or inactive as before.  The
+// thirteen loads are issued before the first test, and the tests are joined with | and & on integers (k_member_domain).  Counts: six
+// ballots per wavefront (eligible and taken per class), one ballot per listed member for its lanes, popcounts in lanes 0 .. 5 and LDS
+// integer adds into the block's row of that member; then one global atomicAdd per non-zero word and block.  The grid is capped
+// (SAMPLE_MAX_BLOCKS) and a block strides over the elements: with one block per 256 elements a 400 x 400 x 100 x 8 state issues 18 million
+// global atomics onto 36 words, which cost five times the loads.  Integer adds only: any order, the same numbers.
+constexpr int SAMPLE_MAX_BLOCKS = 256 * 16;
+
+__global__ __launch_bounds__(256) void k_member_sample_mask_domain(SampleDomainArgs A, long long n, long long plane, int nens, int nm,
+                                                                   unsigned long long key0, unsigned char *__restrict__ mask,
+                                                                   unsigned long long *__restrict__ counts) {
+  __shared__ unsigned int rows[DOMAIN_MAX_MEMBERS * SAMPLE_WORDS];
+  const int lane = threadIdx.x & 63;
+  for (int w = threadIdx.x; w < nm * SAMPLE_WORDS; w += 256) rows[w] = 0u;
+  __syncthreads();
+  for (long long first = (long long)blockIdx.x * 256; first < n; first += (long long)gridDim.x * 256) {     // (block-uniform: the ballots see whole wavefronts)
+    const long long t = first + threadIdx.x;
+    const int j = t < n ? (int)A.listed_at[(int)(t % nens)] : -1;
+    int cls = -1, take = 0;                                                 // cls < 0: not eligible (or not listed, or past the end)
+    if (j >= 0) {
+      const long long up = (t + plane < n) ? t + plane : t;                 // level min(nz - 1, k + 1) of the same column and member
+      const int before[4] = {0, 2, 3, 4};                                   // the input that teacher value v replaces
+      double x[5], u[4], b[4], lo[5], hi[5];
+#pragma unroll
+      for (int f = 0; f < 5; f++) { x[f] = A.in[f][t]; lo[f] = A.box[j][f][0]; hi[f] = A.box[j][f][1]; }
+#pragma unroll
+      for (int v = 0; v < 4; v++) { u[v] = A.in[before[v]][up]; b[v] = A.teach[v][t]; }
+      __builtin_amdgcn_sched_barrier(0);
+      const int ab = (int)((A.above >> j) & 1u);
+      int fin = (int)f32_finite(x[1]), act = 0, out = 0;
+#pragma unroll
+      for (int f = 0; f < 5; f++) out |= (int)(x[f] < lo[f]) | (int)(x[f] > hi[f]);
+#pragma unroll
+      for (int v = 0; v < 4; v++) {
+        const double a = x[before[v]];
+        act |= (int)(fabs(b[v] - a) > 1.e-10);
+        fin &= (int)f32_finite(a) & (int)f32_finite(b[v]) & (int)f32_finite(u[v]);
+        out |= ((int)(u[v] < lo[before[v]]) | (int)(u[v] > hi[before[v]])) & ab;
+      }
+      if (fin) {
+        cls = out ? 0 : act ? 1 : 2;
+        take = (int)(u01_from_key(key0 + (unsigned long long)t) < A.thr[j][cls]);
+      }
+    }
+    if (mask && t < n) mask[t] = (unsigned char)take;
+    const unsigned long long e0 = __ballot(cls == 0), e1 = __ballot(cls == 1), e2 = __ballot(cls == 2);
+    const unsigned long long t0 = __ballot(take && cls == 0), t1 = __ballot(take && cls == 1), t2 = __ballot(take && cls == 2);
+    const unsigned long long mine = lane == 0 ? e0 : lane == 1 ? e1 : lane == 2 ? e2 : lane == 3 ? t0 : lane == 4 ? t1 : t2;
+    if (e0 | e1 | e2) {
+      for (int jj = 0; jj < nm; jj++) {
+        const unsigned long long lanes = __ballot(j == jj);
+        if (lane < SAMPLE_WORDS) {
+          const unsigned int q = (unsigned int)__popcll(mine & lanes);
+          if (q) atomicAdd(&rows[jj * SAMPLE_WORDS + lane], q);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int w = threadIdx.x; w < nm * SAMPLE_WORDS; w += 256) {
+    const unsigned int q = rows[w];
+    if (q) atomicAdd(counts + w, (unsigned long long)q);
+  }
+}
+
 } // namespace mw
 
 using namespace mw;
@@ -499,6 +581,54 @@ extern "C" int mw_member_sample_mask(int nz, long long ncol, int nens, int nm, c
   const long long plane = ncol * nens, n = plane * nz;
   hipLaunchKernelGGL(k_member_sample_mask, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f, n, plane, nens, listed, key0,
                      thr_active, thr_inactive, mask);
+  MW_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mw_member_sample_mask_domain(int nz, long long ncol, int nens, int nm, const int *members, const double *box, const int *above,
+                                            const double *const *fields5, const double *const *teacher4, unsigned long long key0,
+                                            const double *thr, unsigned char *mask, long long *counts, void *stream) {
+  MemberSample f;
+  if (member_sample_fields("member_sample_mask_domain", nz, ncol, nens, fields5, teacher4, &f)) return 1;
+  if (!members || !box || !above || !thr) MW_FAIL("member_sample_mask_domain: null pointer");
+  if (!counts) MW_FAIL("member_sample_mask_domain: null pointer (counts; the mask alone may be null: count only)");
+  if (nm < 1 || nm > DOMAIN_MAX_MEMBERS) MW_FAIL("member_sample_mask_domain: nm must be in [1, " + std::to_string(DOMAIN_MAX_MEMBERS) + "]");
+  if ((double)nz * (double)ncol * (double)nens > 256.0 * 2147483647.0) MW_FAIL("member_sample_mask_domain: the fields are too large");   // (a block's LDS counters are 32-bit)
+  SampleDomainArgs A;
+  for (int v = 0; v < 5; v++) A.in[v] = f.in[v];
+  for (int v = 0; v < 4; v++) A.teach[v] = f.teach[v];
+  A.above = 0u;
+  for (int e = 0; e < 64; e++) A.listed_at[e] = -1;
+  for (int j = 0; j < DOMAIN_MAX_MEMBERS; j++) {
+    for (int c = 0; c < SAMPLE_CLASSES; c++) A.thr[j][c] = 0.0;
+    for (int v = 0; v < 5; v++) { A.box[j][v][0] = -__builtin_inf(); A.box[j][v][1] = __builtin_inf(); }
+  }
+  for (int j = 0; j < nm; j++) {
+    const int e = members[j];
+    if (e < 0 || e >= nens) MW_FAIL("member_sample_mask_domain: member " + std::to_string(e) + " is outside [0, " + std::to_string(nens) + ")");
+    if (A.listed_at[e] >= 0) MW_FAIL("member_sample_mask_domain: member " + std::to_string(e) + " is listed twice");
+    A.listed_at[e] = (signed char)j;
+    for (int v = 0; v < 5; v++) {
+      const double lo = box[(j * 5 + v) * 2], hi = box[(j * 5 + v) * 2 + 1];
+      if (!(lo <= hi)) MW_FAIL("member_sample_mask_domain: the box of member " + std::to_string(e) + ", field " + std::to_string(v) +
+                               ", is not lo <= hi (NaN is refused, +-inf is allowed)");
+      A.box[j][v][0] = lo; A.box[j][v][1] = hi;
+    }
+    for (int c = 0; c < SAMPLE_CLASSES; c++) {
+      const double x = thr[j * SAMPLE_CLASSES + c];
+      if (!(x >= 0.0 && x <= 1.0)) MW_FAIL("member_sample_mask_domain: threshold " + std::to_string(c) + " of member " + std::to_string(e) +
+                                           " is NaN or outside [0, 1]");
+      A.thr[j][c] = x;
+    }
+    if (above[j]) A.above |= 1u << j;
+  }
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  hipStream_t st = (hipStream_t)stream;
+  const long long plane = ncol * nens, n = plane * nz;
+  MW_HIP(hipMemsetAsync(counts, 0, (size_t)nm * SAMPLE_WORDS * 8, st));     // counts is SET: the adds start from zero
+  const long long blocks = std::min<long long>((n + 255) / 256, SAMPLE_MAX_BLOCKS);
+  hipLaunchKernelGGL(k_member_sample_mask_domain, dim3((unsigned)blocks), dim3(256), 0, st, A, n, plane, nens, nm, key0, mask,
+                     (unsigned long long *)counts);
   MW_LAUNCH_CHECK();
   return 0;
 }

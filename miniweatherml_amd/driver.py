@@ -66,6 +66,17 @@ only reads the state.  Inside a committee's guard,
 columns the thresholds flag (a guard may hold only `domain`: a committee of ONE model then has a guard that acts).  Its guard block
 gains `domain` (margin, fields, box) and outside_columns per scoring step; flagged stays the union.  rollout_surrogates and
 inference_ponni honour it.
+    harvest: {interval: 10, samples_per_step: 100, seed: 1, outside: {share: 0.5, margin: 0.0, fields: [temp, water_vapor]}}
+`outside:` (true: share 0.5, margin 0, all five fields) makes the harvester ask `share` of samples_per_step of the cells the member has
+carried OUTSIDE its model's training box -- the only cells whose label the model has never seen.  Their number is
+counted in the call itself, so the rate follows the member; the rest of samples_per_step is drawn from the active and inactive cells as
+before.  The sample files keep their format; the `harvest` block of surrogate_rollout.json gains `outside` (share, margin, fields, the
+members' boxes), `taken` and `eligible` (per member: outside / active / inactive).
+      - {name: tend1, keras_weights_txt: ft/weights.txt, nn_input_scaling: ft/input_scaling.txt, nn_output_scaling: ft/output_scaling.txt,
+         nn_training_domain: ft/training_domain.txt}
+`nn_training_domain` (optional) names the table `surrogate_train --init DIR` writes beside a continued model: per input the minimum and
+maximum over ALL samples the model and the models it continues were trained on, where input_scaling.txt stays the first model's.
+training_domain, a guard's domain and harvest.outside then read the model's box from it, not from the scaling rows.
 """
 import argparse
 import os
@@ -204,13 +215,32 @@ def rollout_config(cfg):
     return models, interval, persistence, nens
 
 
-HARVEST_KEYS = ("interval", "samples_per_step", "ratio_active", "seed", "max_rainsplit", "members")
+HARVEST_KEYS = ("interval", "samples_per_step", "ratio_active", "seed", "max_rainsplit", "members", "outside")
+HARVEST_OUTSIDE_KEYS = ("share", "margin", "fields")
+
+
+def harvest_outside_config(o):
+    """The checked `harvest.outside:` key: true -- share 0.5, margin 0, all five input fields -- or a mapping with
+    `share` (a number in (0, 1], not a bool: the part of samples_per_step asked of the cells outside the member's training box) and
+    domain_config's `margin` and `fields`.  Returns {"share": float, "margin": float, "fields": [names]}."""
+    from .surrogate_eval import domain_config
+    o = {} if o is True else o
+    if not isinstance(o, dict):
+        raise ValueError("ERROR: harvest.outside must be true or a mapping")
+    unknown = sorted(set(o) - set(HARVEST_OUTSIDE_KEYS), key=str)
+    if unknown:
+        raise ValueError("ERROR: unknown key(s) %s in harvest.outside (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(HARVEST_OUTSIDE_KEYS)))
+    share = o.get("share", 0.5)
+    if isinstance(share, bool) or not isinstance(share, (int, float)) or not 0.0 < share <= 1.0:
+        raise ValueError("ERROR: harvest.outside.share must be a number in (0, 1], got %r" % (share,))
+    return dict(share=float(share), **domain_config({k: v for k, v in o.items() if k != "share"}, "harvest.outside"))
 
 
 def harvest_config(cfg):
     """The checked `harvest:` block of a loaded configuration for rollout_surrogates, or None without one: interval (default
     eval_interval), samples_per_step (50), ratio_active (0.5), seed (None: the clock), max_rainsplit (64), members (model names; default all
-    models of the list).  Only that experiment calls it, after rollout_config's checks."""
+    models of the list), and -- only when the YAML has the key -- outside (harvest_outside_config).  Only that experiment calls it, after
+    rollout_config's checks."""
     if "harvest" not in cfg:
         return None
     h = cfg["harvest"]
@@ -247,7 +277,20 @@ def harvest_config(cfg):
             raise ValueError("ERROR: harvest.members names %r, which is no surrogate model (%s)" % (n, ", ".join(names)))
     if len(set(out["members"])) != len(out["members"]):
         raise ValueError("ERROR: harvest.members names a model twice")
+    if "outside" in h and h["outside"] is not False:                        # (false: off, as without the key)
+        out["outside"] = harvest_outside_config(h["outside"])
     return out
+
+
+def harvest_block(harvest, harvester):
+    """The `harvest` block of surrogate_rollout.json: the checked configuration, the harvester's files, samples, skipped and calls, and
+    -- only for a harvester with `outside` -- outside (the configuration with the members' boxes), taken and eligible per member and
+    class (rollout.harvest_outside_report).  Pure Python."""
+    from .rollout import harvest_outside_report
+    block = dict(harvest, files=dict(harvester.files), samples=dict(harvester.samples), skipped=dict(harvester.skipped), calls=harvester.calls)
+    if harvester.outside is not None:
+        block.update(harvest_outside_report(harvester.outside, harvester.member_names, harvester.boxes, harvester.taken, harvester.eligible))
+    return block
 
 
 SURFACE_RAIN_KEYS = ("thresholds_mm_h", "thresholds_mm", "map")
@@ -287,7 +330,8 @@ def training_domain_config(cfg):
 
 def _surrogate_models(entries, yaml_dir):
     """The `surrogate_models:` list: every entry names a model and its three files (relative paths: from the working directory, as the
-    other file keys, else from the YAML file's directory)."""
+    other file keys, else from the YAML file's directory), and optionally `nn_training_domain`, the training_domain.txt of a continued
+    model, which every consumer of the model's box then reads in place of the scaling rows."""
     if not isinstance(entries, list) or not entries:
         raise ValueError("ERROR: surrogate_models must be a non-empty list")
     out = []
@@ -297,7 +341,7 @@ def _surrogate_models(entries, yaml_dir):
         if ("keras_weights_txt" in e) == ("keras_weights_h5" in e):
             raise KeyError("ERROR: surrogate model %r needs exactly one of keras_weights_txt and keras_weights_h5" % e["name"])
         m = {"name": str(e["name"])}
-        for key in ("keras_weights_txt", "keras_weights_h5", "nn_input_scaling", "nn_output_scaling"):
+        for key in ("keras_weights_txt", "keras_weights_h5", "nn_input_scaling", "nn_output_scaling", "nn_training_domain"):
             if key in e:
                 p = str(e[key])
                 if not os.path.isabs(p):
@@ -306,7 +350,7 @@ def _surrogate_models(entries, yaml_dir):
                 if not os.path.exists(p):
                     raise FileNotFoundError("ERROR: surrogate model %r: no file %s" % (e["name"], p))
                 m[key] = p
-            elif key.startswith("nn_"):
+            elif key.startswith("nn_") and key != "nn_training_domain":    # (optional: without it the scaling rows are the domain)
                 raise KeyError("ERROR: surrogate model %r needs '%s'" % (e["name"], key))
         out.append(m)
     if len({m["name"] for m in out}) != len(out):
@@ -438,8 +482,9 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
             base = cfg["_dir"]
             if "_committee" in cfg:                                                # the mean of the committee's models is what runs
                 by_name = {m["name"]: m for m in cfg["surrogate_models"]}
-                micro.init(coupler, committee=mlp.load_surrogate_bank([by_name[n] for n in cfg["_committee"]["members"]]),
-                           guard=cfg["_committee"].get("guard"))
+                entries = [by_name[n] for n in cfg["_committee"]["members"]]
+                bank = mlp.load_surrogate_bank(entries)
+                micro.init(coupler, committee=bank, guard=cfg["_committee"].get("guard"), domains=mlp.load_training_domains(entries, bank))
 
             def rel(p):
                 return p if p is None or os.path.isabs(p) else os.path.normpath(os.path.join(os.getcwd(), p))
@@ -456,8 +501,10 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                 print("inference_ponni: surrogate output form: %s" % info["surrogate_form"], flush=True)
         elif experiment == "rollout_surrogates":
             micro = rollout.Microphysics_Rollout()
-            micro.init(coupler, mlp.load_surrogate_bank(cfg["surrogate_models"]), cfg["persistence_member"],
-                       [m["name"] for m in cfg["surrogate_models"]], [(c["name"], c["members"], c["guard"]) if "guard" in c else (c["name"], c["members"]) for c in committees])
+            bank = mlp.load_surrogate_bank(cfg["surrogate_models"])
+            micro.init(coupler, bank, cfg["persistence_member"],
+                       [m["name"] for m in cfg["surrogate_models"]], [(c["name"], c["members"], c["guard"]) if "guard" in c else (c["name"], c["members"]) for c in committees],
+                       domains=mlp.load_training_domains(cfg["surrogate_models"], bank))
         else:
             micro = microphysics.Microphysics_Kessler()
             micro.init(coupler)                                                # supercell_example/driver.cpp:58
@@ -494,8 +541,15 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
         harvester = None
         if experiment == "rollout_surrogates" and harvest is not None:
             harvester = micro.harvester = rollout.RolloutHarvester()
+            outside = {}
+            if "outside" in harvest:                                           # each harvested model's own box; a stencil model reads the level above
+                o = harvest["outside"]
+                widths = {m["name"]: int(w[0].shape[0]) for m, w in zip(cfg["surrogate_models"], bank)}
+                outside = dict(outside=o, boxes=[micro.model_box(n, o["margin"], o["fields"]) for n in harvest["members"]],
+                               above=[widths[n] == 9 for n in harvest["members"]])
             harvester.init(coupler, harvest["members"], [micro.member_names.index(n) for n in harvest["members"]], os.getcwd(),
-                           harvest["samples_per_step"], harvest["ratio_active"], seed=harvest["seed"], max_rainsplit=harvest["max_rainsplit"])
+                           harvest["samples_per_step"], harvest["ratio_active"], seed=harvest["seed"], max_rainsplit=harvest["max_rainsplit"],
+                           **outside)
 
         def body(dt, etime):                                                   # :73-76
             dycore.time_step(coupler, dt)
@@ -592,9 +646,7 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                     entry["domain"] = blocks[entry["member"]]
                 info["domain_reports"] = {scorer.member_names[m]: b for m, b in enumerate(blocks) if b is not None}
             if harvester is not None:
-                doc["harvest"] = dict(harvest, files=dict(harvester.files), samples=dict(harvester.samples), skipped=dict(harvester.skipped),
-                                      calls=harvester.calls)
-                info["harvest"] = doc["harvest"]
+                doc["harvest"] = info["harvest"] = harvest_block(harvest, harvester)
             if rain is not None:
                 doc["surface_rain"] = dict(rain_cfg, report=rain.times)
                 info["surface_rain_report"], info["rain_total"] = rain.times, micro.rain_total

@@ -105,14 +105,16 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
     last_range = None
     surface_rain = False  # True (with online only): precl after the step is the column water budget of the state left in the coupler
 
-    def init(self, coupler, weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None, committee=None, guard=None):
+    def init(self, coupler, weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None, committee=None, guard=None,
+             domains=None):
         """Single-model files: the model's output form is the one its output scaling file declares (self.form: "state" | "tendency";
         mlp.load_surrogate_model).  committee: a list of 1 .. 16 (W1, b1, W2, b2, scl_in, scl_out) tuples of one width (load_surrogate_weights'
         form, the state form) or SurrogateModel tuples with the form last; a committee may mix the forms.  The network's
         result is then the committee's mean (SurrogateBank.committee_apply), and the weight file arguments are not read.  guard
         (surrogate_eval.guard_config's mapping; with a committee only): the result is the GUARDED committee's step of the state before the
         call -- the mean, and on the columns where the models' range exceeds a threshold what Kessler leaves on those columns alone.  A
-        guard with `domain` hands Kessler the columns with a cell outside the committee's training box too."""
+        guard with `domain` hands Kessler the columns with a cell outside the committee's training box too; domains: None, or
+        per committee model None or its training-domain table (mlp.load_training_domain), which that box is then made of."""
         super().init(coupler)
         self._nn_out = None
         self._committee = None
@@ -132,7 +134,8 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
             self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out, self.form = as_surrogate_model(committee[0])
             if self._guard_cfg is not None and "domain" in self._guard_cfg:
                 from .surrogate_eval import domain_box
-                self._guard_box = domain_box(committee, self._guard_cfg["domain"]["margin"], self._guard_cfg["domain"]["fields"])
+                self._guard_box = domain_box(committee, self._guard_cfg["domain"]["margin"], self._guard_cfg["domain"]["fields"],
+                                             tables=domains)
             return
         self.W1, self.b1, self.W2, self.b2, self.scl_in, self.scl_out, self.form = load_surrogate_model(weights_txt, in_scaling_txt,
                                                                                                         out_scaling_txt, weights_h5)

@@ -223,6 +223,33 @@ def ponni_forward(layers, x, strict=0):
     return out
 
 
+def load_training_domain(path, n_in):
+    """A model's training_domain.txt (surrogate_train --init writes it): n_in rows `min max`, the range of each input
+    over every sample the model and the models it continues were trained on.  Returns the (n_in, 2) fp64 array; a wrong row count, a
+    NaN or a row with min > max is refused with the file's name."""
+    import warnings
+    try:
+        with warnings.catch_warnings():                                        # (an empty file is refused below, by its shape)
+            warnings.simplefilter("ignore")
+            tab = np.atleast_2d(np.loadtxt(path, dtype=np.float64, comments="#"))
+    except (OSError, ValueError) as e:
+        endrun("training domain file %s: %s" % (path, e))
+    if tab.shape != (int(n_in), 2):
+        endrun("training domain file %s: %d rows of `min max` expected, it holds an array %r" % (path, int(n_in), tab.shape))
+    if np.isnan(tab).any():
+        endrun("training domain file %s: row %d holds a NaN" % (path, int(np.argwhere(np.isnan(tab))[0][0])))
+    if (tab[:, 0] > tab[:, 1]).any():
+        endrun("training domain file %s: row %d has min > max" % (path, int(np.argwhere(tab[:, 0] > tab[:, 1])[0][0])))
+    return np.ascontiguousarray(tab)
+
+
+def load_training_domains(entries, models):
+    """Per entry of a `surrogate_models:` list None, or the table its `nn_training_domain` names (load_training_domain, with the row
+    count of the entry's model in `models`): what domain_box takes as `tables`."""
+    return [load_training_domain(e["nn_training_domain"], np.shape(m[4])[0]) if e.get("nn_training_domain") else None
+            for e, m in zip(entries, models)]
+
+
 def load_surrogate_bank(entries):
     """The models of a `surrogate_models:` list (dicts with keras_weights_txt | keras_weights_h5, nn_input_scaling, nn_output_scaling; `name`
     and other keys are ignored) as the list of SurrogateModel tuples that SurrogateBank takes; a model's form is its files'."""

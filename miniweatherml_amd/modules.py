@@ -21,6 +21,8 @@ from .rollout import (RAIN_COUNTS, RAIN_FIELDS, ROLLOUT_FIELDS, ROLLOUT_IN5, ROL
                       RolloutHarvester, RolloutScorer, fields_divergence, kessler_members_teacher, member_column_water, member_divergence,
                       member_rain_table, member_surface_rain, rain_report, rain_scores, rain_thresholds, rollout_member_names, rollout_report)
 from .rollout import box_json, domain_report  # noqa: F401
+from .rollout import SAMPLE_CLASSES, harvest_outside_report, harvest_thresholds, member_sample_mask_domain  # noqa: F401
+from .mlp import load_training_domain, load_training_domains  # noqa: F401
 from .sampling import DataGenerator, StatisticsGatherer  # noqa: F401
 from .surrogate_eval import (EVAL_CLASSES, EVAL_FIELDS, CommitteeEvaluator, CommitteeGuard, SurrogateBank, SurrogateEvaluator, _sums_to_float,  # noqa: F401
                              committee_score, guard_config, json_safe, range_error_correlation, surrogate_scores)

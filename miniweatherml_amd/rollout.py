@@ -79,11 +79,12 @@ class Microphysics_Rollout(Microphysics_Kessler):
     rain_total = None     # with surface_rain: (ny, nx, nens) fp64, metres of water since the first step with the option
     training_domain = None   # None, True or a domain_config mapping: time_step counts the cells outside the box when domain_now is set
     domain_now = False       # (the driver sets it at scoring steps)
+    _domains = None          # per model None or its training-domain table (init's `domains`): the rows domain_box reads
 
     def micro_name(self):
         return "rollout"
 
-    def init(self, coupler, models, persistence=True, names=None, committees=()):
+    def init(self, coupler, models, persistence=True, names=None, committees=(), domains=None):
         """models: (W1, b1, W2, b2, scl_in, scl_out) tuples as load_surrogate_weights returns them (the state form) or SurrogateModel
         tuples with the form last (load_surrogate_model), single-cell and stencil networks and both forms in any order (self.model_forms: the
         forms by name, in the models' order); names: theirs (default model0, model1, ...).  committees: (name, [model names]) pairs; each is one more member after the
@@ -95,6 +96,8 @@ class Microphysics_Rollout(Microphysics_Kessler):
         into ONE mw_member_domain call per step, after the loop of committee_guard_flag.  All guarded members share one scratch
         (CommitteeGuard) and one columns-teacher call per step, so they share one max_rainsplit; every other member keeps the bits it has
         without the guard.
+        domains: None, or per model None or its training-domain table (mlp.load_training_domain), handed to every
+        domain_box this object calls -- the report's boxes and the domain guards' -- in place of the model's scaling rows.
         The coupler must have 1 + len(models) + len(committees) (+ 1 with persistence) members."""
         models = [as_surrogate_model(m) for m in models]
         self.model_forms = [m.form for m in models]
@@ -135,6 +138,9 @@ class Microphysics_Rollout(Microphysics_Kessler):
             self.committees.append((self.banks[widths.index(w)][0], [in_bank.index(names.index(n)) for n in cmodels], 1 + len(models) + ci))
         self.guards = guards                                                   # per committee: the checked guard or None
         self._models, self._model_names, self._committee_names = models, names, committees
+        if domains is not None and len(domains) != len(models):
+            endrun("Microphysics_Rollout: %d domains for %d models (one per model, None where it has none)" % (len(domains), len(models)))
+        self._domains = None if domains is None else list(domains)
         # per committee: the box of a guard with `domain` (refused here, before any step, when the models' ranges do not intersect)
         self._guard_boxes = [self._committee_box(ci, g["domain"]) if g is not None and "domain" in g else None for ci, g in enumerate(guards)]
         self._guard_domain_counts = None                                       # device (domain-guarded members, 16) of the last step
@@ -221,14 +227,23 @@ class Microphysics_Rollout(Microphysics_Kessler):
 
     def _committee_box(self, ci, cfg):
         cname, cmodels = self._committee_names[ci]
-        return domain_box([self._models[self._model_names.index(n)] for n in cmodels], cfg["margin"], cfg["fields"], names=cmodels)
+        places = [self._model_names.index(n) for n in cmodels]
+        return domain_box([self._models[k] for k in places], cfg["margin"], cfg["fields"], names=cmodels, tables=self._tables(places))
+
+    def _tables(self, places):
+        return None if self._domains is None else [self._domains[k] for k in places]
+
+    def model_box(self, name, margin=0.0, fields=IN5):
+        """domain_box of the model called `name` alone, from its training-domain table where it has one."""
+        k = self._model_names.index(str(name))
+        return domain_box([self._models[k]], margin, fields, names=[str(name)], tables=self._tables([k]))
 
     def _domain_setup(self):
         """(the checked training_domain, the network-stepped members, their boxes (members, 5, 2)): every model member with its model's
         box, every committee member with its committee's."""
         if self._domain is None or self._domain[3] is not self.training_domain:
             cfg = domain_config(self.training_domain, "training_domain")
-            boxes = [domain_box([m], cfg["margin"], cfg["fields"], names=[n]) for m, n in zip(self._models, self._model_names)]
+            boxes = [self.model_box(n, cfg["margin"], cfg["fields"]) for n in self._model_names]
             boxes += [self._committee_box(ci, cfg) for ci in range(len(self._committee_names))]
             if not boxes or len(boxes) > capi.MW_DOMAIN_MAX_MEMBERS:
                 endrun("Microphysics_Rollout: training_domain reports 1 to %d network-stepped members, this rollout has %d"
@@ -345,6 +360,64 @@ def kessler_members_teacher(coupler, members, dt, max_rainsplit=64, outs=None, r
     return (outs, [int(rs[j]) for j in range(len(members))]) if return_rainsplit else outs
 
 
+SAMPLE_CLASSES = ("outside", "active", "inactive")      # mw_member_sample_mask_domain's classes, in the order of its thresholds and counts
+
+
+def harvest_thresholds(samples_per_step, ratio_active, prior_active, ncell, share, eligible_outside):
+    """(thr_outside, thr_active, thr_inactive) of a harvest with `outside` -- pure Python.  The part `share` of
+    samples_per_step is asked of the eligible_outside cells that ARE outside the member's box in this call (a count, not a prior: 0 at
+    the start of a rollout, most of the member later); the rest is DataGenerator's two classes at their prior rates, each clamped to 1."""
+    inside = (1 - share) * samples_per_step
+    thr_act, thr_inact = sample_thresholds(ratio_active * inside, (1 - ratio_active) * inside, prior_active, ncell)
+    thr_act, thr_inact = min(1.0, thr_act), min(1.0, thr_inact)
+    thr_out = 0.0 if eligible_outside == 0 else min(1.0, share * samples_per_step / eligible_outside)
+    return thr_out, thr_act, thr_inact
+
+
+def member_sample_mask_domain(nz, fields5, teacher4, members, boxes, above, key0, thr, mask=None, counts=None):
+    """mw_member_sample_mask_domain on the member-fastest fields5 / teacher4 (each (nz, ..., nens), contiguous fp64, one device): for
+    member members[j], its box boxes[j] ((5, 2), domain_box), above[j] (its model reads the level above) and thr[j] = (outside, active,
+    inactive) the six counts -- eligible per class of SAMPLE_CLASSES, then taken per class -- and, with `mask` (uint8, one byte per
+    element), the taken elements.  Returns the DEVICE int64 tensor (len(members), 6), written into `counts` if given; the call SETs it
+    and does not synchronise.  mask=None: count only."""
+    members = [int(m) for m in members]
+    boxes = np.ascontiguousarray(boxes, dtype=np.float64)
+    thr = np.ascontiguousarray(thr, dtype=np.float64)
+    nm, f = len(members), fields5[0]
+    nens, dev = int(f.shape[-1]), f.device
+    if len(fields5) != 5 or len(teacher4) != 4 or any(t.shape != f.shape or t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev
+                                                      for t in list(fields5) + list(teacher4)):
+        endrun("member_sample_mask_domain: five fields and four teacher values, contiguous float64 of one shape (nz, ..., nens) and device, expected")
+    n = f.numel() // nens
+    if int(nz) < 1 or n % int(nz) != 0:
+        endrun("member_sample_mask_domain: %d cells per member are not a whole number of columns of nz = %d" % (n, nz))
+    if not 1 <= nm <= capi.MW_DOMAIN_MAX_MEMBERS or boxes.shape != (nm, 5, 2) or thr.shape != (nm, capi.MW_SAMPLE_CLASSES) or len(above) != nm:
+        endrun("member_sample_mask_domain: 1 to %d members, and a (5, 2) box, an `above` bit and three thresholds for each, expected"
+               % capi.MW_DOMAIN_MAX_MEMBERS)
+    if counts is None:
+        counts = torch.empty((nm, capi.MW_SAMPLE_WORDS), dtype=torch.int64, device=dev)
+    if tuple(counts.shape) != (nm, capi.MW_SAMPLE_WORDS) or counts.dtype != torch.int64 or not counts.is_contiguous() or counts.device != dev:
+        endrun("member_sample_mask_domain: counts must be a contiguous int64 tensor (%d, %d) on the fields' device" % (nm, capi.MW_SAMPLE_WORDS))
+    if mask is not None and (mask.dtype != torch.uint8 or mask.numel() != f.numel() or not mask.is_contiguous() or mask.device != dev):
+        endrun("member_sample_mask_domain: mask must be a contiguous uint8 tensor with one byte per element on the fields' device")
+    with torch.cuda.device(dev):
+        check(capi.lib().mw_member_sample_mask_domain(int(nz), n // int(nz), nens, nm, (C.c_int * nm)(*members),
+                                                      boxes.ctypes.data_as(C.POINTER(C.c_double)), (C.c_int * nm)(*[int(bool(a)) for a in above]),
+                                                      _field_ptr_array(list(fields5)), _field_ptr_array(list(teacher4)), int(key0) % 2 ** 64,
+                                                      thr.ctypes.data_as(C.POINTER(C.c_double)), None if mask is None else C.c_void_p(mask.data_ptr()),
+                                                      C.c_void_p(counts.data_ptr()), _stream_ptr(dev)))
+    return counts
+
+
+def harvest_outside_report(cfg, names, boxes, taken, eligible):
+    """The three blocks `harvest:` gains in surrogate_rollout.json with `outside` -- pure Python: outside (the checked share, margin and
+    fields, and `boxes`: {member: {field: [lo, hi]}}), taken and eligible ({member: {class of SAMPLE_CLASSES: samples / cells}},
+    cumulative over the harvest calls)."""
+    return {"outside": dict(cfg, boxes={str(n): box_json(b) for n, b in zip(names, boxes)}),
+            "taken": {str(n): {c: int(taken[n][c]) for c in SAMPLE_CLASSES} for n in names},
+            "eligible": {str(n): {c: int(eligible[n][c]) for c in SAMPLE_CLASSES} for n in names}}
+
+
 class RolloutHarvester:
     """Data aggregation for the rollout (no reference counterpart): while the candidate models run online as ensemble members, ask the
     teacher -- Kessler -- what it would have done to each model member's OWN state, and keep (state, label) samples of it in one file per
@@ -352,10 +425,15 @@ class RolloutHarvester:
     unchanged).  harvest() is teacher -> mask -> nonzero -> gather -> append; the coupler's state is read, never written."""
 
     def init(self, coupler, member_names, members, directory, samples_per_step=50, ratio_active=0.5, prior_active=0.4, seed=None,
-             max_rainsplit=64):
+             max_rainsplit=64, outside=None, boxes=None, above=None):
         """member_names / members: the harvested model members' names and ensemble indices.  samples_per_step, ratio_active: the wanted
         samples per call and member and the wanted share of active cells among them (DataGenerator's 50 and 0.5); prior_active: the share
-        of active cells assumed when the thresholds are set (DataGenerator's 0.4); seed: call c draws with seed + c (default: the clock)."""
+        of active cells assumed when the thresholds are set (DataGenerator's 0.4); seed: call c draws with seed + c (default: the clock).
+        outside: None, or a mapping {share, margin, fields} -- share in (0, 1] of samples_per_step is asked of the cells
+        outside the member's training box (harvest_thresholds), margin and fields are domain_config's and describe how `boxes` were
+        made: one (5, 2) box per harvested member (domain_box) and, in `above`, one bool per member (its model reads the level above).
+        The harvester then keeps taken[name] and eligible[name] ({class of SAMPLE_CLASSES: count}, cumulative) and last_counts, the raw
+        (live members, 6) array of the last call."""
         import time as _time
         self.member_names, self.members = [str(n) for n in member_names], [int(m) for m in members]
         if len(self.member_names) != len(self.members) or not self.members or len(set(self.members)) != len(self.members) or \
@@ -377,12 +455,40 @@ class RolloutHarvester:
         self._meta_written = False
         self._teacher = None
         self.last_elems = None
+        self.outside = self.boxes = self.above = self.last_counts = None
+        if outside is not None:
+            share = outside.get("share") if hasattr(outside, "get") else None
+            if not hasattr(outside, "keys") or set(outside.keys()) != {"share", "margin", "fields"} or isinstance(share, bool) or \
+                    not isinstance(share, (int, float)) or not 0.0 < share <= 1.0:
+                endrun("RolloutHarvester: outside is None or a mapping {share in (0, 1], margin, fields}")
+            self.outside = dict(share=float(share), **domain_config({k: outside[k] for k in ("margin", "fields")}, "RolloutHarvester: outside"))
+            nm = len(self.members)
+            if boxes is None or above is None or np.shape(boxes) != (nm, 5, 2) or len(above) != nm or nm > capi.MW_DOMAIN_MAX_MEMBERS:
+                endrun("RolloutHarvester: outside needs one (5, 2) box and one `above` bit per harvested member, at most %d members"
+                       % capi.MW_DOMAIN_MAX_MEMBERS)
+            self.boxes, self.above = np.ascontiguousarray(boxes, dtype=np.float64), [bool(a) for a in above]
+            self.taken = {n: {c: 0 for c in SAMPLE_CLASSES} for n in self.member_names}
+            self.eligible = {n: {c: 0 for c in SAMPLE_CLASSES} for n in self.member_names}
+        elif boxes is not None or above is not None:
+            endrun("RolloutHarvester: boxes and above go with outside")
 
     def thresholds(self, coupler):
         """DataGenerator's two formulas (generate_micro_surrogate_data.h:58-62) per member, clamped to 1."""
         thr_act, thr_inact = sample_thresholds(self.ratio_active * self.samples_per_step, (1 - self.ratio_active) * self.samples_per_step,
                                                self.prior_active, coupler.get_nz() * coupler.get_ny() * coupler.get_nx())
         return min(1.0, thr_act), min(1.0, thr_inact)
+
+    def _mask_outside(self, nz, ncol, f5, teacher, live, key0, mask):
+        """The mask of a harvest with `outside`, in two calls of mw_member_sample_mask_domain on the live members: a count-only one, whose
+        eligible-outside words -- this call's one extra synchronising host read -- fix each member's thresholds (harvest_thresholds), then
+        the mask call with them.  self.last_thresholds: (live members, 3); self._counts: the mask call's device counts."""
+        at = [self.member_names.index(n) for n, _ in live]
+        members, boxes, above = [m for _, m in live], self.boxes[at], [self.above[j] for j in at]
+        self._counts = member_sample_mask_domain(nz, f5, teacher, members, boxes, above, key0, np.zeros((len(live), 3)))
+        outside = self._counts.cpu().numpy()[:, 0].tolist()
+        self.last_thresholds = np.array([harvest_thresholds(self.samples_per_step, self.ratio_active, self.prior_active, nz * ncol,
+                                                            self.outside["share"], int(q)) for q in outside], dtype=np.float64).reshape(len(live), 3)
+        member_sample_mask_domain(nz, f5, teacher, members, boxes, above, key0, self.last_thresholds, mask, self._counts)
 
     def harvest(self, coupler, dt, etime):
         """One call: {name: samples added}.  A member the teacher skipped adds none and counts in `skipped`."""
@@ -409,15 +515,26 @@ class RolloutHarvester:
             L = capi.lib()
             mask = torch.empty(nelem, dtype=torch.uint8, device=dev)
             with torch.cuda.device(dev):
-                check(L.mw_member_sample_mask(nz, ncol, nens, len(live), (C.c_int * len(live))(*[m for _, m in live]), _field_ptr_array(f5),
-                                              _field_ptr_array(teacher), key0, thr_act, thr_inact, C.c_void_p(mask.data_ptr()), _stream_ptr(dev)))
+                if self.outside is None:
+                    check(L.mw_member_sample_mask(nz, ncol, nens, len(live), (C.c_int * len(live))(*[m for _, m in live]), _field_ptr_array(f5),
+                                                  _field_ptr_array(teacher), key0, thr_act, thr_inact, C.c_void_p(mask.data_ptr()), _stream_ptr(dev)))
+                else:
+                    self._mask_outside(nz, ncol, f5, teacher, live, key0, mask)
                 elems, n, ins, outs = sample_buffers(mask)                     # ascending, as DataGenerator compacts
                 check(L.mw_member_gather_samples(nz, ncol, nens, _field_ptr_array(f5), _field_ptr_array(teacher), C.c_void_p(elems.data_ptr()), n,
                                                  C.c_void_p(ins.data_ptr()), C.c_void_p(outs.data_ptr()), _stream_ptr(dev)))
             self.last_elems = elems.cpu().numpy()                              # (k * ncol + col) * nens + member of the samples (diagnostic)
             ins, outs, which = ins.cpu().numpy(), outs.cpu().numpy(), self.last_elems % nens
+            if self.outside is not None:                                       # (the stream has been waited for: 48 bytes per member more)
+                self.last_counts = self._counts.cpu().numpy().copy()
+                for (name, _), row in zip(live, self.last_counts):
+                    for c, cname in enumerate(SAMPLE_CLASSES):
+                        self.eligible[name][cname] += int(row[c])
+                        self.taken[name][cname] += int(row[capi.MW_SAMPLE_CLASSES + c])
         else:
             self.last_elems = np.zeros(0, dtype=np.int64)
+            if self.outside is not None:
+                self.last_counts = np.zeros((0, capi.MW_SAMPLE_WORDS), dtype=np.int64)
         for name, m in zip(self.member_names, self.members):
             sel = (which == m) if which is not None else np.zeros(0, dtype=bool)
             a = ins[sel] if which is not None else np.zeros((0, 5, 2), dtype=np.float32)

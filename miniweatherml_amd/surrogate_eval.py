@@ -208,19 +208,28 @@ def domain_config(d, who="domain"):
     return {"margin": float(m), "fields": [f for f in IN5 if f in fields]}
 
 
-def domain_box(models, margin=0.0, fields=IN5, names=None):
+def domain_box(models, margin=0.0, fields=IN5, names=None, tables=None):
     """The box of a model or a committee: (5, 2) fp64 [lo, hi] per IN5 field from the rows of the models' input scaling
     tables, which are the minimum and maximum of each input over the training samples.  A single-cell model gives its rows; a stencil
     model's temp, water_vapor, cloud_liquid and precip_liquid take the intersection of the cell's row and the row of the level above
     (one interval per field at every level: at level 0, whose "level above" the network never sees below it, stricter than necessary);
     several models the intersection over them.  Then [lo - margin * (hi - lo), hi + margin * (hi - lo)] in fp64 as written, and
     [-inf, +inf] for a field not in `fields`.  An empty intersection is refused (ValueError) with the field's and the models' names
-    (names: theirs, default model0, model1, ...)."""
+    (names: theirs, default model0, model1, ...).
+    tables: None, or per model None or its training-domain table (mlp.load_training_domain: the union of what the model and the models it
+    continues were trained on), which then stands in for that model's scaling rows; it may be narrower than they are."""
     models = [as_surrogate_model(m) for m in models]
     if not models:
         raise ValueError("ERROR: domain_box: no models")
     names = ["model%d" % k for k in range(len(models))] if names is None else [str(n) for n in names]
-    tables = [np.asarray(m.scl_in, dtype=np.float64) for m in models]
+    if tables is not None and len(tables) != len(models):
+        raise ValueError("ERROR: domain_box: %d tables for %d models (one per model, None where it has none)" % (len(tables), len(models)))
+    own = [None] * len(models) if tables is None else list(tables)
+    for m, t, n in zip(models, own, names):
+        if t is not None and np.shape(t) != np.shape(m.scl_in):
+            raise ValueError("ERROR: domain_box: the training-domain table of model %s is %r, its input scaling table %r"
+                             % (n, np.shape(t), np.shape(m.scl_in)))
+    tables = [np.asarray(m.scl_in if t is None else t, dtype=np.float64) for m, t in zip(models, own)]
     if len({t.shape for t in tables}) != 1 or tables[0].ndim != 2 or tables[0].shape[1] != 2 or tables[0].shape[0] not in (5, 9):
         raise ValueError("ERROR: domain_box: the models' input scaling tables must be all (5, 2) or all (9, 2)")
     if not (isinstance(margin, (int, float)) and not isinstance(margin, bool) and 0 <= margin < float("inf")):

@@ -256,6 +256,44 @@ def load_init(init, stencil=False):
     return w, np.ascontiguousarray(scl_in, dtype=np.float64), np.ascontiguousarray(scl_out, dtype=np.float64)
 
 
+TRAINING_DOMAIN_FILE = "training_domain.txt"
+
+
+def training_domain_union(data_rows, init_rows):
+    """The rows of a continued model's training_domain.txt: per input the smaller of the two minima and the larger of
+    the two maxima -- data_rows: data_scaling's input table of this run's samples; init_rows: the table of the model that is continued
+    (init_domain).  (n_in, 2) fp64; pure numpy."""
+    a, b = np.asarray(data_rows, dtype=np.float64), np.asarray(init_rows, dtype=np.float64)
+    if a.shape != b.shape or a.ndim != 2 or a.shape[1] != 2:
+        raise SurrogateTrainError("training domain: this run's samples have the input table %r, the continued model's is %r" % (a.shape, b.shape))
+    return np.ascontiguousarray(np.stack([np.minimum(a[:, 0], b[:, 0]), np.maximum(a[:, 1], b[:, 1])], axis=1))
+
+
+def init_domain(init, n_in):
+    """What the model in DIR was trained on, per input [min, max]: DIR/training_domain.txt if DIR's model was itself continued (the union
+    over its ancestors), else DIR/input_scaling.txt, whose rows are the range of its own samples.  Host only."""
+    from .capi import MWError
+    from .mlp import load_training_domain
+    path = os.path.join(os.fspath(init), TRAINING_DOMAIN_FILE)
+    if not os.path.exists(path):
+        path = os.path.join(os.fspath(init), "input_scaling.txt")
+    if not os.path.exists(path):
+        raise SurrogateTrainError("init: no file %s" % path)
+    try:
+        return load_training_domain(path, n_in)
+    except MWError as e:
+        raise SurrogateTrainError("init: %s" % e)
+
+
+def write_training_domain(out_dir, rows):
+    """training_domain.txt in out_dir: `min max` per input, in the scaling files' number format; returns its path."""
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, TRAINING_DOMAIN_FILE)
+    with open(path, "w") as f:
+        f.writelines("%s %s\n" % (_fmt(lo), _fmt(hi)) for lo, hi in np.asarray(rows))
+    return path
+
+
 def init_form(init):
     """The output form of the model in DIR (load_init's): what its output_scaling.txt declares, "state" without a marker.  Host only."""
     from .capi import MWError
@@ -514,8 +552,10 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     evaluate_surrogates driver takes (names seed<seed>; the scaling files are the shared ones).
     init=DIR (a warm start, e.g. on the old sample files and a rollout's harvested ones together): every model starts from DIR/weights.txt
     instead of its seeded draw -- the models then differ by their epoch shuffles only -- and the scaling tables are DIR's, not the data's
-    (samples outside the old range scale outside [0, 1]); the Nadam moments and the step counter start at zero.  The result gains `init`
-    and `initial_weights` (models, 104 | 144).
+    (samples outside the old range scale outside [0, 1]); the Nadam moments and the step counter start at zero.  The result gains `init`,
+    `initial_weights` (models, 104 | 144) and `training_domain` (5 | 9, 2): per input the union of this run's samples' range and DIR's
+    training_domain.txt (DIR's input_scaling.txt if DIR has none) -- what the model has now seen, written to out_dir/training_domain.txt
+    (`training_domain_file`; with keep_all every `surrogate_models` entry names it as nn_training_domain).  DESIGN.md 13.11.
     form="tendency": the network is fitted to the change of the four fields (labels and output table from after - before; module
     docstring); the result, history.json and the written files carry `form`.  The losses and the test metrics are in scaled LABEL space --
     for a tendency model that is the space of the scaled changes, so they do not compare with a state model's.  form=None: "state", or
@@ -525,9 +565,11 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     scl_in, scl_out = data_scaling(inputs, outputs, allow_constant=init is not None, form=form)
     n = inputs.shape[0]
     n_split = check_arguments(n, epochs, batch_size, test_split, validation_split, models)
-    initial = None
+    initial = domain = None
     if init is not None:
-        w0, scl_in, scl_out = load_init(init, stencil)
+        data_in = scl_in
+        w0, scl_in, scl_out = load_init(init, stencil)                                 # (refuses the other width before anything else)
+        domain = training_domain_union(data_in, init_domain(init, data_in.shape[0]))   # this run's samples and all the model saw before
         initial = np.repeat(w0[None, :], int(models), axis=0)
     import torch
     dev = torch.device(device)
@@ -584,7 +626,7 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
               "inputs": "stencil" if stencil else "single_cell", "form": form}
     result.update({k: meta[k] for k in ("time_step_size", "dx", "dy", "dz", "files")})
     if init is not None:
-        result["init"], result["initial_weights"] = os.fspath(init), initial
+        result["init"], result["initial_weights"], result["training_domain"] = os.fspath(init), initial, domain
     if verbose:
         print("Max relative errors:  ", metrics["max_relative_error"])
         print("Mean relative errors: ", metrics["mean_relative_error"])
@@ -597,6 +639,10 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
                                                                                     names=["seed%d" % sd for sd in seeds], form=form)
         else:
             result["files_written"] = write_outputs(out_dir, w[best], scl_in, scl_out, js, form=form)
+        if domain is not None:                                               # the scaling rows stay DIR's; the domain follows the samples
+            result["training_domain_file"] = write_training_domain(out_dir, domain)
+            for m in result.get("surrogate_models", ()):
+                m["nn_training_domain"] = result["training_domain_file"]
     return result
 
 
