@@ -567,6 +567,28 @@ int  mw_surrogate_eval_group(mw_surrogate_bank_t b);
  * grows -- synchronising -- when a call needs more). */
 int  mw_surrogate_eval(mw_surrogate_bank_t b, int nz, long long ncol, const double *const *in5, const double *const *truth4,
                        double *out, long long *counts, void *stream);
+/* mw_surrogate_eval with every model's errors split by whether the cell lies INSIDE or OUTSIDE that model's training box:
+ * how much of a model's one-step error comes from extrapolation.
+ * mw_surrogate_bank_set_domain: box HOST (models, 5, 2) fp64 [lo, hi] per model and in5 field (mw_member_domain's layout and rule: lo <= hi,
+ * NaN refused, +-inf allowed), uploaded into a table the handle owns; synchronises, as mw_surrogate_bank_create does; a later call
+ * replaces the boxes.
+ * A cell is outside for model m iff some tested value x fails lo <= x && x <= hi against m's row of x's field: NaN is outside, a value
+ * equal to a bound is inside (-0.0 against lo = 0.0 too, +-inf against an infinite bound too).  Tested: the cell's five inputs and, for a
+ * bank of width 9, temp, water_vapor, cloud_liquid and precip_liquid of the level above (at the top level the cell itself) against the
+ * same rows.
+ * mw_surrogate_eval_domain_group: the number of models whose predictions the MFMA kernels score per pass over the state.
+ * mw_surrogate_eval_domain: in5, truth4, the classes and the statistics are mw_surrogate_eval's.  out: DEVICE fp64 (models, 2, 2, 2, 4, 4)
+ * = [model][0 prediction | 1 persistence][0 inside | 1 outside][0 inactive | 1 active][field][statistic]; the persistence rows are per
+ * model because the sides are.  counts: DEVICE int64 (models, 2, 2) = [model][side][class].  The tile walk and the reduction order are
+ * mw_surrogate_eval's: with a box no cell leaves, a model's inside rows are that call's bits, and a model's rows depend neither on the
+ * size of the bank, nor on its place in it, nor on the other models' boxes.  A class without cells holds +0.0; NaN reaches the sums and
+ * the maximum of its own class alone.  mw_mlp_set_strict is honoured; nothing is written to in5 / truth4.  Asynchronous on `stream`; one
+ * call at a time per bank (the handle's workspace grows as mw_surrogate_eval's does).  Refused with nothing launched and out / counts
+ * untouched: a null pointer, nz or ncol below 1, a null field, a bank without boxes. */
+int  mw_surrogate_bank_set_domain(mw_surrogate_bank_t b, const double *box);
+int  mw_surrogate_eval_domain_group(mw_surrogate_bank_t b);
+int  mw_surrogate_eval_domain(mw_surrogate_bank_t b, int nz, long long ncol, const double *const *in5, const double *const *truth4,
+                              double *out, long long *counts, void *stream);
 
 /* ---- surrogate rollout: candidate models as ensemble members beside Kessler ------------------------------ */
 /* No reference counterpart (the reference runs one network per simulation, microphysics_kessler_ponni.h:273-276 un-commented).  The

@@ -163,6 +163,9 @@ SYMBOLS = {
     "mw_surrogate_bank_destroy": (None, [C.c_void_p]),
     "mw_surrogate_eval_group": (C.c_int, [C.c_void_p]),
     "mw_surrogate_eval": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mw_surrogate_bank_set_domain": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "mw_surrogate_eval_domain_group": (C.c_int, [C.c_void_p]),
+    "mw_surrogate_eval_domain": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mw_member_extract": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
     "mw_member_insert": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
     "mw_surrogate_members_apply": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),

@@ -77,6 +77,13 @@ members' boxes), `taken` and `eligible` (per member: outside / active / inactive
 `nn_training_domain` (optional) names the table `surrogate_train --init DIR` writes beside a continued model: per input the minimum and
 maximum over ALL samples the model and the models it continues were trained on, where input_scaling.txt stays the first model's.
 training_domain, a guard's domain and harvest.outside then read the model's box from it, not from the scaling rows.
+    eval_domain: true                         # or {margin: 0.05, fields: [temp, water_vapor], box_of: seed0}
+makes evaluate_surrogates split every model's one-step errors by whether the cell lies inside or outside the model's training box
+(surrogate_eval.DomainSplitEvaluator): how much of the error comes from extrapolation.  The boxes are training_domain's
+(`margin`, `fields`, nn_training_domain honoured); `box_of` names one entry of surrogate_models whose box then serves every model, so that
+a continued model and its parent are scored on the same partition.  surrogate_evaluation.json gains a `domain` block (margin, fields,
+box_of, group, per model its box and report, and the per-call history) and a second table is printed; false or absent: no further call
+is made and the document is what it is without the key.
 """
 import argparse
 import os
@@ -109,7 +116,7 @@ def load_config(path):
         if key in cfg:
             out[key] = str(cfg[key])
     out["_dir"] = os.path.dirname(os.path.abspath(path))
-    for key in ("surrogate_models", "eval_interval", "persistence_member", "harvest", "surrogate_committees", "surface_rain", "training_domain"):    # read by surrogate_config / rollout_config / harvest_config / committee_config / surface_rain_config / training_domain_config alone
+    for key in ("surrogate_models", "eval_interval", "persistence_member", "harvest", "surrogate_committees", "surface_rain", "training_domain", "eval_domain"):    # read by surrogate_config / rollout_config / harvest_config / committee_config / surface_rain_config / training_domain_config / eval_domain_key alone
         if key in cfg:
             out[key] = cfg[key]
     return out
@@ -328,6 +335,32 @@ def training_domain_config(cfg):
     return domain_config(b, "training_domain")
 
 
+def eval_domain_key(cfg, model_names):
+    """The checked `eval_domain:` key of a loaded configuration for evaluate_surrogates, or None when it is absent or false
+    (surrogate_eval.eval_domain_config: true or {margin, fields, box_of})."""
+    from .surrogate_eval import eval_domain_config
+    b = cfg.get("eval_domain", False)
+    if b is False or b is None:
+        return None
+    return eval_domain_config(b, model_names)
+
+
+def _domain_split_evaluator(cfg_domain, evaluator, eval_models):
+    """The DomainSplitEvaluator on a SurrogateEvaluator's banks and names: every model's own box (domain_box, its training-domain table
+    honoured), or the box of the entry `box_of` names for all of them."""
+    from . import mlp, surrogate_eval
+    weights = mlp.load_surrogate_bank(eval_models)
+    tables = mlp.load_training_domains(eval_models, weights)
+    names = [m["name"] for m in eval_models]
+    def box(k):
+        return surrogate_eval.domain_box([weights[k]], cfg_domain["margin"], cfg_domain["fields"], names=[names[k]], tables=[tables[k]])
+    if cfg_domain["box_of"] is not None:
+        boxes = [box(names.index(cfg_domain["box_of"]))] * len(names)
+    else:
+        boxes = [box(k) for k in range(len(names))]
+    return surrogate_eval.DomainSplitEvaluator(evaluator.banks, names, boxes)
+
+
 def _surrogate_models(entries, yaml_dir):
     """The `surrogate_models:` list: every entry names a model and its three files (relative paths: from the working directory, as the
     other file keys, else from the YAML file's directory), and optionally `nn_training_domain`, the training_domain.txt of a continued
@@ -439,6 +472,7 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                              "ranks is not built yet" % nranks)
         committees = evaluation_committees(cfg)
         cfg["surrogate_models"], cfg["eval_interval"] = surrogate_config(cfg)
+        eval_domain = eval_domain_key(cfg, [m["name"] for m in cfg["surrogate_models"]])
     if experiment == "inference_ponni" and "surrogate_committees" in cfg and not ("keras_weights_h5" in cfg or "keras_weights_txt" in cfg):
         committees = committee_config(cfg)
         if len(committees) != 1:
@@ -523,6 +557,7 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
         evaluator, eval_calls, eval_step = None, [], [0]
         if experiment == "evaluate_surrogates":
             evaluator, eval_models = _surrogate_evaluator(cfg["surrogate_models"], device)
+            domain_eval = _domain_split_evaluator(eval_domain, evaluator, eval_models) if eval_domain is not None else None
             committee_evals = []                                               # (committee, its evaluator on the bank of its width)
             for c in committees:
                 places = [[m["name"] for m in eval_models].index(n) for n in c["members"]]
@@ -559,6 +594,8 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                     coupler.clone_into(inp)
                     micro.time_step(coupler, dt)
                     evaluator.accumulate(inp, coupler)
+                    if domain_eval is not None:
+                        domain_eval.accumulate(inp, coupler)
                     for _, ce in committee_evals:
                         ce.accumulate(inp, coupler)
                     eval_calls.append({"step": eval_step[0], "etime": etime})
@@ -620,12 +657,21 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
                 doc["committees"] = [dict(c, n_in=ce.bank.n_in, statistics=["sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_r", "sum_r2", "sum_r_abs_d"],
                                           report=ce.report() if eval_calls else {}, history=ce.history) for c, ce in committee_evals]
                 info["committee_reports"] = {c["name"]: d["report"] for (c, _), d in zip(committee_evals, doc["committees"])}
+            if domain_eval is not None:
+                drep = domain_eval.report() if eval_calls else {}
+                doc["domain"] = dict(eval_domain, group={str(b.n_in): b.domain_group for b in evaluator.banks},
+                                     models={n: {"box": surrogate_eval.box_json(domain_eval.boxes[k]), "report": drep.get(n, {})}
+                                             for k, n in enumerate(domain_eval.names)},
+                                     history=[dict(c, banks=h) for c, h in zip(eval_calls, domain_eval.history)])
+                info["domain_report"] = drep
             info["surrogate_evaluation"] = os.path.join(os.getcwd(), "surrogate_evaluation.json")
             with open(info["surrogate_evaluation"], "w") as f:
                 json.dump(doc, f, indent=1)
             info["surrogate_report"] = rep
             if not quiet and rep:
                 print(evaluator.table(rep), flush=True)
+                if domain_eval is not None:
+                    print(domain_eval.table(drep), flush=True)
                 for c, ce in committee_evals:
                     print(ce.table(name=c["name"]), flush=True)
         if scorer is not None:

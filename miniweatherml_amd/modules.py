@@ -27,3 +27,4 @@ from .sampling import DataGenerator, StatisticsGatherer  # noqa: F401
 from .surrogate_eval import (EVAL_CLASSES, EVAL_FIELDS, CommitteeEvaluator, CommitteeGuard, SurrogateBank, SurrogateEvaluator, _sums_to_float,  # noqa: F401
                              committee_score, guard_config, json_safe, range_error_correlation, surrogate_scores)
 from .surrogate_eval import DOMAIN_CLASSES, domain_box, domain_config, member_domain  # noqa: F401
+from .surrogate_eval import EVAL_SIDES, DomainSplitEvaluator, domain_scores, domain_split_report, eval_domain_config  # noqa: F401

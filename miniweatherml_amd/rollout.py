@@ -22,8 +22,8 @@ from .microphysics import Microphysics_Kessler, column_water, surface_rain_finis
 from .mlp import IN5, OUT4, as_surrogate_model
 from .ncio import sample_file_append, sample_file_create
 from .sampling import sample_buffers, sample_thresholds
-from .surrogate_eval import (DOMAIN_CLASSES, CommitteeGuard, SurrogateBank, domain_box, domain_config, finite_or_none, guard_config, json_safe,
-                             member_domain, or_dash, skill_cell)
+from .surrogate_eval import (DOMAIN_CLASSES, CommitteeGuard, SurrogateBank, box_json, domain_box, domain_config, finite_or_none, guard_config,  # noqa: F401
+                             json_safe, member_domain, or_dash, skill_cell)
 
 ROLLOUT_FIELDS = ("density_dry", "uvel", "vvel", "wvel", "temp", "water_vapor", "cloud_liquid", "precip_liquid")
 ROLLOUT_STATS = ("sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_x", "min_x", "max_x")
@@ -304,11 +304,6 @@ class Microphysics_Rollout(Microphysics_Kessler):
             if "domain" in g:
                 out[-1]["domain"] = dict(g["domain"], box=box_json(self._guard_boxes[ci]))
         return out
-
-
-def box_json(box):
-    """A (5, 2) box as {field: [lo, hi]} with inf as a string (json_safe)."""
-    return {f: json_safe([float(box[i][0]), float(box[i][1])]) for i, f in enumerate(IN5)}
 
 
 def domain_report(cfg, box, cells, columns, records):

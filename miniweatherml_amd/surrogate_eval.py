@@ -2,6 +2,7 @@
 those of experiments/supercell_kessler_surrogate/custom_modules/microphysics_kessler_ponni.h:97-202):
 
   SurrogateBank                        mw_surrogate_bank_t: K networks of one width on the device; evaluate, members_apply, committee_apply
+  eval_domain_config, DomainSplitEvaluator   the evaluation split by inside / outside each model's training box (mw_surrogate_eval_domain)
   surrogate_scores, SurrogateEvaluator exact accumulation of mw_surrogate_eval's statistics, report and table
   committee_score, CommitteeEvaluator  mw_committee_score: the committee's mean and range against the truth
   json_safe, finite_or_none, skill_cell, the exact-sum helpers: pure numpy / Python, shared with the rollout's reports"""
@@ -59,8 +60,11 @@ class SurrogateBank:
                                                             scl_out.ctypes.data_as(C.POINTER(C.c_double)), forms))
         self._h = h
         self.group = int(capi.lib().mw_surrogate_eval_group(h))           # models per pass over the state
+        self.domain_group = int(capi.lib().mw_surrogate_eval_domain_group(h))   # ... whose predictions evaluate_domain scores per pass
         self.strict = 0                                                   # 1: the thread-per-cell kernels (mw_mlp_set_strict)
         self._buf = None
+        self.boxes = None                                                 # set_domain's (K, 5, 2) boxes
+        self._dbuf = None
 
     def __del__(self):
         try:                                                              # (at interpreter exit the module's globals may be gone)
@@ -92,6 +96,37 @@ class SurrogateBank:
         check(rc)
         stats, counts = buf.host()
         return stats.reshape(self.models + 1, 2, 4, 4), counts
+
+    def set_domain(self, boxes):
+        """mw_surrogate_bank_set_domain: one (5, 2) box [lo, hi] per model and IN5 field (domain_box), which evaluate_domain splits the
+        cells by; lo <= hi, NaN refused, +-inf allowed.  A later call replaces the boxes."""
+        boxes = np.ascontiguousarray(boxes, dtype=np.float64)
+        if boxes.shape != (self.models, 5, 2):
+            endrun("SurrogateBank.set_domain: one (5, 2) box per model expected, (%d, 5, 2), got %r" % (self.models, boxes.shape))
+        with torch.cuda.device(self.device):
+            check(capi.lib().mw_surrogate_bank_set_domain(self._h, boxes.ctypes.data_as(C.POINTER(C.c_double))))
+        self.boxes = boxes.copy()
+
+    def evaluate_domain(self, nz, in5, truth4):
+        """mw_surrogate_eval_domain on evaluate's arguments, after set_domain.  Returns (stats, counts): the raw (K, 2, 2, 2, 4, 4) fp64
+        array [model][prediction, persistence][inside, outside][inactive, active][field][sum d, sum |d|, sum d^2, max |d|] and the int64
+        cells (K, 2, 2) = [model][side][class] -- one device-to-host copy for both."""
+        if len(in5) != 5 or len(truth4) != 4:
+            endrun("SurrogateBank.evaluate_domain: five input fields and four truth fields expected")
+        n = in5[0].numel()
+        if int(nz) < 1 or n % int(nz) != 0 or any(t.numel() != n for t in list(in5) + list(truth4)):
+            endrun("SurrogateBank.evaluate_domain: the nine fields must have one size, a whole number of columns of nz = %d levels" % nz)
+        dev = self.device
+        if any(t.device != dev for t in list(in5) + list(truth4)):
+            endrun("SurrogateBank.evaluate_domain: the bank lives on %s, the fields on %s" % (dev, sorted({str(t.device) for t in list(in5) + list(truth4)})))
+        buf = StatsAndCounts(self.models * 128, self.models * 4, dev, self._dbuf)
+        self._dbuf = buf.buf
+        with strict_mode(self.strict), torch.cuda.device(dev):
+            rc = capi.lib().mw_surrogate_eval_domain(self._h, int(nz), n // int(nz), _field_ptr_array(in5), _field_ptr_array(truth4),
+                                                     buf.stats_ptr, buf.counts_ptr, _stream_ptr(dev))
+        check(rc)
+        stats, counts = buf.host()
+        return stats.reshape(self.models, 2, 2, 2, 4, 4), counts.reshape(self.models, 2, 2)
 
     def _member_layout(self, who, nz, fields):
         """(columns per member, nens) of member-fastest fields of one shape (nz, ..., nens); refuses, in the caller's name `who`, cells that
@@ -386,6 +421,11 @@ def json_safe(x):
     return x if np.isfinite(x) else str(float(x))
 
 
+def box_json(box):
+    """A (5, 2) box as {field: [lo, hi]} with inf as a string (json_safe)."""
+    return {f: json_safe([float(box[i][0]), float(box[i][1])]) for i, f in enumerate(IN5)}
+
+
 def finite_or_none(row, bad=False):
     """A report's row of statistics (numbers or None): unchanged when every number is finite and `bad` is not set; else the row with None
     for each statistic that is inf or NaN (a diverged model) and "finite": False behind them."""
@@ -523,6 +563,142 @@ class SurrogateEvaluator:
             for cname, row in classes.items():
                 cells = [skill_cell(row[f]["rmse"], row[f]["rmse_over_persistence"]) for f in EVAL_FIELDS]
                 lines.append("%-*s %-8s %12d " % (w, name, cname, row["n"]) + " ".join(cells))
+        return "\n".join(lines)
+
+
+EVAL_SIDES = ("inside", "outside")
+EVAL_DOMAIN_KEYS = DOMAIN_KEYS + ("box_of",)
+
+
+def eval_domain_config(d, model_names, who="eval_domain"):
+    """The checked `eval_domain:` key of evaluate_surrogates: True, or a mapping with domain_config's `margin` and
+    `fields` and, optionally, `box_of`: the name of one of model_names, whose box then serves every model (a continued model and its
+    parent on one partition).  Unknown keys, a box_of that names no model and what domain_config refuses are ValueErrors.  Returns
+    {"margin": float, "fields": [names], "box_of": name or None} -- pure Python."""
+    if d is True:
+        d = {}
+    if not isinstance(d, dict):
+        raise ValueError("ERROR: %s must be true or a mapping" % who)
+    unknown = sorted(set(d) - set(EVAL_DOMAIN_KEYS), key=str)
+    if unknown:
+        raise ValueError("ERROR: unknown key(s) %s in %s (known: %s)" % (", ".join(map(repr, unknown)), who, ", ".join(EVAL_DOMAIN_KEYS)))
+    box_of = d.get("box_of")
+    if box_of is not None and (not isinstance(box_of, str) or box_of not in [str(n) for n in model_names]):
+        raise ValueError("ERROR: %s.box_of must name one of surrogate_models (%s), got %r" % (who, ", ".join(map(str, model_names)), box_of))
+    return dict(domain_config({k: v for k, v in d.items() if k != "box_of"}, who), box_of=box_of)
+
+
+def domain_scores(stats, counts):
+    """One raw result of SurrogateBank.evaluate_domain in surrogate_scores' accumulating form: `sums` (K, 2, 2, 2, 4, 3) exact integers in
+    units of 2^-1074, `nonfinite` the same shape, `max` (K, 2, 2, 2, 4), `counts` (K, 2, 2) and the number of calls."""
+    return surrogate_scores(stats, counts)
+
+
+def domain_split_report(names, boxes, result):
+    """DomainSplitEvaluator.report from accumulated results alone -- pure numpy.  names: the models', bank after bank; boxes: their (5, 2)
+    boxes; result: one domain_scores dict per bank."""
+    rep, first = {}, 0
+    classes = EVAL_CLASSES + ("all",)
+    for r in result:
+        sums, nonf, mx, cnt = r["sums"], r["nonfinite"], r["max"], r["counts"]
+        # class axis (3) -> (inactive, active, all)
+        sums3 = np.concatenate([sums, sums.sum(axis=3, keepdims=True)], axis=3)
+        nonf3 = np.concatenate([nonf, nonf.sum(axis=3, keepdims=True)], axis=3)
+        s3 = _sums_to_float(sums3, nonf3)
+        mx3 = np.concatenate([mx, mx.max(axis=3, keepdims=True)], axis=3)
+        n3 = np.concatenate([cnt, cnt.sum(axis=2, keepdims=True)], axis=2)                         # (K, side, 3)
+        for m in range(sums.shape[0]):
+            box = np.asarray(boxes[first + m], dtype=np.float64)
+            entry = {"box": box_json(box)}
+            for sd, sname in enumerate(EVAL_SIDES):
+                entry[sname] = {}
+                for c, cname in enumerate(classes):
+                    n = int(n3[m, sd, c])
+                    row = {"n": n}
+                    for v, fname in enumerate(EVAL_FIELDS):
+                        if n > 0:
+                            with np.errstate(divide="ignore", invalid="ignore"):
+                                per, pers = s3[m, 0, sd, c, v] / n, s3[m, 1, sd, c, v] / n
+                                rmse, prmse = np.sqrt(per[2]), np.sqrt(pers[2])
+                            row[fname] = finite_or_none({"bias": float(per[0]), "mae": float(per[1]), "rmse": float(rmse),
+                                                         "max_abs": float(mx3[m, 0, sd, c, v]),
+                                                         "rmse_over_persistence": float(rmse / prmse) if prmse > 0 else None})
+                        else:
+                            row[fname] = {"bias": None, "mae": None, "rmse": None, "max_abs": None, "rmse_over_persistence": None}
+                    entry[sname][cname] = row
+            share = {}
+            for c, cname in enumerate(classes):
+                share[cname] = {}
+                for v, fname in enumerate(EVAL_FIELDS):
+                    ins, out = int(sums3[m, 0, 0, c, v, 2]), int(sums3[m, 0, 1, c, v, 2])
+                    bad = nonf3[m, 0, 0, c, v, 2] != 0.0 or nonf3[m, 0, 1, c, v, 2] != 0.0
+                    share[cname][fname] = None if bad or ins + out == 0 else out / (ins + out)           # int / int: correctly rounded
+            entry["outside_share_of_squared_error"] = share
+            rep[str(names[first + m])] = entry
+        first += sums.shape[0]
+    return rep
+
+
+class DomainSplitEvaluator:
+    """SurrogateEvaluator with every model's errors split by inside / outside its training box: how much of a model's
+    one-step error comes from extrapolation.  banks, names: SurrogateEvaluator's; boxes: one (5, 2) box per model, bank after bank
+    (domain_box), handed to the banks here.  accumulate(inp, out) call after call, report() at the end; the sums are exact integers in
+    units of 2^-1074, so combine is order-free."""
+
+    def __init__(self, banks, names, boxes):
+        self.banks = list(banks)
+        self.names = [str(n) for n in names]
+        if len(self.names) != sum(b.models for b in self.banks):
+            endrun("DomainSplitEvaluator: %d names for %d models" % (len(self.names), sum(b.models for b in self.banks)))
+        if len(set(self.names)) != len(self.names):
+            endrun("DomainSplitEvaluator: model names must be unique")
+        self.boxes = np.ascontiguousarray(boxes, dtype=np.float64)
+        if self.boxes.shape != (len(self.names), 5, 2):
+            endrun("DomainSplitEvaluator: one (5, 2) box per model expected, got %r" % (self.boxes.shape,))
+        first = 0
+        for b in self.banks:
+            b.set_domain(self.boxes[first:first + b.models])
+            first += b.models
+        self.total = None
+        self.history = []               # per call: the raw statistics and counts of every bank
+
+    @staticmethod
+    def combine(a, b):
+        """SurrogateEvaluator.combine on domain_scores dicts: sums add, maxima take the larger, counts and calls add."""
+        return SurrogateEvaluator.combine(a, b)
+
+    def accumulate(self, inp, out):
+        """Runs every bank's evaluate_domain on (inp, out) and adds the call to the running total; returns the call's own result."""
+        in5 = [inp.get_data_manager_readonly().get(n, True) for n in IN5]
+        truth4 = [out.get_data_manager_readonly().get(n, True) for n in EVAL_FIELDS]
+        raw = [bank.evaluate_domain(inp.get_nz(), in5, truth4) for bank in self.banks]
+        self.history.append([{"stats": json_safe(s.tolist()), "counts": c.tolist()} for s, c in raw])
+        one = [domain_scores(s, c) for s, c in raw]
+        self.total = one if self.total is None else self.combine(self.total, one)
+        return one
+
+    def report(self, result=None):
+        """Per model: its box; per side (inside, outside), class (inactive, active, all) and field n, bias, mae, rmse, max_abs and
+        rmse_over_persistence against the persistence rows of the same model, side and class; and per class and field
+        outside_share_of_squared_error = sum d^2 outside / (inside + outside) from the exact integers (None when both are 0 or one is
+        not finite).  Empty classes and non-finite statistics as in SurrogateEvaluator.report: None, "finite": False."""
+        result = self.total if result is None else result
+        if result is None:
+            endrun("DomainSplitEvaluator.report: nothing accumulated")
+        return domain_split_report(self.names, self.boxes, result)
+
+    def table(self, rep=None):
+        """report() as text: one line per model, side and class; rmse / persistence rmse per field, then the outside share of sum d^2."""
+        rep = self.report() if rep is None else rep
+        w = max(len(k) for k in rep)
+        lines = ["%-*s %-8s %-8s %12s " % (w, "model", "side", "class", "n") + " ".join("%26s" % ("%s rmse (/pers.)" % f) for f in EVAL_FIELDS)]
+        for name, entry in rep.items():
+            for sname in EVAL_SIDES:
+                for cname, row in entry[sname].items():
+                    cells = [skill_cell(row[f]["rmse"], row[f]["rmse_over_persistence"]) for f in EVAL_FIELDS]
+                    lines.append("%-*s %-8s %-8s %12d " % (w, name, sname, cname, row["n"]) + " ".join(cells))
+            for cname, row in entry["outside_share_of_squared_error"].items():
+                lines.append("%-*s %-8s %-8s %12s " % (w, name, "share", cname, "") + " ".join("%26s" % or_dash(row[f], "%.4f") for f in EVAL_FIELDS))
         return "\n".join(lines)
 
 
