@@ -533,6 +533,31 @@ int  mw_surrogate_prepare_form(int form, int n_in, long long n, const float *raw
                                float *train_y, float *val_x, float *val_y, float *test_x, float *test_y, void *stream);
 long long mw_surrogate_errors_workspace_bytes(int nsets);
 int  mw_surrogate_errors(long long n, int nsets, const float *pred, const float *y, void *workspace, double *out, void *stream);
+/* Weighted training: Keras' fit(sample_weight=...) under the default sum_over_batch_size reduction.  None of
+ * these kernels inspects a weight: finite, non-negative and not all zero are the host's checks (surrogate_train.check_weights).  A NaN
+ * weight gives NaN sums, which is what 0 * NaN gives anyway.
+ * mw_surrogate_prepare_column: ONE fp32 value per sample, col (n,) DEVICE, through the pre-shuffle and split of mw_surrogate_prepare_form
+ * with the same seed, n_train and n_val: col[perm[p]] goes to position p of [train_c | val_c | test_c], bits unchanged.  The trainer sends
+ * the samples' weights through it, and the index of each sample's file (a float: exact below 2^24 files; not checked here). */
+int  mw_surrogate_prepare_column(long long n, const float *col, unsigned long long seed, long long n_train, long long n_val, float *train_c,
+                                 float *val_c, float *test_c, void *stream);
+/* mw_surrogate_train_epoch_v2 with sample weights w (n,) fp32 DEVICE, laid out like a row of y (null: refused, the unweighted epoch is
+ * _v2).  The loss of a batch of B samples is sum_i w_i mean_o((y_io - t_io)^2) / B -- the divisor is the batch size, not the sum of the
+ * weights, and the weights are used as given.  stats (models, 2): sum w sum_o (y - t)^2 and sum w sum_o |y - t| over the epoch (Keras'
+ * running `loss`, and mean_absolute_error as a weighted_metrics entry, = these / (4 n)).  With w = 1 the bits of _v2 in every output. */
+int  mw_surrogate_train_epoch_w(int n_in, int models, const float *x, const float *y, const float *w, long long n, int batch, int epoch,
+                                unsigned long long seed, float *params, float *m1, float *m2, const float *table, float beta1, float beta2,
+                                float eps, double *stats, void *stream);
+/* Test aid: mw_surrogate_batch_grad_v2 of the weighted batch routine, w (batch,) DEVICE: the gradient of the loss above, and
+ * loss[0] = sum_i w_i sum_o r_io^2 / (4 batch). */
+int  mw_surrogate_batch_grad_w(int n_in, const float *params, const float *x, const float *y, const float *w, int batch, float *grad,
+                               float *loss, void *stream);
+/* mw_surrogate_errors with sample weights w (n,) fp32 DEVICE shared by the sets: the same 24 numbers per set, the same reduction order
+ * and workspace, every term of the four sums times (double)w_i, both maxima over the samples with w_i > 0 only (a sample of weight zero
+ * does not exist for this call; no such sample at all: maxima 0).  With w = 1 the bits of mw_surrogate_errors; with the indicator of
+ * a group of samples, the unweighted numbers of that group. */
+int  mw_surrogate_errors_weighted(long long n, int nsets, const float *pred, const float *y, const float *w, void *workspace, double *out,
+                                  void *stream);
 
 /* ---- surrogate evaluation in the model loop ------------------------------------------------------------- */
 /* A bank of `models` candidate networks of ONE width, scored against what the microphysics really did to a state: the four `Relative diff`

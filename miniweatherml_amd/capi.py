@@ -159,6 +159,11 @@ SYMBOLS = {
     "mw_surrogate_batch_grad_v2": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mw_surrogate_errors_workspace_bytes": (C.c_longlong, [C.c_int]),
     "mw_surrogate_errors": (C.c_int, [C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mw_surrogate_prepare_column": (C.c_int, [C.c_longlong, C.c_void_p, C.c_ulonglong, C.c_longlong, C.c_longlong] + [C.c_void_p] * 3 + [C.c_void_p]),
+    "mw_surrogate_train_epoch_w": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_ulonglong] +
+                                   [C.c_void_p] * 4 + [C.c_float] * 3 + [C.c_void_p, C.c_void_p]),
+    "mw_surrogate_batch_grad_w": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mw_surrogate_errors_weighted": (C.c_int, [C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mw_surrogate_bank_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "mw_surrogate_bank_destroy": (None, [C.c_void_p]),
     "mw_surrogate_eval_group": (C.c_int, [C.c_void_p]),

@@ -23,6 +23,11 @@
 // (A 32x32x2 tile would hold all 20 rows at once, but 16 accumulator registers per lane with 1024 entries over 256 threads breaks "entry
 // e belongs to thread e", and its 32 columns would be half empty; two 16x16 tiles cost 4 more accumulator registers and 8 KiB less LDS.)
 // The single-cell instantiation (NIN = 5) is the code above, unchanged in every operation.
+//
+// WEIGHTED (k_surrogate_train<NIN, true>, mw_surrogate_train_epoch_w): Keras' sample_weight.  The sample's weight
+// comes with its x and t through the same permuted index (one more 4-byte gather, prefetched with the others) and multiplies its whole D
+// row -- the ten dpre, the four r, sum r^2 and sum |r| -- so that the tile is sum_i w_i A_i^T D_i; A, the MFMAs, the tile sum, the 0.5 / B
+// factor and Nadam are the code of the unweighted instantiation, which has no weight in its Sample, no load and no multiply.
 // =====================================================================================================
 #include "../../include/mw_cdna4.h"
 #include "mw_common.h"
@@ -78,7 +83,7 @@ template <int NIN> constexpr int npar() { return NIN * 10 + 10 + 40 + 4; }      
 struct SetRef { const float *x, *y; long long n; };
 struct Identity { __device__ long long operator()(long long p) const { return p; } };
 struct Shuffled { Feistel F; __device__ long long operator()(long long p) const { return feistel_index(F, p); } };
-template <int NIN> struct Sample { float v[NIN + 4]; };                    // x0..x(NIN-1), t0..t3
+template <int NIN, bool WEIGHTED> struct Sample { float v[NIN + 4 + (WEIGHTED ? 1 : 0)]; };    // x0..x(NIN-1), t0..t3, then the weight
 
 template <int NIN> struct Smem;
 template <> struct Smem<5> {
@@ -92,9 +97,9 @@ template <> struct Smem<9> {
   float G[4][2][TPB];                                                   // the waves' tiles P and Q
 };
 
-// sample at batch position c + threadIdx.x (zero beyond the batch)
-template <int NIN, class Pos>
-__device__ __forceinline__ void fetch(const SetRef &S, const Pos &pos, long long first, int B, int c, Sample<NIN> &s) {
+// sample at batch position c + threadIdx.x (zero beyond the batch); wt (n,): the samples' weights, read by the WEIGHTED instantiation alone
+template <int NIN, bool WEIGHTED, class Pos>
+__device__ __forceinline__ void fetch(const SetRef &S, const float *wt, const Pos &pos, long long first, int B, int c, Sample<NIN, WEIGHTED> &s) {
   const int i = c + (int)threadIdx.x;
   const bool ok = i < B;
   const long long idx = ok ? pos(first + i) : 0;
@@ -102,9 +107,11 @@ __device__ __forceinline__ void fetch(const SetRef &S, const Pos &pos, long long
   for (int f = 0; f < NIN; f++) s.v[f] = ok ? S.x[f * S.n + idx] : 0.f;
 #pragma unroll
   for (int o = 0; o < 4; o++) s.v[NIN + o] = ok ? S.y[o * S.n + idx] : 0.f;
+  if constexpr (WEIGHTED) s.v[NIN + 4] = ok ? wt[idx] : 0.f;
 }
 
-__device__ __forceinline__ void sample_rows(const float *W, const Sample<5> &s, bool ok, float *a, float *d) {
+template <bool WEIGHTED>
+__device__ __forceinline__ void sample_rows(const float *W, const Sample<5, WEIGHTED> &s, bool ok, float *a, float *d) {
   const float *W1 = W, *b1 = W + 50, *W2 = W + 60, *b2 = W + 100;
   float pre[10], h[10], r[4];
 #pragma unroll
@@ -137,6 +144,7 @@ __device__ __forceinline__ void sample_rows(const float *W, const Sample<5> &s, 
       dv = pre[i] > 0.f ? acc : 0.1f * acc;                              // leaky_relu'(pre): 1 above 0, else the slope
     } else if (i < 14) dv = r[i - 10];
     else dv = (i == 14) ? sq : ab;
+    if constexpr (WEIGHTED) dv *= s.v[9];                                 // the whole D row times the sample's weight; A is untouched
     A[i >> 2][i & 3] = ok ? av : 0.f;
     D[i >> 2][i & 3] = ok ? dv : 0.f;
   }
@@ -145,7 +153,8 @@ __device__ __forceinline__ void sample_rows(const float *W, const Sample<5> &s, 
 }
 
 // the stencil model's rows: a = [x0..x8, 1, 0, 0], hrow = [h0..h8, 0, h9, 0] (12 floats each), d as above
-__device__ __forceinline__ void sample_rows(const float *W, const Sample<9> &s, bool ok, float *a, float *hrow, float *d) {
+template <bool WEIGHTED>
+__device__ __forceinline__ void sample_rows(const float *W, const Sample<9, WEIGHTED> &s, bool ok, float *a, float *hrow, float *d) {
   const float *W1 = W, *b1 = W + 90, *W2 = W + 100, *b2 = W + 140;
   float pre[10], h[10], r[4];
 #pragma unroll
@@ -184,6 +193,7 @@ __device__ __forceinline__ void sample_rows(const float *W, const Sample<9> &s, 
       dv = pre[i] > 0.f ? acc : 0.1f * acc;
     } else if (i < 14) dv = r[i - 10];
     else dv = (i == 14) ? sq : ab;
+    if constexpr (WEIGHTED) dv *= s.v[13];
     D[i >> 2][i & 3] = ok ? dv : 0.f;
   }
 #pragma unroll
@@ -202,14 +212,15 @@ __device__ __forceinline__ void wave_sync() {
 // Raw gradient tile entry threadIdx.x of one batch (sum over its samples of A^T D, waves added in order 0..3).  On entry `pf` holds this
 // thread's sample of the batch's first chunk; on exit the sample of the NEXT batch's first chunk (next_B > 0), fetched while this batch's
 // last chunk computes.  Ends with the tile in sm.G (read after a workgroup barrier); the caller barriers before the next call.
-template <class Pos>
-__device__ float batch_tile(Smem<5> &sm, const SetRef &S, const Pos &pos, long long first, int B, long long next_first, int next_B, Sample<5> &pf) {
+template <bool WEIGHTED, class Pos>
+__device__ float batch_tile(Smem<5> &sm, const SetRef &S, const float *wt, const Pos &pos, long long first, int B, long long next_first, int next_B,
+                            Sample<5, WEIGHTED> &pf) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int c0 = 0; c0 < B; c0 += TPB) {
-    const Sample<5> cur = pf;
-    if (c0 + TPB < B) fetch(S, pos, first, B, c0 + TPB, pf);
-    else if (next_B > 0) fetch(S, pos, next_first, next_B, 0, pf);
+    const Sample<5, WEIGHTED> cur = pf;
+    if (c0 + TPB < B) fetch(S, wt, pos, first, B, c0 + TPB, pf);
+    else if (next_B > 0) fetch(S, wt, pos, next_first, next_B, 0, pf);
     sample_rows(sm.W, cur, c0 + tid < B, sm.A[tid], sm.D[tid]);
     wave_sync();
     const float *Aw = sm.A[wave * 64], *Dw = sm.D[wave * 64];
@@ -225,15 +236,15 @@ __device__ float batch_tile(Smem<5> &sm, const SetRef &S, const Pos &pos, long l
 }
 
 // The stencil model's: the tiles P and Q (see the header), the thread's own entry taken from the tile `which` (0 = P, 1 = Q).
-template <class Pos>
-__device__ float batch_tile(Smem<9> &sm, const SetRef &S, const Pos &pos, long long first, int B, long long next_first, int next_B, Sample<9> &pf,
-                            int which) {
+template <bool WEIGHTED, class Pos>
+__device__ float batch_tile(Smem<9> &sm, const SetRef &S, const float *wt, const Pos &pos, long long first, int B, long long next_first, int next_B,
+                            Sample<9, WEIGHTED> &pf, int which) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
   f32x4 accP = {0.f, 0.f, 0.f, 0.f}, accQ = {0.f, 0.f, 0.f, 0.f};
   for (int c0 = 0; c0 < B; c0 += TPB) {
-    const Sample<9> cur = pf;
-    if (c0 + TPB < B) fetch(S, pos, first, B, c0 + TPB, pf);
-    else if (next_B > 0) fetch(S, pos, next_first, next_B, 0, pf);
+    const Sample<9, WEIGHTED> cur = pf;
+    if (c0 + TPB < B) fetch(S, wt, pos, first, B, c0 + TPB, pf);
+    else if (next_B > 0) fetch(S, wt, pos, next_first, next_B, 0, pf);
     sample_rows(sm.W, cur, c0 + tid < B, sm.A[tid], sm.H[tid], sm.D[tid]);
     wave_sync();
     const float *Aw = sm.A[wave * 64], *Hw = sm.H[wave * 64], *Dw = sm.D[wave * 64];
@@ -280,9 +291,10 @@ struct TrainArgs {
   SetRef S; int B; int epoch; uint64_t seed;
   float *params, *m1, *m2; const float *table; double *stats;
   float beta1, beta2, eps;
+  const float *wt;                                                      // (n,) sample weights: the WEIGHTED instantiations' (last: the others' layout stays)
 };
 
-template <int NIN>
+template <int NIN, bool WEIGHTED>
 __global__ __launch_bounds__(TPB) void k_surrogate_train(TrainArgs a) {
   constexpr int NPAR = npar<NIN>();
   __shared__ Smem<NIN> sm;
@@ -296,8 +308,8 @@ __global__ __launch_bounds__(TPB) void k_surrogate_train(TrainArgs a) {
   }
   const Shuffled pos{make_feistel(a.seed + (uint64_t)model, (uint64_t)a.epoch, a.S.n)};
   const long long n = a.S.n, steps = (n + a.B - 1) / a.B;
-  Sample<NIN> pf;
-  fetch(a.S, pos, 0, (int)std::min<long long>(a.B, n), 0, pf);
+  Sample<NIN, WEIGHTED> pf;
+  fetch(a.S, a.wt, pos, 0, (int)std::min<long long>(a.B, n), 0, pf);
   double sq = 0.0, ab = 0.0;
   __syncthreads();
   for (long long s = 0; s < steps; s++) {
@@ -306,8 +318,8 @@ __global__ __launch_bounds__(TPB) void k_surrogate_train(TrainArgs a) {
     const long long nf = first + B;
     const int nB = (int)std::min<long long>(a.B, n - nf);
     float gsum;
-    if constexpr (NIN == 5) gsum = batch_tile(sm, a.S, pos, first, B, nf, nB > 0 ? nB : 0, pf);
-    else gsum = batch_tile(sm, a.S, pos, first, B, nf, nB > 0 ? nB : 0, pf, which);
+    if constexpr (NIN == 5) gsum = batch_tile(sm, a.S, a.wt, pos, first, B, nf, nB > 0 ? nB : 0, pf);
+    else gsum = batch_tile(sm, a.S, a.wt, pos, first, B, nf, nB > 0 ? nB : 0, pf, which);
     if (p >= 0) {                                                       // Nadam (TF 2.x Keras), scalars from the host table
       const float cg = a.table[3 * s], cm = a.table[3 * s + 1], bc2 = a.table[3 * s + 2];
       const float gr = gsum * (0.5f / (float)B);                        // d mean((y - t)^2) = 2 r / (4 B)
@@ -324,19 +336,19 @@ __global__ __launch_bounds__(TPB) void k_surrogate_train(TrainArgs a) {
   else if (p == -3) a.stats[2 * model + 1] = ab;
 }
 
-template <int NIN>
+template <int NIN, bool WEIGHTED>
 __global__ __launch_bounds__(TPB) void k_surrogate_grad(const float *__restrict__ params, SetRef S, int B, float *__restrict__ grad,
-                                                        float *__restrict__ loss) {
+                                                        float *__restrict__ loss, const float *__restrict__ wt) {
   __shared__ Smem<NIN> sm;
   int which = 0;
   const int tid = threadIdx.x, p = NIN == 5 ? param_of_entry(tid) : param_of_entry9(tid, which);
   if (p >= 0) sm.W[p] = params[p];
-  Sample<NIN> pf;
-  fetch(S, Identity(), 0, B, 0, pf);
+  Sample<NIN, WEIGHTED> pf;
+  fetch(S, wt, Identity(), 0, B, 0, pf);
   __syncthreads();
   float gsum;
-  if constexpr (NIN == 5) gsum = batch_tile(sm, S, Identity(), 0, B, 0, 0, pf);
-  else gsum = batch_tile(sm, S, Identity(), 0, B, 0, 0, pf, which);
+  if constexpr (NIN == 5) gsum = batch_tile(sm, S, wt, Identity(), 0, B, 0, 0, pf);
+  else gsum = batch_tile(sm, S, wt, Identity(), 0, B, 0, 0, pf, which);
   if (p >= 0) grad[p] = gsum * (0.5f / (float)B);
   else if (p == -2) loss[0] = gsum / (4.f * (float)B);
 }
@@ -368,10 +380,25 @@ __global__ __launch_bounds__(TPB) void k_surrogate_prepare(PrepArgs a) {
   }
 }
 
+// one fp32 value per sample through k_surrogate_prepare's pre-shuffle and split (the samples' weights, their file index)
+struct ColArgs { long long n, n_train, n_val; Feistel F; const float *col; float *out[3]; };
+__global__ __launch_bounds__(TPB) void k_surrogate_prepare_column(ColArgs a) {
+  const long long stride = (long long)gridDim.x * TPB;
+  for (long long p = (long long)blockIdx.x * TPB + threadIdx.x; p < a.n; p += stride) {
+    const long long src = feistel_index(a.F, p);
+    const int set = p < a.n_train ? 0 : p < a.n_train + a.n_val ? 1 : 2;
+    const long long q = set == 0 ? p : set == 1 ? p - a.n_train : p - a.n_train - a.n_val;
+    a.out[set][q] = a.col[src];
+  }
+}
+
 // ---- error sums of predictions (validation loss, test metrics) ----
+// WEIGHTED: every sum term times (double)w_i, the two maxima over the samples with w_i > 0 (a zero-weight sample does not exist); with
+// w = 1 the bits of the unweighted instantiation (the terms d (d w), w |d|, w d, w |t| are the unweighted ones times an exact 1).
 constexpr int ERR_BLOCKS = 128, NSTAT = 24;
+template <bool WEIGHTED>
 __global__ __launch_bounds__(TPB) void k_surrogate_sums(long long n, const float *__restrict__ pred, const float *__restrict__ y,
-                                                          double *__restrict__ partial) {
+                                                          double *__restrict__ partial, const float *__restrict__ wt) {
   __shared__ double red[NSTAT][TPB];
   const int tid = threadIdx.x, set = blockIdx.y;
   double acc[NSTAT];
@@ -382,8 +409,14 @@ __global__ __launch_bounds__(TPB) void k_surrogate_sums(long long n, const float
 #pragma unroll
     for (int o = 0; o < 4; o++) {
       const double t = y[o * n + i], d = t - (double)ps[o * n + i];
-      acc[6 * o] += d * d; acc[6 * o + 1] += fabs(d); acc[6 * o + 2] += d; acc[6 * o + 3] += fabs(t);
-      acc[6 * o + 4] = fmax(acc[6 * o + 4], fabs(d)); acc[6 * o + 5] = fmax(acc[6 * o + 5], fabs(t));
+      if constexpr (WEIGHTED) {
+        const double w = (double)wt[i], dw = d * w;
+        acc[6 * o] += d * dw; acc[6 * o + 1] += w * fabs(d); acc[6 * o + 2] += w * d; acc[6 * o + 3] += w * fabs(t);
+        if (w > 0.0) { acc[6 * o + 4] = fmax(acc[6 * o + 4], fabs(d)); acc[6 * o + 5] = fmax(acc[6 * o + 5], fabs(t)); }
+      } else {
+        acc[6 * o] += d * d; acc[6 * o + 1] += fabs(d); acc[6 * o + 2] += d; acc[6 * o + 3] += fabs(t);
+        acc[6 * o + 4] = fmax(acc[6 * o + 4], fabs(d)); acc[6 * o + 5] = fmax(acc[6 * o + 5], fabs(t));
+      }
     }
   }
 #pragma unroll
@@ -451,6 +484,20 @@ int mw_surrogate_prepare_form(int form, int n_in, long long n, const float *raw_
   return 0;
 }
 
+int mw_surrogate_prepare_column(long long n, const float *col, unsigned long long seed, long long n_train, long long n_val, float *train_c,
+                                float *val_c, float *test_c, void *stream) {
+  if (!col || !train_c || !val_c || !test_c) MW_FAIL("surrogate_prepare_column: null argument");
+  if (n < 3 || n_train < 1 || n_val < 1 || n - n_train - n_val < 1) MW_FAIL("surrogate_prepare_column: every set needs at least one sample");
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  ColArgs a;
+  a.n = n; a.n_train = n_train; a.n_val = n_val; a.F = make_feistel(seed, TAG_PRESHUFFLE, n);
+  a.col = col; a.out[0] = train_c; a.out[1] = val_c; a.out[2] = test_c;
+  const long long blocks = std::max(1ll, std::min((n + TPB - 1) / TPB, 256ll * 16));
+  hipLaunchKernelGGL(k_surrogate_prepare_column, dim3((unsigned)blocks), dim3(TPB), 0, (hipStream_t)stream, a);
+  MW_LAUNCH_CHECK();
+  return 0;
+}
+
 int mw_surrogate_prepare_v2(int n_in, long long n, const float *raw_in, const float *raw_out, const double *scl_in, const double *scl_out,
                             unsigned long long seed, long long n_train, long long n_val, float *train_x, float *train_y, float *val_x,
                             float *val_y, float *test_x, float *test_y, void *stream) {
@@ -465,11 +512,13 @@ int mw_surrogate_prepare(long long n, const float *raw_in, const float *raw_out,
                                  stream);
 }
 
-int mw_surrogate_train_epoch_v2(int n_in, int models, const float *x, const float *y, long long n, int batch, int epoch,
-                                unsigned long long seed, float *params, float *m1, float *m2, const float *table, float beta1, float beta2,
-                                float eps, double *stats, void *stream) {
+// the epoch of mw_surrogate_train_epoch_v2 (wt == nullptr) and of mw_surrogate_train_epoch_w
+static int train_epoch(int n_in, int models, const float *x, const float *y, const float *wt, bool weighted, long long n, int batch, int epoch,
+                       unsigned long long seed, float *params, float *m1, float *m2, const float *table, float beta1, float beta2, float eps,
+                       double *stats, void *stream) {
   if (check_n_in(n_in, "surrogate_train_epoch")) return 1;
   if (!x || !y || !params || !m1 || !m2 || !table || !stats) MW_FAIL("surrogate_train_epoch: null argument");
+  if (weighted && !wt) MW_FAIL("surrogate_train_epoch: null weights (the unweighted epoch is mw_surrogate_train_epoch_v2)");
   if (models < 1 || models > MW_SURROGATE_MAX_MODELS) MW_FAIL("surrogate_train_epoch: models must be in [1, " + std::to_string(MW_SURROGATE_MAX_MODELS) + "]");
   if (batch < 1 || batch > MW_SURROGATE_MAX_BATCH) MW_FAIL("surrogate_train_epoch: batch must be in [1, " + std::to_string(MW_SURROGATE_MAX_BATCH) + "]");
   if (n < 1 || epoch < 0) MW_FAIL("surrogate_train_epoch: n must be >= 1 and epoch >= 0");
@@ -477,11 +526,30 @@ int mw_surrogate_train_epoch_v2(int n_in, int models, const float *x, const floa
   TrainArgs a;
   a.S = SetRef{x, y, n}; a.B = batch; a.epoch = epoch; a.seed = seed;
   a.params = params; a.m1 = m1; a.m2 = m2; a.table = table; a.stats = stats;
-  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-  if (n_in == 5) hipLaunchKernelGGL(k_surrogate_train<5>, dim3((unsigned)models), dim3(TPB), 0, (hipStream_t)stream, a);
-  else           hipLaunchKernelGGL(k_surrogate_train<9>, dim3((unsigned)models), dim3(TPB), 0, (hipStream_t)stream, a);
+  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wt = wt;
+  const dim3 grid((unsigned)models), tpb(TPB);
+  hipStream_t st = (hipStream_t)stream;
+  if (weighted) {
+    if (n_in == 5) hipLaunchKernelGGL((k_surrogate_train<5, true>), grid, tpb, 0, st, a);
+    else           hipLaunchKernelGGL((k_surrogate_train<9, true>), grid, tpb, 0, st, a);
+  } else {
+    if (n_in == 5) hipLaunchKernelGGL((k_surrogate_train<5, false>), grid, tpb, 0, st, a);
+    else           hipLaunchKernelGGL((k_surrogate_train<9, false>), grid, tpb, 0, st, a);
+  }
   MW_LAUNCH_CHECK();
   return 0;
+}
+
+int mw_surrogate_train_epoch_v2(int n_in, int models, const float *x, const float *y, long long n, int batch, int epoch,
+                                unsigned long long seed, float *params, float *m1, float *m2, const float *table, float beta1, float beta2,
+                                float eps, double *stats, void *stream) {
+  return train_epoch(n_in, models, x, y, nullptr, false, n, batch, epoch, seed, params, m1, m2, table, beta1, beta2, eps, stats, stream);
+}
+
+int mw_surrogate_train_epoch_w(int n_in, int models, const float *x, const float *y, const float *w, long long n, int batch, int epoch,
+                               unsigned long long seed, float *params, float *m1, float *m2, const float *table, float beta1, float beta2,
+                               float eps, double *stats, void *stream) {
+  return train_epoch(n_in, models, x, y, w, true, n, batch, epoch, seed, params, m1, m2, table, beta1, beta2, eps, stats, stream);
 }
 
 int mw_surrogate_train_epoch(int models, const float *x, const float *y, long long n, int batch, int epoch, unsigned long long seed,
@@ -490,16 +558,34 @@ int mw_surrogate_train_epoch(int models, const float *x, const float *y, long lo
   return mw_surrogate_train_epoch_v2(5, models, x, y, n, batch, epoch, seed, params, m1, m2, table, beta1, beta2, eps, stats, stream);
 }
 
-int mw_surrogate_batch_grad_v2(int n_in, const float *params, const float *x, const float *y, int batch, float *grad, float *loss,
-                               void *stream) {
+static int batch_grad(int n_in, const float *params, const float *x, const float *y, const float *wt, bool weighted, int batch, float *grad,
+                      float *loss, void *stream) {
   if (check_n_in(n_in, "surrogate_batch_grad")) return 1;
   if (!params || !x || !y || !grad || !loss) MW_FAIL("surrogate_batch_grad: null argument");
+  if (weighted && !wt) MW_FAIL("surrogate_batch_grad: null weights (the unweighted gradient is mw_surrogate_batch_grad_v2)");
   if (batch < 1 || batch > MW_SURROGATE_MAX_BATCH) MW_FAIL("surrogate_batch_grad: batch must be in [1, " + std::to_string(MW_SURROGATE_MAX_BATCH) + "]");
   if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
-  if (n_in == 5) hipLaunchKernelGGL(k_surrogate_grad<5>, dim3(1), dim3(TPB), 0, (hipStream_t)stream, params, SetRef{x, y, (long long)batch}, batch, grad, loss);
-  else           hipLaunchKernelGGL(k_surrogate_grad<9>, dim3(1), dim3(TPB), 0, (hipStream_t)stream, params, SetRef{x, y, (long long)batch}, batch, grad, loss);
+  const SetRef S{x, y, (long long)batch};
+  hipStream_t st = (hipStream_t)stream;
+  if (weighted) {
+    if (n_in == 5) hipLaunchKernelGGL((k_surrogate_grad<5, true>), dim3(1), dim3(TPB), 0, st, params, S, batch, grad, loss, wt);
+    else           hipLaunchKernelGGL((k_surrogate_grad<9, true>), dim3(1), dim3(TPB), 0, st, params, S, batch, grad, loss, wt);
+  } else {
+    if (n_in == 5) hipLaunchKernelGGL((k_surrogate_grad<5, false>), dim3(1), dim3(TPB), 0, st, params, S, batch, grad, loss, wt);
+    else           hipLaunchKernelGGL((k_surrogate_grad<9, false>), dim3(1), dim3(TPB), 0, st, params, S, batch, grad, loss, wt);
+  }
   MW_LAUNCH_CHECK();
   return 0;
+}
+
+int mw_surrogate_batch_grad_v2(int n_in, const float *params, const float *x, const float *y, int batch, float *grad, float *loss,
+                               void *stream) {
+  return batch_grad(n_in, params, x, y, nullptr, false, batch, grad, loss, stream);
+}
+
+int mw_surrogate_batch_grad_w(int n_in, const float *params, const float *x, const float *y, const float *w, int batch, float *grad,
+                              float *loss, void *stream) {
+  return batch_grad(n_in, params, x, y, w, true, batch, grad, loss, stream);
 }
 
 int mw_surrogate_batch_grad(const float *params, const float *x, const float *y, int batch, float *grad, float *loss, void *stream) {
@@ -508,17 +594,29 @@ int mw_surrogate_batch_grad(const float *params, const float *x, const float *y,
 
 long long mw_surrogate_errors_workspace_bytes(int nsets) { return nsets < 1 ? 0 : (long long)nsets * ERR_BLOCKS * NSTAT * (long long)sizeof(double); }
 
-int mw_surrogate_errors(long long n, int nsets, const float *pred, const float *y, void *workspace, double *out, void *stream) {
-  if (!pred || !y || !workspace || !out) MW_FAIL("surrogate_errors: null argument");
+static int errors(long long n, int nsets, const float *pred, const float *y, const float *wt, bool weighted, void *workspace, double *out,
+                  void *stream) {
+  if (!pred || !y || !workspace || !out || (weighted && !wt)) MW_FAIL("surrogate_errors: null argument");
   if (n < 1 || nsets < 1 || nsets > 65535) MW_FAIL("surrogate_errors: n must be >= 1 and nsets in [1, 65535]");
   if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
-  hipLaunchKernelGGL(k_surrogate_sums, dim3(ERR_BLOCKS, (unsigned)nsets), dim3(TPB), 0, (hipStream_t)stream, n, pred, y, (double *)workspace);
+  const dim3 grid(ERR_BLOCKS, (unsigned)nsets);
+  if (weighted) hipLaunchKernelGGL(k_surrogate_sums<true>, grid, dim3(TPB), 0, (hipStream_t)stream, n, pred, y, (double *)workspace, wt);
+  else          hipLaunchKernelGGL(k_surrogate_sums<false>, grid, dim3(TPB), 0, (hipStream_t)stream, n, pred, y, (double *)workspace, wt);
   MW_LAUNCH_CHECK();
   const int per = 64 / NSTAT;
   hipLaunchKernelGGL(k_surrogate_sums_final, dim3((unsigned)((nsets + per - 1) / per)), dim3(64), 0, (hipStream_t)stream, nsets,
                      (const double *)workspace, out);
   MW_LAUNCH_CHECK();
   return 0;
+}
+
+int mw_surrogate_errors(long long n, int nsets, const float *pred, const float *y, void *workspace, double *out, void *stream) {
+  return errors(n, nsets, pred, y, nullptr, false, workspace, out, stream);
+}
+
+int mw_surrogate_errors_weighted(long long n, int nsets, const float *pred, const float *y, const float *w, void *workspace, double *out,
+                                 void *stream) {
+  return errors(n, nsets, pred, y, w, true, workspace, out, stream);
 }
 
 } // extern "C"

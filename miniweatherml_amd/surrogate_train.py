@@ -16,6 +16,9 @@ here so that tests can replay the batch order), the Nadam scalars, the reports a
 form="tendency" (CLI --tendency, with or without --stencil) trains the network on the CHANGE of the four output fields instead of their
 new values: the labels are (after - before), scaled by the min and max of those differences, and the written model carries the form
 (output_scaling.txt starts with `# form: tendency`); the network, the fit and every other file are the same.  DESIGN.md section 13.9.
+file_weights / sample_weights (CLI --file-weights) is Keras' fit(sample_weight=...): the loss of a batch is sum_i w_i mean_o((y - t)^2) / B,
+so that a small file -- a rollout's harvest beside the samples the model came from -- can count for more; group_metrics (CLI
+--group-metrics) reports the validation and test errors of every file on its own.  DESIGN.md section 13.13.
 """
 import argparse
 import ctypes as C
@@ -168,7 +171,8 @@ def read_samples(sample_files, stencil=False):
     """Concatenates the files DataGenerator writes (CDF-5: inputs (nsamples, 5, 2), outputs (nsamples, 4) fp32) in the order given, through
     ncio.NcFile.  Returns inputs (n, 5) = slot 0 of the stencil (the single-cell model), outputs (n, 4), and the grid metadata.
     stencil=True: inputs (n, 9) = slot 0, then rows 0..3 of slot 1 (temperature, vapor, cloud and precipitation of the level above; its
-    row 4 is never assigned and is not read)."""
+    row 4 is never assigned and is not read).
+    meta["file_index"] (n,) int32 is the position in `sample_files` of the file each sample came from, meta["file_counts"] the files' sizes."""
     from .ncio import NcFile
     if isinstance(sample_files, (str, os.PathLike)):
         sample_files = [sample_files]
@@ -194,6 +198,8 @@ def read_samples(sample_files, stencil=False):
         outs.append(o2)
     inputs, outputs = np.concatenate(ins).astype(np.float32), np.concatenate(outs).astype(np.float32)
     meta["files"] = [os.fspath(p) for p in sample_files]
+    meta["file_counts"] = [int(o.shape[0]) for o in outs]
+    meta["file_index"] = np.repeat(np.arange(len(outs), dtype=np.int32), meta["file_counts"])
     return inputs, outputs, meta
 
 
@@ -339,6 +345,47 @@ def check_arguments(n, epochs, batch_size, test_split, validation_split, models)
     return n_train, n_val, n_test
 
 
+def parse_file_weights(text):
+    """The CLI's --file-weights: a comma list of floats, "1,1,25" -> (1.0, 1.0, 25.0)."""
+    try:
+        return tuple(float(t) for t in str(text).split(","))
+    except ValueError:
+        raise SurrogateTrainError("--file-weights: expected a comma list of numbers such as 1,1,25, got %r" % (text,))
+
+
+def check_weights(n, file_index, n_files, file_weights=None, sample_weights=None):
+    """The samples' weights (n,) fp32 in concatenated file order, or None when neither argument is given.  file_weights: one float per
+    sample file; sample_weights: (n,).  Refused: both, a wrong count, a non-finite or a negative weight.  A weight of 0 is allowed."""
+    if file_weights is None and sample_weights is None:
+        return None
+    if file_weights is not None and sample_weights is not None:
+        raise SurrogateTrainError("file_weights and sample_weights are two ways to say the same thing: give one of them")
+    what = "file_weights" if file_weights is not None else "sample_weights"
+    try:
+        w = np.asarray(file_weights if file_weights is not None else sample_weights, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise SurrogateTrainError("%s must be numbers" % what)
+    want = n_files if file_weights is not None else n
+    if w.ndim != 1 or w.size != want:
+        raise SurrogateTrainError("%s: %d weights for %d %s" % (what, w.size, want, "sample files" if file_weights is not None else "samples"))
+    if not np.isfinite(w).all():
+        raise SurrogateTrainError("%s: non-finite weight (first at index %d)" % (what, int(np.flatnonzero(~np.isfinite(w))[0])))
+    if (w < 0).any():
+        raise SurrogateTrainError("%s: negative weight %r at index %d" % (what, float(w[w < 0][0]), int(np.flatnonzero(w < 0)[0])))
+    w = w.astype(np.float32)
+    return np.ascontiguousarray(w[file_index] if file_weights is not None else w)
+
+
+def check_training_weights(w, n_train, split_seed):
+    """Refuses weights that leave the training set without a positive one (every batch's loss would be zero).  The training set is the
+    first n_train positions of the pre-shuffle; the permutation is only built when some weight is zero."""
+    if w is None or (w > 0).all():
+        return
+    if not (w[preshuffle_permutation(w.size, split_seed)[:n_train]] > 0).any():
+        raise SurrogateTrainError("no sample of the training set (%d of %d samples, split seed %d) has a positive weight: nothing would be "
+                                  "trained" % (n_train, w.size, split_seed))
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # output files
 def _fmt(v):
@@ -408,10 +455,14 @@ class Trainer:
     training launch plus the validation pass, with one host synchronisation (the copy of the weights and sums).  The model follows the
     data: raw_in (n, 5) trains the single-cell model (104 parameters), raw_in (n, 9) the stencil model (144).  form="tendency": the y sets
     are the scaled changes (mw_surrogate_prepare_form) and scl_out is the table of the changes; everything behind the prepare -- epochs,
-    validation, test errors, predict_test -- works in scaled label space and is the same for both forms."""
+    validation, test errors, predict_test -- works in scaled label space and is the same for both forms.
+    sample_weights (n,): the samples' weights in the order of raw_in; they go through the same pre-shuffle and split
+    (mw_surrogate_prepare_column), epoch() then runs mw_surrogate_train_epoch_w and validate() mw_surrogate_errors_weighted with the
+    validation samples' weights, as Keras weights its validation split.  groups (n,): an integer label per sample (the index of its file),
+    split the same way, for group_sums.  Without the two the trainer calls what it always called."""
 
     def __init__(self, raw_in, raw_out, scl_in, scl_out, n_split, seed=0, split_seed=None, models=1, batch_size=1024, epochs=10,
-                 learning_rate=1e-3, initial=None, form="state"):
+                 learning_rate=1e-3, initial=None, form="state", sample_weights=None, groups=None):
         import torch
         from . import capi
         self.torch, self.L = torch, capi.lib()
@@ -436,6 +487,9 @@ class Trainer:
             capi.check(self.L.mw_surrogate_prepare_form(FORMS.index(self.form), self.n_in, raw_in.shape[0], self._p(raw_in), self._p(raw_out),
                                                         self.scl_in.ctypes.data_as(dp), self.scl_out.ctypes.data_as(dp), self.split_seed & M64,
                                                         self.n_train, self.n_val, *[self._p(t) for t in (tx, ty, vx, vy, sx, sy)], self._stream()))
+        self.wsets = self._column(sample_weights, raw_in.shape[0])
+        self.gsets = self._column(groups, raw_in.shape[0])
+        self.n_groups = 0 if self.gsets is None else int(max(float(t.max()) for t in self.gsets.values())) + 1
         # ONE device buffer for what the host reads each epoch: parameters (K, 104) fp32 | training sums (K, 2) fp64 | validation sums (K, 24)
         self.buf = torch.zeros(self.K * (NP * 4 + 2 * 8 + 24 * 8), dtype=torch.uint8, device=dev)
         self.params = self.buf[:self.K * NP * 4].view(f32).view(self.K, NP)
@@ -462,6 +516,21 @@ class Trainer:
     def _p(self, t):
         return C.c_void_p(t.data_ptr())
 
+    def _column(self, col, n):
+        """One value per sample, (n,) host or device, through the pre-shuffle and split: {"train": (n_train,), "val": ..., "test": ...} fp32."""
+        if col is None:
+            return None
+        from . import capi
+        torch = self.torch
+        c = torch.as_tensor(col).to(device=self.device, dtype=torch.float32).contiguous()
+        if c.shape != (n,):
+            raise SurrogateTrainError("Trainer: a per-sample column of shape %r for %d samples" % (tuple(c.shape), n))
+        out = {k: torch.empty(m, dtype=torch.float32, device=self.device) for k, m in (("train", self.n_train), ("val", self.n_val), ("test", self.n_test))}
+        with torch.cuda.device(self.device):
+            capi.check(self.L.mw_surrogate_prepare_column(n, self._p(c), self.split_seed & M64, self.n_train, self.n_val, self._p(out["train"]),
+                                                          self._p(out["val"]), self._p(out["test"]), self._stream()))
+        return out
+
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
@@ -473,9 +542,12 @@ class Trainer:
         check(self.L.mw_ponni_forward(C.cast(lay, C.c_void_p), 5, w.ctypes.data_as(C.POINTER(C.c_float)), self.npar, x.shape[1], self._p(x),
                                       self._p(out), self._stream()))
 
-    def _errors(self, n, nsets, pred, y, out_ptr):
+    def _errors(self, n, nsets, pred, y, out_ptr, w=None):
         from .capi import check
-        check(self.L.mw_surrogate_errors(n, nsets, self._p(pred), self._p(y), self._p(self.ws), out_ptr, self._stream()))
+        if w is None:
+            check(self.L.mw_surrogate_errors(n, nsets, self._p(pred), self._p(y), self._p(self.ws), out_ptr, self._stream()))
+        else:
+            check(self.L.mw_surrogate_errors_weighted(n, nsets, self._p(pred), self._p(y), self._p(w), self._p(self.ws), out_ptr, self._stream()))
 
     def validate(self, weights):
         """Launches the validation pass of every model (weights: HOST (K, 104)); its sums land in vstats (read at the next copy)."""
@@ -488,18 +560,22 @@ class Trainer:
                 pred = self.pred[:ng * 4 * self.n_val].view(ng, 4, self.n_val)
                 for j in range(ng):
                     self._predict(weights[g0 + j], vx, pred[j])
-                self._errors(self.n_val, ng, pred, vy, C.c_void_p(self.vstats.data_ptr() + g0 * 24 * 8))
+                self._errors(self.n_val, ng, pred, vy, C.c_void_p(self.vstats.data_ptr() + g0 * 24 * 8),
+                             None if self.wsets is None else self.wsets["val"])
 
     def epoch(self):
         """One training launch, ONE host synchronisation (a single copy of weights and sums), the validation launches.  Returns the host
         copy: weights (K, 104), this epoch's training sums (K, 2) and the PREVIOUS epoch's validation sums (K, 24)."""
         from .capi import check
         tx, ty = self.sets["train"]
+        tail = (self.n_train, self.B, self.epoch_no, self.seed & M64, self._p(self.params), self._p(self.m1), self._p(self.m2),
+                C.c_void_p(self.table.data_ptr() + self.epoch_no * self.steps * 12), NADAM["beta1"], NADAM["beta2"], NADAM["eps"],
+                self._p(self.tstats), self._stream())
         with self.torch.cuda.device(self.device):
-            check(self.L.mw_surrogate_train_epoch_v2(self.n_in, self.K, self._p(tx), self._p(ty), self.n_train, self.B, self.epoch_no, self.seed & M64,
-                                                  self._p(self.params), self._p(self.m1), self._p(self.m2),
-                                                  C.c_void_p(self.table.data_ptr() + self.epoch_no * self.steps * 12), NADAM["beta1"],
-                                                  NADAM["beta2"], NADAM["eps"], self._p(self.tstats), self._stream()))
+            if self.wsets is None:
+                check(self.L.mw_surrogate_train_epoch_v2(self.n_in, self.K, self._p(tx), self._p(ty), *tail))
+            else:
+                check(self.L.mw_surrogate_train_epoch_w(self.n_in, self.K, self._p(tx), self._p(ty), self._p(self.wsets["train"]), *tail))
         host = self._host()
         self.validate(host[0])
         self.epoch_no += 1
@@ -532,6 +608,55 @@ class Trainer:
             self._errors(self.n_test, 1, pred, sy, self._p(self.test_out))
         return self.test_out.cpu().numpy().reshape(4, 6)
 
+    def group_counts(self):
+        """(n_groups, 3) int: every group's samples in the training, validation and test set, from the prepared label tensors."""
+        return np.stack([self.torch.bincount(self.gsets[k].long(), minlength=self.n_groups).cpu().numpy() for k in ("train", "val", "test")], axis=1)
+
+    def group_sums(self, w104, which):
+        """The UNWEIGHTED error sums (4, 6) of every group's samples in the set `which` ("val" | "test") at the weights w104: one forward
+        of the set, then one mw_surrogate_errors_weighted call per group with the group's indicator as weights.  None for an empty group."""
+        x, y = self.sets[which]
+        n = x.shape[1]
+        pred = self.pred[:4 * n].view(4, n)
+        out = []
+        with self.torch.cuda.device(self.device):
+            self._predict(w104, x, pred)
+            for g in range(self.n_groups):
+                ind = (self.gsets[which] == g).to(self.torch.float32)
+                if not bool(ind.any()):
+                    out.append(None)
+                    continue
+                self._errors(n, 1, pred, y, self._p(self.test_out), ind)
+                out.append(self.test_out.cpu().numpy().reshape(4, 6).copy())
+        return out
+
+
+def _group_records(tr, w104, files, file_weights, unweighted):
+    """train_surrogate's `group_metrics`: one record per file (see there)."""
+    counts, vsum, tsum = tr.group_counts(), tr.group_sums(w104, "val"), tr.group_sums(w104, "test")
+    out = []
+    for g, path in enumerate(files):
+        rec = {"file": path, "weight": 1.0 if unweighted else None if file_weights is None else float(file_weights[g]),
+               "n_train": int(counts[g, 0]), "n_val": int(counts[g, 1]), "n_test": int(counts[g, 2])}
+        v, t = vsum[g], tsum[g]
+        rec["val_loss"] = None if v is None else float(v[:, 0].sum() / (4 * rec["n_val"]))
+        rec["val_mean_absolute_error"] = None if v is None else float(v[:, 1].sum() / (4 * rec["n_val"]))
+        rec["test_loss"] = None if t is None else float(t[:, 0].sum() / (4 * rec["n_test"]))
+        m = None if t is None else _metrics(t)
+        for k in ("max_relative_error", "mean_relative_error", "mean_relative_bias"):
+            rec[k] = None if m is None else m[k]
+        out.append(rec)
+    return out
+
+
+def group_line(g):
+    """The CLI's line for one record of `group_metrics`."""
+    num = lambda v: "none" if v is None else "%.4e" % v                  # noqa: E731
+    return ("file %s (weight %s): train %d / val %d / test %d - val_loss: %s - val_mean_absolute_error: %s - test_loss: %s - "
+            "mean relative errors: %s" % (g["file"], "per sample" if g["weight"] is None else "%g" % g["weight"], g["n_train"], g["n_val"],
+                                          g["n_test"], num(g["val_loss"]), num(g["val_mean_absolute_error"]), num(g["test_loss"]),
+                                          g["mean_relative_error"]))
+
 
 def _metrics(s):
     """The notebook's test cell from the error sums of one set (4 outputs x [sum d^2, sum |d|, sum d, sum |o|, max |d|, max |o|])."""
@@ -541,7 +666,8 @@ def _metrics(s):
 
 
 def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test_split=0.2, validation_split=0.2, learning_rate=1e-3,
-                    seed=0, models=1, device="cuda:0", split_seed=None, verbose=False, stencil=False, keep_all=False, init=None, form=None):
+                    seed=0, models=1, device="cuda:0", split_seed=None, verbose=False, stencil=False, keep_all=False, init=None, form=None,
+                    file_weights=None, sample_weights=None, group_metrics=False):
     """Trains `models` surrogates (seeds seed .. seed + models - 1; the pre-shuffle / split uses split_seed, default seed) on the samples of
     `sample_files` and returns a dict: per-model `history` (Keras' loss, mean_absolute_error, val_loss, val_mean_absolute_error per
     epoch), `weights` (models, 104) fp32, `best_model` (lowest final val_loss, ties to the lowest index), `test_metrics` of the best model
@@ -559,12 +685,25 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     form="tendency": the network is fitted to the change of the four fields (labels and output table from after - before; module
     docstring); the result, history.json and the written files carry `form`.  The losses and the test metrics are in scaled LABEL space --
     for a tendency model that is the space of the scaled changes, so they do not compare with a state model's.  form=None: "state", or
-    with init=DIR the form of DIR's model; a form that contradicts DIR's is refused (resolve_form)."""
+    with init=DIR the form of DIR's model; a form that contradicts DIR's is refused (resolve_form).
+    file_weights (one float per sample file, in the files' order) or sample_weights ((n,) in concatenated file order; giving both is
+    refused): Keras' fit(sample_weight=...) under its default reduction -- the loss of a batch is sum_i w_i mean_o((y - t)^2) / B, the
+    divisor the batch size.  The weights are used AS GIVEN, as Keras uses them: no renormalisation, so doubling every weight doubles the
+    gradient.  A weight of 0 is allowed (such samples are never trained on; with group_metrics a file of weight 0 is a pure evaluation
+    group); non-finite or negative weights, a wrong count, and a training set without a positive weight are refused on the host.  The
+    four `history` series are then the weighted quantities (loss = sum w r^2 / (4 n_train), val_loss = sum w d^2 / (4 n_val), the same
+    for the two absolute errors) and best_model follows the weighted val_loss; `test_metrics` stay UNWEIGHTED over the whole test set, so
+    they compare with any other run.  The result and history.json gain `weighted: True` and `file_weights` (None with sample_weights).
+    group_metrics=True (with or without weights) adds `group_metrics`: per file {file, weight, n_train, n_val, n_test, and, unweighted, at
+    the best model's final weights: val_loss, val_mean_absolute_error, test_loss and the notebook's three test metrics on that file's
+    samples alone}; a file without a sample in a set has None for that set's numbers.  DESIGN.md 13.13."""
     form = resolve_form(form, init)
     inputs, outputs, meta = read_samples(sample_files, stencil=stencil)
     scl_in, scl_out = data_scaling(inputs, outputs, allow_constant=init is not None, form=form)
     n = inputs.shape[0]
     n_split = check_arguments(n, epochs, batch_size, test_split, validation_split, models)
+    weights = check_weights(n, meta["file_index"], len(meta["files"]), file_weights, sample_weights)
+    check_training_weights(weights, n_split[0], int(seed if split_seed is None else split_seed))
     initial = domain = None
     if init is not None:
         data_in = scl_in
@@ -575,7 +714,10 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     dev = torch.device(device)
     raw_in = torch.from_numpy(inputs).to(dev)
     raw_out = torch.from_numpy(outputs).to(dev)
-    tr = Trainer(raw_in, raw_out, scl_in, scl_out, n_split, seed, split_seed, models, batch_size, epochs, learning_rate, initial=initial, form=form)
+    tr = Trainer(raw_in, raw_out, scl_in, scl_out, n_split, seed, split_seed, models, batch_size, epochs, learning_rate, initial=initial, form=form,
+                 sample_weights=weights, groups=meta["file_index"] if group_metrics else None)
+    if group_metrics:
+        tr.n_groups = len(meta["files"])                                      # (a last file without samples is a group too)
     if verbose:
         print("output form: %s -- loss, errors and test metrics below are in scaled label space: %s"
               % (form, "the scaled change (after - before) of each field" if form == "tendency" else "the scaled new value of each field"), flush=True)
@@ -627,10 +769,17 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     result.update({k: meta[k] for k in ("time_step_size", "dx", "dy", "dz", "files")})
     if init is not None:
         result["init"], result["initial_weights"], result["training_domain"] = os.fspath(init), initial, domain
+    if weights is not None:
+        result["weighted"], result["file_weights"] = True, None if file_weights is None else [float(v) for v in file_weights]
     if verbose:
         print("Max relative errors:  ", metrics["max_relative_error"])
         print("Mean relative errors: ", metrics["mean_relative_error"])
         print("Mean relative bias:   ", metrics["mean_relative_bias"], flush=True)
+    if group_metrics:
+        result["group_metrics"] = _group_records(tr, w[best], meta["files"], file_weights, unweighted=weights is None)
+        if verbose:
+            for g in result["group_metrics"]:
+                print(group_line(g), flush=True)
     if out_dir is not None:
         js = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in result.items() if k != "weights"}
         js["best_weights"] = w[best].astype(np.float64).tolist()
@@ -675,11 +824,15 @@ def main(argv=None):
     ap.add_argument("--stencil", action="store_true", help="train the two-cell stencil model (the cell and the level above: 9 inputs, 144 weights)")
     ap.add_argument("--tendency", action="store_true", help="train the tendency form: the network predicts the change of the four fields, which inference "
                     "adds to the state in fp64 (with --init DIR the form is DIR's; a state-form DIR is refused)")
+    ap.add_argument("--file-weights", default=None, metavar="W,W,...", help="one weight per sample file, in their order (Keras' sample_weight: the "
+                    "batch loss is sum w (y - t)^2 / batch size, weights as given; 0 = evaluate the file only)")
+    ap.add_argument("--group-metrics", action="store_true", help="also report validation and test errors of every sample file on its own")
     a = ap.parse_args(argv)
     try:
         r = train_surrogate(a.files, a.out, a.epochs, a.batch_size, a.test_split, a.validation_split, a.learning_rate, a.seed, a.models,
                             a.device, a.split_seed, verbose=True, stencil=a.stencil, keep_all=a.keep_all,
-                            init=a.init, form="tendency" if a.tendency else None)
+                            init=a.init, form="tendency" if a.tendency else None,
+                            file_weights=None if a.file_weights is None else parse_file_weights(a.file_weights), group_metrics=a.group_metrics)
     except SurrogateTrainError as e:
         print("ERROR: %s" % e, file=sys.stderr)
         return 2

@@ -9,6 +9,9 @@ Linear(10,4) in fp32, mse_loss, torch.optim.NAdam(eps=1e-7, momentum_decay=4e-3,
 resident on the device, the same validation set evaluated at the end of the epoch.  Warm-up epoch excluded; --reps timed epochs each;
 median, min and max reported.  The data are synthetic Kessler-like samples generated on the device from a fixed seed.
 Writes profiles/surrogate_train_<tag>.json.
+--weighted: times the WEIGHTED epoch (mw_surrogate_train_epoch_w and the weighted validation sums; sample weights log-uniform in
+[2^-4, 2^4] from a fixed seed) beside the unweighted one in the same run, on the same data, for K in 1, 8 (or --models), without the
+torch baseline:    ... surrogate_train_timing.py --weighted --tag weighted_mi355x
 """
 import argparse
 import json
@@ -37,10 +40,10 @@ def summary(ms):
             "max_ms": round(max(ms), 3), "spread_pct": round(100.0 * (max(ms) - min(ms)) / statistics.median(ms), 2)}
 
 
-def time_hip(raw_in, raw_out, scl_in, scl_out, n_split, K, reps, batch):
+def time_hip(raw_in, raw_out, scl_in, scl_out, n_split, K, reps, batch, sample_weights=None):
     import torch
     from miniweatherml_amd.surrogate_train import Trainer
-    tr = Trainer(raw_in, raw_out, scl_in, scl_out, n_split, seed=0, models=K, batch_size=batch, epochs=1 + reps)
+    tr = Trainer(raw_in, raw_out, scl_in, scl_out, n_split, seed=0, models=K, batch_size=batch, epochs=1 + reps, sample_weights=sample_weights)
     tr.epoch()
     torch.cuda.synchronize()
     ms = []
@@ -103,7 +106,8 @@ def main():
     ap.add_argument("--n", type=int, default=9118906)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1024)
-    ap.add_argument("--models", default="1,8,64")
+    ap.add_argument("--models", default=None, help="comma list of K (default 1,8,64; with --weighted 1,8)")
+    ap.add_argument("--weighted", action="store_true", help="time the weighted epoch beside the unweighted one (no torch baseline)")
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -120,11 +124,22 @@ def main():
            "n_val": n_split[1], "batch": a.batch, "reps": a.reps,
            "epoch": "training launch + copy of weights and sums + validation pass, closed by a device synchronise; warm-up epoch excluded",
            "hip": {}}
-    for K in [int(k) for k in a.models.split(",")]:
+    weights = None
+    if a.weighted:
+        g = torch.Generator(device=dev).manual_seed(1)
+        weights = torch.exp2(8.0 * torch.rand(a.n, generator=g, device=dev) - 4.0)
+        res["weights"] = "log-uniform in [2^-4, 2^4], torch.Generator seed 1"
+        res["hip_weighted"], res["weighted_over_unweighted"] = {}, {}
+    for K in [int(k) for k in (a.models or ("1,8" if a.weighted else "1,8,64")).split(",")]:
         r = time_hip(raw_in, raw_out, scl_in, scl_out, n_split, K, a.reps, a.batch)
         res["hip"]["K%d" % K] = r
         print("HIP trainer K=%-3d  %s" % (K, json.dumps(r)), flush=True)
-    if not a.no_torch:
+        if a.weighted:
+            rw = time_hip(raw_in, raw_out, scl_in, scl_out, n_split, K, a.reps, a.batch, sample_weights=weights)
+            res["hip_weighted"]["K%d" % K] = rw
+            res["weighted_over_unweighted"]["K%d" % K] = round(rw["median_ms"] / r["median_ms"], 4)
+            print("    weighted K=%-3d  %s" % (K, json.dumps(rw)), flush=True)
+    if not a.no_torch and not a.weighted:
         tr = Trainer(raw_in, raw_out, scl_in, scl_out, n_split, seed=0, models=1, batch_size=a.batch, epochs=1)
         r = time_torch(tr.sets["train"], tr.sets["val"], a.reps, a.batch)
         del tr
