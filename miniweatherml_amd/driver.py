@@ -86,11 +86,19 @@ box_of, group, per model its box and report, and the per-call history) and a sec
 is made and the document is what it is without the key.
 """
 import argparse
+import json
 import os
 import sys
 import time
 
+import numpy as np
+import torch
 import yaml
+
+from . import city, column, microphysics, mlp, rollout, sampling, surrogate_eval
+from .coupler import Coupler
+from .dycore import Dynamics_Euler_Stratified_WenoFV, perturb_temperature
+from .experiments import simple_city_step
 
 EXPERIMENTS = ("supercell_example", "community_benchmark", "simple_city", "inference_ponni", "gather_statistics", "generate_micro_data",
                "evaluate_surrogates", "rollout_surrogates")
@@ -348,7 +356,6 @@ def eval_domain_key(cfg, model_names):
 def _domain_split_evaluator(cfg_domain, evaluator, eval_models):
     """The DomainSplitEvaluator on a SurrogateEvaluator's banks and names: every model's own box (domain_box, its training-domain table
     honoured), or the box of the entry `box_of` names for all of them."""
-    from . import mlp, surrogate_eval
     weights = mlp.load_surrogate_bank(eval_models)
     tables = mlp.load_training_domains(eval_models, weights)
     names = [m["name"] for m in eval_models]
@@ -393,7 +400,6 @@ def _surrogate_models(entries, yaml_dir):
 
 def _surrogate_evaluator(entries, device):
     """One bank per width, in the order the widths first appear; the models' names bank after bank."""
-    from . import mlp, surrogate_eval
     weights = mlp.load_surrogate_bank(entries)
     widths = []
     for w in weights:
@@ -406,7 +412,6 @@ def _surrogate_evaluator(entries, device):
 
 def _distributed(device):
     """One process per GPU when launched by torchrun; returns (nranks, myrank, device)."""
-    import torch
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world == 1:
         return 1, 0, device
@@ -425,7 +430,6 @@ def _distributed(device):
 
 
 def _coupler(cfg, device, nranks, myrank, yaml_path):
-    from .coupler import Coupler
     c = Coupler(device)
     c.set_option("out_prefix", cfg["out_prefix"])
     c.set_option("init_data", cfg["init_data"])
@@ -458,68 +462,113 @@ def _time_loop(cfg, dycore, coupler, body, max_steps):
     return etime, steps
 
 
-def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
-    import torch
-    from . import city, column, microphysics, mlp, rollout, sampling, surrogate_eval
-    from .dycore import Dynamics_Euler_Stratified_WenoFV, perturb_temperature
-    if experiment not in EXPERIMENTS:
-        raise ValueError("unknown experiment %r (one of %s)" % (experiment, ", ".join(EXPERIMENTS)))
-    cfg = load_config(yaml_path)
-    nranks, myrank, device = _distributed(device)
-    if experiment == "evaluate_surrogates":
-        if nranks > 1:
-            raise ValueError("evaluate_surrogates runs on one rank (%d given): SurrogateEvaluator.combine is exact, but the reduction over "
-                             "ranks is not built yet" % nranks)
-        committees = evaluation_committees(cfg)
-        cfg["surrogate_models"], cfg["eval_interval"] = surrogate_config(cfg)
-        eval_domain = eval_domain_key(cfg, [m["name"] for m in cfg["surrogate_models"]])
-    if experiment == "inference_ponni" and "surrogate_committees" in cfg and not ("keras_weights_h5" in cfg or "keras_weights_txt" in cfg):
-        committees = committee_config(cfg)
-        if len(committees) != 1:
-            raise ValueError("ERROR: inference_ponni runs one committee, surrogate_committees lists %d" % len(committees))
-        cfg["surrogate_models"], _ = surrogate_config(cfg)
-        cfg["_committee"] = committees[0]
-    if experiment == "rollout_surrogates":
-        if nranks > 1:
-            raise ValueError("rollout_surrogates runs on one rank (%d given): SurrogateEvaluator.combine is exact, but the reduction over "
-                             "ranks is not built yet" % nranks)
-        harvest = harvest_config(cfg)
-        rain_cfg = surface_rain_config(cfg)
-        domain_cfg = training_domain_config(cfg)
-        committees = committee_config(cfg)
-        cfg["surrogate_models"], cfg["eval_interval"], cfg["persistence_member"], cfg["nens"] = rollout_config(cfg)
-    coupler = _coupler(cfg, device, nranks, myrank, yaml_path)
-    dycore = Dynamics_Euler_Stratified_WenoFV()
-    info = {"experiment": experiment, "nranks": nranks}
-    t_main = time.perf_counter()
-    if experiment == "simple_city":
-        horiz_sponge, time_averager = city.Horizontal_Sponge(), city.Time_Averager()
+class Experiment:
+    """One experiment of EXPERIMENTS, in four stages that run() calls in this order: configure (the experiment's YAML checks; no device
+    is touched yet), setup (the modules, after the coupler and the dycore exist), step (the time loop's body) and finish (reports and
+    files, after the loop).  Collaborators are plain attributes, so a test can put recording stubs in their place."""
+
+    timed = False                                                              # True: run() times the loop as info["simulation_loop_s"]
+
+    def configure(self, cfg, nranks):
+        pass
+
+    def setup(self, cfg, coupler, dycore, info, device, quiet):
+        self.cfg, self.coupler, self.dycore, self.info, self.device, self.quiet = cfg, coupler, dycore, info, device, quiet
+
+    def finish(self, steps, yaml_path):
+        pass
+
+
+def _one_rank(experiment, nranks):
+    if nranks > 1:
+        raise ValueError("%s runs on one rank (%d given): SurrogateEvaluator.combine is exact, but the reduction over "
+                         "ranks is not built yet" % (experiment, nranks))
+
+
+class SimpleCity(Experiment):
+    def setup(self, *args):
+        super().setup(*args)
+        coupler, dycore = self.coupler, self.dycore
+        self.horiz_sponge, self.time_averager = city.Horizontal_Sponge(), city.Time_Averager()
         coupler.add_tracer("water_vapor", "water_vapor", True, True)           # simple_city/driver.cpp:55-56
         coupler.get_data_manager_readwrite().get("water_vapor").zero_()
         dycore.init(coupler)
         _exchange(dycore, coupler)
-        horiz_sponge.init(coupler, 10, 1.0)
-        time_averager.init(coupler)
+        self.horiz_sponge.init(coupler, 10, 1.0)
+        self.time_averager.init(coupler)
 
-        def body(dt, etime):                                                   # :72-75
-            horiz_sponge.apply(coupler, dt, True, True, False, False)
-            dycore.time_step(coupler, dt)
-            column.sponge_layer(coupler, dt, 1)
-            time_averager.accumulate(coupler, dt)
-        etime, steps = _time_loop(cfg, dycore, coupler, body, max_steps)
-        time_averager.finalize(coupler)                                        # :82 -> time_averaged_fields.nc
-    else:
-        column_nudger = column.ColumnNudger()
-        stats = None
-        if experiment == "inference_ponni":
-            micro = microphysics.Microphysics_Kessler_Surrogate()
-            base = cfg["_dir"]
-            if "_committee" in cfg:                                                # the mean of the committee's models is what runs
-                by_name = {m["name"]: m for m in cfg["surrogate_models"]}
-                entries = [by_name[n] for n in cfg["_committee"]["members"]]
-                bank = mlp.load_surrogate_bank(entries)
-                micro.init(coupler, committee=bank, guard=cfg["_committee"].get("guard"), domains=mlp.load_training_domains(entries, bank))
+    def step(self, dt, etime):                                                 # :72-75
+        simple_city_step(self.coupler, self.dycore, self.horiz_sponge, self.time_averager, dt)
 
+    def finish(self, steps, yaml_path):
+        self.time_averager.finalize(self.coupler)                              # :82 -> time_averaged_fields.nc
+
+
+class Column(Experiment):
+    """supercell_example as it stands, and the family of the experiments that run its loop with another microphysics (make_micro), with
+    work around the microphysics step (micro_step) or after the nudger (after_step)."""
+
+    def make_micro(self):
+        micro = microphysics.Microphysics_Kessler()
+        micro.init(self.coupler)                                               # supercell_example/driver.cpp:58
+        return micro
+
+    def setup(self, *args):
+        super().setup(*args)
+        self.nstep = 0                                                         # steps taken so far
+        self.nudger = column.ColumnNudger()
+        self.micro = self.make_micro()
+        self.dycore.init(self.coupler)                                         # :59
+        _exchange(self.dycore, self.coupler)
+        self.nudger.set_column(self.coupler)                                   # :60
+        perturb_temperature(self.coupler)                                      # :61
+
+    def step(self, dt, etime):                                                 # :73-76
+        self.dycore.time_step(self.coupler, dt)
+        self.micro_step(dt, etime)
+        column.sponge_layer(self.coupler, dt)
+        self.nudger.nudge_to_column(self.coupler, dt)                          # (eager: a scorer reads the nudged fields)
+        self.after_step(dt, etime)
+        self.nstep += 1
+
+    def micro_step(self, dt, etime):
+        self.micro.time_step(self.coupler, dt)
+
+    def micro_step_keeping_input(self, dt):
+        """The microphysics step on the coupler; returns a copy of the state it started from (gather_statistics.cpp:79-80)."""
+        inp = Coupler(self.device)
+        self.coupler.clone_into(inp)
+        self.micro.time_step(self.coupler, dt)
+        return inp
+
+    def after_step(self, dt, etime):
+        pass
+
+
+class CommunityBenchmark(Column):
+    timed = True                                                               # timer "simulation_loop", community_benchmark/driver.cpp:66,82
+
+
+class InferencePonni(Column):
+    committee = None                                                           # the one committee that runs in place of a single network
+
+    def configure(self, cfg, nranks):
+        if "surrogate_committees" in cfg and not ("keras_weights_h5" in cfg or "keras_weights_txt" in cfg):
+            committees = committee_config(cfg)
+            if len(committees) != 1:
+                raise ValueError("ERROR: inference_ponni runs one committee, surrogate_committees lists %d" % len(committees))
+            cfg["surrogate_models"], _ = surrogate_config(cfg)
+            self.committee = committees[0]
+
+    def make_micro(self):
+        cfg, coupler, info = self.cfg, self.coupler, self.info
+        micro = microphysics.Microphysics_Kessler_Surrogate()
+        if self.committee is not None:                                         # the mean of the committee's models is what runs
+            by_name = {m["name"]: m for m in cfg["surrogate_models"]}
+            entries = [by_name[n] for n in self.committee["members"]]
+            bank = mlp.load_surrogate_bank(entries)
+            micro.init(coupler, committee=bank, guard=self.committee.get("guard"), domains=mlp.load_training_domains(entries, bank))
+        else:
             def rel(p):
                 return p if p is None or os.path.isabs(p) else os.path.normpath(os.path.join(os.getcwd(), p))
             h5 = rel(cfg.get("keras_weights_h5"))
@@ -527,187 +576,260 @@ def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
             for k_yaml, k_arg in (("nn_input_scaling", "in_scaling_txt"), ("nn_output_scaling", "out_scaling_txt")):
                 p = rel(cfg.get(k_yaml))
                 kw[k_arg] = p if p and os.path.exists(p) else None             # else: the shipped tables
-            if "_committee" not in cfg:
-                micro.init(coupler, **kw)
-            # the form travels with the files: the single model's, or every committee model's
-            info["surrogate_form"] = micro._committee.forms if "_committee" in cfg else micro.form
-            if "tendency" in info["surrogate_form"] and not quiet and coupler.is_mainproc():     # (a state model prints what it always did)
-                print("inference_ponni: surrogate output form: %s" % info["surrogate_form"], flush=True)
-        elif experiment == "rollout_surrogates":
-            micro = rollout.Microphysics_Rollout()
-            bank = mlp.load_surrogate_bank(cfg["surrogate_models"])
-            micro.init(coupler, bank, cfg["persistence_member"],
-                       [m["name"] for m in cfg["surrogate_models"]], [(c["name"], c["members"], c["guard"]) if "guard" in c else (c["name"], c["members"]) for c in committees],
-                       domains=mlp.load_training_domains(cfg["surrogate_models"], bank))
-        else:
-            micro = microphysics.Microphysics_Kessler()
-            micro.init(coupler)                                                # supercell_example/driver.cpp:58
-        dycore.init(coupler)                                                   # :59
-        _exchange(dycore, coupler)
-        column_nudger.set_column(coupler)                                      # :60
-        perturb_temperature(coupler)                                           # :61
-        from .coupler import Coupler
-        datagen = None
-        if experiment == "gather_statistics":
-            stats = sampling.StatisticsGatherer()
-        if experiment == "generate_micro_data":
-            datagen = sampling.DataGenerator()
-            datagen.init(coupler, os.getcwd())                                 # generate_micro_data.cpp:66
-            info["samples"] = 0
-        evaluator, eval_calls, eval_step = None, [], [0]
-        if experiment == "evaluate_surrogates":
-            evaluator, eval_models = _surrogate_evaluator(cfg["surrogate_models"], device)
-            domain_eval = _domain_split_evaluator(eval_domain, evaluator, eval_models) if eval_domain is not None else None
-            committee_evals = []                                               # (committee, its evaluator on the bank of its width)
-            for c in committees:
-                places = [[m["name"] for m in eval_models].index(n) for n in c["members"]]
-                first = 0
-                for bank in evaluator.banks:
-                    if first <= places[0] < first + bank.models:
-                        committee_evals.append((c, surrogate_eval.CommitteeEvaluator(bank, [i - first for i in places])))
-                    first += bank.models
-        scorer = rollout.RolloutScorer(micro.member_names) if experiment == "rollout_surrogates" else None
-        rain = None
-        if experiment == "rollout_surrogates" and rain_cfg is not None:
-            micro.surface_rain = {}                                            # every member but Kessler from its water budget
-            rain = rollout.RainScorer(micro.member_names, rain_cfg["thresholds_mm_h"], rain_cfg["thresholds_mm"])
-        if experiment == "rollout_surrogates" and domain_cfg is not None:
-            micro.training_domain = domain_cfg
-        harvester = None
-        if experiment == "rollout_surrogates" and harvest is not None:
-            harvester = micro.harvester = rollout.RolloutHarvester()
-            outside = {}
-            if "outside" in harvest:                                           # each harvested model's own box; a stencil model reads the level above
-                o = harvest["outside"]
-                widths = {m["name"]: int(w[0].shape[0]) for m, w in zip(cfg["surrogate_models"], bank)}
-                outside = dict(outside=o, boxes=[micro.model_box(n, o["margin"], o["fields"]) for n in harvest["members"]],
-                               above=[widths[n] == 9 for n in harvest["members"]])
-            harvester.init(coupler, harvest["members"], [micro.member_names.index(n) for n in harvest["members"]], os.getcwd(),
-                           harvest["samples_per_step"], harvest["ratio_active"], seed=harvest["seed"], max_rainsplit=harvest["max_rainsplit"],
-                           **outside)
+            micro.init(coupler, **kw)
+        # the form travels with the files: the single model's, or every committee model's
+        info["surrogate_form"] = micro.form if self.committee is None else micro._committee.forms
+        if "tendency" in info["surrogate_form"] and not self.quiet and coupler.is_mainproc():     # (a state model prints what it always did)
+            print("inference_ponni: surrogate output form: %s" % info["surrogate_form"], flush=True)
+        return micro
 
-        def body(dt, etime):                                                   # :73-76
-            dycore.time_step(coupler, dt)
-            if evaluator is not None:
-                if eval_step[0] % cfg["eval_interval"] == 0:
-                    inp = Coupler(device)
-                    coupler.clone_into(inp)
-                    micro.time_step(coupler, dt)
-                    evaluator.accumulate(inp, coupler)
-                    if domain_eval is not None:
-                        domain_eval.accumulate(inp, coupler)
-                    for _, ce in committee_evals:
-                        ce.accumulate(inp, coupler)
-                    eval_calls.append({"step": eval_step[0], "etime": etime})
-                else:
-                    micro.time_step(coupler, dt)
-                eval_step[0] += 1
-            elif stats is not None or datagen is not None:
-                inp = Coupler(device)
-                coupler.clone_into(inp)                                        # gather_statistics.cpp:79-80
-                micro.time_step(coupler, dt)
-                if stats is not None:
-                    stats.gather_micro_statistics(inp, coupler, dt, etime)
-                else:
-                    info["samples"] += datagen.generate_samples_stencil(inp, coupler, dt, etime)
-            else:
-                if harvester is not None:                                      # (eval_step counts the steps of a rollout)
-                    micro.harvest_now, micro.harvest_etime = eval_step[0] % harvest["interval"] == 0, etime
-                if scorer is not None and domain_cfg is not None:              # the report's pass runs at scoring steps only
-                    micro.domain_now = eval_step[0] % cfg["eval_interval"] == 0
-                micro.time_step(coupler, dt)
-                if experiment == "inference_ponni" and not quiet and coupler.is_mainproc():
-                    d = micro.mean_diffs(coupler)                              # microphysics_kessler_ponni.h:266-269
-                    print("Relative diff rho_v: %r\nRelative diff rho_c: %r\nRelative diff rho_r: %r\nRelative diff temp : %r" %
-                          (d["rho_v"], d["rho_c"], d["rho_r"], d["temp"]), flush=True)
-            column.sponge_layer(coupler, dt)
-            column_nudger.nudge_to_column(coupler, dt)                         # (eager: the scorer reads the nudged fields)
-            if scorer is not None:
-                if eval_step[0] % cfg["eval_interval"] == 0:
-                    before = dict(scorer.diverged_at)
-                    scorer.accumulate(coupler, eval_step[0], etime + dt)
-                    micro.guard_record(eval_step[0], dt)                       # (the only host read of the guards' counts)
-                    micro.domain_record(eval_step[0])                          # (and of the training-domain report's)
-                    if rain is not None:
-                        rain.accumulate(coupler, micro, eval_step[0], etime + dt)
-                    for m, d in scorer.diverged_at.items():                    # the other members do not see it: the run goes on
-                        if d is not None and before[m] is None and not quiet:
-                            print("rollout_surrogates: member %r is non-finite at step %d" % (m, d["step"]), flush=True)
-                eval_step[0] += 1
-        if experiment == "community_benchmark":                                # timer "simulation_loop", community_benchmark/driver.cpp:66,82
-            torch.cuda.synchronize(device)
-            t0 = time.perf_counter()
-        etime, steps = _time_loop(cfg, dycore, coupler, body, max_steps)
-        if experiment == "community_benchmark":
-            torch.cuda.synchronize(device)
-            info["simulation_loop_s"] = time.perf_counter() - t0
-        if stats is not None:
-            stats.finalize(coupler)
-            info["ratio_active"] = stats.ratio(coupler)
-        if evaluator is not None:
-            import json
-            rep = evaluator.report() if eval_calls else {}
-            doc = {"experiment": experiment, "yaml": os.path.abspath(yaml_path), "eval_interval": cfg["eval_interval"], "steps": steps,
-                   "models": [dict(m, bank=ib, n_in=b.n_in, form=b.forms[k]) for ib, b in enumerate(evaluator.banks)
-                              for k, m in enumerate(eval_models[sum(x.models for x in evaluator.banks[:ib]):][:b.models])],
-                   "statistics": ["sum_d", "sum_abs_d", "sum_d2", "max_abs_d"], "fields": list(surrogate_eval.EVAL_FIELDS),
-                   "classes": list(surrogate_eval.EVAL_CLASSES), "report": rep,
-                   "history": [dict(c, banks=h) for c, h in zip(eval_calls, evaluator.history)]}
-            if committee_evals:
-                doc["committees"] = [dict(c, n_in=ce.bank.n_in, statistics=["sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_r", "sum_r2", "sum_r_abs_d"],
-                                          report=ce.report() if eval_calls else {}, history=ce.history) for c, ce in committee_evals]
-                info["committee_reports"] = {c["name"]: d["report"] for (c, _), d in zip(committee_evals, doc["committees"])}
+    def micro_step(self, dt, etime):
+        self.micro.time_step(self.coupler, dt)
+        if not self.quiet and self.coupler.is_mainproc():
+            d = self.micro.mean_diffs(self.coupler)                            # microphysics_kessler_ponni.h:266-269
+            print("Relative diff rho_v: %r\nRelative diff rho_c: %r\nRelative diff rho_r: %r\nRelative diff temp : %r" %
+                  (d["rho_v"], d["rho_c"], d["rho_r"], d["temp"]), flush=True)
+
+
+class GatherStatistics(Column):
+    def setup(self, *args):
+        super().setup(*args)
+        self.stats = sampling.StatisticsGatherer()
+
+    def micro_step(self, dt, etime):
+        inp = self.micro_step_keeping_input(dt)
+        self.stats.gather_micro_statistics(inp, self.coupler, dt, etime)
+
+    def finish(self, steps, yaml_path):
+        self.stats.finalize(self.coupler)
+        self.info["ratio_active"] = self.stats.ratio(self.coupler)
+
+
+class GenerateMicroData(Column):
+    def setup(self, *args):
+        super().setup(*args)
+        self.datagen = sampling.DataGenerator()
+        self.datagen.init(self.coupler, os.getcwd())                           # generate_micro_data.cpp:66
+        self.info["samples"] = 0
+
+    def micro_step(self, dt, etime):
+        inp = self.micro_step_keeping_input(dt)
+        self.info["samples"] += self.datagen.generate_samples_stencil(inp, self.coupler, dt, etime)
+
+
+def evaluation_document(experiment, yaml_path, eval_interval, steps, evaluator, eval_models, eval_calls, rep, committee_evals=(),
+                        eval_domain=None, domain_eval=None, drep=None):
+    """surrogate_evaluation.json as a dict.  rep, drep: the evaluator's and the DomainSplitEvaluator's reports ({} without a call);
+    committee_evals: (committee, its CommitteeEvaluator) pairs; eval_domain: the checked key, None with domain_eval None."""
+    doc = {"experiment": experiment, "yaml": os.path.abspath(yaml_path), "eval_interval": eval_interval, "steps": steps,
+           "models": [dict(m, bank=ib, n_in=b.n_in, form=b.forms[k]) for ib, b in enumerate(evaluator.banks)
+                      for k, m in enumerate(eval_models[sum(x.models for x in evaluator.banks[:ib]):][:b.models])],
+           "statistics": ["sum_d", "sum_abs_d", "sum_d2", "max_abs_d"], "fields": list(surrogate_eval.EVAL_FIELDS),
+           "classes": list(surrogate_eval.EVAL_CLASSES), "report": rep,
+           "history": [dict(c, banks=h) for c, h in zip(eval_calls, evaluator.history)]}
+    if committee_evals:
+        doc["committees"] = [dict(c, n_in=ce.bank.n_in, statistics=["sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_r", "sum_r2", "sum_r_abs_d"],
+                                  report=ce.report() if eval_calls else {}, history=ce.history) for c, ce in committee_evals]
+    if domain_eval is not None:
+        doc["domain"] = dict(eval_domain, group={str(b.n_in): b.domain_group for b in evaluator.banks},
+                             models={n: {"box": surrogate_eval.box_json(domain_eval.boxes[k]), "report": drep.get(n, {})}
+                                     for k, n in enumerate(domain_eval.names)},
+                             history=[dict(c, banks=h) for c, h in zip(eval_calls, domain_eval.history)])
+    return doc
+
+
+class EvaluateSurrogates(Column):
+    def configure(self, cfg, nranks):
+        _one_rank("evaluate_surrogates", nranks)
+        self.committees = evaluation_committees(cfg)
+        cfg["surrogate_models"], cfg["eval_interval"] = surrogate_config(cfg)
+        self.eval_domain = eval_domain_key(cfg, [m["name"] for m in cfg["surrogate_models"]])
+
+    def setup(self, *args):
+        super().setup(*args)
+        self.evaluator, self.eval_models = _surrogate_evaluator(self.cfg["surrogate_models"], self.device)
+        self.domain_eval = None
+        if self.eval_domain is not None:
+            self.domain_eval = _domain_split_evaluator(self.eval_domain, self.evaluator, self.eval_models)
+        self.committee_evals = []                                              # (committee, its evaluator on the bank of its width)
+        for c in self.committees:
+            places = [[m["name"] for m in self.eval_models].index(n) for n in c["members"]]
+            first = 0
+            for bank in self.evaluator.banks:
+                if first <= places[0] < first + bank.models:
+                    self.committee_evals.append((c, surrogate_eval.CommitteeEvaluator(bank, [i - first for i in places])))
+                first += bank.models
+        self.eval_calls = []
+
+    def micro_step(self, dt, etime):
+        if self.nstep % self.cfg["eval_interval"] != 0:
+            return super().micro_step(dt, etime)
+        inp = self.micro_step_keeping_input(dt)
+        self.evaluator.accumulate(inp, self.coupler)
+        if self.domain_eval is not None:
+            self.domain_eval.accumulate(inp, self.coupler)
+        for _, ce in self.committee_evals:
+            ce.accumulate(inp, self.coupler)
+        self.eval_calls.append({"step": self.nstep, "etime": etime})
+
+    def finish(self, steps, yaml_path):
+        info, evaluator, domain_eval = self.info, self.evaluator, self.domain_eval
+        rep = evaluator.report() if self.eval_calls else {}
+        drep = None if domain_eval is None else (domain_eval.report() if self.eval_calls else {})
+        doc = evaluation_document(info["experiment"], yaml_path, self.cfg["eval_interval"], steps, evaluator, self.eval_models, self.eval_calls,
+                                  rep, self.committee_evals, self.eval_domain, domain_eval, drep)
+        if self.committee_evals:
+            info["committee_reports"] = {d["name"]: d["report"] for d in doc["committees"]}
+        if domain_eval is not None:
+            info["domain_report"] = drep
+        info["surrogate_evaluation"] = os.path.join(os.getcwd(), "surrogate_evaluation.json")
+        with open(info["surrogate_evaluation"], "w") as f:
+            json.dump(doc, f, indent=1)
+        info["surrogate_report"] = rep
+        if not self.quiet and rep:
+            print(evaluator.table(rep), flush=True)
             if domain_eval is not None:
-                drep = domain_eval.report() if eval_calls else {}
-                doc["domain"] = dict(eval_domain, group={str(b.n_in): b.domain_group for b in evaluator.banks},
-                                     models={n: {"box": surrogate_eval.box_json(domain_eval.boxes[k]), "report": drep.get(n, {})}
-                                             for k, n in enumerate(domain_eval.names)},
-                                     history=[dict(c, banks=h) for c, h in zip(eval_calls, domain_eval.history)])
-                info["domain_report"] = drep
-            info["surrogate_evaluation"] = os.path.join(os.getcwd(), "surrogate_evaluation.json")
-            with open(info["surrogate_evaluation"], "w") as f:
-                json.dump(doc, f, indent=1)
-            info["surrogate_report"] = rep
-            if not quiet and rep:
-                print(evaluator.table(rep), flush=True)
-                if domain_eval is not None:
-                    print(domain_eval.table(drep), flush=True)
-                for c, ce in committee_evals:
-                    print(ce.table(name=c["name"]), flush=True)
-        if scorer is not None:
-            import json
-            rep = scorer.report() if scorer.times else {"times": [], "diverged_at": dict(scorer.diverged_at)}
-            doc = {"experiment": experiment, "yaml": os.path.abspath(yaml_path), "eval_interval": cfg["eval_interval"], "steps": steps,
-                   "members": list(scorer.member_names), "models": [dict(m, member=1 + k, form=micro.model_forms[k]) for k, m in enumerate(cfg["surrogate_models"])],
-                   "fields": list(scorer.fields), "statistics": list(rollout.ROLLOUT_STATS), "history": scorer.history,
-                   "report": rep["times"], "diverged_at": rep["diverged_at"]}
-            if committees:
-                doc["committees"] = [dict(c, member=scorer.member_names.index(c["name"])) for c in committees]
-                for c, g in zip(doc["committees"], micro.guard_reports()):
-                    if g is not None:
-                        c["guard"] = g
-            if domain_cfg is not None:                                         # one block per network-stepped member
-                blocks = micro.domain_reports()
-                for entry in doc["models"] + doc.get("committees", []):
-                    entry["domain"] = blocks[entry["member"]]
-                info["domain_reports"] = {scorer.member_names[m]: b for m, b in enumerate(blocks) if b is not None}
-            if harvester is not None:
-                doc["harvest"] = info["harvest"] = harvest_block(harvest, harvester)
-            if rain is not None:
-                doc["surface_rain"] = dict(rain_cfg, report=rain.times)
-                info["surface_rain_report"], info["rain_total"] = rain.times, micro.rain_total
-                if rain_cfg["map"] and micro.rain_total is not None:           # (nens, ny, nx) fp64, mm since the start of the run
-                    import numpy as np
-                    info["surface_rain_map"] = os.path.join(os.getcwd(), "surrogate_rollout_rain.npy")
-                    np.save(info["surface_rain_map"], np.ascontiguousarray((1000.0 * micro.rain_total).permute(2, 0, 1).cpu().numpy()))
-            info["surrogate_rollout"] = os.path.join(os.getcwd(), "surrogate_rollout.json")
-            with open(info["surrogate_rollout"], "w") as f:
-                json.dump(doc, f, indent=1, allow_nan=False)
-            info["rollout_report"] = rep
-            if not quiet and scorer.times:
-                print(scorer.table(rep), flush=True)
-                if rain is not None and rain.times:
-                    print(rain.table(), flush=True)
+                print(domain_eval.table(drep), flush=True)
+            for c, ce in self.committee_evals:
+                print(ce.table(name=c["name"]), flush=True)
+
+
+def rollout_document(experiment, yaml_path, eval_interval, steps, models, scorer, rep, micro, committees=(), domain_blocks=None,
+                     harvest=None, rain_cfg=None, rain=None):
+    """surrogate_rollout.json as a dict.  rep: the scorer's report; domain_blocks: micro.domain_reports() with `training_domain`;
+    harvest: harvest_block's result with a harvester; rain_cfg, rain: the checked `surface_rain` and its RainScorer.  None: no such block."""
+    doc = {"experiment": experiment, "yaml": os.path.abspath(yaml_path), "eval_interval": eval_interval, "steps": steps,
+           "members": list(scorer.member_names), "models": [dict(m, member=1 + k, form=micro.model_forms[k]) for k, m in enumerate(models)],
+           "fields": list(scorer.fields), "statistics": list(rollout.ROLLOUT_STATS), "history": scorer.history,
+           "report": rep["times"], "diverged_at": rep["diverged_at"]}
+    if committees:
+        doc["committees"] = [dict(c, member=scorer.member_names.index(c["name"])) for c in committees]
+        for c, g in zip(doc["committees"], micro.guard_reports()):
+            if g is not None:
+                c["guard"] = g
+    if domain_blocks is not None:                                              # one block per network-stepped member
+        for entry in doc["models"] + doc.get("committees", []):
+            entry["domain"] = domain_blocks[entry["member"]]
+    if harvest is not None:
+        doc["harvest"] = harvest
+    if rain is not None:
+        doc["surface_rain"] = dict(rain_cfg, report=rain.times)
+    return doc
+
+
+class RolloutSurrogates(Column):
+    def configure(self, cfg, nranks):
+        _one_rank("rollout_surrogates", nranks)
+        self.harvest = harvest_config(cfg)
+        self.rain_cfg = surface_rain_config(cfg)
+        self.domain_cfg = training_domain_config(cfg)
+        self.committees = committee_config(cfg)
+        cfg["surrogate_models"], cfg["eval_interval"], cfg["persistence_member"], cfg["nens"] = rollout_config(cfg)
+
+    def make_micro(self):
+        models = self.cfg["surrogate_models"]
+        micro = rollout.Microphysics_Rollout()
+        bank = mlp.load_surrogate_bank(models)
+        self.stencil = {m["name"]: int(w[0].shape[0]) == 9 for m, w in zip(models, bank)}      # a stencil model reads the level above
+        micro.init(self.coupler, bank, self.cfg["persistence_member"], [m["name"] for m in models],
+                   [(c["name"], c["members"], c["guard"]) if "guard" in c else (c["name"], c["members"]) for c in self.committees],
+                   domains=mlp.load_training_domains(models, bank))
+        return micro
+
+    def setup(self, *args):
+        super().setup(*args)
+        micro, harvest = self.micro, self.harvest
+        self.scorer = rollout.RolloutScorer(micro.member_names)
+        self.rain = None
+        if self.rain_cfg is not None:
+            micro.surface_rain = {}                                            # every member but Kessler from its water budget
+            self.rain = rollout.RainScorer(micro.member_names, self.rain_cfg["thresholds_mm_h"], self.rain_cfg["thresholds_mm"])
+        if self.domain_cfg is not None:
+            micro.training_domain = self.domain_cfg
+        self.harvester = None
+        if harvest is not None:
+            self.harvester = micro.harvester = rollout.RolloutHarvester()
+            outside = {}
+            if "outside" in harvest:                                           # each harvested model's own box
+                o = harvest["outside"]
+                outside = dict(outside=o, boxes=[micro.model_box(n, o["margin"], o["fields"]) for n in harvest["members"]],
+                               above=[self.stencil[n] for n in harvest["members"]])
+            self.harvester.init(self.coupler, harvest["members"], [micro.member_names.index(n) for n in harvest["members"]], os.getcwd(),
+                                harvest["samples_per_step"], harvest["ratio_active"], seed=harvest["seed"],
+                                max_rainsplit=harvest["max_rainsplit"], **outside)
+
+    def micro_step(self, dt, etime):
+        if self.harvester is not None:
+            self.micro.harvest_now, self.micro.harvest_etime = self.nstep % self.harvest["interval"] == 0, etime
+        if self.domain_cfg is not None:                                        # the report's pass runs at scoring steps only
+            self.micro.domain_now = self.nstep % self.cfg["eval_interval"] == 0
+        self.micro.time_step(self.coupler, dt)
+
+    def after_step(self, dt, etime):
+        if self.nstep % self.cfg["eval_interval"] != 0:
+            return
+        scorer, micro, step = self.scorer, self.micro, self.nstep
+        before = dict(scorer.diverged_at)
+        scorer.accumulate(self.coupler, step, etime + dt)
+        micro.guard_record(step, dt)                                           # (the only host read of the guards' counts)
+        micro.domain_record(step)                                              # (and of the training-domain report's)
+        if self.rain is not None:
+            self.rain.accumulate(self.coupler, micro, step, etime + dt)
+        for m, d in scorer.diverged_at.items():                                # the other members do not see it: the run goes on
+            if d is not None and before[m] is None and not self.quiet:
+                print("rollout_surrogates: member %r is non-finite at step %d" % (m, d["step"]), flush=True)
+
+    def finish(self, steps, yaml_path):
+        info, scorer, micro, rain = self.info, self.scorer, self.micro, self.rain
+        rep = scorer.report() if scorer.times else {"times": [], "diverged_at": dict(scorer.diverged_at)}
+        blocks = micro.domain_reports() if self.domain_cfg is not None else None
+        doc = rollout_document(info["experiment"], yaml_path, self.cfg["eval_interval"], steps, self.cfg["surrogate_models"], scorer, rep, micro,
+                               self.committees, domain_blocks=blocks, rain_cfg=self.rain_cfg, rain=rain,
+                               harvest=harvest_block(self.harvest, self.harvester) if self.harvester is not None else None)
+        if blocks is not None:
+            info["domain_reports"] = {scorer.member_names[m]: b for m, b in enumerate(blocks) if b is not None}
+        if self.harvester is not None:
+            info["harvest"] = doc["harvest"]
+        if rain is not None:
+            info["surface_rain_report"], info["rain_total"] = rain.times, micro.rain_total
+            if self.rain_cfg["map"] and micro.rain_total is not None:          # (nens, ny, nx) fp64, mm since the start of the run
+                info["surface_rain_map"] = os.path.join(os.getcwd(), "surrogate_rollout_rain.npy")
+                np.save(info["surface_rain_map"], np.ascontiguousarray((1000.0 * micro.rain_total).permute(2, 0, 1).cpu().numpy()))
+        info["surrogate_rollout"] = os.path.join(os.getcwd(), "surrogate_rollout.json")
+        with open(info["surrogate_rollout"], "w") as f:
+            json.dump(doc, f, indent=1, allow_nan=False)
+        info["rollout_report"] = rep
+        if not self.quiet and scorer.times:
+            print(scorer.table(rep), flush=True)
+            if rain is not None and rain.times:
+                print(rain.table(), flush=True)
+
+
+EXPERIMENT_CLASSES = {"supercell_example": Column, "community_benchmark": CommunityBenchmark, "simple_city": SimpleCity,
+                      "inference_ponni": InferencePonni, "gather_statistics": GatherStatistics, "generate_micro_data": GenerateMicroData,
+                      "evaluate_surrogates": EvaluateSurrogates, "rollout_surrogates": RolloutSurrogates}
+
+
+def run(experiment, yaml_path, max_steps=None, device="cuda:0", quiet=False):
+    if experiment not in EXPERIMENTS:
+        raise ValueError("unknown experiment %r (one of %s)" % (experiment, ", ".join(EXPERIMENTS)))
+    cfg = load_config(yaml_path)
+    nranks, myrank, device = _distributed(device)
+    exp = EXPERIMENT_CLASSES[experiment]()
+    exp.configure(cfg, nranks)
+    coupler = _coupler(cfg, device, nranks, myrank, yaml_path)
+    dycore = Dynamics_Euler_Stratified_WenoFV()
+    info = {"experiment": experiment, "nranks": nranks}
+    t_main = time.perf_counter()
+    exp.setup(cfg, coupler, dycore, info, device, quiet)
+    if exp.timed:
+        torch.cuda.synchronize(device)
+        t0 = time.perf_counter()
+    etime, steps = _time_loop(cfg, dycore, coupler, exp.step, max_steps)
+    if exp.timed:
+        torch.cuda.synchronize(device)
+        info["simulation_loop_s"] = time.perf_counter() - t0
+    exp.finish(steps, yaml_path)
     torch.cuda.synchronize(device)
     info.update(etime=etime, steps=steps, main_s=time.perf_counter() - t_main, dycore_etime=dycore.etime, num_out=dycore.num_out)
     if not quiet and coupler.is_mainproc():
