@@ -238,9 +238,6 @@ int mw::mlp_strict() { return g_mlp_strict; }
 
 static bool form_known(int form) { return form == MW_FORM_STATE || form == MW_FORM_TENDENCY; }
 
-// launches the first kernel where the condition holds, else the second (a kernel template's two instantiations, each in parentheses)
-#define MW_LAUNCH_FORM(cond, KT, KF, ...) do { if (cond) hipLaunchKernelGGL(KT, __VA_ARGS__); else hipLaunchKernelGGL(KF, __VA_ARGS__); } while (0)
-
 extern "C" int mw_mlp_forward_form(int form, long long ncells, const double *temp, const double *rho_d, const double *rho_v, const double *rho_c,
                                    const double *rho_r, const float *W1, const float *b1, const float *W2, const float *b2,
                                    const double *scl_in, const double *scl_out, double *temp_out, double *rho_v_out,
@@ -254,7 +251,7 @@ extern "C" int mw_mlp_forward_form(int form, long long ncells, const double *tem
   if (g_mlp_strict) {
     MlpRef R;
     fill_ref(R, 5, W1, b1, W2, b2, scl_in, scl_out, form);
-    MW_LAUNCH_FORM(tend, (k_mlp_strict<true>), (k_mlp_strict<false>), dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, R, ncells, temp, rho_d, rho_v, rho_c,
+    MW_LAUNCH_IF(tend, (k_mlp_strict<true>), (k_mlp_strict<false>), dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, R, ncells, temp, rho_d, rho_v, rho_c,
                        rho_r, temp_out, rho_v_out, rho_c_out, rho_r_out);
     MW_LAUNCH_CHECK();
     return 0;
@@ -274,7 +271,7 @@ extern "C" int mw_mlp_forward_form(int form, long long ncells, const double *tem
     long long waves_needed = (bulk / 32 + PAIRS - 1) / PAIRS;
     long long blocks = (waves_needed + 3) / 4;
     if (blocks > 256 * 16) blocks = 256 * 16;                   // grid-stride beyond 16 blocks per CU
-    MW_LAUNCH_FORM(tend, (k_mlp_x2<PAIRS, true>), (k_mlp_x2<PAIRS, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, bulk, temp, rho_d, rho_v, rho_c,
+    MW_LAUNCH_IF(tend, (k_mlp_x2<PAIRS, true>), (k_mlp_x2<PAIRS, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, bulk, temp, rho_d, rho_v, rho_c,
                        rho_r, temp_out, rho_v_out, rho_c_out, rho_r_out);
     MW_LAUNCH_CHECK();
   }
@@ -285,7 +282,7 @@ extern "C" int mw_mlp_forward_form(int form, long long ncells, const double *tem
     long long blocks = (waves_needed + 3) / 4;
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (blocks < 1) blocks = 1;
-    MW_LAUNCH_FORM(tend, (k_mlp<TILES, true>), (k_mlp<TILES, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, rest, temp + bulk, rho_d + bulk, rho_v + bulk,
+    MW_LAUNCH_IF(tend, (k_mlp<TILES, true>), (k_mlp<TILES, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, rest, temp + bulk, rho_d + bulk, rho_v + bulk,
                        rho_c + bulk, rho_r + bulk, temp_out + bulk, rho_v_out + bulk, rho_c_out + bulk, rho_r_out + bulk);
     MW_LAUNCH_CHECK();
   }
@@ -468,7 +465,7 @@ extern "C" int mw_mlp_stencil_forward_form(int form, int nz, long long ncol, con
   if (g_mlp_strict) {
     StencilRef R;
     fill_ref(R, 9, W1, b1, W2, b2, scl_in, scl_out, form);
-    MW_LAUNCH_FORM(tend, (k_mlp_stencil_strict<true>), (k_mlp_stencil_strict<false>), dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, R, nz, ncol, temp, rho_d,
+    MW_LAUNCH_IF(tend, (k_mlp_stencil_strict<true>), (k_mlp_stencil_strict<false>), dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, R, nz, ncol, temp, rho_d,
                        rho_v, rho_c, rho_r, temp_out, rho_v_out, rho_c_out, rho_r_out);
     MW_LAUNCH_CHECK();
     return 0;
@@ -481,7 +478,7 @@ extern "C" int mw_mlp_stencil_forward_form(int form, int nz, long long ncol, con
   const int zc = mw_mlp_stencil_chunk(nz, ncol), nchunks = (nz + zc - 1) / zc;
   const long long waves = ((ncol + 15) / 16) * nchunks, blocks = (waves + 3) / 4;
   if (blocks > 0x7fffffffll) MW_FAIL("mlp_stencil: grid too large");
-  MW_LAUNCH_FORM(tend, (k_mlp_stencil<4, true>), (k_mlp_stencil<4, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, nz, ncol, zc, nchunks, temp, rho_d, rho_v,
+  MW_LAUNCH_IF(tend, (k_mlp_stencil<4, true>), (k_mlp_stencil<4, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, nz, ncol, zc, nchunks, temp, rho_d, rho_v,
                      rho_c, rho_r, temp_out, rho_v_out, rho_c_out, rho_r_out);
   MW_LAUNCH_CHECK();
   return 0;

@@ -75,6 +75,9 @@ inline void fill_ref(R &ref, int n_in, const float *W1, const float *b1, const f
   memcpy(ref.W1, W1, sizeof(float) * 10 * n_in); memcpy(ref.b1, b1, sizeof(ref.b1)); memcpy(ref.W2, W2, sizeof(ref.W2)); memcpy(ref.b2, b2, sizeof(ref.b2));
   fill_scaling(n_in, scl_in, scl_out, ref.in_min, ref.in_rng, ref.out_min, ref.out_rng);
 }
+// launches the first kernel where the condition holds, else the second (a kernel template's two instantiations, each in parentheses):
+// TEND of the forward kernels, ANYT of the bank's
+#define MW_LAUNCH_IF(cond, KT, KF, ...) do { if (cond) hipLaunchKernelGGL(KT, __VA_ARGS__); else hipLaunchKernelGGL(KF, __VA_ARGS__); } while (0)
 
 // the larger / smaller of two values, NaN if either is: a diverged model must not show a finite extremum (fmax / fmin would drop the NaN)
 __device__ __forceinline__ double eval_max(double a, double b) { return (b > a || b != b) ? b : a; }

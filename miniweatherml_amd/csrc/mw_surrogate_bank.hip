@@ -62,20 +62,12 @@ __global__ __launch_bounds__(256) void k_surrogate_eval(const EvalModel *__restr
   for (long long t0 = wave * TILES; t0 < ntiles; t0 += nwaves * TILES) {
     double xin[TILES], xs[TILES], xt[TILES];
     bool ina[TILES], inn[TILES];
-#pragma unroll
-    for (int u = 0; u < TILES; u++) {
-      const long long cell = (t0 + u) * 16 + cidx;
-      const bool ok = cell < ncells;
-      xin[u] = ok ? in_g[cell] : 0.0;
-      xs[u]  = ok ? in_s[cell] : 0.0;
-      xt[u]  = ok ? tr_g[cell] : 0.0;
-    }
+    MW_EVAL_TILE_LOAD(TILES, xin, xs, xt, in_g, in_s, tr_g, t0, cidx, ncells)
 #pragma unroll
     for (int u = 0; u < TILES; u++) {
       const bool ok = (t0 + u) * 16 + cidx < ncells;
       const double before = g == 0 ? xin[u] : xs[u];
-      const bool act = eval_cell_active(ok && fabs(xt[u] - before) > 1.e-10, cidx);          // gather_micro_statistics.h:61-74
-      ina[u] = ok && act; inn[u] = ok && !act;
+      MW_EVAL_CELL_CLASS(ina[u], inn[u], ok, xt[u], before, cidx)
       nact += __popcll(__ballot(ina[u] && g == 0));
       eval_add(accp, before, xt[u], inn[u], ina[u]);
     }
@@ -123,10 +115,7 @@ __global__ __launch_bounds__(256) void k_surrogate_eval_stencil(const EvalModel 
     const bool ok = col < ncol;
     const int k_lo = chunk * zc, k_hi = min(nz, k_lo + zc) - 1, k_top = min(nz - 1, k_hi + 1);
     double above = 0.0, rr = 0.0;                                         // raw: the level above of this lane's field, this group's latest rho_r
-    if (ok) {
-      above = in_g[(long long)k_top * ncol + col];
-      if (g == ((k_hi & 1) ^ 1)) rr = rho_r[(long long)k_top * ncol + col];
-    }
+    MW_SWEEP_TOP(above, rr, in_g, rho_r, (long long)k_top * ncol + col, ok, g, k_hi)
     for (int k0 = k_hi; k0 >= k_lo; k0 -= U) {
       double xin[U], xab[U], xrr[U], xs[U], xt[U];
       bool ina[U], inn[U];
@@ -135,21 +124,15 @@ __global__ __launch_bounds__(256) void k_surrogate_eval_stencil(const EvalModel 
         const int k = k0 - u;
         const bool lv = ok && k >= k_lo;
         const long long idx = (long long)k * ncol + col;
-        xin[u] = lv ? in_g[idx] : 0.0;
-        xrr[u] = (lv && g == (k & 1)) ? rho_r[idx] : 0.0;
-        xs[u]  = (lv && g != 0) ? in_s[idx] : xin[u];                     // the field output g replaces (group 0: temp, which it holds)
+        MW_SWEEP_LEVEL(xin[u], xrr[u], xs[u], in_g, rho_r, in_s, idx, lv, g, k)
         xt[u]  = lv ? tr_g[idx] : 0.0;
       }
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const int k = k0 - u;
         const bool lv = ok && k >= k_lo;
-        if (k >= k_lo) {                                                  // (wave-uniform)
-          if (g == (k & 1)) rr = xrr[u];
-          xrr[u] = rr; xab[u] = above; above = xin[u];                    // level k is level k - 1's level above
-        }
-        const bool act = eval_cell_active(lv && fabs(xt[u] - xs[u]) > 1.e-10, cidx);
-        ina[u] = lv && act; inn[u] = lv && !act;
+        if (k >= k_lo) MW_SWEEP_CARRY(g, k, xin[u], xrr[u], xab[u], rr, above)        // (wave-uniform)
+        MW_EVAL_CELL_CLASS(ina[u], inn[u], lv, xt[u], xs[u], cidx)
         nact += __popcll(__ballot(ina[u] && g == 0));
         eval_add(accp, xs[u], xt[u], inn[u], ina[u]);
       }
@@ -191,10 +174,8 @@ __global__ __launch_bounds__(256) void k_surrogate_eval_strict(const StencilRef 
   for (int v = 0; v < 4; v++) eval_zero(acc[v]);
   long long nact = 0;
   for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < n; c += (long long)gridDim.x * 256) {
-    const long long k = c / ncol;
-    const long long ca = (k + 1 < nz) ? c + ncol : c;                     // level min(nz - 1, k + 1), same column
-    double in[9] = {F.in[0][c], F.in[1][c], F.in[2][c], F.in[3][c], F.in[4][c], 0.0, 0.0, 0.0, 0.0};
-    if (NIN == 9) { in[5] = F.in[0][ca]; in[6] = F.in[2][ca]; in[7] = F.in[3][ca]; in[8] = F.in[4][ca]; }
+    const StrictIn I = strict_cell_inputs<NIN>(F.in, c, nz, ncol);
+    const double *in = I.v;
     const double before[4] = {in[0], in[2], in[3], in[4]};
     const double tr[4] = {F.truth[0][c], F.truth[1][c], F.truth[2][c], F.truth[3][c]};
     bool act = false;
@@ -209,21 +190,11 @@ __global__ __launch_bounds__(256) void k_surrogate_eval_strict(const StencilRef 
     nact += act ? 1 : 0;
   }
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int r = 0; r < EVAL_ROW; r++) {
-    const double q = eval_lane_tree<64>(acc[(r >> 2) & 3].s[r >> 4][r & 3], (r & 3) == 3);
-    if (lane == 0) red[wv][r] = q;
-  }
+  eval_strict_trees<EVAL_ROW>(acc, red);
   for (int off = 32; off > 0; off >>= 1) nact += __shfl_xor(nact, off, 64);
   if (lane == 0) wcount[wv] = nact;
   __syncthreads();
-  if (threadIdx.x < EVAL_ROW) {
-    const int r = threadIdx.x;
-    double q = red[0][r];
-#pragma unroll
-    for (int w = 1; w < 4; w++) q = (r & 3) == 3 ? eval_max(q, red[w][r]) : q + red[w][r];
-    partial[((long long)blockIdx.x * (models + 1) + m) * EVAL_ROW + r] = q;
-  }
+  eval_strict_row_store<EVAL_ROW>(red, partial + ((long long)blockIdx.x * (models + 1) + m) * EVAL_ROW);
   if (threadIdx.x == 0 && m == models) cpartial[blockIdx.x] = wcount[0] + wcount[1] + wcount[2] + wcount[3];
 }
 
@@ -232,14 +203,7 @@ __global__ __launch_bounds__(256) void k_surrogate_eval_final(int nblocks, int r
                                                               const long long *__restrict__ cpartial, double *__restrict__ out,
                                                               long long *__restrict__ counts) {
   const int e = blockIdx.x * 256 + threadIdx.x, len = rows * EVAL_ROW;
-  if (e < len) {
-    double q = 0.0;
-    for (int b = 0; b < nblocks; b++) {
-      const double o = partial[(long long)b * len + e];
-      q = (e & 3) == 3 ? eval_max(q, o) : q + o;
-    }
-    out[e] = q;
-  }
+  eval_final_store(nblocks, len, e, partial, out);
   if (e == 0) {
     long long a = 0;
     for (int b = 0; b < nblocks; b++) a += cpartial[b];
@@ -324,39 +288,25 @@ extern "C" int mw_surrogate_eval_group(mw_surrogate_bank_t b) {
 
 extern "C" int mw_surrogate_eval(mw_surrogate_bank_t b, int nz, long long ncol, const double *const *in5, const double *const *truth4,
                                  double *out, long long *counts, void *stream) {
-  if (!b || !in5 || !truth4 || !out || !counts) MW_FAIL("surrogate_eval: null pointer");
-  if (nz < 1 || ncol < 1) MW_FAIL("surrogate_eval: nz and ncol must be >= 1");
   EvalFields F;
-  for (int i = 0; i < 5; i++) { if (!in5[i]) MW_FAIL("surrogate_eval: null field"); F.in[i] = in5[i]; }
-  for (int i = 0; i < 4; i++) { if (!truth4[i]) MW_FAIL("surrogate_eval: null field"); F.truth[i] = truth4[i]; }
-  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  if (eval_fields("surrogate_eval", F, b, nz, ncol, in5, truth4, out, counts)) return 1;
   hipStream_t st = (hipStream_t)stream;
   const long long ncells = (long long)nz * ncol;
   const int models = b->models, rows = models + 1;
-  // grid.x from the shape alone: a model's partial sums do not depend on how many models share the call
-  constexpr int TILES = 4, U = 4;
-  const int zc = mw_mlp_stencil_chunk(nz, ncol), nchunks = (nz + zc - 1) / zc;
-  long long blocks;
-  if (mlp_strict()) blocks = (ncells + 255) / 256;
-  else if (b->n_in == 5) blocks = (((ncells + 15) / 16 + TILES - 1) / TILES + 3) / 4;
-  else blocks = (((ncol + 15) / 16) * nchunks + 3) / 4;
-  blocks = std::max<long long>(1, std::min<long long>(blocks, EVAL_MAX_BLOCKS));
-  if (blocks > b->partial_blocks) {
-    (void)hipFree(b->partial); b->partial = nullptr; b->partial_blocks = 0;
-    MW_HIP(hipMalloc(&b->partial, sizeof(double) * (size_t)blocks * rows * EVAL_ROW));
-    b->partial_blocks = blocks;
-  }
+  constexpr int TILES = EVAL_TILES, U = EVAL_U;
+  const auto [blocks, zc, nchunks] = eval_grid(b->n_in, nz, ncol);
+  if (eval_grow(b->partial, b->partial_blocks, blocks, (size_t)rows * EVAL_ROW)) return 1;
   if (mlp_strict()) {
     const dim3 grid((unsigned)blocks, (unsigned)rows);
-    if (b->n_in == 5) MW_LAUNCH_ANYT(b->any_tendency, (k_surrogate_eval_strict<5, true>), (k_surrogate_eval_strict<5, false>), grid, dim3(256), 0, st, b->refs, models, nz, ncol, F, b->partial, b->cpartial);
-    else              MW_LAUNCH_ANYT(b->any_tendency, (k_surrogate_eval_strict<9, true>), (k_surrogate_eval_strict<9, false>), grid, dim3(256), 0, st, b->refs, models, nz, ncol, F, b->partial, b->cpartial);
+    if (b->n_in == 5) MW_LAUNCH_IF(b->any_tendency, (k_surrogate_eval_strict<5, true>), (k_surrogate_eval_strict<5, false>), grid, dim3(256), 0, st, b->refs, models, nz, ncol, F, b->partial, b->cpartial);
+    else              MW_LAUNCH_IF(b->any_tendency, (k_surrogate_eval_strict<9, true>), (k_surrogate_eval_strict<9, false>), grid, dim3(256), 0, st, b->refs, models, nz, ncol, F, b->partial, b->cpartial);
   } else {
     const int G = b->n_in == 5 ? EVAL_G5 : EVAL_G9;
     const dim3 grid((unsigned)blocks, (unsigned)((models + G - 1) / G));
-    if (b->n_in == 5) MW_LAUNCH_ANYT(b->any_tendency, (k_surrogate_eval<EVAL_G5, TILES, true>), (k_surrogate_eval<EVAL_G5, TILES, false>), grid, dim3(256), 0, st, b->images, models, ncells, F, b->partial,
-                                     b->cpartial);
-    else              MW_LAUNCH_ANYT(b->any_tendency, (k_surrogate_eval_stencil<EVAL_G9, U, true>), (k_surrogate_eval_stencil<EVAL_G9, U, false>), grid, dim3(256), 0, st, b->images, models, nz, ncol, zc, nchunks, F,
-                                     b->partial, b->cpartial);
+    if (b->n_in == 5) MW_LAUNCH_IF(b->any_tendency, (k_surrogate_eval<EVAL_G5, TILES, true>), (k_surrogate_eval<EVAL_G5, TILES, false>), grid, dim3(256), 0, st, b->images, models, ncells, F, b->partial,
+                                   b->cpartial);
+    else              MW_LAUNCH_IF(b->any_tendency, (k_surrogate_eval_stencil<EVAL_G9, U, true>), (k_surrogate_eval_stencil<EVAL_G9, U, false>), grid, dim3(256), 0, st, b->images, models, nz, ncol, zc, nchunks, F,
+                                   b->partial, b->cpartial);
   }
   MW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_surrogate_eval_final, dim3((unsigned)((rows * EVAL_ROW + 255) / 256)), dim3(256), 0, st, (int)blocks, rows, ncells,
@@ -386,13 +336,13 @@ struct ApplyMap { int member[APPLY_MAX_MEMBERS]; };
 struct ApplyFields { double *f[5]; };      // temp, density_dry, water_vapor, cloud_liquid, precip_liquid (density_dry is only read)
 
 // wave -> (model, tile slot) of a workgroup: mpb models per workgroup (1, 2 or 4), 4 / mpb tile slots
+__host__ __device__ __forceinline__ int apply_mpb(int models) { return models >= 3 ? 4 : models; }
 __device__ __forceinline__ void apply_slot(int models, int &j, int &slot, int &slots) {
-  const int mpb = models >= 3 ? 4 : models, wv = threadIdx.x >> 6;
+  const int mpb = apply_mpb(models), wv = threadIdx.x >> 6;
   slots = 4 / mpb;
   j = blockIdx.y * mpb + (wv % mpb);
   slot = wv / mpb;
 }
-static int apply_mpb(int models) { return models >= 3 ? 4 : models; }
 
 // ANYT and a model of the tendency form: lane group g > 0 also loads the field its output replaces -- the one it stores to -- in the register
 // that only group 0 uses for rho_r (stencil: one more register per level), with the tile's other loads and ahead of its stores.
@@ -401,7 +351,7 @@ __global__ __launch_bounds__(256) void k_members_apply(const EvalModel *__restri
                                                        ApplyFields F) {
 #pragma clang fp contract(off)
   __shared__ EvalModel sm[4];
-  const int mpb = models >= 3 ? 4 : models, m0 = blockIdx.y * mpb, cnt = min(mpb, models - m0);
+  const int mpb = apply_mpb(models), m0 = blockIdx.y * mpb, cnt = min(mpb, models - m0);
   eval_load_models<4>(sm, bank, m0, cnt);
   int j, slot, slots;
   apply_slot(models, j, slot, slots);
@@ -442,7 +392,7 @@ __global__ __launch_bounds__(256) void k_members_apply_stencil(const EvalModel *
                                                                int nens, ApplyFields F) {
 #pragma clang fp contract(off)
   __shared__ EvalModel sm[4];
-  const int mpb = models >= 3 ? 4 : models, m0 = blockIdx.y * mpb, cnt = min(mpb, models - m0);
+  const int mpb = apply_mpb(models), m0 = blockIdx.y * mpb, cnt = min(mpb, models - m0);
   eval_load_models<4>(sm, bank, m0, cnt);
   int j, slot, slots;
   apply_slot(models, j, slot, slots);
@@ -509,10 +459,8 @@ __global__ __launch_bounds__(256) void k_members_apply_strict(const StencilRef *
     double ab[4];                                                         // temp, rho_v, rho_c, rho_r of level min(nz - 1, k + 1) as they were
     for (int k = nz - 1; k >= 0; k--) {
       const long long c = (long long)k * lev + base;
-      double in[9] = {F.f[0][c], F.f[1][c], F.f[2][c], F.f[3][c], F.f[4][c], 0.0, 0.0, 0.0, 0.0};
-      if (k == nz - 1) { ab[0] = in[0]; ab[1] = in[2]; ab[2] = in[3]; ab[3] = in[4]; }
-      if (NIN == 9) { in[5] = ab[0]; in[6] = ab[1]; in[7] = ab[2]; in[8] = ab[3]; }
-      ab[0] = in[0]; ab[1] = in[2]; ab[2] = in[3]; ab[3] = in[4];
+      const StrictIn I = strict_column_inputs<NIN>(ab, F.f, c, k == nz - 1);
+      const double *in = I.v;
       MW_STRICT_CELL_FORM(NIN, P, in, ANYT && P.form != MW_FORM_STATE, F.f[0][c], F.f[2][c], F.f[3][c], F.f[4][c])
     }
   }
@@ -544,8 +492,8 @@ extern "C" int mw_surrogate_members_apply(mw_surrogate_bank_t b, const int *memb
   if (mlp_strict()) {
     const long long blocks = std::max<long long>(1, std::min<long long>((ncol + 255) / 256, APPLY_MAX_BLOCKS));
     const dim3 grid((unsigned)blocks, (unsigned)models);
-    if (b->n_in == 5) MW_LAUNCH_ANYT(b->any_tendency, (k_members_apply_strict<5, true>), (k_members_apply_strict<5, false>), grid, dim3(256), 0, st, b->refs, map, nz, ncol, nens, F);
-    else              MW_LAUNCH_ANYT(b->any_tendency, (k_members_apply_strict<9, true>), (k_members_apply_strict<9, false>), grid, dim3(256), 0, st, b->refs, map, nz, ncol, nens, F);
+    if (b->n_in == 5) MW_LAUNCH_IF(b->any_tendency, (k_members_apply_strict<5, true>), (k_members_apply_strict<5, false>), grid, dim3(256), 0, st, b->refs, map, nz, ncol, nens, F);
+    else              MW_LAUNCH_IF(b->any_tendency, (k_members_apply_strict<9, true>), (k_members_apply_strict<9, false>), grid, dim3(256), 0, st, b->refs, map, nz, ncol, nens, F);
     MW_LAUNCH_CHECK();
     return 0;
   }
@@ -555,11 +503,11 @@ extern "C" int mw_surrogate_members_apply(mw_surrogate_bank_t b, const int *memb
   if (b->n_in == 5) {
     const long long groups = ((ncells + 15) / 16 + TILES - 1) / TILES;
     const long long blocks = std::max<long long>(1, std::min<long long>((groups + slots - 1) / slots, APPLY_MAX_BLOCKS));
-    MW_LAUNCH_ANYT(b->any_tendency, (k_members_apply<TILES, true>), (k_members_apply<TILES, false>), dim3((unsigned)blocks, gy), dim3(256), 0, st, b->images, models, map, ncells, nens, F);
+    MW_LAUNCH_IF(b->any_tendency, (k_members_apply<TILES, true>), (k_members_apply<TILES, false>), dim3((unsigned)blocks, gy), dim3(256), 0, st, b->images, models, map, ncells, nens, F);
   } else {
     const long long tiles = (ncol + 15) / 16;
     const long long blocks = std::max<long long>(1, std::min<long long>((tiles + slots - 1) / slots, APPLY_MAX_BLOCKS));
-    MW_LAUNCH_ANYT(b->any_tendency, (k_members_apply_stencil<U, true>), (k_members_apply_stencil<U, false>), dim3((unsigned)blocks, gy), dim3(256), 0, st, b->images, models, map, nz, ncol, nens, F);
+    MW_LAUNCH_IF(b->any_tendency, (k_members_apply_stencil<U, true>), (k_members_apply_stencil<U, false>), dim3((unsigned)blocks, gy), dim3(256), 0, st, b->images, models, map, nz, ncol, nens, F);
   }
   MW_LAUNCH_CHECK();
   return 0;
@@ -658,28 +606,21 @@ __global__ __launch_bounds__(256) void k_committee_apply_stencil(const EvalModel
     const long long base = col * nens + member;
     const int k_hi = nz - 1;
     double above = 0.0, rr = 0.0;                                         // raw: the level above of this lane's field, this group's latest rho_r
-    if (ok) {
-      above = in_g[(long long)k_hi * lev + base];                         // the model top is its own level above
-      if (g == ((k_hi & 1) ^ 1)) rr = rho_r[(long long)k_hi * lev + base];
-    }
+    MW_SWEEP_TOP(above, rr, in_g, rho_r, (long long)k_hi * lev + base, ok, g, k_hi)      // the model top is its own level above
     for (int k0 = k_hi; k0 >= 0; k0 -= U) {
       double xin[U], xab[U], xrr[U], xs[U], sum[U], hi[U], lo[U];
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const int k = k0 - u;
         const bool lv = ok && k >= 0;
-        xin[u] = lv ? in_g[(long long)k * lev + base] : 0.0;
-        xrr[u] = (lv && g == (k & 1)) ? rho_r[(long long)k * lev + base] : 0.0;
-        if (ANYT) xs[u] = (lv && g != 0) ? in_s[(long long)k * lev + base] : xin[u];                // level k's own value of the field output g replaces
+        MW_SWEEP_LEVEL(xin[u], xrr[u], xs[u], in_g, rho_r, in_s, (long long)k * lev + base, lv, g, k)
         sum[u] = hi[u] = lo[u] = 0.0;
       }
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const int k = k0 - u;
-        if (k >= 0) {                                                     // (wave-uniform)
-          if (g == (k & 1)) rr = xrr[u];
-          xrr[u] = rr; xab[u] = above; above = xin[u];                    // level k is level k - 1's level above
-        } else { xab[u] = 0.0; }
+        if (k >= 0) MW_SWEEP_CARRY(g, k, xin[u], xrr[u], xab[u], rr, above)           // (wave-uniform)
+        else xab[u] = 0.0;
       }
       for (int j = 0; j < S.n; j++) {
         Net9 N;
@@ -723,10 +664,8 @@ __global__ __launch_bounds__(256) void k_committee_apply_strict(const StencilRef
     double ab[4];                                                         // temp, rho_v, rho_c, rho_r of level min(nz - 1, k + 1) as they were
     for (int k = nz - 1; k >= 0; k--) {
       const long long c = (long long)k * lev + base;
-      double in[9] = {F.in[0][c], F.in[1][c], F.in[2][c], F.in[3][c], F.in[4][c], 0.0, 0.0, 0.0, 0.0};
-      if (k == nz - 1) { ab[0] = in[0]; ab[1] = in[2]; ab[2] = in[3]; ab[3] = in[4]; }
-      if (NIN == 9) { in[5] = ab[0]; in[6] = ab[1]; in[7] = ab[2]; in[8] = ab[3]; }
-      ab[0] = in[0]; ab[1] = in[2]; ab[2] = in[3]; ab[3] = in[4];
+      const StrictIn I = strict_column_inputs<NIN>(ab, F.in, c, k == nz - 1);
+      const double *in = I.v;
       double sum[4], hi[4], lo[4];
       for (int j = 0; j < S.n; j++) {
         double p[4];
@@ -879,8 +818,8 @@ extern "C" int mw_surrogate_committee_apply(mw_surrogate_bank_t b, int n_sel, co
   for (int j = 0; j < n_sel; j++) anyt = anyt || b->forms[(size_t)sel[j]] != MW_FORM_STATE;
   if (mlp_strict()) {
     const long long blocks = std::max<long long>(1, std::min<long long>((ncol + 255) / 256, APPLY_MAX_BLOCKS));
-    if (b->n_in == 5) MW_LAUNCH_ANYT(anyt, (k_committee_apply_strict<5, true>), (k_committee_apply_strict<5, false>), dim3((unsigned)blocks), dim3(256), 0, st, b->refs, S, member, nz, ncol, nens, F);
-    else              MW_LAUNCH_ANYT(anyt, (k_committee_apply_strict<9, true>), (k_committee_apply_strict<9, false>), dim3((unsigned)blocks), dim3(256), 0, st, b->refs, S, member, nz, ncol, nens, F);
+    if (b->n_in == 5) MW_LAUNCH_IF(anyt, (k_committee_apply_strict<5, true>), (k_committee_apply_strict<5, false>), dim3((unsigned)blocks), dim3(256), 0, st, b->refs, S, member, nz, ncol, nens, F);
+    else              MW_LAUNCH_IF(anyt, (k_committee_apply_strict<9, true>), (k_committee_apply_strict<9, false>), dim3((unsigned)blocks), dim3(256), 0, st, b->refs, S, member, nz, ncol, nens, F);
     MW_LAUNCH_CHECK();
     return 0;
   }
@@ -888,11 +827,11 @@ extern "C" int mw_surrogate_committee_apply(mw_surrogate_bank_t b, int n_sel, co
   if (b->n_in == 5) {
     const long long groups = ((ncells + 15) / 16 + TILES - 1) / TILES;
     const long long blocks = std::max<long long>(1, std::min<long long>((groups + 3) / 4, APPLY_MAX_BLOCKS));
-    MW_LAUNCH_ANYT(anyt, (k_committee_apply<TILES, true>), (k_committee_apply<TILES, false>), dim3((unsigned)blocks), dim3(256), 0, st, b->images, S, member, ncells, nens, F);
+    MW_LAUNCH_IF(anyt, (k_committee_apply<TILES, true>), (k_committee_apply<TILES, false>), dim3((unsigned)blocks), dim3(256), 0, st, b->images, S, member, ncells, nens, F);
   } else {
     const long long tiles = (ncol + 15) / 16;
     const long long blocks = std::max<long long>(1, std::min<long long>((tiles + 3) / 4, APPLY_MAX_BLOCKS));
-    MW_LAUNCH_ANYT(anyt, (k_committee_apply_stencil<U, true>), (k_committee_apply_stencil<U, false>), dim3((unsigned)blocks), dim3(256), 0, st, b->images, S, member, nz, ncol, nens, F);
+    MW_LAUNCH_IF(anyt, (k_committee_apply_stencil<U, true>), (k_committee_apply_stencil<U, false>), dim3((unsigned)blocks), dim3(256), 0, st, b->images, S, member, nz, ncol, nens, F);
   }
   MW_LAUNCH_CHECK();
   return 0;

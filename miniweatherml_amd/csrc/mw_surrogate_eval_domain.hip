@@ -127,20 +127,12 @@ __global__ __launch_bounds__(256) void k_surrogate_eval_domain(const EvalModel *
   for (long long t0 = wave * TILES; t0 < ntiles; t0 += nwaves * TILES) {
     double xin[TILES], xs[TILES], xt[TILES];
     bool ina[TILES], inn[TILES];
-#pragma unroll
-    for (int u = 0; u < TILES; u++) {
-      const long long cell = (t0 + u) * 16 + cidx;
-      const bool ok = cell < ncells;
-      xin[u] = ok ? in_g[cell] : 0.0;
-      xs[u]  = ok ? in_s[cell] : 0.0;
-      xt[u]  = ok ? tr_g[cell] : 0.0;
-    }
+    MW_EVAL_TILE_LOAD(TILES, xin, xs, xt, in_g, in_s, tr_g, t0, cidx, ncells)
 #pragma unroll
     for (int u = 0; u < TILES; u++) {
       const bool ok = (t0 + u) * 16 + cidx < ncells;
       const double before = g == 0 ? xin[u] : xs[u];
-      const bool act = eval_cell_active(ok && fabs(xt[u] - before) > 1.e-10, cidx);          // gather_micro_statistics.h:61-74
-      ina[u] = ok && act; inn[u] = ok && !act;
+      MW_EVAL_CELL_CLASS(ina[u], inn[u], ok, xt[u], before, cidx)
       if (!NET) nact += (ina[u] && g == 0) ? 1u : 0u;
     }
 #pragma unroll
@@ -199,10 +191,7 @@ __global__ __launch_bounds__(256) void k_surrogate_eval_domain_stencil(const Eva
     const bool ok = col < ncol;
     const int k_lo = chunk * zc, k_hi = min(nz, k_lo + zc) - 1, k_top = min(nz - 1, k_hi + 1);
     double above = 0.0, rr = 0.0;                                         // raw: the level above of this lane's field, this group's latest rho_r
-    if (ok) {
-      above = in_g[(long long)k_top * ncol + col];
-      if (g == ((k_hi & 1) ^ 1)) rr = rho_r[(long long)k_top * ncol + col];
-    }
+    MW_SWEEP_TOP(above, rr, in_g, rho_r, (long long)k_top * ncol + col, ok, g, k_hi)
     for (int k0 = k_hi; k0 >= k_lo; k0 -= U) {
       double xin[U], xab[U], xrr[U], xs[U], xt[U];
       bool ina[U], inn[U];
@@ -211,21 +200,16 @@ __global__ __launch_bounds__(256) void k_surrogate_eval_domain_stencil(const Eva
         const int k = k0 - u;
         const bool lv = ok && k >= k_lo;
         const long long idx = (long long)k * ncol + col;
-        xin[u] = lv ? in_g[idx] : 0.0;
-        xrr[u] = (lv && g == (k & 1)) ? rho_r[idx] : 0.0;
-        xs[u]  = (lv && g != 0) ? in_s[idx] : xin[u];                     // the field output g replaces (group 0: temp, which it holds)
+        MW_SWEEP_LEVEL(xin[u], xrr[u], xs[u], in_g, rho_r, in_s, idx, lv, g, k)
         xt[u]  = lv ? tr_g[idx] : 0.0;
       }
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const int k = k0 - u;
         const bool lv = ok && k >= k_lo;
-        if (k >= k_lo) {                                                  // (wave-uniform)
-          if (g == (k & 1)) rr = xrr[u];
-          xrr[u] = rr; xab[u] = above; above = xin[u];                    // level k is level k - 1's level above
-        } else { xab[u] = 0.0; }
-        const bool act = eval_cell_active(lv && fabs(xt[u] - xs[u]) > 1.e-10, cidx);
-        ina[u] = lv && act; inn[u] = lv && !act;
+        if (k >= k_lo) MW_SWEEP_CARRY(g, k, xin[u], xrr[u], xab[u], rr, above)        // (wave-uniform)
+        else xab[u] = 0.0;
+        MW_EVAL_CELL_CLASS(ina[u], inn[u], lv, xt[u], xs[u], cidx)
         if (!NET) nact += (ina[u] && g == 0) ? 1u : 0u;
       }
 #pragma unroll
@@ -279,10 +263,8 @@ __global__ __launch_bounds__(256) void k_surrogate_eval_domain_strict(const Sten
   for (int v = 0; v < 4; v++) dom_zero(acc[v]);
   long long nact = 0, nout0 = 0, nout1 = 0;
   for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < n; c += (long long)gridDim.x * 256) {
-    const long long k = c / ncol;
-    const long long ca = (k + 1 < nz) ? c + ncol : c;                     // level min(nz - 1, k + 1), same column
-    double in[9] = {F.in[0][c], F.in[1][c], F.in[2][c], F.in[3][c], F.in[4][c], 0.0, 0.0, 0.0, 0.0};
-    if (NIN == 9) { in[5] = F.in[0][ca]; in[6] = F.in[2][ca]; in[7] = F.in[3][ca]; in[8] = F.in[4][ca]; }
+    const StrictIn I = strict_cell_inputs<NIN>(F.in, c, nz, ncol);
+    const double *in = I.v;
     const double before[4] = {in[0], in[2], in[3], in[4]};
     const double tr[4] = {F.truth[0][c], F.truth[1][c], F.truth[2][c], F.truth[3][c]};
     bool act = false, outside = false;
@@ -305,23 +287,13 @@ __global__ __launch_bounds__(256) void k_surrogate_eval_domain_strict(const Sten
     nout1 += (outside && act) ? 1 : 0;
   }
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int r = 0; r < DOM_ROW; r++) {
-    const double q = eval_lane_tree<64>(acc[(r >> 2) & 3].s[r >> 4][r & 3], (r & 3) == 3);
-    if (lane == 0) red[wv][r] = q;
-  }
+  eval_strict_trees<DOM_ROW>(acc, red);
   for (int off = 32; off > 0; off >>= 1) {
     nact += __shfl_xor(nact, off, 64); nout0 += __shfl_xor(nout0, off, 64); nout1 += __shfl_xor(nout1, off, 64);
   }
   if (lane == 0) { wcount[wv][0] = nact; wcount[wv][1] = nout0; wcount[wv][2] = nout1; }
   __syncthreads();
-  if (threadIdx.x < DOM_ROW) {
-    const int r = threadIdx.x;
-    double q = red[0][r];
-#pragma unroll
-    for (int w = 1; w < 4; w++) q = (r & 3) == 3 ? eval_max(q, red[w][r]) : q + red[w][r];
-    partial[(((long long)blockIdx.x * models + m) * 2 + kind) * DOM_ROW + r] = q;
-  }
+  eval_strict_row_store<DOM_ROW>(red, partial + (((long long)blockIdx.x * models + m) * 2 + kind) * DOM_ROW);
   if (kind == 1 && threadIdx.x < 3) {
     const int e = threadIdx.x;
     const long long q = wcount[0][e] + wcount[1][e] + wcount[2][e] + wcount[3][e];
@@ -337,14 +309,7 @@ __global__ __launch_bounds__(256) void k_surrogate_eval_domain_final(int nblocks
                                                                      const long long *__restrict__ cpartial, double *__restrict__ out,
                                                                      long long *__restrict__ counts) {
   const int e = blockIdx.x * 256 + threadIdx.x, len = models * 2 * DOM_ROW;
-  if (e < len) {
-    double q = 0.0;
-    for (int b = 0; b < nblocks; b++) {
-      const double o = partial[(long long)b * len + e];
-      q = (e & 3) == 3 ? eval_max(q, o) : q + o;
-    }
-    out[e] = q;
-  }
+  eval_final_store(nblocks, len, e, partial, out);
   if (e < models * 2) {
     const int m = e >> 1, c = e & 1, w = 1 + 2 * models;
     long long a = 0, o = 0;
@@ -383,47 +348,33 @@ extern "C" int mw_surrogate_eval_domain_group(mw_surrogate_bank_t b) {
 
 extern "C" int mw_surrogate_eval_domain(mw_surrogate_bank_t b, int nz, long long ncol, const double *const *in5, const double *const *truth4,
                                         double *out, long long *counts, void *stream) {
-  if (!b || !in5 || !truth4 || !out || !counts) MW_FAIL("surrogate_eval_domain: null pointer");
-  if (nz < 1 || ncol < 1) MW_FAIL("surrogate_eval_domain: nz and ncol must be >= 1");
   EvalFields F;
-  for (int i = 0; i < 5; i++) { if (!in5[i]) MW_FAIL("surrogate_eval_domain: null field"); F.in[i] = in5[i]; }
-  for (int i = 0; i < 4; i++) { if (!truth4[i]) MW_FAIL("surrogate_eval_domain: null field"); F.truth[i] = truth4[i]; }
-  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");      // (a handle exists only with a device)
+  if (eval_fields("surrogate_eval_domain", F, b, nz, ncol, in5, truth4, out, counts)) return 1;
   if (!b->dom_box) MW_FAIL("surrogate_eval_domain: the bank has no boxes (mw_surrogate_bank_set_domain comes first)");
   hipStream_t st = (hipStream_t)stream;
   const long long ncells = (long long)nz * ncol;
   const int models = b->models;
-  // mw_surrogate_eval's grid.x: from the shape alone
-  constexpr int TILES = 4, U = 4;
-  const int zc = mw_mlp_stencil_chunk(nz, ncol), nchunks = (nz + zc - 1) / zc;
-  long long blocks;
-  if (mlp_strict()) blocks = (ncells + 255) / 256;
-  else if (b->n_in == 5) blocks = (((ncells + 15) / 16 + TILES - 1) / TILES + 3) / 4;
-  else blocks = (((ncol + 15) / 16) * nchunks + 3) / 4;
-  blocks = std::max<long long>(1, std::min<long long>(blocks, EVAL_MAX_BLOCKS));
-  if (blocks > b->dom_partial_blocks) {
-    (void)hipFree(b->dom_partial); b->dom_partial = nullptr; b->dom_partial_blocks = 0;
-    MW_HIP(hipMalloc(&b->dom_partial, sizeof(double) * (size_t)blocks * models * 2 * DOM_ROW));
-    b->dom_partial_blocks = blocks;
-  }
+  constexpr int TILES = EVAL_TILES, U = EVAL_U;
+  const auto [blocks, zc, nchunks] = eval_grid(b->n_in, nz, ncol);        // mw_surrogate_eval's grid.x
+  if (eval_grow(b->dom_partial, b->dom_partial_blocks, blocks, (size_t)models * 2 * DOM_ROW)) return 1;
   const double *box = b->dom_box;
   if (mlp_strict()) {
     const dim3 grid((unsigned)blocks, (unsigned)(2 * models));
-    if (b->n_in == 5) MW_LAUNCH_ANYT(b->any_tendency, (k_surrogate_eval_domain_strict<5, true>), (k_surrogate_eval_domain_strict<5, false>), grid, dim3(256), 0, st, b->refs, box, models, nz, ncol, F, b->dom_partial, b->dom_cpartial);
-    else              MW_LAUNCH_ANYT(b->any_tendency, (k_surrogate_eval_domain_strict<9, true>), (k_surrogate_eval_domain_strict<9, false>), grid, dim3(256), 0, st, b->refs, box, models, nz, ncol, F, b->dom_partial, b->dom_cpartial);
+    if (b->n_in == 5) MW_LAUNCH_IF(b->any_tendency, (k_surrogate_eval_domain_strict<5, true>), (k_surrogate_eval_domain_strict<5, false>), grid, dim3(256), 0, st, b->refs, box, models, nz, ncol, F, b->dom_partial, b->dom_cpartial);
+    else              MW_LAUNCH_IF(b->any_tendency, (k_surrogate_eval_domain_strict<9, true>), (k_surrogate_eval_domain_strict<9, false>), grid, dim3(256), 0, st, b->refs, box, models, nz, ncol, F, b->dom_partial, b->dom_cpartial);
     MW_LAUNCH_CHECK();
   } else {
     const int G = b->n_in == 5 ? DOM_G5 : DOM_G9;
     const int GP = b->n_in == 5 ? DOM_GP5 : DOM_GP9;
     const dim3 grid((unsigned)blocks, (unsigned)((models + G - 1) / G)), gridp((unsigned)blocks, (unsigned)((models + GP - 1) / GP));
     if (b->n_in == 5) {
-      MW_LAUNCH_ANYT(b->any_tendency, (k_surrogate_eval_domain<DOM_G5, TILES, true, true>), (k_surrogate_eval_domain<DOM_G5, TILES, false, true>), grid, dim3(256), 0, st, b->images, box, models, ncells, F,
-                     b->dom_partial, b->dom_cpartial);
+      MW_LAUNCH_IF(b->any_tendency, (k_surrogate_eval_domain<DOM_G5, TILES, true, true>), (k_surrogate_eval_domain<DOM_G5, TILES, false, true>), grid, dim3(256), 0, st, b->images, box, models, ncells, F,
+                   b->dom_partial, b->dom_cpartial);
       MW_LAUNCH_CHECK();
       hipLaunchKernelGGL((k_surrogate_eval_domain<DOM_GP5, TILES, false, false>), gridp, dim3(256), 0, st, b->images, box, models, ncells, F, b->dom_partial, b->dom_cpartial);
     } else {
-      MW_LAUNCH_ANYT(b->any_tendency, (k_surrogate_eval_domain_stencil<DOM_G9, U, true, true>), (k_surrogate_eval_domain_stencil<DOM_G9, U, false, true>), grid, dim3(256), 0, st, b->images, box, models, nz, ncol,
-                     zc, nchunks, F, b->dom_partial, b->dom_cpartial);
+      MW_LAUNCH_IF(b->any_tendency, (k_surrogate_eval_domain_stencil<DOM_G9, U, true, true>), (k_surrogate_eval_domain_stencil<DOM_G9, U, false, true>), grid, dim3(256), 0, st, b->images, box, models, nz, ncol,
+                   zc, nchunks, F, b->dom_partial, b->dom_cpartial);
       MW_LAUNCH_CHECK();
       hipLaunchKernelGGL((k_surrogate_eval_domain_stencil<DOM_GP9, U, false, false>), gridp, dim3(256), 0, st, b->images, box, models, nz, ncol, zc, nchunks, F, b->dom_partial,
                          b->dom_cpartial);

@@ -75,19 +75,25 @@ class SurrogateBank:
         except Exception:
             pass
 
+    def _eval_layout(self, who, nz, in5, truth4):
+        """(cells, device) of evaluate's nine fields; refuses, in the caller's name `who`, a wrong number of fields, fields of different
+        sizes or of no whole number of columns, and fields off the bank's device."""
+        if len(in5) != 5 or len(truth4) != 4:
+            endrun(who + "five input fields and four truth fields expected")
+        n = in5[0].numel()
+        if int(nz) < 1 or n % int(nz) != 0 or any(t.numel() != n for t in list(in5) + list(truth4)):
+            endrun(who + "the nine fields must have one size, a whole number of columns of nz = %d levels" % nz)
+        dev = self.device
+        if any(t.device != dev for t in list(in5) + list(truth4)):
+            endrun(who + "the bank lives on %s, the fields on %s" % (dev, sorted({str(t.device) for t in list(in5) + list(truth4)})))
+        return n, dev
+
     def evaluate(self, nz, in5, truth4):
         """in5: the five fields before the microphysics call (temp, density_dry, water_vapor, cloud_liquid, precip_liquid), truth4: the four
         after it (EVAL_FIELDS); fp64 CUDA tensors of nz levels.  Returns (stats, counts): the raw (K + 1, 2, 4, 4) fp64 array
         [model | persistence][inactive, active][field][sum d, sum |d|, sum d^2, max |d|], d = prediction - truth, and the int64 cells per
         class -- one device-to-host copy for both."""
-        if len(in5) != 5 or len(truth4) != 4:
-            endrun("SurrogateBank.evaluate: five input fields and four truth fields expected")
-        n = in5[0].numel()
-        if int(nz) < 1 or n % int(nz) != 0 or any(t.numel() != n for t in list(in5) + list(truth4)):
-            endrun("SurrogateBank.evaluate: the nine fields must have one size, a whole number of columns of nz = %d levels" % nz)
-        dev = self.device
-        if any(t.device != dev for t in list(in5) + list(truth4)):
-            endrun("SurrogateBank.evaluate: the bank lives on %s, the fields on %s" % (dev, sorted({str(t.device) for t in list(in5) + list(truth4)})))
+        n, dev = self._eval_layout("SurrogateBank.evaluate: ", nz, in5, truth4)
         buf = StatsAndCounts((self.models + 1) * 32, 2, dev, self._buf)
         self._buf = buf.buf                                               # (the int64 tensor itself: kept from call to call)
         with strict_mode(self.strict), torch.cuda.device(dev):
@@ -111,14 +117,7 @@ class SurrogateBank:
         """mw_surrogate_eval_domain on evaluate's arguments, after set_domain.  Returns (stats, counts): the raw (K, 2, 2, 2, 4, 4) fp64
         array [model][prediction, persistence][inside, outside][inactive, active][field][sum d, sum |d|, sum d^2, max |d|] and the int64
         cells (K, 2, 2) = [model][side][class] -- one device-to-host copy for both."""
-        if len(in5) != 5 or len(truth4) != 4:
-            endrun("SurrogateBank.evaluate_domain: five input fields and four truth fields expected")
-        n = in5[0].numel()
-        if int(nz) < 1 or n % int(nz) != 0 or any(t.numel() != n for t in list(in5) + list(truth4)):
-            endrun("SurrogateBank.evaluate_domain: the nine fields must have one size, a whole number of columns of nz = %d levels" % nz)
-        dev = self.device
-        if any(t.device != dev for t in list(in5) + list(truth4)):
-            endrun("SurrogateBank.evaluate_domain: the bank lives on %s, the fields on %s" % (dev, sorted({str(t.device) for t in list(in5) + list(truth4)})))
+        n, dev = self._eval_layout("SurrogateBank.evaluate_domain: ", nz, in5, truth4)
         buf = StatsAndCounts(self.models * 128, self.models * 4, dev, self._dbuf)
         self._dbuf = buf.buf
         with strict_mode(self.strict), torch.cuda.device(dev):
