@@ -694,6 +694,30 @@ int  mw_member_column_water(int nz, long long ncol, int nens, const double *cons
 int  mw_member_surface_rain(int nz, long long ncol, int nens, int nm, const int *members, int na, const int *accum,
                             const double *const *water3, double dz, double dt, const double *w_before, double *precl, double *rain_total,
                             void *stream);
+/* The water fixer: mw_member_surface_rain that also acts.  members, accum, w_before, precl, rain_total, dz, dt: as
+ * above.  fixed: HOST array of nfix (0 .. nens) distinct members, every one of them in `members`.  For element t = col * nens + e of a
+ * fixed member, with W_b = w_before[t] and W_a = mw_member_column_water of the state given (same order):
+ *   W_a or W_b not finite, or W_a > W_b with W_b < 0:  SKIPPED -- counted, the state untouched, precl as mw_member_surface_rain's;
+ *   W_b >= 0 and W_a - W_b > tolerance * W_b:           FIXED -- s = W_b / W_a (one fp64 division), every level's water_vapor,
+ *     cloud_liquid and precip_liquid becomes q * s (one fp64 product each, no contraction, ordinary stores), W' is the column water of
+ *     the STORED products in the same order (a later mw_member_column_water returns W' to the bit), precl[t] = (W_b - W') / (1000 dt),
+ *     and the column's excess is W_a - W_b, kg / m^2;
+ *   otherwise exactly mw_member_surface_rain's bits, and nothing of the state is written.
+ * With non-negative fields and no underflow |W' - W_b| <= (nz + 4) * 2^-52 * W_b.  Only the three water fields are written: this is
+ * a mass fixer, no latent heat is exchanged, temp and density_dry are not arguments.  water3: HOST array of 3 DEVICE pointers to three
+ * different arrays.  counts: DEVICE int64 (nens, 2) = fixed columns, skipped columns of every member; stats: DEVICE fp64 (nens, 2) = sum and
+ * maximum of the excess over the member's fixed columns (0 for a member not in `fixed`); both SET.  excess: NULL, or DEVICE fp64
+ * (ncol, nens) that receives every element's excess, +0.0 where nothing was fixed (every member).  Reduction: a block of 256 consecutive
+ * elements folds each member's lanes in ascending order; for each member thread l of 256 folds the blocks l, l + 256, ... in ascending
+ * order, then the 256 results are folded in ascending l -- no atomics, no memset, run-to-run identical.  workspace: DEVICE,
+ * mw_member_water_fix_workspace_bytes(ncol, nens) bytes (0: arguments out of range).  Refused, with nothing launched: what
+ * mw_member_surface_rain refuses, a fixed member outside `members`, a tolerance that is negative or not finite, null workspace, counts
+ * or stats.  Asynchronous on `stream`. */
+long long mw_member_water_fix_workspace_bytes(long long ncol, int nens);
+int  mw_member_water_fix(int nz, long long ncol, int nens, int nm, const int *members, int na, const int *accum, int nfix,
+                         const int *fixed, double tolerance, double *const *water3, double dz, double dt, const double *w_before,
+                         double *precl, double *rain_total, void *workspace, long long *counts, double *stats, double *excess,
+                         void *stream);
 /* The contingency table of nf (1 .. 4) member-fastest DEVICE fp64 fields (ncol, nens) against member 0, the observation.  Field f has
  * nt[f] (1 .. 8) thresholds, finite and strictly ascending: thresholds is a HOST (nf, 8) fp64 array whose row f holds them first (the
  * rest is not read); nt: HOST.  An event is x >= thr.  counts: DEVICE int64 (nf, 8, nens, 5) = hits (member and member 0 both have the

@@ -183,6 +183,9 @@ SYMBOLS = {
     "mw_member_column_water": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_void_p, C.c_void_p]),
     "mw_member_surface_rain": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
                                          C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mw_member_water_fix_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int]),
+    "mw_member_water_fix": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int,
+                                      C.POINTER(C.c_int), C.c_double, C.POINTER(C.c_void_p), C.c_double, C.c_double] + [C.c_void_p] * 8),
     "mw_member_rain_table_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     "mw_member_rain_table": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                        C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -9,7 +9,9 @@
 // mw_member_rain_table are every member's surface rain from its column water budget and its contingency table.
 // mw_member_domain counts the cells of the listed members that lie outside the box their models were trained in, and flags their columns
 // for the guarded committee's Kessler pass.  mw_member_sample_mask_domain is the member sampler with a third class, the
-// cells outside the member's box, and the counts of every class that fix its rate.
+// cells outside the member's box, and the counts of every class that fix its rate.  mw_member_water_fix is
+// mw_member_surface_rain that also acts: a listed member's column that holds more water than before the step is scaled back to what it
+// held, and the step's precl is the budget of the state left behind.
 // =====================================================================================================
 #include "../../include/mw_cdna4.h"
 #include "mw_common.h"
@@ -259,6 +261,136 @@ __global__ __launch_bounds__(256) void k_member_surface_rain(int nz, long long p
   }
   if (sums) rain_total[t] = rain_total[t] + dt * p;
 }
+
+// ---- mw_member_water_fix ------------------------------------------------------------------------------------------------------------
+struct FixFields { double *v, *c, *r; };
+constexpr int FIX_ROW = 4;                 // per block and member: fixed columns, skipped columns (int64 bits), sum of excess, max of excess
+constexpr int FIX_FIXED = 1, FIX_SKIPPED = 2;
+
+// k_member_surface_rain with the remedy.  Thread t is one (column, member) of the plane and first sweeps its column as
+// column_water does.  A member of `fixed` whose column holds more water than before the step (W_a - W_b > tolerance * W_b, W_b >= 0)
+// sweeps it a second time: the twelve loads of WATER_AHEAD levels, each value times s = W_b / W_a, twelve ordinary stores, and the stored
+// products summed in column_water's order, so that column_water of the state left behind is W' to the bit.  The second sweep is behind a
+// ballot: a wavefront with no column to fix does not enter it.  Statistics: every lane's flags and excess go to LDS; a block with nothing
+// fixed or skipped writes rows of zeros, any other folds, for member m and each of the four numbers, the lanes of m in ascending lane
+// order (one thread per number).  k_member_water_fix_final then folds the blocks' rows.  No atomics, no memset, one fixed order.
+__global__ __launch_bounds__(256) void k_member_water_fix(int nz, long long plane, int nens, unsigned long long listed, unsigned long long accum,
+                                                          unsigned long long fixed, double tolerance, FixFields F, double dz, double dt,
+                                                          double per_rate, const double *__restrict__ w_before, double *__restrict__ precl,
+                                                          double *__restrict__ rain_total, double *__restrict__ partial,
+                                                          double *__restrict__ excess) {
+#pragma clang fp contract(off)
+  __shared__ double ex[256];
+  __shared__ int what[256];
+  const int l = threadIdx.x;
+  const long long t = (long long)blockIdx.x * 256 + l;
+  const int e = (int)(t % nens);
+  const bool in = t < plane;
+  const bool mine = in && ((listed >> e) & 1ull), sums = in && ((accum >> e) & 1ull);
+  double wb = 0.0, wa = 0.0, over = 0.0;
+  int flag = 0;
+  if (mine) {
+    const WaterFields R = {F.v, F.c, F.r};
+    wb = w_before[t];
+    wa = column_water(nz, plane, t, R, dz);
+    if ((fixed >> e) & 1ull) {
+      const double d = wa - wb;
+      if (wa - wa != 0.0 || wb - wb != 0.0) flag = FIX_SKIPPED;                // NaN or inf: the budget's own bits show it
+      else if (wa > wb && wb < 0.0) flag = FIX_SKIPPED;                        // no scale of a negative total is a remedy
+      else if (wb >= 0.0 && d > tolerance * wb) { flag = FIX_FIXED; over = d; }
+    }
+  }
+  if (__ballot(flag == FIX_FIXED)) {                                          // wavefront-uniform: only a wavefront with a column to fix sweeps again
+    if (flag == FIX_FIXED) {
+      const double s = wb / wa;
+      double acc = 0.0;
+      int k = 0;
+      for (; k + WATER_AHEAD <= nz; k += WATER_AHEAD) {
+        double v[WATER_AHEAD], c[WATER_AHEAD], r[WATER_AHEAD];
+#pragma unroll
+        for (int j = 0; j < WATER_AHEAD; j++) {
+          const long long i = (long long)(k + j) * plane + t;
+          v[j] = F.v[i]; c[j] = F.c[i]; r[j] = F.r[i];
+        }
+#pragma unroll
+        for (int j = 0; j < WATER_AHEAD; j++) {
+          const long long i = (long long)(k + j) * plane + t;
+          v[j] = v[j] * s; c[j] = c[j] * s; r[j] = r[j] * s;
+          F.v[i] = v[j]; F.c[i] = c[j]; F.r[i] = r[j];
+          acc = acc + ((v[j] + c[j]) + r[j]);
+        }
+      }
+      for (; k < nz; k++) {
+        const long long i = (long long)k * plane + t;
+        const double v = F.v[i] * s, c = F.c[i] * s, r = F.r[i] * s;
+        F.v[i] = v; F.c[i] = c; F.r[i] = r;
+        acc = acc + ((v + c) + r);
+      }
+      wa = dz * acc;                                                           // W': what column_water now returns for this column
+    }
+  }
+  if (mine || sums) {
+    double p;
+    if (mine) {
+      p = (wb - wa) / per_rate;
+      precl[t] = p;
+    } else {
+      p = precl[t];
+    }
+    if (sums) rain_total[t] = rain_total[t] + dt * p;
+  }
+  if (excess && in) excess[t] = over;
+  ex[l] = over;
+  what[l] = flag;
+  if (!__syncthreads_or(flag)) {                                               // nothing fixed or skipped in this block: what the fold below would give
+    if (l < nens * FIX_ROW) partial[(long long)blockIdx.x * nens * FIX_ROW + l] = 0.0;     // (+0.0 is the int64 0 too)
+    return;
+  }
+  if (l < nens * FIX_ROW) {
+    const int m = l / FIX_ROW, s = l % FIX_ROW;
+    const int first = (int)(((long long)m - (long long)(((long long)blockIdx.x * 256) % nens) + nens) % nens);      // the block's first lane of member m
+    double *row = partial + ((long long)blockIdx.x * nens + m) * FIX_ROW;
+    if (s < 2) {
+      long long q = 0;
+      for (int j = first; j < 256; j += nens) q += (what[j] == s + 1) ? 1 : 0;
+      ((long long *)row)[s] = q;
+    } else {
+      double q = 0.0;
+      for (int j = first; j < 256; j += nens) q = (s == 2) ? q + ex[j] : (ex[j] > q ? ex[j] : q);
+      row[s] = q;
+    }
+  }
+}
+
+// block m = member m; thread l folds the rows of the blocks l, l + 256, ... in ascending order, then threads 0 .. 3 fold the 256 partial
+// results of one number each in ascending l.  counts (nens, 2) = fixed, skipped; stats (nens, 2) = sum, max of the excess.
+__global__ __launch_bounds__(256) void k_member_water_fix_final(long long nblocks, int nens, const double *__restrict__ partial,
+                                                                long long *__restrict__ counts, double *__restrict__ stats) {
+#pragma clang fp contract(off)
+  __shared__ double red[256][2];
+  __shared__ long long cnt[256][2];
+  const int m = blockIdx.x, l = threadIdx.x;
+  long long nf = 0, ns = 0;
+  double sum = 0.0, mx = 0.0;
+  for (long long b = l; b < nblocks; b += 256) {
+    const double *row = partial + (b * nens + m) * FIX_ROW;
+    nf += ((const long long *)row)[0]; ns += ((const long long *)row)[1];
+    sum = sum + row[2]; mx = row[3] > mx ? row[3] : mx;
+  }
+  cnt[l][0] = nf; cnt[l][1] = ns; red[l][0] = sum; red[l][1] = mx;
+  __syncthreads();
+  if (l < 2) {
+    long long q = 0;
+    for (int j = 0; j < 256; j++) q += cnt[j][l];
+    counts[m * 2 + l] = q;
+  } else if (l < 4) {
+    double q = red[0][l - 2];
+    for (int j = 1; j < 256; j++) q = (l == 2) ? q + red[j][0] : (red[j][1] > q ? red[j][1] : q);
+    stats[m * 2 + (l - 2)] = q;
+  }
+}
+
+static long long water_fix_blocks(long long ncol, int nens) { return (ncol * nens + 255) / 256; }
 
 // ---- mw_member_rain_table -----------------------------------------------------------------------------------------------------------
 constexpr int RAIN_MAX_FIELDS = 4, RAIN_MAX_THR = 8;
@@ -751,6 +883,40 @@ extern "C" int mw_member_surface_rain(int nz, long long ncol, int nens, int nm, 
   const long long plane = ncol * nens;
   hipLaunchKernelGGL(k_member_surface_rain, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nz, plane, nens, listed, sums, F,
                      dz, dt, 1000.0 * dt, w_before, precl, rain_total);
+  MW_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" long long mw_member_water_fix_workspace_bytes(long long ncol, int nens) {
+  if (ncol < 1 || nens < 1 || nens > 64 || (double)ncol * (double)nens > 256.0 * 2147483647.0) return 0;
+  return water_fix_blocks(ncol, nens) * nens * FIX_ROW * 8;
+}
+
+extern "C" int mw_member_water_fix(int nz, long long ncol, int nens, int nm, const int *members, int na, const int *accum, int nfix,
+                                   const int *fixed, double tolerance, double *const *water3, double dz, double dt, const double *w_before,
+                                   double *precl, double *rain_total, void *workspace, long long *counts, double *stats, double *excess,
+                                   void *stream) {
+  WaterFields R;
+  if (water_fields("member_water_fix", nz, ncol, nens, water3, dz, &R)) return 1;
+  if (!positive_finite(dt)) MW_FAIL("member_water_fix: dt must be positive and finite");
+  if (!(tolerance >= 0.0 && tolerance - tolerance == 0.0)) MW_FAIL("member_water_fix: tolerance must be finite and >= 0");
+  unsigned long long listed = 0, sums = 0, fix = 0;
+  if (member_bits("member_water_fix", "members", nens, nm, members, &listed)) return 1;
+  if (member_bits("member_water_fix", "accum", nens, na, accum, &sums)) return 1;
+  if (member_bits("member_water_fix", "fixed", nens, nfix, fixed, &fix)) return 1;
+  for (int e = 0; e < nens; e++)
+    if (((fix & ~listed) >> e) & 1ull) MW_FAIL("member_water_fix: member " + std::to_string(e) + " is in fixed but not in members (a fixed member is a budget member)");
+  if (!precl || (nm > 0 && !w_before) || (na > 0 && !rain_total) || !workspace || !counts || !stats) MW_FAIL("member_water_fix: null pointer");
+  if (water3[0] == water3[1] || water3[0] == water3[2] || water3[1] == water3[2]) MW_FAIL("member_water_fix: the three water fields must be three arrays");
+  if ((double)ncol * (double)nens > 256.0 * 2147483647.0) MW_FAIL("member_water_fix: the fields are too large");
+  if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
+  const FixFields F = {water3[0], water3[1], water3[2]};
+  hipStream_t st = (hipStream_t)stream;
+  const long long plane = ncol * nens, blocks = water_fix_blocks(ncol, nens);
+  hipLaunchKernelGGL(k_member_water_fix, dim3((unsigned)blocks), dim3(256), 0, st, nz, plane, nens, listed, sums, fix, tolerance, F, dz, dt,
+                     1000.0 * dt, w_before, precl, rain_total, (double *)workspace, excess);
+  MW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_member_water_fix_final, dim3((unsigned)nens), dim3(256), 0, st, blocks, nens, (const double *)workspace, counts, stats);
   MW_LAUNCH_CHECK();
   return 0;
 }

@@ -84,6 +84,16 @@ makes evaluate_surrogates split every model's one-step errors by whether the cel
 a continued model and its parent are scored on the same partition.  surrogate_evaluation.json gains a `domain` block (margin, fields,
 box_of, group, per model its box and report, and the per-call history) and a second table is printed; false or absent: no further call
 is made and the document is what it is without the key.
+    water_fixer: true                         # or {members: [tend0, mean3], tolerance: 0.0}
+makes the listed members of rollout_surrogates (default: every model and committee member; never kessler or persistence) give back the
+water their model made: a column that holds more water after the microphysics step than before it, by more than
+tolerance times what it held, has its three water fields scaled back to what it held.  temp is not touched: a mass fixer, no latent
+heat.  The fixed members become budget members (their precl is the water budget of the state left behind) and rain_total exists with
+or without surface_rain.  surrogate_rollout.json gets a `water_fixer` block: tolerance, members, columns, per scoring step and member
+columns_fixed, columns_skipped and water_removed_kg_m2 {mean over the columns, max}, and the totals over the scoring steps.  Listing
+one set of weights under two names and fixing one of them shows the fixer's effect in one run.  inference_ponni reads the key (without
+`members`) and then runs its network online with the fixer on every column.  false or absent: the document and the run are what they are
+without the key.
 """
 import argparse
 import json
@@ -124,7 +134,7 @@ def load_config(path):
         if key in cfg:
             out[key] = str(cfg[key])
     out["_dir"] = os.path.dirname(os.path.abspath(path))
-    for key in ("surrogate_models", "eval_interval", "persistence_member", "harvest", "surrogate_committees", "surface_rain", "training_domain", "eval_domain"):    # read by surrogate_config / rollout_config / harvest_config / committee_config / surface_rain_config / training_domain_config / eval_domain_key alone
+    for key in ("surrogate_models", "eval_interval", "persistence_member", "harvest", "surrogate_committees", "surface_rain", "training_domain", "eval_domain", "water_fixer"):    # read by surrogate_config / rollout_config / harvest_config / committee_config / surface_rain_config / training_domain_config / eval_domain_key / water_fixer_config alone
         if key in cfg:
             out[key] = cfg[key]
     return out
@@ -330,6 +340,39 @@ def surface_rain_config(cfg):
     out["map"] = b.get("map", True)
     if not isinstance(out["map"], bool):
         raise ValueError("ERROR: surface_rain.map must be true or false")
+    return out
+
+
+WATER_FIXER_KEYS = ("members", "tolerance")
+
+
+def water_fixer_config(cfg, member_names=None):
+    """The checked `water_fixer:` key of a loaded configuration for rollout_surrogates (and, without `members`, inference_ponni), or None
+    when it is absent or false: true (every network-stepped member, tolerance 0) or {members: [names], tolerance: t}.  members: a non-empty
+    list of distinct names, never kessler or persistence -- and, when member_names (the names a network steps) is given, each one of them;
+    absent: all of them (None in the result).  tolerance: a finite number >= 0 (default 0): a column is fixed when its water grew by more
+    than tolerance times what it held."""
+    b = cfg.get("water_fixer", False)
+    if b is False or b is None:
+        return None
+    b = {} if b is True else b
+    if not isinstance(b, dict):
+        raise ValueError("ERROR: water_fixer must be true, false or a mapping")
+    unknown = sorted(set(b) - set(WATER_FIXER_KEYS), key=str)
+    if unknown:
+        raise ValueError("ERROR: unknown key(s) %s in water_fixer (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(WATER_FIXER_KEYS)))
+    out = {"members": None, "tolerance": microphysics.water_fix_tolerance(b.get("tolerance", 0.0), "water_fixer.tolerance")}
+    if b.get("members") is not None:
+        names = b["members"]
+        if not isinstance(names, list) or not names or not all(isinstance(n, str) for n in names) or len(set(names)) != len(names):
+            raise ValueError("ERROR: water_fixer.members must be a non-empty list of distinct member names")
+        for n in names:
+            if n in ("kessler", "persistence"):
+                raise ValueError("ERROR: water_fixer.members names %r: only a member that a network steps can be fixed" % n)
+            if member_names is not None and n not in member_names:
+                raise ValueError("ERROR: water_fixer.members names %r, which is no model or committee of this run (%s)"
+                                 % (n, ", ".join(member_names)))
+        out["members"] = list(names)
     return out
 
 
@@ -551,6 +594,7 @@ class CommunityBenchmark(Column):
 
 class InferencePonni(Column):
     committee = None                                                           # the one committee that runs in place of a single network
+    fixer_cfg = None                                                           # the checked `water_fixer` key (without members)
 
     def configure(self, cfg, nranks):
         if "surrogate_committees" in cfg and not ("keras_weights_h5" in cfg or "keras_weights_txt" in cfg):
@@ -559,6 +603,9 @@ class InferencePonni(Column):
                 raise ValueError("ERROR: inference_ponni runs one committee, surrogate_committees lists %d" % len(committees))
             cfg["surrogate_models"], _ = surrogate_config(cfg)
             self.committee = committees[0]
+        self.fixer_cfg = water_fixer_config(cfg)
+        if self.fixer_cfg is not None and self.fixer_cfg["members"] is not None:
+            raise ValueError("ERROR: inference_ponni's water_fixer takes no members: the one network steps every column")
 
     def make_micro(self):
         cfg, coupler, info = self.cfg, self.coupler, self.info
@@ -581,6 +628,8 @@ class InferencePonni(Column):
         info["surrogate_form"] = micro.form if self.committee is None else micro._committee.forms
         if "tendency" in info["surrogate_form"] and not self.quiet and coupler.is_mainproc():     # (a state model prints what it always did)
             print("inference_ponni: surrogate output form: %s" % info["surrogate_form"], flush=True)
+        if self.fixer_cfg is not None:                                         # the fixer acts on the state the network leaves: online
+            micro.online, micro.water_fixer = True, {"tolerance": self.fixer_cfg["tolerance"]}
         return micro
 
     def micro_step(self, dt, etime):
@@ -695,9 +744,10 @@ class EvaluateSurrogates(Column):
 
 
 def rollout_document(experiment, yaml_path, eval_interval, steps, models, scorer, rep, micro, committees=(), domain_blocks=None,
-                     harvest=None, rain_cfg=None, rain=None):
+                     harvest=None, rain_cfg=None, rain=None, water_fixer=None):
     """surrogate_rollout.json as a dict.  rep: the scorer's report; domain_blocks: micro.domain_reports() with `training_domain`;
-    harvest: harvest_block's result with a harvester; rain_cfg, rain: the checked `surface_rain` and its RainScorer.  None: no such block."""
+    harvest: harvest_block's result with a harvester; rain_cfg, rain: the checked `surface_rain` and its RainScorer; water_fixer:
+    micro.water_fix_reports() with `water_fixer`.  None: no such block."""
     doc = {"experiment": experiment, "yaml": os.path.abspath(yaml_path), "eval_interval": eval_interval, "steps": steps,
            "members": list(scorer.member_names), "models": [dict(m, member=1 + k, form=micro.model_forms[k]) for k, m in enumerate(models)],
            "fields": list(scorer.fields), "statistics": list(rollout.ROLLOUT_STATS), "history": scorer.history,
@@ -714,10 +764,14 @@ def rollout_document(experiment, yaml_path, eval_interval, steps, models, scorer
         doc["harvest"] = harvest
     if rain is not None:
         doc["surface_rain"] = dict(rain_cfg, report=rain.times)
+    if water_fixer is not None:
+        doc["water_fixer"] = water_fixer
     return doc
 
 
 class RolloutSurrogates(Column):
+    fixer_cfg = None                                                           # the checked `water_fixer` key
+
     def configure(self, cfg, nranks):
         _one_rank("rollout_surrogates", nranks)
         self.harvest = harvest_config(cfg)
@@ -725,6 +779,7 @@ class RolloutSurrogates(Column):
         self.domain_cfg = training_domain_config(cfg)
         self.committees = committee_config(cfg)
         cfg["surrogate_models"], cfg["eval_interval"], cfg["persistence_member"], cfg["nens"] = rollout_config(cfg)
+        self.fixer_cfg = water_fixer_config(cfg, [m["name"] for m in cfg["surrogate_models"]] + [c["name"] for c in self.committees])
 
     def make_micro(self):
         models = self.cfg["surrogate_models"]
@@ -746,6 +801,8 @@ class RolloutSurrogates(Column):
             self.rain = rollout.RainScorer(micro.member_names, self.rain_cfg["thresholds_mm_h"], self.rain_cfg["thresholds_mm"])
         if self.domain_cfg is not None:
             micro.training_domain = self.domain_cfg
+        if self.fixer_cfg is not None:                                         # (members None: every model and committee member)
+            micro.water_fixer = {k: v for k, v in self.fixer_cfg.items() if v is not None}
         self.harvester = None
         if harvest is not None:
             self.harvester = micro.harvester = rollout.RolloutHarvester()
@@ -773,6 +830,8 @@ class RolloutSurrogates(Column):
         scorer.accumulate(self.coupler, step, etime + dt)
         micro.guard_record(step, dt)                                           # (the only host read of the guards' counts)
         micro.domain_record(step)                                              # (and of the training-domain report's)
+        if self.fixer_cfg is not None:
+            micro.water_fix_record(step)                                       # (and of the water fixer's statistics)
         if self.rain is not None:
             self.rain.accumulate(self.coupler, micro, step, etime + dt)
         for m, d in scorer.diverged_at.items():                                # the other members do not see it: the run goes on
@@ -785,11 +844,14 @@ class RolloutSurrogates(Column):
         blocks = micro.domain_reports() if self.domain_cfg is not None else None
         doc = rollout_document(info["experiment"], yaml_path, self.cfg["eval_interval"], steps, self.cfg["surrogate_models"], scorer, rep, micro,
                                self.committees, domain_blocks=blocks, rain_cfg=self.rain_cfg, rain=rain,
+                               water_fixer=micro.water_fix_reports() if self.fixer_cfg is not None else None,
                                harvest=harvest_block(self.harvest, self.harvester) if self.harvester is not None else None)
         if blocks is not None:
             info["domain_reports"] = {scorer.member_names[m]: b for m, b in enumerate(blocks) if b is not None}
         if self.harvester is not None:
             info["harvest"] = doc["harvest"]
+        if self.fixer_cfg is not None:
+            info["water_fixer_report"], info["rain_total"] = doc["water_fixer"], micro.rain_total
         if rain is not None:
             info["surface_rain_report"], info["rain_total"] = rain.times, micro.rain_total
             if self.rain_cfg["map"] and micro.rain_total is not None:          # (nens, ny, nx) fp64, mm since the start of the run

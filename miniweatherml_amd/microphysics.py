@@ -5,11 +5,12 @@
 
 No arithmetic happens in Python: everything runs in libmw_cdna4.so on the GPU (no fallback)."""
 import ctypes as C
+import types
 
 import torch
 
 from . import capi
-from ._ffi import _field_ptr_array, _ptr, _stream_ptr, grown_workspace
+from ._ffi import StatsAndCounts, _field_ptr_array, _ptr, _stream_ptr, grown_workspace
 from .capi import check
 from .coupler import endrun
 from .mlp import OUT4, as_surrogate_model, load_surrogate_model, mlp_forward, mlp_stencil_forward
@@ -37,6 +38,42 @@ def surface_rain_finish(water3, nz, ncol, nens, members, accum, dz, dt, w_before
                                                 (C.c_int * max(1, len(accum)))(*accum), _field_ptr_array(water3), float(dz), float(dt),
                                                 _ptr(w_before) if w_before is not None else None, _ptr(precl),
                                                 _ptr(rain_total) if rain_total is not None else None, _stream_ptr(dev)))
+
+
+def water_fix_finish(water3, nz, ncol, nens, members, accum, fixed, tolerance, dz, dt, w_before, precl, rain_total=None, holder=None,
+                     excess=None):
+    """mw_member_water_fix: surface_rain_finish that also acts.  A column of a member in `fixed` (a subset of `members`)
+    that holds more water than w_before, by more than tolerance * w_before, has its three water fields scaled back to w_before; its precl
+    is the budget of the state left behind.  Every other element gets surface_rain_finish's bits.  Returns the StatsAndCounts of the
+    call, on the device: 2 * nens doubles (sum and maximum of the excess per member, kg / m^2) and 2 * nens counts (fixed and skipped
+    columns per member).  holder: the object that keeps the workspace and that buffer between calls; excess: an (ncol * nens) tensor."""
+    dev = water3[0].device
+    members, accum, fixed = [int(m) for m in members], [int(m) for m in accum], [int(m) for m in fixed]
+    L = capi.lib()
+    nbytes = L.mw_member_water_fix_workspace_bytes(ncol, nens)
+    if nbytes <= 0:
+        endrun("water_fix_finish: %d columns x %d members are out of range (at most 64 members)" % (ncol, nens))
+    holder = holder if holder is not None else types.SimpleNamespace()
+    ws = grown_workspace(holder, "_ws_water_fix", nbytes, dev)
+    held = getattr(holder, "_water_fix_out", None)
+    out = StatsAndCounts(2 * nens, 2 * nens, dev, held.buf if held is not None and held.buf.numel() == 4 * nens and held.buf.device == ws.device
+                         else None)
+    holder._water_fix_out = out
+    ints = lambda v: (C.c_int * max(1, len(v)))(*v)                            # noqa: E731
+    with torch.cuda.device(dev):
+        check(L.mw_member_water_fix(nz, ncol, nens, len(members), ints(members), len(accum), ints(accum), len(fixed), ints(fixed),
+                                    float(tolerance), _field_ptr_array(water3), float(dz), float(dt),
+                                    _ptr(w_before) if w_before is not None else None, _ptr(precl),
+                                    _ptr(rain_total) if rain_total is not None else None, _ptr(ws), out.counts_ptr, out.stats_ptr,
+                                    _ptr(excess) if excess is not None else None, _stream_ptr(dev)))
+    return out
+
+
+def water_fix_tolerance(value, what):
+    """A checked tolerance of a water fixer: a finite number >= 0 (ValueError)."""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (value >= 0.0 and value - value == 0.0):
+        raise ValueError("ERROR: %s must be a finite number >= 0, not %r" % (what, value))
+    return float(value)
 
 
 class Microphysics_Kessler:
@@ -104,6 +141,8 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
     want_range = False    # with a committee: time_step also fills last_range, the four fields of the members' spread
     last_range = None
     surface_rain = False  # True (with online only): precl after the step is the column water budget of the state left in the coupler
+    water_fixer = None    # True or {tolerance} (with online only): a column that gained water in the step is scaled back
+    last_water_fix = None  # with water_fixer: the StatsAndCounts of the last step, on the device (water_fix_stats fetches it)
 
     def init(self, coupler, weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None, committee=None, guard=None,
              domains=None):
@@ -177,8 +216,11 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
         return self._finish_step(coupler, dt, temp, rho_v, rho_c, rho_r)
 
     def _finish_step(self, coupler, dt, temp, rho_v, rho_c, rho_r):
-        budget = bool(self.surface_rain)
+        fixer = self._water_fixer_tolerance()
+        budget = bool(self.surface_rain) or fixer is not None
         if budget:
+            if fixer is not None and not self.online:
+                endrun("Microphysics_Kessler_Surrogate: water_fixer needs online = True (offline the state is Kessler's, which makes no water)")
             if not self.online:
                 endrun("Microphysics_Kessler_Surrogate: surface_rain needs online = True (offline the state is Kessler's, and so is precl)")
             # every member is one more column: the whole (ny * nx * nens) plane is one member's columns (the network's result is still
@@ -194,8 +236,35 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
                 dst.copy_(src)
         if budget:                                                             # Kessler's precl gives way to the budget of the state that stays
             precl = coupler.get_data_manager_readwrite().get("precl")
-            surface_rain_finish([rho_v, rho_c, rho_r], nz, ncol, 1, [0], [], coupler.get_dz(), dt, self._w_before, precl)
+            if fixer is None:
+                surface_rain_finish([rho_v, rho_c, rho_r], nz, ncol, 1, [0], [], coupler.get_dz(), dt, self._w_before, precl)
+            else:                                                              # ... and a column that gained water gives it back
+                self.last_water_fix = water_fix_finish([rho_v, rho_c, rho_r], nz, ncol, 1, [0], [], [0], fixer, coupler.get_dz(), dt,
+                                                       self._w_before, precl, holder=self)
         return self._nn_out            # (temp_tmp, rho_v_tmp, rho_c_tmp, rho_r_tmp)
+
+    def _water_fixer_tolerance(self):
+        """None without `water_fixer`; else its checked tolerance."""
+        wf = self.water_fixer
+        if wf is None or wf is False:
+            return None
+        if wf is True:
+            return 0.0
+        if not hasattr(wf, "keys") or set(wf.keys()) - {"tolerance"}:
+            endrun("Microphysics_Kessler_Surrogate: water_fixer is None, True or a mapping whose only key is tolerance")
+        try:
+            return water_fix_tolerance(wf.get("tolerance", 0.0), "water_fixer.tolerance")
+        except ValueError as err:
+            endrun("Microphysics_Kessler_Surrogate: " + str(err))
+
+    def water_fix_stats(self):
+        """The last step's fixer statistics of the whole plane, fetched from the device: columns_fixed, columns_skipped,
+        water_removed_kg_m2 {sum, max}; None before the first step with `water_fixer`."""
+        if self.last_water_fix is None:
+            return None
+        stats, counts = self.last_water_fix.host()
+        return {"columns_fixed": int(counts[0]), "columns_skipped": int(counts[1]),
+                "water_removed_kg_m2": {"sum": float(stats[0]), "max": float(stats[1])}}
 
     def mean_diffs(self, coupler):
         """The four 'Relative diff' prints (:266-269): mean(NN - Kessler)."""

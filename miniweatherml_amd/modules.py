@@ -21,6 +21,8 @@ from .rollout import (RAIN_COUNTS, RAIN_FIELDS, ROLLOUT_FIELDS, ROLLOUT_IN5, ROL
                       RolloutHarvester, RolloutScorer, fields_divergence, kessler_members_teacher, member_column_water, member_divergence,
                       member_rain_table, member_surface_rain, rain_report, rain_scores, rain_thresholds, rollout_member_names, rollout_report)
 from .rollout import box_json, domain_report  # noqa: F401
+from .rollout import member_water_fix, water_fix_report  # noqa: F401
+from .microphysics import water_fix_finish  # noqa: F401
 from .rollout import SAMPLE_CLASSES, harvest_outside_report, harvest_thresholds, member_sample_mask_domain  # noqa: F401
 from .mlp import load_training_domain, load_training_domains  # noqa: F401
 from .sampling import DataGenerator, StatisticsGatherer  # noqa: F401

@@ -7,6 +7,7 @@ experiments/supercell_kessler_surrogate/custom_modules/generate_micro_surrogate_
   member_divergence, rollout_report, RolloutScorer    mw_member_divergence and its reports
   member_column_water, member_surface_rain            every member's surface rain from its column water budget
   member_rain_table, rain_report, RainScorer          its contingency table against the Kessler member and the reports
+  member_water_fix, water_fix_report                  the water fixer: a member gives back the water its model made
   domain_report                                       a member's cells outside its model's training box, per scoring step"""
 import ctypes as C
 import os
@@ -18,7 +19,7 @@ from . import capi
 from ._ffi import StatsAndCounts, _field_ptr_array, _ptr, _stream_ptr, grown_workspace
 from .capi import check
 from .coupler import endrun
-from .microphysics import Microphysics_Kessler, column_water, surface_rain_finish
+from .microphysics import Microphysics_Kessler, column_water, surface_rain_finish, water_fix_finish, water_fix_tolerance
 from .mlp import IN5, OUT4, as_surrogate_model
 from .ncio import sample_file_append, sample_file_create
 from .sampling import sample_buffers, sample_thresholds
@@ -61,6 +62,11 @@ class Microphysics_Rollout(Microphysics_Kessler):
     metres, accumulates dt * precl of every member -- Kessler's own precl for member 0.  The mapping may hold `budget_members`, the
     members' names (default: every member but kessler; with kessler in it the budget overwrites Kessler's own precl of member 0, which
     is the closure check of DESIGN.md 13.8).  The step itself is the same either way: the budget only reads the state.
+    With `water_fixer` set to a mapping ({members: names, tolerance: 0.0}; members default: every model and committee member; kessler and
+    persistence are refused) the step ends with mw_member_water_fix in place of mw_member_surface_rain: a fixed member's column that holds
+    more water than before the step is scaled back to what it held (the three water fields only: a mass fixer, no latent heat), the fixed
+    members are budget members beside surface_rain's, and rain_total exists with or without surface_rain.  Every other member keeps the
+    bits it has without the option.  water_fix_record / water_fix_reports keep the per-step statistics.
     With a `harvester` (RolloutHarvester) and `harvest_now` set, the step harvests Kessler labels on the model members' own states
     between the Kessler member's step and the models'; harvesting reads the state and never writes it.
     With `training_domain` (surrogate_eval.domain_config's mapping, or True) and `domain_now` set, the step counts, for every model member
@@ -77,6 +83,11 @@ class Microphysics_Rollout(Microphysics_Kessler):
     surface_rain = None   # a mapping (may be empty; key budget_members): precl of the budget members and rain_total from the water budget
     _w_before = None
     rain_total = None     # with surface_rain: (ny, nx, nens) fp64, metres of water since the first step with the option
+    water_fixer = None    # a mapping (keys members, tolerance): a fixed member's column that gained water is scaled back
+    _water_fix = None     # with water_fixer: the StatsAndCounts of the last step, on the device
+    _water_fix_fresh = False
+    _water_fix_for = None
+    _water_fix_steps = ()
     training_domain = None   # None, True or a domain_config mapping: time_step counts the cells outside the box when domain_now is set
     domain_now = False       # (the driver sets it at scoring steps)
     _domains = None          # per model None or its training-domain table (init's `domains`): the rows domain_box reads
@@ -152,6 +163,7 @@ class Microphysics_Rollout(Microphysics_Kessler):
         self._guard_steps = [[] for _ in committees]
         self._m0 = None
         self._w_before = self.rain_total = None
+        self._water_fix, self._water_fix_fresh, self._water_fix_for, self._water_fix_steps = None, False, None, []
 
     def time_step(self, coupler, dt):
         dm = coupler.get_data_manager_readwrite()
@@ -168,7 +180,8 @@ class Microphysics_Rollout(Microphysics_Kessler):
         (v0, c0, r0, d0, t0), p0 = self._m0
         ws = grown_workspace(self, "_ws", L.mw_kessler_workspace_bytes(nz, ncol), coupler.device)
         st = _stream_ptr(coupler.device)
-        budget = self._budget_members(coupler)
+        fixer = self._fixer_setup()
+        budget = self._budget_members(coupler, None if fixer is None else fixer[0])
         if budget is not None:                                                 # W_before of ALL members, before anything is stepped
             self._w_before = column_water([rho_v, rho_c, rho_r], nz, ncol, nens, coupler.get_dz(), self._w_before)
         check(L.mw_kessler_set_strict(self.strict))
@@ -204,13 +217,57 @@ class Microphysics_Rollout(Microphysics_Kessler):
                                                       self._guard_domain_counts, self._guard, [guarded.index(ci) for ci in boxed])
         if guarded:                                                            # Kessler on every flagged column, then the guarded members' commit
             self._guard.commit(nz, [self.committees[ci][2] for ci in guarded], in5, guards[guarded[0]]["max_rainsplit"], coupler.get_dz(), dt)
-        if budget is not None:
+        if fixer is not None:                                                  # the budget, and the fixed members give back the water they made
+            self._water_fix = water_fix_finish([rho_v, rho_c, rho_r], nz, ncol, nens, budget, range(nens), fixer[0], fixer[1], coupler.get_dz(),
+                                               dt, self._w_before, precl, self.rain_total, holder=self)
+            self._water_fix_fresh = True
+        elif budget is not None:
             surface_rain_finish([rho_v, rho_c, rho_r], nz, ncol, nens, budget, range(nens), coupler.get_dz(), dt, self._w_before, precl,
                                 self.rain_total)
 
-    def _budget_members(self, coupler):
-        """None without `surface_rain`; else the budget members' indices, with rain_total and the W_before buffer in place."""
+    def _fixer_setup(self):
+        """None without `water_fixer`; else (the fixed members' indices, the tolerance), checked."""
+        wf = self.water_fixer
+        if wf is None:
+            return None
+        if not hasattr(wf, "keys") or set(wf.keys()) - {"members", "tolerance"}:
+            endrun("Microphysics_Rollout: water_fixer is None or a mapping whose keys are members and tolerance")
+        stepped = self.member_names[1:len(self.member_names) - int(self.persistence)]      # models and committees: what a network steps
+        names = wf.get("members")
+        names = list(stepped) if names is None else [str(m) for m in names]
+        if len(set(names)) != len(names) or any(m not in stepped for m in names):
+            endrun("Microphysics_Rollout: water_fixer's members must be distinct network-stepped members (%s), never kessler or persistence"
+                   % ", ".join(stepped))
+        try:
+            tolerance = water_fix_tolerance(wf.get("tolerance", 0.0), "water_fixer.tolerance")
+        except ValueError as err:
+            endrun("Microphysics_Rollout: " + str(err))
+        if self._water_fix_for is not wf:                                      # another configuration: its own records
+            self._water_fix_for, self._water_fix_steps, self._water_fix, self._water_fix_fresh = wf, [], None, False
+        return [self.member_names.index(m) for m in names], tolerance
+
+    def water_fix_record(self, step):
+        """At a scoring step, after a time_step with `water_fixer`: fetches that step's statistics of every member (the only host read of
+        them; no other step synchronises for the report)."""
+        if self.water_fixer is None or not self._water_fix_fresh:
+            return
+        stats, counts = self._water_fix.host()
+        self._water_fix_steps.append((int(step), counts.reshape(-1, 2), stats.reshape(-1, 2)))
+        self._water_fix_fresh = False
+
+    def water_fix_reports(self):
+        """None without `water_fixer`; else the `water_fixer` block of surrogate_rollout.json (water_fix_report) from the recorded steps."""
+        fixer = self._fixer_setup()
+        if fixer is None:
+            return None
+        return water_fix_report(self.member_names, fixer[0], fixer[1], self._domain_cells[1], self._water_fix_steps)
+
+    def _budget_members(self, coupler, fixed=None):
+        """None without `surface_rain` and without a fixer (fixed: None or its members' indices); else the budget members' indices --
+        surface_rain's, then the fixed ones that are not among them -- with rain_total and the W_before buffer in place."""
         sr = self.surface_rain
+        if sr is None and fixed is not None:
+            sr = {"budget_members": []}
         if sr is None:
             return None
         if not hasattr(sr, "keys") or set(sr.keys()) - {"budget_members"}:
@@ -223,7 +280,8 @@ class Microphysics_Rollout(Microphysics_Kessler):
         if self.rain_total is None or tuple(self.rain_total.shape) != shape:
             self.rain_total = torch.zeros(shape, dtype=torch.float64, device=coupler.device)
             self._w_before = None
-        return [self.member_names.index(m) for m in names]
+        budget = [self.member_names.index(m) for m in names]
+        return budget + [m for m in (fixed or ()) if m not in budget]
 
     def _committee_box(self, ci, cfg):
         cname, cmodels = self._committee_names[ci]
@@ -304,6 +362,39 @@ class Microphysics_Rollout(Microphysics_Kessler):
             if "domain" in g:
                 out[-1]["domain"] = dict(g["domain"], box=box_json(self._guard_boxes[ci]))
         return out
+
+
+def water_fix_report(member_names, fixed, tolerance, columns, records):
+    """The `water_fixer` block of surrogate_rollout.json from raw arrays -- pure numpy.  member_names: the rollout's; fixed: the fixed
+    members' indices; columns: a member's columns; records: (step, counts (nens, 2) int64 = fixed and skipped columns, stats (nens, 2) fp64 =
+    sum and max of the excess, kg / m^2) per scoring step, mw_member_water_fix's outputs.  Returns tolerance, members (names), columns,
+    steps: {step, members: {name: {columns_fixed, columns_skipped, water_removed_kg_m2: {mean, max}}}} with the mean over ALL the member's
+    columns, and totals per member over the recorded steps: the counts summed, water_removed_kg_m2 {mean: the steps' means summed -- what a
+    column lost to the fixer on average over those steps -- and max}."""
+    nens = len(member_names)
+    fixed = [int(m) for m in fixed]
+    if any(not 0 <= m < nens for m in fixed) or len(set(fixed)) != len(fixed):
+        endrun("water_fix_report: the fixed members must be distinct indices of the member names")
+    columns = None if columns is None else int(columns)
+    steps = []
+    totals = {member_names[m]: {"columns_fixed": 0, "columns_skipped": 0, "water_removed_kg_m2": {"mean": 0.0, "max": 0.0}} for m in fixed}
+    for step, counts, stats in records:
+        counts, stats = np.asarray(counts, dtype=np.int64), np.asarray(stats, dtype=np.float64)
+        if counts.shape != (nens, 2) or stats.shape != (nens, 2):
+            endrun("water_fix_report: (%d, 2) counts and (%d, 2) statistics per step expected" % (nens, nens))
+        row = {}
+        for m in fixed:
+            mean = float(stats[m, 0]) / columns if columns else None
+            row[member_names[m]] = {"columns_fixed": int(counts[m, 0]), "columns_skipped": int(counts[m, 1]),
+                                    "water_removed_kg_m2": {"mean": mean, "max": float(stats[m, 1])}}
+            t = totals[member_names[m]]
+            t["columns_fixed"] += int(counts[m, 0])
+            t["columns_skipped"] += int(counts[m, 1])
+            if mean is not None:
+                t["water_removed_kg_m2"]["mean"] += mean
+            t["water_removed_kg_m2"]["max"] = max(t["water_removed_kg_m2"]["max"], float(stats[m, 1]))
+        steps.append({"step": int(step), "members": row})
+    return {"tolerance": float(tolerance), "members": [member_names[m] for m in fixed], "columns": columns, "steps": steps, "totals": totals}
 
 
 def domain_report(cfg, box, cells, columns, records):
@@ -684,6 +775,23 @@ def member_surface_rain(coupler, members, accum, dt, w_before, rain_total=None):
             endrun("member_surface_rain: %s must be a (ny, nx, nens) tensor" % what)
     precl = coupler.get_data_manager_readwrite().get("precl")
     surface_rain_finish(_water3(coupler), coupler.get_nz(), ny * nx, nens, members, accum, coupler.get_dz(), dt, w_before, precl, rain_total)
+
+
+def member_water_fix(coupler, members, accum, fixed, dt, w_before, rain_total=None, tolerance=0.0, excess=None):
+    """mw_member_water_fix on the coupler's state and its `precl`: member_surface_rain that also acts.  A column of a member in `fixed`
+    (indices, a subset of `members`) that holds more water than w_before by more than tolerance * w_before has water_vapor, cloud_liquid
+    and precip_liquid scaled by w_before / (its water now); its precl is the budget of the state left behind.  temp and density_dry are
+    never touched.  excess: None or a (ny, nx, nens) tensor that receives the water removed per column, kg / m^2.  Returns (counts
+    (nens, 2) int64 = fixed, skipped columns; stats (nens, 2) fp64 = sum, max of the excess) as numpy arrays."""
+    ny, nx, nens = coupler.get_ny(), coupler.get_nx(), coupler.get_nens()
+    for t, what in ((w_before, "w_before"), (rain_total, "rain_total"), (excess, "excess")):
+        if t is not None and (tuple(t.shape) != (ny, nx, nens) or not t.is_contiguous()):
+            endrun("member_water_fix: %s must be a (ny, nx, nens) tensor" % what)
+    precl = coupler.get_data_manager_readwrite().get("precl")
+    out = water_fix_finish(_water3(coupler), coupler.get_nz(), ny * nx, nens, members, accum, fixed, tolerance, coupler.get_dz(), dt, w_before,
+                           precl, rain_total, holder=coupler, excess=excess)
+    stats, counts = out.host()
+    return counts.reshape(nens, 2), stats.reshape(nens, 2)
 
 
 def member_rain_table(coupler, fields, thresholds):
