@@ -718,6 +718,34 @@ int  mw_member_water_fix(int nz, long long ncol, int nens, int nm, const int *me
                          const int *fixed, double tolerance, double *const *water3, double dz, double dt, const double *w_before,
                          double *precl, double *rain_total, void *workspace, long long *counts, double *stats, double *excess,
                          void *stream);
+/* The latent-heat closure.  In a Kessler step temp changes only by the vapour that condenses or evaporates in the cell,
+ * so temp_after - temp_before = (lv / cp_d) * (rho_v_before - rho_v_after) / rho_d per cell; a network writes temp and water_vapor as two
+ * unrelated outputs.  All fields DEVICE fp64, member-fastest (nz, ncol, nens).  members: HOST array of nm (0 .. nens) distinct DIAGNOSED
+ * members; closed: HOST array of nclosed distinct members, every one of them in `members`.  Per cell i = (k * ncol + col) * nens + e of a
+ * diagnosed member e, in fp64, no contraction, every operation rounded once:
+ *   C   = lv / cp_d                                              (one division, on the host)
+ *   T_c = temp_before[i] + C * ((rho_v_before[i] - rho_v[i]) / rho_d[i])
+ *   r   = temp[i] - T_c                                          (the residual, K)
+ *   r not finite (any of the five values NaN or inf, or rho_d == 0):  SKIPPED -- counted, temp untouched, left out of every sum;
+ *   e in `closed` and |r| > tolerance (strict):                       CLOSED -- temp[i] = T_c, an ordinary store, counted;
+ *   otherwise nothing is written.
+ * Only temp is written, and only in closed members.  Statistics of every diagnosed member over its cells with finite r, r BEFORE closing:
+ * counts: DEVICE int64 (nens, 2) = closed cells, skipped cells; stats: DEVICE fp64 (nens, 6) = sum r, sum |r|, sum r^2, max |r|, sum H,
+ * max |H|, where H[t] = ((cp_d * dz) / dt) * (sum over k of rho_d * r), W / m^2, is the spurious heating of column t = col * nens + e (k
+ * ascending in one accumulator from +0.0; the scale, made on the host, applied once); both SET, zeros for a member not diagnosed.  heating:
+ * NULL, or DEVICE fp64 (ncol, nens) that receives H, +0.0 for members not diagnosed.  Order of the sums: a column's cells in ascending k from
+ * +0.0; a block of 256 consecutive plane elements folds each member's lanes in ascending order from +0.0; for each member thread l of 256
+ * folds the blocks l, l + 256, ... in ascending order from +0.0, then the 256 results are folded in ascending l -- no atomics, no memset,
+ * run-to-run identical.  before2: HOST array of 2 DEVICE pointers, temp_before and rho_v_before, read only at elements of diagnosed members.
+ * workspace: DEVICE, mw_member_heat_closure_workspace_bytes(ncol, nens) bytes (0: arguments out of range).  Refused, with nothing launched:
+ * what mw_member_surface_rain refuses, a closed member outside `members`, a tolerance that is negative or not finite, lv or cp_d not
+ * positive and finite, null workspace, counts or stats, temp equal to any of the four arrays that are only read.  Asynchronous on `stream`. */
+long long mw_member_heat_closure_workspace_bytes(long long ncol, int nens);
+int  mw_member_heat_closure(int nz, long long ncol, int nens, int nm, const int *members, int nclosed, const int *closed,
+                            double tolerance, double lv, double cp_d, double dz, double dt,
+                            double *temp, const double *rho_d, const double *rho_v,
+                            const double *const *before2 /* temp_before, rho_v_before */,
+                            void *workspace, long long *counts, double *stats, double *heating /* or NULL */, void *stream);
 /* The contingency table of nf (1 .. 4) member-fastest DEVICE fp64 fields (ncol, nens) against member 0, the observation.  Field f has
  * nt[f] (1 .. 8) thresholds, finite and strictly ascending: thresholds is a HOST (nf, 8) fp64 array whose row f holds them first (the
  * rest is not read); nt: HOST.  An event is x >= thr.  counts: DEVICE int64 (nf, 8, nens, 5) = hits (member and member 0 both have the

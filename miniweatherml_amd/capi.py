@@ -186,6 +186,9 @@ SYMBOLS = {
     "mw_member_water_fix_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int]),
     "mw_member_water_fix": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int,
                                       C.POINTER(C.c_int), C.c_double, C.POINTER(C.c_void_p), C.c_double, C.c_double] + [C.c_void_p] * 8),
+    "mw_member_heat_closure_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int]),
+    "mw_member_heat_closure": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)] + [C.c_double] * 5
+                               + [C.c_void_p] * 3 + [C.POINTER(C.c_void_p)] + [C.c_void_p] * 5),
     "mw_member_rain_table_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     "mw_member_rain_table": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                        C.c_void_p, C.c_void_p, C.c_void_p]),

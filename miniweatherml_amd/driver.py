@@ -94,6 +94,16 @@ columns_fixed, columns_skipped and water_removed_kg_m2 {mean over the columns, m
 one set of weights under two names and fixing one of them shows the fixer's effect in one run.  inference_ponni reads the key (without
 `members`) and then runs its network online with the fixer on every column.  false or absent: the document and the run are what they are
 without the key.
+    heat_closure: true                        # or {members: [kessler, tend0], closed: [tend0], tolerance: 0.0}
+makes rollout_surrogates hold its members to Kessler's latent-heat identity: in a Kessler step a cell's temp changes by
+(lv / cp_d) * (its loss of water vapour) / density_dry and by nothing else.  `members` (default: every member but persistence) are
+diagnosed: their residual temp - (that value) is measured per cell.  `closed` (default: every model and committee member; never kessler
+or persistence; a subset of members) have their temp replaced by the diagnosed value where |residual| > tolerance (K), after the networks
+and before the water fixer.  surrogate_rollout.json gets a `heat_closure` block: lv, cp_d, tolerance, members, closed, cells, per scoring
+step and member cells_closed, cells_skipped, residual_K {bias, mae, rmse, max} (before closing) and heating_W_m2 {mean, max} (the
+spurious heating of a column), and the totals over the scoring steps.  The kessler row is the report's sanity line: a few ulp of temp.
+inference_ponni reads the key (without the lists) and then runs its network online with the closure on every cell.  false or absent: the
+document and the run are what they are without the key.
 """
 import argparse
 import json
@@ -134,7 +144,7 @@ def load_config(path):
         if key in cfg:
             out[key] = str(cfg[key])
     out["_dir"] = os.path.dirname(os.path.abspath(path))
-    for key in ("surrogate_models", "eval_interval", "persistence_member", "harvest", "surrogate_committees", "surface_rain", "training_domain", "eval_domain", "water_fixer"):    # read by surrogate_config / rollout_config / harvest_config / committee_config / surface_rain_config / training_domain_config / eval_domain_key / water_fixer_config alone
+    for key in ("surrogate_models", "eval_interval", "persistence_member", "harvest", "surrogate_committees", "surface_rain", "training_domain", "eval_domain", "water_fixer", "heat_closure"):    # read by surrogate_config / rollout_config / harvest_config / committee_config / surface_rain_config / training_domain_config / eval_domain_key / water_fixer_config / heat_closure_config alone
         if key in cfg:
             out[key] = cfg[key]
     return out
@@ -376,6 +386,53 @@ def water_fixer_config(cfg, member_names=None):
     return out
 
 
+HEAT_CLOSURE_KEYS = ("members", "closed", "tolerance")
+
+
+def heat_closure_config(cfg, member_names=None, stepped_names=None):
+    """The checked `heat_closure:` key of a loaded configuration for rollout_surrogates (and, without the lists, inference_ponni), or None
+    when it is absent or false: true (every member but persistence diagnosed, every network-stepped member closed, tolerance 0) or
+    {members: [names], closed: [names], tolerance: t}.  members: a non-empty list of distinct names, never persistence -- and, when
+    member_names (the rollout's diagnosable members) is given, each one of them; absent: all of them (None in the result).  closed: a list
+    (it may be empty: diagnose only) of distinct names, never kessler or persistence, each in `members` when that is given -- and, when
+    stepped_names (the names a network steps) is given, each one of them; absent: every network-stepped member among `members` (None).
+    tolerance: a finite number >= 0 (default 0), K: a cell is closed when |residual| exceeds it."""
+    b = cfg.get("heat_closure", False)
+    if b is False or b is None:
+        return None
+    b = {} if b is True else b
+    if not isinstance(b, dict):
+        raise ValueError("ERROR: heat_closure must be true, false or a mapping")
+    unknown = sorted(set(b) - set(HEAT_CLOSURE_KEYS), key=str)
+    if unknown:
+        raise ValueError("ERROR: unknown key(s) %s in heat_closure (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(HEAT_CLOSURE_KEYS)))
+    out = {"members": None, "closed": None, "tolerance": microphysics.water_fix_tolerance(b.get("tolerance", 0.0), "heat_closure.tolerance")}
+    if b.get("members") is not None:
+        names = b["members"]
+        if not isinstance(names, list) or not names or not all(isinstance(n, str) for n in names) or len(set(names)) != len(names):
+            raise ValueError("ERROR: heat_closure.members must be a non-empty list of distinct member names")
+        for n in names:
+            if n == "persistence":
+                raise ValueError("ERROR: heat_closure.members names 'persistence': a member that nothing steps has no residual")
+            if member_names is not None and n not in member_names:
+                raise ValueError("ERROR: heat_closure.members names %r, which is no member of this run (%s)" % (n, ", ".join(member_names)))
+        out["members"] = list(names)
+    if b.get("closed") is not None:
+        names = b["closed"]
+        if not isinstance(names, list) or not all(isinstance(n, str) for n in names) or len(set(names)) != len(names):
+            raise ValueError("ERROR: heat_closure.closed must be a list of distinct member names")
+        for n in names:
+            if n in ("kessler", "persistence"):
+                raise ValueError("ERROR: heat_closure.closed names %r: only a member that a network steps can be closed" % n)
+            if stepped_names is not None and n not in stepped_names:
+                raise ValueError("ERROR: heat_closure.closed names %r, which is no model or committee of this run (%s)"
+                                 % (n, ", ".join(stepped_names)))
+            if out["members"] is not None and n not in out["members"]:
+                raise ValueError("ERROR: heat_closure.closed names %r, which is not in heat_closure.members" % n)
+        out["closed"] = list(names)
+    return out
+
+
 def training_domain_config(cfg):
     """The checked `training_domain:` key of a loaded configuration for rollout_surrogates, or None when it is absent or false: true
     (margin 0, all five input fields) or {margin, fields} (surrogate_eval.domain_config)."""
@@ -595,6 +652,7 @@ class CommunityBenchmark(Column):
 class InferencePonni(Column):
     committee = None                                                           # the one committee that runs in place of a single network
     fixer_cfg = None                                                           # the checked `water_fixer` key (without members)
+    closure_cfg = None                                                         # the checked `heat_closure` key (without the lists)
 
     def configure(self, cfg, nranks):
         if "surrogate_committees" in cfg and not ("keras_weights_h5" in cfg or "keras_weights_txt" in cfg):
@@ -606,6 +664,9 @@ class InferencePonni(Column):
         self.fixer_cfg = water_fixer_config(cfg)
         if self.fixer_cfg is not None and self.fixer_cfg["members"] is not None:
             raise ValueError("ERROR: inference_ponni's water_fixer takes no members: the one network steps every column")
+        self.closure_cfg = heat_closure_config(cfg)
+        if self.closure_cfg is not None and (self.closure_cfg["members"] is not None or self.closure_cfg["closed"] is not None):
+            raise ValueError("ERROR: inference_ponni's heat_closure takes no members and no closed: the one network steps every cell")
 
     def make_micro(self):
         cfg, coupler, info = self.cfg, self.coupler, self.info
@@ -630,6 +691,8 @@ class InferencePonni(Column):
             print("inference_ponni: surrogate output form: %s" % info["surrogate_form"], flush=True)
         if self.fixer_cfg is not None:                                         # the fixer acts on the state the network leaves: online
             micro.online, micro.water_fixer = True, {"tolerance": self.fixer_cfg["tolerance"]}
+        if self.closure_cfg is not None:                                       # the closure acts on the state the network leaves: online
+            micro.online, micro.heat_closure = True, {"tolerance": self.closure_cfg["tolerance"]}
         return micro
 
     def micro_step(self, dt, etime):
@@ -744,10 +807,10 @@ class EvaluateSurrogates(Column):
 
 
 def rollout_document(experiment, yaml_path, eval_interval, steps, models, scorer, rep, micro, committees=(), domain_blocks=None,
-                     harvest=None, rain_cfg=None, rain=None, water_fixer=None):
+                     harvest=None, rain_cfg=None, rain=None, water_fixer=None, heat_closure=None):
     """surrogate_rollout.json as a dict.  rep: the scorer's report; domain_blocks: micro.domain_reports() with `training_domain`;
     harvest: harvest_block's result with a harvester; rain_cfg, rain: the checked `surface_rain` and its RainScorer; water_fixer:
-    micro.water_fix_reports() with `water_fixer`.  None: no such block."""
+    micro.water_fix_reports() with `water_fixer`; heat_closure: micro.heat_closure_reports() with `heat_closure`.  None: no such block."""
     doc = {"experiment": experiment, "yaml": os.path.abspath(yaml_path), "eval_interval": eval_interval, "steps": steps,
            "members": list(scorer.member_names), "models": [dict(m, member=1 + k, form=micro.model_forms[k]) for k, m in enumerate(models)],
            "fields": list(scorer.fields), "statistics": list(rollout.ROLLOUT_STATS), "history": scorer.history,
@@ -766,11 +829,14 @@ def rollout_document(experiment, yaml_path, eval_interval, steps, models, scorer
         doc["surface_rain"] = dict(rain_cfg, report=rain.times)
     if water_fixer is not None:
         doc["water_fixer"] = water_fixer
+    if heat_closure is not None:
+        doc["heat_closure"] = heat_closure
     return doc
 
 
 class RolloutSurrogates(Column):
     fixer_cfg = None                                                           # the checked `water_fixer` key
+    closure_cfg = None                                                         # the checked `heat_closure` key
 
     def configure(self, cfg, nranks):
         _one_rank("rollout_surrogates", nranks)
@@ -779,7 +845,9 @@ class RolloutSurrogates(Column):
         self.domain_cfg = training_domain_config(cfg)
         self.committees = committee_config(cfg)
         cfg["surrogate_models"], cfg["eval_interval"], cfg["persistence_member"], cfg["nens"] = rollout_config(cfg)
-        self.fixer_cfg = water_fixer_config(cfg, [m["name"] for m in cfg["surrogate_models"]] + [c["name"] for c in self.committees])
+        stepped = [m["name"] for m in cfg["surrogate_models"]] + [c["name"] for c in self.committees]
+        self.fixer_cfg = water_fixer_config(cfg, stepped)
+        self.closure_cfg = heat_closure_config(cfg, ["kessler"] + stepped, stepped)
 
     def make_micro(self):
         models = self.cfg["surrogate_models"]
@@ -803,6 +871,8 @@ class RolloutSurrogates(Column):
             micro.training_domain = self.domain_cfg
         if self.fixer_cfg is not None:                                         # (members None: every model and committee member)
             micro.water_fixer = {k: v for k, v in self.fixer_cfg.items() if v is not None}
+        if self.closure_cfg is not None:                                       # (lists None: the rollout's defaults)
+            micro.heat_closure = {k: v for k, v in self.closure_cfg.items() if v is not None}
         self.harvester = None
         if harvest is not None:
             self.harvester = micro.harvester = rollout.RolloutHarvester()
@@ -832,6 +902,8 @@ class RolloutSurrogates(Column):
         micro.domain_record(step)                                              # (and of the training-domain report's)
         if self.fixer_cfg is not None:
             micro.water_fix_record(step)                                       # (and of the water fixer's statistics)
+        if self.closure_cfg is not None:
+            micro.heat_closure_record(step)                                    # (and of the latent-heat closure's)
         if self.rain is not None:
             self.rain.accumulate(self.coupler, micro, step, etime + dt)
         for m, d in scorer.diverged_at.items():                                # the other members do not see it: the run goes on
@@ -845,6 +917,7 @@ class RolloutSurrogates(Column):
         doc = rollout_document(info["experiment"], yaml_path, self.cfg["eval_interval"], steps, self.cfg["surrogate_models"], scorer, rep, micro,
                                self.committees, domain_blocks=blocks, rain_cfg=self.rain_cfg, rain=rain,
                                water_fixer=micro.water_fix_reports() if self.fixer_cfg is not None else None,
+                               heat_closure=micro.heat_closure_reports() if self.closure_cfg is not None else None,
                                harvest=harvest_block(self.harvest, self.harvester) if self.harvester is not None else None)
         if blocks is not None:
             info["domain_reports"] = {scorer.member_names[m]: b for m, b in enumerate(blocks) if b is not None}
@@ -852,6 +925,8 @@ class RolloutSurrogates(Column):
             info["harvest"] = doc["harvest"]
         if self.fixer_cfg is not None:
             info["water_fixer_report"], info["rain_total"] = doc["water_fixer"], micro.rain_total
+        if self.closure_cfg is not None:
+            info["heat_closure_report"] = doc["heat_closure"]
         if rain is not None:
             info["surface_rain_report"], info["rain_total"] = rain.times, micro.rain_total
             if self.rain_cfg["map"] and micro.rain_total is not None:          # (nens, ny, nx) fp64, mm since the start of the run

@@ -69,6 +69,47 @@ def water_fix_finish(water3, nz, ncol, nens, members, accum, fixed, tolerance, d
     return out
 
 
+LV, CP_D = 2.5e6, 1003.0       # Kessler's latent heat of vaporisation (microphysics_kessler.h:247) and cp_d (:32), the closure's constants
+
+
+def members_copy(n, nens, members, src, dst):
+    """mw_members_copy: the listed members' elements of the member-fastest (n, nens) tensors `src` into `dst` (1 .. 8 pairs)."""
+    dev = src[0].device
+    members = [int(m) for m in members]
+    with torch.cuda.device(dev):
+        check(capi.lib().mw_members_copy(n, nens, len(members), (C.c_int * max(1, len(members)))(*members), len(src), _field_ptr_array(src),
+                                         _field_ptr_array(dst), _stream_ptr(dev)))
+
+
+def heat_closure_finish(temp, rho_d, rho_v, before2, nz, ncol, nens, members, closed, tolerance, dz, dt, holder=None, heating=None,
+                        lv=LV, cp_d=CP_D):
+    """mw_member_heat_closure, its one caller.  Per cell of a member in `members`, T_c = temp_before + (lv / cp_d) *
+    (rho_v_before - rho_v) / rho_d and r = temp - T_c; a cell of a member in `closed` (a subset of `members`) with |r| > tolerance gets
+    temp = T_c; a cell whose r is not finite is skipped.  before2: (temp_before, rho_v_before), read at the diagnosed members' elements.
+    Returns the StatsAndCounts of the call, on the device: 6 * nens doubles (sum r, sum |r|, sum r^2, max |r|, sum H, max |H| per member,
+    of the residual BEFORE closing) and 2 * nens counts (closed and skipped cells per member).  holder: the object that keeps the workspace
+    and that buffer between calls; heating: an (ncol * nens) tensor that receives every column's spurious heating H, W / m^2."""
+    dev = temp.device
+    members, closed = [int(m) for m in members], [int(m) for m in closed]
+    L = capi.lib()
+    nbytes = L.mw_member_heat_closure_workspace_bytes(ncol, nens)
+    if nbytes <= 0:
+        endrun("heat_closure_finish: %d columns x %d members are out of range (at most 64 members)" % (ncol, nens))
+    holder = holder if holder is not None else types.SimpleNamespace()
+    ws = grown_workspace(holder, "_ws_heat_closure", nbytes, dev)
+    held = getattr(holder, "_heat_closure_out", None)
+    out = StatsAndCounts(6 * nens, 2 * nens, dev, held.buf if held is not None and held.buf.numel() == 8 * nens and held.buf.device == ws.device
+                         else None)
+    holder._heat_closure_out = out
+    ints = lambda v: (C.c_int * max(1, len(v)))(*v)                            # noqa: E731
+    with torch.cuda.device(dev):
+        check(L.mw_member_heat_closure(nz, ncol, nens, len(members), ints(members), len(closed), ints(closed), float(tolerance), float(lv),
+                                       float(cp_d), float(dz), float(dt), _ptr(temp), _ptr(rho_d), _ptr(rho_v), _field_ptr_array(list(before2)),
+                                       _ptr(ws), out.counts_ptr, out.stats_ptr, _ptr(heating) if heating is not None else None,
+                                       _stream_ptr(dev)))
+    return out
+
+
 def water_fix_tolerance(value, what):
     """A checked tolerance of a water fixer: a finite number >= 0 (ValueError)."""
     if isinstance(value, bool) or not isinstance(value, (int, float)) or not (value >= 0.0 and value - value == 0.0):
@@ -143,6 +184,8 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
     surface_rain = False  # True (with online only): precl after the step is the column water budget of the state left in the coupler
     water_fixer = None    # True or {tolerance} (with online only): a column that gained water in the step is scaled back
     last_water_fix = None  # with water_fixer: the StatsAndCounts of the last step, on the device (water_fix_stats fetches it)
+    heat_closure = None   # True or {tolerance} (with online only): temp becomes what the network's own vapour change makes it
+    last_heat_closure = None  # with heat_closure: the StatsAndCounts of the last step, on the device (heat_closure_stats fetches it)
 
     def init(self, coupler, weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None, committee=None, guard=None,
              domains=None):
@@ -229,11 +272,23 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
             held = getattr(self, "_w_before", None)
             self._w_before = column_water([rho_v, rho_c, rho_r], nz, ncol, 1, coupler.get_dz(),
                                           held if held is not None and held.numel() == ncol else None)
+        closure = self._heat_closure_tolerance()
+        if closure is not None:                                                # temp and water_vapor before the call: the plane is one member
+            if not self.online:
+                endrun("Microphysics_Kessler_Surrogate: heat_closure needs online = True (offline the state is Kessler's, which obeys the closure)")
+            held = getattr(self, "_heat_before", None)
+            if held is None or held[0].shape != temp.shape or held[0].device != temp.device:
+                self._heat_before = held = [torch.empty_like(temp), torch.empty_like(temp)]
+            members_copy(temp.numel(), 1, [0], [temp, rho_v], held)
         super().time_step(coupler, dt)
         if self.online:                                                        # :273-276
             self._diffs = self.mean_diffs(coupler)                             # (the prints of :266-269 come first)
             for dst, src in zip((temp, rho_v, rho_c, rho_r), self._nn_out):
                 dst.copy_(src)
+        if closure is not None:                                                # before the fixer: the vapour change is the network's
+            rho_d = coupler.get_data_manager_readonly().get("density_dry", True)
+            self.last_heat_closure = heat_closure_finish(temp, rho_d, rho_v, self._heat_before, coupler.get_nz(), temp.numel() // coupler.get_nz(),
+                                                         1, [0], [0], closure, coupler.get_dz(), dt, holder=self)
         if budget:                                                             # Kessler's precl gives way to the budget of the state that stays
             precl = coupler.get_data_manager_readwrite().get("precl")
             if fixer is None:
@@ -256,6 +311,30 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
             return water_fix_tolerance(wf.get("tolerance", 0.0), "water_fixer.tolerance")
         except ValueError as err:
             endrun("Microphysics_Kessler_Surrogate: " + str(err))
+
+    def _heat_closure_tolerance(self):
+        """None without `heat_closure`; else its checked tolerance."""
+        hc = self.heat_closure
+        if hc is None or hc is False:
+            return None
+        if hc is True:
+            return 0.0
+        if not hasattr(hc, "keys") or set(hc.keys()) - {"tolerance"}:
+            endrun("Microphysics_Kessler_Surrogate: heat_closure is None, True or a mapping whose only key is tolerance")
+        try:
+            return water_fix_tolerance(hc.get("tolerance", 0.0), "heat_closure.tolerance")
+        except ValueError as err:
+            endrun("Microphysics_Kessler_Surrogate: " + str(err))
+
+    def heat_closure_stats(self):
+        """The last step's closure statistics of the whole plane, fetched from the device: cells_closed, cells_skipped, residual_K {sum,
+        sum_abs, sum_sq, max}, heating_W_m2 {sum, max}; None before the first step with `heat_closure`."""
+        if self.last_heat_closure is None:
+            return None
+        stats, counts = self.last_heat_closure.host()
+        return {"cells_closed": int(counts[0]), "cells_skipped": int(counts[1]),
+                "residual_K": {"sum": float(stats[0]), "sum_abs": float(stats[1]), "sum_sq": float(stats[2]), "max": float(stats[3])},
+                "heating_W_m2": {"sum": float(stats[4]), "max": float(stats[5])}}
 
     def water_fix_stats(self):
         """The last step's fixer statistics of the whole plane, fetched from the device: columns_fixed, columns_skipped,

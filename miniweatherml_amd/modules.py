@@ -23,6 +23,8 @@ from .rollout import (RAIN_COUNTS, RAIN_FIELDS, ROLLOUT_FIELDS, ROLLOUT_IN5, ROL
 from .rollout import box_json, domain_report  # noqa: F401
 from .rollout import member_water_fix, water_fix_report  # noqa: F401
 from .microphysics import water_fix_finish  # noqa: F401
+from .rollout import heat_closure_report, member_heat_closure  # noqa: F401
+from .microphysics import heat_closure_finish  # noqa: F401
 from .rollout import SAMPLE_CLASSES, harvest_outside_report, harvest_thresholds, member_sample_mask_domain  # noqa: F401
 from .mlp import load_training_domain, load_training_domains  # noqa: F401
 from .sampling import DataGenerator, StatisticsGatherer  # noqa: F401

@@ -8,6 +8,7 @@ experiments/supercell_kessler_surrogate/custom_modules/generate_micro_surrogate_
   member_column_water, member_surface_rain            every member's surface rain from its column water budget
   member_rain_table, rain_report, RainScorer          its contingency table against the Kessler member and the reports
   member_water_fix, water_fix_report                  the water fixer: a member gives back the water its model made
+  member_heat_closure, heat_closure_report            the latent-heat closure: a member's temp from its own vapour change
   domain_report                                       a member's cells outside its model's training box, per scoring step"""
 import ctypes as C
 import os
@@ -19,7 +20,8 @@ from . import capi
 from ._ffi import StatsAndCounts, _field_ptr_array, _ptr, _stream_ptr, grown_workspace
 from .capi import check
 from .coupler import endrun
-from .microphysics import Microphysics_Kessler, column_water, surface_rain_finish, water_fix_finish, water_fix_tolerance
+from .microphysics import (CP_D, LV, Microphysics_Kessler, column_water, heat_closure_finish, members_copy, surface_rain_finish, water_fix_finish,
+                           water_fix_tolerance)
 from .mlp import IN5, OUT4, as_surrogate_model
 from .ncio import sample_file_append, sample_file_create
 from .sampling import sample_buffers, sample_thresholds
@@ -67,6 +69,12 @@ class Microphysics_Rollout(Microphysics_Kessler):
     more water than before the step is scaled back to what it held (the three water fields only: a mass fixer, no latent heat), the fixed
     members are budget members beside surface_rain's, and rain_total exists with or without surface_rain.  Every other member keeps the
     bits it has without the option.  water_fix_record / water_fix_reports keep the per-step statistics.
+    With `heat_closure` set to a mapping ({members: names, closed: names, tolerance: 0.0}; members default: every member but persistence;
+    closed default: every model and committee member, a subset of members; kessler and persistence are refused in closed) the step first
+    copies temp and water_vapor of the diagnosed members aside and, after the banks, the committees and the guard's commit and BEFORE the
+    water fixer, calls mw_member_heat_closure: every diagnosed member's residual r = temp - (temp_before + (lv / cp_d) (rho_v_before -
+    rho_v) / rho_d) is measured and a closed member's temp becomes the diagnosed value where |r| > tolerance.  Only temp is written, and
+    only in closed members.  heat_closure_record / heat_closure_reports keep the per-step statistics.
     With a `harvester` (RolloutHarvester) and `harvest_now` set, the step harvests Kessler labels on the model members' own states
     between the Kessler member's step and the models'; harvesting reads the state and never writes it.
     With `training_domain` (surrogate_eval.domain_config's mapping, or True) and `domain_now` set, the step counts, for every model member
@@ -88,6 +96,12 @@ class Microphysics_Rollout(Microphysics_Kessler):
     _water_fix_fresh = False
     _water_fix_for = None
     _water_fix_steps = ()
+    heat_closure = None   # a mapping (keys members, closed, tolerance): a closed member's temp follows from its own vapour change
+    _heat = None          # with heat_closure: the StatsAndCounts of the last step, on the device
+    _heat_fresh = False
+    _heat_for = None
+    _heat_steps = ()
+    _heat_before = None   # the two scratch fields: temp and water_vapor of the diagnosed members before the step
     training_domain = None   # None, True or a domain_config mapping: time_step counts the cells outside the box when domain_now is set
     domain_now = False       # (the driver sets it at scoring steps)
     _domains = None          # per model None or its training-domain table (init's `domains`): the rows domain_box reads
@@ -164,6 +178,7 @@ class Microphysics_Rollout(Microphysics_Kessler):
         self._m0 = None
         self._w_before = self.rain_total = None
         self._water_fix, self._water_fix_fresh, self._water_fix_for, self._water_fix_steps = None, False, None, []
+        self._heat, self._heat_fresh, self._heat_for, self._heat_steps, self._heat_before = None, False, None, [], None
 
     def time_step(self, coupler, dt):
         dm = coupler.get_data_manager_readwrite()
@@ -180,6 +195,11 @@ class Microphysics_Rollout(Microphysics_Kessler):
         (v0, c0, r0, d0, t0), p0 = self._m0
         ws = grown_workspace(self, "_ws", L.mw_kessler_workspace_bytes(nz, ncol), coupler.device)
         st = _stream_ptr(coupler.device)
+        closure = self._closure_setup()
+        if closure is not None:                                                # temp and water_vapor of the diagnosed members, before anything is stepped
+            if self._heat_before is None or self._heat_before[0].shape != temp.shape or self._heat_before[0].device != temp.device:
+                self._heat_before = [torch.empty_like(temp), torch.empty_like(temp)]
+            members_copy(n, nens, closure[0], [temp, rho_v], self._heat_before)
         fixer = self._fixer_setup()
         budget = self._budget_members(coupler, None if fixer is None else fixer[0])
         if budget is not None:                                                 # W_before of ALL members, before anything is stepped
@@ -217,6 +237,10 @@ class Microphysics_Rollout(Microphysics_Kessler):
                                                       self._guard_domain_counts, self._guard, [guarded.index(ci) for ci in boxed])
         if guarded:                                                            # Kessler on every flagged column, then the guarded members' commit
             self._guard.commit(nz, [self.committees[ci][2] for ci in guarded], in5, guards[guarded[0]]["max_rainsplit"], coupler.get_dz(), dt)
+        if closure is not None:                                                # the vapour change is the network's: before the fixer
+            self._heat = heat_closure_finish(temp, rho_d, rho_v, self._heat_before, nz, ncol, nens, closure[0], closure[1], closure[2],
+                                             coupler.get_dz(), dt, holder=self)
+            self._heat_fresh = True
         if fixer is not None:                                                  # the budget, and the fixed members give back the water they made
             self._water_fix = water_fix_finish([rho_v, rho_c, rho_r], nz, ncol, nens, budget, range(nens), fixer[0], fixer[1], coupler.get_dz(),
                                                dt, self._w_before, precl, self.rain_total, holder=self)
@@ -261,6 +285,51 @@ class Microphysics_Rollout(Microphysics_Kessler):
         if fixer is None:
             return None
         return water_fix_report(self.member_names, fixer[0], fixer[1], self._domain_cells[1], self._water_fix_steps)
+
+    def _closure_setup(self):
+        """None without `heat_closure`; else (the diagnosed members' indices, the closed members' indices, the tolerance), checked."""
+        hc = self.heat_closure
+        if hc is None:
+            return None
+        if not hasattr(hc, "keys") or set(hc.keys()) - {"members", "closed", "tolerance"}:
+            endrun("Microphysics_Rollout: heat_closure is None or a mapping whose keys are members, closed and tolerance")
+        stepped = self.member_names[1:len(self.member_names) - int(self.persistence)]      # models and committees: what a network steps
+        every = self.member_names[:len(self.member_names) - int(self.persistence)]
+        names = hc.get("members")
+        names = list(every) if names is None else [str(m) for m in names]
+        if not names or len(set(names)) != len(names) or any(m not in self.member_names for m in names):
+            endrun("Microphysics_Rollout: heat_closure's members must be one or more distinct members (%s)" % ", ".join(self.member_names))
+        closed = hc.get("closed")
+        closed = [m for m in stepped if m in names] if closed is None else [str(m) for m in closed]
+        if len(set(closed)) != len(closed) or any(m not in stepped for m in closed):
+            endrun("Microphysics_Rollout: heat_closure's closed must be distinct network-stepped members (%s), never kessler or persistence"
+                   % ", ".join(stepped))
+        if any(m not in names for m in closed):
+            endrun("Microphysics_Rollout: heat_closure's closed members must be among its members (%s)" % ", ".join(names))
+        try:
+            tolerance = water_fix_tolerance(hc.get("tolerance", 0.0), "heat_closure.tolerance")
+        except ValueError as err:
+            endrun("Microphysics_Rollout: " + str(err))
+        if self._heat_for is not hc:                                           # another configuration: its own records
+            self._heat_for, self._heat_steps, self._heat, self._heat_fresh = hc, [], None, False
+        return [self.member_names.index(m) for m in names], [self.member_names.index(m) for m in closed], tolerance
+
+    def heat_closure_record(self, step):
+        """At a scoring step, after a time_step with `heat_closure`: fetches that step's statistics of every member (the only host read of
+        them; no other step synchronises for the report)."""
+        if self.heat_closure is None or not self._heat_fresh:
+            return
+        stats, counts = self._heat.host()
+        self._heat_steps.append((int(step), counts.reshape(-1, 2), stats.reshape(-1, 6)))
+        self._heat_fresh = False
+
+    def heat_closure_reports(self):
+        """None without `heat_closure`; else the `heat_closure` block of surrogate_rollout.json (heat_closure_report) from the recorded steps."""
+        closure = self._closure_setup()
+        if closure is None:
+            return None
+        return heat_closure_report(self.member_names, closure[0], closure[1], closure[2], self._domain_cells[0], self._domain_cells[1],
+                                   self._heat_steps)
 
     def _budget_members(self, coupler, fixed=None):
         """None without `surface_rain` and without a fixer (fixed: None or its members' indices); else the budget members' indices --
@@ -395,6 +464,53 @@ def water_fix_report(member_names, fixed, tolerance, columns, records):
             t["water_removed_kg_m2"]["max"] = max(t["water_removed_kg_m2"]["max"], float(stats[m, 1]))
         steps.append({"step": int(step), "members": row})
     return {"tolerance": float(tolerance), "members": [member_names[m] for m in fixed], "columns": columns, "steps": steps, "totals": totals}
+
+
+def heat_closure_report(member_names, members, closed, tolerance, cells, columns, records, lv=LV, cp_d=CP_D):
+    """The `heat_closure` block of surrogate_rollout.json from raw arrays -- pure numpy.  member_names: the rollout's; members / closed: the
+    diagnosed and the closed members' indices (closed a subset of members); cells / columns: a member's cells (nz * ny * nx) and columns;
+    records: (step, counts (nens, 2) int64 = closed and skipped cells, stats (nens, 6) fp64 = sum r, sum |r|, sum r^2, max |r|, sum H,
+    max |H|) per scoring step, mw_member_heat_closure's outputs.  Returns lv, cp_d, tolerance, members, closed (names), cells, columns,
+    steps: {step, members: {name: {cells_closed, cells_skipped, residual_K: {bias, mae, rmse, max}, heating_W_m2: {mean, max}}}} -- bias, mae
+    and rmse over the member's cells that were not skipped (None when there is none), the mean of the heating over ALL the member's
+    columns -- and totals per member over the recorded steps: the counts summed, residual_K {bias, mae, rmse over all the steps' cells, max},
+    heating_W_m2 {mean: the mean of the steps' means, max}."""
+    nens = len(member_names)
+    members, closed = [int(m) for m in members], [int(m) for m in closed]
+    if any(not 0 <= m < nens for m in members) or len(set(members)) != len(members):
+        endrun("heat_closure_report: the diagnosed members must be distinct indices of the member names")
+    if any(m not in members for m in closed) or len(set(closed)) != len(closed):
+        endrun("heat_closure_report: the closed members must be distinct members of the diagnosed ones")
+    cells = None if cells is None else int(cells)
+    columns = None if columns is None else int(columns)
+
+    def residual(n, s, a, q, mx):
+        return {"bias": s / n if n else None, "mae": a / n if n else None, "rmse": float(np.sqrt(q / n)) if n else None, "max": mx}
+
+    steps = []
+    acc = {m: {"closed": 0, "skipped": 0, "n": 0, "s": 0.0, "a": 0.0, "q": 0.0, "max": 0.0, "h": 0.0, "hmax": 0.0, "steps": 0} for m in members}
+    for step, counts, stats in records:
+        counts, stats = np.asarray(counts, dtype=np.int64), np.asarray(stats, dtype=np.float64)
+        if counts.shape != (nens, 2) or stats.shape != (nens, 6):
+            endrun("heat_closure_report: (%d, 2) counts and (%d, 6) statistics per step expected" % (nens, nens))
+        row = {}
+        for m in members:
+            n = (cells - int(counts[m, 1])) if cells is not None else 0
+            s, a, q, mx, h, hmax = (float(x) for x in stats[m])
+            mean = h / columns if columns else None
+            row[member_names[m]] = {"cells_closed": int(counts[m, 0]), "cells_skipped": int(counts[m, 1]), "residual_K": residual(n, s, a, q, mx),
+                                    "heating_W_m2": {"mean": mean, "max": hmax}}
+            t = acc[m]
+            t["closed"] += int(counts[m, 0]); t["skipped"] += int(counts[m, 1]); t["n"] += n; t["steps"] += 1      # noqa: E702
+            t["s"] += s; t["a"] += a; t["q"] += q; t["max"] = max(t["max"], mx); t["hmax"] = max(t["hmax"], hmax)  # noqa: E702
+            t["h"] += mean if mean is not None else 0.0
+        steps.append({"step": int(step), "members": row})
+    totals = {member_names[m]: {"cells_closed": t["closed"], "cells_skipped": t["skipped"],
+                                "residual_K": residual(t["n"], t["s"], t["a"], t["q"], t["max"]),
+                                "heating_W_m2": {"mean": t["h"] / t["steps"] if t["steps"] and columns else None, "max": t["hmax"]}}
+              for m, t in acc.items()}
+    return {"lv": float(lv), "cp_d": float(cp_d), "tolerance": float(tolerance), "members": [member_names[m] for m in members],
+            "closed": [member_names[m] for m in closed], "cells": cells, "columns": columns, "steps": steps, "totals": totals}
 
 
 def domain_report(cfg, box, cells, columns, records):
@@ -792,6 +908,25 @@ def member_water_fix(coupler, members, accum, fixed, dt, w_before, rain_total=No
                            precl, rain_total, holder=coupler, excess=excess)
     stats, counts = out.host()
     return counts.reshape(nens, 2), stats.reshape(nens, 2)
+
+
+def member_heat_closure(coupler, members, closed, dt, before2, tolerance=0.0, heating=None):
+    """mw_member_heat_closure on the coupler's state.  before2: (temp_before, rho_v_before), two (nz, ny, nx, nens)
+    tensors read at the elements of the members in `members` (indices).  Per cell of such a member r = temp - (temp_before + (lv / cp_d) *
+    (rho_v_before - water_vapor) / density_dry); a cell of a member in `closed` (a subset of `members`) with |r| > tolerance gets the
+    diagnosed temp; a cell with a non-finite r is skipped.  Only temp is written.  heating: None or a (ny, nx, nens) tensor that receives
+    every column's spurious heating, W / m^2.  Returns (counts (nens, 2) int64 = closed, skipped cells; stats (nens, 6) fp64 = sum r,
+    sum |r|, sum r^2, max |r|, sum H, max |H|, of the residual before closing) as numpy arrays."""
+    nz, ny, nx, nens = coupler.get_nz(), coupler.get_ny(), coupler.get_nx(), coupler.get_nens()
+    if len(before2) != 2 or any(tuple(t.shape) != (nz, ny, nx, nens) or not t.is_contiguous() for t in before2):
+        endrun("member_heat_closure: before2 must be two (nz, ny, nx, nens) tensors")
+    if heating is not None and (tuple(heating.shape) != (ny, nx, nens) or not heating.is_contiguous()):
+        endrun("member_heat_closure: heating must be a (ny, nx, nens) tensor")
+    dm = coupler.get_data_manager_readwrite()
+    out = heat_closure_finish(dm.get("temp"), dm.get("density_dry", readonly=True), dm.get("water_vapor", readonly=True), before2, nz, ny * nx,
+                              nens, members, closed, tolerance, coupler.get_dz(), dt, holder=coupler, heating=heating)
+    stats, counts = out.host()
+    return counts.reshape(nens, 2), stats.reshape(nens, 6)
 
 
 def member_rain_table(coupler, fields, thresholds):
