@@ -14,8 +14,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmw_cdna4.so")
 # the dycore is eight units (map: csrc/mw_dycore_int.h); every kernel family is launched from exactly one of them
 SOURCES = ["mw_host.cpp", "mw_dycore.hip", "mw_march_y.hip", "mw_march_xz.hip", "mw_march_tracers.hip", "mw_march_sched.hip", "mw_zero_rows.hip",
-           "mw_dycore_init.hip", "mw_dycore_aids.hip", "mw_kessler.hip", "mw_mlp.hip", "mw_surrogate_bank.hip", "mw_surrogate_eval_domain.hip", "mw_member.hip", "mw_member_heat.hip", "mw_train.hip", "mw_column.hip", "mw_output.hip", "mw_netcdf.cpp", "mw_rccl.cpp", "mw_h5.cpp"]
-HEADERS = ["mw_common.h", "mw_dycore_int.h", "mw_weno.h", "mw_weno79.h", "mw_march.h", "mw_zero_rows.h", "mw_calib.h", "mw_glibc_pow.h", "mw_glibc_pow_tables.h", "mw_kessler_teacher.h", "mw_sample_key.h", "mw_mlp_net.h", "mw_surrogate_bank.h", os.path.join("..", "..", "include", "mw_cdna4.h")]
+           "mw_dycore_init.hip", "mw_dycore_aids.hip", "mw_kessler.hip", "mw_mlp.hip", "mw_surrogate_bank.hip", "mw_surrogate_eval_domain.hip", "mw_member.hip", "mw_member_sample.hip", "mw_member_guard.hip", "mw_member_water.hip", "mw_member_heat.hip", "mw_train.hip", "mw_column.hip", "mw_output.hip", "mw_netcdf.cpp", "mw_rccl.cpp", "mw_h5.cpp"]
+HEADERS = ["mw_common.h", "mw_dycore_int.h", "mw_weno.h", "mw_weno79.h", "mw_march.h", "mw_zero_rows.h", "mw_calib.h", "mw_glibc_pow.h", "mw_glibc_pow_tables.h", "mw_kessler_teacher.h", "mw_sample_key.h", "mw_mlp_net.h", "mw_surrogate_bank.h", "mw_member.h", os.path.join("..", "..", "include", "mw_cdna4.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 MAX_JOBS = 16      # hipcc processes at a time (never sized by the machine's CPU count: build boxes are shared)
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",

@@ -20,6 +20,7 @@
 #include "mw_common.h"
 #include "mw_glibc_pow.h"
 #include "mw_kessler_teacher.h"
+#include "mw_member.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -795,12 +796,7 @@ int mw_kessler_members_teacher(int nz, long long ncol, int nens, int nm, const i
   if (!members || !fields5 || !out4 || !workspace) MW_FAIL("kessler_members_teacher: null pointer");
   if (nm < 1 || nm > nens) MW_FAIL("kessler_members_teacher: nm must be in [1, nens]");
   unsigned long long listed = 0;
-  for (int j = 0; j < nm; j++) {
-    const int e = members[j];
-    if (e < 0 || e >= nens) MW_FAIL("kessler_members_teacher: member " + std::to_string(e) + " is outside [0, " + std::to_string(nens) + ")");
-    if ((listed >> e) & 1ull) MW_FAIL("kessler_members_teacher: member " + std::to_string(e) + " is listed twice");
-    listed |= 1ull << e;
-  }
+  if (member_bits("kessler_members_teacher", "members", nens, nm, members, &listed)) return 1;
   for (int f = 0; f < 5; f++) if (!fields5[f]) MW_FAIL("kessler_members_teacher: null field");
   for (int f = 0; f < 4; f++) if (!out4[f]) MW_FAIL("kessler_members_teacher: null field");
   if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");

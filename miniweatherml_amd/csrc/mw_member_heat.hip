@@ -3,18 +3,19 @@
 // only thing that changes a cell's temp is the vapour that leaves or enters it, so temp_after - temp_before = (lv / cp_d) *
 // (rho_v_before - rho_v_after) / rho_d in every cell.  mw_member_heat_closure measures how far a member's step is from that (the residual,
 // K, and the spurious heating of a column, W / m^2) and, for the members listed as closed, makes temp the diagnosed quantity of the member's
-// own vapour change.  A unit of its own: the kernels of mw_member.hip keep their code object.
+// own vapour change.  One of the five member units: the list parser, the scalar checks and the block-row reduction
+// are mw_member.h's, shared with the water fixer.
 // =====================================================================================================
 #include "../../include/mw_cdna4.h"
-#include "mw_common.h"
-#include <string>
+#include "mw_member.h"
 
 namespace mw {
 
 struct HeatFields { double *temp; const double *rho_d, *rho_v, *temp_b, *rho_v_b; };
 constexpr int HEAT_AHEAD = 4;              // levels whose loads are issued ahead of their arithmetic
+constexpr int HEAT_COUNTS = 2;             // per block and member: closed cells, skipped cells (int64 bits), then
 constexpr int HEAT_STATS = 6;              // sum r, sum |r|, sum r^2, max |r|, sum H, max |H|
-constexpr int HEAT_ROW = 8;                // per block and member: closed cells, skipped cells (int64 bits), then the six statistics
+constexpr unsigned HEAT_MAX = (1u << 3) | (1u << 5);      // (statistics 3 and 5 are maxima)
 
 // one cell of a diagnosed lane; every operation is rounded once (contraction is off), so numpy restates it bit for bit
 struct HeatLane {
@@ -46,10 +47,8 @@ __device__ __forceinline__ void heat_cell(HeatLane &q, double C, double toleranc
 // k_member_surface_rain's mapping: thread t is one (column, member) of the plane, so a wavefront's loads of a level are 64 consecutive
 // doubles per field whatever nens is; a wavefront with no diagnosed lane takes no load at all (its lanes' branch is empty).  The twenty
 // loads of HEAT_AHEAD levels are issued before the first of their cells is worked on; the cells keep the order of k.  A lane's sums start
-// from +0.0 and run over k ascending; H = scale * (sum over k of rho_d * r), the scale applied once.  Every lane's numbers go to LDS; a
-// block with no diagnosed lane writes rows of zeros (what the fold would give), any other folds, for member m and each of the eight
-// numbers, the lanes of m in ascending lane order (one thread per number).  k_member_heat_closure_final then folds the blocks' rows.  No
-// atomics, no memset, one fixed order.
+// from +0.0 and run over k ascending; H = scale * (sum over k of rho_d * r), the scale applied once.  Every lane's numbers go to LDS, and
+// the block's rows and k_member_rows_final follow (mw_member.h); a block with no diagnosed lane writes rows of zeros.
 __global__ __launch_bounds__(256) void k_member_heat_closure(int nz, long long plane, int nens, unsigned long long listed, unsigned long long closed,
                                                              double tolerance, double C, double scale, HeatFields F,
                                                              double *__restrict__ partial, double *__restrict__ heating) {
@@ -87,78 +86,8 @@ __global__ __launch_bounds__(256) void k_member_heat_closure(int nz, long long p
   const double aH = fabs(H);
   red[l][0] = q.sr; red[l][1] = q.sa; red[l][2] = q.s2; red[l][3] = q.mx; red[l][4] = H; red[l][5] = aH;
   cnt[l][0] = q.nclosed; cnt[l][1] = q.nskipped;
-  const int rows = nens * HEAT_ROW;
-  if (!__syncthreads_or(mine ? 1 : 0)) {                                       // no diagnosed lane in this block
-    for (int w = l; w < rows; w += 256) partial[(long long)blockIdx.x * rows + w] = 0.0;       // (+0.0 is the int64 0 too)
-    return;
-  }
-  const int shift = (int)(((long long)blockIdx.x * 256) % nens);
-  for (int w = l; w < rows; w += 256) {
-    const int m = w / HEAT_ROW, s = w % HEAT_ROW;
-    const int first = (m - shift + nens) % nens;                               // the block's first lane of member m
-    double *row = partial + ((long long)blockIdx.x * nens + m) * HEAT_ROW;
-    if (s < 2) {
-      long long n = 0;
-      for (int j = first; j < 256; j += nens) n += cnt[j][s];
-      ((long long *)row)[s] = n;
-    } else {
-      const int c = s - 2;
-      const bool is_max = (c == 3 || c == 5);
-      double v = 0.0;
-      for (int j = first; j < 256; j += nens) v = is_max ? (red[j][c] > v ? red[j][c] : v) : v + red[j][c];
-      row[s] = v;
-    }
-  }
-}
-
-// block m = member m; thread l folds the rows of the blocks l, l + 256, ... in ascending order, then threads 0 .. 7 fold the 256 partial
-// results of one number each in ascending l.  counts (nens, 2) = closed, skipped cells; stats (nens, 6).
-__global__ __launch_bounds__(256) void k_member_heat_closure_final(long long nblocks, int nens, const double *__restrict__ partial,
-                                                                   long long *__restrict__ counts, double *__restrict__ stats) {
-#pragma clang fp contract(off)
-  __shared__ double red[256][HEAT_STATS];
-  __shared__ long long cnt[256][2];
-  const int m = blockIdx.x, l = threadIdx.x;
-  long long n0 = 0, n1 = 0;
-  double v[HEAT_STATS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (long long b = l; b < nblocks; b += 256) {
-    const double *row = partial + (b * nens + m) * HEAT_ROW;
-    n0 += ((const long long *)row)[0]; n1 += ((const long long *)row)[1];
-#pragma unroll
-    for (int c = 0; c < HEAT_STATS; c++) v[c] = (c == 3 || c == 5) ? (row[2 + c] > v[c] ? row[2 + c] : v[c]) : v[c] + row[2 + c];
-  }
-  cnt[l][0] = n0; cnt[l][1] = n1;
-#pragma unroll
-  for (int c = 0; c < HEAT_STATS; c++) red[l][c] = v[c];
-  __syncthreads();
-  if (l < 2) {
-    long long n = 0;
-    for (int j = 0; j < 256; j++) n += cnt[j][l];
-    counts[m * 2 + l] = n;
-  } else if (l < HEAT_ROW) {
-    const int c = l - 2;
-    const bool is_max = (c == 3 || c == 5);
-    double x = red[0][c];
-    for (int j = 1; j < 256; j++) x = is_max ? (red[j][c] > x ? red[j][c] : x) : x + red[j][c];
-    stats[m * HEAT_STATS + c] = x;
-  }
-}
-
-static long long heat_blocks(long long ncol, int nens) { return (ncol * nens + 255) / 256; }
-static bool heat_positive_finite(double x) { return x > 0.0 && x - x == 0.0; }
-
-// the bit set of a member list: distinct indices in [0, nens), nens <= 64
-static int heat_member_bits(const char *what, int nens, int n, const int *list, unsigned long long *bits) {
-  if (n < 0 || n > nens) MW_FAIL(std::string("member_heat_closure: ") + what + " holds " + std::to_string(n) + " members, not 0 to nens");
-  if (n > 0 && !list) MW_FAIL("member_heat_closure: null pointer");
-  *bits = 0;
-  for (int j = 0; j < n; j++) {
-    const int e = list[j];
-    if (e < 0 || e >= nens) MW_FAIL("member_heat_closure: member " + std::to_string(e) + " is outside [0, " + std::to_string(nens) + ")");
-    if ((*bits >> e) & 1ull) MW_FAIL("member_heat_closure: member " + std::to_string(e) + " is listed twice in " + what);
-    *bits |= 1ull << e;
-  }
-  return 0;
+  member_rows_fold<HEAT_COUNTS, HEAT_STATS, HEAT_MAX>(nens, mine ? 1 : 0, partial, [&](int j, int s) { return cnt[j][s]; },
+                                                      [&](int j, int c) { return red[j][c]; });
 }
 
 } // namespace mw
@@ -166,8 +95,8 @@ static int heat_member_bits(const char *what, int nens, int n, const int *list, 
 using namespace mw;
 
 extern "C" long long mw_member_heat_closure_workspace_bytes(long long ncol, int nens) {
-  if (ncol < 1 || nens < 1 || nens > 64 || (double)ncol * (double)nens > 256.0 * 2147483647.0) return 0;
-  return heat_blocks(ncol, nens) * nens * HEAT_ROW * 8;
+  if (ncol < 1 || nens < 1 || nens > 64 || !member_counts_fit((double)ncol * (double)nens, 256.0)) return 0;
+  return member_plane_blocks(ncol, nens) * nens * (HEAT_COUNTS + HEAT_STATS) * 8;
 }
 
 extern "C" int mw_member_heat_closure(int nz, long long ncol, int nens, int nm, const int *members, int nclosed, const int *closed,
@@ -177,27 +106,27 @@ extern "C" int mw_member_heat_closure(int nz, long long ncol, int nens, int nm, 
   if (nz < 1 || ncol < 1) MW_FAIL("member_heat_closure: nz and ncol must be >= 1");
   if (nens < 1 || nens > 64) MW_FAIL("member_heat_closure: nens must be in [1, 64]");
   if ((double)nz * (double)ncol * (double)nens > 9.0e18) MW_FAIL("member_heat_closure: the fields are too large");
-  if (!heat_positive_finite(dz)) MW_FAIL("member_heat_closure: dz must be positive and finite");
-  if (!heat_positive_finite(dt)) MW_FAIL("member_heat_closure: dt must be positive and finite");
-  if (!(tolerance >= 0.0 && tolerance - tolerance == 0.0)) MW_FAIL("member_heat_closure: tolerance must be finite and >= 0");
-  if (!heat_positive_finite(lv) || !heat_positive_finite(cp_d)) MW_FAIL("member_heat_closure: lv and cp_d must be positive and finite");
+  if (!positive_finite(dz)) MW_FAIL("member_heat_closure: dz must be positive and finite");
+  if (!positive_finite(dt)) MW_FAIL("member_heat_closure: dt must be positive and finite");
+  if (!finite_nonnegative(tolerance)) MW_FAIL("member_heat_closure: tolerance must be finite and >= 0");
+  if (!positive_finite(lv) || !positive_finite(cp_d)) MW_FAIL("member_heat_closure: lv and cp_d must be positive and finite");
   unsigned long long listed = 0, closes = 0;
-  if (heat_member_bits("members", nens, nm, members, &listed)) return 1;
-  if (heat_member_bits("closed", nens, nclosed, closed, &closes)) return 1;
-  for (int e = 0; e < nens; e++)
-    if (((closes & ~listed) >> e) & 1ull) MW_FAIL("member_heat_closure: member " + std::to_string(e) + " is in closed but not in members (a closed member is a diagnosed member)");
+  if (member_bits("member_heat_closure", "members", nens, nm, members, &listed)) return 1;
+  if (member_bits("member_heat_closure", "closed", nens, nclosed, closed, &closes)) return 1;
+  if (member_subset("member_heat_closure", "closed", "members", closes, listed, nens)) return 1;
   if (!temp || !rho_d || !rho_v || !before2 || !workspace || !counts || !stats) MW_FAIL("member_heat_closure: null pointer");
   if (!before2[0] || !before2[1]) MW_FAIL("member_heat_closure: null field");
   if (temp == rho_d || temp == rho_v || temp == before2[0] || temp == before2[1]) MW_FAIL("member_heat_closure: temp must not be one of the arrays that are only read");
-  if ((double)ncol * (double)nens > 256.0 * 2147483647.0) MW_FAIL("member_heat_closure: the fields are too large");
+  if (member_plane_limit("member_heat_closure", ncol, nens)) return 1;
   if (mw_device_count() < 1) MW_FAIL("no HIP device available: libmw_cdna4 has no CPU fallback");
   const HeatFields F = {temp, rho_d, rho_v, before2[0], before2[1]};
   hipStream_t st = (hipStream_t)stream;
-  const long long plane = ncol * nens, blocks = heat_blocks(ncol, nens);
+  const long long plane = ncol * nens, blocks = member_plane_blocks(ncol, nens);
   hipLaunchKernelGGL(k_member_heat_closure, dim3((unsigned)blocks), dim3(256), 0, st, nz, plane, nens, listed, closes, tolerance, lv / cp_d,
                      cp_d * dz / dt, F, (double *)workspace, heating);
   MW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_member_heat_closure_final, dim3((unsigned)nens), dim3(256), 0, st, blocks, nens, (const double *)workspace, counts, stats);
+  hipLaunchKernelGGL((k_member_rows_final<HEAT_COUNTS, HEAT_STATS, HEAT_MAX>), dim3((unsigned)nens), dim3(256), 0, st, blocks, nens,
+                     (const double *)workspace, counts, stats);
   MW_LAUNCH_CHECK();
   return 0;
 }

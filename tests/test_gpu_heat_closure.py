@@ -80,7 +80,10 @@ def recipe(nz, ncol, nens, seed):
     return ta, rd, rva, tb, rvb, planted
 
 
-SHAPES = [(1, 1, 1), (2, 1, 3), (3, 65, 2), (4, 64, 4), (5, 7, 64), (8, 255, 1), (9, 64, 4), (9, 257, 1), (37, 257, 3)]
+# the last shape: 65,538 plane elements are 257 blocks, the smallest plane at which a thread of the final kernel (thread 0: block rows 0
+# and 256) folds two rows; five levels are one look-ahead group and a tail.  Block 256 holds members 1 and 2 of the last column.
+STRIDE = (5, 21846, 3)
+SHAPES = [(1, 1, 1), (2, 1, 3), (3, 65, 2), (4, 64, 4), (5, 7, 64), (8, 255, 1), (9, 64, 4), (9, 257, 1), (37, 257, 3), STRIDE]
 _CASES = {}
 
 
@@ -112,6 +115,8 @@ def test_bit_for_bit(mw, shape):
     assert same_bits(got["heating"], want["heating"])
     assert same_bits(got["stats"][:, 3], want["max_r"]) and same_bits(got["stats"][:, 5], want["max_h"])
     assert same_bits(got["stats"], ref.kernel_order_stats(want["lanes"]))
+    if shape == STRIDE:                                                         # row 256 is not a row of zeros: the loop's second turn adds something
+        assert np.all(want["lanes"][-1, 1:, 1:4] > 0.0)
     r = np.where(np.isfinite(want["r"]), want["r"], 0.0)
     listed = np.zeros(nens, dtype=bool)
     listed[members] = True

@@ -131,21 +131,44 @@ def recipe(nz, ncol, nens, seed):
     return after, wb, planted
 
 
-SHAPES = [(1, 1, 1), (2, 1, 3), (3, 65, 2), (4, 64, 4), (5, 7, 64), (8, 255, 1), (9, 64, 4), (9, 257, 1), (37, 257, 3)]
+def grid_recipe(nz, ncol, nens, dz, seed, last_gains=False):
+    """(after, w_before) on the 2^-10 grid (dz a power of two): every W and every partial sum of the excess is exact.  last_gains: every
+    cell of the last column gains 2^-4, eight times what any other cell can."""
+    rng = np.random.default_rng(seed)
+    before = [rng.integers(0, 64, (nz, ncol, nens)) / 1024.0 for _ in range(3)]
+    after = [q + rng.integers(-8, 9, q.shape).clip(-q * 1024.0, None) / 1024.0 for q in before]
+    if last_gains:
+        for q, b in zip(after, before):
+            q[:, -1] = b[:, -1] + 0.0625
+    return after, ref.column_water(*before, dz)
+
+
+# the last shape: 65,538 plane elements are 257 blocks, the smallest plane at which a thread of the final kernel (thread 0: block rows 0
+# and 256) folds two rows; five levels are one look-ahead group and a tail.  Its fields are grid_recipe's, so the sum is held exactly,
+# and its last column (of block 256) gains the most: row 256 carries a count, a part of the sum and the maximum of the last member.
+STRIDE = (5, 21846, 3)
+SHAPES = [(1, 1, 1), (2, 1, 3), (3, 65, 2), (4, 64, 4), (5, 7, 64), (8, 255, 1), (9, 64, 4), (9, 257, 1), (37, 257, 3), STRIDE]
 _CASES = {}
+
+
+def dz_of(shape):
+    return 128.0 if shape == STRIDE else DZ
 
 
 def case(shape):
     """The recipe, the call's result and the reference's for a shape, computed once and never changed."""
     if shape not in _CASES:
         nz, ncol, nens = shape
-        after, wb, planted = recipe(nz, ncol, nens, seed=sum(shape))
+        if shape == STRIDE:
+            (after, wb), planted = grid_recipe(nz, ncol, nens, dz_of(shape), seed=sum(shape), last_gains=True), {}
+        else:
+            after, wb, planted = recipe(nz, ncol, nens, seed=sum(shape))
         members, accum, fixed = lists_for(nens)
         rng = np.random.default_rng(7)
         precl0, total0 = rng.uniform(1.0, 2.0, (ncol, nens)), rng.uniform(-1.0, 1.0, (ncol, nens))
         dt = 0.5 if nz % 2 else 60.0
-        got = call_fix(after, wb, precl0, total0, members, accum, fixed, 0.0, DZ, dt)
-        want = ref.water_fix(*after, DZ, dt, wb, precl0, total0, members, accum, fixed, 0.0)
+        got = call_fix(after, wb, precl0, total0, members, accum, fixed, 0.0, dz_of(shape), dt)
+        want = ref.water_fix(*after, dz_of(shape), dt, wb, precl0, total0, members, accum, fixed, 0.0)
         _CASES[shape] = (after, wb, planted, got, want, (members, accum, fixed))
     return _CASES[shape]
 
@@ -154,8 +177,8 @@ def case(shape):
 @pytest.mark.parametrize("shape", SHAPES, ids=["x".join(map(str, s)) for s in SHAPES])
 def test_bit_for_bit(mw, shape):
     """nz below, at and above the look-ahead of four and its multiples; planes below, at and above a wavefront and a block; bit 63 of the
-    member mask.  The three fields, precl, rain_total, the excess plane, both counts and the maximum are the reference's bits; a later
-    mw_member_column_water returns the W' that precl was made of."""
+    member mask; 257 blocks (STRIDE), where the sum is the reference's bits too.  The three fields, precl, rain_total, the excess plane,
+    both counts and the maximum are the reference's bits; a later mw_member_column_water returns the W' that precl was made of."""
     import torch
     from miniweatherml_amd import microphysics
     nz, ncol, nens = shape
@@ -182,7 +205,7 @@ def test_bit_for_bit(mw, shape):
         assert int(want["counts"][:, 1].sum()) == 3
     # the bound on the residual, and the state's own column water
     w3 = [torch.from_numpy(got[k]).cuda() for k in "vcr"]
-    w_now = host(microphysics.column_water(w3, nz, ncol, nens, DZ)).reshape(ncol, nens)
+    w_now = host(microphysics.column_water(w3, nz, ncol, nens, dz_of(shape))).reshape(ncol, nens)
     assert same(w_now, want["w_now"])
     live = fix & (wb > 0.0)
     if live.any():
@@ -191,6 +214,10 @@ def test_bit_for_bit(mw, shape):
     assert np.all(np.abs(w_now[fix] - wb[fix]) <= ref.bound(nz, wb[fix]))
     # the sum of the excess: the kernels' order against numpy's, within n * 2^-52 * sum |x| (k_surrogate_sums' yardstick)
     assert np.all(np.abs(got["stats"][:, 0] - want["sum"]) <= ncol * 2.0 ** -52 * np.abs(want["excess"]).sum(axis=0))
+    if shape == STRIDE:                                                         # every order agrees: the second turn of the final kernel's loop too
+        assert same_bits(got["stats"][:, 0], want["sum"]) and np.all(want["counts"][fixed, 0] > 256)
+        assert fix[-1, nens - 1] and want["excess"][-1, nens - 1] == want["max"][nens - 1] == dz_of(shape) * nz * 3 * 0.0625
+        assert np.all(want["sum"] == np.array([float(np.sum(want["excess"][::-1, e])) for e in range(nens)]))      # (exact indeed)
     # members in no list keep every bit; without the excess plane nothing else changes
     idle = [e for e in range(nens) if e not in members and e not in accum]
     rng = np.random.default_rng(7)
@@ -230,10 +257,7 @@ def test_sum_of_excess_where_every_order_agrees(mw):
     """Fields on a 2^-10 grid and dz a power of two: every W and every partial sum of the excess is exact, so any order of the blocks and
     lanes gives the same bits as numpy's."""
     nz, ncol, nens = 6, 700, 3
-    rng = np.random.default_rng(11)
-    before = [rng.integers(0, 64, (nz, ncol, nens)) / 1024.0 for _ in range(3)]
-    after = [q + rng.integers(-8, 9, q.shape).clip(-q * 1024.0, None) / 1024.0 for q in before]
-    wb = ref.column_water(*before, 128.0)
+    after, wb = grid_recipe(nz, ncol, nens, 128.0, seed=11)
     members = accum = fixed = [2, 0, 1]
     z = np.zeros((ncol, nens))
     got = call_fix(after, wb, z, z, members, accum, fixed, 0.0, 128.0, 1.0)
