@@ -416,6 +416,30 @@ typedef struct { int kind, n_in, n_out; float negative_slope; int offset; } mw_p
 int  mw_ponni_forward(const mw_ponni_layer_t *layers, int nlayers, const float *params, int nparams, long long batch,
                       const float *in, float *out, void *stream);
 
+/* A dense surrogate STACK n_in -> H_1 -> ... -> H_L -> 4 on the coupler's fields (no reference counterpart; the reference's training
+ * notebook invites wider and deeper networks than ponni's 5 -> 10 -> 4): L = nhidden in [1, 4] hidden Dense layers of widths[l] in
+ * [1, 64] units, each with a bias and a leaky ReLU of its own slopes[l] >= 0 (x > 0 ? x : slope * x), then Dense(4) with a bias and no
+ * activation.  n_in 5: the features of mw_mlp_forward; n_in 9: those of mw_mlp_stencil_forward (features 5..8 from level
+ * min(nz - 1, k + 1)).  params: HOST fp32, the layers back to back in Keras order -- W (in, out), then b, per Dense: the order of
+ * weights.txt -- and nparams the count the shape implies.  scl_in (n_in, 2), scl_out (4, 2): HOST fp64 [min, max] rows.  form: MW_FORM_*;
+ * the input scaling, the un-scaling, the base of the tendency form and the clip are mw_mlp_forward_form's.  create builds the MFMA operand
+ * images once, uploads them with the parameters to the current device (synchronously) and the handle owns them.  Refused with an error
+ * text, before anything touches the device: a width outside [1, 64], a depth outside [1, 4], n_in other than 5 or 9, a negative or
+ * non-finite slope, nparams other than the shape's count, a scaling row with max == min, an unknown form.
+ * forward: fields DEVICE fp64, level-major (cell (k, col) at k * ncol + col); nz is used by n_in = 9 alone -- for n_in = 5 the field is
+ * nz * ncol flat cells, any count.  With n_in = 9 the four outputs must not overlap any input (an error); with n_in = 5 they may alias
+ * them, as in mw_mlp_forward.  Honours mw_mlp_set_strict: 0 = one fused kernel on v_mfma_f32_16x16x4_f32 (fp32 operands and
+ * accumulation, the weights in LDS, a layer H_in -> H_out at ceil(H_in / 4) * ceil(H_out / 16) MFMAs per 16 cells; 72 B of HBM traffic
+ * per cell); 1 = thread per cell, every layer a plain fp32 loop in index order, no contraction, the quotient form of the scaling.
+ * Asynchronous on `stream`; a cell never influences another cell. */
+typedef struct mw_mlp_stack_s *mw_mlp_stack_t;
+int  mw_mlp_stack_create(mw_mlp_stack_t *s, int n_in, int nhidden, const int *widths, const float *slopes,
+                         const float *params, long long nparams, const double *scl_in, const double *scl_out, int form);
+int  mw_mlp_stack_forward(mw_mlp_stack_t s, int nz, long long ncol, const double *temp, const double *rho_d, const double *rho_v,
+                          const double *rho_c, const double *rho_r, double *temp_out, double *rho_v_out, double *rho_c_out,
+                          double *rho_r_out, void *stream);
+void mw_mlp_stack_destroy(mw_mlp_stack_t s);
+
 /* ---- file output ------------------------------------------------------------ */
 /* A minimal netCDF *classic* writer (mw_netcdf.cpp): the reference writes through PnetCDF with NC_CLOBBER | NC_64BIT_DATA,
  * i.e. the CDF-5 on-disk format, dims x,y,z (+ unlimited t), double variables, no attributes

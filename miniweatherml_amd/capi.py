@@ -228,6 +228,10 @@ SYMBOLS = {
     "mw_surrogate_bank_create_forms": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double),
                                                  C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "mw_surrogate_bank_form": (C.c_int, [C.c_void_p, C.c_int]),
+    "mw_mlp_stack_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                      C.c_longlong, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),
+    "mw_mlp_stack_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong] + [C.c_void_p] * 9 + [C.c_void_p]),
+    "mw_mlp_stack_destroy": (None, [C.c_void_p]),
 }
 
 _lib = None

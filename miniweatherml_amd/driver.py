@@ -17,7 +17,10 @@ The YAML keys are the reference's (sim_time, nens, nx_glob, ny_glob, nz, xlen, y
 out_freq, enable_gravity, file_per_process; keras_weights_h5 / nn_input_scaling / nn_output_scaling for the surrogate).  The
 Keras HDF5 file named by `keras_weights_h5` is read by the library's own reader (mw_h5.cpp = ponni::load_h5_weights); a text export
 (`keras_weights_txt`, tools/export_mlp_weights.sh) is accepted too; without either, the reference's shipped weight file
-(miniweatherml_amd/data/) is used.
+(miniweatherml_amd/data/) is used.  A `keras_weights_txt` file whose comment lines declare a shape (`# stack: 5 32 32 4`, `# slopes: 0.1 0.1`;
+mlp.write_surrogate_stack writes them) is a dense stack of that width and depth: inference_ponni runs it on the fused stack kernel
+ and prints the shape; `surrogate_models:` entries refuse such a file -- banks, committees and members hold the two
+fixed models only.
 
 evaluate_surrogates scores the networks of a YAML list against the Kessler scheme that runs the simulation (surrogate_eval.SurrogateEvaluator):
     surrogate_models:
@@ -489,6 +492,10 @@ def _surrogate_models(entries, yaml_dir):
                     p = here if os.path.exists(here) else os.path.normpath(os.path.join(yaml_dir, p))
                 if not os.path.exists(p):
                     raise FileNotFoundError("ERROR: surrogate model %r: no file %s" % (e["name"], p))
+                if key == "keras_weights_txt" and mlp.stack_header(p) is not None:
+                    raise ValueError("ERROR: surrogate model %r: %s declares a dense stack (`%s`); banks, committees and rollout members hold "
+                                     "the 5 / 9 -> 10 -> 4 models only -- stacks run in inference_ponni only (keras_weights_txt there)"
+                                     % (e["name"], p, mlp.STACK_MARKER))
                 m[key] = p
             elif key.startswith("nn_") and key != "nn_training_domain":    # (optional: without it the scaling rows are the domain)
                 raise KeyError("ERROR: surrogate model %r needs '%s'" % (e["name"], key))
@@ -684,7 +691,17 @@ class InferencePonni(Column):
             for k_yaml, k_arg in (("nn_input_scaling", "in_scaling_txt"), ("nn_output_scaling", "out_scaling_txt")):
                 p = rel(cfg.get(k_yaml))
                 kw[k_arg] = p if p and os.path.exists(p) else None             # else: the shipped tables
-            micro.init(coupler, **kw)
+            head = mlp.stack_header(kw["weights_txt"]) if kw["weights_txt"] and kw["weights_h5"] is None else None
+            if head is not None:                                               # a `# stack:` header: a dense stack of its own shape
+                data = mlp._DATA
+                micro.init(coupler, stack=(kw["weights_txt"], kw["in_scaling_txt"] or os.path.join(data, "kessler_surrogate_input_scaling.txt"),
+                                           kw["out_scaling_txt"] or os.path.join(data, "kessler_surrogate_output_scaling.txt")))
+                info["surrogate_stack"] = {"widths": micro._stack.widths, "slopes": [float(s) for s in micro._stack.stack.slopes]}
+                if not self.quiet and coupler.is_mainproc():
+                    print("inference_ponni: dense stack %s, slopes %s" % (" -> ".join(str(w) for w in micro._stack.widths),
+                                                                          info["surrogate_stack"]["slopes"]), flush=True)
+            else:
+                micro.init(coupler, **kw)
         # the form travels with the files: the single model's, or every committee model's
         info["surrogate_form"] = micro.form if self.committee is None else micro._committee.forms
         if "tendency" in info["surrogate_form"] and not self.quiet and coupler.is_mainproc():     # (a state model prints what it always did)

@@ -13,7 +13,8 @@ from . import capi
 from ._ffi import StatsAndCounts, _field_ptr_array, _ptr, _stream_ptr, grown_workspace
 from .capi import check
 from .coupler import endrun
-from .mlp import OUT4, as_surrogate_model, load_surrogate_model, mlp_forward, mlp_stencil_forward
+from .mlp import (OUT4, MlpStack, SurrogateStack, as_surrogate_model, load_surrogate_model, load_surrogate_stack, mlp_forward,
+                  mlp_stencil_forward)
 from .surrogate_eval import SurrogateBank
 
 
@@ -188,8 +189,12 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
     last_heat_closure = None  # with heat_closure: the StatsAndCounts of the last step, on the device (heat_closure_stats fetches it)
 
     def init(self, coupler, weights_txt=None, in_scaling_txt=None, out_scaling_txt=None, weights_h5=None, committee=None, guard=None,
-             domains=None):
-        """Single-model files: the model's output form is the one its output scaling file declares (self.form: "state" | "tendency";
+             domains=None, stack=None):
+        """stack: a dense stack of any width and depth in place of the two fixed models -- an mlp.SurrogateStack, or the
+        three paths (weights, input scaling, output scaling) that mlp.load_surrogate_stack reads; time_step then runs mlp.MlpStack.forward
+        where it runs mlp_forward otherwise, and online, surface_rain, water_fixer and heat_closure act on the state behind it as for the
+        other models.  A stack brings its own weights: no file argument and no committee beside it.
+        Single-model files: the model's output form is the one its output scaling file declares (self.form: "state" | "tendency";
         mlp.load_surrogate_model).  committee: a list of 1 .. 16 (W1, b1, W2, b2, scl_in, scl_out) tuples of one width (load_surrogate_weights'
         form, the state form) or SurrogateModel tuples with the form last; a committee may mix the forms.  The network's
         result is then the committee's mean (SurrogateBank.committee_apply), and the weight file arguments are not read.  guard
@@ -201,6 +206,17 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
         self._nn_out = None
         self._committee = None
         self._guard_cfg = self._guard = self._guard_box = None
+        self._stack = None
+        if stack is not None:
+            if committee is not None:
+                endrun("Microphysics_Kessler_Surrogate: stack= and committee= exclude each other (a committee's models are 5 / 9 -> 10 -> 4)")
+            if guard is not None or any(k is not None for k in (weights_txt, in_scaling_txt, out_scaling_txt, weights_h5)):
+                endrun("Microphysics_Kessler_Surrogate: a stack brings its own weights and scaling tables: give no file and no guard beside it")
+            if not isinstance(stack, SurrogateStack):
+                stack = load_surrogate_stack(*stack)
+            self._stack = MlpStack(stack, coupler.device)
+            self.form, self.scl_in, self.scl_out = self._stack.stack.form, self._stack.stack.scl_in, self._stack.stack.scl_out
+            return
         if guard is not None:
             if committee is None:
                 endrun("Microphysics_Kessler_Surrogate: a guard needs a committee")
@@ -226,7 +242,9 @@ class Microphysics_Kessler_Surrogate(Microphysics_Kessler):
         dm = coupler.get_data_manager_readwrite()
         temp, rho_d = dm.get("temp"), dm.get("density_dry", readonly=True)
         rho_v, rho_c, rho_r = dm.get("water_vapor"), dm.get("cloud_liquid"), dm.get("precip_liquid")
-        if getattr(self, "_committee", None) is not None:
+        if getattr(self, "_stack", None) is not None:
+            self._nn_out = self._stack.forward(coupler.get_nz(), temp, rho_d, rho_v, rho_c, rho_r, self._nn_out, strict=self.mlp_strict)
+        elif getattr(self, "_committee", None) is not None:
             guarded = getattr(self, "_guard_cfg", None) is not None            # (the guard's scratch holds the result and the range)
             if self._nn_out is None and not guarded:
                 self._nn_out = [torch.empty_like(temp) for _ in range(4)]

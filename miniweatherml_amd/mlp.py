@@ -4,6 +4,8 @@
   load_surrogate_model, SurrogateModel      the same files with the model's output form (no reference counterpart: DESIGN.md 13.9)
   mlp_forward, mlp_stencil_forward          model.forward_batch_parallel with the fused scaling, :176-202
   ponni_forward, _PonniLayer                ponni::create_inference_model / Inference::forward_batch_parallel, :109, :189
+  SurrogateStack, load_surrogate_stack, write_surrogate_stack, stack_from_h5, MlpStack, mlp_stack_forward
+                                            dense stacks of any width and depth (no reference counterpart: DESIGN.md 13.18)
 
 IN5 and OUT4 name the network's five input and four output fields in its order; every module that feeds or scores it takes them here."""
 import collections
@@ -131,7 +133,8 @@ def load_surrogate_model(weights_txt=None, in_scaling_txt=None, out_scaling_txt=
     rows = scl_in.shape[0] if scl_in.shape[1:] == (2,) else -1
     if (rows, nw) not in ((5, 104), (9, 144)):
         endrun("surrogate files: %d input scaling rows with %d weights; expected 5 rows + 104 weights (single-cell model) or 9 rows + 144 "
-               "weights (stencil model)" % (rows if rows >= 0 else scl_in.size // 2, nw))
+               "weights (stencil model).  A dense stack of another shape declares it in a `# stack:` line and is read with "
+               "mlp.load_surrogate_stack" % (rows if rows >= 0 else scl_in.size // 2, nw))
     if weights_h5 is None:
         a = 10 * rows
         W1, b1, W2, b2 = w[:a].reshape(rows, 10).copy(), w[a:a + 10].copy(), w[a + 10:a + 50].reshape(10, 4).copy(), w[a + 50:a + 54].copy()
@@ -255,3 +258,180 @@ def load_surrogate_bank(entries):
     and other keys are ignored) as the list of SurrogateModel tuples that SurrogateBank takes; a model's form is its files'."""
     return [load_surrogate_model(weights_txt=e.get("keras_weights_txt"), in_scaling_txt=e.get("nn_input_scaling"),
                                    out_scaling_txt=e.get("nn_output_scaling"), weights_h5=e.get("keras_weights_h5")) for e in entries]
+
+
+# ---- dense stacks n_in -> H1 -> ... -> HL -> 4 (mw_mlp_stack_*, DESIGN.md 13.18) ----
+# A stack's weights file declares its shape in comment lines ahead of the numbers, which np.loadtxt skips: `# stack: 5 32 32 4` (n_in, the
+# hidden widths, 4) and `# slopes: 0.1 0.1` (one leaky-ReLU slope per hidden layer); the numbers are the layers back to back in Keras
+# order, W (in, out) then b per Dense.  The scaling files are the other models', the form marker included.
+STACK_MARKER, SLOPES_MARKER = "# stack:", "# slopes:"
+STACK_MAX_HIDDEN, STACK_MAX_WIDTH = 4, 64
+SurrogateStack = collections.namedtuple("SurrogateStack", ("layers", "slopes", "scl_in", "scl_out", "form"))
+
+
+def stack_header(weights_txt):
+    """(widths, slopes) that the comment lines ahead of a weights file's numbers declare -- widths: [n_in, H1, .., HL, 4], slopes: a list
+    of L floats or None without a `# slopes:` line -- or None for a file without a `# stack:` line (every file of the two fixed models)."""
+    widths = slopes = None
+    with open(weights_txt) as f:
+        for line in f:
+            t = line.strip()
+            if t and not t.startswith("#"):
+                break
+            try:
+                if t.startswith(STACK_MARKER):
+                    widths = [int(w) for w in t[len(STACK_MARKER):].split()]
+                elif t.startswith(SLOPES_MARKER):
+                    slopes = [float(w) for w in t[len(SLOPES_MARKER):].split()]
+            except ValueError:
+                endrun("%s: the header line %r does not hold numbers" % (weights_txt, t))
+    return None if widths is None else (widths, slopes)
+
+
+def _stack_checked(stack, what):
+    """The stack with float32 (W, b) layers, float32 slopes and float64 scaling tables, its shape checked against the limits of
+    mw_mlp_stack_create (which checks them again: this is where the message names the file or the argument)."""
+    layers, slopes, scl_in, scl_out, form = stack
+    layers = [(np.ascontiguousarray(W, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)) for W, b in layers]
+    slopes = np.ascontiguousarray(slopes, dtype=np.float32).ravel()
+    scl_in, scl_out = np.ascontiguousarray(scl_in, dtype=np.float64), np.ascontiguousarray(scl_out, dtype=np.float64)
+    widths = [layers[0][0].shape[0]] + [b.size for _, b in layers] if layers and layers[0][0].ndim == 2 else []
+    if not widths or len(layers) < 2 or len(layers) > STACK_MAX_HIDDEN + 1 or widths[0] not in (5, 9) or widths[-1] != 4 or \
+            any(not 1 <= w <= STACK_MAX_WIDTH for w in widths[1:-1]):
+        endrun("%s: a stack is n_in (5 or 9) -> 1 to %d hidden layers of 1 to %d units -> 4, got %r" % (what, STACK_MAX_HIDDEN, STACK_MAX_WIDTH, widths))
+    for l, (W, b) in enumerate(layers):
+        if W.shape != (widths[l], widths[l + 1]) or b.shape != (widths[l + 1],):
+            endrun("%s: layer %d holds W %r and b %r, the widths %r need W (%d, %d)" % (what, l, W.shape, b.shape, widths, widths[l], widths[l + 1]))
+    if slopes.size != len(layers) - 1 or not np.all(np.isfinite(slopes)) or np.any(slopes < 0):
+        endrun("%s: one finite slope >= 0 per hidden layer expected (%d), got %r" % (what, len(layers) - 1, slopes.tolist()))
+    if scl_in.shape != (widths[0], 2) or scl_out.shape != (4, 2):
+        endrun("%s: scaling tables (%d, 2) and (4, 2) expected for n_in = %d, got %r and %r" % (what, widths[0], widths[0], scl_in.shape, scl_out.shape))
+    return SurrogateStack(layers, slopes, scl_in, scl_out, FORMS[form_code(form)])
+
+
+def stack_widths(stack):
+    """[n_in, H1, .., HL, 4] of a SurrogateStack."""
+    return [int(np.shape(stack.layers[0][0])[0])] + [int(np.size(b)) for _, b in stack.layers]
+
+
+def load_surrogate_stack(weights_txt, in_scaling_txt, out_scaling_txt):
+    """A SurrogateStack from a weights file with a `# stack:` / `# slopes:` header (write_surrogate_stack's) and the two scaling files;
+    the form is the one the output scaling file declares (read_form).  A missing header, a number count that is not the header's, and
+    scaling rows that are not n_in's are refused with the file's name."""
+    head = stack_header(weights_txt)
+    if head is None:
+        endrun("%s: no `%s n_in H1 .. HL 4` line ahead of the numbers: not a stack's weights file (the two fixed models are read with "
+               "mlp.load_surrogate_model)" % (weights_txt, STACK_MARKER))
+    widths, slopes = head
+    if slopes is None:
+        endrun("%s: no `%s` line ahead of the numbers (one slope per hidden layer)" % (weights_txt, SLOPES_MARKER))
+    if len(widths) < 3 or min(widths) < 1:
+        endrun("%s: `%s` needs n_in, at least one hidden width and 4, all >= 1; it holds %r" % (weights_txt, STACK_MARKER, widths))
+    w = np.atleast_1d(np.loadtxt(weights_txt, dtype=np.float64, comments="#")).astype(np.float32).ravel()
+    need = sum((a + 1) * b for a, b in zip(widths[:-1], widths[1:]))
+    if w.size != need:
+        endrun("%s: the header %r declares %d weights, the file holds %d" % (weights_txt, widths, need, w.size))
+    layers, off = [], 0
+    for a, b in zip(widths[:-1], widths[1:]):
+        layers.append((w[off:off + a * b].reshape(a, b).copy(), w[off + a * b:off + (a + 1) * b].copy()))
+        off += (a + 1) * b
+    scl_in = np.atleast_2d(np.loadtxt(in_scaling_txt, comments="#"))
+    if scl_in.shape != (widths[0], 2):
+        endrun("%s: %d rows of `min max` expected for the %d inputs that %s declares, it holds an array %r"
+               % (in_scaling_txt, widths[0], widths[0], weights_txt, scl_in.shape))
+    scl_out = np.atleast_2d(np.loadtxt(out_scaling_txt, comments="#"))
+    if scl_out.shape != (4, 2):
+        endrun("%s: 4 rows of `min max` expected, it holds an array %r" % (out_scaling_txt, scl_out.shape))
+    return _stack_checked(SurrogateStack(layers, slopes, scl_in, scl_out, read_form(out_scaling_txt)), weights_txt)
+
+
+def write_surrogate_stack(stack, out_dir):
+    """Writes weights.txt (with the header), input_scaling.txt and output_scaling.txt (with the form marker of a tendency model) into
+    out_dir, every number with the digits that restore its bits; returns the three paths in load_surrogate_stack's order."""
+    stack = _stack_checked(stack, "write_surrogate_stack")
+    os.makedirs(out_dir, exist_ok=True)
+    paths = [os.path.join(out_dir, n) for n in ("weights.txt", "input_scaling.txt", "output_scaling.txt")]
+    with open(paths[0], "w") as f:
+        f.write("%s %s\n" % (STACK_MARKER, " ".join(str(w) for w in stack_widths(stack))))
+        f.write("%s %s\n" % (SLOPES_MARKER, " ".join(repr(float(s)) for s in stack.slopes)))     # (a float32 as a double: exact)
+        for W, b in stack.layers:
+            for v in np.concatenate([W.ravel(), b.ravel()]):
+                f.write("%.9e\n" % v)
+    for path, tab, marker in ((paths[1], stack.scl_in, False), (paths[2], stack.scl_out, stack.form == "tendency")):
+        with open(path, "w") as f:
+            if marker:
+                f.write(FORM_MARKER + "\n")
+            for lo, hi in tab:
+                f.write("%.17e %.17e\n" % (lo, hi))
+    return tuple(paths)
+
+
+def stack_from_h5(path, dense_groups, slopes, in_scaling_txt=None, out_scaling_txt=None):
+    """A SurrogateStack from the Dense layers of a Keras HDF5 weight file (load_h5_weights): dense_groups names them in order, e.g.
+    ("dense_6", "dense_7") for the reference's shipped 5 -> 10 -> 4 file; slopes: one per hidden layer.  The scaling files default to the
+    shipped tables; the form is the output scaling file's."""
+    layers = []
+    for gname in dense_groups:
+        grp = "/%s/%s" % (gname, gname)
+        layers.append((load_h5_weights(path, grp, "kernel:0"), load_h5_weights(path, grp, "bias:0")))
+    out_scaling_txt = out_scaling_txt or os.path.join(_DATA, "kessler_surrogate_output_scaling.txt")
+    scl_in = np.atleast_2d(np.loadtxt(in_scaling_txt or os.path.join(_DATA, "kessler_surrogate_input_scaling.txt"), comments="#"))
+    scl_out = np.atleast_2d(np.loadtxt(out_scaling_txt, comments="#"))
+    return _stack_checked(SurrogateStack(layers, slopes, scl_in, scl_out, read_form(out_scaling_txt)), str(path))
+
+
+class MlpStack:
+    """Owner of one mw_mlp_stack_t: the handle is created once (the operand images are built and uploaded to `device` then) and destroyed
+    in close() / __del__."""
+
+    def __init__(self, stack, device):
+        self.stack = _stack_checked(stack, "MlpStack")
+        self.device = torch.device(device)
+        self.widths = stack_widths(self.stack)
+        self._h = C.c_void_p()
+        hidden = (C.c_int * (len(self.widths) - 2))(*self.widths[1:-1])
+        params = np.concatenate([np.concatenate([W.ravel(), b.ravel()]) for W, b in self.stack.layers]).astype(np.float32)
+        fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+        with torch.cuda.device(self.device):
+            check(capi.lib().mw_mlp_stack_create(C.byref(self._h), self.widths[0], len(hidden), hidden, self.stack.slopes.ctypes.data_as(fp),
+                                                 params.ctypes.data_as(fp), params.size, self.stack.scl_in.ctypes.data_as(dp),
+                                                 self.stack.scl_out.ctypes.data_as(dp), form_code(self.stack.form)))
+
+    def forward(self, nz, temp, rho_d, rho_v, rho_c, rho_r, outs=None, strict=0):
+        """mw_mlp_stack_forward on whole coupler arrays (nz, ...); n_in = 5 reads them as flat cells and may write in place."""
+        if self._h is None or not self._h.value:
+            endrun("MlpStack: the handle is closed")
+        if temp.numel() % int(nz) != 0:
+            endrun("mlp_stack_forward: %d cells are not a whole number of columns of nz = %d" % (temp.numel(), nz))
+        if outs is None:
+            outs = [torch.empty_like(temp) for _ in range(4)]
+        with strict_mode(strict), torch.cuda.device(temp.device):
+            rc = capi.lib().mw_mlp_stack_forward(self._h, int(nz), temp.numel() // int(nz), _ptr(temp), _ptr(rho_d), _ptr(rho_v), _ptr(rho_c),
+                                                 _ptr(rho_r), *[_ptr(o) for o in outs], _stream_ptr(temp.device))
+        check(rc)
+        return outs
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None and h.value:
+            capi.lib().mw_mlp_stack_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def mlp_stack_forward(stack_or_handle, nz, temp, rho_d, rho_v, rho_c, rho_r, outs=None, strict=0):
+    """The forward pass of a dense stack on the coupler's fields: stack_or_handle is an MlpStack, or a SurrogateStack, for which a handle
+    is created for this call and destroyed behind it (a loop keeps an MlpStack).  strict = 1: the thread-per-cell kernel in index order."""
+    if isinstance(stack_or_handle, MlpStack):
+        return stack_or_handle.forward(nz, temp, rho_d, rho_v, rho_c, rho_r, outs, strict)
+    h = MlpStack(stack_or_handle, temp.device)
+    try:
+        outs = h.forward(nz, temp, rho_d, rho_v, rho_c, rho_r, outs, strict)
+        torch.cuda.synchronize(temp.device)                                    # the handle's images are freed behind the call
+    finally:
+        h.close()
+    return outs
