@@ -583,6 +583,30 @@ int  mw_surrogate_batch_grad_w(int n_in, const float *params, const float *x, co
 int  mw_surrogate_errors_weighted(long long n, int nsets, const float *pred, const float *y, const float *w, void *workspace, double *out,
                                   void *stream);
 
+/* ---- training of dense stacks (csrc/mw_train_stack.hip) ------------------------------------------- */
+/* The trainer above for the stacks n_in -> H1 -> ... -> HL -> 4 that mw_mlp_stack_create accepts, with the same limits and the same
+ * refusals (n_in 5 or 9, 1 to 4 hidden layers of 1 to 64 units, slopes finite and >= 0: one check serves both): what can be trained can
+ * be run.  widths (nhidden) and slopes (nhidden): HOST.  params, m1, m2: (models, nparams) fp32 DEVICE, per model the layers back to back
+ * in Keras order -- W (in, out), then b, per Dense: the order of mw_mlp_stack_create's params and of a stack's weights.txt.  x (n_in, n),
+ * y (4, n), table, beta1, beta2, eps, epoch, seed, n, batch, stats (models, 2) fp64 and the limits MW_SURROGATE_MAX_BATCH /
+ * MW_SURROGATE_MAX_MODELS: mw_surrogate_train_epoch_v2's.  w (n,) fp32 DEVICE: the samples' weights with the semantics of
+ * mw_surrogate_train_epoch_w, or NULL = unweighted.  One workgroup per model, one launch per epoch, both passes and the weight gradient
+ * on v_mfma_f32_16x16x4_f32; every sum has a fixed order, so a model's bits do not depend on the launch or on `models`.
+ * workspace: DEVICE, 16-byte aligned, mw_stack_train_workspace_bytes(...) bytes (-1 and an error text for a refused shape, models or
+ * batch): per model and sample of a batch one row of activations and deltas.  Its contents mean nothing between calls. */
+long long mw_stack_train_workspace_bytes(int n_in, int nhidden, const int *widths, int models, int batch);
+int  mw_stack_train_epoch(int n_in, int nhidden, const int *widths, const float *slopes, int models, const float *x, const float *y,
+                          const float *w, long long n, int batch, int epoch, unsigned long long seed, float *params, float *m1, float *m2,
+                          const float *table, float beta1, float beta2, float eps, double *stats, void *workspace, void *stream);
+/* The stack's forward pass on a prepared set, in scaled label space: x (n_in, n) fp32 DEVICE -> out (4, n) fp32 DEVICE, params (nparams)
+ * DEVICE.  The trainer's validation and test predictions (mw_ponni_forward's layer kernel stops at 32 units and 10 layers). */
+int  mw_stack_predict(int n_in, int nhidden, const int *widths, const float *slopes, const float *params, long long n, const float *x,
+                      float *out, void *stream);
+/* Test aid: the gradient (nparams) of mean((out - t)^2) (weighted: sum_i w_i mean_o(...) / batch) and loss[0] of ONE batch in identity
+ * order, from the batch routine the epoch kernel runs.  x (n_in, batch), y (4, batch), w (batch) or NULL; workspace for models = 1. */
+int  mw_stack_batch_grad(int n_in, int nhidden, const int *widths, const float *slopes, const float *params, const float *x, const float *y,
+                         const float *w, int batch, float *grad, float *loss, void *workspace, void *stream);
+
 /* ---- surrogate evaluation in the model loop ------------------------------------------------------------- */
 /* A bank of `models` candidate networks of ONE width, scored against what the microphysics really did to a state: the four `Relative diff`
  * prints of microphysics_kessler_ponni.h:266-269 for many models at once, split by output field and by the active / inactive classes of

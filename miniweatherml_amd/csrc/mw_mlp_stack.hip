@@ -21,15 +21,12 @@
 // that one LDS read of an A operand feeds TILES MFMAs.
 // =====================================================================================================
 #include "mw_mlp_net.h"
+#include "mw_stack_shape.h"                                         // the shape limits (MW_STACK_*) and their check
 #include <cmath>
 #include <string>
 #include <vector>
 #include <algorithm>
 
-#define MW_STACK_MAX_HIDDEN 4
-#define MW_STACK_MAX_WIDTH 64
-#define MW_STACK_DENSE (MW_STACK_MAX_HIDDEN + 1)                   // Dense layers of the deepest model
-#define MW_STACK_UB (MW_STACK_MAX_WIDTH / 16)                      // unit blocks of the widest layer
 #define MW_STACK_PAD (64 * (MW_STACK_UB - 1))                      // floats behind the image in LDS: a layer with fewer unit blocks reads (and drops) up to here
 
 namespace mw {
@@ -232,19 +229,8 @@ extern "C" int mw_mlp_stack_create(mw_mlp_stack_t *out, int n_in, int nhidden, c
                                    long long nparams, const double *scl_in, const double *scl_out, int form) {
   if (!out) MW_FAIL("mlp_stack_create: null pointer");
   *out = nullptr;
-  if (n_in != 5 && n_in != 9) MW_FAIL("mlp_stack_create: n_in must be 5 (single cell) or 9 (stencil), got " + std::to_string(n_in));
-  if (nhidden < 1 || nhidden > MW_STACK_MAX_HIDDEN)
-    MW_FAIL("mlp_stack_create: the number of hidden layers must be in [1, " + std::to_string(MW_STACK_MAX_HIDDEN) + "], got " + std::to_string(nhidden));
-  if (!widths || !slopes || !params || !scl_in || !scl_out) MW_FAIL("mlp_stack_create: null pointer");
   long long need = 0;
-  for (int l = 0; l < nhidden; l++) {
-    if (widths[l] < 1 || widths[l] > MW_STACK_MAX_WIDTH)
-      MW_FAIL("mlp_stack_create: hidden layer " + std::to_string(l) + " has " + std::to_string(widths[l]) + " units; a width is in [1, " + std::to_string(MW_STACK_MAX_WIDTH) + "]");
-    if (!(slopes[l] >= 0.f) || std::isinf(slopes[l]))
-      MW_FAIL("mlp_stack_create: the slope of hidden layer " + std::to_string(l) + " must be finite and >= 0");
-    need += (long long)((l ? widths[l - 1] : n_in) + 1) * widths[l];
-  }
-  need += (long long)(widths[nhidden - 1] + 1) * 4;
+  if (stack_shape_check("mlp_stack_create", n_in, nhidden, widths, slopes, !params || !scl_in || !scl_out, &need)) return 1;
   if (nparams != need)
     MW_FAIL("mlp_stack_create: this shape has " + std::to_string(need) + " parameters, nparams is " + std::to_string(nparams));
   for (int i = 0; i < n_in; i++) if (scl_in[2 * i + 1] == scl_in[2 * i]) MW_FAIL("mlp_stack_create: input scaling row " + std::to_string(i) + " has max == min");

@@ -345,18 +345,24 @@ def load_surrogate_stack(weights_txt, in_scaling_txt, out_scaling_txt):
     return _stack_checked(SurrogateStack(layers, slopes, scl_in, scl_out, read_form(out_scaling_txt)), weights_txt)
 
 
+def write_stack_weights(stack, path):
+    """One weights file of a stack: the `# stack:` / `# slopes:` header, then the layers in Keras order, every number with the digits
+    that restore its bits (the trainer's weights_<k>.txt are written with it)."""
+    with open(path, "w") as f:
+        f.write("%s %s\n" % (STACK_MARKER, " ".join(str(w) for w in stack_widths(stack))))
+        f.write("%s %s\n" % (SLOPES_MARKER, " ".join(repr(float(s)) for s in stack.slopes)))     # (a float32 as a double: exact)
+        for W, b in stack.layers:
+            for v in np.concatenate([W.ravel(), b.ravel()]):
+                f.write("%.9e\n" % v)
+
+
 def write_surrogate_stack(stack, out_dir):
     """Writes weights.txt (with the header), input_scaling.txt and output_scaling.txt (with the form marker of a tendency model) into
     out_dir, every number with the digits that restore its bits; returns the three paths in load_surrogate_stack's order."""
     stack = _stack_checked(stack, "write_surrogate_stack")
     os.makedirs(out_dir, exist_ok=True)
     paths = [os.path.join(out_dir, n) for n in ("weights.txt", "input_scaling.txt", "output_scaling.txt")]
-    with open(paths[0], "w") as f:
-        f.write("%s %s\n" % (STACK_MARKER, " ".join(str(w) for w in stack_widths(stack))))
-        f.write("%s %s\n" % (SLOPES_MARKER, " ".join(repr(float(s)) for s in stack.slopes)))     # (a float32 as a double: exact)
-        for W, b in stack.layers:
-            for v in np.concatenate([W.ravel(), b.ravel()]):
-                f.write("%.9e\n" % v)
+    write_stack_weights(stack, paths[0])
     for path, tab, marker in ((paths[1], stack.scl_in, False), (paths[2], stack.scl_out, stack.form == "tendency")):
         with open(path, "w") as f:
             if marker:

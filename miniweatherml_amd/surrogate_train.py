@@ -19,6 +19,9 @@ new values: the labels are (after - before), scaled by the min and max of those 
 file_weights / sample_weights (CLI --file-weights) is Keras' fit(sample_weight=...): the loss of a batch is sum_i w_i mean_o((y - t)^2) / B,
 so that a small file -- a rollout's harvest beside the samples the model came from -- can count for more; group_metrics (CLI
 --group-metrics) reports the validation and test errors of every file on its own.  DESIGN.md section 13.13.
+stack=[32, 32] (CLI --stack 32,32 [--slopes ...]) trains a dense stack n_in -> 32 -> 32 -> 4 instead of the fixed 10-unit model: one to
+four hidden layers of 1 to 64 units, a leaky-ReLU slope per layer, the same fit on csrc/mw_train_stack.hip; the written weights.txt
+carries the `# stack:` header that inference_ponni reads.  DESIGN.md section 13.19.
 """
 import argparse
 import ctypes as C
@@ -131,6 +134,112 @@ def initial_weights(seed, models, stencil=False):
             u = (splitmix64((base + p) & M64) >> 40) * (1.0 / 16777216.0)
             w[m, p] = np.float32(0.1 * u - 0.05)
     return w
+
+
+# ---- dense stacks n_in -> H1 -> ... -> HL -> 4 (csrc/mw_train_stack.hip) ----
+def parse_stack(text, what="--stack", kind=int):
+    """The CLI's --stack 32,32 and --slopes 0.1,0.1: a comma list of numbers."""
+    try:
+        return [kind(t) for t in str(text).split(",")]
+    except ValueError:
+        raise SurrogateTrainError("%s: expected a comma list of numbers such as %s, got %r" % (what, "32,32" if kind is int else "0.1,0.1", text))
+
+
+def stack_shape(stack, slopes=0.1, stencil=False):
+    """(widths [n_in, H1, .., HL, 4], slopes (L,) fp32) of a stack run, or a refusal: 1 to 4 hidden layers of 1 to 64 units, one finite
+    slope >= 0 per hidden layer (one number serves all) -- the limits of mw_mlp_stack_create, so that what is trained can be run."""
+    from .mlp import STACK_MAX_HIDDEN, STACK_MAX_WIDTH
+    try:
+        hidden = [int(w) for w in stack]
+        ok = all(float(w) == int(w) for w in stack)
+    except (TypeError, ValueError):
+        hidden, ok = [], False
+    if not ok:
+        raise SurrogateTrainError("stack: a list of hidden widths such as [32, 32] expected, got %r" % (stack,))
+    if not 1 <= len(hidden) <= STACK_MAX_HIDDEN:
+        raise SurrogateTrainError("stack: the depth (number of hidden layers) must be in [1, %d], got %d" % (STACK_MAX_HIDDEN, len(hidden)))
+    for l, w in enumerate(hidden):
+        if not 1 <= w <= STACK_MAX_WIDTH:
+            raise SurrogateTrainError("stack: hidden layer %d has %d units; a width is in [1, %d]" % (l, w, STACK_MAX_WIDTH))
+    try:
+        sl = np.asarray(slopes, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise SurrogateTrainError("slopes must be numbers, got %r" % (slopes,))
+    if sl.size == 1:                                                       # one number, bare or in a list, serves every layer
+        sl = np.full(len(hidden), float(sl.ravel()[0]))
+    if sl.shape != (len(hidden),):
+        raise SurrogateTrainError("slopes: %d slopes for %d hidden layers (one per hidden layer, or one number for all)" % (sl.size, len(hidden)))
+    if not np.isfinite(sl).all() or (sl < 0).any():
+        raise SurrogateTrainError("slopes: every slope must be finite and >= 0, got %r" % (sl.tolist(),))
+    return [9 if stencil else 5] + hidden + [4], np.ascontiguousarray(sl, dtype=np.float32)
+
+
+def stack_n_params(widths):
+    """The parameter count of a stack: W (in, out) and b per Dense."""
+    return int(sum((a + 1) * b for a, b in zip(widths[:-1], widths[1:])))
+
+
+def stack_layers(widths, slopes):
+    """The mw_ponni_layer_t records (kind, n_in, n_out, negative_slope, offset) of a stack whose parameters lie in Keras order: per Dense
+    a Matvec and a Bias, a Relu behind every hidden one.  _layers(n_in) is the fixed models' (mw_ponni_forward itself stops at 32 units
+    and 10 layers: the stack trainer predicts with mw_stack_predict)."""
+    recs, off = [], 0
+    for l, (a, b) in enumerate(zip(widths[:-1], widths[1:])):
+        recs += [(0, a, b, 0.0, off), (1, b, b, 0.0, off + a * b)]
+        if l < len(widths) - 2:
+            recs.append((2, b, b, float(slopes[l]), 0))
+        off += (a + 1) * b
+    return tuple(recs)
+
+
+def split_stack_weights(w, widths):
+    """[(W (in, out), b (out)), ...] of a flat parameter vector in Keras order."""
+    w, out, off = np.asarray(w), [], 0
+    for a, b in zip(widths[:-1], widths[1:]):
+        out.append((w[off:off + a * b].reshape(a, b), w[off + a * b:off + (a + 1) * b]))
+        off += (a + 1) * b
+    return out
+
+
+def stack_initial_weights(seed, models, widths):
+    """(models, nparams) fp32: Keras' Dense default glorot_uniform -- w = fp32(limit (2 u - 1)), limit = sqrt(6 / (fan_in + fan_out)), u the
+    seeded draw of initial_weights for the parameter's position p in the flat vector -- and zero biases.  A deliberate difference from
+    the fixed models' RandomUniform(-0.05, 0.05), which is what the reference's notebook sets for ITS two layers: a layer of 64 units
+    started that small barely moves, and glorot is what a Keras user who widens the notebook's network gets."""
+    w = np.zeros((models, stack_n_params(widths)), dtype=np.float32)
+    for m in range(models):
+        base = splitmix64(splitmix64((int(seed) + m) & M64) ^ TAG_WEIGHTS)
+        off = 0
+        for a, b in zip(widths[:-1], widths[1:]):
+            limit = np.sqrt(6.0 / (a + b))
+            for p in range(off, off + a * b):
+                u = (splitmix64((base + p) & M64) >> 40) * (1.0 / 16777216.0)
+                w[m, p] = np.float32(limit * (2.0 * u - 1.0))
+            off += (a + 1) * b
+    return w
+
+
+def load_init_stack(init, widths, slopes):
+    """load_init for a stack run: DIR must hold a stack file (`# stack:` header) of the SAME widths and slopes."""
+    from .capi import MWError
+    from .mlp import load_surrogate_stack, stack_header, stack_widths
+    paths = [os.path.join(os.fspath(init), f) for f in ("weights.txt", "input_scaling.txt", "output_scaling.txt")]
+    for path in paths:
+        if not os.path.exists(path):
+            raise SurrogateTrainError("init: no file %s" % path)
+    if stack_header(paths[0]) is None:
+        raise SurrogateTrainError("init: %s holds a fixed model (no `# stack:` header), but the stack %r is trained; a fixed model is "
+                                  "continued without --stack" % (init, list(widths)))
+    try:
+        st = load_surrogate_stack(*paths)
+    except MWError as e:
+        raise SurrogateTrainError("init: %s" % e)
+    have, hs = stack_widths(st), [float(v) for v in st.slopes]
+    if have != list(widths) or hs != [float(v) for v in slopes]:
+        raise SurrogateTrainError("init: %s holds the stack %r with slopes %r, but the stack %r with slopes %r is trained: a warm start "
+                                  "needs the same shape and slopes" % (init, have, hs, list(widths), [float(v) for v in slopes]))
+    w = np.concatenate([np.concatenate([W.ravel(), b.ravel()]) for W, b in st.layers]).astype(np.float32)
+    return w, np.ascontiguousarray(st.scl_in, dtype=np.float64), np.ascontiguousarray(st.scl_out, dtype=np.float64)
 
 
 def split_sizes(n, test_split=0.2, validation_split=0.2):
@@ -250,6 +359,11 @@ def load_init(init, stencil=False):
     for path in paths:
         if not os.path.exists(path):
             raise SurrogateTrainError("init: no file %s" % path)
+    from .mlp import stack_header
+    head = stack_header(paths[0])
+    if head is not None:
+        raise SurrogateTrainError("init: %s holds the dense stack %r, but the fixed %s model is trained (--stack %s continues it)"
+                                  % (init, head[0], "stencil" if stencil else "single-cell", ",".join(str(w) for w in head[0][1:-1])))
     try:
         W1, b1, W2, b2, scl_in, scl_out = load_surrogate_model(weights_txt=paths[0], in_scaling_txt=paths[1], out_scaling_txt=paths[2])[:6]
     except MWError as e:
@@ -440,11 +554,25 @@ def write_outputs(out_dir, weights, scl_in, scl_out, history, all_weights=None, 
     return paths, models
 
 
+def write_stack_outputs(out_dir, weights, widths, slopes, scl_in, scl_out, history, form="state", all_weights=None):
+    """write_outputs for a stack: weights.txt with the `# stack:` / `# slopes:` header, the two scaling files (a tendency model's output
+    file starts with the form marker) -- mlp.write_surrogate_stack's files, which mlp.load_surrogate_stack and inference_ponni read --
+    and history.json; all_weights (models, nparams): also weights_<k>.txt with the same header.  Returns the three paths."""
+    from .mlp import SurrogateStack, write_stack_weights, write_surrogate_stack
+    _check_form(form)
+    mk = lambda w: SurrogateStack(split_stack_weights(np.asarray(w, dtype=np.float32).ravel(), widths), slopes, scl_in, scl_out, form)   # noqa: E731
+    paths = list(write_surrogate_stack(mk(weights), out_dir))
+    for k in range(0 if all_weights is None else len(all_weights)):
+        write_stack_weights(mk(all_weights[k]), os.path.join(out_dir, "weights_%d.txt" % k))
+    with open(os.path.join(out_dir, "history.json"), "w") as f:
+        json.dump(history, f, indent=1)
+    return paths
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the device side
 def _layers(n_in):
-    a = 10 * n_in
-    return ((0, n_in, 10, 0.0, 0), (1, 10, 10, 0.0, a), (2, 10, 10, 0.1, 0), (0, 10, 4, 0.0, a + 10), (1, 4, 4, 0.0, a + 50))
+    return stack_layers((n_in, 10, 4), (0.1,))
 
 
 _LAYERS = _layers(5)
@@ -462,7 +590,7 @@ class Trainer:
     split the same way, for group_sums.  Without the two the trainer calls what it always called."""
 
     def __init__(self, raw_in, raw_out, scl_in, scl_out, n_split, seed=0, split_seed=None, models=1, batch_size=1024, epochs=10,
-                 learning_rate=1e-3, initial=None, form="state", sample_weights=None, groups=None):
+                 learning_rate=1e-3, initial=None, form="state", sample_weights=None, groups=None, stack=None, slopes=0.1):
         import torch
         from . import capi
         self.torch, self.L = torch, capi.lib()
@@ -472,7 +600,12 @@ class Trainer:
         if self.n_in not in (5, 9) or np.asarray(scl_in).shape != (self.n_in, 2):
             raise SurrogateTrainError("Trainer: inputs (n, %d) with a scaling table %r; expected (n, 5) or (n, 9) and as many scaling rows"
                                       % (self.n_in, np.asarray(scl_in).shape))
-        self.npar = NP = 54 + 10 * self.n_in
+        # stack (hidden widths): the dense stack n_in -> stack -> 4 with `slopes` instead of the fixed model (mw_stack_train_epoch)
+        self.widths = self.slopes = None
+        if stack is not None:
+            self.widths, self.slopes = stack_shape(stack, slopes, stencil=self.n_in == 9)
+            self._hidden = (C.c_int * (len(self.widths) - 2))(*self.widths[1:-1])
+        self.npar = NP = 54 + 10 * self.n_in if stack is None else stack_n_params(self.widths)
         self.n_train, self.n_val, self.n_test = n_split
         self.K, self.B, self.seed = int(models), int(batch_size), int(seed)
         self.split_seed = self.seed if split_seed is None else int(split_seed)
@@ -496,7 +629,7 @@ class Trainer:
         self.tstats = self.buf[self.K * NP * 4:self.K * (NP * 4 + 16)].view(torch.float64).view(self.K, 2)
         self.vstats = self.buf[self.K * (NP * 4 + 16):].view(torch.float64).view(self.K, 24)
         if initial is None:
-            w0 = initial_weights(self.seed, self.K, stencil=self.n_in == 9)
+            w0 = initial_weights(self.seed, self.K, stencil=self.n_in == 9) if stack is None else stack_initial_weights(self.seed, self.K, self.widths)
         else:                                                              # a warm start: (K, npar), the moments and the step counter at zero
             w0 = np.ascontiguousarray(initial, dtype=np.float32)
             if w0.shape != (self.K, NP):
@@ -512,6 +645,15 @@ class Trainer:
         self.ws = torch.empty(int(self.L.mw_surrogate_errors_workspace_bytes(self.group)), dtype=torch.uint8, device=dev)
         self.test_out = torch.empty(24, dtype=torch.float64, device=dev)
         self.epoch_no = 0
+        if stack is not None:
+            nb = int(self.L.mw_stack_train_workspace_bytes(self.n_in, len(self._hidden), self._hidden, self.K, self.B))
+            if nb < 0:
+                capi.check(1)
+            self.stack_ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            self.dev_w = torch.empty(NP, dtype=f32, device=dev)            # one model's weights for mw_stack_predict
+
+    def _shape_args(self):
+        return self.n_in, len(self._hidden), self._hidden, self.slopes.ctypes.data_as(C.POINTER(C.c_float))
 
     def _p(self, t):
         return C.c_void_p(t.data_ptr())
@@ -536,6 +678,10 @@ class Trainer:
 
     def _predict(self, w104, x, out):
         from .capi import check
+        if self.widths is not None:
+            self.dev_w.copy_(self.torch.from_numpy(np.ascontiguousarray(w104, dtype=np.float32)))
+            check(self.L.mw_stack_predict(*self._shape_args(), self._p(self.dev_w), x.shape[1], self._p(x), self._p(out), self._stream()))
+            return
         from .mlp import _PonniLayer
         lay = (_PonniLayer * 5)(*[_PonniLayer(*r) for r in _layers(self.n_in)])
         w = np.ascontiguousarray(w104, dtype=np.float32)
@@ -572,7 +718,10 @@ class Trainer:
                 C.c_void_p(self.table.data_ptr() + self.epoch_no * self.steps * 12), NADAM["beta1"], NADAM["beta2"], NADAM["eps"],
                 self._p(self.tstats), self._stream())
         with self.torch.cuda.device(self.device):
-            if self.wsets is None:
+            if self.widths is not None:
+                check(self.L.mw_stack_train_epoch(*self._shape_args(), self.K, self._p(tx), self._p(ty),
+                                                  None if self.wsets is None else self._p(self.wsets["train"]), *tail[:-1], self._p(self.stack_ws), tail[-1]))
+            elif self.wsets is None:
                 check(self.L.mw_surrogate_train_epoch_v2(self.n_in, self.K, self._p(tx), self._p(ty), *tail))
             else:
                 check(self.L.mw_surrogate_train_epoch_w(self.n_in, self.K, self._p(tx), self._p(ty), self._p(self.wsets["train"]), *tail))
@@ -667,7 +816,7 @@ def _metrics(s):
 
 def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test_split=0.2, validation_split=0.2, learning_rate=1e-3,
                     seed=0, models=1, device="cuda:0", split_seed=None, verbose=False, stencil=False, keep_all=False, init=None, form=None,
-                    file_weights=None, sample_weights=None, group_metrics=False):
+                    file_weights=None, sample_weights=None, group_metrics=False, stack=None, slopes=0.1):
     """Trains `models` surrogates (seeds seed .. seed + models - 1; the pre-shuffle / split uses split_seed, default seed) on the samples of
     `sample_files` and returns a dict: per-model `history` (Keras' loss, mean_absolute_error, val_loss, val_mean_absolute_error per
     epoch), `weights` (models, 104) fp32, `best_model` (lowest final val_loss, ties to the lowest index), `test_metrics` of the best model
@@ -696,7 +845,16 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     they compare with any other run.  The result and history.json gain `weighted: True` and `file_weights` (None with sample_weights).
     group_metrics=True (with or without weights) adds `group_metrics`: per file {file, weight, n_train, n_val, n_test, and, unweighted, at
     the best model's final weights: val_loss, val_mean_absolute_error, test_loss and the notebook's three test metrics on that file's
-    samples alone}; a file without a sample in a set has None for that set's numbers.  DESIGN.md 13.13."""
+    samples alone}; a file without a sample in a set has None for that set's numbers.  DESIGN.md 13.13.
+    stack=[32, 32] (CLI --stack 32,32): trains the dense stack n_in -> 32 -> 32 -> 4 instead of the fixed model -- 1 to 4 hidden layers of
+    1 to 64 units, leaky ReLU with `slopes` (one number for all hidden layers, or one per layer; default 0.1), the shapes
+    inference_ponni runs from a `# stack:` weights file.  Every other option works as above; the initial weights are Keras' Dense default
+    (stack_initial_weights), init=DIR needs a stack file of the same shape and slopes, the written weights.txt (and with keep_all
+    weights_<k>.txt) carries the `# stack:` / `# slopes:` header of mlp.write_surrogate_stack, and the result and history.json gain
+    `stack` (the hidden widths) and `slopes`.  `surrogate_models` is not produced: banks take the fixed models only.  DESIGN.md 13.19."""
+    widths = sl = None
+    if stack is not None:
+        widths, sl = stack_shape(stack, slopes, stencil=stencil)
     form = resolve_form(form, init)
     inputs, outputs, meta = read_samples(sample_files, stencil=stencil)
     scl_in, scl_out = data_scaling(inputs, outputs, allow_constant=init is not None, form=form)
@@ -707,7 +865,7 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     initial = domain = None
     if init is not None:
         data_in = scl_in
-        w0, scl_in, scl_out = load_init(init, stencil)                                 # (refuses the other width before anything else)
+        w0, scl_in, scl_out = load_init(init, stencil) if widths is None else load_init_stack(init, widths, sl)   # (refuses another model first)
         domain = training_domain_union(data_in, init_domain(init, data_in.shape[0]))   # this run's samples and all the model saw before
         initial = np.repeat(w0[None, :], int(models), axis=0)
     import torch
@@ -715,7 +873,8 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     raw_in = torch.from_numpy(inputs).to(dev)
     raw_out = torch.from_numpy(outputs).to(dev)
     tr = Trainer(raw_in, raw_out, scl_in, scl_out, n_split, seed, split_seed, models, batch_size, epochs, learning_rate, initial=initial, form=form,
-                 sample_weights=weights, groups=meta["file_index"] if group_metrics else None)
+                 sample_weights=weights, groups=meta["file_index"] if group_metrics else None, stack=None if widths is None else widths[1:-1],
+                 slopes=sl)
     if group_metrics:
         tr.n_groups = len(meta["files"])                                      # (a last file without samples is a group too)
     if verbose:
@@ -767,6 +926,8 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
               "batch_size": int(batch_size), "epochs": int(epochs), "learning_rate": float(learning_rate),
               "inputs": "stencil" if stencil else "single_cell", "form": form}
     result.update({k: meta[k] for k in ("time_step_size", "dx", "dy", "dz", "files")})
+    if widths is not None:
+        result["stack"], result["slopes"] = widths[1:-1], [float(v) for v in sl]
     if init is not None:
         result["init"], result["initial_weights"], result["training_domain"] = os.fspath(init), initial, domain
     if weights is not None:
@@ -783,7 +944,9 @@ def train_surrogate(sample_files, out_dir=None, epochs=10, batch_size=1024, test
     if out_dir is not None:
         js = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in result.items() if k != "weights"}
         js["best_weights"] = w[best].astype(np.float64).tolist()
-        if keep_all:
+        if widths is not None:
+            result["files_written"] = write_stack_outputs(out_dir, w[best], widths, sl, scl_in, scl_out, js, form, w if keep_all else None)
+        elif keep_all:
             result["files_written"], result["surrogate_models"] = write_outputs(out_dir, w[best], scl_in, scl_out, js, all_weights=w,
                                                                                     names=["seed%d" % sd for sd in seeds], form=form)
         else:
@@ -826,18 +989,30 @@ def main(argv=None):
                     "adds to the state in fp64 (with --init DIR the form is DIR's; a state-form DIR is refused)")
     ap.add_argument("--file-weights", default=None, metavar="W,W,...", help="one weight per sample file, in their order (Keras' sample_weight: the "
                     "batch loss is sum w (y - t)^2 / batch size, weights as given; 0 = evaluate the file only)")
+    ap.add_argument("--stack", default=None, metavar="H,H,...", help="train a dense stack n_in -> H -> ... -> 4 (1 to 4 hidden layers of 1 to 64 units) "
+                    "instead of the fixed 10-unit model; inference_ponni runs the written files")
+    ap.add_argument("--slopes", default=None, metavar="S,S,...", help="with --stack: the leaky-ReLU slope of every hidden layer (one number serves "
+                    "all; default 0.1)")
     ap.add_argument("--group-metrics", action="store_true", help="also report validation and test errors of every sample file on its own")
     a = ap.parse_args(argv)
     try:
+        if a.stack is not None and a.committee:
+            raise SurrogateTrainError("--committee with --stack: committees and banks take the two fixed models only; a stack runs in inference_ponni")
+        if a.slopes is not None and a.stack is None:
+            raise SurrogateTrainError("--slopes without --stack: the fixed models' slope is 0.1")
+        slopes = 0.1 if a.slopes is None else parse_stack(a.slopes, "--slopes", float)
         r = train_surrogate(a.files, a.out, a.epochs, a.batch_size, a.test_split, a.validation_split, a.learning_rate, a.seed, a.models,
                             a.device, a.split_seed, verbose=True, stencil=a.stencil, keep_all=a.keep_all,
                             init=a.init, form="tendency" if a.tendency else None,
-                            file_weights=None if a.file_weights is None else parse_file_weights(a.file_weights), group_metrics=a.group_metrics)
+                            file_weights=None if a.file_weights is None else parse_file_weights(a.file_weights), group_metrics=a.group_metrics,
+                            stack=None if a.stack is None else parse_stack(a.stack), slopes=slopes)
     except SurrogateTrainError as e:
         print("ERROR: %s" % e, file=sys.stderr)
         return 2
     print("best model %d (seed %d); wrote %s" % (r["best_model"], r["seeds"][r["best_model"]], ", ".join(r["files_written"])))
-    if a.keep_all:
+    if a.stack is not None:
+        print("a dense stack runs in inference_ponni (keras_weights_txt: the written weights.txt); banks and committees take the fixed models")
+    elif a.keep_all:
         print("surrogate_models:")
         for m in r["surrogate_models"]:
             print("  - {%s}" % ", ".join("%s: %s" % kv for kv in m.items()))
