@@ -440,6 +440,21 @@ int  mw_mlp_stack_forward(mw_mlp_stack_t s, int nz, long long ncol, const double
                           double *rho_r_out, void *stream);
 void mw_mlp_stack_destroy(mw_mlp_stack_t s);
 
+/* A GROUP of 1 .. 32 stacks rolled out as ensemble members (mw_stack_members.hip): mw_surrogate_members_apply for stacks.  create packs
+ * the stacks' MFMA images, kernel tables and parameters into device buffers of the group's own (synchronously, on the current device):
+ * the group does not depend on the handles' lifetime, and n_in 5 and 9, any shapes and both output forms may be mixed.
+ * members_apply: stack j replaces temp, water_vapor, cloud_liquid and precip_liquid of ensemble member members[j] of fields5 = (temp,
+ * density_dry, water_vapor, cloud_liquid, precip_liquid), DEVICE fp64, each (nz, ncol, nens) with the member fastest, IN PLACE and from
+ * that member's own values (n_in = 9: the level above is read as it was); density_dry and every other member keep every bit.  Member
+ * members[j] then holds the bits mw_mlp_stack_forward of stack j stores, out of place, for that member extracted to contiguous arrays --
+ * with mw_mlp_set_strict(1) the bits of its strict form.  Refused with an error text: a member twice or outside [0, nens), a null
+ * pointer, sizes of 9e18 elements or more, no device.  A call allocates nothing and copies nothing; asynchronous on `stream`. */
+typedef struct mw_stack_group_s *mw_stack_group_t;
+int  mw_stack_group_create(mw_stack_group_t *g, int n, const mw_mlp_stack_t *stacks);
+int  mw_stack_group_members_apply(mw_stack_group_t g, const int *members, int nz, long long ncol, int nens, double *const *fields5,
+                                  void *stream);
+void mw_stack_group_destroy(mw_stack_group_t g);
+
 /* ---- file output ------------------------------------------------------------ */
 /* A minimal netCDF *classic* writer (mw_netcdf.cpp): the reference writes through PnetCDF with NC_CLOBBER | NC_64BIT_DATA,
  * i.e. the CDF-5 on-disk format, dims x,y,z (+ unlimited t), double variables, no attributes

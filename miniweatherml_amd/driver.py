@@ -19,8 +19,12 @@ Keras HDF5 file named by `keras_weights_h5` is read by the library's own reader 
 (`keras_weights_txt`, tools/export_mlp_weights.sh) is accepted too; without either, the reference's shipped weight file
 (miniweatherml_amd/data/) is used.  A `keras_weights_txt` file whose comment lines declare a shape (`# stack: 5 32 32 4`, `# slopes: 0.1 0.1`;
 mlp.write_surrogate_stack writes them) is a dense stack of that width and depth: inference_ponni runs it on the fused stack kernel
- and prints the shape; `surrogate_models:` entries refuse such a file -- banks, committees and members hold the two
-fixed models only.
+ and prints the shape; `surrogate_models:` entries refuse such a file -- banks and committees hold the two
+fixed models only.  rollout_surrogates takes stacks in a list of their own, with or without surrogate_models:
+    surrogate_stacks:
+      - {name: wide, keras_weights_txt: out/weights_0.txt, nn_input_scaling: out/input_scaling.txt, nn_output_scaling: out/output_scaling.txt}
+Each is one more member behind the committees', stepped in place by mlp.MlpStackGroup, scored, budgeted, fixed, closed and harvested
+as a model member; surrogate_rollout.json lists them under `stacks`.
 
 evaluate_surrogates scores the networks of a YAML list against the Kessler scheme that runs the simulation (surrogate_eval.SurrogateEvaluator):
     surrogate_models:
@@ -147,7 +151,7 @@ def load_config(path):
         if key in cfg:
             out[key] = str(cfg[key])
     out["_dir"] = os.path.dirname(os.path.abspath(path))
-    for key in ("surrogate_models", "eval_interval", "persistence_member", "harvest", "surrogate_committees", "surface_rain", "training_domain", "eval_domain", "water_fixer", "heat_closure"):    # read by surrogate_config / rollout_config / harvest_config / committee_config / surface_rain_config / training_domain_config / eval_domain_key / water_fixer_config / heat_closure_config alone
+    for key in ("surrogate_models", "surrogate_stacks", "eval_interval", "persistence_member", "harvest", "surrogate_committees", "surface_rain", "training_domain", "eval_domain", "water_fixer", "heat_closure"):    # read by surrogate_config / rollout_config / harvest_config / committee_config / surface_rain_config / training_domain_config / eval_domain_key / water_fixer_config / heat_closure_config alone
         if key in cfg:
             out[key] = cfg[key]
     return out
@@ -200,6 +204,9 @@ def committee_config(cfg):
             raise ValueError("ERROR: committee %r: members must be a non-empty list of model names" % cname)
         members = [str(n) for n in e["members"]]
         for n in members:
+            if n not in names and n in _stack_names(cfg):
+                raise ValueError("ERROR: committee %r names %r, which is a stack of surrogate_stacks: a committee holds the 5 / 9 -> 10 -> 4 "
+                                 "models of surrogate_models only" % (cname, n))
             if n not in names:
                 raise ValueError("ERROR: committee %r names %r, which is no surrogate model (%s)" % (cname, n, ", ".join(names)))
         if len(set(members)) != len(members):
@@ -229,19 +236,82 @@ def evaluation_committees(cfg):
     return committees
 
 
+STACK_KEYS = ("name", "keras_weights_txt", "nn_input_scaling", "nn_output_scaling")
+
+
+def _rollout_models(cfg):
+    """surrogate_config for rollout_surrogates, where a rollout of `surrogate_stacks:` alone needs no `surrogate_models:`: then ([],
+    eval_interval)."""
+    if "surrogate_models" in cfg or "surrogate_stacks" not in cfg:
+        return surrogate_config(cfg)
+    interval = int(cfg.get("eval_interval", 1))
+    if interval < 1:
+        raise ValueError("ERROR: eval_interval must be >= 1")
+    return [], interval
+
+
+def _stack_names(cfg):
+    """The names a `surrogate_stacks:` list declares, unchecked: what committee_config and harvest_config tell a stack by."""
+    entries = cfg.get("surrogate_stacks")
+    return [str(e["name"]) for e in entries if isinstance(e, dict) and "name" in e] if isinstance(entries, list) else []
+
+
+def stack_config(cfg):
+    """The checked `surrogate_stacks:` list of a loaded configuration for rollout_surrogates, [] without the key: entries
+    {name, keras_weights_txt, nn_input_scaling, nn_output_scaling} with the files resolved as those of surrogate_models.  The weights file
+    must carry a `# stack:` header -- a fixed model's file is refused by name -- and the names are unique across models, committees and
+    stacks and neither 'kessler' nor 'persistence'.  Only that experiment calls it."""
+    if "surrogate_stacks" not in cfg:
+        return []
+    entries = cfg["surrogate_stacks"]
+    if not isinstance(entries, list) or not entries:
+        raise ValueError("ERROR: surrogate_stacks must be a non-empty list")
+    taken = [m["name"] for m in _rollout_models(cfg)[0]] + [c["name"] for c in committee_config(cfg)]
+    out = []
+    for e in entries:
+        if not isinstance(e, dict) or "name" not in e:
+            raise KeyError("ERROR: every entry of surrogate_stacks needs a 'name'")
+        name = str(e["name"])
+        unknown = sorted(set(e) - set(STACK_KEYS), key=str)
+        if unknown:
+            raise ValueError("ERROR: unknown key(s) %s in surrogate stack %r (known: %s)" % (", ".join(map(repr, unknown)), name, ", ".join(STACK_KEYS)))
+        if name in ("kessler", "persistence"):
+            raise ValueError("ERROR: 'kessler' and 'persistence' name members of their own: no surrogate stack may be called so")
+        if name in taken:
+            raise ValueError("ERROR: surrogate stack %r has the name of a surrogate model, a committee or another stack: names are unique across "
+                             "surrogate_models, surrogate_committees and surrogate_stacks" % name)
+        taken.append(name)
+        s = {"name": name}
+        for key in STACK_KEYS[1:]:
+            if key not in e:
+                raise KeyError("ERROR: surrogate stack %r needs '%s'" % (name, key))
+            p = str(e[key])
+            if not os.path.isabs(p):
+                here = os.path.normpath(os.path.join(os.getcwd(), p))
+                p = here if os.path.exists(here) else os.path.normpath(os.path.join(cfg["_dir"], p))
+            if not os.path.exists(p):
+                raise FileNotFoundError("ERROR: surrogate stack %r: no file %s" % (name, p))
+            if key == "keras_weights_txt" and mlp.stack_header(p) is None:
+                raise ValueError("ERROR: surrogate stack %r: %s carries no `%s` header: it is a fixed model's file, which belongs in "
+                                 "surrogate_models" % (name, p, mlp.STACK_MARKER))
+            s[key] = p
+        out.append(s)
+    return out
+
+
 def rollout_config(cfg):
-    """(models, eval_interval, persistence, nens) of a loaded configuration for rollout_surrogates: surrogate_config's list and interval,
-    `persistence_member` (default true) and the member count they imply -- Kessler, one member per model, one per committee of
-    `surrogate_committees` (committee_config), persistence.  A `nens` in the YAML that disagrees is an error, and so are more members than
-    the dycore steps in one call."""
+    """(models, eval_interval, persistence, nens) of a loaded configuration for rollout_surrogates: surrogate_config's list and interval
+    (no list with `surrogate_stacks:` alone), `persistence_member` (default true) and the member count they imply -- Kessler, one member
+    per model, one per committee of `surrogate_committees` (committee_config), one per stack of `surrogate_stacks` (stack_config),
+    persistence.  A `nens` in the YAML that disagrees is an error, and so are more members than the dycore steps in one call."""
     from . import capi
-    models, interval = surrogate_config(cfg)
+    models, interval = _rollout_models(cfg)
     persistence = cfg.get("persistence_member", True)
     if not isinstance(persistence, bool):
         raise ValueError("ERROR: persistence_member must be true or false")
-    ncom = len(committee_config(cfg))
-    com = (", %d surrogate_committees" % ncom) if ncom else ""
-    nens = 1 + len(models) + ncom + (1 if persistence else 0)
+    ncom, nstk = len(committee_config(cfg)), len(stack_config(cfg))
+    com = ((", %d surrogate_committees" % ncom) if ncom else "") + ((", %d surrogate_stacks" % nstk) if nstk else "")
+    nens = 1 + len(models) + ncom + nstk + (1 if persistence else 0)
     if nens > capi.MW_ROLLOUT_MAX_MEMBERS:
         raise ValueError("ERROR: %d surrogate_models%s%s beside Kessler are %d ensemble members, the dycore steps at most %d"
                          % (len(models), com, " and the persistence member" if persistence else "", nens, capi.MW_ROLLOUT_MAX_MEMBERS))
@@ -288,8 +358,9 @@ def harvest_config(cfg):
     unknown = sorted(set(h) - set(HARVEST_KEYS))
     if unknown:
         raise ValueError("ERROR: unknown key(s) %s in harvest (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(HARVEST_KEYS)))
-    models, eval_interval = surrogate_config(cfg)
-    names = [m["name"] for m in models]
+    models, eval_interval = _rollout_models(cfg)
+    stack_names = _stack_names(cfg)                                            # a stack member is harvested as a model member is
+    names = [m["name"] for m in models] + stack_names
     out = {"interval": h.get("interval", eval_interval), "samples_per_step": h.get("samples_per_step", 50),
            "ratio_active": h.get("ratio_active", 0.5), "seed": h.get("seed"), "max_rainsplit": h.get("max_rainsplit", 64),
            "members": h.get("members", names)}
@@ -317,6 +388,10 @@ def harvest_config(cfg):
         raise ValueError("ERROR: harvest.members names a model twice")
     if "outside" in h and h["outside"] is not False:                        # (false: off, as without the key)
         out["outside"] = harvest_outside_config(h["outside"])
+        listed = [n for n in out["members"] if n in stack_names]
+        if listed:
+            raise ValueError("ERROR: harvest.outside with the stack member(s) %s among harvest.members: the training box is kept for the "
+                             "models of surrogate_models only -- name those in harvest.members" % ", ".join(map(repr, listed)))
     return out
 
 
@@ -494,7 +569,8 @@ def _surrogate_models(entries, yaml_dir):
                     raise FileNotFoundError("ERROR: surrogate model %r: no file %s" % (e["name"], p))
                 if key == "keras_weights_txt" and mlp.stack_header(p) is not None:
                     raise ValueError("ERROR: surrogate model %r: %s declares a dense stack (`%s`); banks, committees and rollout members hold "
-                                     "the 5 / 9 -> 10 -> 4 models only -- stacks run in inference_ponni only (keras_weights_txt there)"
+                                     "the 5 / 9 -> 10 -> 4 models only -- stacks run as `surrogate_stacks:` members of rollout_surrogates and in "
+                                     "inference_ponni only (keras_weights_txt there)"
                                      % (e["name"], p, mlp.STACK_MARKER))
                 m[key] = p
             elif key.startswith("nn_") and key != "nn_training_domain":    # (optional: without it the scaling rows are the domain)
@@ -824,8 +900,9 @@ class EvaluateSurrogates(Column):
 
 
 def rollout_document(experiment, yaml_path, eval_interval, steps, models, scorer, rep, micro, committees=(), domain_blocks=None,
-                     harvest=None, rain_cfg=None, rain=None, water_fixer=None, heat_closure=None):
+                     harvest=None, rain_cfg=None, rain=None, water_fixer=None, heat_closure=None, stacks=()):
     """surrogate_rollout.json as a dict.  rep: the scorer's report; domain_blocks: micro.domain_reports() with `training_domain`;
+    stacks: the checked `surrogate_stacks` list, whose entries gain member, widths, slopes and form;
     harvest: harvest_block's result with a harvester; rain_cfg, rain: the checked `surface_rain` and its RainScorer; water_fixer:
     micro.water_fix_reports() with `water_fixer`; heat_closure: micro.heat_closure_reports() with `heat_closure`.  None: no such block."""
     doc = {"experiment": experiment, "yaml": os.path.abspath(yaml_path), "eval_interval": eval_interval, "steps": steps,
@@ -837,6 +914,9 @@ def rollout_document(experiment, yaml_path, eval_interval, steps, models, scorer
         for c, g in zip(doc["committees"], micro.guard_reports()):
             if g is not None:
                 c["guard"] = g
+    if stacks:                                                                 # (no `domain` block: the report stays with the models and committees)
+        doc["stacks"] = [dict(s, member=micro.stack_members[k], widths=mlp.stack_widths(micro.stacks[k]),
+                              slopes=[float(v) for v in micro.stacks[k].slopes], form=micro.stacks[k].form) for k, s in enumerate(stacks)]
     if domain_blocks is not None:                                              # one block per network-stepped member
         for entry in doc["models"] + doc.get("committees", []):
             entry["domain"] = domain_blocks[entry["member"]]
@@ -861,8 +941,9 @@ class RolloutSurrogates(Column):
         self.rain_cfg = surface_rain_config(cfg)
         self.domain_cfg = training_domain_config(cfg)
         self.committees = committee_config(cfg)
+        self.stacks = stack_config(cfg)
         cfg["surrogate_models"], cfg["eval_interval"], cfg["persistence_member"], cfg["nens"] = rollout_config(cfg)
-        stepped = [m["name"] for m in cfg["surrogate_models"]] + [c["name"] for c in self.committees]
+        stepped = [m["name"] for m in cfg["surrogate_models"]] + [c["name"] for c in self.committees] + [s["name"] for s in self.stacks]
         self.fixer_cfg = water_fixer_config(cfg, stepped)
         self.closure_cfg = heat_closure_config(cfg, ["kessler"] + stepped, stepped)
 
@@ -873,7 +954,8 @@ class RolloutSurrogates(Column):
         self.stencil = {m["name"]: int(w[0].shape[0]) == 9 for m, w in zip(models, bank)}      # a stencil model reads the level above
         micro.init(self.coupler, bank, self.cfg["persistence_member"], [m["name"] for m in models],
                    [(c["name"], c["members"], c["guard"]) if "guard" in c else (c["name"], c["members"]) for c in self.committees],
-                   domains=mlp.load_training_domains(models, bank))
+                   domains=mlp.load_training_domains(models, bank),
+                   stacks=[(s["name"], tuple(s[k] for k in STACK_KEYS[1:])) for s in self.stacks])
         return micro
 
     def setup(self, *args):
@@ -932,7 +1014,7 @@ class RolloutSurrogates(Column):
         rep = scorer.report() if scorer.times else {"times": [], "diverged_at": dict(scorer.diverged_at)}
         blocks = micro.domain_reports() if self.domain_cfg is not None else None
         doc = rollout_document(info["experiment"], yaml_path, self.cfg["eval_interval"], steps, self.cfg["surrogate_models"], scorer, rep, micro,
-                               self.committees, domain_blocks=blocks, rain_cfg=self.rain_cfg, rain=rain,
+                               self.committees, domain_blocks=blocks, rain_cfg=self.rain_cfg, rain=rain, stacks=self.stacks,
                                water_fixer=micro.water_fix_reports() if self.fixer_cfg is not None else None,
                                heat_closure=micro.heat_closure_reports() if self.closure_cfg is not None else None,
                                harvest=harvest_block(self.harvest, self.harvester) if self.harvester is not None else None)

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import capi
-from ._ffi import _ptr, _stream_ptr
+from ._ffi import _field_ptr_array, _ptr, _stream_ptr
 from .capi import check
 from .coupler import endrun
 
@@ -421,6 +421,69 @@ class MlpStack:
         h, self._h = getattr(self, "_h", None), None
         if h is not None and h.value:
             capi.lib().mw_mlp_stack_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+STACK_GROUP_MAX = 32
+
+
+class MlpStackGroup:
+    """Owner of one mw_stack_group_t: 1 to 32 stacks -- SurrogateStack tuples or MlpStack handles, n_in 5 and 9, any
+    shapes and both forms mixed -- packed into device buffers of the group's own on `device`; members_apply rolls them out as ensemble
+    members.  The handle is destroyed in close() / __del__."""
+
+    def __init__(self, stacks, device):
+        self.device = torch.device(device)
+        self._h = None
+        stacks = list(stacks)
+        if not 1 <= len(stacks) <= STACK_GROUP_MAX:
+            endrun("MlpStackGroup: a group holds 1 to %d stacks, got %d" % (STACK_GROUP_MAX, len(stacks)))
+        own = [None if isinstance(s, MlpStack) else MlpStack(s, self.device) for s in stacks]      # handles made for the packing alone
+        handles = [s if o is None else o for s, o in zip(stacks, own)]
+        self.stacks = [h.stack for h in handles]
+        self.widths = [h.widths for h in handles]
+        h = C.c_void_p()
+        try:
+            if any(x._h is None or not x._h.value for x in handles):
+                endrun("MlpStackGroup: a stack's handle is closed")
+            with torch.cuda.device(self.device):
+                check(capi.lib().mw_stack_group_create(C.byref(h), len(handles), (C.c_void_p * len(handles))(*[x._h.value for x in handles])))
+        finally:
+            for o in own:
+                if o is not None:
+                    o.close()
+        self._h = h
+
+    def members_apply(self, nz, members, fields5, strict=0):
+        """mw_stack_group_members_apply: stack j replaces temp and the three water fields of ensemble member members[j] of the coupler's
+        member-fastest arrays fields5 = (temp, density_dry, water_vapor, cloud_liquid, precip_liquid), each (nz, ..., nens), in place, with
+        the bits MlpStack.forward writes for that member's own values (strict = 1: those of its thread-per-cell form)."""
+        if self._h is None or not self._h.value:
+            endrun("MlpStackGroup: the handle is closed")
+        members = [int(m) for m in members]
+        if len(members) != len(self.stacks):
+            endrun("MlpStackGroup.members_apply: %d members for %d stacks" % (len(members), len(self.stacks)))
+        f = fields5[0] if len(fields5) == 5 else None
+        if f is None or f.dim() < 2 or any(t.shape != f.shape or t.device != f.device for t in fields5):
+            endrun("MlpStackGroup.members_apply: five fields of one shape (nz, ..., nens) on one device expected")
+        nens = int(f.shape[-1])
+        n = f.numel() // nens
+        if int(nz) < 1 or n % int(nz) != 0:
+            endrun("MlpStackGroup.members_apply: %d cells per member are not a whole number of columns of nz = %d" % (n, nz))
+        with strict_mode(strict), torch.cuda.device(f.device):
+            rc = capi.lib().mw_stack_group_members_apply(self._h, (C.c_int * len(members))(*members), int(nz), n // int(nz), nens,
+                                                         _field_ptr_array(list(fields5)), _stream_ptr(f.device))
+        check(rc)
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None and h.value:
+            capi.lib().mw_stack_group_destroy(h)
 
     def __del__(self):
         try:

@@ -27,7 +27,7 @@ from .rollout import heat_closure_report, member_heat_closure  # noqa: F401
 from .microphysics import heat_closure_finish  # noqa: F401
 from .rollout import SAMPLE_CLASSES, harvest_outside_report, harvest_thresholds, member_sample_mask_domain  # noqa: F401
 from .mlp import load_training_domain, load_training_domains  # noqa: F401
-from .mlp import (MlpStack, SurrogateStack, load_surrogate_stack, mlp_stack_forward, stack_from_h5, stack_header,  # noqa: F401
+from .mlp import (MlpStack, MlpStackGroup, SurrogateStack, load_surrogate_stack, mlp_stack_forward, stack_from_h5, stack_header,  # noqa: F401
                   stack_widths, write_surrogate_stack)
 from .sampling import DataGenerator, StatisticsGatherer  # noqa: F401
 from .surrogate_eval import (EVAL_CLASSES, EVAL_FIELDS, CommitteeEvaluator, CommitteeGuard, SurrogateBank, SurrogateEvaluator, _sums_to_float,  # noqa: F401

@@ -22,7 +22,7 @@ from .capi import check
 from .coupler import endrun
 from .microphysics import (CP_D, LV, Microphysics_Kessler, column_water, heat_closure_finish, members_copy, surface_rain_finish, water_fix_finish,
                            water_fix_tolerance)
-from .mlp import IN5, OUT4, as_surrogate_model
+from .mlp import IN5, OUT4, MlpStackGroup, SurrogateStack, as_surrogate_model, load_surrogate_stack
 from .ncio import sample_file_append, sample_file_create
 from .sampling import sample_buffers, sample_thresholds
 from .surrogate_eval import (DOMAIN_CLASSES, CommitteeGuard, SurrogateBank, box_json, domain_box, domain_config, finite_or_none, guard_config,  # noqa: F401
@@ -35,21 +35,24 @@ GUARD_FIELDS = OUT4               # the order of a guard's four thresholds
 ROLLOUT_IN5 = IN5                 # fields5 of members_apply and of the teacher
 
 
-def rollout_member_names(model_names, persistence=True, committees=()):
+def rollout_member_names(model_names, persistence=True, committees=(), stacks=()):
     """The fixed roles of a rollout's ensemble members: member 0 is Kessler, members 1 .. K the models of the list in its order, then one
-    member per committee (names of `committees`, in its order), an optional last member persistence (no microphysics).  More members than
-    the dycore steps in one call is an error that names the limit."""
+    member per committee (names of `committees`, in its order), then one per dense stack (names of `stacks`, in its order), an optional
+    last member persistence (no microphysics).  More members than the dycore steps in one call is an error that names the limit."""
     names = [str(n) for n in model_names]
     if len(set(names)) != len(names) or {"kessler", "persistence"} & set(names):
         endrun("rollout: model names must be unique and neither 'kessler' nor 'persistence'")
     cnames = [str(n) for n in committees]
     if len(set(cnames)) != len(cnames) or ({"kessler", "persistence"} | set(names)) & set(cnames):
         endrun("rollout: committee names must be unique and neither a model's name nor 'kessler' nor 'persistence'")
-    members = ["kessler"] + names + cnames + (["persistence"] if persistence else [])
+    snames = [str(n) for n in stacks]
+    if len(set(snames)) != len(snames) or ({"kessler", "persistence"} | set(names) | set(cnames)) & set(snames):
+        endrun("rollout: stack names must be unique and neither a model's nor a committee's name nor 'kessler' nor 'persistence'")
+    members = ["kessler"] + names + cnames + snames + (["persistence"] if persistence else [])
     if len(members) > capi.MW_ROLLOUT_MAX_MEMBERS:
-        endrun("rollout: %d models%s%s beside Kessler are %d ensemble members, the dycore steps at most %d"
-               % (len(names), (", %d committees" % len(cnames)) if cnames else "", " and persistence" if persistence else "", len(members),
-                  capi.MW_ROLLOUT_MAX_MEMBERS))
+        endrun("rollout: %d models%s%s%s beside Kessler are %d ensemble members, the dycore steps at most %d"
+               % (len(names), (", %d committees" % len(cnames)) if cnames else "", (", %d stacks" % len(snames)) if snames else "",
+                  " and persistence" if persistence else "", len(members), capi.MW_ROLLOUT_MAX_MEMBERS))
     return members
 
 
@@ -109,7 +112,7 @@ class Microphysics_Rollout(Microphysics_Kessler):
     def micro_name(self):
         return "rollout"
 
-    def init(self, coupler, models, persistence=True, names=None, committees=(), domains=None):
+    def init(self, coupler, models, persistence=True, names=None, committees=(), domains=None, stacks=()):
         """models: (W1, b1, W2, b2, scl_in, scl_out) tuples as load_surrogate_weights returns them (the state form) or SurrogateModel
         tuples with the form last (load_surrogate_model), single-cell and stencil networks and both forms in any order (self.model_forms: the
         forms by name, in the models' order); names: theirs (default model0, model1, ...).  committees: (name, [model names]) pairs; each is one more member after the
@@ -123,7 +126,12 @@ class Microphysics_Rollout(Microphysics_Kessler):
         without the guard.
         domains: None, or per model None or its training-domain table (mlp.load_training_domain), handed to every
         domain_box this object calls -- the report's boxes and the domain guards' -- in place of the model's scaling rows.
-        The coupler must have 1 + len(models) + len(committees) (+ 1 with persistence) members."""
+        stacks: (name, SurrogateStack or its three paths in load_surrogate_stack's order) pairs, dense stacks of any shape, n_in and form
+        (DESIGN.md 13.20): each is one more member after the committees' -- member 1 + len(models) + len(committees) + s -- replaced in
+        place from its own state, all of them by ONE MlpStackGroup.members_apply call per step behind the banks' loop.  surface_rain,
+        water_fixer, heat_closure and the harvester treat a stack member as a model member; the training_domain report and a guard's
+        domain stay with the fixed models and the committees, and a committee that names a stack is refused.
+        The coupler must have 1 + len(models) + len(committees) + len(stacks) (+ 1 with persistence) members."""
         models = [as_surrogate_model(m) for m in models]
         self.model_forms = [m.form for m in models]
         names = ["model%d" % k for k in range(len(models))] if names is None else [str(n) for n in names]
@@ -133,13 +141,17 @@ class Microphysics_Rollout(Microphysics_Kessler):
         if len({g["max_rainsplit"] for g in guards if g is not None}) > 1:
             endrun("Microphysics_Rollout: the guarded committees share one columns-teacher call per step: give them one max_rainsplit")
         committees = [(str(c[0]), [str(n) for n in c[1]]) for c in committees]
-        self.member_names = rollout_member_names(names, persistence, [c[0] for c in committees])
+        stacks = [(str(s[0]), s[1] if isinstance(s[1], SurrogateStack) else load_surrogate_stack(*s[1])) for s in stacks]
+        self.member_names = rollout_member_names(names, persistence, [c[0] for c in committees], [s[0] for s in stacks])
         self.persistence = bool(persistence)
         if coupler.get_nens() != len(self.member_names):
-            endrun("Microphysics_Rollout: %d models%s%s beside Kessler need nens = %d, the coupler has %d"
-                   % (len(models), (", %d committees" % len(committees)) if committees else "", " and persistence" if persistence else "",
-                      len(self.member_names), coupler.get_nens()))
+            endrun("Microphysics_Rollout: %d models%s%s%s beside Kessler need nens = %d, the coupler has %d"
+                   % (len(models), (", %d committees" % len(committees)) if committees else "", (", %d stacks" % len(stacks)) if stacks else "",
+                      " and persistence" if persistence else "", len(self.member_names), coupler.get_nens()))
         for cname, cmodels in committees:
+            for sname, _ in stacks:
+                if sname in cmodels:
+                    endrun("Microphysics_Rollout: committee %r names the stack %r: a committee holds the two fixed models only" % (cname, sname))
             if not 1 <= len(cmodels) <= capi.MW_COMMITTEE_MAX_MODELS:
                 endrun("Microphysics_Rollout: committee %r has %d models, a committee has 1 to %d" % (cname, len(cmodels), capi.MW_COMMITTEE_MAX_MODELS))
             if len(set(cmodels)) != len(cmodels) or any(n not in names for n in cmodels):
@@ -162,6 +174,10 @@ class Microphysics_Rollout(Microphysics_Kessler):
             in_bank = [k for k, m in enumerate(models) if np.shape(m[0])[0] == w]
             self.committees.append((self.banks[widths.index(w)][0], [in_bank.index(names.index(n)) for n in cmodels], 1 + len(models) + ci))
         self.guards = guards                                                   # per committee: the checked guard or None
+        # the dense stacks: one group, one members_apply call per step for all of them; their members follow the committees'
+        self.stack_names, self.stacks = [s[0] for s in stacks], [s[1] for s in stacks]
+        self.stack_members = [1 + len(models) + len(committees) + k for k in range(len(stacks))]
+        self.stack_group = MlpStackGroup(self.stacks, coupler.device) if stacks else None
         self._models, self._model_names, self._committee_names = models, names, committees
         if domains is not None and len(domains) != len(models):
             endrun("Microphysics_Rollout: %d domains for %d models (one per model, None where it has none)" % (len(domains), len(models)))
@@ -220,6 +236,8 @@ class Microphysics_Rollout(Microphysics_Kessler):
         for bank, members in self.banks:
             bank.strict = self.mlp_strict
             bank.members_apply(nz, members, [temp, rho_d, rho_v, rho_c, rho_r])
+        if getattr(self, "stack_group", None) is not None:                     # every stack member in one call
+            self.stack_group.members_apply(nz, self.stack_members, [temp, rho_d, rho_v, rho_c, rho_r], strict=self.mlp_strict)
         guards = getattr(self, "guards", None) or [None] * len(getattr(self, "committees", ()))
         guarded = [ci for ci, g in enumerate(guards) if g is not None]
         in5 = [temp, rho_d, rho_v, rho_c, rho_r]

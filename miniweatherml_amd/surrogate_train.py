@@ -1011,7 +1011,13 @@ def main(argv=None):
         return 2
     print("best model %d (seed %d); wrote %s" % (r["best_model"], r["seeds"][r["best_model"]], ", ".join(r["files_written"])))
     if a.stack is not None:
-        print("a dense stack runs in inference_ponni (keras_weights_txt: the written weights.txt); banks and committees take the fixed models")
+        print("a dense stack runs in inference_ponni (keras_weights_txt: the written weights.txt) and as a `surrogate_stacks:` member of "
+              "rollout_surrogates; banks and committees take the fixed models")
+        if a.keep_all:                                                         # ready to paste into a rollout_surrogates YAML
+            print("surrogate_stacks:")
+            for k, sd in enumerate(r["seeds"]):
+                print("  - {name: seed%d, keras_weights_txt: %s, nn_input_scaling: %s, nn_output_scaling: %s}"
+                      % (sd, os.path.join(os.path.dirname(r["files_written"][0]), "weights_%d.txt" % k), r["files_written"][1], r["files_written"][2]))
     elif a.keep_all:
         print("surrogate_models:")
         for m in r["surrogate_models"]:
