@@ -453,6 +453,20 @@ typedef struct mw_stack_group_s *mw_stack_group_t;
 int  mw_stack_group_create(mw_stack_group_t *g, int n, const mw_mlp_stack_t *stacks);
 int  mw_stack_group_members_apply(mw_stack_group_t g, const int *members, int nz, long long ncol, int nens, double *const *fields5,
                                   void *stream);
+/* The group scored against the truth fields (mw_stack_eval.hip): mw_surrogate_eval for stacks.  in5 = (temp,
+ * density_dry, water_vapor, cloud_liquid, precip_liquid) before the microphysics call and truth4 = (temp, water_vapor, cloud_liquid,
+ * precip_liquid) after it: level-major contiguous (nz, ncol) DEVICE fp64, only read.  out (n + 1, 2, 4, 4) DEVICE fp64 = [stack |
+ * persistence][inactive, active][field][sum d, sum |d|, sum d^2, max |d|] with mw_surrogate_eval's classes and statistics, row j the
+ * j-th stack in the order given to mw_stack_group_create, row n persistence (prediction = input); counts DEVICE int64 [2]: the cells per
+ * class.  Stack j's prediction at a cell is bit for bit what mw_mlp_stack_forward stores there out of place (with mw_mlp_set_strict(1):
+ * its strict form), and no prediction reaches memory.  A row depends on (nz, ncol) and the stack alone, not on the group: fixed
+ * reduction order, no floating-point atomics, NaN reaches the sums and the maximum of its class.  workspace: DEVICE, 8-byte aligned,
+ * mw_stack_group_eval_workspace_bytes(g, nz, ncol) bytes (0: arguments out of range).  Refused with an error text, nothing launched and
+ * out / counts untouched: a null handle, pointer or field, nz or ncol below 1, more column tiles than an int holds, sizes of 9e18
+ * elements or more.  A call allocates nothing and copies nothing; asynchronous on `stream`. */
+long long mw_stack_group_eval_workspace_bytes(mw_stack_group_t g, int nz, long long ncol);
+int  mw_stack_group_eval(mw_stack_group_t g, int nz, long long ncol, const double *const *in5, const double *const *truth4,
+                         double *out, long long *counts, void *workspace, void *stream);
 void mw_stack_group_destroy(mw_stack_group_t g);
 
 /* ---- file output ------------------------------------------------------------ */

@@ -1,15 +1,18 @@
 // =====================================================================================================
 // mw_mlp_stack.h -- what the units that run a dense surrogate stack share (mw_mlp_stack.hip: the handle and mw_mlp_stack_forward on
-// level-major fields; mw_stack_members.hip: groups of stacks as ensemble members on the member-fastest layout): the kernels' parameter
-// struct, the leaky ReLU, one Dense layer of MFMA tiles from LDS images, the host's image builder and the handle itself.  Only inline
+// level-major fields; mw_stack_members.hip: groups of stacks as ensemble members on the member-fastest layout; mw_stack_eval.hip: groups
+// of stacks scored against the truth fields): the kernels' parameter struct, the leaky ReLU, one Dense layer of MFMA tiles from LDS
+// images, the cell of a group's kernels (stack_cells), the host's image builder, the group's lists and the handles.  Only inline
 // functions, templates and plain structs: every kernel is emitted from one unit.  The tile layout is described in mw_mlp_stack.hip.
 // =====================================================================================================
 #pragma once
 #include "mw_mlp_net.h"
 #include "mw_stack_shape.h"                                         // the shape limits (MW_STACK_*) and their check
+#include <algorithm>
 #include <vector>
 
 #define MW_STACK_PAD (64 * (MW_STACK_UB - 1))                      // floats behind the image in LDS: a layer with fewer unit blocks reads (and drops) up to here
+#define MW_STACK_EVAL_RED 4096                                     // bytes of static LDS of k_stack_eval's tail: red[stack 4][slot 4][group 4][8] doubles
 
 namespace mw {
 
@@ -79,10 +82,106 @@ static void stack_images(std::vector<float> &img, const float *W, const float *b
     for (int r = 0; r < 16; r++) { const int u = unit_at(ob, r); img.push_back(u < n_o ? b[u] : 0.f); }
 }
 
+// ---- what the units that run a GROUP of stacks share (mw_stack_members.hip: rollout members; mw_stack_eval.hip: the scorer) ----
+#define MW_STACK_GROUP_MAX 32                                       // stacks of a group = members a call can address
+#define MW_STACK_GROUP_LDS 65536                                    // bytes of dynamic LDS a workgroup's images may take together
+
+struct StackRow { StackP P; int form, img_off, par_off, pad_; };   // img_off / par_off: floats, in the group's packed images / parameters
+struct StackMap { int member[MW_STACK_GROUP_MAX]; };
+
+// a lane's scaling constants of one stack: feature g, feature f1 (4 + g, or 4), feature 8, output g
+struct StackLane { double imin0, irng0, imin1, irng1, imin2, irng2, omin, orng; };
+
+// TILES tiles of one stack from raw features: x0 = feature g, x1 = feature 4 + g (n_in = 5: rho_r in group 0), x2 = feature 8 (group 0
+// of n_in = 9).  k_mlp_stack's statements between its loads and its stores; every lane of the wave calls it (the rotate).
+template <int TILES, bool N9>
+__device__ __forceinline__ void stack_cells(double (&y)[TILES], const StackP *P, const float *img, const StackLane &S, bool tend, int lane, int g,
+                                            const double (&x0)[TILES], const double (&x1)[TILES], const double (&x2)[TILES]) {
+#pragma clang fp contract(off)
+  const bool has1 = N9 || g == 0, has2 = N9 && g == 0;
+  const int last = P->nl - 1;
+  f32x4 a[MW_STACK_UB][TILES];
+  double base[TILES];
+#pragma unroll
+  for (int u = 0; u < TILES; u++) {
+    a[0][u] = (f32x4){net_scaled(x0[u], S.imin0, S.irng0), has1 ? net_scaled(x1[u], S.imin1, S.irng1) : 0.f, has2 ? net_scaled(x2[u], S.imin2, S.irng2) : 0.f, 0.f};
+    base[u] = 0.0;
+    if (tend) { const double b = net5_rotate_base(g, x0[u], x1[u]); base[u] = g == 0 ? x0[u] : b; }      // (wave-uniform)
+  }
+  for (int l = 0; l < last; l++) {                                        // the hidden layers
+    f32x4 d[MW_STACK_UB][TILES];
+    const int nob = P->nob[l];
+    const float slope = P->slope[l];
+    stack_dense<TILES, MW_STACK_UB>(d, a, img + P->aoff[l], img + P->boff[l], P->nk[l], nob, lane, g);
+#pragma unroll
+    for (int ob = 0; ob < MW_STACK_UB; ob++) {
+      if (ob < nob) {
+#pragma unroll
+        for (int u = 0; u < TILES; u++)
+#pragma unroll
+          for (int r = 0; r < 4; r++) a[ob][u][r] = leaky_slope(d[ob][u][r], slope);
+      }
+    }
+  }
+  f32x4 o[1][TILES];                                                      // Dense(4): output g in register 0 of group g
+  stack_dense<TILES, 1>(o, a, img + P->aoff[last], img + P->boff[last], P->nk[last], 1, lane, g);
+#pragma unroll
+  for (int u = 0; u < TILES; u++) {
+    double v = (double)o[0][u][0] * S.orng + S.omin;
+    if (tend) v = base[u] + v;
+    if (g != 0) v = fmax(0.0, v);
+    y[u] = v;
+  }
+}
+
+// the scaling constants of lane group g of one stack (the divisions are k_mlp_stack's)
+template <bool N9>
+__device__ __forceinline__ StackLane stack_lane(const StackP *P, int g) {
+  const int f1 = (N9 || g == 0) ? 4 + g : 4;
+  StackLane S;
+  S.imin0 = P->in_min[g]; S.irng0 = 1.0 / P->in_rng[g]; S.imin1 = P->in_min[f1]; S.irng1 = 1.0 / P->in_rng[f1];
+  S.imin2 = N9 ? P->in_min[8] : 0.0; S.irng2 = N9 ? 1.0 / P->in_rng[8] : 1.0;
+  S.omin = P->out_min[g]; S.orng = P->out_rng[g];
+  return S;
+}
+
+// one list of the group: rows [r0, r0 + n) of the table
+struct StackList {
+  int r0, n, mpb;
+  size_t lds;                                                             // bytes of dynamic LDS: the largest workgroup's images + pads
+  bool anyt;
+};
+
+// the largest mpb of 4, 2, 1 (at most apply_slot's rule for n stacks) for which every workgroup's images + pads fit `budget` bytes
+inline void stack_list_plan(StackList &L, const std::vector<StackRow> &rows, size_t budget = MW_STACK_GROUP_LDS) {
+  L.mpb = 1; L.lds = 0;
+  if (L.n < 1) return;
+  for (int mpb = L.n >= 3 ? 4 : L.n; mpb >= 1; mpb /= 2) {
+    size_t worst = 0;
+    for (int m0 = 0; m0 < L.n; m0 += mpb) {
+      size_t bytes = 0;
+      for (int j = m0; j < std::min(L.n, m0 + mpb); j++) bytes += sizeof(float) * (size_t)(rows[(size_t)(L.r0 + j)].P.nimg + MW_STACK_PAD);
+      worst = std::max(worst, bytes);
+    }
+    L.mpb = mpb; L.lds = worst;
+    if (worst <= budget) return;
+  }
+}
+
 } // namespace mw
 
 struct mw_mlp_stack_s {
   mw::StackP P;
   int form;
   float *img, *params;                                                    // DEVICE: the MFMA image, the parameters as they came
+};
+
+struct mw_stack_group_s {
+  int n;
+  mw::StackRow *rows;                   // DEVICE (n): the n_in = 5 list, then the n_in = 9 list
+  float *imgs, *params;                 // DEVICE: the images, each with its pad behind it, and the parameters as they came, in row order
+  mw::StackList list[2];                // n_in = 5, n_in = 9
+  mw::StackList elist[2];               // the same lists as mw_stack_group_eval plans them (its tail takes MW_STACK_EVAL_RED bytes of the LDS)
+  int row_of[MW_STACK_GROUP_MAX];       // HOST: the row of stack j (the order given at creation)
+  bool any_tendency;
 };

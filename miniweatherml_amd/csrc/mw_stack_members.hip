@@ -32,62 +32,12 @@
 #include <vector>
 #include <algorithm>
 
-#define MW_STACK_GROUP_MAX 32                                       // stacks of a group = members a call can address
-#define MW_STACK_GROUP_LDS 65536                                    // bytes of dynamic LDS a workgroup's images may take together
-
 namespace mw {
 
-struct StackRow { StackP P; int form, img_off, par_off, pad_; };   // img_off / par_off: floats, in the group's packed images / parameters
-struct StackMap { int member[MW_STACK_GROUP_MAX]; };
 struct StackFields { double *f[5]; };                               // temp, density_dry, water_vapor, cloud_liquid, precip_liquid (density_dry is only read)
 
 constexpr int SM_TILES = 4;
 constexpr long long SM_MAX_BLOCKS = 256 * 8;                        // grid.x: grid-stride beyond 8 blocks per CU (every block fills its LDS once)
-
-// a lane's scaling constants of one stack: feature g, feature f1 (4 + g, or 4), feature 8, output g
-struct StackLane { double imin0, irng0, imin1, irng1, imin2, irng2, omin, orng; };
-
-// TILES tiles of one stack from raw features: x0 = feature g, x1 = feature 4 + g (n_in = 5: rho_r in group 0), x2 = feature 8 (group 0
-// of n_in = 9).  k_mlp_stack's statements between its loads and its stores; every lane of the wave calls it (the rotate).
-template <int TILES, bool N9>
-__device__ __forceinline__ void stack_cells(double (&y)[TILES], const StackP *P, const float *img, const StackLane &S, bool tend, int lane, int g,
-                                            const double (&x0)[TILES], const double (&x1)[TILES], const double (&x2)[TILES]) {
-#pragma clang fp contract(off)
-  const bool has1 = N9 || g == 0, has2 = N9 && g == 0;
-  const int last = P->nl - 1;
-  f32x4 a[MW_STACK_UB][TILES];
-  double base[TILES];
-#pragma unroll
-  for (int u = 0; u < TILES; u++) {
-    a[0][u] = (f32x4){net_scaled(x0[u], S.imin0, S.irng0), has1 ? net_scaled(x1[u], S.imin1, S.irng1) : 0.f, has2 ? net_scaled(x2[u], S.imin2, S.irng2) : 0.f, 0.f};
-    base[u] = 0.0;
-    if (tend) { const double b = net5_rotate_base(g, x0[u], x1[u]); base[u] = g == 0 ? x0[u] : b; }      // (wave-uniform)
-  }
-  for (int l = 0; l < last; l++) {                                        // the hidden layers
-    f32x4 d[MW_STACK_UB][TILES];
-    const int nob = P->nob[l];
-    const float slope = P->slope[l];
-    stack_dense<TILES, MW_STACK_UB>(d, a, img + P->aoff[l], img + P->boff[l], P->nk[l], nob, lane, g);
-#pragma unroll
-    for (int ob = 0; ob < MW_STACK_UB; ob++) {
-      if (ob < nob) {
-#pragma unroll
-        for (int u = 0; u < TILES; u++)
-#pragma unroll
-          for (int r = 0; r < 4; r++) a[ob][u][r] = leaky_slope(d[ob][u][r], slope);
-      }
-    }
-  }
-  f32x4 o[1][TILES];                                                      // Dense(4): output g in register 0 of group g
-  stack_dense<TILES, 1>(o, a, img + P->aoff[last], img + P->boff[last], P->nk[last], 1, lane, g);
-#pragma unroll
-  for (int u = 0; u < TILES; u++) {
-    double v = (double)o[0][u][0] * S.orng + S.omin;
-    if (tend) v = base[u] + v;
-    if (g != 0) v = fmax(0.0, v);
-    y[u] = v;
-  }
-}
 
 // rows: the list's rows (n_in = 5 or 9 alone), `models` of them; map.member[j]: the member of row j.  ANYT: the list holds a stack of the
 // tendency form (then a wave's form picks the epilogue, wave-uniformly).
@@ -229,41 +179,9 @@ __global__ __launch_bounds__(256) void k_stack_members_strict(const StackRow *__
   }
 }
 
-// one list of the group: rows [r0, r0 + n) of the table
-struct StackList {
-  int r0, n, mpb;
-  size_t lds;                                                             // bytes of dynamic LDS: the largest workgroup's images + pads
-  bool anyt;
-};
-
-// the largest mpb of 4, 2, 1 (at most apply_slot's rule for n stacks) for which every workgroup's images + pads fit MW_STACK_GROUP_LDS
-static void stack_list_plan(StackList &L, const std::vector<StackRow> &rows) {
-  L.mpb = 1; L.lds = 0;
-  if (L.n < 1) return;
-  for (int mpb = L.n >= 3 ? 4 : L.n; mpb >= 1; mpb /= 2) {
-    size_t worst = 0;
-    for (int m0 = 0; m0 < L.n; m0 += mpb) {
-      size_t bytes = 0;
-      for (int j = m0; j < std::min(L.n, m0 + mpb); j++) bytes += sizeof(float) * (size_t)(rows[(size_t)(L.r0 + j)].P.nimg + MW_STACK_PAD);
-      worst = std::max(worst, bytes);
-    }
-    L.mpb = mpb; L.lds = worst;
-    if (worst <= MW_STACK_GROUP_LDS) return;
-  }
-}
-
 } // namespace mw
 
 using namespace mw;
-
-struct mw_stack_group_s {
-  int n;
-  StackRow *rows;                       // DEVICE (n): the n_in = 5 list, then the n_in = 9 list
-  float *imgs, *params;                 // DEVICE: the images, each with its pad behind it, and the parameters as they came, in row order
-  StackList list[2];                    // n_in = 5, n_in = 9
-  int row_of[MW_STACK_GROUP_MAX];       // HOST: the row of stack j (the order given at creation)
-  bool any_tendency;
-};
 
 extern "C" void mw_stack_group_destroy(mw_stack_group_t g) {
   if (!g) return;
@@ -303,7 +221,11 @@ extern "C" int mw_stack_group_create(mw_stack_group_t *out, int n, const mw_mlp_
     nimg += (size_t)R.P.nimg + MW_STACK_PAD;
     npar += (size_t)(R.P.bwoff[R.P.nl - 1] + 4);
   }
-  for (int pass = 0; pass < 2; pass++) stack_list_plan(g->list[pass], rows);
+  for (int pass = 0; pass < 2; pass++) {
+    stack_list_plan(g->list[pass], rows);
+    g->elist[pass] = g->list[pass];
+    stack_list_plan(g->elist[pass], rows, MW_STACK_GROUP_LDS - MW_STACK_EVAL_RED);
+  }
   hipError_t e = hipMalloc(&g->rows, sizeof(StackRow) * rows.size());
   if (e == hipSuccess) e = hipMalloc(&g->imgs, sizeof(float) * nimg);
   if (e == hipSuccess) e = hipMalloc(&g->params, sizeof(float) * npar);

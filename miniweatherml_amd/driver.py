@@ -31,7 +31,9 @@ evaluate_surrogates scores the networks of a YAML list against the Kessler schem
       - {name: seed0, keras_weights_txt: out/weights_0.txt, nn_input_scaling: out/input_scaling.txt, nn_output_scaling: out/output_scaling.txt}
       - ...                                   # (keras_weights_h5 instead of keras_weights_txt for a Keras file; both widths may be mixed)
     eval_interval: 1                          # evaluate every n-th step (default 1)
-and writes surrogate_evaluation.json (the report and the per-call history) into the working directory.  One rank only.
+and writes surrogate_evaluation.json (the report and the per-call history) into the working directory.  One rank only.  A
+`surrogate_stacks:` list (at most 32, with or without surrogate_models) is scored beside them by one mlp.MlpStackGroup.evaluate call per
+step and listed under `stacks`; eval_domain and surrogate_committees cover the fixed models only.
 
 rollout_surrogates reads the same list and runs every network ONLINE, as an ensemble member of its own beside Kessler (member 0; members
 1 .. K the list's models in its order, rollout.Microphysics_Rollout): each member's output is fed back through the dycore, and every
@@ -250,6 +252,16 @@ def _rollout_models(cfg):
     return [], interval
 
 
+def evaluation_stacks(cfg):
+    """stack_config for evaluate_surrogates, which scores every listed stack in ONE group: more than a group holds
+    (mlp.STACK_GROUP_MAX) are refused by name."""
+    stacks = stack_config(cfg)
+    if len(stacks) > mlp.STACK_GROUP_MAX:
+        raise ValueError("ERROR: evaluate_surrogates scores at most %d surrogate_stacks in one run, got %d (the first one over is %r)"
+                         % (mlp.STACK_GROUP_MAX, len(stacks), stacks[mlp.STACK_GROUP_MAX]["name"]))
+    return stacks
+
+
 def _stack_names(cfg):
     """The names a `surrogate_stacks:` list declares, unchecked: what committee_config and harvest_config tell a stack by."""
     entries = cfg.get("surrogate_stacks")
@@ -257,10 +269,11 @@ def _stack_names(cfg):
 
 
 def stack_config(cfg):
-    """The checked `surrogate_stacks:` list of a loaded configuration for rollout_surrogates, [] without the key: entries
+    """The checked `surrogate_stacks:` list of a loaded configuration for rollout_surrogates and evaluate_surrogates
+    (13.21), [] without the key: entries
     {name, keras_weights_txt, nn_input_scaling, nn_output_scaling} with the files resolved as those of surrogate_models.  The weights file
     must carry a `# stack:` header -- a fixed model's file is refused by name -- and the names are unique across models, committees and
-    stacks and neither 'kessler' nor 'persistence'.  Only that experiment calls it."""
+    stacks and neither 'kessler' nor 'persistence'.  Only those experiments call it."""
     if "surrogate_stacks" not in cfg:
         return []
     entries = cfg["surrogate_stacks"]
@@ -528,6 +541,9 @@ def eval_domain_key(cfg, model_names):
     b = cfg.get("eval_domain", False)
     if b is False or b is None:
         return None
+    if isinstance(b, dict) and isinstance(b.get("box_of"), str) and b["box_of"] not in [str(n) for n in model_names] and b["box_of"] in _stack_names(cfg):
+        raise ValueError("ERROR: eval_domain.box_of names %r, which is a stack of surrogate_stacks: the inside / outside split covers the "
+                         "models of surrogate_models only" % b["box_of"])
     return eval_domain_config(b, model_names)
 
 
@@ -543,7 +559,7 @@ def _domain_split_evaluator(cfg_domain, evaluator, eval_models):
         boxes = [box(names.index(cfg_domain["box_of"]))] * len(names)
     else:
         boxes = [box(k) for k in range(len(names))]
-    return surrogate_eval.DomainSplitEvaluator(evaluator.banks, names, boxes)
+    return surrogate_eval.DomainSplitEvaluator(_fixed_banks(evaluator), names, boxes)
 
 
 def _surrogate_models(entries, yaml_dir):
@@ -570,7 +586,7 @@ def _surrogate_models(entries, yaml_dir):
                 if key == "keras_weights_txt" and mlp.stack_header(p) is not None:
                     raise ValueError("ERROR: surrogate model %r: %s declares a dense stack (`%s`); banks, committees and rollout members hold "
                                      "the 5 / 9 -> 10 -> 4 models only -- stacks run as `surrogate_stacks:` members of rollout_surrogates and in "
-                                     "inference_ponni only (keras_weights_txt there)"
+                                     "inference_ponni only (keras_weights_txt there), and are scored as `surrogate_stacks:` of evaluate_surrogates"
                                      % (e["name"], p, mlp.STACK_MARKER))
                 m[key] = p
             elif key.startswith("nn_") and key != "nn_training_domain":    # (optional: without it the scaling rows are the domain)
@@ -581,16 +597,25 @@ def _surrogate_models(entries, yaml_dir):
     return out
 
 
-def _surrogate_evaluator(entries, device):
-    """One bank per width, in the order the widths first appear; the models' names bank after bank."""
-    weights = mlp.load_surrogate_bank(entries)
+def _fixed_banks(evaluator):
+    """The evaluator's banks of 5 / 9 -> 10 -> 4 models: all but the group of stacks, which comes last and has n_ins in place of n_in."""
+    return [b for b in evaluator.banks if not hasattr(b, "n_ins")]
+
+
+def _surrogate_evaluator(entries, device, stacks=()):
+    """One bank per width, in the order the widths first appear, then ONE mlp.MlpStackGroup of all `stacks` (the checked surrogate_stacks
+    list); the models' names bank after bank, the stacks' behind them."""
+    weights = mlp.load_surrogate_bank(entries) if entries else []
     widths = []
     for w in weights:
         if w[0].shape[0] not in widths:
             widths.append(w[0].shape[0])
     order = [i for n_in in widths for i, w in enumerate(weights) if w[0].shape[0] == n_in]
     banks = [surrogate_eval.SurrogateBank([w for w in weights if w[0].shape[0] == n_in], device) for n_in in widths]
-    return surrogate_eval.SurrogateEvaluator(banks, [entries[i]["name"] for i in order]), [entries[i] for i in order]
+    if stacks:
+        banks.append(mlp.MlpStackGroup([mlp.load_surrogate_stack(*[s[k] for k in STACK_KEYS[1:]]) for s in stacks], device))
+    names = [entries[i]["name"] for i in order] + [s["name"] for s in stacks]
+    return surrogate_eval.SurrogateEvaluator(banks, names), [entries[i] for i in order]
 
 
 def _distributed(device):
@@ -823,20 +848,27 @@ class GenerateMicroData(Column):
 
 
 def evaluation_document(experiment, yaml_path, eval_interval, steps, evaluator, eval_models, eval_calls, rep, committee_evals=(),
-                        eval_domain=None, domain_eval=None, drep=None):
+                        eval_domain=None, domain_eval=None, drep=None, stacks=()):
     """surrogate_evaluation.json as a dict.  rep, drep: the evaluator's and the DomainSplitEvaluator's reports ({} without a call);
-    committee_evals: (committee, its CommitteeEvaluator) pairs; eval_domain: the checked key, None with domain_eval None."""
+    committee_evals: (committee, its CommitteeEvaluator) pairs; eval_domain: the checked key, None with domain_eval None; stacks: the
+    checked `surrogate_stacks` list, whose entries gain bank (the group's index), widths, slopes and form -- `models` stays the fixed
+    models' list and the stacks get no `domain` rows."""
+    fixed = _fixed_banks(evaluator)
     doc = {"experiment": experiment, "yaml": os.path.abspath(yaml_path), "eval_interval": eval_interval, "steps": steps,
-           "models": [dict(m, bank=ib, n_in=b.n_in, form=b.forms[k]) for ib, b in enumerate(evaluator.banks)
-                      for k, m in enumerate(eval_models[sum(x.models for x in evaluator.banks[:ib]):][:b.models])],
+           "models": [dict(m, bank=ib, n_in=b.n_in, form=b.forms[k]) for ib, b in enumerate(fixed)
+                      for k, m in enumerate(eval_models[sum(x.models for x in fixed[:ib]):][:b.models])],
            "statistics": ["sum_d", "sum_abs_d", "sum_d2", "max_abs_d"], "fields": list(surrogate_eval.EVAL_FIELDS),
            "classes": list(surrogate_eval.EVAL_CLASSES), "report": rep,
            "history": [dict(c, banks=h) for c, h in zip(eval_calls, evaluator.history)]}
+    if stacks:
+        group = evaluator.banks[len(fixed)]
+        doc["stacks"] = [dict(s, bank=len(fixed), widths=list(group.widths[k]), slopes=[float(v) for v in group.stacks[k].slopes], form=group.forms[k])
+                         for k, s in enumerate(stacks)]
     if committee_evals:
         doc["committees"] = [dict(c, n_in=ce.bank.n_in, statistics=["sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_r", "sum_r2", "sum_r_abs_d"],
                                   report=ce.report() if eval_calls else {}, history=ce.history) for c, ce in committee_evals]
     if domain_eval is not None:
-        doc["domain"] = dict(eval_domain, group={str(b.n_in): b.domain_group for b in evaluator.banks},
+        doc["domain"] = dict(eval_domain, group={str(b.n_in): b.domain_group for b in fixed},
                              models={n: {"box": surrogate_eval.box_json(domain_eval.boxes[k]), "report": drep.get(n, {})}
                                      for k, n in enumerate(domain_eval.names)},
                              history=[dict(c, banks=h) for c, h in zip(eval_calls, domain_eval.history)])
@@ -847,12 +879,15 @@ class EvaluateSurrogates(Column):
     def configure(self, cfg, nranks):
         _one_rank("evaluate_surrogates", nranks)
         self.committees = evaluation_committees(cfg)
-        cfg["surrogate_models"], cfg["eval_interval"] = surrogate_config(cfg)
+        self.stacks = evaluation_stacks(cfg)
+        cfg["surrogate_models"], cfg["eval_interval"] = _rollout_models(cfg)      # (stacks alone are an evaluation, as they are a rollout)
         self.eval_domain = eval_domain_key(cfg, [m["name"] for m in cfg["surrogate_models"]])
+        if self.eval_domain is not None and not cfg["surrogate_models"]:
+            raise ValueError("ERROR: eval_domain splits the errors of surrogate_models, and this run lists surrogate_stacks only")
 
     def setup(self, *args):
         super().setup(*args)
-        self.evaluator, self.eval_models = _surrogate_evaluator(self.cfg["surrogate_models"], self.device)
+        self.evaluator, self.eval_models = _surrogate_evaluator(self.cfg["surrogate_models"], self.device, self.stacks)
         self.domain_eval = None
         if self.eval_domain is not None:
             self.domain_eval = _domain_split_evaluator(self.eval_domain, self.evaluator, self.eval_models)
@@ -860,7 +895,7 @@ class EvaluateSurrogates(Column):
         for c in self.committees:
             places = [[m["name"] for m in self.eval_models].index(n) for n in c["members"]]
             first = 0
-            for bank in self.evaluator.banks:
+            for bank in _fixed_banks(self.evaluator):
                 if first <= places[0] < first + bank.models:
                     self.committee_evals.append((c, surrogate_eval.CommitteeEvaluator(bank, [i - first for i in places])))
                 first += bank.models
@@ -882,7 +917,7 @@ class EvaluateSurrogates(Column):
         rep = evaluator.report() if self.eval_calls else {}
         drep = None if domain_eval is None else (domain_eval.report() if self.eval_calls else {})
         doc = evaluation_document(info["experiment"], yaml_path, self.cfg["eval_interval"], steps, evaluator, self.eval_models, self.eval_calls,
-                                  rep, self.committee_evals, self.eval_domain, domain_eval, drep)
+                                  rep, self.committee_evals, self.eval_domain, domain_eval, drep, stacks=self.stacks)
         if self.committee_evals:
             info["committee_reports"] = {d["name"]: d["report"] for d in doc["committees"]}
         if domain_eval is not None:

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import capi
-from ._ffi import _field_ptr_array, _ptr, _stream_ptr
+from ._ffi import StatsAndCounts, _field_ptr_array, _ptr, _stream_ptr, grown_workspace
 from .capi import check
 from .coupler import endrun
 
@@ -435,7 +435,8 @@ STACK_GROUP_MAX = 32
 class MlpStackGroup:
     """Owner of one mw_stack_group_t: 1 to 32 stacks -- SurrogateStack tuples or MlpStack handles, n_in 5 and 9, any
     shapes and both forms mixed -- packed into device buffers of the group's own on `device`; members_apply rolls them out as ensemble
-    members.  The handle is destroyed in close() / __del__."""
+    members, evaluate scores them against the truth fields (with models, forms, n_ins and strict the group is a bank to
+    surrogate_eval.SurrogateEvaluator).  The handle is destroyed in close() / __del__."""
 
     def __init__(self, stacks, device):
         self.device = torch.device(device)
@@ -447,6 +448,11 @@ class MlpStackGroup:
         handles = [s if o is None else o for s, o in zip(stacks, own)]
         self.stacks = [h.stack for h in handles]
         self.widths = [h.widths for h in handles]
+        self.models = len(handles)                                        # what SurrogateEvaluator reads of a bank
+        self.forms = [x.form for x in self.stacks]
+        self.n_ins = [w[0] for w in self.widths]
+        self.strict = 0                                                   # evaluate: 1 for the thread-per-cell kernel (mw_mlp_set_strict)
+        self._buf = self._ws = None
         h = C.c_void_p()
         try:
             if any(x._h is None or not x._h.value for x in handles):
@@ -479,6 +485,36 @@ class MlpStackGroup:
             rc = capi.lib().mw_stack_group_members_apply(self._h, (C.c_int * len(members))(*members), int(nz), n // int(nz), nens,
                                                          _field_ptr_array(list(fields5)), _stream_ptr(f.device))
         check(rc)
+
+    def evaluate(self, nz, in5, truth4):
+        """mw_stack_group_eval: in5 the five fields before the microphysics call (IN5), truth4 the four after it (OUT4); fp64 tensors of
+        nz levels on the group's device.  Returns (stats, counts) as SurrogateBank.evaluate does: the raw (n + 1, 2, 4, 4) fp64 array
+        [stack | persistence][inactive, active][field][sum d, sum |d|, sum d^2, max |d|], row j the j-th stack given, and the int64 cells
+        per class -- one device-to-host copy for both.  The workspace is kept from call to call and regrown when the shape grows."""
+        if self._h is None or not self._h.value:
+            endrun("MlpStackGroup: the handle is closed")
+        who = "MlpStackGroup.evaluate: "
+        if len(in5) != 5 or len(truth4) != 4:
+            endrun(who + "five input fields and four truth fields expected")
+        every = list(in5) + list(truth4)
+        n = in5[0].numel()
+        if int(nz) < 1 or n % int(nz) != 0 or any(t.numel() != n for t in every):
+            endrun(who + "the nine fields must have one size, a whole number of columns of nz = %d levels" % nz)
+        if any(t.device != self.device for t in every):
+            endrun(who + "the group lives on %s, the fields on %s" % (self.device, sorted({str(t.device) for t in every})))
+        ncol = n // int(nz)
+        nbytes = int(capi.lib().mw_stack_group_eval_workspace_bytes(self._h, int(nz), ncol))
+        if nbytes < 1:
+            endrun(who + "nz = %d and %d columns are out of range" % (nz, ncol))
+        ws = grown_workspace(self, "_ws", nbytes, self.device)
+        buf = StatsAndCounts((self.models + 1) * 32, 2, self.device, self._buf)
+        self._buf = buf.buf                                               # (the int64 tensor itself: kept from call to call)
+        with strict_mode(self.strict), torch.cuda.device(self.device):
+            rc = capi.lib().mw_stack_group_eval(self._h, int(nz), ncol, _field_ptr_array(in5), _field_ptr_array(truth4), buf.stats_ptr,
+                                                buf.counts_ptr, _ptr(ws), _stream_ptr(self.device))
+        check(rc)
+        stats, counts = buf.host()
+        return stats.reshape(self.models + 1, 2, 4, 4), counts
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

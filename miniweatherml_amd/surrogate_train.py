@@ -1012,8 +1012,8 @@ def main(argv=None):
     print("best model %d (seed %d); wrote %s" % (r["best_model"], r["seeds"][r["best_model"]], ", ".join(r["files_written"])))
     if a.stack is not None:
         print("a dense stack runs in inference_ponni (keras_weights_txt: the written weights.txt) and as a `surrogate_stacks:` member of "
-              "rollout_surrogates; banks and committees take the fixed models")
-        if a.keep_all:                                                         # ready to paste into a rollout_surrogates YAML
+              "rollout_surrogates, and evaluate_surrogates scores the same list; banks and committees take the fixed models")
+        if a.keep_all:                                                         # ready to paste into a rollout_surrogates / evaluate_surrogates YAML
             print("surrogate_stacks:")
             for k, sd in enumerate(r["seeds"]):
                 print("  - {name: seed%d, keras_weights_txt: %s, nn_input_scaling: %s, nn_output_scaling: %s}"
