@@ -467,6 +467,27 @@ int  mw_stack_group_members_apply(mw_stack_group_t g, const int *members, int nz
 long long mw_stack_group_eval_workspace_bytes(mw_stack_group_t g, int nz, long long ncol);
 int  mw_stack_group_eval(mw_stack_group_t g, int nz, long long ncol, const double *const *in5, const double *const *truth4,
                          double *out, long long *counts, void *workspace, void *stream);
+/* A COMMITTEE of the group's stacks (mw_stack_committee.hip): mw_surrogate_committee_apply for stacks (no
+ * reference counterpart; the forward pass it averages is microphysics_kessler_ponni.h:176-202's, generalised to any depth).  sel: HOST,
+ * n_sel = 1 .. MW_COMMITTEE_MAX_MODELS distinct indices of stacks in the order given to mw_stack_group_create, all of one n_in; shapes,
+ * slopes and forms may mix.  For every cell of ensemble member `member` and every output field, y_j is bit for bit what
+ * mw_mlp_stack_forward stores for stack sel[j] -- its own scaling, base and clip applied before combining, mw_mlp_set_strict honoured --
+ *   out   = (((y_0 + y_1) + y_2) + ...) / (double)n_sel      fp64, in the order of sel, no contraction, a true division
+ *   range = hi - lo                                          hi / lo: the largest / smallest y_j, NaN if any y_j is
+ * so a committee of one returns its stack's own bits (-0 included) and range 0.  in5, out4, range4 (optional: NULL) and the layout are
+ * mw_surrogate_committee_apply's: member-fastest (nz, ncol, nens), out4[f] the matching input field (in place) or disjoint from every
+ * input, range4 disjoint from everything; density_dry, the other members and the cells behind the arrays are never written.
+ * The selection is run in CHUNKS, greedily in listed order: the longest run of consecutive stacks whose LDS images fit 64 KB together,
+ * one launch per chunk on `stream`.  With more than one chunk the partial sum, hi and lo travel in `workspace` (DEVICE, 8-byte aligned,
+ * disjoint from every field): mw_stack_group_committee_workspace_bytes gives its size, 96 bytes per cell of the member, 0 for a
+ * one-chunk committee (then workspace may be NULL) and in strict mode.  The chunking does not show in the bits.
+ * Refused with an error text, nothing launched: a null handle or pointer, n_sel outside [1, 16], an index outside the group or given
+ * twice, mixed n_in, member outside [0, nens), overlapping fields as above, a workspace that is too small, more column tiles than an
+ * int holds, sizes of 9e18 elements or more.  A call allocates nothing and copies nothing; asynchronous on `stream`. */
+int  mw_stack_group_committee_workspace_bytes(mw_stack_group_t g, int n_sel, const int *sel, int nz, long long ncol, long long *bytes);
+int  mw_stack_group_committee_apply(mw_stack_group_t g, int n_sel, const int *sel, int member, int nz, long long ncol, int nens,
+                                    const double *const *in5, double *const *out4, double *const *range4, void *workspace,
+                                    long long workspace_bytes, void *stream);
 void mw_stack_group_destroy(mw_stack_group_t g);
 
 /* ---- file output ------------------------------------------------------------ */

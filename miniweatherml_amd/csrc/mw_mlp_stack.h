@@ -1,7 +1,7 @@
 // =====================================================================================================
 // mw_mlp_stack.h -- what the units that run a dense surrogate stack share (mw_mlp_stack.hip: the handle and mw_mlp_stack_forward on
 // level-major fields; mw_stack_members.hip: groups of stacks as ensemble members on the member-fastest layout; mw_stack_eval.hip: groups
-// of stacks scored against the truth fields): the kernels' parameter struct, the leaky ReLU, one Dense layer of MFMA tiles from LDS
+// of stacks scored against the truth fields; mw_stack_committee.hip: the mean and range of a selection of a group's stacks): the kernels' parameter struct, the leaky ReLU, one Dense layer of MFMA tiles from LDS
 // images, the cell of a group's kernels (stack_cells), the host's image builder, the group's lists and the handles.  Only inline
 // functions, templates and plain structs: every kernel is emitted from one unit.  The tile layout is described in mw_mlp_stack.hip.
 // =====================================================================================================
@@ -183,5 +183,6 @@ struct mw_stack_group_s {
   mw::StackList list[2];                // n_in = 5, n_in = 9
   mw::StackList elist[2];               // the same lists as mw_stack_group_eval plans them (its tail takes MW_STACK_EVAL_RED bytes of the LDS)
   int row_of[MW_STACK_GROUP_MAX];       // HOST: the row of stack j (the order given at creation)
+  int form_of[MW_STACK_GROUP_MAX], nimg_of[MW_STACK_GROUP_MAX];      // HOST, by row: its form and the floats of its image (what a committee's chunks are planned from)
   bool any_tendency;
 };

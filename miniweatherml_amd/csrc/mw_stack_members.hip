@@ -218,6 +218,7 @@ extern "C" int mw_stack_group_create(mw_stack_group_t *out, int n, const mw_mlp_
   size_t nimg = 0, npar = 0;
   for (StackRow &R : rows) {
     R.img_off = (int)nimg; R.par_off = (int)npar;
+    g->form_of[&R - rows.data()] = R.form; g->nimg_of[&R - rows.data()] = R.P.nimg;
     nimg += (size_t)R.P.nimg + MW_STACK_PAD;
     npar += (size_t)(R.P.bwoff[R.P.nl - 1] + 4);
   }

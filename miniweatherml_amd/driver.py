@@ -179,18 +179,36 @@ def _model_width(m):
         return sum(1 for ln in f if ln.split("#")[0].strip())
 
 
+def _stack_n_in(cfg, name):
+    """n_in that the weights file of the `surrogate_stacks:` entry called `name` declares, None where stack_config will refuse the entry
+    (no file, no header): committee_config tells a stack committee's width by it."""
+    for e in cfg.get("surrogate_stacks") or ():
+        if isinstance(e, dict) and str(e.get("name")) == name and "keras_weights_txt" in e:
+            p = str(e["keras_weights_txt"])
+            if not os.path.isabs(p):
+                here = os.path.normpath(os.path.join(os.getcwd(), p))
+                p = here if os.path.exists(here) else os.path.normpath(os.path.join(cfg["_dir"], p))
+            head = mlp.stack_header(p) if os.path.exists(p) else None
+            return head[0][0] if head and head[0] else None
+    return None
+
+
 def committee_config(cfg):
     """The checked `surrogate_committees:` list of a loaded configuration, [] without the key: entries {name, members: [model names]} --
     1 .. 16 distinct models of `surrogate_models`, all of one width; committee names unique and no model's name, 'kessler' or
     'persistence'.  An entry may carry `guard:` (surrogate_eval.guard_config: thresholds per field and max_rainsplit), which makes it a
-    guarded committee; a guarded and an unguarded committee of the same models may stand side by side under two names.  Returns
-    [{"name", "members"}] in the YAML's order, with "guard" (the checked mapping) where the entry has one."""
+    guarded committee; a guarded and an unguarded committee of the same models may stand side by side under two names.
+    An entry whose members are ALL names of `surrogate_stacks:` is a committee of dense stacks (it needs no
+    `surrogate_models:` key, by _rollout_models' rule): one n_in, no guard, and its dict carries "stacks": True.  An entry that mixes
+    models and stacks is refused.  Returns [{"name", "members"}] in the YAML's order, with "guard" (the checked mapping) where the
+    entry has one."""
     from . import capi
     from .surrogate_eval import guard_config
     if "surrogate_committees" not in cfg:
         return []
-    models, _ = surrogate_config(cfg)
+    models, _ = _rollout_models(cfg)
     names = [m["name"] for m in models]
+    stack_names = _stack_names(cfg)
     entries = cfg["surrogate_committees"]
     if not isinstance(entries, list) or not entries:
         raise ValueError("ERROR: surrogate_committees must be a non-empty list")
@@ -205,21 +223,30 @@ def committee_config(cfg):
         if not isinstance(e["members"], list) or not e["members"]:
             raise ValueError("ERROR: committee %r: members must be a non-empty list of model names" % cname)
         members = [str(n) for n in e["members"]]
+        of_stacks = [n for n in members if n not in names and n in stack_names]
         for n in members:
-            if n not in names and n in _stack_names(cfg):
-                raise ValueError("ERROR: committee %r names %r, which is a stack of surrogate_stacks: a committee holds the 5 / 9 -> 10 -> 4 "
-                                 "models of surrogate_models only" % (cname, n))
-            if n not in names:
-                raise ValueError("ERROR: committee %r names %r, which is no surrogate model (%s)" % (cname, n, ", ".join(names)))
+            if n in of_stacks and len(of_stacks) != len(members):
+                raise ValueError("ERROR: committee %r names %r, which is a stack of surrogate_stacks, beside members that are none: a committee "
+                                 "holds the 5 / 9 -> 10 -> 4 models of surrogate_models or stacks of surrogate_stacks, never both" % (cname, n))
+            if n not in names and n not in of_stacks:
+                raise ValueError("ERROR: committee %r names %r, which is no surrogate model (%s)" % (cname, n, ", ".join(names + stack_names)))
         if len(set(members)) != len(members):
             raise ValueError("ERROR: committee %r names a model twice" % cname)
         if len(members) > capi.MW_COMMITTEE_MAX_MODELS:
             raise ValueError("ERROR: committee %r has %d models, a committee holds at most %d" % (cname, len(members), capi.MW_COMMITTEE_MAX_MODELS))
-        if len({_model_width(models[names.index(n)]) for n in members}) != 1:
+        if of_stacks:
+            if len({_stack_n_in(cfg, n) for n in members} - {None}) > 1:
+                raise ValueError("ERROR: committee %r mixes stacks of n_in 5 and 9: a committee has one width" % cname)
+            if "guard" in e:
+                raise ValueError("ERROR: committee %r is a committee of stacks and has a guard: guards stay with the committees of "
+                                 "surrogate_models" % cname)
+        elif len({_model_width(models[names.index(n)]) for n in members}) != 1:
             raise ValueError("ERROR: committee %r mixes single-cell and stencil models: a committee has one width" % cname)
         if cname in names or cname in ("kessler", "persistence"):
             raise ValueError("ERROR: committee name %r collides with a surrogate model, 'kessler' or 'persistence'" % cname)
         out.append({"name": cname, "members": members})
+        if of_stacks:
+            out[-1]["stacks"] = True
         if "guard" in e:
             out[-1]["guard"] = guard_config(e["guard"], "the guard of committee %r" % cname)
     if len({c["name"] for c in out}) != len(out):
@@ -767,6 +794,9 @@ class InferencePonni(Column):
             committees = committee_config(cfg)
             if len(committees) != 1:
                 raise ValueError("ERROR: inference_ponni runs one committee, surrogate_committees lists %d" % len(committees))
+            if committees[0].get("stacks"):
+                raise ValueError("ERROR: inference_ponni runs a committee of surrogate_models; committee %r is one of surrogate_stacks "
+                                 "(rollout_surrogates and evaluate_surrogates run those)" % committees[0]["name"])
             cfg["surrogate_models"], _ = surrogate_config(cfg)
             self.committee = committees[0]
         self.fixer_cfg = water_fixer_config(cfg)
@@ -865,7 +895,7 @@ def evaluation_document(experiment, yaml_path, eval_interval, steps, evaluator, 
         doc["stacks"] = [dict(s, bank=len(fixed), widths=list(group.widths[k]), slopes=[float(v) for v in group.stacks[k].slopes], form=group.forms[k])
                          for k, s in enumerate(stacks)]
     if committee_evals:
-        doc["committees"] = [dict(c, n_in=ce.bank.n_in, statistics=["sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_r", "sum_r2", "sum_r_abs_d"],
+        doc["committees"] = [dict(c, n_in=ce.bank.n_ins[ce.sel[0]] if c.get("stacks") else ce.bank.n_in, statistics=["sum_d", "sum_abs_d", "sum_d2", "max_abs_d", "sum_r", "sum_r2", "sum_r_abs_d"],
                                   report=ce.report() if eval_calls else {}, history=ce.history) for c, ce in committee_evals]
     if domain_eval is not None:
         doc["domain"] = dict(eval_domain, group={str(b.n_in): b.domain_group for b in fixed},
@@ -893,6 +923,10 @@ class EvaluateSurrogates(Column):
             self.domain_eval = _domain_split_evaluator(self.eval_domain, self.evaluator, self.eval_models)
         self.committee_evals = []                                              # (committee, its evaluator on the bank of its width)
         for c in self.committees:
+            if c.get("stacks"):                                                # on the stacks' group, the bank behind the fixed ones
+                group = self.evaluator.banks[len(_fixed_banks(self.evaluator))]
+                self.committee_evals.append((c, surrogate_eval.CommitteeEvaluator(group, [[s["name"] for s in self.stacks].index(n) for n in c["members"]])))
+                continue
             places = [[m["name"] for m in self.eval_models].index(n) for n in c["members"]]
             first = 0
             for bank in _fixed_banks(self.evaluator):
@@ -977,6 +1011,10 @@ class RolloutSurrogates(Column):
         self.domain_cfg = training_domain_config(cfg)
         self.committees = committee_config(cfg)
         self.stacks = stack_config(cfg)
+        for c in self.committees:
+            if c.get("stacks") and self.domain_cfg is not None:
+                raise ValueError("ERROR: training_domain reports the models of surrogate_models and their committees; committee %r is one of "
+                                 "surrogate_stacks, which keep no training box" % c["name"])
         cfg["surrogate_models"], cfg["eval_interval"], cfg["persistence_member"], cfg["nens"] = rollout_config(cfg)
         stepped = [m["name"] for m in cfg["surrogate_models"]] + [c["name"] for c in self.committees] + [s["name"] for s in self.stacks]
         self.fixer_cfg = water_fixer_config(cfg, stepped)

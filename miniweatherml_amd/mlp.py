@@ -452,7 +452,7 @@ class MlpStackGroup:
         self.forms = [x.form for x in self.stacks]
         self.n_ins = [w[0] for w in self.widths]
         self.strict = 0                                                   # evaluate: 1 for the thread-per-cell kernel (mw_mlp_set_strict)
-        self._buf = self._ws = None
+        self._buf = self._ws = self._cws = None
         h = C.c_void_p()
         try:
             if any(x._h is None or not x._h.value for x in handles):
@@ -515,6 +515,43 @@ class MlpStackGroup:
         check(rc)
         stats, counts = buf.host()
         return stats.reshape(self.models + 1, 2, 4, 4), counts
+
+    def committee_apply(self, nz, sel, member, in5, out4, range4=None):
+        """mw_stack_group_committee_apply: the mean of the group's stacks sel (1 .. 16 distinct indices of one n_in, summed
+        in that order) on ensemble member `member` of the member-fastest fields in5 = (temp, density_dry, water_vapor, cloud_liquid,
+        precip_liquid), each (nz, ..., nens), written to out4 = (temp, water_vapor, cloud_liquid, precip_liquid) of the same shape -- each
+        the matching input tensor (in place) or a tensor of its own -- and, with range4, the stacks' largest minus smallest value per cell
+        and field: SurrogateBank.committee_apply for stacks.  Only elements of `member` are read and written (self.strict = 1: the
+        thread-per-cell form).  A committee whose images do not fit the kernel's LDS together runs in chunks; their workspace is kept from
+        call to call and regrown when the shape grows."""
+        if self._h is None or not self._h.value:
+            endrun("MlpStackGroup: the handle is closed")
+        who = "MlpStackGroup.committee_apply: "
+        sel = [int(s) for s in sel]
+        if len(in5) != 5 or len(out4) != 4 or (range4 is not None and len(range4) != 4):
+            endrun(who + "five input fields, four output fields and (optionally) four range fields expected")
+        every = list(in5) + list(out4) + (list(range4) if range4 is not None else [])
+        if any(t.shape != in5[0].shape for t in every) or in5[0].dim() < 2:
+            endrun(who + "fields of one shape (nz, ..., nens) expected")
+        if any(t.dtype != torch.float64 or not t.is_contiguous() for t in every):
+            endrun(who + "contiguous float64 fields expected")
+        nens = int(in5[0].shape[-1])
+        n = in5[0].numel() // nens
+        if int(nz) < 1 or n % int(nz) != 0:
+            endrun(who + "%d cells per member are not a whole number of columns of nz = %d" % (n, nz))
+        dev = in5[0].device                                               # (a group made on "cuda" lives on the current device)
+        if any(t.device != dev for t in every) or dev.type != self.device.type or self.device.index not in (None, dev.index):
+            endrun(who + "the group lives on %s, the fields on %s" % (self.device, sorted({str(t.device) for t in every})))
+        ncol = n // int(nz)
+        csel, nbytes = (C.c_int * max(1, len(sel)))(*sel), C.c_longlong(0)
+        with strict_mode(self.strict), torch.cuda.device(self.device):
+            rc = capi.lib().mw_stack_group_committee_workspace_bytes(self._h, len(sel), csel, int(nz), ncol, C.byref(nbytes))
+            if rc == 0:
+                ws = grown_workspace(self, "_cws", nbytes.value, self.device) if nbytes.value > 0 else None
+                rc = capi.lib().mw_stack_group_committee_apply(self._h, len(sel), csel, int(member), int(nz), ncol, nens, _field_ptr_array(in5),
+                                                               _field_ptr_array(out4), _field_ptr_array(range4) if range4 is not None else None,
+                                                               _ptr(ws) if ws is not None else None, nbytes.value, _stream_ptr(self.device))
+        check(rc)
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

@@ -22,7 +22,7 @@ from .capi import check
 from .coupler import endrun
 from .microphysics import (CP_D, LV, Microphysics_Kessler, column_water, heat_closure_finish, members_copy, surface_rain_finish, water_fix_finish,
                            water_fix_tolerance)
-from .mlp import IN5, OUT4, MlpStackGroup, SurrogateStack, as_surrogate_model, load_surrogate_stack
+from .mlp import IN5, OUT4, MlpStackGroup, SurrogateStack, as_surrogate_model, load_surrogate_stack, stack_widths
 from .ncio import sample_file_append, sample_file_create
 from .sampling import sample_buffers, sample_thresholds
 from .surrogate_eval import (DOMAIN_CLASSES, CommitteeGuard, SurrogateBank, box_json, domain_box, domain_config, finite_or_none, guard_config,  # noqa: F401
@@ -130,7 +130,10 @@ class Microphysics_Rollout(Microphysics_Kessler):
         (DESIGN.md 13.20): each is one more member after the committees' -- member 1 + len(models) + len(committees) + s -- replaced in
         place from its own state, all of them by ONE MlpStackGroup.members_apply call per step behind the banks' loop.  surface_rain,
         water_fixer, heat_closure and the harvester treat a stack member as a model member; the training_domain report and a guard's
-        domain stay with the fixed models and the committees, and a committee that names a stack is refused.
+        domain stay with the fixed models and their committees.  A committee whose names are ALL stacks of `stacks`, with one n_in, is a
+        committee of stacks: it takes its place among the committees -- member 1 + len(models) + ci -- and is replaced
+        in place from its own state by MlpStackGroup.committee_apply on this rollout's stack group, where the fixed committees are
+        applied; a committee mixing models and stacks or n_in 5 and 9, a guard on one, and one under training_domain are refused.
         The coupler must have 1 + len(models) + len(committees) + len(stacks) (+ 1 with persistence) members."""
         models = [as_surrogate_model(m) for m in models]
         self.model_forms = [m.form for m in models]
@@ -148,15 +151,25 @@ class Microphysics_Rollout(Microphysics_Kessler):
             endrun("Microphysics_Rollout: %d models%s%s%s beside Kessler need nens = %d, the coupler has %d"
                    % (len(models), (", %d committees" % len(committees)) if committees else "", (", %d stacks" % len(stacks)) if stacks else "",
                       " and persistence" if persistence else "", len(self.member_names), coupler.get_nens()))
-        for cname, cmodels in committees:
-            for sname, _ in stacks:
-                if sname in cmodels:
-                    endrun("Microphysics_Rollout: committee %r names the stack %r: a committee holds the two fixed models only" % (cname, sname))
+        stack_names = [s[0] for s in stacks]
+        of_stacks = []                                                         # per committee: its members are stacks
+        for ci, (cname, cmodels) in enumerate(committees):
+            named = [n for n in cmodels if n in stack_names and n not in names]
+            if named and len(named) != len(cmodels):
+                endrun("Microphysics_Rollout: committee %r names the stack %r beside members that are none: a committee holds fixed models or "
+                       "stacks, never both" % (cname, named[0]))
+            of_stacks.append(bool(named))
             if not 1 <= len(cmodels) <= capi.MW_COMMITTEE_MAX_MODELS:
                 endrun("Microphysics_Rollout: committee %r has %d models, a committee has 1 to %d" % (cname, len(cmodels), capi.MW_COMMITTEE_MAX_MODELS))
-            if len(set(cmodels)) != len(cmodels) or any(n not in names for n in cmodels):
-                endrun("Microphysics_Rollout: committee %r must name distinct models of the list (%s)" % (cname, ", ".join(names)))
-            if len({int(np.shape(models[names.index(n)][0])[0]) for n in cmodels}) != 1:
+            if len(set(cmodels)) != len(cmodels) or any(n not in (stack_names if named else names) for n in cmodels):
+                endrun("Microphysics_Rollout: committee %r must name distinct models of the list (%s)" % (cname, ", ".join(stack_names if named else names)))
+            if named:
+                if len({stack_widths(stacks[stack_names.index(n)][1])[0] for n in cmodels}) != 1:
+                    endrun("Microphysics_Rollout: committee %r mixes stacks of n_in 5 and 9: a committee has one width" % cname)
+                if guards[ci] is not None:
+                    endrun("Microphysics_Rollout: committee %r is a committee of stacks and has a guard: guards stay with the fixed models' "
+                           "committees" % cname)
+            elif len({int(np.shape(models[names.index(n)][0])[0]) for n in cmodels}) != 1:
                 endrun("Microphysics_Rollout: committee %r mixes single-cell and stencil models: a committee has one width" % cname)
         super().init(coupler)
         coupler.set_option("micro", "rollout")
@@ -167,17 +180,21 @@ class Microphysics_Rollout(Microphysics_Kessler):
         # one bank per width; a model keeps the member its place in the list gives it
         self.banks = [(SurrogateBank([m for m in models if np.shape(m[0])[0] == w], coupler.device),
                        [1 + k for k, m in enumerate(models) if np.shape(m[0])[0] == w]) for w in widths]
-        # a committee runs on its width's bank: (bank, its models' places in that bank, its member)
+        self.stack_names, self.stacks = [s[0] for s in stacks], [s[1] for s in stacks]
+        self.stack_members = [1 + len(models) + len(committees) + k for k in range(len(stacks))]
+        self.stack_group = MlpStackGroup(self.stacks, coupler.device) if stacks else None
+        # a committee runs on its width's bank: (bank, its models' places in that bank, its member); a committee of stacks on the stacks'
+        # group, which is a bank to the step's loop (MlpStackGroup.committee_apply)
         self.committees = []
         for ci, (cname, cmodels) in enumerate(committees):
+            if of_stacks[ci]:
+                self.committees.append((self.stack_group, [stack_names.index(n) for n in cmodels], 1 + len(models) + ci))
+                continue
             w = int(np.shape(models[names.index(cmodels[0])][0])[0])
             in_bank = [k for k, m in enumerate(models) if np.shape(m[0])[0] == w]
             self.committees.append((self.banks[widths.index(w)][0], [in_bank.index(names.index(n)) for n in cmodels], 1 + len(models) + ci))
         self.guards = guards                                                   # per committee: the checked guard or None
-        # the dense stacks: one group, one members_apply call per step for all of them; their members follow the committees'
-        self.stack_names, self.stacks = [s[0] for s in stacks], [s[1] for s in stacks]
-        self.stack_members = [1 + len(models) + len(committees) + k for k in range(len(stacks))]
-        self.stack_group = MlpStackGroup(self.stacks, coupler.device) if stacks else None
+        self._stack_committees = [c[0] for c, st in zip(committees, of_stacks) if st]
         self._models, self._model_names, self._committee_names = models, names, committees
         if domains is not None and len(domains) != len(models):
             endrun("Microphysics_Rollout: %d domains for %d models (one per model, None where it has none)" % (len(domains), len(models)))
@@ -388,6 +405,9 @@ class Microphysics_Rollout(Microphysics_Kessler):
         box, every committee member with its committee's."""
         if self._domain is None or self._domain[3] is not self.training_domain:
             cfg = domain_config(self.training_domain, "training_domain")
+            if getattr(self, "_stack_committees", None):
+                endrun("Microphysics_Rollout: training_domain reports the fixed models and their committees; committee %r is one of stacks, which "
+                       "keep no training box" % self._stack_committees[0])
             boxes = [self.model_box(n, cfg["margin"], cfg["fields"]) for n in self._model_names]
             boxes += [self._committee_box(ci, cfg) for ci in range(len(self._committee_names))]
             if not boxes or len(boxes) > capi.MW_DOMAIN_MAX_MEMBERS:
