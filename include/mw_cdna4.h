@@ -488,6 +488,21 @@ int  mw_stack_group_committee_workspace_bytes(mw_stack_group_t g, int n_sel, con
 int  mw_stack_group_committee_apply(mw_stack_group_t g, int n_sel, const int *sel, int member, int nz, long long ncol, int nens,
                                     const double *const *in5, double *const *out4, double *const *range4, void *workspace,
                                     long long workspace_bytes, void *stream);
+/* The GUARDED committee of the group's stacks (mw_stack_guard.hip; no reference counterpart): steps 1 and 2 of
+ * a guarded committee's step (13.7) in the committee's own last launch.  mean4 (and range4, optional: NULL) receive bit for bit what
+ * mw_stack_group_committee_apply writes out of place for the same selection; the member's bytes flags[col * nens + member] (DEVICE,
+ * ncol * nens bytes; no other byte is touched) and counts (DEVICE int64 [2]) receive what mw_committee_guard_flags writes when given
+ * those means and ranges and thr4 (HOST, four thresholds for temp, water_vapor, cloud_liquid, precip_liquid): counts[0] is SET to this
+ * call's flagged columns (an 8-byte memset in stream order, then integer adds), counts[1] is INCREASED by them.  mw_mlp_set_strict is
+ * honoured; one chunk or several, the same bits.  The workspace is mw_stack_group_committee_workspace_bytes'.
+ * Refused with an error text before any device is looked for, nothing launched: a null pointer or field, nz, ncol or nens below 1,
+ * member outside [0, nens), a threshold that is negative or NaN (+inf is allowed), a mean or range field that overlaps an input, the
+ * workspace or another output -- IN PLACE IS REFUSED: Kessler reads the state on the flagged columns --, then the handle's and the
+ * selection's refusals of mw_stack_group_committee_apply and a workspace that is too small.  Asynchronous on `stream`. */
+int  mw_stack_group_committee_guard_flag(mw_stack_group_t g, int n_sel, const int *sel, int member, int nz, long long ncol, int nens,
+                                         const double *const *in5, double *const *mean4, double *const *range4 /* may be null */,
+                                         const double *thr4, unsigned char *flags, long long *counts, void *workspace,
+                                         long long workspace_bytes, void *stream);
 void mw_stack_group_destroy(mw_stack_group_t g);
 
 /* ---- file output ------------------------------------------------------------ */

@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmw_cdna4.so")
 # the dycore is eight units (map: csrc/mw_dycore_int.h); every kernel family is launched from exactly one of them
 SOURCES = ["mw_host.cpp", "mw_dycore.hip", "mw_march_y.hip", "mw_march_xz.hip", "mw_march_tracers.hip", "mw_march_sched.hip", "mw_zero_rows.hip",
-           "mw_dycore_init.hip", "mw_dycore_aids.hip", "mw_kessler.hip", "mw_mlp.hip", "mw_mlp_stack.hip", "mw_stack_members.hip", "mw_stack_eval.hip", "mw_stack_committee.hip", "mw_surrogate_bank.hip", "mw_surrogate_eval_domain.hip", "mw_member.hip", "mw_member_sample.hip", "mw_member_guard.hip", "mw_member_water.hip", "mw_member_heat.hip", "mw_train.hip", "mw_train_stack.hip", "mw_column.hip", "mw_output.hip", "mw_netcdf.cpp", "mw_rccl.cpp", "mw_h5.cpp"]
+           "mw_dycore_init.hip", "mw_dycore_aids.hip", "mw_kessler.hip", "mw_mlp.hip", "mw_mlp_stack.hip", "mw_stack_members.hip", "mw_stack_eval.hip", "mw_stack_committee.hip", "mw_stack_guard.hip", "mw_surrogate_bank.hip", "mw_surrogate_eval_domain.hip", "mw_member.hip", "mw_member_sample.hip", "mw_member_guard.hip", "mw_member_water.hip", "mw_member_heat.hip", "mw_train.hip", "mw_train_stack.hip", "mw_column.hip", "mw_output.hip", "mw_netcdf.cpp", "mw_rccl.cpp", "mw_h5.cpp"]
 HEADERS = ["mw_common.h", "mw_dycore_int.h", "mw_weno.h", "mw_weno79.h", "mw_march.h", "mw_zero_rows.h", "mw_calib.h", "mw_glibc_pow.h", "mw_glibc_pow_tables.h", "mw_kessler_teacher.h", "mw_sample_key.h", "mw_mlp_net.h", "mw_feistel.h", "mw_stack_shape.h", "mw_mlp_stack.h", "mw_surrogate_bank.h", "mw_member.h", os.path.join("..", "..", "include", "mw_cdna4.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 MAX_JOBS = 16      # hipcc processes at a time (never sized by the machine's CPU count: build boxes are shared)
@@ -23,9 +23,9 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", 
 # per unit, behind FLAGS.  mw_mlp_stack.hip: no packed fp32 instructions (v_pk_fma_f32 and its kin) in the activation and scaling code
 # between the MFMAs; the older units keep the code generation they were measured with
 # mw_train_stack.hip: the same, for the leaky ReLU, its derivative and Nadam between the MFMAs
-# mw_stack_members.hip, mw_stack_eval.hip, mw_stack_committee.hip: mw_mlp_stack.hip's flags, whose bits their kernels reproduce
+# mw_stack_members.hip, mw_stack_eval.hip, mw_stack_committee.hip, mw_stack_guard.hip: mw_mlp_stack.hip's flags, whose bits their kernels reproduce
 _NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-UNIT_FLAGS = {"mw_mlp_stack.hip": _NO_PK, "mw_stack_members.hip": _NO_PK, "mw_stack_eval.hip": _NO_PK, "mw_stack_committee.hip": _NO_PK, "mw_train_stack.hip": _NO_PK}
+UNIT_FLAGS = {"mw_mlp_stack.hip": _NO_PK, "mw_stack_members.hip": _NO_PK, "mw_stack_eval.hip": _NO_PK, "mw_stack_committee.hip": _NO_PK, "mw_stack_guard.hip": _NO_PK, "mw_train_stack.hip": _NO_PK}
 
 
 def _stale(target, deps):

@@ -240,6 +240,9 @@ SYMBOLS = {
     "mw_stack_group_committee_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_longlong, C.POINTER(C.c_longlong)]),
     "mw_stack_group_committee_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_longlong, C.c_int,
                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_longlong, C.c_void_p]),
+    "mw_stack_group_committee_guard_flag": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_longlong, C.c_int,
+                                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_double),
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "mw_stack_group_destroy": (None, [C.c_void_p]),
     "mw_stack_train_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int]),
     "mw_stack_train_epoch": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

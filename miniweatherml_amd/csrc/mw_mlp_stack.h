@@ -1,14 +1,17 @@
 // =====================================================================================================
 // mw_mlp_stack.h -- what the units that run a dense surrogate stack share (mw_mlp_stack.hip: the handle and mw_mlp_stack_forward on
 // level-major fields; mw_stack_members.hip: groups of stacks as ensemble members on the member-fastest layout; mw_stack_eval.hip: groups
-// of stacks scored against the truth fields; mw_stack_committee.hip: the mean and range of a selection of a group's stacks): the kernels' parameter struct, the leaky ReLU, one Dense layer of MFMA tiles from LDS
-// images, the cell of a group's kernels (stack_cells), the host's image builder, the group's lists and the handles.  Only inline
+// of stacks scored against the truth fields; mw_stack_committee.hip: the mean and range of a selection of a group's stacks;
+// mw_stack_guard.hip: that mean with the guard's column flags): the kernels' parameter struct, the leaky ReLU, one Dense layer of MFMA tiles from LDS
+// images, the cell of a group's kernels (stack_cells), the host's image builder, the group's lists, the handles and a committee's plan.  Only inline
 // functions, templates and plain structs: every kernel is emitted from one unit.  The tile layout is described in mw_mlp_stack.hip.
 // =====================================================================================================
 #pragma once
 #include "mw_mlp_net.h"
 #include "mw_stack_shape.h"                                         // the shape limits (MW_STACK_*) and their check
 #include <algorithm>
+#include <cstring>
+#include <string>
 #include <vector>
 
 #define MW_STACK_PAD (64 * (MW_STACK_UB - 1))                      // floats behind the image in LDS: a layer with fewer unit blocks reads (and drops) up to here
@@ -186,3 +189,95 @@ struct mw_stack_group_s {
   int form_of[MW_STACK_GROUP_MAX], nimg_of[MW_STACK_GROUP_MAX];      // HOST, by row: its form and the floats of its image (what a committee's chunks are planned from)
   bool any_tendency;
 };
+
+// ---- what the units that run a COMMITTEE of a group's stacks share (mw_stack_committee.hip: mean and range; mw_stack_guard.hip: the
+// guarded committee's last launch) ----
+namespace mw {
+
+constexpr int SC_MAX = MW_COMMITTEE_MAX_MODELS;
+constexpr int SC_TILES = 4;                                         // tiles (n_in = 9: levels) per wave and pass
+constexpr long long SC_MAX_BLOCKS = 256 * 4;                        // grid.x: grid-stride beyond 4 blocks per CU (every block fills its LDS once)
+
+struct StackChunk { int n, first, last; int row[SC_MAX], lds_off[SC_MAX]; };   // rows of the group's table, floats from the LDS base
+struct StackSel { int n; int row[SC_MAX]; };
+struct StackCommitteeFields { const double *in[5]; double *out[4]; double *range[4]; };      // range[*]: all null or all set
+
+// what a lane carries of its (cell, field) across the stacks of a chunk, and across chunks through the workspace: plane (3 g + q) of
+// `cells` doubles, q = sum, hi, lo
+struct CommitteeAcc { double sum, hi, lo; };
+
+__device__ __forceinline__ void acc_add(CommitteeAcc &a, double y, bool init) {
+#pragma clang fp contract(off)
+  a.sum = init ? y : a.sum + y;                                     // (the first addend as it is: a committee of one keeps its bits)
+  a.hi  = init ? y : eval_max(a.hi, y);
+  a.lo  = init ? y : eval_min(a.lo, y);
+}
+
+// k_mlp_stack_strict's expressions for one cell of one stack: in[9] raw (n_in = 5: the first five), p[4] the four outputs
+__device__ __forceinline__ void stack_strict_cell(const StackRow *R, const float *par, const double (&in)[9], double (&p)[4]) {
+#pragma clang fp contract(off)
+  const StackP &P = R->P;
+  float x[MW_STACK_MAX_WIDTH], h[MW_STACK_MAX_WIDTH];
+  for (int i = 0; i < P.n_in; i++) x[i] = (float)((in[i] - P.in_min[i]) / P.in_rng[i]);
+  for (int l = 0; l < P.nl; l++) {
+    const int n = P.width[l], no = P.width[l + 1];
+    const float *W = par + P.woff[l], *b = par + P.bwoff[l];
+    for (int o = 0; o < no; o++) {
+      float acc = 0.f;
+      for (int i = 0; i < n; i++) acc += x[i] * W[i * no + o];
+      acc = acc + b[o];
+      h[o] = (l < P.nl - 1) ? (acc > 0.f ? acc : P.slope[l] * acc) : acc;
+    }
+    for (int o = 0; o < no; o++) x[o] = h[o];
+  }
+  if (R->form != MW_FORM_STATE) {
+    p[0] =           in[0] + (x[0] * P.out_rng[0] + P.out_min[0]);
+    p[1] = fmax(0.0, in[2] + (x[1] * P.out_rng[1] + P.out_min[1]));
+    p[2] = fmax(0.0, in[3] + (x[2] * P.out_rng[2] + P.out_min[2]));
+    p[3] = fmax(0.0, in[4] + (x[3] * P.out_rng[3] + P.out_min[3]));
+  } else {
+    p[0] =           x[0] * P.out_rng[0] + P.out_min[0];
+    p[1] = fmax(0.0, x[1] * P.out_rng[1] + P.out_min[1]);
+    p[2] = fmax(0.0, x[2] * P.out_rng[2] + P.out_min[2]);
+    p[3] = fmax(0.0, x[3] * P.out_rng[3] + P.out_min[3]);
+  }
+}
+
+// The checked selection: the rows of sel in the group's table and the greedy chunks of the fast form, from the group's host mirror of
+// its rows (n_in by list, form_of, nimg_of).  Returns an error text, or empty.
+struct StackCommitteePlan { StackSel sel; int n_in; bool anyt; int nchunks; StackChunk chunk[SC_MAX]; size_t lds[SC_MAX]; };
+
+static std::string stack_committee_plan(StackCommitteePlan &Q, const mw_stack_group_s *g, int n_sel, const int *sel, const std::string &w) {
+  if (!g) return w + ": null handle";
+  if (!sel) return w + ": null pointer";
+  if (n_sel < 1 || n_sel > SC_MAX) return w + ": a committee has 1 to " + std::to_string(SC_MAX) + " stacks, got " + std::to_string(n_sel);
+  memset(&Q, 0, sizeof(Q));
+  Q.sel.n = n_sel;
+  size_t used = 0;
+  for (int j = 0; j < n_sel; j++) {
+    if (sel[j] < 0 || sel[j] >= g->n) return w + ": stack " + std::to_string(sel[j]) + " is outside the group's [0, " + std::to_string(g->n) + ")";
+    for (int i = 0; i < j; i++) if (sel[i] == sel[j]) return w + ": stack " + std::to_string(sel[j]) + " is given twice";
+    const int r = g->row_of[sel[j]], n_in = r >= g->list[1].r0 ? 9 : 5;    // (the n_in = 5 list comes first in the table)
+    if (j > 0 && n_in != Q.n_in) return w + ": stacks " + std::to_string(sel[0]) + " and " + std::to_string(sel[j]) + " differ in n_in: a committee has one";
+    Q.n_in = n_in;
+    Q.sel.row[j] = r;
+    Q.anyt = Q.anyt || g->form_of[r] != MW_FORM_STATE;
+    const size_t bytes = sizeof(float) * (size_t)(g->nimg_of[r] + MW_STACK_PAD);
+    if (bytes > MW_STACK_GROUP_LDS) return w + ": a stack's image exceeds the kernel's LDS";      // (no shape mw_mlp_stack_create accepts does)
+    if (Q.nchunks == 0 || used + bytes > MW_STACK_GROUP_LDS) { Q.nchunks++; used = 0; }      // greedy, in listed order
+    StackChunk &C = Q.chunk[Q.nchunks - 1];
+    C.row[C.n] = r; C.lds_off[C.n] = (int)(used / sizeof(float)); C.n++;
+    used += bytes;
+    Q.lds[Q.nchunks - 1] = used;
+  }
+  Q.chunk[0].first = 1; Q.chunk[Q.nchunks - 1].last = 1;
+  return std::string();
+}
+
+// chunk c of the plan in the fast form (mw_stack_committee.hip, where k_stack_committee is emitted); 0, or 1 with the error text set
+int stack_committee_launch(const mw_stack_group_s *g, const StackCommitteePlan &Q, int c, int member, int nz, long long ncol, int nens,
+                           const StackCommitteeFields &F, double *workspace, hipStream_t st);
+
+static bool sc_overlap(const double *a, long long na, const double *b, long long nb) { return a < b + nb && b < a + na; }
+
+} // namespace mw

@@ -26,29 +26,8 @@
 // k_mlp_stack_strict's index-order loops on the parameters as they came, the stacks in listed order, no chunks and no workspace.
 // =====================================================================================================
 #include "mw_mlp_stack.h"
-#include <cstring>
-#include <string>
 
 namespace mw {
-
-constexpr int SC_MAX = MW_COMMITTEE_MAX_MODELS;
-constexpr int SC_TILES = 4;                                         // tiles (n_in = 9: levels) per wave and pass
-constexpr long long SC_MAX_BLOCKS = 256 * 4;                        // grid.x: grid-stride beyond 4 blocks per CU (every block fills its LDS once)
-
-struct StackChunk { int n, first, last; int row[SC_MAX], lds_off[SC_MAX]; };   // rows of the group's table, floats from the LDS base
-struct StackSel { int n; int row[SC_MAX]; };
-struct StackCommitteeFields { const double *in[5]; double *out[4]; double *range[4]; };      // range[*]: all null or all set
-
-// what a lane carries of its (cell, field) across the stacks of a chunk, and across chunks through the workspace: plane (3 g + q) of
-// `cells` doubles, q = sum, hi, lo
-struct CommitteeAcc { double sum, hi, lo; };
-
-__device__ __forceinline__ void acc_add(CommitteeAcc &a, double y, bool init) {
-#pragma clang fp contract(off)
-  a.sum = init ? y : a.sum + y;                                     // (the first addend as it is: a committee of one keeps its bits)
-  a.hi  = init ? y : eval_max(a.hi, y);
-  a.lo  = init ? y : eval_min(a.lo, y);
-}
 
 template <bool N9, bool ANYT>
 __global__ __launch_bounds__(256, 2) void k_stack_committee(const StackRow *__restrict__ rows, const float *__restrict__ imgs, StackChunk C, double dn,
@@ -167,35 +146,6 @@ __global__ __launch_bounds__(256, 2) void k_stack_committee(const StackRow *__re
   }
 }
 
-// k_mlp_stack_strict's expressions for one cell of one stack: in[9] raw (n_in = 5: the first five), p[4] the four outputs
-__device__ __forceinline__ void stack_strict_cell(const StackRow *R, const float *par, const double (&in)[9], double (&p)[4]) {
-#pragma clang fp contract(off)
-  const StackP &P = R->P;
-  float x[MW_STACK_MAX_WIDTH], h[MW_STACK_MAX_WIDTH];
-  for (int i = 0; i < P.n_in; i++) x[i] = (float)((in[i] - P.in_min[i]) / P.in_rng[i]);
-  for (int l = 0; l < P.nl; l++) {
-    const int n = P.width[l], no = P.width[l + 1];
-    const float *W = par + P.woff[l], *b = par + P.bwoff[l];
-    for (int o = 0; o < no; o++) {
-      float acc = 0.f;
-      for (int i = 0; i < n; i++) acc += x[i] * W[i * no + o];
-      acc = acc + b[o];
-      h[o] = (l < P.nl - 1) ? (acc > 0.f ? acc : P.slope[l] * acc) : acc;
-    }
-    for (int o = 0; o < no; o++) x[o] = h[o];
-  }
-  if (R->form != MW_FORM_STATE) {
-    p[0] =           in[0] + (x[0] * P.out_rng[0] + P.out_min[0]);
-    p[1] = fmax(0.0, in[2] + (x[1] * P.out_rng[1] + P.out_min[1]));
-    p[2] = fmax(0.0, in[3] + (x[2] * P.out_rng[2] + P.out_min[2]));
-    p[3] = fmax(0.0, in[4] + (x[3] * P.out_rng[3] + P.out_min[3]));
-  } else {
-    p[0] =           x[0] * P.out_rng[0] + P.out_min[0];
-    p[1] = fmax(0.0, x[1] * P.out_rng[1] + P.out_min[1]);
-    p[2] = fmax(0.0, x[2] * P.out_rng[2] + P.out_min[2]);
-    p[3] = fmax(0.0, x[3] * P.out_rng[3] + P.out_min[3]);
-  }
-}
 
 // STRICT form.  NIN = 5: thread = one cell of the member; NIN = 9: thread = one column of the member, swept top-down with temp, rho_v,
 // rho_c, rho_r of the level above AS THEY WERE in registers.  items: the member's cells / columns.
@@ -233,42 +183,25 @@ __global__ __launch_bounds__(256) void k_stack_committee_strict(const StackRow *
   }
 }
 
-// The checked selection: the rows of sel in the group's table and the greedy chunks of the fast form, from the group's host mirror of
-// its rows (n_in by list, form_of, nimg_of).  Returns an error text, or empty.
-struct StackCommitteePlan { StackSel sel; int n_in; bool anyt; int nchunks; StackChunk chunk[SC_MAX]; size_t lds[SC_MAX]; };
-
-static std::string stack_committee_plan(StackCommitteePlan &Q, const mw_stack_group_s *g, int n_sel, const int *sel, const std::string &w) {
-  if (!g) return w + ": null handle";
-  if (!sel) return w + ": null pointer";
-  if (n_sel < 1 || n_sel > SC_MAX) return w + ": a committee has 1 to " + std::to_string(SC_MAX) + " stacks, got " + std::to_string(n_sel);
-  memset(&Q, 0, sizeof(Q));
-  Q.sel.n = n_sel;
-  size_t used = 0;
-  for (int j = 0; j < n_sel; j++) {
-    if (sel[j] < 0 || sel[j] >= g->n) return w + ": stack " + std::to_string(sel[j]) + " is outside the group's [0, " + std::to_string(g->n) + ")";
-    for (int i = 0; i < j; i++) if (sel[i] == sel[j]) return w + ": stack " + std::to_string(sel[j]) + " is given twice";
-    const int r = g->row_of[sel[j]], n_in = r >= g->list[1].r0 ? 9 : 5;    // (the n_in = 5 list comes first in the table)
-    if (j > 0 && n_in != Q.n_in) return w + ": stacks " + std::to_string(sel[0]) + " and " + std::to_string(sel[j]) + " differ in n_in: a committee has one";
-    Q.n_in = n_in;
-    Q.sel.row[j] = r;
-    Q.anyt = Q.anyt || g->form_of[r] != MW_FORM_STATE;
-    const size_t bytes = sizeof(float) * (size_t)(g->nimg_of[r] + MW_STACK_PAD);
-    if (bytes > MW_STACK_GROUP_LDS) return w + ": a stack's image exceeds the kernel's LDS";      // (no shape mw_mlp_stack_create accepts does)
-    if (Q.nchunks == 0 || used + bytes > MW_STACK_GROUP_LDS) { Q.nchunks++; used = 0; }      // greedy, in listed order
-    StackChunk &C = Q.chunk[Q.nchunks - 1];
-    C.row[C.n] = r; C.lds_off[C.n] = (int)(used / sizeof(float)); C.n++;
-    used += bytes;
-    Q.lds[Q.nchunks - 1] = used;
-  }
-  Q.chunk[0].first = 1; Q.chunk[Q.nchunks - 1].last = 1;
-  return std::string();
-}
 
 } // namespace mw
 
 using namespace mw;
 
-static bool sc_overlap(const double *a, long long na, const double *b, long long nb) { return a < b + nb && b < a + na; }
+// Chunk c of a planned committee in the fast form, on `st`: what mw_stack_group_committee_apply launches for it.  mw_stack_guard.hip
+// sends the chunks before its own last launch through here, so they are these kernels unchanged.
+int mw::stack_committee_launch(const mw_stack_group_s *g, const StackCommitteePlan &Q, int c, int member, int nz, long long ncol, int nens,
+                               const StackCommitteeFields &F, double *workspace, hipStream_t st) {
+  const long long ncells = (long long)nz * ncol;
+  const long long items = Q.n_in == 5 ? ((ncells + 15) / 16 + SC_TILES - 1) / SC_TILES : (ncol + 15) / 16;      // tile groups / column tiles
+  const long long blocks = std::max<long long>(1, std::min<long long>((items + 3) / 4, SC_MAX_BLOCKS));
+  const double dn = (double)Q.sel.n;
+  const dim3 grid((unsigned)blocks);
+  if (Q.n_in == 5) MW_LAUNCH_IF(Q.anyt, (k_stack_committee<false, true>), (k_stack_committee<false, false>), grid, dim3(256), Q.lds[c], st, g->rows, g->imgs, Q.chunk[c], dn, member, nz, ncol, nens, F, workspace);
+  else             MW_LAUNCH_IF(Q.anyt, (k_stack_committee<true, true>), (k_stack_committee<true, false>), grid, dim3(256), Q.lds[c], st, g->rows, g->imgs, Q.chunk[c], dn, member, nz, ncol, nens, F, workspace);
+  MW_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int mw_stack_group_committee_workspace_bytes(mw_stack_group_t g, int n_sel, const int *sel, int nz, long long ncol, long long *bytes) {
   if (!bytes) MW_FAIL("stack_group_committee_workspace_bytes: null pointer");
@@ -333,14 +266,7 @@ extern "C" int mw_stack_group_committee_apply(mw_stack_group_t g, int n_sel, con
     MW_LAUNCH_CHECK();
     return 0;
   }
-  const long long items = Q.n_in == 5 ? ((ncells + 15) / 16 + SC_TILES - 1) / SC_TILES : (ncol + 15) / 16;      // tile groups / column tiles
-  const long long blocks = std::max<long long>(1, std::min<long long>((items + 3) / 4, SC_MAX_BLOCKS));
-  const double dn = (double)n_sel;
-  for (int c = 0; c < Q.nchunks; c++) {
-    const dim3 grid((unsigned)blocks);
-    if (Q.n_in == 5) MW_LAUNCH_IF(Q.anyt, (k_stack_committee<false, true>), (k_stack_committee<false, false>), grid, dim3(256), Q.lds[c], st, g->rows, g->imgs, Q.chunk[c], dn, member, nz, ncol, nens, F, (double *)workspace);
-    else             MW_LAUNCH_IF(Q.anyt, (k_stack_committee<true, true>), (k_stack_committee<true, false>), grid, dim3(256), Q.lds[c], st, g->rows, g->imgs, Q.chunk[c], dn, member, nz, ncol, nens, F, (double *)workspace);
-    MW_LAUNCH_CHECK();
-  }
+  for (int c = 0; c < Q.nchunks; c++)
+    if (stack_committee_launch(g, Q, c, member, nz, ncol, nens, F, (double *)workspace, st)) return 1;
   return 0;
 }

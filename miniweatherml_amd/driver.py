@@ -57,6 +57,11 @@ field left out never flags by size; a non-finite mean always flags), Kessler tak
 the flagged columns alone (more than max_rainsplit, default 64: the mean stays).  surrogate_rollout.json gets a `guard` block per
 guarded committee: the thresholds, `columns`, `flagged_total`, and `flagged` / `rainsplit` at every scoring step.  inference_ponni runs
 the guarded step when its one committee has a guard; evaluate_surrogates, which scores the mean, refuses an entry with a guard.
+A committee whose members are all `surrogate_stacks:` names is guarded by
+      - {name: guarded_stacks, members: [wide, deep], range_guard: {temp: 0.5, max_rainsplit: 64}}
+(DESIGN.md 13.23): `guard:`'s thresholds and max_rainsplit without `domain` (stacks keep no training box), the same guarded step and the
+same `guard` block in surrogate_rollout.json.  `guard:` on such a committee, `range_guard:` on a committee of surrogate_models or beside
+`guard:`, and `range_guard:` in evaluate_surrogates or inference_ponni are refused by name.
     surface_rain: {thresholds_mm_h: [0.1, 1, 5, 10, 25], thresholds_mm: [0.1, 1, 5, 10, 25], map: true}
 makes rollout_surrogates score rain at the ground: every member's precl becomes what its microphysics step removed from
 its column's water (the Kessler member keeps Kessler's own), and surrogate_rollout.json gets a `surface_rain` block -- the thresholds and,
@@ -170,7 +175,7 @@ def surrogate_config(cfg):
     return _surrogate_models(cfg["surrogate_models"], cfg["_dir"]), interval
 
 
-COMMITTEE_KEYS = ("name", "members", "guard")
+COMMITTEE_KEYS = ("name", "members", "guard", "range_guard")
 
 
 def _model_width(m):
@@ -199,9 +204,11 @@ def committee_config(cfg):
     'persistence'.  An entry may carry `guard:` (surrogate_eval.guard_config: thresholds per field and max_rainsplit), which makes it a
     guarded committee; a guarded and an unguarded committee of the same models may stand side by side under two names.
     An entry whose members are ALL names of `surrogate_stacks:` is a committee of dense stacks (it needs no
-    `surrogate_models:` key, by _rollout_models' rule): one n_in, no guard, and its dict carries "stacks": True.  An entry that mixes
-    models and stacks is refused.  Returns [{"name", "members"}] in the YAML's order, with "guard" (the checked mapping) where the
-    entry has one."""
+    `surrogate_models:` key, by _rollout_models' rule): one n_in, no `guard:`, and its dict carries "stacks": True.  An entry that mixes
+    models and stacks is refused.  A committee of stacks, and only one, may carry `range_guard:`: the four thresholds
+    and max_rainsplit of guard_config without `domain`, which stacks, keeping no training box, cannot honour; it is returned under
+    "guard".  `range_guard:` beside `guard:` or on a committee of fixed models is refused.  Returns [{"name", "members"}] in the YAML's
+    order, with "guard" (the checked mapping) where the entry has one."""
     from . import capi
     from .surrogate_eval import guard_config
     if "surrogate_committees" not in cfg:
@@ -220,6 +227,8 @@ def committee_config(cfg):
         if unknown:
             raise ValueError("ERROR: unknown key(s) %s in a surrogate_committees entry (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(COMMITTEE_KEYS)))
         cname = str(e["name"])
+        if "range_guard" in e and "guard" in e:
+            raise ValueError("ERROR: committee %r has a range_guard beside a guard: an entry takes one" % cname)
         if not isinstance(e["members"], list) or not e["members"]:
             raise ValueError("ERROR: committee %r: members must be a non-empty list of model names" % cname)
         members = [str(n) for n in e["members"]]
@@ -239,9 +248,15 @@ def committee_config(cfg):
                 raise ValueError("ERROR: committee %r mixes stacks of n_in 5 and 9: a committee has one width" % cname)
             if "guard" in e:
                 raise ValueError("ERROR: committee %r is a committee of stacks and has a guard: guards stay with the committees of "
-                                 "surrogate_models" % cname)
+                                 "surrogate_models (a committee of stacks takes range_guard: thresholds and max_rainsplit, no domain)" % cname)
         elif len({_model_width(models[names.index(n)]) for n in members}) != 1:
             raise ValueError("ERROR: committee %r mixes single-cell and stencil models: a committee has one width" % cname)
+        if "range_guard" in e:
+            if not of_stacks:
+                raise ValueError("ERROR: committee %r has a range_guard and is a committee of surrogate_models: range_guard is for "
+                                 "committees of surrogate_stacks (guard: is theirs)" % cname)
+            if isinstance(e["range_guard"], dict) and "domain" in e["range_guard"]:
+                raise ValueError("ERROR: the range_guard of committee %r has a domain: stacks keep no training box" % cname)
         if cname in names or cname in ("kessler", "persistence"):
             raise ValueError("ERROR: committee name %r collides with a surrogate model, 'kessler' or 'persistence'" % cname)
         out.append({"name": cname, "members": members})
@@ -249,6 +264,8 @@ def committee_config(cfg):
             out[-1]["stacks"] = True
         if "guard" in e:
             out[-1]["guard"] = guard_config(e["guard"], "the guard of committee %r" % cname)
+        if "range_guard" in e:
+            out[-1]["guard"] = guard_config(e["range_guard"], "the range_guard of committee %r" % cname)
     if len({c["name"] for c in out}) != len(out):
         raise ValueError("ERROR: the names of surrogate_committees must be unique")
     return out
@@ -256,12 +273,12 @@ def committee_config(cfg):
 
 def evaluation_committees(cfg):
     """committee_config for evaluate_surrogates, which scores a committee's mean and range against the microphysics in charge and has no
-    guarded step to score: an entry with a `guard:` is refused, not scored without it under a name that claims one."""
+    guarded step to score: an entry with a `guard:` or a `range_guard:` is refused, not scored without it under a name that claims one."""
     committees = committee_config(cfg)
     for c in committees:
         if "guard" in c:
             raise ValueError("ERROR: evaluate_surrogates scores a committee's mean and does not apply a guard: committee %r has one "
-                             "(rollout_surrogates and inference_ponni run guarded committees)" % c["name"])
+                             "(guard or range_guard; rollout_surrogates and inference_ponni run guarded committees)" % c["name"])
     return committees
 
 
@@ -795,8 +812,9 @@ class InferencePonni(Column):
             if len(committees) != 1:
                 raise ValueError("ERROR: inference_ponni runs one committee, surrogate_committees lists %d" % len(committees))
             if committees[0].get("stacks"):
-                raise ValueError("ERROR: inference_ponni runs a committee of surrogate_models; committee %r is one of surrogate_stacks "
-                                 "(rollout_surrogates and evaluate_surrogates run those)" % committees[0]["name"])
+                raise ValueError("ERROR: inference_ponni runs a committee of surrogate_models; committee %r is one of surrogate_stacks%s "
+                                 "(rollout_surrogates and evaluate_surrogates run those)"
+                                 % (committees[0]["name"], " with a range_guard" if "guard" in committees[0] else ""))
             cfg["surrogate_models"], _ = surrogate_config(cfg)
             self.committee = committees[0]
         self.fixer_cfg = water_fixer_config(cfg)

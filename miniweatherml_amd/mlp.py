@@ -516,6 +516,24 @@ class MlpStackGroup:
         stats, counts = buf.host()
         return stats.reshape(self.models + 1, 2, 4, 4), counts
 
+    def _committee_layout(self, who, nz, every):
+        """(ncol, nens) of the member-fastest fields `every` of a committee call, or endrun: one shape (nz, ..., nens), contiguous
+        float64, on the group's device."""
+        if self._h is None or not self._h.value:
+            endrun("MlpStackGroup: the handle is closed")
+        if any(t.shape != every[0].shape for t in every) or every[0].dim() < 2:
+            endrun(who + "fields of one shape (nz, ..., nens) expected")
+        if any(t.dtype != torch.float64 or not t.is_contiguous() for t in every):
+            endrun(who + "contiguous float64 fields expected")
+        nens = int(every[0].shape[-1])
+        n = every[0].numel() // nens
+        if int(nz) < 1 or n % int(nz) != 0:
+            endrun(who + "%d cells per member are not a whole number of columns of nz = %d" % (n, nz))
+        dev = every[0].device                                             # (a group made on "cuda" lives on the current device)
+        if any(t.device != dev for t in every) or dev.type != self.device.type or self.device.index not in (None, dev.index):
+            endrun(who + "the group lives on %s, the fields on %s" % (self.device, sorted({str(t.device) for t in every})))
+        return n // int(nz), nens
+
     def committee_apply(self, nz, sel, member, in5, out4, range4=None):
         """mw_stack_group_committee_apply: the mean of the group's stacks sel (1 .. 16 distinct indices of one n_in, summed
         in that order) on ensemble member `member` of the member-fastest fields in5 = (temp, density_dry, water_vapor, cloud_liquid,
@@ -524,25 +542,11 @@ class MlpStackGroup:
         and field: SurrogateBank.committee_apply for stacks.  Only elements of `member` are read and written (self.strict = 1: the
         thread-per-cell form).  A committee whose images do not fit the kernel's LDS together runs in chunks; their workspace is kept from
         call to call and regrown when the shape grows."""
-        if self._h is None or not self._h.value:
-            endrun("MlpStackGroup: the handle is closed")
         who = "MlpStackGroup.committee_apply: "
         sel = [int(s) for s in sel]
         if len(in5) != 5 or len(out4) != 4 or (range4 is not None and len(range4) != 4):
             endrun(who + "five input fields, four output fields and (optionally) four range fields expected")
-        every = list(in5) + list(out4) + (list(range4) if range4 is not None else [])
-        if any(t.shape != in5[0].shape for t in every) or in5[0].dim() < 2:
-            endrun(who + "fields of one shape (nz, ..., nens) expected")
-        if any(t.dtype != torch.float64 or not t.is_contiguous() for t in every):
-            endrun(who + "contiguous float64 fields expected")
-        nens = int(in5[0].shape[-1])
-        n = in5[0].numel() // nens
-        if int(nz) < 1 or n % int(nz) != 0:
-            endrun(who + "%d cells per member are not a whole number of columns of nz = %d" % (n, nz))
-        dev = in5[0].device                                               # (a group made on "cuda" lives on the current device)
-        if any(t.device != dev for t in every) or dev.type != self.device.type or self.device.index not in (None, dev.index):
-            endrun(who + "the group lives on %s, the fields on %s" % (self.device, sorted({str(t.device) for t in every})))
-        ncol = n // int(nz)
+        ncol, nens = self._committee_layout(who, nz, list(in5) + list(out4) + (list(range4) if range4 is not None else []))
         csel, nbytes = (C.c_int * max(1, len(sel)))(*sel), C.c_longlong(0)
         with strict_mode(self.strict), torch.cuda.device(self.device):
             rc = capi.lib().mw_stack_group_committee_workspace_bytes(self._h, len(sel), csel, int(nz), ncol, C.byref(nbytes))
@@ -552,6 +556,45 @@ class MlpStackGroup:
                                                                _field_ptr_array(out4), _field_ptr_array(range4) if range4 is not None else None,
                                                                _ptr(ws) if ws is not None else None, nbytes.value, _stream_ptr(self.device))
         check(rc)
+
+    def committee_guard_flag(self, nz, sel, member, in5, thr4, guard, slot=0, domain_box=None):
+        """mw_stack_group_committee_guard_flag: steps 1 and 2 of a guarded committee's step for ensemble member `member`
+        in the committee's own last launch -- the mean of the stacks sel out of place into guard.mean4 (and guard.range4, when the
+        CommitteeGuard keeps ranges), the member's bytes of guard.flags and row `slot` of guard.counts by mw_committee_guard_flags' rule
+        with the thresholds thr4 (temp, water_vapor, cloud_liquid, precip_liquid; each >= 0, inf: never by size).  The state is only
+        read.  SurrogateBank.committee_guard_flag's signature, so a rollout's loop calls either bank; stacks keep no training box and
+        a domain_box is refused."""
+        who = "MlpStackGroup.committee_guard_flag: "
+        if domain_box is not None:
+            endrun(who + "domain_box is not supported on a committee of stacks, which keep no training box")
+        sel = [int(s) for s in sel]
+        if len(in5) != 5 or len(thr4) != 4:
+            endrun(who + "five input fields and four thresholds expected")
+        ncol, nens = self._committee_layout(who, nz, list(in5))
+        guard.check_layout(who, nz, in5[0], slot)
+        csel, nbytes = (C.c_int * max(1, len(sel)))(*sel), C.c_longlong(0)
+        thr = (C.c_double * 4)(*[float(t) for t in thr4])
+        with strict_mode(self.strict), torch.cuda.device(self.device):
+            rc = capi.lib().mw_stack_group_committee_workspace_bytes(self._h, len(sel), csel, int(nz), ncol, C.byref(nbytes))
+            if rc == 0:
+                ws = grown_workspace(self, "_cws", nbytes.value, self.device) if nbytes.value > 0 else None
+                rc = capi.lib().mw_stack_group_committee_guard_flag(
+                    self._h, len(sel), csel, int(member), int(nz), ncol, nens, _field_ptr_array(in5), _field_ptr_array(guard.mean4),
+                    _field_ptr_array(guard.range4) if guard.range4 is not None else None, thr, C.c_void_p(guard.flags.data_ptr()),
+                    C.c_void_p(guard.counts[slot].data_ptr()), _ptr(ws) if ws is not None else None, nbytes.value, _stream_ptr(self.device))
+        check(rc)
+        guard.flagged_members.add(int(member))
+
+    def committee_guard_apply(self, nz, sel, member, in5, thr4, max_rainsplit, dz, dt, scratch, domain_box=None):
+        """One step of a guarded committee of stacks on ensemble member `member`, in place (SurrogateBank.committee_guard_apply's
+        contract and signature): committee_guard_flag into the scratch (a CommitteeGuard, with or without ranges), then
+        CommitteeGuard.commit -- mw_kessler_columns_teacher on the flagged columns with out4 = mean4, mw_members_copy of mean4 into the
+        four fields.  A scratch used for another member before has that member's flag bytes cleared first."""
+        if scratch.flagged_members - {int(member)}:
+            scratch.flags.zero_()
+            scratch.flagged_members.clear()
+        self.committee_guard_flag(nz, sel, member, in5, thr4, scratch, domain_box=domain_box)
+        scratch.commit(nz, [member], in5, max_rainsplit, dz, dt)
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

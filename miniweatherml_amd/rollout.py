@@ -133,7 +133,10 @@ class Microphysics_Rollout(Microphysics_Kessler):
         domain stay with the fixed models and their committees.  A committee whose names are ALL stacks of `stacks`, with one n_in, is a
         committee of stacks: it takes its place among the committees -- member 1 + len(models) + ci -- and is replaced
         in place from its own state by MlpStackGroup.committee_apply on this rollout's stack group, where the fixed committees are
-        applied; a committee mixing models and stacks or n_in 5 and 9, a guard on one, and one under training_domain are refused.
+        applied; a committee mixing models and stacks or n_in 5 and 9 and one under training_domain are refused.  With a guard of
+        thresholds and max_rainsplit it is a GUARDED committee of stacks: MlpStackGroup.committee_guard_flag writes its
+        mean and flags in one launch, and it shares the scratch, the columns-teacher call, the commit and the report with the fixed
+        guarded committees; a guard with `domain` on it is refused (stacks keep no training box).
         The coupler must have 1 + len(models) + len(committees) + len(stacks) (+ 1 with persistence) members."""
         models = [as_surrogate_model(m) for m in models]
         self.model_forms = [m.form for m in models]
@@ -166,9 +169,9 @@ class Microphysics_Rollout(Microphysics_Kessler):
             if named:
                 if len({stack_widths(stacks[stack_names.index(n)][1])[0] for n in cmodels}) != 1:
                     endrun("Microphysics_Rollout: committee %r mixes stacks of n_in 5 and 9: a committee has one width" % cname)
-                if guards[ci] is not None:
-                    endrun("Microphysics_Rollout: committee %r is a committee of stacks and has a guard: guards stay with the fixed models' "
-                           "committees" % cname)
+                if guards[ci] is not None and "domain" in guards[ci]:
+                    endrun("Microphysics_Rollout: committee %r is a committee of stacks and its guard has a domain: stacks keep no training "
+                           "box (a range guard of thresholds and max_rainsplit is what they take)" % cname)
             elif len({int(np.shape(models[names.index(n)][0])[0]) for n in cmodels}) != 1:
                 endrun("Microphysics_Rollout: committee %r mixes single-cell and stencil models: a committee has one width" % cname)
         super().init(coupler)
@@ -259,7 +262,8 @@ class Microphysics_Rollout(Microphysics_Kessler):
         guarded = [ci for ci, g in enumerate(guards) if g is not None]
         in5 = [temp, rho_d, rho_v, rho_c, rho_r]
         if guarded and self._guard is None:
-            self._guard = CommitteeGuard(temp, nz, len(guarded))
+            # (the range fields only where a committee of fixed models reads them: a committee of stacks decides its flags in registers)
+            self._guard = CommitteeGuard(temp, nz, len(guarded), ranges=any(self.committees[ci][0] is not getattr(self, "stack_group", None) for ci in guarded))
         for ci, (bank, sel, member) in enumerate(getattr(self, "committees", ())):
             bank.strict = self.mlp_strict
             if guards[ci] is None:

@@ -184,6 +184,9 @@ class SurrogateBank:
             endrun("SurrogateBank.committee_guard_flag: five input fields and four thresholds expected")
         ncol, nens = self._member_layout("SurrogateBank.committee_guard_flag: ", nz, list(in5))
         guard.check_layout("SurrogateBank.committee_guard_flag: ", nz, in5[0], slot)
+        if guard.range4 is None:
+            endrun("SurrogateBank.committee_guard_flag: the CommitteeGuard was made with ranges=False, and mw_committee_guard_flags reads the "
+                   "committee's ranges (only MlpStackGroup.committee_guard_flag decides the flags without them)")
         self.committee_apply(nz, sel, member, in5, guard.mean4, guard.range4)
         thr = (C.c_double * 4)(*[float(t) for t in thr4])
         with torch.cuda.device(self.device):
@@ -361,9 +364,11 @@ class CommitteeGuard:
     """What the guarded committees of one state share (no reference counterpart): mean4 and range4, eight member-fastest scratch fields of
     the state's shape (nz, ..., nens) -- 64 bytes per element of all members, allocated here once; flags, one byte per column and member
     (zero for members that are not guarded: mw_committee_guard_flags writes its own member's bytes only); the columns teacher's workspace;
-    counts, int64 (slots, 2): per guarded member this step's flagged columns and their running total."""
+    counts, int64 (slots, 2): per guarded member this step's flagged columns and their running total.  ranges=False: range4 is None and
+    its four fields are not allocated (32 bytes per element of all members saved) -- for committees of dense stacks, whose kernel decides
+    the flags on its registers (MlpStackGroup.committee_guard_flag); SurrogateBank.committee_guard_flag refuses it."""
 
-    def __init__(self, like, nz, slots=1):
+    def __init__(self, like, nz, slots=1, ranges=True):
         if like.dim() < 2 or like.dtype != torch.float64 or not like.is_contiguous() or int(nz) < 2 or like.numel() % (int(nz) * like.shape[-1]) != 0:
             endrun("CommitteeGuard: a contiguous float64 field (nz, ..., nens) with nz >= 2 expected")
         self.nz, self.nens, self.shape, self.device = int(nz), int(like.shape[-1]), tuple(like.shape), like.device
@@ -372,7 +377,7 @@ class CommitteeGuard:
         if nbytes <= 0:
             endrun("CommitteeGuard: nz = %d, %d columns and %d members are out of range (nz >= 2, at most 64 members)" % (self.nz, self.ncol, self.nens))
         self.mean4 = [torch.empty_like(like) for _ in range(4)]
-        self.range4 = [torch.empty_like(like) for _ in range(4)]
+        self.range4 = [torch.empty_like(like) for _ in range(4)] if ranges else None
         self.flags = torch.zeros(self.ncol * self.nens, dtype=torch.uint8, device=like.device)
         self.counts = torch.zeros((int(slots), 2), dtype=torch.int64, device=like.device)
         self.workspace = fit_workspace(None, nbytes, like.device)
