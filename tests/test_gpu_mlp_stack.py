@@ -14,6 +14,8 @@ of fp64 from it.  A clipped cell shows no output: there the fp64 reference must 
 Measured on an MI355X, the worst left / right over a shape's calls, state | tendency:
     5->[1] .114 .141   5->[3] .190 .190   5->[4] .139 .139   5->[5] .178 .201   5->[15] .180 .180   5->[16] .208 .208   5->[17] .175 .177
     5->[33] .243 .304   5->[64] .424 .424   5->[17, 3, 64] .301 .573   5->[64] * 4 .302 .366   9->[10] .203 .203   9->[17, 5] .243 .252
+Every width class, every pair of layer shapes and a second grid pass are held to the same yardstick in test_gpu_stack_shapes.py, whose
+header has its ratios per depth.
 """
 import ctypes as C
 
